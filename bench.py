@@ -8,7 +8,10 @@ Vocoder.generate (B x 32 000 samples).  The per-GPU batch is BASELINE.json confi
 (256 utterances / 8 GPUs = 32, 2 s each), the same at every N (weak scaling); for N > 1 the
 waveforms are gathered on rank 0 over RCCL inside the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step returned (waveforms, and the code indices they were decoded from) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no torch.distributed.run environment, this process starts the N ranks
 itself (fresh children of `python -m torch.distributed.run`, before it makes any GPU call),
@@ -64,6 +67,7 @@ KERNEL_SOURCES = ("vectorquantizedcpc_amd/csrc/vocoder.hip", "vectorquantizedcpc
                   "vectorquantizedcpc_amd/csrc/ar_xcm.hip", "vectorquantizedcpc_amd/csrc/ar_shared.h",
                   "vectorquantizedcpc_amd/csrc/ar_chain.h", "vectorquantizedcpc_amd/csrc/ar_xcd.h",
                   "vectorquantizedcpc_amd/csrc/common.h")
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much on disk in all
 
 
 def log(msg):
@@ -151,9 +155,12 @@ def selftest_rank(args):
                     nn = m.shape[-1] // 2 * 2 * 160
                     out[k, :nn] = float(i) + 0.001 * s
                 return out
-            r = manifest_sharded(args, rank, world, torch.device("cpu"), mels, spk, fake_decode, None, True)
+            outputs = {}
+            r = manifest_sharded(args, rank, world, torch.device("cpu"), mels, spk, fake_decode, None, True, outputs)
             if rank == 0:
                 r["selftest"] = True
+                if args.dump_outputs:
+                    r["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
                 print(json.dumps(r), flush=True)
             return
         wav = torch.full((2, 8), float(rank))
@@ -170,9 +177,48 @@ def selftest_rank(args):
 
 
 # ------------------------------------------------------------------------------------------
-def manifest_sharded(args, rank, world, dev, mels, speakers, decode_fn, check_fn, launched):
+def dump_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per entry of
+    `outputs` (name -> per-utterance 1-D tensors, the same utterances in every entry).  Floating values are written as
+    float32 (float64 stays float64), integers (code indices) as float64, which holds them exactly.  Rows of unequal length
+    are zero-padded to the longest kept row, and lengths.npy gives each row's own length.  When the files would pass
+    `limit` bytes in all, a fixed sample of the utterances is kept: taken in the order of a permutation seeded with synth.SEED
+    while it fits, so every run with the same arguments keeps the same rows.  utterances.npy lists the kept rows."""
+    import numpy as np
+    rows = {k: [np.asarray(t.detach().cpu()).reshape(-1) for t in v] for k, v in outputs.items()}
+    n = len(next(iter(rows.values())))
+    assert all(len(v) == n for v in rows.values()), "every dumped output needs one row per utterance"
+    dtype = {k: np.float64 if v and (v[0].dtype.kind in "iub" or v[0].dtype == np.float64) else np.float32 for k, v in rows.items()}
+    budget = limit - 2 * 8 * n - 128 * (len(rows) + 2)          # utterances.npy, lengths.npy and the .npy headers
+    keep, width = [], {k: 0 for k in rows}
+    for u in np.random.default_rng(synth.SEED).permutation(n):
+        w = {k: max(width[k], rows[k][u].size) for k in rows}
+        if sum((len(keep) + 1) * w[k] * np.dtype(dtype[k]).itemsize for k in rows) > budget:
+            break
+        keep.append(int(u))
+        width = w
+    keep.sort()
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for k, v in rows.items():
+        a = np.zeros((len(keep), width[k]), dtype=dtype[k])
+        for j, u in enumerate(keep):
+            a[j, : v[u].size] = v[u]
+        files[k] = a
+    files["utterances"] = np.asarray(keep, dtype=np.float64)
+    first = next(iter(rows))
+    files["lengths"] = np.asarray([rows[first][u].size for u in keep], dtype=np.float64)
+    for k, a in files.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k}{tuple(a.shape)}" for k, a in files.items()))
+    return {"dir": out_dir, "files": {k + ".npy": list(a.shape) for k, a in files.items()}, "utterances_kept": len(keep),
+            "utterances": n, "bytes": int(sum(a.nbytes for a in files.values()))}
+
+
+def manifest_sharded(args, rank, world, dev, mels, speakers, decode_fn, check_fn, launched, outputs=None):
     """BASELINE configs[4]: the ragged manifest over `world` ranks -- shard.convert_sharded (LPT by sample count, local decode,
-    check, ragged gather on rank 0), timed as a whole between barriers; max over ranks.  Returns rank 0's result object."""
+    check, ragged gather on rank 0), timed as a whole between barriers; max over ranks.  Returns rank 0's result object;
+    `outputs` (a dict), if given, receives rank 0's waveforms of the last timed step under "waveforms"."""
     ddp = launched and dist.is_initialized()
     n = len(mels)
     total_samples = sum(int(m.shape[-1]) // 2 * 2 * 160 for m in mels)
@@ -193,6 +239,8 @@ def manifest_sharded(args, rank, world, dev, mels, speakers, decode_fn, check_fn
         if ddp:
             dist.barrier()
         times.append(time.perf_counter() - t0)
+    if outputs is not None and rank == 0:
+        outputs["waveforms"] = res
     dt = sum(times)
     per_rank = torch.tensor([dt, st["decode_s"], st["gather_s"], float(st["utterances"]), float(st["samples"])], dtype=torch.float64, device=dev)
     allr = [torch.zeros_like(per_rank) for _ in range(world)] if ddp else [per_rank]
@@ -578,8 +626,15 @@ def main():
     ap.add_argument("--force-gather", action="store_true", help="manifest workload: run the gather's collectives at world size 1 too")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of the utterances beyond that)")
     ap.add_argument("--selftest-spawn", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)      # the ranks' working directory need not be ours
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ       # under torch.distributed.run
     if not launched and args.gpus > 1:
@@ -636,11 +691,14 @@ def main():
             for k, w in enumerate(wavs):
                 out[k, : w.numel()] = w
             return out
-        result = manifest_sharded(args, rank, world, dev, mels_all, spk_all, decode_fn, voc.check, launched)
+        outputs = {}
+        result = manifest_sharded(args, rank, world, dev, mels_all, spk_all, decode_fn, voc.check, launched, outputs)
         if rank == 0:
             result["decode_slots_rank0"] = voc.last_slots()
             result["decode_path_rank0"] = voc.last_path()
             result["workspace_peak_bytes_rank0"] = voc.workspace_bytes()
+            if args.dump_outputs:
+                result["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(result), flush=True)
         if launched:
             dist.destroy_process_group()
@@ -660,12 +718,24 @@ def main():
             out = [torch.empty_like(wav) for _ in range(world)] if rank == 0 else None
             dist.gather(wav, out, dst=0)                      # the one exchange step (RCCL over xGMI)
             state["gathered"] = out
-        state["wav"] = wav
+        state["wav"], state["idx"] = wav, idx
 
     log(f"models built; timing {args.steps} step(s) of {Bp} utterances x {L} samples on {world} GPU(s)")
     dt = timed(step, args.steps, args.warmup, dev, world)
     voc.check()                                               # an in-kernel hand-off that gave up anywhere in the timed steps is an error
     log(f"timed region done: {dt:.3f} s")
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's waveforms (gathered on rank 0 when N > 1) and the code indices they were decoded from; the
+        # indices are gathered here, outside the timed region
+        wav, idx = state["wav"], state["idx"]
+        if launched:
+            gi = [torch.empty_like(idx) for _ in range(world)] if rank == 0 else None
+            dist.gather(idx, gi, dst=0)
+            if rank == 0:
+                wav, idx = torch.cat(state["gathered"]), torch.cat(gi)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"waveforms": list(wav), "indices": list(idx)})
     samples = n_total * L * args.steps
     value = samples / dt
     loop_ms, n_loop = voc.last_timing()                       # HIP events around the last decode loop
@@ -686,6 +756,8 @@ def main():
         "realtime_factor_16k_per_gpu": value / 16000.0 / world,
         "roofline": roof,
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if launched:
         # the exchange step alone: every rank's (Bp, L) fp32 waveforms to rank 0, max over ranks of 5 repetitions
         wav = state["wav"]

@@ -66,3 +66,27 @@ def test_bench_contract_line_on_a_tiny_workload():
     assert d["n_gpus"] == 1 and d["unit"] == "samples/s" and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(d["roofline"])
     assert d["value"] > 0 and "workload" in d["config"]
+
+
+def test_bench_dump_outputs_are_the_same_at_any_step_count(tmp_path):
+    """--dump-outputs: the last timed step's waveforms and code indices; every step decodes the same seeded inputs, so one timed
+    step and three give the same files.  --steps sets the number of timed steps the line reports."""
+    import numpy as np
+    got = []
+    for steps in (1, 3):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--utterances-per-gpu", "2", "--frames", "8",
+                              "--steps", str(steps), "--warmup", "0", "--no-cpu-baseline", "--no-extras", "--manifest", "0",
+                              "--dump-outputs", str(tmp_path / str(steps))],
+                             capture_output=True, text=True, timeout=280, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-800:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        got.append({f: np.load(tmp_path / str(steps) / f) for f in ("waveforms.npy", "indices.npy", "lengths.npy", "utterances.npy")})
+    a, b = got
+    assert a["waveforms.npy"].shape == (2, 1280) and a["waveforms.npy"].dtype == np.float32
+    assert a["indices.npy"].shape == (2, 4) and a["indices.npy"].dtype == np.float64
+    idx = a["indices.npy"]
+    assert np.array_equal(idx, np.round(idx)) and idx.min() >= 0 and idx.max() < 512
+    assert np.isfinite(a["waveforms.npy"]).all() and np.abs(a["waveforms.npy"]).max() <= 1.0
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
