@@ -1,5 +1,5 @@
-// Device helpers shared by the decode kernels of vocoder.hip (launch-per-step and 64-workgroup persistent decoders)
-// and ar_xcd.hip (one resident decoder per XCD).  Everything that decides a BIT of the result lives here once, so that
+// Device helpers shared by the decode kernels of vocoder.hip (launch per step), ar_xcd.hip / ar_xcm.hip (one resident
+// decoder per XCD) and the scans of scan.hip.  Everything that decides a BIT of the result lives here once, so that
 // an utterance decoded on any of the paths gives the same samples: the Philox stream of the sampling protocol, the
 // gate non-linearities, and the order in which a row's fp32 fma chains are loaded and combined.
 #pragma once
@@ -7,6 +7,53 @@
 #include <math.h>
 
 typedef unsigned long long u64;
+
+// Bits of the decoder handle's host-mapped status word (its low byte; the reporting call's epoch sits above it, vqcpc_vocoder_check).
+constexpr unsigned STATUS_TIMEOUT = 1u;      // an in-kernel exchange timed out
+constexpr unsigned STATUS_MISPLACED = 2u;    // the resident decoders' workgroups were not dealt 32 per XCD (nothing written)
+constexpr unsigned STATUS_BAD_INDEX = 4u;    // a code index or speaker id outside its embedding table
+
+// ---- launch-per-step recurrences (vocoder.hip's sample loop, scan.hip's sequence scans): weights in fragment order
+// (scan.hip, build_wfrag_kernel), one 16-row x 16-utterance MFMA tile per workgroup, K split over 4 waves.
+// state layout "hL": h[b][k] at ((b/16) * (K/4) + k/4) * 64 + (b%16) * 4 + k%4
+__device__ __forceinline__ size_t hl_index(int K, int b, int k) {
+    return ((size_t)(b >> 4) * (K >> 2) + (k >> 2)) * 64 + (b & 15) * 4 + (k & 3);
+}
+
+template <int SW>
+__device__ __forceinline__ void load_wfrag(const float *Wf, int rg, int ksplit, int wave, int lane, float4 (&wf)[SW]) {
+    const float4 *p = (const float4 *)Wf + ((size_t)(rg * ksplit + wave) * SW) * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < SW; ++s) wf[s] = p[s * 64];
+}
+
+// 16 rows x 16 utterances partial product over this wave's K quarter.
+template <int SW>
+__device__ __forceinline__ f32x4 mv16(const float4 (&wf)[SW], const float *hL, int K, int bt, int wave, int lane) {
+    const float4 *hp = (const float4 *)hL + ((size_t)bt * (K >> 2)) * 16 + (size_t)wave * SW * 64 + lane;
+    float4 hv[SW];
+#pragma unroll
+    for (int s = 0; s < SW; ++s) hv[s] = hp[s * 64];
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < SW; ++s) {
+        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, hv[s].x, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, hv[s].y, a1, 0, 0, 0);
+        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].z, hv[s].z, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].w, hv[s].w, a1, 0, 0, 0);
+    }
+    return a0 + a1;
+}
+
+// cross-wave reduction of the 4 K-quarters: red[wave][row][b] -> returns sum for (row=tid>>4, b=tid&15)
+__device__ __forceinline__ float reduce4(float (*red)[16][17], const f32x4 &acc, int wave, int lane, int tid) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][(lane >> 4) * 4 + r][lane & 15] = acc[r];
+    __syncthreads();
+    const int row = tid >> 4, b = tid & 15;
+    return ((red[0][row][b] + red[1][row][b]) + red[2][row][b]) + red[3][row][b];
+}
+
 
 __device__ __forceinline__ u64 ps_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void ps_store(u64 *p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -76,7 +123,7 @@ struct Waiter {                      // bounded spinning shared by all sweeps of
     // The wall clock (s_memrealtime: a scalar memory read, ~0.3 us) is only consulted once a wait has spun 64 times: a wait
     // that succeeds quickly never pays for it.  t0 = 0: not taken yet.
     __device__ __forceinline__ void start() { t0 = 0; }
-    // true: give up (deadline passed -- status bit 0 is then set -- or somebody else already gave up).  `tagp`: an LDS word with the
+    // true: give up (deadline passed -- STATUS_TIMEOUT is then set -- or somebody else already gave up).  `tagp`: an LDS word with the
     // call's epoch << 8, so that the status word says WHICH call of the handle gave up; it is read only when the deadline has
     // passed (kept in a register for the whole call, the tag cost ar_xcd_kernel<2> a VGPR spill inside its sample loop)
     __device__ __forceinline__ bool expired(unsigned spins, int lane, const int *tagp) {
@@ -84,7 +131,7 @@ struct Waiter {                      // bounded spinning shared by all sweeps of
         const u64 now = __builtin_amdgcn_s_memrealtime();
         if (t0 == 0) t0 = now;
         const bool late = now - t0 > (u64)ticks;
-        if (late && lane == 0) __hip_atomic_store(status, (unsigned)*tagp | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // host-mapped: a plain store, no PCIe atomic
+        if (late && lane == 0) __hip_atomic_store(status, (unsigned)*tagp | STATUS_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // host-mapped: a plain store, no PCIe atomic
         return late || (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u);
     }
 };

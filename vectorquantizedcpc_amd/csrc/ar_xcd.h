@@ -19,7 +19,7 @@ struct XdParams {
     const float *mulaw_tab;   // [n_cls]
     const XdSeg *segs;        // [8 * bxt slots][max_seg]; slot s lives on XCD s % 8 as its local slot s / 8; then int gbase[rows]
     unsigned long long *xg;   // exchange area (xd_exchange_bytes), zeroed by xd_launch
-    unsigned *status;         // host-mapped word: status_tag | 1 = an exchange timed out, | 2 = the workgroups were not dealt 32 per XCD
+    unsigned *status;         // host-mapped word: status_tag | a STATUS_* bit (ar_shared.h)
     unsigned status_tag;      // the call's epoch << 8 (which call of the handle reported)
     float *wav;               // (rows, Lout) or null
     int64_t *mulaw;           // (rows, Lout) or null
@@ -30,7 +30,7 @@ struct XdParams {
     int agent_stores;         // 1: publish with agent-scope (sc1) stores instead of workgroup-scope ones (tests / A-B)
     unsigned timeout_ticks;   // bound of every in-kernel wait, 100 MHz ticks
     int dbg_drop_step;        // >= 0: rank 3 of XCD 0 skips its candidate publish at that step (exercises the abort path)
-    int dbg_misplace;         // != 0: workgroup 0 reports the XCD next to its own (exercises the placement check: status 2, nothing written)
+    int dbg_misplace;         // != 0: workgroup 0 reports the XCD next to its own (exercises the placement check: STATUS_MISPLACED, nothing written)
 };
 
 size_t xd_exchange_bytes(int bxt);

@@ -11,7 +11,7 @@
 //     inside the XCD: published with workgroup-scope stores (the write-through L1 leaves them in the XCD's L2) and swept
 //     with sc1 loads that bypass L1 -- 0.41 us per exchange against 1.2 us across XCDs
 //     (profiles/r02_xcd_exchange_microbench.csv).  The placement is CHECKED, not assumed: every workgroup reads its
-//     XCC_ID and takes a ticket; unless each XCD got exactly 32 workgroups the launch gives up (status 2) before it
+//     XCC_ID and takes a ticket; unless each XCD got exactly 32 workgroups the launch gives up (STATUS_MISPLACED) before it
 //     touches any output, and the host falls back to the launch-per-step kernels.
 // Arithmetic is bit-identical to those kernels: a row's dot product is the same 8 fp32 fma chains (K quarter x x/z|y/w
 // accumulator: ar_shared.h), combined in the same order; cell update, fc epilogues and the Gumbel-max draw are the
@@ -41,7 +41,7 @@
 // fc2 + draw of slots 0..3 on waves 2, 3, 6, 7; waves 4 and 8 -- fc1's SIMD mates -- start their chains when a_t is out (two
 // dependent-chain waves keep a SIMD's issue port ~80 % busy, whatever s_setprio says); wave 11 draws the next step's noise
 // behind its chain from the slots' clocks the service waves post in LDS.
-// Two workgroup barriers per sample.  Every wait is wall-clock bounded; a timeout sets status bit 0, every workgroup
+// Two workgroup barriers per sample.  Every wait is wall-clock bounded; a timeout sets STATUS_TIMEOUT, every workgroup
 // leaves, and the call's outputs are incomplete (vqcpc_vocoder_check reports it).
 #include "ar_xcd.h"
 #include "ar_shared.h"
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
         if (ok)
             for (int x = 0; x < 8; ++x)
                 if (__hip_atomic_load(ctl + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)NW) ok = 0;
-        if (!ok) __hip_atomic_store(p.status, p.status_tag | 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!ok) __hip_atomic_store(p.status, p.status_tag | STATUS_MISPLACED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         s_ctl[0] = (int)xid; s_ctl[1] = (int)r; s_ctl[2] = ok; s_ctl[3] = 0; s_ctl[4] = (int)p.status_tag; s_ctl[5] = 0;
     }
     __syncthreads();

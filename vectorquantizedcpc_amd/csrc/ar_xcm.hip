@@ -33,7 +33,7 @@
 // late quarters: 11.3 us (tile 5 is complete later, and the extra barrier sits in the middle of the MFMA phase); wave 0's
 // quarter of tile 4 behind x_t instead of behind the fc1 publish: 11.2 us.
 // Exchanges are the 8-byte {tag, value} granules of ar_xcd.hip, two per 16-byte load, laid out so that every sweep reads
-// a linear array.  Every wait is wall-clock bounded (status bit 0, vqcpc_vocoder_check); placement is checked as there.
+// a linear array.  Every wait is wall-clock bounded (STATUS_TIMEOUT, vqcpc_vocoder_check); placement is checked as there.
 #include "ar_xcd.h"
 #include "ar_shared.h"
 
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
         if (ok)
             for (int x = 0; x < 8; ++x)
                 if (__hip_atomic_load(ctl + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)NW) ok = 0;
-        if (!ok) __hip_atomic_store(p.status, p.status_tag | 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!ok) __hip_atomic_store(p.status, p.status_tag | STATUS_MISPLACED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         par_set(par, PAR_WAV, (unsigned long long)p.wav); par_set(par, PAR_MULAW, (unsigned long long)p.mulaw); par_set(par, PAR_SEGS, (unsigned long long)p.segs);
         par_set(par, PAR_GCOND, (unsigned long long)p.Gcond); par_set(par, PAR_SEED, p.seed); par_set(par, PAR_GEMB, (unsigned long long)p.Gemb);
         par[PAR_LOUT] = p.Lout; par[PAR_MAXSEG] = p.max_seg; par[PAR_F] = p.F; par[PAR_UPS] = p.upsample; par[PAR_DROP] = p.dbg_drop_step;

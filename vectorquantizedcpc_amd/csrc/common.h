@@ -60,7 +60,14 @@ int vq_gemm_chain(const float *A, int lda, const float *W, const float *bias, fl
 int vq_gemm_chain_ex(const float *A, int lda, const float *W, const float *bias, float *Y, int ldy,
                      int M, int N, int K, int KC, int relu, int ydiv, int ystride, int yoff, int ylim, hipStream_t s);
 
-// ---- recurrent machinery (vocoder.hip), shared with the encoder's LSTM.
+// ---- recurrent scans (scan.hip): the encoder's context LSTM and the vocoder prenet's bidirectional GRU layers.
+// W (n_rg row groups x K) in fragment order for the launch-per-step MFMA kernels; rowmode and layout: scan.hip.  *out is hipMalloc'ed.
+int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, float **out);
+// One bidirectional GRU layer's T steps from zero state.  Gi: hoisted input projection [rows][2][3H] (+ b_ih); Wf: both directions'
+// W_hh, each from vq_build_wfrag(rowmode 3); b_hh [2][3H]; hbuf: 4 * ceil(B / 16) * 16 * H floats of state; out [rows][2H].
+// len / row0: valid steps and first row of every utterance (ragged rows), or null = T steps from row b * T.
+int vq_bigru_scan(const float *Wf, const float *b_hh, const float *Gi, float *hbuf, float *out, const int *len, const int *row0,
+                  int H, int B, int T, hipStream_t s);
 struct LstmPlan;   // opaque, owns fragment-ordered weights
 int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
                         int D, int H, LstmPlan **out);

@@ -1,7 +1,6 @@
 // vocoder.hip -- Vocoder.generate / Vocoder.forward on gfx950 (reference call sites
 // network_vocoder.py:41-78; the RNN_MS arithmetic is the project's spec of the absent
-// third-party `rnnms` package -- see oracle/vqcpc_oracle.c and DESIGN.md), plus the
-// recurrent-step machinery the encoder's LSTM (model.py:57, :69) shares.
+// third-party `rnnms` package -- see oracle/vqcpc_oracle.c and DESIGN.md).  The prenet's bi-GRU scans run in scan.hip.
 //
 // Design (DESIGN.md "Decode loop"): every recurrence is WEIGHT-STATIONARY across the chip
 // and BATCHED over utterances.  One step = a skinny fp32 GEMM [rows x K] x [K x B]; each
@@ -18,6 +17,7 @@
 #include "ar_xcd.h"
 #include <math.h>
 #include <stdio.h>
+#include <limits.h>
 #include <string.h>
 #include <algorithm>
 #include <map>
@@ -25,50 +25,6 @@
 
 int vq_require_gfx950();
 #define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
-// state layout "hL": h[b][k] at ((b/16) * (K/4) + k/4) * 64 + (b%16) * 4 + k%4
-__device__ __forceinline__ size_t hl_index(int K, int b, int k) {
-    return ((size_t)(b >> 4) * (K >> 2) + (k >> 2)) * 64 + (b & 15) * 4 + (k & 3);
-}
-
-// ------------------------------------------------------------------------------------------
-// Fragment-ordered weights.  For row group `rg` (16 rows, row_of(rg, i) or -1 = zero row),
-// K split over `ksplit` waves, super-step S = 16 consecutive k:
-//   Wf[((rg*ksplit + w)*SW + s)*64 + lane] (float4) = W[row_of(rg, lane&15)][16*S + 4*(lane>>4) + 0..3]
-// with S = w*SW + s.  rowmode: 0 plain (row = 16 rg + i), 8 half groups (row = 8 rg + i, i < 8), 16 GRU gate tiles (rg = 3 blk + gate: that gate of units 16 blk + i), 3 GRU gates, 4 LSTM gates
-// (row = gate*H + 4 rg + i%4, gate = i/4; rows >= G*4 are zero).
-// ------------------------------------------------------------------------------------------
-__global__ void build_wfrag_kernel(const float *__restrict__ W, int ldw, float *__restrict__ Wf, int n_rg,
-                                   int K, int ksplit, int rowmode, int H) {
-    const int SW = K / 16 / ksplit;
-    const size_t total = (size_t)n_rg * ksplit * SW * 64;
-    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= total) return;
-    const int lane = (int)(id & 63);
-    size_t r = id >> 6;
-    const int s = (int)(r % SW); r /= SW;
-    const int w = (int)(r % ksplit);
-    const int rg = (int)(r / ksplit);
-    const int i = lane & 15, kq = lane >> 4, S = w * SW + s;
-    int row;
-    if (rowmode == 0) row = 16 * rg + i;
-    else if (rowmode == 8) row = i < 8 ? 8 * rg + i : -1;
-    else if (rowmode == 16) row = (rg % 3) * H + 16 * (rg / 3) + i;
-    else row = (i >> 2) < rowmode ? (i >> 2) * H + 4 * rg + (i & 3) : -1;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row >= 0) v = *(const float4 *)(W + (size_t)row * ldw + 16 * S + 4 * kq);
-    ((float4 *)Wf)[id] = v;
-}
-
-static int build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, float **out) {
-    VQ_REQUIRE(K % (16 * ksplit) == 0 && ldw % 4 == 0, "build_wfrag: K=%d not a multiple of %d", K, 16 * ksplit);
-    const size_t n4 = (size_t)n_rg * (K / 16) * 64;
-    HIP_TRY(hipMalloc((void **)out, n4 * sizeof(float4)));
-    hipLaunchKernelGGL(build_wfrag_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, ldw, *out, n_rg, K,
-                       ksplit, rowmode, H);
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
 
 // Packed GRU fragments: the 12 gate rows of a 4-unit row group WITHOUT the 4 padding rows of the 16-row MFMA
 // tile.  Per (rg, K quarter w, super-step s): 48 float4 = [kq 0..3][i 0..11], 768 B = six whole 128-B lines;
@@ -95,213 +51,6 @@ static int build_wfrag12(const float *W, int ldw, int n_rg, int K, int H, float 
     const size_t n4 = (size_t)n_rg * (K / 16) * 48;
     HIP_TRY(hipMalloc((void **)out, n4 * sizeof(float4)));
     hipLaunchKernelGGL(build_wfrag12_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, ldw, *out, n_rg, K, H);
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
-
-template <int SW>
-__device__ __forceinline__ void load_wfrag(const float *Wf, int rg, int ksplit, int wave, int lane, float4 (&wf)[SW]) {
-    const float4 *p = (const float4 *)Wf + ((size_t)(rg * ksplit + wave) * SW) * 64 + lane;
-#pragma unroll
-    for (int s = 0; s < SW; ++s) wf[s] = p[s * 64];
-}
-
-// 16 rows x 16 utterances partial product over this wave's K quarter.
-template <int SW>
-__device__ __forceinline__ f32x4 mv16(const float4 (&wf)[SW], const float *hL, int K, int bt, int wave, int lane) {
-    const float4 *hp = (const float4 *)hL + ((size_t)bt * (K >> 2)) * 16 + (size_t)wave * SW * 64 + lane;
-    float4 hv[SW];
-#pragma unroll
-    for (int s = 0; s < SW; ++s) hv[s] = hp[s * 64];
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < SW; ++s) {
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, hv[s].x, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, hv[s].y, a1, 0, 0, 0);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].z, hv[s].z, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].w, hv[s].w, a1, 0, 0, 0);
-    }
-    return a0 + a1;
-}
-
-// cross-wave reduction of the 4 K-quarters: red[wave][row][b] -> returns sum for (row=tid>>4, b=tid&15)
-__device__ __forceinline__ float reduce4(float (*red)[16][17], const f32x4 &acc, int wave, int lane, int tid) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave][(lane >> 4) * 4 + r][lane & 15] = acc[r];
-    __syncthreads();
-    const int row = tid >> 4, b = tid & 15;
-    return ((red[0][row][b] + red[1][row][b]) + red[2][row][b]) + red[3][row][b];
-}
-
-
-// ------------------------------------------------------------------------------------------
-// Sequence recurrences with a hoisted input projection (prenet bi-GRU, encoder LSTM).
-// ------------------------------------------------------------------------------------------
-struct SeqP {
-    const float *Wf;      // [dir][H/4 row groups][4 waves][SW][64] float4
-    const float *b_hh;    // GRU: [dir][3H]; LSTM: unused (folded into Gi)
-    const float *Gi;      // [B*T][ndir*G*H]  input projection (+ biases)
-    float *hbuf;          // [2][ndir][nbt][H*16]
-    float *cbuf;          // LSTM cell state [ndir][nbt][H*16]
-    float *out;           // [B][T][ndir*H]
-    const int *len;       // valid steps per utterance (nbt*16) or null = T for b < B
-    const int *row0;      // first row of every utterance in Gi / out (ragged rows) or null = b * T
-    int H, nbt, B, T, ndir;
-};
-
-template <int G, int SW>   // G = 3 GRU, 4 LSTM
-__global__ __launch_bounds__(256) void seq_step_kernel(SeqP p, int step) {
-    __shared__ float red[4][16][17];
-    __shared__ float gate[16][17];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int rg = blockIdx.x, dir = blockIdx.y, H = p.H;
-    const size_t hsz = (size_t)p.nbt * H * 16;
-    const float *hin = p.hbuf + ((size_t)(step & 1) * p.ndir + dir) * hsz;
-    float *hout = p.hbuf + ((size_t)((step + 1) & 1) * p.ndir + dir) * hsz;
-    const int bt = blockIdx.z;                     // one utterance tile per workgroup
-    // cell-update operands of wave 0's lanes are requested first: they do not depend on this step's
-    // W_hh h, so their latency hides under the fragment loads and the MFMAs
-    const int u = (tid >> 4) & 3, b = tid & 15, bg = bt * 16 + b, unit = 4 * rg + u;
-    bool act = false;
-    int tpos = 0;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f, bh0 = 0.f, bh1 = 0.f, bh2 = 0.f, hold = 0.f, cold = 0.f;
-    const size_t hi = hl_index(H, bg, unit);
-    if (tid < 64) {
-        const int L = p.len ? p.len[bg] : (bg < p.B ? p.T : 0);
-        if (step < L) {
-            act = true;
-            tpos = dir == 0 ? step : L - 1 - step;
-            const float *gi = p.Gi + ((p.row0 ? (size_t)p.row0[bg] : (size_t)bg * p.T) + tpos) * (p.ndir * G * H) + (size_t)dir * G * H + unit;
-            g0 = gi[0]; g1 = gi[H]; g2 = gi[2 * H];
-            if (G == 3) {
-                const float *bh = p.b_hh + (size_t)dir * 3 * H + unit;
-                bh0 = bh[0]; bh1 = bh[H]; bh2 = bh[2 * H];
-                hold = hin[hi];
-            } else {
-                g3 = gi[3 * H];
-                cold = p.cbuf[(size_t)dir * hsz + hi];
-            }
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float4 wf[SW];
-    load_wfrag<SW>(p.Wf + (size_t)dir * (H / 4) * (H / 16) * 64 * 4, rg, 4, wave, lane, wf);
-    const f32x4 acc = mv16<SW>(wf, hin, H, bt, wave, lane);
-    const float v = reduce4(red, acc, wave, lane, tid);
-    gate[tid >> 4][tid & 15] = v;
-    __syncthreads();
-    if (act) {
-        float hn;
-        if (G == 3) {
-            const float r = sigmoidf_(g0 + (gate[u][b] + bh0));
-            const float z = sigmoidf_(g1 + (gate[4 + u][b] + bh1));
-            const float n = tanhf(g2 + r * (gate[8 + u][b] + bh2));
-            hn = (1.0f - z) * n + z * hold;
-        } else {
-            const float ig = sigmoidf_(g0 + gate[u][b]), fg = sigmoidf_(g1 + gate[4 + u][b]);
-            const float gg = tanhf(g2 + gate[8 + u][b]), og = sigmoidf_(g3 + gate[12 + u][b]);
-            const float cn = fg * cold + ig * gg;
-            p.cbuf[(size_t)dir * hsz + hi] = cn;
-            hn = og * tanhf(cn);
-        }
-        hout[hi] = hn;
-        p.out[((p.row0 ? (size_t)p.row0[bg] : (size_t)bg * p.T) + tpos) * (p.ndir * H) + (size_t)dir * H + unit] = hn;
-    }
-}
-
-template <int G>
-static int launch_seq(const SeqP &p, int step, hipStream_t s) {
-    const int SW = p.H / 64;
-    dim3 grid(p.H / 4, p.ndir, p.nbt), blk(256);
-    switch (SW) {
-#define CASE(n) case n: hipLaunchKernelGGL((seq_step_kernel<G, n>), grid, blk, 0, s, p, step); break;
-        CASE(1) CASE(2) CASE(4) CASE(8)         // hidden sizes 64, 128 (the reference's prenet), 256 (its context LSTM), 512
-#undef CASE
-        default: vq_set_error("recurrent step: hidden size %d unsupported (64, 128, 256 and 512 are built)", p.H); return VQCPC_ERR_INVALID;
-    }
-    return VQCPC_OK;
-}
-
-__global__ void add_vec_kernel(const float *a, const float *b, float *o, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = a[i] + b[i];
-}
-
-// ---- encoder LSTM plan (model.py:57)
-struct LstmPlan {
-    int D, H;
-    float *w_ih = nullptr, *bias = nullptr, *Wf = nullptr;
-    float *w_hh = nullptr;               // plain [4H][H] copy for the persistent single-utterance scan
-    DevBuf gi, hbuf, cbuf, px;
-    unsigned *abort_host = nullptr;      // pinned, host-mapped: a timed-out exchange of the persistent scan is reported by the next call
-    int persistent = -1;                 // -1 auto (one utterance, H = 256), 0 off, 2 = auto with agent-scope stores forced (tests)
-    bool pending = false;                // a persistent scan may have raised the flag
-    int dbg_drop_step = -1;              // tests: worker 3 skips its publish at this step -> the others time out
-    int timeout_ms = 1000;               // bound of the scan's in-kernel waits
-};
-static int lstm_persist_launch(LstmPlan *p, int T, float *out, hipStream_t s);
-void vq_lstm_plan_destroy(LstmPlan *p) {
-    if (!p) return;
-    if (p->w_ih) (void)hipFree(p->w_ih);
-    if (p->bias) (void)hipFree(p->bias);
-    if (p->Wf) (void)hipFree(p->Wf);
-    if (p->w_hh) (void)hipFree(p->w_hh);
-    if (p->abort_host) (void)hipHostFree(p->abort_host);
-    p->gi.release(); p->hbuf.release(); p->cbuf.release(); p->px.release();
-    delete p;
-}
-int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int D, int H,
-                        LstmPlan **out) {
-    VQ_REQUIRE(D % 32 == 0 && (H == 64 || H == 128 || H == 256 || H == 512), "LSTM: need D %% 32 == 0 and a hidden size of 64, 128, 256 "
-               "(model.py:57) or 512 (got %d, %d)", D, H);
-    LstmPlan *p = new LstmPlan();
-    p->D = D; p->H = H;
-    *out = p;
-    HIP_TRY(hipMalloc((void **)&p->w_ih, (size_t)4 * H * D * sizeof(float)));
-    HIP_TRY(hipMemcpy(p->w_ih, w_ih, (size_t)4 * H * D * sizeof(float), hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMalloc((void **)&p->bias, (size_t)4 * H * sizeof(float)));
-    hipLaunchKernelGGL(add_vec_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, 0, b_ih, b_hh, p->bias, 4 * H);
-    HIP_TRY(hipGetLastError());
-    TRY(build_wfrag(w_hh, H, H / 4, H, 4, 4, H, &p->Wf));
-    HIP_TRY(hipMalloc((void **)&p->w_hh, (size_t)4 * H * H * sizeof(float)));
-    HIP_TRY(hipMemcpy(p->w_hh, w_hh, (size_t)4 * H * H * sizeof(float), hipMemcpyDeviceToDevice));
-    HIP_TRY(hipHostMalloc((void **)&p->abort_host, 64, hipHostMallocMapped));
-    *p->abort_host = 0u;
-    return VQCPC_OK;
-}
-int vq_lstm_set_persistent(LstmPlan *p, int value) { p->persistent = value; return VQCPC_OK; }
-int vq_lstm_set_debug(LstmPlan *p, int drop_step, int timeout_ms) { p->dbg_drop_step = drop_step; p->timeout_ms = timeout_ms; return VQCPC_OK; }
-// Valid once the stream that carried the scan has been synchronised (the next call on the handle checks as well: by then
-// the flag of a still-running scan may not be set yet, which is why callers that fetch results check after their sync).
-int vq_lstm_check(LstmPlan *p) {
-    if (!p->pending) return VQCPC_OK;
-    p->pending = false;
-    if (*(volatile unsigned *)p->abort_host != 0u) {
-        *p->abort_host = 0u;
-        p->persistent = 0;
-        vq_set_error("encoder LSTM: an in-kernel exchange of the resident scan timed out (the context of that call is incomplete); "
-                     "this handle now uses one launch per time step -- call again");
-        return VQCPC_ERR_HIP;
-    }
-    return VQCPC_OK;
-}
-int vq_lstm_run(LstmPlan *p, const float *x, int B, int T, float *out, hipStream_t s) {
-    const int H = p->H, nbt = (B + 15) / 16;
-    TRY(p->gi.reserve((size_t)B * T * 4 * H * sizeof(float)));
-    const size_t hsz = (size_t)nbt * H * 16 * sizeof(float);
-    TRY(p->hbuf.reserve(2 * hsz));
-    TRY(p->cbuf.reserve(hsz));
-    TRY(vq_gemm_chain(x, p->D, p->w_ih, p->bias, p->gi.as<float>(), 4 * H, B * T, 4 * H, p->D, p->D, s));
-    TRY(vq_lstm_check(p));               // did an earlier persistent scan report a timeout?  (no HIP call: host-mapped word)
-    // encode.py:42-46 calls encode() on ONE utterance at a time: that scan is a chain of T dependent 256-value exchanges,
-    // 3.6 us each as launches, < 1 us each inside one resident kernel
-    if (p->persistent != 0 && B == 1 && H == 256 && T >= 1) return lstm_persist_launch(p, T, out, s);
-    HIP_TRY(hipMemsetAsync(p->hbuf.p, 0, 2 * hsz, s));
-    HIP_TRY(hipMemsetAsync(p->cbuf.p, 0, hsz, s));
-    SeqP q{};
-    q.Wf = p->Wf; q.Gi = p->gi.as<float>(); q.hbuf = p->hbuf.as<float>(); q.cbuf = p->cbuf.as<float>();
-    q.out = out; q.len = nullptr; q.H = H; q.nbt = nbt; q.B = B; q.T = T; q.ndir = 1;
-    for (int t = 0; t < T; ++t) TRY(launch_seq<4>(q, t, s));
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }
@@ -444,7 +193,7 @@ __device__ __forceinline__ int wait_candidates(const ArModel &m, int sg, int t, 
             if ((spins & 255) == 255 && __builtin_amdgcn_s_memrealtime() - t0 > (u64)m.timeout_ticks) {      // default 0.25 s
                 if (lane == 0) {
                     __hip_atomic_store(m.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(m.abort_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(m.abort_host, STATUS_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 gave_up = true;
             }
@@ -505,7 +254,7 @@ __device__ __forceinline__ bool handoff_timed_out(const ArModel &m, u64 t0, unsi
     if ((spins & 255) != 255 || __builtin_amdgcn_s_memrealtime() - t0 <= (u64)m.timeout_ticks) return false;      // default 0.25 s
     if (lane == 0) {
         __hip_atomic_store(m.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(m.abort_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(m.abort_host, STATUS_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     return true;
 }
@@ -986,192 +735,6 @@ __global__ __launch_bounds__(256) void ar_fc2_kernel(ArModel m, const ArCall *__
     AR_STAMP(threadIdx.x == 0, 2, 3);
 }
 
-// ------------------------------------------------------------------------------------------
-// fp32 fma chains on the vector ALU, bit-identical to the v_mfma_f32_16x16x4_f32 schedule of the launch-per-step kernels
-// (a chain is a sequence of fp32 fmas in a fixed k order: two accumulators per K quarter, the x/z and y/w components of
-// the fragment; partial sums combined a0 + a1, then ((q0 + q1) + q2) + q3) -- used by the resident context scan below.
-// (Round 2's 64-workgroup persistent single-utterance decoder, ar_persist_kernel, lived here; the per-XCD decoders of
-// ar_xcd.hip replaced it in round 3 -- 2.6 us per sample against 4.95 -- and it was removed in round 4.)
-// ------------------------------------------------------------------------------------------
-// index of h[k] in the LDS copy: inside each 16-block, [component k % 4][k / 4 % 4], so that a chain reads the four
-// k of one MFMA as one 16-byte LDS word
-__device__ __forceinline__ int ps_perm(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-
-// one accumulator chain: NS super-steps of this K quarter, components c0 then c0 + 2 (the x/z or y/w MFMA operands)
-// (hipcc keeps one or two operand reads in flight here -- read, wait, 4 fmas.  Forcing a deeper window, by a register
-// window, by volatile reads or by sched_group_barrier, each made it spill 70-240 registers; measured alternatives dropped.)
-template <int NS>
-__device__ __forceinline__ float ps_chain(const float (&w)[8 * NS], const float4 *hb, int kw, int c0) {
-    float acc = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const float4 h0 = hb[(kw * NS + s) * 4 + c0], h1 = hb[(kw * NS + s) * 4 + c0 + 2];
-        acc = __builtin_fmaf(w[8 * s + 0], h0.x, acc); acc = __builtin_fmaf(w[8 * s + 1], h0.y, acc);
-        acc = __builtin_fmaf(w[8 * s + 2], h0.z, acc); acc = __builtin_fmaf(w[8 * s + 3], h0.w, acc);
-        acc = __builtin_fmaf(w[8 * s + 4], h1.x, acc); acc = __builtin_fmaf(w[8 * s + 5], h1.y, acc);
-        acc = __builtin_fmaf(w[8 * s + 6], h1.z, acc); acc = __builtin_fmaf(w[8 * s + 7], h1.w, acc);
-    }
-    return acc;
-}
-// the 8 chains of a row sit in 8 consecutive lanes (index 2 kw + a): returns, in the row's first lane, the row sum in
-// the order of the launch-per-step kernels
-// (DPP moves inside the row of 16 lanes instead of ds_bpermute round trips; only the row's first lane is meaningful)
-__device__ __forceinline__ float ps_combine(float acc, int lane) {
-    (void)lane;
-    const float other = PS_DPP(acc, 0xB1);             // quad_perm [1,0,3,2]: lane ^ 1
-    const float q = acc + other;                       // a0 + a1 (both lanes hold it)
-    const float q1 = PS_DPP(q, 0x4E);                  // quad_perm [2,3,0,1]: lane ^ 2 (= base + 2 in the first lane)
-    const float q2 = PS_DPP(q, 0x104);                 // row_shl:4: lane + 4
-    const float q3 = PS_DPP(q, 0x106);                 // row_shl:6: lane + 6
-    return ((q + q1) + q2) + q3;
-}
-
-// Every workgroup's granules start on a 128-byte line of their own (16 granules): lines shared by writers on different
-// CUs serialised the write-through stores -- the 64 one-granule candidate stores into 4 lines took 2.7 us to be seen.
-#define PS_PAD 16
-__device__ __forceinline__ int ps_slot(int idx, int per_blk) { return (idx / per_blk) * PS_PAD + idx % per_blk; }
-
-// Sweep N granules per lane (stride 64) until every tag equals `tag`; bounded.  Returns false on timeout / abort.
-template <int N>
-__device__ __forceinline__ bool ps_sweep(const u64 *g, int lane, int per_blk, unsigned tag, unsigned (&val)[N], unsigned *abort_flag,
-                                         u64 ticks = 100000000ull) {
-    const u64 t0 = __builtin_amdgcn_s_memrealtime();
-    int slot[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) slot[j] = ps_slot(lane + 64 * j, per_blk);
-    for (unsigned spins = 0;; ++spins) {
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const u64 x = ps_load(g + slot[j]);
-            val[j] = (unsigned)x;
-            ok &= (unsigned)(x >> 32) == tag;
-        }
-        if (__all(ok)) return true;
-        if ((spins & 63) == 63) {
-            const bool late = __builtin_amdgcn_s_memrealtime() - t0 > ticks;                 // default 1 s at 100 MHz
-            if (late || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) {
-                if (late && lane == 0) __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                return false;
-            }
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Persistent scan of the encoder LSTM for ONE utterance (model.py:57 as encode.py:42-46 calls it: batch 1).
-// The input projection is hoisted (Gi), so a time step is W_hh h_{t-1} (1024 x 256) + the cell update + an all-to-all of
-// 256 values.  32 workgroups of 256 threads stay resident, each with 8 hidden units = 32 gate rows in registers (8 chain
-// lanes per row, the chains and their combination exactly those of seq_step_kernel's MFMAs -> the same bits), and exchange
-// h_t as {tag, value} granules, one 128-B line per workgroup.
-// All 32 sit on ONE XCD: the grid is 8 x 32 and only every 8th workgroup works (workgroup id % 8 is the XCD:
-// profiles/r02_xcd_exchange_microbench.csv).  Parties that share an L2 can publish with plain stores -- the write-through
-// L1 leaves them in that L2, where sc1 loads find them: 0.41 us per exchange against 1.2 us through memory.  The placement
-// is CHECKED, not assumed: the workers first exchange their XCC_ID with agent-scope stores, and fall back to those for the
-// scan unless all ids agree.  Every wait is bounded; a timeout raises a host-mapped flag the next call reports.
-// ------------------------------------------------------------------------------------------
-#define LP_NW 32          // workers
-#define LP_UPB 8          // hidden units per worker (H = 256)
-struct LstmPersistP {
-    const float *w_hh;    // [4H][H]
-    const float *Gi;      // [T][4H]  W_ih x_t + b_ih + b_hh
-    float *out;           // [T][H]
-    u64 *g;               // [2][LP_NW][PS_PAD] granules: h_t goes to buffer t & 1 -- with ONE exchange per step a fast worker
-                          // publishes h_t while a slow one still sweeps h_{t-1}; it cannot reach h_{t+1} before that sweep ended
-    unsigned *abort_flag;
-    int T;
-    int force_agent;      // tests: publish with agent-scope stores even when all workers share an XCD (the fallback path)
-    int dbg_drop_step;    // tests: worker 3 skips its publish at this step
-    unsigned timeout_ticks;
-};
-template <bool LOCAL>
-__device__ __forceinline__ void lp_store(u64 *p, u64 v) {
-    if (LOCAL) asm volatile("global_store_dwordx2 %0, %1, off sc0" :: "v"(p), "v"(v) : "memory");    // workgroup scope: leaves the CU, stays in this XCD's L2
-    else ps_store(p, v);
-}
-__global__ __launch_bounds__(256) void lstm_persist_kernel(LstmPersistP p) {
-    constexpr int H = 256;
-    if (blockIdx.x % 8 != 0) return;
-    const int blk = blockIdx.x / 8, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ __attribute__((aligned(16))) float hbuf[H];             // h_{t-1}, ps_perm order
-    __shared__ float gsum[4 * LP_UPB];                                  // W_hh h_{t-1} of the owned rows [gate][unit]
-    // ---- resident weights: row r = gate * 8 + unit, 8 chain lanes per row (as ar_persist_kernel)
-    const int row_local = tid >> 3, gate = row_local / LP_UPB, ul = row_local % LP_UPB;
-    const int kw = (lane & 7) >> 1, c0 = lane & 1;
-    float w[8 * 4];
-    ps_load_weights<4>(p.w_hh + (size_t)(gate * H + LP_UPB * blk + ul) * H, kw, c0, w);
-    const int unit = LP_UPB * blk + (tid < LP_UPB ? tid : 0);
-    const u64 *gw = p.g + (size_t)(8 * wave) * PS_PAD;                  // this wave sweeps granules 64 wave .. 64 wave + 63
-    // ---- are all workers on one XCD?  (ids exchanged through memory: agent-scope stores, slot 8 of every line)
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 0xfu;
-    if (tid == 0) ps_store(p.g + (size_t)blk * PS_PAD + 8, ((u64)0xC0DEu << 32) | xcc);
-    bool dead = false, local = true;
-    {
-        const u64 t0 = __builtin_amdgcn_s_memrealtime();
-        for (unsigned spins = 0;; ++spins) {
-            const u64 x = ps_load(p.g + (size_t)(lane & 31) * PS_PAD + 8);
-            if (__all((unsigned)(x >> 32) == 0xC0DEu)) { local = __all((unsigned)x == xcc) && !p.force_agent; break; }
-            if ((spins & 63) == 63 && (__builtin_amdgcn_s_memrealtime() - t0 > 100000000ull ||
-                                       __hip_atomic_load(p.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) {
-                if (lane == 0) __hip_atomic_store(p.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                dead = true;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    float cst = 0.f;                                                    // cell state of unit `tid` (tid < 8)
-    float gi0 = 0.f, gi1 = 0.f, gi2 = 0.f, gi3 = 0.f;
-    if (tid < LP_UPB) { const float *gp = p.Gi + unit; gi0 = gp[0]; gi1 = gp[H]; gi2 = gp[2 * H]; gi3 = gp[3 * H]; }
-    for (int t = 0; t < p.T; ++t) {
-        // ---- h_{t-1} from everyone (zero at t = 0)
-        float hv = 0.f;
-        if (t > 0 && !dead) {
-            unsigned v[1];
-            if (ps_sweep<1>(gw + (size_t)((t - 1) & 1) * LP_NW * PS_PAD, lane, LP_UPB, (unsigned)t, v, p.abort_flag, (u64)p.timeout_ticks)) hv = __uint_as_float(v[0]);
-            else dead = true;
-        }
-        hbuf[ps_perm(tid)] = hv;
-        ps_barrier();
-        const float acc = ps_chain<4>(w, (const float4 *)hbuf, kw, c0);
-        const float v = ps_combine(acc, lane);
-        if ((lane & 7) == 0) gsum[row_local] = v;
-        ps_barrier();
-        if (tid < LP_UPB) {
-            const float ig = sigmoidf_(gi0 + gsum[tid]), fg = sigmoidf_(gi1 + gsum[LP_UPB + tid]);
-            const float gg = tanhf(gi2 + gsum[2 * LP_UPB + tid]), og = sigmoidf_(gi3 + gsum[3 * LP_UPB + tid]);
-            cst = fg * cst + ig * gg;
-            const float hn = og * tanhf(cst);
-            const u64 gr = ((u64)(unsigned)(t + 1) << 32) | __float_as_uint(hn);
-            u64 *dst = p.g + ((size_t)(t & 1) * LP_NW + blk) * PS_PAD + tid;
-            const bool drop = p.dbg_drop_step == t && blk == 3;          // tests: the other workers' sweeps of h_t time out
-            if (drop) { }
-            else if (local) lp_store<true>(dst, gr);
-            else lp_store<false>(dst, gr);
-            p.out[(size_t)t * H + unit] = hn;
-            if (t + 1 < p.T) { const float *gp = p.Gi + (size_t)(t + 1) * 4 * H + unit; gi0 = gp[0]; gi1 = gp[H]; gi2 = gp[2 * H]; gi3 = gp[3 * H]; }
-        }
-    }
-}
-static int lstm_persist_launch(LstmPlan *p, int T, float *out, hipStream_t s) {
-    const size_t bytes = (size_t)2 * LP_NW * PS_PAD * sizeof(u64);
-    TRY(p->px.reserve(bytes));
-    HIP_TRY(hipMemsetAsync(p->px.p, 0, bytes, s));
-    LstmPersistP q{};
-    q.w_hh = p->w_hh; q.Gi = p->gi.as<float>(); q.out = out; q.g = p->px.as<u64>(); q.T = T;
-    q.force_agent = p->persistent == 2;
-    q.dbg_drop_step = p->dbg_drop_step;
-    q.timeout_ticks = (unsigned)p->timeout_ms * 100000u;
-    HIP_TRY(hipHostGetDevicePointer((void **)&q.abort_flag, p->abort_host, 0));
-    hipLaunchKernelGGL(lstm_persist_kernel, dim3(8 * LP_NW), dim3(256), 0, s, q);
-    HIP_TRY(hipGetLastError());
-    p->pending = true;
-    return VQCPC_OK;
-}
-
 __global__ void ar_advance_kernel(ArCall *c, int n) {
     c->t_base += n;
     if (c->hall && c->t_base - c->hall_t0 >= c->CH) c->hall_t0 += c->CH;      // next chunk of the teacher-forced scan
@@ -1248,7 +811,7 @@ __global__ void ar_finalize_kernel(ArModel m, const ArCall *__restrict__ cp) {
 
 // Vocoder glue (network_vocoder.py:73-77): series[b, t2, :dz] = code_emb[idx[b, t2/2]], [dz:] = spk_emb[spk[b]]
 // An index outside its table (nn.Embedding raises IndexError, network_vocoder.py:73,75) is clamped for the read and reported through
-// the handle's host-mapped status word (bit 2; vqcpc_vocoder_check): no read-back of the indices on the host, no synchronisation.
+// the handle's host-mapped status word (STATUS_BAD_INDEX; vqcpc_vocoder_check): no read-back of the indices on the host, no synchronisation.
 __global__ void glue_kernel(const int64_t *__restrict__ idx, const int64_t *__restrict__ spk,
                             const float *__restrict__ ce, const float *__restrict__ se, float *__restrict__ out,
                             int B, int Tc, int dz, int ds, int n_codes, int n_spk, unsigned *status, unsigned status_tag,
@@ -1265,12 +828,12 @@ __global__ void glue_kernel(const int64_t *__restrict__ idx, const int64_t *__re
     }
     if (f < dz) {
         long long z = idx[(size_t)b * Tc + t2 / 2];
-        if ((z < 0 || z >= n_codes) && f == 0 && status) __hip_atomic_fetch_or(status, status_tag | 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if ((z < 0 || z >= n_codes) && f == 0 && status) __hip_atomic_fetch_or(status, status_tag | STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         z = z < 0 ? 0 : (z >= n_codes ? n_codes - 1 : z);
         out[i] = ce[(size_t)z * dz + f];
     } else {
         long long sp = spk[b];
-        if ((sp < 0 || sp >= n_spk) && f == dz && t2 == 0 && status) __hip_atomic_fetch_or(status, status_tag | 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if ((sp < 0 || sp >= n_spk) && f == dz && t2 == 0 && status) __hip_atomic_fetch_or(status, status_tag | STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         sp = sp < 0 ? 0 : (sp >= n_spk ? n_spk - 1 : sp);
         out[i] = se[(size_t)sp * ds + (f - dz)];
     }
@@ -1326,6 +889,9 @@ struct HostStage {
 // ------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------
+// Defaults of the decode-loop options: the handle starts with them, and vqcpc_vocoder_plan takes them for -1 / 0.
+constexpr int XCM_MIN_DEFAULT = 68, XCM_MAX_DEFAULT = 512, XCD_SLOTS_DEFAULT = 8 * XD_MAX_BX, XCM_SLOTS_DEFAULT = 8 * XM_BX;
+
 struct vqcpc_vocoder {
     vqcpc_vocoder_weights d;             // dims only (pointers below are owned copies)
     float *code_emb = nullptr, *spk_emb = nullptr;
@@ -1349,17 +915,17 @@ struct vqcpc_vocoder {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     DevBuf series, gi, out0, cond, gcond, gbase, hseq, len;
     DevBuf hall, a1c;                    // teacher-forced scan: h_t and fc1 outputs of one chunk
-    unsigned *abort_host = nullptr;      // the handle's status word: pinned host memory the kernels write and the host reads without a HIP call
-    unsigned *abort_dev = nullptr;       // the device's view of it
+    unsigned *status_host = nullptr;     // the handle's status word: pinned host memory the kernels write and the host reads without a HIP call
+    unsigned *status_dev = nullptr;      // the device's view of it
     HostStage stage;
     float *w_hh = nullptr;               // plain (3Hr, Hr) copy of W_hh for it
     int fuse_fc2 = 1;                    // fc2 + draw of step t-1 and the GRU step t share one launch
-    bool persist_pending = false;        // a call with in-kernel hand-offs is in flight: its status word has not been read behind a sync yet
+    bool status_pending = false;         // a call with in-kernel hand-offs is in flight: its status word has not been read behind a sync yet
     unsigned epoch = 0;                  // calls of run_ar so far: the resident decoders tag the status word with it
     int last_slots = 0;                  // decode slots the last call's loop actually used
-    // Fallback policy.  A placement miss (status 2: the 256 workgroups were not dealt 32 per XCD -- another kernel held CUs) wrote
+    // Fallback policy.  A placement miss (STATUS_MISPLACED: the 256 workgroups were not dealt 32 per XCD -- another kernel held CUs) wrote
     // nothing and is transient: the call is reported, the handle keeps its options, the caller repeats; only the second miss in
-    // a row switches the resident decoders off.  A timeout (status 1) switches the in-kernel hand-offs off at once and the
+    // a row switches the resident decoders off.  A timeout (STATUS_TIMEOUT) switches the in-kernel hand-offs off at once and the
     // handle re-arms itself after REARM_CLEAN clean calls (or when the option is set again).
     int placement_misses = 0;
     bool fell_back = false;
@@ -1368,7 +934,7 @@ struct vqcpc_vocoder {
     int handoff_timeout_ms = 250;        // bound of the candidate waits of the fused fc2 || GRU launch
     int handoff_debug_drop_step = -1;    // tests: one fc2 team skips its publish at this step
     int xcd = -1;
-    int xcd_slots = 8 * XD_MAX_BX;       // decode slots it may use (<= 8 * XD_MAX_BX); more utterances run back to back in them
+    int xcd_slots = XCD_SLOTS_DEFAULT;   // decode slots it may use (<= 8 * XD_MAX_BX); more utterances run back to back in them
     int xcd_agent_stores = 0;            // tests / A-B: publish with agent-scope stores
     int xcd_timeout_ms = 250;            // bound of its in-kernel waits
     int xcd_debug_drop_step = -1;        // tests: one worker skips a candidate publish at this step -> the waits time out
@@ -1377,11 +943,10 @@ struct vqcpc_vocoder {
     // per step whatever the number of slots in use -> 6.2 M samples/s at 64 utterances (ar_xcd.hip through its 32 slots: 8.5 M),
     // 12.3 M at 128 and 256 (launches: 8.2 / 10.8 M), against 12.4 M on the launch path with 512 utterances in flight.
     int xcm = -1;
-    int xcm_min = 68, xcm_max = 512;
-    int xcm_slots = 8 * XM_BX;
+    int xcm_min = XCM_MIN_DEFAULT, xcm_max = XCM_MAX_DEFAULT;
+    int xcm_slots = XCM_SLOTS_DEFAULT;
     int xcd_debug_misplace = 0;          // tests: workgroup 0 reports the wrong XCD -> status 2, nothing written
     DevBuf xd_x, xd_segs;                // exchange area, slot schedule
-    bool last_was_xcd = false, last_was_xcm = false;
     int tf_chunk_replays = 4;            // graph replays (of steps_per_graph steps) per chunk of the teacher-forced scan
     int use_graph = 1, steps_per_graph = 160;
     int n_slots = 0;                     // 0 = one slot per utterance; else continuous batching over this many
@@ -1393,8 +958,24 @@ struct vqcpc_vocoder {
     int last_steps = 0;
     ArCall last_call{};                  // host copies of group 0 of the last decode call (kernel timing)
     ArModel last_model{};
-    bool have_last = false;
+    int last_path = 1;                   // vqcpc_vocoder_last_path: 0 launch path (last_call / last_model valid), 1 none, 2 / 3 resident
 };
+
+static void clear_graphs(vqcpc_vocoder::Group &G) {
+    for (auto &kv : G.graphs) (void)hipGraphExecDestroy(kv.second);
+    G.graphs.clear();
+}
+static void clear_graphs(vqcpc_vocoder *v) {
+    for (auto &G : v->grp) clear_graphs(G);
+}
+
+// The handle's grow-only work buffers: freed by vqcpc_vocoder_destroy, counted by vqcpc_vocoder_workspace_bytes.
+static std::vector<DevBuf *> work_buffers(vqcpc_vocoder *v) {
+    std::vector<DevBuf *> b = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c,
+                               &v->xd_x, &v->xd_segs};
+    for (auto &G : v->grp) b.insert(b.end(), {&G.har, &G.a1, &G.cand_s, &G.cand_k, &G.slot_tab, &G.cur, &G.gcur, &G.candg});
+    return b;
+}
 
 static int dcopy(float **dst, const float *src, size_t n) {
     HIP_TRY(hipMalloc((void **)dst, n * sizeof(float)));
@@ -1404,12 +985,9 @@ static int dcopy(float **dst, const float *src, size_t n) {
 
 extern "C" void vqcpc_vocoder_destroy(vqcpc_vocoder *v) {
     if (!v) return;
-    for (auto &g : v->grp) {
-        for (auto &kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
-        if (g.call) (void)hipFree(g.call);
-        DevBuf *gb[] = {&g.har, &g.a1, &g.cand_s, &g.cand_k, &g.slot_tab, &g.cur, &g.gcur, &g.candg};
-        for (DevBuf *b : gb) b->release();
-    }
+    clear_graphs(v);
+    for (auto &g : v->grp) if (g.call) (void)hipFree(g.call);
+    for (DevBuf *b : work_buffers(v)) b->release();
     if (v->side_stream) (void)hipStreamDestroy(v->side_stream);
     if (v->ev_fork) (void)hipEventDestroy(v->ev_fork);
     if (v->ev_join) (void)hipEventDestroy(v->ev_join);
@@ -1418,12 +996,10 @@ extern "C" void vqcpc_vocoder_destroy(vqcpc_vocoder *v) {
                      v->Wf_fc1, v->Wf_fc1h, v->b_fc1, v->Wf_fc2, v->b_fc2, v->mulaw_tab, v->w_fc1, v->w_fc2};
     for (float *p : ptrs) if (p) (void)hipFree(p);
     v->stage.release();
-    if (v->abort_host) (void)hipHostFree(v->abort_host);
+    if (v->status_host) (void)hipHostFree(v->status_host);
     if (v->w_hh) (void)hipFree(v->w_hh);
     if (v->Gemb4) (void)hipFree(v->Gemb4);
     if (v->bh4) (void)hipFree(v->bh4);
-    DevBuf *bufs[] = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c, &v->xd_x, &v->xd_segs};
-    for (DevBuf *b : bufs) b->release();
     if (v->cap_stream) (void)hipStreamDestroy(v->cap_stream);
     if (v->ev0) (void)hipEventDestroy(v->ev0);
     if (v->ev1) (void)hipEventDestroy(v->ev1);
@@ -1446,7 +1022,7 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
             HIP_TRY(hipMemcpy(v->p_bih[l] + (size_t)d * 3 * Hp, w->prenet_b_ih[l][d], (size_t)3 * Hp * sizeof(float), hipMemcpyDeviceToDevice));
             HIP_TRY(hipMemcpy(v->p_bhh[l] + (size_t)d * 3 * Hp, w->prenet_b_hh[l][d], (size_t)3 * Hp * sizeof(float), hipMemcpyDeviceToDevice));
             float *tmp = nullptr;
-            TRY(build_wfrag(w->prenet_w_hh[l][d], Hp, Hp / 4, Hp, 4, 3, Hp, &tmp));
+            TRY(vq_build_wfrag(w->prenet_w_hh[l][d], Hp, Hp / 4, Hp, 4, 3, Hp, &tmp));
             const size_t nb = (size_t)(Hp / 4) * (Hp / 16) * 64 * sizeof(float4);
             HIP_TRY(hipMemcpy((char *)v->p_wf[l] + d * nb, tmp, nb, hipMemcpyDeviceToDevice));
             HIP_TRY(hipFree(tmp));
@@ -1473,10 +1049,10 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
     hipLaunchKernelGGL(quads_build_kernel, dim3((unsigned)((Hr + 255) / 256)), dim3(256), 0, 0, v->b_hh, v->bh4, 1, Hr);
     HIP_TRY(hipGetLastError());
     TRY(build_wfrag12(w->ar_w_hh, Hr, Hr / 4, Hr, Hr, &v->Wf_hh12));
-    if (Hr % 16 == 0) TRY(build_wfrag(w->ar_w_hh, Hr, 3 * (Hr / 16), Hr, 4, 16, Hr, &v->Wf_hh16));
-    TRY(build_wfrag(w->fc1_weight, Hr, w->Hf / 16, Hr, 4, 0, 0, &v->Wf_fc1));
-    TRY(build_wfrag(w->fc1_weight, Hr, w->Hf / 8, Hr, 4, 8, 0, &v->Wf_fc1h));
-    TRY(build_wfrag(w->fc2_weight, w->Hf, w->n_cls / 16, w->Hf, 1, 0, 0, &v->Wf_fc2));
+    if (Hr % 16 == 0) TRY(vq_build_wfrag(w->ar_w_hh, Hr, 3 * (Hr / 16), Hr, 4, 16, Hr, &v->Wf_hh16));
+    TRY(vq_build_wfrag(w->fc1_weight, Hr, w->Hf / 16, Hr, 4, 0, 0, &v->Wf_fc1));
+    TRY(vq_build_wfrag(w->fc1_weight, Hr, w->Hf / 8, Hr, 4, 8, 0, &v->Wf_fc1h));
+    TRY(vq_build_wfrag(w->fc2_weight, w->Hf, w->n_cls / 16, w->Hf, 1, 0, 0, &v->Wf_fc2));
     TRY(dcopy(&v->w_hh, w->ar_w_hh, (size_t)3 * Hr * Hr));
     TRY(dcopy(&v->w_fc1, w->fc1_weight, (size_t)w->Hf * Hr));
     TRY(dcopy(&v->w_fc2, w->fc2_weight, (size_t)w->n_cls * w->Hf));
@@ -1492,9 +1068,9 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
     HIP_TRY(hipMalloc((void **)&v->mulaw_tab, tab.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(v->mulaw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     for (auto &g : v->grp) HIP_TRY(hipMalloc((void **)&g.call, sizeof(ArCall)));
-    HIP_TRY(hipHostMalloc((void **)&v->abort_host, 64, hipHostMallocMapped));
-    *v->abort_host = 0u;
-    HIP_TRY(hipHostGetDevicePointer((void **)&v->abort_dev, v->abort_host, 0));
+    HIP_TRY(hipHostMalloc((void **)&v->status_host, 64, hipHostMallocMapped));
+    *v->status_host = 0u;
+    HIP_TRY(hipHostGetDevicePointer((void **)&v->status_dev, v->status_host, 0));
     HIP_TRY(hipStreamCreateWithFlags(&v->side_stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&v->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&v->ev_join, hipEventDisableTiming));
@@ -1528,109 +1104,58 @@ extern "C" int vqcpc_vocoder_create(const vqcpc_vocoder_weights *w, vqcpc_vocode
     return VQCPC_OK;
 }
 
-static void clear_graphs(vqcpc_vocoder *v) {
-    for (auto &g : v->grp) {
-        for (auto &kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
-        g.graphs.clear();
-    }
-}
+// set_option: name, member, accepted range, and flags -- OPT_BOOL stores value != 0 (any value is accepted), OPT_GRAPHS drops the
+// captured graphs when the value changes (they bake it), OPT_EVEN takes even values only.
+enum { OPT_BOOL = 1, OPT_GRAPHS = 2, OPT_EVEN = 4 };
+struct OptSpec { const char *name; int vqcpc_vocoder::*field; int lo, hi, flags; };
+static const OptSpec k_options[] = {
+    {"use_graph", &vqcpc_vocoder::use_graph, 0, 1, OPT_BOOL},
+    {"steps_per_graph", &vqcpc_vocoder::steps_per_graph, 2, 4096, OPT_GRAPHS | OPT_EVEN},
+    {"big_min_tiles", &vqcpc_vocoder::big_min_tiles, 0, INT_MAX, OPT_GRAPHS},
+    {"two_groups", &vqcpc_vocoder::two_groups, 0, 1, OPT_BOOL},
+    {"fuse_fc2", &vqcpc_vocoder::fuse_fc2, 0, 1, OPT_BOOL | OPT_GRAPHS},
+    {"handoff_timeout_ms", &vqcpc_vocoder::handoff_timeout_ms, 1, 10000, OPT_GRAPHS},
+    {"handoff_debug_drop_step", &vqcpc_vocoder::handoff_debug_drop_step, INT_MIN, INT_MAX, OPT_GRAPHS},
+    {"xcd", &vqcpc_vocoder::xcd, -1, 1, 0},
+    {"xcd_slots", &vqcpc_vocoder::xcd_slots, 1, 8 * XD_MAX_BX, 0},
+    {"xcd_agent_stores", &vqcpc_vocoder::xcd_agent_stores, 0, 1, OPT_BOOL},
+    {"xcm", &vqcpc_vocoder::xcm, -1, 1, 0},
+    {"xcm_min", &vqcpc_vocoder::xcm_min, 0, 65536, 0},
+    {"xcm_max", &vqcpc_vocoder::xcm_max, 0, 1 << 20, 0},
+    {"xcm_slots", &vqcpc_vocoder::xcm_slots, 1, 8 * XM_BX, 0},
+    {"xcd_timeout_ms", &vqcpc_vocoder::xcd_timeout_ms, 1, 10000, 0},
+    {"xcd_debug_drop_step", &vqcpc_vocoder::xcd_debug_drop_step, INT_MIN, INT_MAX, 0},
+    {"xcd_debug_misplace", &vqcpc_vocoder::xcd_debug_misplace, 0, 1, OPT_BOOL},
+    {"tf_chunk_replays", &vqcpc_vocoder::tf_chunk_replays, 1, 64, 0},
+    {"slots", &vqcpc_vocoder::n_slots, 0, 65536, 0},
+};
 
 extern "C" int vqcpc_vocoder_set_option(vqcpc_vocoder *v, const char *name, int value) {
     VQ_REQUIRE(v && name, "vqcpc_vocoder_set_option: null argument");
-    if (!strcmp(name, "use_graph")) { v->use_graph = value != 0; return VQCPC_OK; }
-    if (!strcmp(name, "steps_per_graph")) {
-        VQ_REQUIRE(value > 0 && value <= 4096 && value % 2 == 0, "steps_per_graph must be even and in [2, 4096]");
-        if (value != v->steps_per_graph) clear_graphs(v);
-        v->steps_per_graph = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "big_min_tiles")) {
-        VQ_REQUIRE(value >= 0, "big_min_tiles must be >= 0");
-        if (value != v->big_min_tiles) clear_graphs(v);
-        v->big_min_tiles = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "two_groups")) { v->two_groups = value != 0; return VQCPC_OK; }
-    if (!strcmp(name, "fuse_fc2")) {
-        if ((value != 0) != (v->fuse_fc2 != 0)) clear_graphs(v);
-        v->fuse_fc2 = value != 0;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "handoff_timeout_ms")) {
-        VQ_REQUIRE(value >= 1 && value <= 10000, "handoff_timeout_ms must be in [1, 10000]");
-        if (value != v->handoff_timeout_ms) clear_graphs(v);
-        v->handoff_timeout_ms = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "handoff_debug_drop_step")) {
-        if (value != v->handoff_debug_drop_step) clear_graphs(v);
-        v->handoff_debug_drop_step = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcd")) {
-        VQ_REQUIRE(value >= -1 && value <= 1, "xcd must be -1 (auto), 0 or 1");
-        v->xcd = value;
-        v->fell_back = false; v->placement_misses = 0;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcd_slots")) {
-        VQ_REQUIRE(value >= 1 && value <= 8 * XD_MAX_BX, "xcd_slots must be in [1, %d]", 8 * XD_MAX_BX);
-        v->xcd_slots = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcd_agent_stores")) { v->xcd_agent_stores = value != 0; return VQCPC_OK; }
-    if (!strcmp(name, "xcm")) {
-        VQ_REQUIRE(value >= -1 && value <= 1, "xcm must be -1 (auto), 0 or 1");
-        v->xcm = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcm_min")) {
-        VQ_REQUIRE(value >= 0 && value <= 65536, "xcm_min out of range");
-        v->xcm_min = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcm_max")) {
-        VQ_REQUIRE(value >= 0 && value <= (1 << 20), "xcm_max out of range");
-        v->xcm_max = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcm_slots")) {
-        VQ_REQUIRE(value >= 1 && value <= 8 * XM_BX, "xcm_slots must be in [1, %d]", 8 * XM_BX);
-        v->xcm_slots = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcd_timeout_ms")) {
-        VQ_REQUIRE(value >= 1 && value <= 10000, "xcd_timeout_ms must be in [1, 10000]");
-        v->xcd_timeout_ms = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "xcd_debug_drop_step")) { v->xcd_debug_drop_step = value; return VQCPC_OK; }
-    if (!strcmp(name, "xcd_debug_misplace")) { v->xcd_debug_misplace = value != 0; return VQCPC_OK; }
-    if (!strcmp(name, "tf_chunk_replays")) {
-        VQ_REQUIRE(value >= 1 && value <= 64, "tf_chunk_replays must be in [1, 64]");
-        v->tf_chunk_replays = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "slots")) {
-        VQ_REQUIRE(value >= 0 && value <= 65536, "slots out of range");
-        v->n_slots = value;
+    for (const OptSpec &o : k_options) {
+        if (strcmp(name, o.name)) continue;
+        if (o.flags & OPT_BOOL) value = value != 0;
+        VQ_REQUIRE(value >= o.lo && value <= o.hi && !((o.flags & OPT_EVEN) && value % 2), "%s must be %sin [%d, %d]", name,
+                   (o.flags & OPT_EVEN) ? "even and " : "", o.lo, o.hi);
+        if ((o.flags & OPT_GRAPHS) && value != v->*o.field) clear_graphs(v);
+        v->*o.field = value;
+        if (o.field == &vqcpc_vocoder::xcd) { v->fell_back = false; v->placement_misses = 0; }   // a choice of its own re-arms the fallback
         return VQCPC_OK;
     }
     vq_set_error("unknown option %s", name);
     return VQCPC_ERR_INVALID;
 }
 
-static void clear_graphs(vqcpc_vocoder *v);
 // Did an in-kernel hand-off of an earlier call give up?  The status word is host-mapped (no HIP call).  `synced`: the caller has
 // synchronised the stream that carried the calls (vqcpc_vocoder_check's contract), so a zero word clears every call in flight;
 // without it (the start of the next call) only a word that is already set is acted on -- nothing is cleared before a sync.
 constexpr int REARM_CLEAN = 16;
-static int persist_check(vqcpc_vocoder *v, bool synced) {
-    if (!v->persist_pending) return VQCPC_OK;
-    const unsigned flag = *(volatile unsigned *)v->abort_host;        // written by the kernel; no HIP call
+static int status_check(vqcpc_vocoder *v, bool synced) {
+    if (!v->status_pending) return VQCPC_OK;
+    const unsigned flag = *(volatile unsigned *)v->status_host;        // written by the kernel; no HIP call
     if (flag == 0) {
         if (synced) {
-            v->persist_pending = false;
+            v->status_pending = false;
             v->placement_misses = 0;
             if (v->fell_back && ++v->clean_calls >= REARM_CLEAN) {     // re-arm: the cause (a co-tenant kernel, a hung peer) is probably gone
                 v->fell_back = false;
@@ -1640,17 +1165,17 @@ static int persist_check(vqcpc_vocoder *v, bool synced) {
         }
         return VQCPC_OK;
     }
-    *(volatile unsigned *)v->abort_host = 0u;
-    v->persist_pending = false;
+    *(volatile unsigned *)v->status_host = 0u;
+    v->status_pending = false;
     const unsigned code = flag & 0xffu, ep = flag >> 8;
     char which[64];
     if (ep) snprintf(which, sizeof which, "call #%u of this handle", ep);
     else snprintf(which, sizeof which, "an earlier call of this handle");
-    if (code & 4u) {
+    if (code & STATUS_BAD_INDEX) {
         vq_set_error("index out of range in self (%s): a code index or speaker id outside its embedding table (network_vocoder.py:73,75)", which);
         return VQCPC_ERR_INVALID;
     }
-    if (code & 2u) {
+    if (code & STATUS_MISPLACED) {
         v->placement_misses += 1;
         if (v->placement_misses >= 2) {
             if (!v->fell_back) { v->saved_xcd = v->xcd; v->saved_fuse_fc2 = v->fuse_fc2; }
@@ -1675,12 +1200,12 @@ static int persist_check(vqcpc_vocoder *v, bool synced) {
 
 extern "C" int vqcpc_vocoder_last_path(vqcpc_vocoder *v) {
     if (!v) return -1;
-    return v->last_was_xcm ? 3 : v->last_was_xcd ? 2 : (v->have_last ? 0 : 1);
+    return v->last_path;
 }
 
 extern "C" int vqcpc_vocoder_check(vqcpc_vocoder *v) {
     VQ_REQUIRE(v, "vqcpc_vocoder_check: null argument");
-    return persist_check(v, true);
+    return status_check(v, true);
 }
 
 extern "C" int vqcpc_vocoder_last_slots(vqcpc_vocoder *v) {
@@ -1690,16 +1215,14 @@ extern "C" int vqcpc_vocoder_last_slots(vqcpc_vocoder *v) {
 extern "C" int vqcpc_vocoder_workspace_bytes(vqcpc_vocoder *v, uint64_t *bytes) {
     VQ_REQUIRE(v && bytes, "vqcpc_vocoder_workspace_bytes: null argument");
     uint64_t n = 0;
-    DevBuf *bufs[] = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c, &v->xd_x, &v->xd_segs};
-    for (DevBuf *b : bufs) n += b->cap;
-    for (auto &G : v->grp) { DevBuf *gb[] = {&G.har, &G.a1, &G.cand_s, &G.cand_k, &G.gcur, &G.candg, &G.slot_tab, &G.cur}; for (DevBuf *b : gb) n += b->cap; }
+    for (DevBuf *b : work_buffers(v)) n += b->cap;
     *bytes = n;
     return VQCPC_OK;
 }
 
 extern "C" int vqcpc_vocoder_last_timing(vqcpc_vocoder *v, float *loop_ms, int *n_steps) {
     VQ_REQUIRE(v && loop_ms && n_steps, "vqcpc_vocoder_last_timing: null argument");
-    TRY(persist_check(v, true));
+    TRY(status_check(v, true));
     HIP_TRY(hipEventElapsedTime(loop_ms, v->ev0, v->ev1));
     *n_steps = v->last_steps;
     return VQCPC_OK;
@@ -1721,20 +1244,16 @@ static int run_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *sp
     TRY(v->hseq.reserve(2 * hsz));
     const size_t ng = (size_t)B * T2 * F;
     hipLaunchKernelGGL(glue_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, idx, spk, v->code_emb,
-                       v->spk_emb, v->series.as<float>(), B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->abort_dev, v->epoch << 8,
+                       v->spk_emb, v->series.as<float>(), B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status_dev, v->epoch << 8,
                        frames_dev, row0_dev);
-    v->persist_pending = true;            // an index outside its table is reported through the status word
+    v->status_pending = true;            // an index outside its table is reported through the status word
     for (int l = 0; l < 2; ++l) {
         const float *xin = l == 0 ? v->series.as<float>() : v->out0.as<float>();
         const int I = l == 0 ? F : dl;
         float *xout = l == 0 ? v->out0.as<float>() : cond_out;
         TRY(vq_gemm_chain(xin, I, v->p_wih[l], v->p_bih[l], v->gi.as<float>(), 6 * Hp, (int)rows, 6 * Hp, I, I, s));
-        HIP_TRY(hipMemsetAsync(v->hseq.p, 0, 2 * hsz, s));
         if (frames_dev && !row0_dev) HIP_TRY(hipMemsetAsync(xout, 0, rows * dl * sizeof(float), s));      // dense rows past an utterance's end
-        SeqP q{};
-        q.Wf = v->p_wf[l]; q.b_hh = v->p_bhh[l]; q.Gi = v->gi.as<float>(); q.hbuf = v->hseq.as<float>();
-        q.out = xout; q.len = frames_dev; q.row0 = row0_dev; q.H = Hp; q.nbt = nbt; q.B = B; q.T = T2; q.ndir = 2;
-        for (int t = 0; t < T2; ++t) TRY(launch_seq<3>(q, t, s));
+        TRY(vq_bigru_scan(v->p_wf[l], v->p_bhh[l], v->gi.as<float>(), v->hseq.as<float>(), xout, frames_dev, row0_dev, Hp, B, T2, s));
     }
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
@@ -1757,7 +1276,6 @@ static int launch_gru_step(vqcpc_vocoder *v, const ArModel &m, const ArCall *cal
 #define CASE(k) case k: \
         if (m.fused && big) hipLaunchKernelGGL((ar_gru_big_kernel<k, 1>), dim3(nf + (Hr / 16) * npass), dim3(1024), lds, s, m, call, tl, nbt, nf); \
         else if (m.fused && nbt == 1) hipLaunchKernelGGL((ar_gru_kernel<k, 1, 3, 1>), dim3(nf + rgs), dim3(320), 0, s, m, call, tl, nbt, nf); \
-        else if (m.fused && m.lead6) hipLaunchKernelGGL((ar_gru_kernel<k, 2, 6, 1>), dim3(nf + rgs * npass), dim3(384), 0, s, m, call, tl, nbt, nf); \
         else if (m.fused) hipLaunchKernelGGL((ar_gru_kernel<k, 2, 3, 1>), dim3(nf + rgs * npass), dim3(384), 0, s, m, call, tl, nbt, nf); \
         else if (nbt == 1) hipLaunchKernelGGL((ar_gru_kernel<k, 1, 3, 0>), dim3(rgs), dim3(320), 0, s, m, call, tl, nbt, 0); \
         else if (big) hipLaunchKernelGGL((ar_gru_big_kernel<k, 0>), dim3(Hr / 16, npass), dim3(1024), lds, s, m, call, tl, nbt, 0); \
@@ -1785,7 +1303,7 @@ static int launch_fc1_step(vqcpc_vocoder *v, const ArModel &m, const ArCall *cal
 }
 
 // tf: teacher-forced scan -- x_{t-1} comes from the inputs, so only the GRU step runs per sample (fc1 / fc2 follow
-// as batched GEMMs over the whole chunk, run_ar)
+// as batched GEMMs over the whole chunk, run_launch_path)
 static int launch_ar_steps(vqcpc_vocoder *v, const ArModel &m, ArCall *call, int nbt, int n, bool tf, hipStream_t s) {
     const dim3 blk(256);
     const bool big = use_big(v, nbt);
@@ -1843,6 +1361,32 @@ struct DecodePlan {
     std::vector<long> xend;
 };
 struct PlanOpts { int xcd, xcm, xcm_min, xcm_max, xcd_slots, xcm_slots, n_slots; bool supported; };
+
+static std::vector<int> longest_first(const int *samples, int B) {
+    std::vector<int> order(B);
+    for (int b = 0; b < B; ++b) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return samples[a] > samples[b]; });
+    return order;
+}
+
+// Longest-first assignment (LPT) of the utterances of `order` over xs slots: each onto the slot that frees up first (the lowest
+// on a tie), where it starts; a slot frees up at the first multiple of `gran` steps from the end of its last utterance
+// (steps_per_graph on the launch path, whose utterances start at replay boundaries; 1 on the resident decoders).
+static void lpt(const std::vector<int> &order, const int *samples, const unsigned *utt, int xs, int gran, DecodePlan &pl) {
+    pl.xend.assign(xs, 0);
+    pl.lists.assign(xs, {});
+    for (int row : order) {
+        const int len = samples[row];
+        if (len <= 0) continue;
+        int best = 0;
+        for (int q = 1; q < xs; ++q) if (pl.xend[q] < pl.xend[best]) best = q;
+        pl.lists[best].push_back(XdSeg{row, (int)pl.xend[best], len, utt ? utt[row] : (unsigned)row});
+        pl.xend[best] = (pl.xend[best] + len + gran - 1) / gran * gran;
+    }
+    pl.longest = 0;
+    for (long e : pl.xend) pl.longest = e > pl.longest ? e : pl.longest;
+}
+
 static bool plan_decode(const PlanOpts &o, const int *samples, const unsigned *utt, const std::vector<int> &order, DecodePlan &pl) {
     int nz = 0;
     long max_len = 0;
@@ -1859,17 +1403,7 @@ static bool plan_decode(const PlanOpts &o, const int *samples, const unsigned *u
     if (o.n_slots > 0 && o.n_slots < xs) xs = o.n_slots;
     if (nz < xs) xs = nz;
     const int bxt = xcm_wanted ? XM_BX : xd_pick_bxt((xs + 7) / 8);
-    pl.xend.assign(xs, 0);
-    pl.lists.assign(xs, {});
-    for (int row : order) {
-        const int len = samples[row];
-        if (len <= 0) continue;
-        int best = 0;
-        for (int q = 1; q < xs; ++q) if (pl.xend[q] < pl.xend[best]) best = q;
-        pl.lists[best].push_back(XdSeg{row, (int)pl.xend[best], len, utt ? utt[row] : (unsigned)row});
-        pl.xend[best] += len;
-    }
-    for (int q = 0; q < xs; ++q) pl.longest = pl.xend[q] > pl.longest ? pl.xend[q] : pl.longest;
+    lpt(order, samples, utt, xs, 1, pl);
     const bool fits = bxt > 0 && pl.longest + 1 < (1L << 24);
     if (!fits) {
         pl.lists.clear(); pl.xend.clear();
@@ -1882,179 +1416,175 @@ static bool plan_decode(const PlanOpts &o, const int *samples, const unsigned *u
 extern "C" int vqcpc_vocoder_plan(int xcd, int xcm, int xcm_min, int xcm_max, int xcd_slots, int xcm_slots, int slots,
                                   const int *n_samples, int B, int *path, int *slots_used, int64_t *longest) {
     VQ_REQUIRE(n_samples && B > 0 && path && slots_used && longest, "vqcpc_vocoder_plan: bad argument");
-    std::vector<int> order(B);
-    for (int b = 0; b < B; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n_samples[a] > n_samples[b]; });
     DecodePlan pl;
-    const PlanOpts o{xcd, xcm, xcm_min < 0 ? 68 : xcm_min, xcm_max < 0 ? 512 : xcm_max, xcd_slots <= 0 ? 8 * XD_MAX_BX : xcd_slots,
-                     xcm_slots <= 0 ? 8 * XM_BX : xcm_slots, slots, true};
-    VQ_REQUIRE(plan_decode(o, n_samples, nullptr, order, pl), "vocoder: a decode slot's schedule does not fit the resident decoders "
-               "(< 2^24 - 1 samples); use more slots or xcd = -1");
+    const PlanOpts o{xcd, xcm, xcm_min < 0 ? XCM_MIN_DEFAULT : xcm_min, xcm_max < 0 ? XCM_MAX_DEFAULT : xcm_max,
+                     xcd_slots <= 0 ? XCD_SLOTS_DEFAULT : xcd_slots, xcm_slots <= 0 ? XCM_SLOTS_DEFAULT : xcm_slots, slots, true};
+    VQ_REQUIRE(plan_decode(o, n_samples, nullptr, longest_first(n_samples, B), pl), "vocoder: a decode slot's schedule does not fit "
+               "the resident decoders (< 2^24 - 1 samples); use more slots or xcd = -1");
     *path = pl.path; *slots_used = pl.path ? pl.xs : (slots > 0 && slots < B ? slots : B); *longest = pl.longest;
     return VQCPC_OK;
 }
 
-// Shared driver of generate() and logits().
-static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int B, int Tc, const int *n_codes_host,
-                  const int64_t *inputs, int Ts, unsigned long long seed, unsigned utt_base,
-                  const uint32_t *utt_ids_host, float *wav,
-                  int64_t *mulaw, float *logits, int max_steps, hipStream_t s) {
+// A decode call as planned on the host before anything is uploaded (no HIP call).
+struct CallPlan {
+    std::vector<int> lens;               // [frames | samples] per utterance, Bp entries each
+    std::vector<unsigned> utt;           // sampling-stream id per utterance
+    std::vector<int> gbase;              // first conditioning row per utterance (prefix sums of the frame counts)
+    long grows = 0;                      // conditioning rows in all
+    DecodePlan dp;                       // path 0: the launch path's dp.xs slots, utterances starting at replay boundaries
+    int n_grp = 1, tiles[2] = {0, 0}, rep[2] = {0, 0}, gmax[2] = {0, 0};   // launch path: tile groups (tiles, replays, steps)
+    std::vector<ArSlot> table[2];        // launch path: per group [replay][slot] what every decode slot is doing
+};
+
+static int plan_call(const vqcpc_vocoder *v, int B, int Tc, const int *n_codes_host, bool tf, int Ts, int max_steps,
+                     unsigned utt_base, const uint32_t *utt_ids_host, CallPlan &cp) {
     const auto &d = v->d;
-    const int Hr = d.Hr, dl = 2 * d.Hp, T2 = 2 * Tc, Bp = (B + 15) / 16 * 16;
-    const int Lout = d.upsample_t * T2;
-    const int S = v->steps_per_graph;
+    const int Bp = (B + 15) / 16 * 16, S = v->steps_per_graph;
     // per-utterance lengths: frames for the prenet, samples for the AR loop
-    std::vector<int> lens(2 * Bp, 0);     // [frames | samples]
-    std::vector<unsigned> utt(B);
+    cp.lens.assign(2 * Bp, 0);
+    cp.utt.resize(B);
     for (int b = 0; b < B; ++b) {
         int nc = n_codes_host ? n_codes_host[b] : Tc;
         VQ_REQUIRE(nc >= 0 && nc <= Tc, "vocoder: n_codes[%d] = %d outside [0, %d]", b, nc, Tc);
-        lens[b] = 2 * nc;
+        cp.lens[b] = 2 * nc;
         int ns = d.upsample_t * 2 * nc;
-        if (inputs) ns = ns < Ts ? ns : Ts;
+        if (tf) ns = ns < Ts ? ns : Ts;
         if (max_steps > 0 && ns > max_steps) ns = max_steps;
-        lens[Bp + b] = ns;
-        utt[b] = utt_ids_host ? utt_ids_host[b] : utt_base + (unsigned)b;
+        cp.lens[Bp + b] = ns;
+        cp.utt[b] = utt_ids_host ? utt_ids_host[b] : utt_base + (unsigned)b;
     }
-    // Decode-slot schedule (continuous batching): longest utterance first onto the slot that frees
-    // up first; an utterance starts at a replay boundary.  n_slots >= B: everything starts at 0.
-    int n_slots = (v->n_slots > 0 && v->n_slots < B && !inputs) ? v->n_slots : B;
-    const int nbt = (n_slots + 15) / 16;
-    std::vector<int> order(B);
-    for (int b = 0; b < B; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[Bp + a] > lens[Bp + b]; });
-    std::vector<long> slot_end(n_slots, 0);
-    struct Seg { int slot, row, t0, len; };
-    std::vector<Seg> segs;
-    long total = 0;
-    for (int row : order) {
-        const int len = lens[Bp + row];
-        if (len <= 0) continue;
-        int best = 0;
-        for (int q = 1; q < n_slots; ++q) if (slot_end[q] < slot_end[best]) best = q;
-        segs.push_back({best, row, (int)slot_end[best], len});
-        slot_end[best] = (slot_end[best] + len + S - 1) / S * S;
-        total = slot_end[best] > total ? slot_end[best] : total;
-    }
-    VQ_REQUIRE(total < (1L << 30), "vocoder: schedule too long");
-    const int max_t = (int)total;
+    // Conditioning over every utterance's own frames (ragged rows)
+    cp.gbase.assign(Bp, 0);
+    for (int b = 0; b < B; ++b) { cp.gbase[b] = (int)cp.grows; cp.grows += cp.lens[b]; }
+    VQ_REQUIRE(cp.grows < (1L << 31), "vocoder: %ld conditioning frames in one call", cp.grows);
+    const int *samples = cp.lens.data() + Bp;
+    const std::vector<int> order = longest_first(samples, B);
+    const PlanOpts po{v->xcd, v->xcm, v->xcm_min, v->xcm_max, v->xcd_slots, v->xcm_slots, tf ? 0 : v->n_slots,
+                      !tf && xd_supported(d.Hr, d.Hf, d.n_cls)};
+    VQ_REQUIRE(plan_decode(po, samples, cp.utt.data(), order, cp.dp), "vocoder: a decode slot's schedule does not fit the resident "
+               "decoders (< 2^24 - 1 samples); use more slots or xcd = -1");
+    if (cp.dp.path != 0) return VQCPC_OK;
+    // Launch path (continuous batching): n_slots >= B: everything starts at 0.
+    DecodePlan &dp = cp.dp;
+    dp.xs = !tf && v->n_slots > 0 && v->n_slots < B ? v->n_slots : B;
+    lpt(order, samples, cp.utt.data(), dp.xs, S, dp);
+    VQ_REQUIRE(dp.longest < (1L << 30), "vocoder: schedule too long");
+    const int nbt = (dp.xs + 15) / 16;
     // Tile groups: 3..big_min_tiles-1 tiles, or >= 2*big_min_tiles (both halves on the large-batch kernel), split in two.  (Measured: 2 x 16 utterances is slower than one
     // group of 32 -- the chip retires only ~0.43 dependent launches per us across queues -- while
-    // 2 x 32 runs at 14.5 us per sample against 17.3 us for one group of 64.)
-    const bool tf = inputs != nullptr;     // teacher-forced scan: one group, GRU steps only, chunked GEMMs for fc1 / fc2
+    // 2 x 32 runs at 14.5 us per sample against 17.3 us for one group of 64.)  A teacher-forced scan runs as one group.
     // With the fused fc2 || GRU launch the overlap two groups were for happens inside one launch, and two fused launches in
     // flight only compete (64 utterances: 17.4 us per step on two groups, 13.4 on one: profiles/r02_gru_variants.csv): the
     // small kernel runs as ONE group; only large-batch calls of >= 2 * big_min_tiles tiles are still split.
     const bool small_fused = v->fuse_fc2 && !(v->big_min_tiles > 0 && nbt >= v->big_min_tiles);
     const bool split = !tf && v->two_groups && v->use_graph && nbt >= 3 && !small_fused &&
                        !(v->big_min_tiles > 0 && nbt >= v->big_min_tiles && nbt < 2 * v->big_min_tiles);
-    const int n_grp = split ? 2 : 1;
-    const int tiles[2] = {split ? (nbt + 1) / 2 : nbt, split ? nbt / 2 : 0};
-    const int slot0[2] = {0, tiles[0] * 16};
-    TRY(persist_check(v, false));         // has an earlier call's hand-off reported already?  (nothing is cleared without a sync)
-    v->epoch = (v->epoch + 1u) & 0xffffffu;
-    if (v->epoch == 0) v->epoch = 1;
-    TRY(v->len.reserve(lens.size() * sizeof(int)));
-    std::vector<ArSlot> table[2];
-    int rep[2] = {0, 0}, gmax[2] = {0, 0};
-    for (int g = 0; g < n_grp; ++g) {
-        const int Spg = tiles[g] * 16;
+    cp.n_grp = split ? 2 : 1;
+    cp.tiles[0] = split ? (nbt + 1) / 2 : nbt;
+    cp.tiles[1] = split ? nbt / 2 : 0;
+    for (int g = 0; g < cp.n_grp; ++g) {
+        const int slot0 = g * cp.tiles[0] * 16, Spg = cp.tiles[g] * 16;
+        const int q_end = slot0 + Spg < dp.xs ? slot0 + Spg : dp.xs;
         long end = 0;
-        for (int q = slot0[g]; q < slot0[g] + Spg && q < n_slots; ++q) end = slot_end[q] > end ? slot_end[q] : end;
-        gmax[g] = (int)end; rep[g] = gmax[g] / S;
-        table[g].assign((size_t)(rep[g] > 0 ? rep[g] : 1) * Spg, ArSlot{-1, 0, 0, 0u});
-        for (const Seg &sg : segs) {
-            if (sg.slot < slot0[g] || sg.slot >= slot0[g] + Spg) continue;
-            for (int r = sg.t0 / S; r < (sg.t0 + sg.len + S - 1) / S; ++r)
-                table[g][(size_t)r * Spg + (sg.slot - slot0[g])] = ArSlot{sg.row, sg.t0, sg.len, utt[sg.row]};
-        }
-        TRY(v->grp[g].slot_tab.reserve(table[g].size() * sizeof(ArSlot)));
-        TRY(v->grp[g].cur.reserve((size_t)Spg * sizeof(ArSlot)));
+        for (int q = slot0; q < q_end; ++q) end = dp.xend[q] > end ? dp.xend[q] : end;
+        cp.gmax[g] = (int)end; cp.rep[g] = cp.gmax[g] / S;
+        cp.table[g].assign((size_t)(cp.rep[g] > 0 ? cp.rep[g] : 1) * Spg, ArSlot{-1, 0, 0, 0u});
+        for (int q = slot0; q < q_end; ++q)
+            for (const XdSeg &sg : dp.lists[q])
+                for (int r = sg.t0 / S; r < (sg.t0 + sg.len + S - 1) / S; ++r)
+                    cp.table[g][(size_t)r * Spg + (q - slot0)] = ArSlot{sg.row, sg.t0, sg.len, sg.utt};
     }
-    // upload through the pinned arena: no synchronisation of the caller's stream
-    TRY(v->stage.begin(lens.size() * sizeof(int) + (table[0].size() + table[1].size()) * sizeof(ArSlot) +
-                       (size_t)(tiles[0] + tiles[1]) * 16 * sizeof(ArSlot) + 2 * sizeof(ArCall) + 256 +
-                       (size_t)8 * XM_BX * (B + 1) * sizeof(XdSeg) + (size_t)2 * (B + 16) * sizeof(int)));
-    TRY(v->stage.upload(v->len.p, lens.data(), lens.size() * sizeof(int), s));
-    for (int g = 0; g < n_grp; ++g) {
-        TRY(v->stage.upload(v->grp[g].slot_tab.p, table[g].data(), table[g].size() * sizeof(ArSlot), s));
-        TRY(v->stage.upload(v->grp[g].cur.p, table[g].data(), (size_t)tiles[g] * 16 * sizeof(ArSlot), s));
-    }
-    // Conditioning over every utterance's own frames (ragged rows): row base of utterance b = prefix sum of the frame counts
-    std::vector<int> gbase(Bp, 0);
-    long grows = 0;
-    for (int b = 0; b < B; ++b) { gbase[b] = (int)grows; grows += lens[b]; }
-    VQ_REQUIRE(grows < (1L << 31), "vocoder: %ld conditioning frames in one call", grows);
-    TRY(v->gbase.reserve((size_t)Bp * sizeof(int)));
-    TRY(v->stage.upload(v->gbase.p, gbase.data(), (size_t)Bp * sizeof(int), s));
-    const size_t crows = grows > 0 ? (size_t)grows : 1;
-    TRY(v->cond.reserve(crows * dl * sizeof(float)));
-    TRY(run_condition(v, idx, spk, B, Tc, v->len.as<int>(), v->gbase.as<int>(), (size_t)grows, v->cond.as<float>(), s));
-    TRY(v->gcond.reserve(crows * 3 * Hr * sizeof(float)));
-    if (grows > 0)
-        TRY(vq_gemm_chain(v->cond.as<float>(), dl, v->w_cond, v->b_ih, v->gcond.as<float>(), 3 * Hr, (int)grows, 3 * Hr, dl, dl, s));
-    if (wav) HIP_TRY(hipMemsetAsync(wav, 0, (size_t)B * Lout * sizeof(float), s));
-    if (mulaw) HIP_TRY(hipMemsetAsync(mulaw, 0, (size_t)B * Lout * sizeof(int64_t), s));
+    return VQCPC_OK;
+}
 
-    unsigned *abort_dev_ptr = v->abort_dev;  // device view of the host-mapped status word (in-kernel waits that time out)
-    // One resident, weight-stationary decoder per XCD (ar_xcd.hip): utterances dealt over the XCDs' decode slots, longest
-    // first onto the slot that frees up first; a slot runs its utterances back to back (no replay boundaries here).
-    v->last_was_xcd = false; v->last_was_xcm = false;
-    DecodePlan pl;
-    {
-        const PlanOpts po{v->xcd, v->xcm, v->xcm_min, v->xcm_max, v->xcd_slots, v->xcm_slots, v->n_slots,
-                          !inputs && xd_supported(Hr, d.Hf, d.n_cls) && max_t > 0};
-        VQ_REQUIRE(plan_decode(po, lens.data() + Bp, utt.data(), order, pl), "vocoder: a decode slot's schedule does not fit the resident "
-                   "decoders (< 2^24 - 1 samples); use more slots or xcd = -1");
+// One resident, weight-stationary decoder per XCD (ar_xcd.hip, or its matrix-core form ar_xcm.hip): slot q runs the utterances
+// of cp.dp.lists[q] back to back (no replay boundaries here).
+static int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long long seed, float *wav, int64_t *mulaw,
+                        hipStream_t s) {
+    const auto &d = v->d;
+    const DecodePlan &pl = cp.dp;
+    const int B = (int)cp.utt.size();
+    size_t max_seg = 1;
+    for (auto &l : pl.lists) max_seg = l.size() + 1 > max_seg ? l.size() + 1 : max_seg;
+    std::vector<XdSeg> tab((size_t)8 * pl.bxt * max_seg, XdSeg{-1, 0, 0, 0u});
+    XdParams xp{};
+    for (int q = 0; q < pl.xs; ++q) {
+        for (size_t i = 0; i < pl.lists[q].size(); ++i) tab[(size_t)q * max_seg + i] = pl.lists[q][i];
+        const int x = q % 8;
+        if (pl.xend[q] + 1 > xp.n_steps[x]) xp.n_steps[x] = (int)pl.xend[q] + 1;
     }
-    if (pl.path != 0) {
-        {
-            const bool xcm_wanted = pl.path == 3;
-            const int xs = pl.xs, bxt = pl.bxt;
-            const long longest = pl.longest;
-            auto &lists = pl.lists;
-            auto &xend = pl.xend;
-            size_t max_seg = 1;
-            for (auto &l : lists) max_seg = l.size() + 1 > max_seg ? l.size() + 1 : max_seg;
-            std::vector<XdSeg> tab((size_t)8 * bxt * max_seg, XdSeg{-1, 0, 0, 0u});
-            XdParams xp{};
-            for (int q = 0; q < xs; ++q) {
-                for (size_t i = 0; i < lists[q].size(); ++i) tab[(size_t)q * max_seg + i] = lists[q][i];
-                const int x = q % 8;
-                if (xend[q] + 1 > xp.n_steps[x]) xp.n_steps[x] = (int)xend[q] + 1;
-            }
-            // behind the table: first Gcond row of every utterance (the kernels find it from the table's own address)
-            const size_t tab_bytes = tab.size() * sizeof(XdSeg);
-            TRY(v->xd_segs.reserve(tab_bytes + (size_t)B * sizeof(int)));
-            TRY(v->stage.upload((char *)v->xd_segs.p + tab_bytes, gbase.data(), (size_t)B * sizeof(int), s));
-            TRY(v->xd_x.reserve(xcm_wanted ? xm_exchange_bytes() : xd_exchange_bytes(bxt)));
-            TRY(v->stage.upload(v->xd_segs.p, tab.data(), tab.size() * sizeof(XdSeg), s));
-            xp.w_hh = v->w_hh; xp.w_fc1 = v->w_fc1; xp.b_fc1 = v->b_fc1; xp.w_fc2 = v->w_fc2; xp.b_fc2 = v->b_fc2;
-            xp.Gemb = v->Gemb; xp.b_hh = v->b_hh; xp.Gcond = v->gcond.as<float>(); xp.mulaw_tab = v->mulaw_tab;
-            xp.segs = v->xd_segs.as<XdSeg>(); xp.xg = v->xd_x.as<unsigned long long>(); xp.status = abort_dev_ptr;
-            xp.status_tag = v->epoch << 8;
-            xp.wav = wav; xp.mulaw = mulaw; xp.seed = seed; xp.max_seg = (int)max_seg; xp.n_slots = xs; xp.bxt = bxt;
-            xp.Lout = Lout; xp.F = T2; xp.upsample = d.upsample_t; xp.agent_stores = v->xcd_agent_stores;
-            xp.timeout_ticks = (unsigned)v->xcd_timeout_ms * 100000u; xp.dbg_drop_step = v->xcd_debug_drop_step;
-            xp.dbg_misplace = v->xcd_debug_misplace;
-            v->xcd_debug_misplace = 0;                     // one shot: the repeated call finds the workgroups where they are
-            HIP_TRY(hipEventRecord(v->ev0, s));
-            TRY(xcm_wanted ? xm_launch(xp, s) : xd_launch(xp, s));
-            HIP_TRY(hipEventRecord(v->ev1, s));
-            v->last_steps = (int)longest;
-            v->last_slots = xs;
-            v->have_last = false;
-            v->persist_pending = true;
-            v->last_was_xcd = !xcm_wanted; v->last_was_xcm = xcm_wanted;
-            return VQCPC_OK;
-        }
-    }
+    // behind the table: first Gcond row of every utterance (the kernels find it from the table's own address)
+    const size_t tab_bytes = tab.size() * sizeof(XdSeg);
+    TRY(v->xd_segs.reserve(tab_bytes + (size_t)B * sizeof(int)));
+    TRY(v->stage.upload((char *)v->xd_segs.p + tab_bytes, cp.gbase.data(), (size_t)B * sizeof(int), s));
+    TRY(v->xd_x.reserve(pl.path == 3 ? xm_exchange_bytes() : xd_exchange_bytes(pl.bxt)));
+    TRY(v->stage.upload(v->xd_segs.p, tab.data(), tab_bytes, s));
+    xp.w_hh = v->w_hh; xp.w_fc1 = v->w_fc1; xp.b_fc1 = v->b_fc1; xp.w_fc2 = v->w_fc2; xp.b_fc2 = v->b_fc2;
+    xp.Gemb = v->Gemb; xp.b_hh = v->b_hh; xp.Gcond = v->gcond.as<float>(); xp.mulaw_tab = v->mulaw_tab;
+    xp.segs = v->xd_segs.as<XdSeg>(); xp.xg = v->xd_x.as<unsigned long long>(); xp.status = v->status_dev;
+    xp.status_tag = v->epoch << 8;
+    xp.wav = wav; xp.mulaw = mulaw; xp.seed = seed; xp.max_seg = (int)max_seg; xp.n_slots = pl.xs; xp.bxt = pl.bxt;
+    xp.Lout = d.upsample_t * T2; xp.F = T2; xp.upsample = d.upsample_t; xp.agent_stores = v->xcd_agent_stores;
+    xp.timeout_ticks = (unsigned)v->xcd_timeout_ms * 100000u; xp.dbg_drop_step = v->xcd_debug_drop_step;
+    xp.dbg_misplace = v->xcd_debug_misplace;
+    v->xcd_debug_misplace = 0;                     // one shot: the repeated call finds the workgroups where they are
+    HIP_TRY(hipEventRecord(v->ev0, s));
+    TRY(pl.path == 3 ? xm_launch(xp, s) : xd_launch(xp, s));
+    HIP_TRY(hipEventRecord(v->ev1, s));
+    v->last_steps = (int)pl.longest;
+    v->last_slots = pl.xs;
+    v->last_path = pl.path;
+    v->status_pending = true;
+    return VQCPC_OK;
+}
 
+// The cached graph of one replay of group g (captured on first use).  A graph bakes its ArModel's buffer pointers: when a
+// workspace of the group moved, the group's cached graphs are dropped first.
+static int group_graph(vqcpc_vocoder *v, int g, const ArModel &m, int nbt, bool tf, hipGraphExec_t *out) {
+    auto &G = v->grp[g];
+    const void *now[8] = {G.har.p, G.a1.p, G.cand_s.p, G.cand_k.p, G.cur.p, G.gcur.p, G.candg.p, nullptr};
+    if (memcmp(G.baked, now, sizeof now) != 0) {
+        clear_graphs(G);
+        memcpy(G.baked, now, sizeof now);
+    }
+    const int gkey = (((nbt * 17 + m.live_last) * 2 + m.lead6) * 2 + (tf ? 1 : 0)) * 3 + m.fused;   // what the capture bakes
+    auto it = G.graphs.find(gkey);
+    if (it == G.graphs.end()) {
+        hipGraph_t gr = nullptr;
+        hipGraphExec_t ge = nullptr;
+        HIP_TRY(hipStreamBeginCapture(v->cap_stream, hipStreamCaptureModeThreadLocal));
+        int rc = launch_ar_steps(v, m, G.call, nbt, v->steps_per_graph, tf, v->cap_stream);
+        hipError_t e = hipStreamEndCapture(v->cap_stream, &gr);     // always end the capture, also on failure
+        if (rc != VQCPC_OK || e != hipSuccess) {
+            if (gr) (void)hipGraphDestroy(gr);
+            if (rc != VQCPC_OK) return rc;
+            HIP_TRY(e);
+        }
+        e = hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(gr);
+        HIP_TRY(e);
+        it = G.graphs.emplace(gkey, ge).first;
+    }
+    *out = it->second;
+    return VQCPC_OK;
+}
+
+// The launch-per-step kernels: per tile group its state buffers, call record (ArCall) and model (ArModel), then the replays of
+// steps_per_graph steps each -- captured graphs, or plain launches with use_graph = 0.
+static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs, int T2, int Ts, unsigned long long seed,
+                           float *wav, int64_t *mulaw, float *logits, hipStream_t s) {
+    const auto &d = v->d;
+    const int Hr = d.Hr, S = v->steps_per_graph, B = (int)cp.utt.size(), n_slots = cp.dp.xs, max_t = (int)cp.dp.longest;
+    const bool tf = inputs != nullptr;     // teacher-forced scan: one group, GRU steps only, chunked GEMMs for fc1 / fc2
     ArCall calls[2];
     ArModel models[2];
-    for (int g = 0; g < n_grp; ++g) {
+    for (int g = 0; g < cp.n_grp; ++g) {
         auto &G = v->grp[g];
-        const int nb = tiles[g], Spg = nb * 16;
+        const int nb = cp.tiles[g], Spg = nb * 16, slot0 = g * cp.tiles[0] * 16;
+        TRY(G.slot_tab.reserve(cp.table[g].size() * sizeof(ArSlot)));
+        TRY(G.cur.reserve((size_t)Spg * sizeof(ArSlot)));
+        TRY(v->stage.upload(G.slot_tab.p, cp.table[g].data(), cp.table[g].size() * sizeof(ArSlot), s));
+        TRY(v->stage.upload(G.cur.p, cp.table[g].data(), (size_t)Spg * sizeof(ArSlot), s));
         const size_t hsz = (size_t)nb * Hr * 16 * sizeof(float);
         TRY(G.har.reserve(2 * hsz));
         TRY(G.a1.reserve((size_t)nb * d.Hf * 16 * sizeof(float)));
@@ -2071,8 +1601,8 @@ static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int 
         ArCall &c = calls[g];
         c = ArCall{};
         c.Gcond = v->gcond.as<float>(); c.gbase = v->gbase.as<int>(); c.inputs = inputs; c.wav = wav; c.mulaw = mulaw; c.logits = logits;
-        c.slots = G.slot_tab.as<ArSlot>(); c.S = S; c.Sp = Spg; c.n_rep = rep[g] > 0 ? rep[g] : 1;
-        c.F = T2; c.Ts = Ts; c.Lout = Lout; c.max_t = gmax[g]; c.nbt = nb; c.seed = seed; c.t_base = 0;
+        c.slots = G.slot_tab.as<ArSlot>(); c.S = S; c.Sp = Spg; c.n_rep = cp.rep[g] > 0 ? cp.rep[g] : 1;
+        c.F = T2; c.Ts = Ts; c.Lout = d.upsample_t * T2; c.max_t = cp.gmax[g]; c.nbt = nb; c.seed = seed; c.t_base = 0;
         if (tf) {
             c.CH = v->tf_chunk_replays * S;
             TRY(v->hall.reserve((size_t)B * c.CH * Hr * sizeof(float)));
@@ -2087,77 +1617,42 @@ static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int 
         m.Wf_fc2 = v->Wf_fc2; m.b_fc2 = v->b_fc2; m.mulaw_tab = v->mulaw_tab;
         m.hbuf = G.har.as<float>(); m.a1 = G.a1.as<float>(); m.cand_s = G.cand_s.as<float>(); m.cand_k = G.cand_k.as<int>(); m.cur = G.cur.as<ArSlot>(); m.gcur4 = G.gcur.as<float4>();
         m.gc_replay = d.upsample_t % S == 0;
-        {
-            const int live = (n_slots - slot0[g] < Spg ? n_slots - slot0[g] : Spg) - (nb - 1) * 16;
-            m.live_last = live < 1 ? 1 : (live > 16 ? 16 : live);
-        }
-        m.lead6 = n_grp == 2 && nb <= 2;
+        const int live = (n_slots - slot0 < Spg ? n_slots - slot0 : Spg) - (nb - 1) * 16;
+        m.live_last = live < 1 ? 1 : (live > 16 ? 16 : live);
+        m.lead6 = cp.n_grp == 2 && nb <= 2;
         m.candg = G.candg.as<u64>();
         m.abort_dev = (unsigned *)((char *)G.candg.p + cg_bytes);
-        m.abort_host = abort_dev_ptr;
+        m.abort_host = v->status_dev;
         m.timeout_ticks = (unsigned)v->handoff_timeout_ms * 100000u;
         m.dbg_drop_t = v->handoff_debug_drop_step;
-        {
-            const size_t big_lds = (size_t)2 * Hr * 16 * sizeof(float) + (size_t)2 * 3 * 4 * 16 * 17 * sizeof(float);
-            const bool big = v->big_min_tiles > 0 && nb >= v->big_min_tiles && Hr % 16 == 0 && big_lds <= 160 * 1024;
-            (void)big;
-            m.fused = (v->fuse_fc2 && !tf && gmax[g] < (1 << CAND_TAG_BITS)) ? 1 : 0;
-        }
+        m.fused = (v->fuse_fc2 && !tf && cp.gmax[g] < (1 << CAND_TAG_BITS)) ? 1 : 0;
         m.Hr = Hr; m.Hf = d.Hf; m.n_cls = d.n_cls; m.upsample = d.upsample_t;
     }
-    for (int g = 0; g < n_grp; ++g)       // replay 0's slot row and Gcond rows
-        hipLaunchKernelGGL(ar_next_row_kernel, dim3(tiles[g] * 16), dim3(256), 0, s, models[g], (const ArCall *)v->grp[g].call);
+    for (int g = 0; g < cp.n_grp; ++g)    // replay 0's slot row and Gcond rows
+        hipLaunchKernelGGL(ar_next_row_kernel, dim3(cp.tiles[g] * 16), dim3(256), 0, s, models[g], (const ArCall *)v->grp[g].call);
 
     HIP_TRY(hipEventRecord(v->ev0, s));
     if (v->use_graph) {
         hipGraphExec_t exec[2] = {nullptr, nullptr};
-        for (int g = 0; g < n_grp; ++g) {
-            auto &G = v->grp[g];
-            // a graph bakes its ArModel (buffer pointers): drop cached graphs if a workspace moved
-            const void *now[8] = {G.har.p, G.a1.p, G.cand_s.p, G.cand_k.p, G.cur.p, G.gcur.p, G.candg.p, nullptr};
-            if (memcmp(G.baked, now, sizeof now) != 0) {
-                for (auto &kv : G.graphs) (void)hipGraphExecDestroy(kv.second);
-                G.graphs.clear();
-                memcpy(G.baked, now, sizeof now);
-            }
-            const int gkey = (((tiles[g] * 17 + models[g].live_last) * 2 + models[g].lead6) * 2 + (tf ? 1 : 0)) * 3 + models[g].fused;   // what the capture bakes
-            auto it = G.graphs.find(gkey);
-            if (it == G.graphs.end()) {
-                hipGraph_t gr = nullptr;
-                hipGraphExec_t ge = nullptr;
-                HIP_TRY(hipStreamBeginCapture(v->cap_stream, hipStreamCaptureModeThreadLocal));
-                int rc = launch_ar_steps(v, models[g], G.call, tiles[g], S, tf, v->cap_stream);
-                hipError_t e = hipStreamEndCapture(v->cap_stream, &gr);     // always end the capture, also on failure
-                if (rc != VQCPC_OK || e != hipSuccess) {
-                    if (gr) (void)hipGraphDestroy(gr);
-                    if (rc != VQCPC_OK) return rc;
-                    HIP_TRY(e);
-                }
-                e = hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(gr);
-                HIP_TRY(e);
-                it = G.graphs.emplace(gkey, ge).first;
-            }
-            exec[g] = it->second;
-        }
-        if (n_grp == 2) {                 // group 1 runs on the side stream.  (Round 1 started it a fixed 12 000 cycles late "to
+        for (int g = 0; g < cp.n_grp; ++g) TRY(group_graph(v, g, models[g], cp.tiles[g], tf, &exec[g]));
+        if (cp.n_grp == 2) {              // group 1 runs on the side stream.  (Round 1 started it a fixed 12 000 cycles late "to
             HIP_TRY(hipEventRecord(v->ev_fork, s));                     // de-phase the groups": measured with and without, and with
             HIP_TRY(hipStreamWaitEvent(v->side_stream, v->ev_fork, 0));  // 40 000 -- the same 23.4 / 40.6 us per step at 256 / 512
         }                                                               // utterances; the streams drift over 200 replays anyway.)
-        const int nr = rep[0] > rep[1] ? rep[0] : rep[1];
+        const int nr = cp.rep[0] > cp.rep[1] ? cp.rep[0] : cp.rep[1];
         for (int r = 0; r < nr; ++r) {
-            if (r < rep[0]) HIP_TRY(hipGraphLaunch(exec[0], s));
-            if (n_grp == 2 && r < rep[1]) HIP_TRY(hipGraphLaunch(exec[1], v->side_stream));
+            if (r < cp.rep[0]) HIP_TRY(hipGraphLaunch(exec[0], s));
+            if (cp.n_grp == 2 && r < cp.rep[1]) HIP_TRY(hipGraphLaunch(exec[1], v->side_stream));
             if (tf && ((r + 1) % v->tf_chunk_replays == 0 || r + 1 == nr))
                 TRY(tf_chunk_gemms(v, B, Ts, calls[0].CH, r / v->tf_chunk_replays, logits, s));
         }
-        if (n_grp == 2) {
+        if (cp.n_grp == 2) {
             HIP_TRY(hipEventRecord(v->ev_join, v->side_stream));
             HIP_TRY(hipStreamWaitEvent(s, v->ev_join, 0));
         }
     } else {
         for (int t0 = 0, r = 0; t0 < max_t; t0 += S, ++r) {
-            TRY(launch_ar_steps(v, models[0], v->grp[0].call, nbt, S, tf, s));
+            TRY(launch_ar_steps(v, models[0], v->grp[0].call, cp.tiles[0], S, tf, s));
             if (tf && ((r + 1) % v->tf_chunk_replays == 0 || t0 + S >= max_t))
                 TRY(tf_chunk_gemms(v, B, Ts, calls[0].CH, r / v->tf_chunk_replays, logits, s));
         }
@@ -2165,9 +1660,43 @@ static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int 
     HIP_TRY(hipEventRecord(v->ev1, s));
     v->last_steps = max_t;
     v->last_slots = n_slots;
-    v->last_call = calls[0]; v->last_model = models[0]; v->have_last = true;
-    if (models[0].fused) v->persist_pending = true;      // an in-kernel candidate wait may report a timeout
+    v->last_call = calls[0]; v->last_model = models[0]; v->last_path = 0;
+    if (models[0].fused) v->status_pending = true;      // an in-kernel candidate wait may report a timeout
     return VQCPC_OK;
+}
+
+// Shared driver of generate() and logits(): validate and plan on the host, upload the tables and run the conditioning, then
+// the decode loop the plan chose.
+static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int B, int Tc, const int *n_codes_host,
+                  const int64_t *inputs, int Ts, unsigned long long seed, unsigned utt_base,
+                  const uint32_t *utt_ids_host, float *wav,
+                  int64_t *mulaw, float *logits, int max_steps, hipStream_t s) {
+    const auto &d = v->d;
+    const int Hr = d.Hr, dl = 2 * d.Hp, Lout = d.upsample_t * 2 * Tc;
+    CallPlan cp;
+    TRY(plan_call(v, B, Tc, n_codes_host, inputs != nullptr, Ts, max_steps, utt_base, utt_ids_host, cp));
+    TRY(status_check(v, false));          // has an earlier call's hand-off reported already?  (nothing is cleared without a sync)
+    v->epoch = (v->epoch + 1u) & 0xffffffu;
+    if (v->epoch == 0) v->epoch = 1;
+    // upload through the pinned arena: no synchronisation of the caller's stream
+    TRY(v->stage.begin(cp.lens.size() * sizeof(int) + (cp.table[0].size() + cp.table[1].size()) * sizeof(ArSlot) +
+                       (size_t)(cp.tiles[0] + cp.tiles[1]) * 16 * sizeof(ArSlot) + 2 * sizeof(ArCall) + 256 +
+                       (size_t)8 * XM_BX * (B + 1) * sizeof(XdSeg) + (size_t)2 * (B + 16) * sizeof(int)));
+    TRY(v->len.reserve(cp.lens.size() * sizeof(int)));
+    TRY(v->stage.upload(v->len.p, cp.lens.data(), cp.lens.size() * sizeof(int), s));
+    TRY(v->gbase.reserve(cp.gbase.size() * sizeof(int)));
+    TRY(v->stage.upload(v->gbase.p, cp.gbase.data(), cp.gbase.size() * sizeof(int), s));
+    const size_t crows = cp.grows > 0 ? (size_t)cp.grows : 1;
+    TRY(v->cond.reserve(crows * dl * sizeof(float)));
+    TRY(run_condition(v, idx, spk, B, Tc, v->len.as<int>(), v->gbase.as<int>(), (size_t)cp.grows, v->cond.as<float>(), s));
+    TRY(v->gcond.reserve(crows * 3 * Hr * sizeof(float)));
+    if (cp.grows > 0)
+        TRY(vq_gemm_chain(v->cond.as<float>(), dl, v->w_cond, v->b_ih, v->gcond.as<float>(), 3 * Hr, (int)cp.grows, 3 * Hr, dl, dl, s));
+    if (wav) HIP_TRY(hipMemsetAsync(wav, 0, (size_t)B * Lout * sizeof(float), s));
+    if (mulaw) HIP_TRY(hipMemsetAsync(mulaw, 0, (size_t)B * Lout * sizeof(int64_t), s));
+    if (v->last_path != 0) v->last_path = 1;      // a call that fails from here on ran no decode loop
+    if (cp.dp.path != 0) return run_resident(v, cp, 2 * Tc, seed, wav, mulaw, s);
+    return run_launch_path(v, cp, inputs, 2 * Tc, Ts, seed, wav, mulaw, logits, s);
 }
 
 extern "C" int vqcpc_vocoder_generate(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc,
@@ -2196,7 +1725,7 @@ extern "C" int vqcpc_vocoder_logits(vqcpc_vocoder *v, const int64_t *x, const in
 // the previous repetition's granules already tagged with it and time the launch without its hand-off.
 extern "C" int vqcpc_vocoder_kernel_times(vqcpc_vocoder *v, int reps, float *out_us, void *stream) {
     VQ_REQUIRE(v && out_us && reps > 0, "vqcpc_vocoder_kernel_times: bad argument");
-    VQ_REQUIRE(v->have_last, "vqcpc_vocoder_kernel_times: call generate() or logits() first");
+    VQ_REQUIRE(v->last_path == 0, "vqcpc_vocoder_kernel_times: call generate() or logits() first");
     hipStream_t s = (hipStream_t)stream;
     ArCall c = v->last_call;
     c.t_base = 1;                        // a mid-utterance step (t = 1: candidates are merged, Gemb gathered)
@@ -2238,8 +1767,8 @@ extern "C" int vqcpc_vocoder_glue(vqcpc_vocoder *v, const int64_t *idx, const in
     const auto &d = v->d;
     const size_t ng = (size_t)B * 2 * Tc * (d.dz + d.ds);
     hipLaunchKernelGGL(glue_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, speaker, v->code_emb,
-                       v->spk_emb, series, B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->abort_dev, v->epoch << 8, nullptr, nullptr);
-    v->persist_pending = true;
+                       v->spk_emb, series, B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status_dev, v->epoch << 8, nullptr, nullptr);
+    v->status_pending = true;
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }
