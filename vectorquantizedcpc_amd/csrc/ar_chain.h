@@ -162,7 +162,8 @@ __device__ __forceinline__ float chain_regs(const float *w, const float *opnd) {
     return acc;
 }
 // The same chain for ONE or TWO operand vectors (two decode slots) with its weights streamed from LDS a phase ahead of their use: a
-// service wave must not hold 112 weights next to everything else it keeps.  The weights of a lane's chain are NT / 4 16-byte words,
+// service wave must not hold 112 weights next to everything else it keeps (four slots, fc1 on wave 0: 112 pinned weights spill even
+// with a loop of its own, and the fits of up to 9 pinned groups run slower than this -- profiles/r05_fc1_pin_sweep.txt).  The weights of a lane's chain are NT / 4 16-byte words,
 // word i at wp[i * WS]: the words of the WS lane-chains of a wave are interleaved ([word][lane-chain]), so that a wave's read of word
 // i is one contiguous run -- with a lane's chain contiguous ([lane-chain][NT], 448 bytes apart) the sixteen lanes of a read group hit
 // four bank windows four ways each.  w0 = the weights of phase 0, already in registers (requested before the barrier the chain waits

@@ -65,7 +65,24 @@ __device__ __forceinline__ void ps_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// libm gates: the sequence scans of scan.hip, pinned against the reference's own fixtures
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// Gates of the sample loop's GRU cell update (every decode form: vocoder.hip, ar_xcd.hip, ar_xcm.hip -- they must give the same
+// bits) on the hardware transcendentals: v_exp_f32 (2^x) and v_rcp_f32, ~1 ulp each, without the range reduction of OCML's expf
+// and the IEEE divide sequence and their branches -- the cell update runs on one wave on the step's critical path
+// (profiles/r05_ab_gate_math.txt).  The ends saturate exactly: 2^x overflows to +inf and rcp(+inf) = 0, so sigmoid -> 0 / 1 and tanh -> -1 / +1.
+// Every product and sum is written out (-ffp-contract=off).
+constexpr float GATE_LOG2E = 1.44269504088896340736f;
+__device__ __forceinline__ float gate_sigmoid(float v) {
+    const float e = __builtin_amdgcn_exp2f(-v * GATE_LOG2E);
+    return __builtin_amdgcn_rcpf(1.0f + e);
+}
+__device__ __forceinline__ float gate_tanh(float v) {            // 1 - 2 / (1 + e^{2v})
+    const float e = __builtin_amdgcn_exp2f(v * (2.0f * GATE_LOG2E));
+    const float q = __builtin_amdgcn_rcpf(1.0f + e);
+    return 1.0f - 2.0f * q;
+}
 
 // Philox4x32-10, word `k & 3` of counter (t, utt, k >> 2, 0): the sampling protocol's stream.
 __device__ __forceinline__ unsigned philox_word(unsigned c0, unsigned c1, unsigned c2, unsigned k0, unsigned k1, int w) {

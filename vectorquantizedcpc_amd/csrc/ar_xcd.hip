@@ -361,8 +361,13 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
                 // busy; fc1 -- the head of the step's critical path -- ran at a third of the matrix pipe, and the 60 vector instructions between its
                 // last term and the a_t stores took 0.4..0.7 us among the others' matrix instructions (profiles/r04_mfma_chains.txt)
 #if XD_HOLD
+                // Bounded: behind barrier A wave 0 either posts the flag, with no wait in between, or it leaves because it read *s_abort
+                // set -- and *s_abort is never cleared within a call.  So the flag comes or *s_abort is seen; then the chain runs on
+                // whatever it reads, and the wave leaves at barrier B.
                 if ((wave & 3) == 0)
-                    while (__hip_atomic_load(s_ctl + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != (int)tag) __builtin_amdgcn_s_sleep(2);
+                    while (__hip_atomic_load(s_ctl + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != (int)tag &&
+                           __hip_atomic_load(s_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+                        __builtin_amdgcn_s_sleep(2);
 #endif
                 chain_mfma_regs<0, XD_GSPLIT>(a4, w, opm, cur);
                 if (fc2_wave) fc2_and_draw();
@@ -501,9 +506,9 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
                 if (st_active && cu < UPB) {
                     const int xe = st_first ? NC / 2 : x;
                     const float e0 = gemb[(xe * 3 + 0) * UPB + cu], e1 = gemb[(xe * 3 + 1) * UPB + cu], e2 = gemb[(xe * 3 + 2) * UPB + cu];
-                    const float r = sigmoidf_((e0 + g0) + s0);
-                    const float z = sigmoidf_((e1 + g1) + s1);
-                    const float nn = tanhf((e2 + g2) + r * sn);
+                    const float r = gate_sigmoid((e0 + g0) + s0);
+                    const float z = gate_sigmoid((e1 + g1) + s1);
+                    const float nn = gate_tanh((e2 + g2) + r * sn);
                     hn = (1.0f - z) * nn + z * hold;
                     hprev = hn;
                 }

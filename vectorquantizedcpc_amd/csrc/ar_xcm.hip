@@ -366,9 +366,9 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
                 float hn = 0.f;
                 if (active) {
                     const float *cp = gcl + cs * 84 + cu;
-                    const float r = sigmoidf_((e0 + cp[0]) + s0);
-                    const float z = sigmoidf_((e1 + cp[UPB]) + s1);
-                    const float nn = tanhf((e2 + cp[2 * UPB]) + r * sn);
+                    const float r = gate_sigmoid((e0 + cp[0]) + s0);
+                    const float z = gate_sigmoid((e1 + cp[UPB]) + s1);
+                    const float nn = gate_tanh((e2 + cp[2 * UPB]) + r * sn);
                     hn = (1.0f - z) * nn + z * hold;
                     hprev = hn;
                 }

@@ -520,9 +520,9 @@ __global__ __launch_bounds__(64 * (4 + NB)) void ar_gru_kernel(ArModel m, const 
             const float gr = first ? 0.f : ((red[g][0][u][b] + red[g][1][u][b]) + red[g][2][u][b]) + red[g][3][u][b];
             const float gz = first ? 0.f : ((red[g][0][4 + u][b] + red[g][1][4 + u][b]) + red[g][2][4 + u][b]) + red[g][3][4 + u][b];
             const float gn = first ? 0.f : ((red[g][0][8 + u][b] + red[g][1][8 + u][b]) + red[g][2][8 + u][b]) + red[g][3][8 + u][b];
-            const float r = sigmoidf_((ge0 + gc0) + (gr + bh0));
-            const float z = sigmoidf_((ge1 + gc1) + (gz + bh1));
-            const float n = tanhf((ge2 + gc2) + r * (gn + bh2));
+            const float r = gate_sigmoid((ge0 + gc0) + (gr + bh0));
+            const float z = gate_sigmoid((ge1 + gc1) + (gz + bh1));
+            const float n = gate_tanh((ge2 + gc2) + r * (gn + bh2));
             const float hn = (1.0f - z) * n + z * hold;
             hout[hi] = hn;
             if (hallp) *hallp = hn;
@@ -671,9 +671,9 @@ __global__ __launch_bounds__(1024) void ar_gru_big_kernel(ArModel m, const ArCal
                 const float gr = first ? 0.f : ((red[q][0][0][ul][b] + red[q][0][1][ul][b]) + red[q][0][2][ul][b]) + red[q][0][3][ul][b];
                 const float gz = first ? 0.f : ((red[q][1][0][ul][b] + red[q][1][1][ul][b]) + red[q][1][2][ul][b]) + red[q][1][3][ul][b];
                 const float gn = first ? 0.f : ((red[q][2][0][ul][b] + red[q][2][1][ul][b]) + red[q][2][2][ul][b]) + red[q][2][3][ul][b];
-                const float rr = sigmoidf_((ge[p][0] + gc[p][0]) + (gr + bh[p][0]));
-                const float z = sigmoidf_((ge[p][1] + gc[p][1]) + (gz + bh[p][1]));
-                const float n = tanhf((ge[p][2] + gc[p][2]) + rr * (gn + bh[p][2]));
+                const float rr = gate_sigmoid((ge[p][0] + gc[p][0]) + (gr + bh[p][0]));
+                const float z = gate_sigmoid((ge[p][1] + gc[p][1]) + (gz + bh[p][1]));
+                const float n = gate_tanh((ge[p][2] + gc[p][2]) + rr * (gn + bh[p][2]));
                 const float hn = (1.0f - z) * n + z * hold[p];
                 hout[hi[p]] = hn;
                 if (hallp) hallp[4 * p] = hn;
