@@ -195,6 +195,27 @@ int vqcpc_vocoder_generate(vqcpc_vocoder *voc, const int64_t *idx, const int64_t
                            const uint32_t *utt_ids, float *wav, int64_t *mulaw, int max_steps,
                            void *stream);
 
+/* Streaming decode: the samples of vqcpc_vocoder_generate, chunk by chunk.  stream_open takes the arguments of generate (same
+ * meaning; the utterance ids are fixed here) and runs the prenet over every utterance's full length (it is bidirectional, so all of
+ * idx is needed up front); the stream keeps that conditioning and the decoder state itself, so generate() calls on the same handle
+ * may run between chunks.  stream_next decodes samples [pos, pos + n_samples) of every utterance into DEVICE wav (B, n_samples)
+ * fp32 and mulaw (B, n_samples) int64 or NULL (row stride n_samples; columns past an utterance's end are zero, as in generate) and
+ * advances pos; n_samples > 0 and a multiple of upsample_t.  It sets vqcpc_vocoder_last_path / _last_slots / _last_timing like a
+ * generate call, and returns VQCPC_ERR_INVALID once pos == total (2 * upsample_t * Tc).  The chunks concatenate to exactly the
+ * samples of one generate call with the same seed and ids.  A chunk is checked like a call (vqcpc_vocoder_check after a sync);
+ * stream_redo runs the last chunk again from the state it started from -- same samples -- e.g. after check reported that the
+ * resident decoders' workgroups were not dealt 32 per XCD.  Chunks run on the per-XCD decoders (xcd) up to xcm_max utterances,
+ * more than 32 back to back in their slots, never on the matrix-core form (xcm); otherwise, and for other dimensions, on the
+ * launch-per-step kernels.  One chunk per stream in flight; close a stream before its vocoder is destroyed. */
+typedef struct vqcpc_vocoder_stream vqcpc_vocoder_stream;
+int vqcpc_vocoder_stream_open(vqcpc_vocoder *voc, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                              const int *n_codes, uint64_t seed, uint32_t utt_base, const uint32_t *utt_ids,
+                              vqcpc_vocoder_stream **out, void *stream);
+int vqcpc_vocoder_stream_next(vqcpc_vocoder_stream *st, int n_samples, float *wav, int64_t *mulaw, void *stream);
+int vqcpc_vocoder_stream_redo(vqcpc_vocoder_stream *st, float *wav, int64_t *mulaw, void *stream);
+int vqcpc_vocoder_stream_position(const vqcpc_vocoder_stream *st, int64_t *done, int64_t *total);
+void vqcpc_vocoder_stream_close(vqcpc_vocoder_stream *st);
+
 /* Replaces Vocoder.forward (network_vocoder.py:41-67; caller vocoder.py:62): teacher-forced
  * energies.  x DEVICE (B, Ts) int64 mu-law input samples, Ts <= 2*upsample_t*Tc;
  * logits DEVICE (B, Ts, n_cls) fp32.  Runs as a fused scan: with x given, only the GRU step is serial (one launch per

@@ -18,6 +18,8 @@ SYMBOLS = [
     "vqcpc_vocoder_create", "vqcpc_vocoder_destroy", "vqcpc_vocoder_generate",
     "vqcpc_vocoder_logits", "vqcpc_vocoder_condition", "vqcpc_vocoder_glue", "vqcpc_vocoder_set_option",
     "vqcpc_vocoder_last_timing", "vqcpc_vocoder_kernel_times",
+    "vqcpc_vocoder_stream_open", "vqcpc_vocoder_stream_next", "vqcpc_vocoder_stream_redo", "vqcpc_vocoder_stream_position",
+    "vqcpc_vocoder_stream_close",
     "vqcpc_melfront_create", "vqcpc_melfront_destroy", "vqcpc_melfront_frames", "vqcpc_melfront_run",
     "vqcpc_loudness_create", "vqcpc_loudness_destroy", "vqcpc_loudness_blocks", "vqcpc_loudness_integrated",
     "vqcpc_loudness_normalize",
@@ -89,6 +91,13 @@ def load():
     lib.vqcpc_vocoder_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.vqcpc_vocoder_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.vqcpc_vocoder_kernel_times.argtypes = [vp, i32, C.POINTER(C.c_float), vp]
+    lib.vqcpc_vocoder_stream_open.argtypes = [vp, i64p, i64p, i32, i32, C.POINTER(C.c_int), C.c_uint64, C.c_uint32,
+                                              C.POINTER(C.c_uint32), C.POINTER(vp), vp]
+    lib.vqcpc_vocoder_stream_next.argtypes = [vp, i32, vp, i64p, vp]
+    lib.vqcpc_vocoder_stream_redo.argtypes = [vp, vp, i64p, vp]
+    lib.vqcpc_vocoder_stream_position.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.vqcpc_vocoder_stream_close.argtypes = [vp]
+    lib.vqcpc_vocoder_stream_close.restype = None
     lib.vqcpc_melfront_create.argtypes = [i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(vp)]
     lib.vqcpc_melfront_destroy.argtypes = [vp]
     lib.vqcpc_melfront_destroy.restype = None

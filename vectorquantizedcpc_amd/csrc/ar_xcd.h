@@ -33,11 +33,23 @@ struct XdParams {
     int dbg_misplace;         // != 0: workgroup 0 reports the XCD next to its own (exercises the placement check: STATUS_MISPLACED, nothing written)
 };
 
+// Resumed segments (a chunk of a stream, vqcpc_vocoder_stream_next), ar_xcd.hip only: a launch with an XdResume runs
+// ar_xcd_resume_kernel, in which every segment takes one PRIMING step first -- its cell update publishes h_in (or 0), so that the
+// chains of that step make W_hh h_in -- and then its samples.  The draw of the priming step is emitted as column 0 of the row and
+// counts for nothing; a segment's len covers the priming step: len - 1 samples, at columns 1 ..  (A separate kernel argument: the
+// one-shot kernels' XdParams, and so their machine code, stay as they are.)
+struct XdResume {
+    int s0;                   // absolute sample index of every segment's first sample (a multiple of upsample): Philox counter s0 + lt, frame s0 / upsample + ..
+    const float *h_in;        // [rows][Hr] state to start from, or null: h = 0
+    const int *x_in;          // [rows] sample to start from, or null: n_cls / 2
+    float *h_out;             // [rows][Hr] state after the segment's last sample, or null
+};
+
 size_t xd_exchange_bytes(int bxt);
 // Dimensions this decoder is built for (the reference's: size_h_rnn 896, size_h_fc 256, 8-bit mu-law).
 bool xd_supported(int Hr, int Hf, int n_cls);
 int xd_pick_bxt(int slots_per_xcd);            // 1, 2, 4 (0: too many)
-int xd_launch(const XdParams &p, hipStream_t s);
+int xd_launch(const XdParams &p, hipStream_t s, const XdResume *rs = nullptr);
 
 // The same decoders for large batches (ar_xcm.hip): 16 decode slots per XCD on the matrix cores.  Same XdParams (bxt is
 // ignored: the layout is fixed at XM_BX slots per XCD), same schedule table, same status word.

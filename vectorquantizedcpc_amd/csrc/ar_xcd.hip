@@ -127,8 +127,10 @@ template <int BXT> struct Lds {
     static constexpr int total = ctl + 8;
 };
 
-template <int BXT>
-__global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
+// RESUME: every segment is a chunk of a stream (XdResume, ar_xcd.h): a priming step, then its samples from (h_in, x_in, s0).  The
+// one-shot kernels ar_xcd_kernel<BXT> are the RESUME = false copies and do not contain that code; ar_xcd_resume_kernel<BXT> the others.
+template <int BXT, bool RESUME>
+__device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &rp) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using L = Lds<BXT>;
     float *gemb = smem + L::gemb, *fc1w = smem + L::fc1w, *fc2w = smem + L::fc2w, *whx = smem + L::whx, *hc = smem + L::hc,
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
     for (unsigned e = tid; e < BXT; e += THREADS) {
         const XdSeg sg = (int)e < bx ? p.segs[(size_t)(xcc + 8 * e) * p.max_seg] : XdSeg{-1, 0, 0, 0u};
         seg_st[e * 8 + 0] = 0; seg_st[e * 8 + 1] = sg.len > 0 ? sg.row : -1; seg_st[e * 8 + 2] = sg.t0; seg_st[e * 8 + 3] = sg.len;
-        seg_st[e * 8 + 4] = (int)sg.utt; seg_st[e * 8 + 5] = 0; seg_st[e * 8 + 6] = 0;      // samples into / index of the conditioning frame
+        seg_st[e * 8 + 4] = (int)sg.utt; seg_st[e * 8 + 5] = 0; seg_st[e * 8 + 6] = RESUME ? rp.s0 / p.upsample : 0;      // samples into / index of the conditioning frame
         seg_st[e * 8 + 7] = sg.len > 0 ? ((const int *)(p.segs + (size_t)8 * BXT * p.max_seg))[sg.row] : 0;      // the utterance's first Gcond row
     }
     __syncthreads();
@@ -435,8 +437,13 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
         int st_erow = 0, st_eidx = 0, st_lt = 0;
         unsigned st_utt = 0u;
         float g0 = 0.f, g1 = 0.f, g2 = 0.f, hprev = 0.f;
+        // RESUME: raw step 0 of a segment primes (publishes h_in), its samples are raw steps 1 .. len - 1
+        bool st_prime = false, st_last = false;
+        int st_row = 0, st_xin = NC / 2;
+        float st_hin = 0.f;
         auto advance = [&](int tn) {
             st_active = false; st_first = false; st_emit = false;
+            if constexpr (RESUME) { st_prime = false; st_last = false; }
             if (!cell_on) return;
             int si = seg_st[cb * 8 + 0], row = seg_st[cb * 8 + 1], t0 = seg_st[cb * 8 + 2], len = seg_st[cb * 8 + 3];
             int fpos = seg_st[cb * 8 + 5], fidx = seg_st[cb * 8 + 6], gb = seg_st[cb * 8 + 7];
@@ -449,15 +456,27 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
                 if (si < p.max_seg) sg = p.segs[(size_t)(xcc + 8 * cb) * p.max_seg + si];
                 row = sg.len > 0 ? sg.row : -1; t0 = sg.t0; len = sg.len; utt = sg.utt;
                 lt = tn - t0;
-                fpos = 0; fidx = 0;
+                fpos = 0; fidx = RESUME ? rp.s0 / p.upsample : 0;
                 gb = row >= 0 ? ((const int *)(p.segs + (size_t)8 * BXT * p.max_seg))[row] : 0;
                 if (cu == 0) { seg_st[cb * 8 + 0] = si; seg_st[cb * 8 + 1] = row; seg_st[cb * 8 + 2] = t0; seg_st[cb * 8 + 3] = len; seg_st[cb * 8 + 4] = (int)utt;
-                               seg_st[cb * 8 + 5] = 0; seg_st[cb * 8 + 6] = 0; seg_st[cb * 8 + 7] = gb; }
+                               seg_st[cb * 8 + 5] = 0; seg_st[cb * 8 + 6] = fidx; seg_st[cb * 8 + 7] = gb; }
             }
             st_active = row >= 0 && lt >= 0 && lt < len;
             st_first = lt == 0;
             st_lt = lt; st_utt = utt;
-            if (BXT == 4 && cu == 0) { sinfo[cb * 2] = lt; sinfo[cb * 2 + 1] = (int)utt; }
+            if constexpr (RESUME) {
+                st_prime = st_active && lt == 0;
+                st_last = st_active && lt == len - 1 && lt >= 1;
+                st_active = st_active && lt >= 1;
+                st_first = lt == 1;
+                st_lt = rp.s0 + lt - 1;                               // the Philox counter: the sample's absolute index
+                if (st_prime) {
+                    st_row = row;
+                    st_xin = rp.x_in ? rp.x_in[row] : NC / 2;
+                    st_hin = rp.h_in && cu < UPB ? rp.h_in[(size_t)row * HR + UPB * rank + cu] : 0.f;
+                }
+            }
+            if (BXT == 4 && cu == 0) { sinfo[cb * 2] = st_lt; sinfo[cb * 2 + 1] = (int)utt; }
             if (st_active) {
                 if (fpos == p.upsample) { fpos = 0; fidx += 1; }
                 if (fpos == 0 && cu < UPB) {                         // next conditioning frame (once per hop)
@@ -496,7 +515,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
             XD_STAMP(0, 0);
             // ---- cell update: gsum of step t-1 is complete (barrier B), x_{t-1} was picked up before it
             float s0 = 0.f, s1 = 0.f, sn = 0.f, hold = 0.f;
-            if (st_active && !st_first) {
+            if (st_active && (RESUME || !st_first)) {                  // resumed: the priming step's chains made W_hh h_in
                 s0 = gsum[cb * 96 + cu]; s1 = gsum[cb * 96 + UPB + cu]; sn = gsum[cb * 96 + 2 * UPB + cu];
                 hold = hprev;
             }
@@ -504,13 +523,17 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
             if (cell_on) {
                 float hn = 0.f;
                 if (st_active && cu < UPB) {
-                    const int xe = st_first ? NC / 2 : x;
+                    const int xe = st_first ? (RESUME ? st_xin : NC / 2) : x;
                     const float e0 = gemb[(xe * 3 + 0) * UPB + cu], e1 = gemb[(xe * 3 + 1) * UPB + cu], e2 = gemb[(xe * 3 + 2) * UPB + cu];
                     const float r = gate_sigmoid((e0 + g0) + s0);
                     const float z = gate_sigmoid((e1 + g1) + s1);
                     const float nn = gate_tanh((e2 + g2) + r * sn);
                     hn = (1.0f - z) * nn + z * hold;
                     hprev = hn;
+                }
+                if constexpr (RESUME) {
+                    if (st_prime && cu < UPB) { hn = st_hin; hprev = hn; }
+                    if (st_last && rp.h_out && cu < UPB) rp.h_out[(size_t)st_row * HR + UPB * rank + cu] = hn;
                 }
                 if (cu < UPB) xd_put(gh, (((unsigned)(rank * BXT + cb) << 5) + cu) * 8u, ((u64)tag << 32) | __float_as_uint(hn), agent);
             }
@@ -634,13 +657,24 @@ __global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) {
 }
 
 template <int BXT>
+__global__ __launch_bounds__(THREADS) void ar_xcd_kernel(XdParams p) { xcd_decoder<BXT, false>(p, XdResume{}); }
+template <int BXT>
+__global__ __launch_bounds__(THREADS) void ar_xcd_resume_kernel(XdParams p, XdResume r) { xcd_decoder<BXT, true>(p, r); }
+
+template <int BXT>
 constexpr size_t lds_bytes() { return sizeof(float) * (size_t)Lds<BXT>::total; }
 
 template <int BXT>
-int launch_t(const XdParams &p, hipStream_t s) {
+int launch_t(const XdParams &p, hipStream_t s, const XdResume *rs) {
     constexpr size_t lds = lds_bytes<BXT>();
     static_assert(lds <= 160 * 1024, "LDS budget");
     // per launch, not once per process: the attribute belongs to the current device, and a process may hold handles on several
+    if (rs) {
+        HIP_TRY(hipFuncSetAttribute((const void *)ar_xcd_resume_kernel<BXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((ar_xcd_resume_kernel<BXT>), dim3(8 * NW), dim3(THREADS), lds, s, p, *rs);
+        HIP_TRY(hipGetLastError());
+        return VQCPC_OK;
+    }
     HIP_TRY(hipFuncSetAttribute((const void *)ar_xcd_kernel<BXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((ar_xcd_kernel<BXT>), dim3(8 * NW), dim3(THREADS), lds, s, p);
     HIP_TRY(hipGetLastError());
@@ -653,14 +687,15 @@ size_t xd_exchange_bytes(int bxt) { return (size_t)CTL_WORDS * 4 + (size_t)8 * x
 bool xd_supported(int Hr, int Hf, int n_cls) { return Hr == HR && Hf == HF && n_cls == NC; }
 int xd_pick_bxt(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= XD_MAX_BX ? 4 : 0; }
 
-int xd_launch(const XdParams &p, hipStream_t s) {
+int xd_launch(const XdParams &p, hipStream_t s, const XdResume *rs) {
     VQ_REQUIRE(p.bxt == 1 || p.bxt == 2 || p.bxt == 4, "xd_launch: bxt %d", p.bxt);
     VQ_REQUIRE(p.n_slots >= 1 && p.n_slots <= 8 * p.bxt, "xd_launch: %d slots do not fit 8 x %d", p.n_slots, p.bxt);
+    VQ_REQUIRE(!rs || (rs->s0 >= 0 && rs->s0 % p.upsample == 0), "xd_launch: resume at sample %d, not a multiple of %d", rs ? rs->s0 : 0, p.upsample);
     HIP_TRY(hipMemsetAsync(p.xg, 0, xd_exchange_bytes(p.bxt), s));
     switch (p.bxt) {
-        case 1: return launch_t<1>(p, s);
-        case 2: return launch_t<2>(p, s);
-        case 4: return launch_t<4>(p, s);
-        default: return launch_t<4>(p, s);
+        case 1: return launch_t<1>(p, s, rs);
+        case 2: return launch_t<2>(p, s, rs);
+        case 4: return launch_t<4>(p, s, rs);
+        default: return launch_t<4>(p, s, rs);
     }
 }

@@ -88,6 +88,15 @@ struct ArCall {
     // chunk is kept, row-major, for the two batched GEMMs (fc1 + ReLU, fc2) that follow the chunk
     float *hall;               // [B][CH][Hr] or null
     int CH, hall_t0;           // chunk length (a multiple of S); first step of the chunk in flight (advanced on device)
+    // A chunk of a stream (vqcpc_vocoder_stream_next).  Every utterance resumes at absolute sample s0: its slot rows carry
+    // t0 - s0 and s0 + len, so the step kernels see absolute sample indices (Philox counter, conditioning frame) unchanged, and
+    // wav / mulaw point s0 - 1 columns in front of a buffer whose column 0 takes sample s0 - 1 again.  ar_next_row_kernel
+    // seeds a resumed slot (h_in in its state column, x_in as every candidate of its first step) and copies a finished one's
+    // final state to h_out.  All null / 0 for a one-shot call.
+    const float *h_in;         // [B][Hr] or null: fresh start (s0 == 0)
+    const int *x_in;           // [B]
+    float *h_out;              // [B][Hr] or null
+    int s0;
 };
 
 // Timeline stamps of workgroup (0, 0) (100 MHz wall clock) for tools/decode_timeline.py: compiled in only
@@ -746,9 +755,35 @@ __global__ __launch_bounds__(256) void ar_next_row_kernel(ArModel m, const ArCal
     const int sg = blockIdx.x;
     const ArCall c = *cp;
     const int r = c.t_base / c.S;
-    if (sg >= c.Sp || r >= c.n_rep) return;
+    if (sg >= c.Sp) return;
+    if (c.h_out && r > 0 && r - 1 < c.n_rep) {
+        // stream chunk: an utterance that ended in the replay just run leaves its state (nothing has written its column since)
+        const ArSlot pv = c.slots[(size_t)(r - 1) * c.Sp + sg];
+        const int end = pv.t0 + pv.len;
+        if (pv.row >= 0 && end > c.t_base - c.S && end <= c.t_base) {
+            const float *hb = m.hbuf + (size_t)(end & 1) * c.nbt * m.Hr * 16;
+            for (int k = threadIdx.x; k < m.Hr; k += 256) c.h_out[(size_t)pv.row * m.Hr + k] = hb[hl_index(m.Hr, sg, k)];
+        }
+        __syncthreads();
+    }
+    if (r >= c.n_rep) return;
     const ArSlot sl = c.slots[(size_t)r * c.Sp + sg];
     if (threadIdx.x == 0) m.cur[sg] = sl;
+    if (c.h_in && sl.row >= 0 && c.t_base - sl.t0 == c.s0) {
+        // stream chunk: a resumed utterance starts in this replay (at local step 0: state parity 0) -- its first step is then an
+        // ordinary continuing one that finds h_in as its state and x_in as the drawn sample
+        for (int k = threadIdx.x; k < m.Hr; k += 256) m.hbuf[hl_index(m.Hr, sg, k)] = c.h_in[(size_t)sl.row * m.Hr + k];
+        const int nrg = m.n_cls >> 4, x = c.x_in[sl.row];
+        for (int q = threadIdx.x; q < nrg; q += 256) {
+            if (m.fused) {
+                const unsigned tag = (unsigned)c.t_base & ((1u << CAND_TAG_BITS) - 1u);
+                m.candg[((size_t)(sg >> 4) * nrg + q) * 16 + (sg & 15)] = ((u64)((tag << 10) | (unsigned)x) << 32) | __float_as_uint(0.f);
+            } else {
+                m.cand_s[(size_t)sg * nrg + q] = 0.f;
+                m.cand_k[(size_t)sg * nrg + q] = x;
+            }
+        }
+    }
     if (!m.gc_replay || sl.row < 0 || c.t_base < sl.t0) return;
     const int f = (c.t_base - sl.t0) / m.upsample;
     if (f >= c.F) return;
@@ -1436,10 +1471,12 @@ struct CallPlan {
     std::vector<ArSlot> table[2];        // launch path: per group [replay][slot] what every decode slot is doing
 };
 
+static int plan_launch_tables(const vqcpc_vocoder *v, const int *samples, const std::vector<int> &order, bool tf, int B, int s0,
+                              CallPlan &cp);
 static int plan_call(const vqcpc_vocoder *v, int B, int Tc, const int *n_codes_host, bool tf, int Ts, int max_steps,
                      unsigned utt_base, const uint32_t *utt_ids_host, CallPlan &cp) {
     const auto &d = v->d;
-    const int Bp = (B + 15) / 16 * 16, S = v->steps_per_graph;
+    const int Bp = (B + 15) / 16 * 16;
     // per-utterance lengths: frames for the prenet, samples for the AR loop
     cp.lens.assign(2 * Bp, 0);
     cp.utt.resize(B);
@@ -1464,6 +1501,14 @@ static int plan_call(const vqcpc_vocoder *v, int B, int Tc, const int *n_codes_h
     VQ_REQUIRE(plan_decode(po, samples, cp.utt.data(), order, cp.dp), "vocoder: a decode slot's schedule does not fit the resident "
                "decoders (< 2^24 - 1 samples); use more slots or xcd = -1");
     if (cp.dp.path != 0) return VQCPC_OK;
+    return plan_launch_tables(v, samples, order, tf, B, 0, cp);
+}
+
+// The launch path's schedule: slots, tile groups and per-replay slot tables.  s0 > 0 (a stream chunk): every utterance resumes at
+// absolute sample s0, and its slot rows say t0 - s0 and s0 + len (ArCall::s0).
+static int plan_launch_tables(const vqcpc_vocoder *v, const int *samples, const std::vector<int> &order, bool tf, int B, int s0,
+                              CallPlan &cp) {
+    const int S = v->steps_per_graph;
     // Launch path (continuous batching): n_slots >= B: everything starts at 0.
     DecodePlan &dp = cp.dp;
     dp.xs = !tf && v->n_slots > 0 && v->n_slots < B ? v->n_slots : B;
@@ -1492,15 +1537,28 @@ static int plan_call(const vqcpc_vocoder *v, int B, int Tc, const int *n_codes_h
         for (int q = slot0; q < q_end; ++q)
             for (const XdSeg &sg : dp.lists[q])
                 for (int r = sg.t0 / S; r < (sg.t0 + sg.len + S - 1) / S; ++r)
-                    cp.table[g][(size_t)r * Spg + (q - slot0)] = ArSlot{sg.row, sg.t0, sg.len, sg.utt};
+                    cp.table[g][(size_t)r * Spg + (q - slot0)] = ArSlot{sg.row, sg.t0 - s0, sg.len + s0, sg.utt};
     }
     return VQCPC_OK;
 }
 
+// What a stream chunk (vqcpc_vocoder_stream_next) hands the decode loops: every utterance resumes at absolute sample s0 from
+// (h_in, x_in) -- null at s0 = 0 -- and leaves its final h in h_out.  wav / mulaw are the stream's (B, Lout = n + 1) buffers:
+// sample s0 + j at column 1 + j, column 0 takes what the first step re-emits.  The conditioning is the stream's own.
+struct Resume {
+    int s0, Lout;
+    const float *Gcond;
+    const int *gbase;                    // device copy of cp.gbase (the launch path reads it)
+    const float *h_in;
+    const int *x_in;
+    float *h_out;
+};
+
 // One resident, weight-stationary decoder per XCD (ar_xcd.hip, or its matrix-core form ar_xcm.hip): slot q runs the utterances
 // of cp.dp.lists[q] back to back (no replay boundaries here).
 static int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long long seed, float *wav, int64_t *mulaw,
-                        hipStream_t s) {
+                        hipStream_t s, const Resume *rs = nullptr) {
+    VQ_REQUIRE(!rs || cp.dp.path == 2, "vocoder stream: chunks do not run on the matrix-core decoders");
     const auto &d = v->d;
     const DecodePlan &pl = cp.dp;
     const int B = (int)cp.utt.size();
@@ -1527,9 +1585,14 @@ static int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned l
     xp.Lout = d.upsample_t * T2; xp.F = T2; xp.upsample = d.upsample_t; xp.agent_stores = v->xcd_agent_stores;
     xp.timeout_ticks = (unsigned)v->xcd_timeout_ms * 100000u; xp.dbg_drop_step = v->xcd_debug_drop_step;
     xp.dbg_misplace = v->xcd_debug_misplace;
+    XdResume xr{};
+    if (rs) {
+        xp.Lout = rs->Lout; xp.Gcond = rs->Gcond;
+        xr = XdResume{rs->s0, rs->h_in, rs->x_in, rs->h_out};
+    }
     v->xcd_debug_misplace = 0;                     // one shot: the repeated call finds the workgroups where they are
     HIP_TRY(hipEventRecord(v->ev0, s));
-    TRY(pl.path == 3 ? xm_launch(xp, s) : xd_launch(xp, s));
+    TRY(pl.path == 3 ? xm_launch(xp, s) : xd_launch(xp, s, rs ? &xr : nullptr));
     HIP_TRY(hipEventRecord(v->ev1, s));
     v->last_steps = (int)pl.longest;
     v->last_slots = pl.xs;
@@ -1572,7 +1635,7 @@ static int group_graph(vqcpc_vocoder *v, int g, const ArModel &m, int nbt, bool 
 // The launch-per-step kernels: per tile group its state buffers, call record (ArCall) and model (ArModel), then the replays of
 // steps_per_graph steps each -- captured graphs, or plain launches with use_graph = 0.
 static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs, int T2, int Ts, unsigned long long seed,
-                           float *wav, int64_t *mulaw, float *logits, hipStream_t s) {
+                           float *wav, int64_t *mulaw, float *logits, hipStream_t s, const Resume *rs = nullptr) {
     const auto &d = v->d;
     const int Hr = d.Hr, S = v->steps_per_graph, B = (int)cp.utt.size(), n_slots = cp.dp.xs, max_t = (int)cp.dp.longest;
     const bool tf = inputs != nullptr;     // teacher-forced scan: one group, GRU steps only, chunked GEMMs for fc1 / fc2
@@ -1603,6 +1666,13 @@ static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *
         c.Gcond = v->gcond.as<float>(); c.gbase = v->gbase.as<int>(); c.inputs = inputs; c.wav = wav; c.mulaw = mulaw; c.logits = logits;
         c.slots = G.slot_tab.as<ArSlot>(); c.S = S; c.Sp = Spg; c.n_rep = cp.rep[g] > 0 ? cp.rep[g] : 1;
         c.F = T2; c.Ts = Ts; c.Lout = d.upsample_t * T2; c.max_t = cp.gmax[g]; c.nbt = nb; c.seed = seed; c.t_base = 0;
+        if (rs) {
+            // sample s0 + j of a row goes to column 1 + j: the step kernels index with the absolute sample from a base s0 - 1 columns back
+            c.Gcond = rs->Gcond; c.gbase = rs->gbase; c.Lout = rs->Lout;
+            c.wav = wav ? (float *)((uintptr_t)wav - (uintptr_t)(rs->s0 - 1) * sizeof(float)) : nullptr;
+            c.mulaw = mulaw ? (int64_t *)((uintptr_t)mulaw - (uintptr_t)(rs->s0 - 1) * sizeof(int64_t)) : nullptr;
+            c.h_in = rs->s0 > 0 ? rs->h_in : nullptr; c.x_in = rs->x_in; c.h_out = rs->h_out; c.s0 = rs->s0;
+        }
         if (tf) {
             c.CH = v->tf_chunk_replays * S;
             TRY(v->hall.reserve((size_t)B * c.CH * Hr * sizeof(float)));
@@ -1777,4 +1847,156 @@ extern "C" int vqcpc_vocoder_condition(vqcpc_vocoder *v, const int64_t *idx, con
                                        float *cond, void *stream) {
     VQ_REQUIRE(v && idx && speaker && cond && B > 0 && Tc > 0, "vqcpc_vocoder_condition: bad argument");
     return run_condition(v, idx, speaker, B, Tc, nullptr, nullptr, 0, cond, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// streaming decode (vqcpc_vocoder_stream_*): the prenet runs once at open over every utterance's full length (it is
+// bidirectional); each chunk is then one call of the decode loop whose utterances RESUME -- at absolute sample pos, from the h
+// and x the previous chunk left -- so the chunks concatenate to exactly what one generate() call gives (same Philox counters,
+// same conditioning frames, same state).  Chunks plan with xcm = 0: up to xcm_max utterances run on the per-XCD decoders of
+// ar_xcd.hip (more than 32 back to back in their slots, each one a resumed segment), beyond that on the launch path.
+// ------------------------------------------------------------------------------------------
+struct vqcpc_vocoder_stream {
+    vqcpc_vocoder *v = nullptr;
+    int B = 0, Tc = 0;
+    unsigned long long seed = 0;
+    std::vector<unsigned> utt;
+    std::vector<int> samples, gbase;     // per utterance: samples in all, first conditioning row
+    long grows = 0;
+    DevBuf cond, gcond, gbase_dev;       // the stream's own prenet output [grows][2Hp] and conditioning rows (W_ih[:, de:] cond + b_ih) [grows][3Hr]
+    DevBuf h, x;                         // [2][B][Hr] fp32, [2][B] int: chunk c resumes from half c & 1 and leaves half (c + 1) & 1
+    DevBuf owav, omul;                   // (B, n + 1) decode buffers of the chunk in flight
+    int64_t pos = 0, total = 0, last_pos = 0;
+    int last_n = 0, chunks = 0;
+};
+
+// (B, n + 1) decode buffers -> the caller's (B, n) outputs; the row's last class is the next chunk's x_in
+__global__ void stream_out_kernel(const float *__restrict__ owav, const int64_t *__restrict__ omul, int B, int n, float *wav,
+                                  int64_t *mulaw, int *x_next) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * n) return;
+    const size_t b = i / n, j = i % n, src = b * (n + 1) + 1 + j;
+    wav[i] = owav[src];
+    if (mulaw) mulaw[i] = omul[src];
+    if (j == (size_t)n - 1) x_next[b] = (int)omul[src];
+}
+
+static int stream_chunk(vqcpc_vocoder_stream *st, int64_t pos, int n, int ci, float *wav, int64_t *mulaw, hipStream_t s) {
+    vqcpc_vocoder *v = st->v;
+    const auto &d = v->d;
+    const int B = st->B, Bp = (B + 15) / 16 * 16, Hr = d.Hr;
+    // samples of every utterance in [pos, pos + n); the resident decoders take one priming step in front of them
+    std::vector<int> nr(B), res(B);
+    for (int b = 0; b < B; ++b) {
+        const int64_t left = st->samples[b] - pos;
+        nr[b] = left <= 0 ? 0 : (left < n ? (int)left : n);
+        res[b] = nr[b] > 0 ? nr[b] + 1 : 0;
+    }
+    CallPlan cp;
+    cp.lens.assign(2 * Bp, 0);
+    cp.utt = st->utt; cp.gbase = st->gbase; cp.grows = st->grows;
+    const PlanOpts po{v->xcd, 0, v->xcm_max, v->xcm_max, v->xcd_slots, v->xcm_slots, v->n_slots, xd_supported(d.Hr, d.Hf, d.n_cls)};
+    VQ_REQUIRE(plan_decode(po, res.data(), cp.utt.data(), longest_first(res.data(), B), cp.dp), "vocoder stream: a decode slot's "
+               "schedule does not fit the resident decoders; use more slots or xcd = -1");
+    if (cp.dp.path == 0) TRY(plan_launch_tables(v, nr.data(), longest_first(nr.data(), B), false, B, (int)pos, cp));
+    TRY(status_check(v, false));
+    v->epoch = (v->epoch + 1u) & 0xffffffu;
+    if (v->epoch == 0) v->epoch = 1;
+    TRY(v->stage.begin((cp.table[0].size() + cp.table[1].size()) * sizeof(ArSlot) + (size_t)(cp.tiles[0] + cp.tiles[1]) * 16 * sizeof(ArSlot) +
+                       2 * sizeof(ArCall) + 256 + (size_t)8 * XD_MAX_BX * (B + 1) * sizeof(XdSeg) + (size_t)(B + 16) * sizeof(int)));
+    const size_t ob = (size_t)B * (n + 1);
+    TRY(st->owav.reserve(ob * sizeof(float)));
+    TRY(st->omul.reserve(ob * sizeof(int64_t)));
+    HIP_TRY(hipMemsetAsync(st->owav.p, 0, ob * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(st->omul.p, 0, ob * sizeof(int64_t), s));
+    const int in = ci & 1, out = (ci + 1) & 1;
+    Resume rs{(int)pos, n + 1, st->gcond.as<float>(), st->gbase_dev.as<int>(),
+              ci > 0 ? st->h.as<float>() + (size_t)in * B * Hr : nullptr, ci > 0 ? st->x.as<int>() + (size_t)in * B : nullptr,
+              st->h.as<float>() + (size_t)out * B * Hr};
+    if (v->last_path != 0) v->last_path = 1;      // a chunk that fails from here on ran no decode loop
+    if (cp.dp.path != 0) TRY(run_resident(v, cp, 2 * st->Tc, st->seed, st->owav.as<float>(), st->omul.as<int64_t>(), s, &rs));
+    else TRY(run_launch_path(v, cp, nullptr, 2 * st->Tc, 0, st->seed, st->owav.as<float>(), st->omul.as<int64_t>(), nullptr, s, &rs));
+    hipLaunchKernelGGL(stream_out_kernel, dim3((unsigned)(((size_t)B * n + 255) / 256)), dim3(256), 0, s, st->owav.as<float>(),
+                       st->omul.as<int64_t>(), B, n, wav, mulaw, st->x.as<int>() + (size_t)out * B);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_vocoder_stream_open(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                                         const int *n_codes, uint64_t seed, uint32_t utt_base, const uint32_t *utt_ids,
+                                         vqcpc_vocoder_stream **out, void *stream) {
+    VQ_REQUIRE(v && idx && speaker && out, "vqcpc_vocoder_stream_open: null argument");
+    VQ_REQUIRE(B > 0 && Tc > 0, "vocoder stream: need B > 0 and Tc > 0 (got %d, %d)", B, Tc);
+    *out = nullptr;
+    const auto &d = v->d;
+    const int Bp = (B + 15) / 16 * 16, dl = 2 * d.Hp, Hr = d.Hr;
+    hipStream_t s = (hipStream_t)stream;
+    vqcpc_vocoder_stream *st = new vqcpc_vocoder_stream();
+    st->v = v; st->B = B; st->Tc = Tc; st->seed = seed;
+    st->total = (int64_t)2 * d.upsample_t * Tc;
+    std::vector<int> lens(2 * Bp, 0);
+    st->utt.resize(B); st->samples.resize(B); st->gbase.assign(Bp, 0);
+    int rc = VQCPC_OK;
+    DevBuf &cond = st->cond;
+    auto fail = [&](int code) { vqcpc_vocoder_stream_close(st); return code; };
+    for (int b = 0; b < B; ++b) {
+        const int nc = n_codes ? n_codes[b] : Tc;
+        if (nc < 0 || nc > Tc) { vq_set_error("vocoder stream: n_codes[%d] = %d outside [0, %d]", b, nc, Tc); return fail(VQCPC_ERR_INVALID); }
+        lens[b] = 2 * nc;
+        st->samples[b] = d.upsample_t * 2 * nc;
+        st->utt[b] = utt_ids ? utt_ids[b] : utt_base + (unsigned)b;
+        st->gbase[b] = (int)st->grows;
+        st->grows += 2 * nc;
+    }
+    if (st->grows >= (1L << 31)) { vq_set_error("vocoder stream: %ld conditioning frames", st->grows); return fail(VQCPC_ERR_INVALID); }
+    const size_t crows = st->grows > 0 ? (size_t)st->grows : 1;
+#define STRY(x) do { rc = (x); if (rc != VQCPC_OK) return fail(rc); } while (0)
+    STRY(status_check(v, false));
+    v->epoch = (v->epoch + 1u) & 0xffffffu;
+    if (v->epoch == 0) v->epoch = 1;
+    STRY(v->stage.begin(lens.size() * sizeof(int) + st->gbase.size() * sizeof(int) + 64));
+    STRY(v->len.reserve(lens.size() * sizeof(int)));
+    STRY(v->stage.upload(v->len.p, lens.data(), lens.size() * sizeof(int), s));
+    STRY(st->gbase_dev.reserve(st->gbase.size() * sizeof(int)));
+    STRY(v->stage.upload(st->gbase_dev.p, st->gbase.data(), st->gbase.size() * sizeof(int), s));
+    STRY(cond.reserve(crows * dl * sizeof(float)));
+    STRY(run_condition(v, idx, speaker, B, Tc, v->len.as<int>(), st->gbase_dev.as<int>(), (size_t)st->grows, cond.as<float>(), s));
+    STRY(st->gcond.reserve(crows * 3 * Hr * sizeof(float)));
+    if (st->grows > 0)
+        STRY(vq_gemm_chain(cond.as<float>(), dl, v->w_cond, v->b_ih, st->gcond.as<float>(), 3 * Hr, (int)st->grows, 3 * Hr, dl, dl, s));
+    STRY(st->h.reserve((size_t)2 * B * Hr * sizeof(float)));
+    STRY(st->x.reserve((size_t)2 * B * sizeof(int)));
+#undef STRY
+    *out = st;
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_vocoder_stream_next(vqcpc_vocoder_stream *st, int n_samples, float *wav, int64_t *mulaw, void *stream) {
+    VQ_REQUIRE(st && wav, "vqcpc_vocoder_stream_next: null argument");
+    const int up = st->v->d.upsample_t;
+    VQ_REQUIRE(n_samples > 0 && n_samples % up == 0, "vocoder stream: n_samples = %d must be a positive multiple of %d", n_samples, up);
+    VQ_REQUIRE(st->pos < st->total, "vocoder stream: all %lld samples have been decoded", (long long)st->total);
+    TRY(stream_chunk(st, st->pos, n_samples, st->chunks, wav, mulaw, (hipStream_t)stream));
+    st->last_pos = st->pos; st->last_n = n_samples;
+    st->chunks += 1;
+    st->pos = st->pos + n_samples < st->total ? st->pos + n_samples : st->total;
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_vocoder_stream_redo(vqcpc_vocoder_stream *st, float *wav, int64_t *mulaw, void *stream) {
+    VQ_REQUIRE(st && wav, "vqcpc_vocoder_stream_redo: null argument");
+    VQ_REQUIRE(st->chunks > 0, "vocoder stream: no chunk to repeat");
+    return stream_chunk(st, st->last_pos, st->last_n, st->chunks - 1, wav, mulaw, (hipStream_t)stream);
+}
+
+extern "C" int vqcpc_vocoder_stream_position(const vqcpc_vocoder_stream *st, int64_t *done, int64_t *total) {
+    VQ_REQUIRE(st && done && total, "vqcpc_vocoder_stream_position: null argument");
+    *done = st->pos; *total = st->total;
+    return VQCPC_OK;
+}
+
+extern "C" void vqcpc_vocoder_stream_close(vqcpc_vocoder_stream *st) {
+    if (!st) return;
+    for (DevBuf *b : {&st->cond, &st->gcond, &st->gbase_dev, &st->h, &st->x, &st->owav, &st->omul}) b->release();
+    delete st;
 }

@@ -8,6 +8,7 @@ available offline; ``RNNMSVocoder`` below is this project's statement of it (sha
 hold parameters; all arithmetic runs in ``libvqcpc_hip.so``.
 """
 import ctypes as C
+import numbers
 from dataclasses import dataclass, field
 
 import torch
@@ -286,6 +287,37 @@ class Vocoder(nn.Module):
         return (wav, mulaw) if return_mulaw else wav
 
     @torch.no_grad()
+    def generate_stream(self, z: Tensor, speaker: Tensor, *, chunk_samples: int, n_codes=None, seed=None, utt_base=None,
+                        utt_ids=None, return_mulaw: bool = False) -> "VocoderStream":
+        """``generate`` chunk by chunk: an iterable of (B, n) device waveforms (or ``(wav, mulaw)`` pairs) of ``chunk_samples``
+        samples each, the last one shorter; ``torch.cat(list(stream), 1)`` equals ``generate(...)`` with the same seed and ids.
+        The prenet runs here, over all of ``z`` (it is bidirectional); every chunk then resumes the sample loop where the last
+        one stopped.  Default ids take ``B`` utterances from this module's count, as ``generate`` does."""
+        up = self.conf.rnnms.upsampling_t
+        if isinstance(chunk_samples, bool) or not isinstance(chunk_samples, numbers.Integral) or chunk_samples <= 0 or chunk_samples % up:
+            raise ValueError(f"chunk_samples must be a positive multiple of upsampling_t = {up} (got {chunk_samples!r})")
+        z, speaker = self._prep(z, speaker)
+        B, Tc = z.shape
+        h = self._native()
+        seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        if utt_base is None:
+            utt_base = self._utterances_done
+            if utt_ids is None:
+                self._utterances_done += B
+        ids = None
+        if utt_ids is not None:
+            ids = (C.c_uint32 * B)(*[int(v) & 0xFFFFFFFF for v in utt_ids])
+        nc = None
+        if n_codes is not None:
+            nc = (C.c_int * B)(*[int(v) for v in n_codes])
+        st = C.c_void_p()
+        with _lib.device_guard(z.device):
+            _lib.check(_lib.load().vqcpc_vocoder_stream_open(
+                h, z.data_ptr(), speaker.data_ptr(), B, Tc, nc, seed, int(utt_base) & 0xFFFFFFFF, ids, C.byref(st),
+                _lib.current_stream()))
+        return VocoderStream(self, h, st, B, int(chunk_samples), z.device, return_mulaw)
+
+    @torch.no_grad()
     def forward(self, x: Tensor, z: Tensor, speaker: Tensor) -> Tensor:
         """``network_vocoder.py:41-67``: teacher-forced energies (B, T_s, 2**bits)."""
         z, speaker = self._prep(z, speaker)
@@ -325,3 +357,77 @@ class Vocoder(nn.Module):
             _lib.check(_lib.load().vqcpc_vocoder_condition(self._native(), z.data_ptr(), speaker.data_ptr(), B, Tc,
                                                            out.data_ptr(), _lib.current_stream()))
         return out
+
+
+class VocoderStream:
+    """Chunks of one ``Vocoder.generate_stream`` call (``vqcpc_vocoder_stream_*``).  Each ``__next__`` decodes the next chunk,
+    synchronises its stream and checks the handle like ``generate``: if the resident decoders reported the chunk (a shared GPU),
+    it is decoded ONCE more from the state it started from -- the same samples -- with a warning; if that fails as well, the
+    stream is closed (the state the next chunk would start from is not there) and the error raised.  Keeps its vocoder alive;
+    ``close()`` frees the native stream (also at exhaustion and on garbage collection); ``position`` stays readable after it."""
+
+    def __init__(self, voc, handle, st, B, chunk, device, return_mulaw):
+        self._voc, self._handle, self._st = voc, handle, st
+        self._B, self._chunk, self._device, self._return_mulaw = B, chunk, device, return_mulaw
+        self._final = None                               # (done, total) at close
+
+    def __iter__(self):
+        return self
+
+    @property
+    def position(self):
+        """(samples decoded so far per utterance, samples in all = 2 * upsampling_t * T'); after ``close()`` the last values."""
+        if self._st is None:
+            return self._final
+        done, total = C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().vqcpc_vocoder_stream_position(self._st, C.byref(done), C.byref(total)))
+        return int(done.value), int(total.value)
+
+    @torch.no_grad()
+    def __next__(self):
+        if self._st is None:
+            if self._final is not None and self._final[0] < self._final[1]:
+                raise RuntimeError("VocoderStream was closed before its last chunk")
+            raise StopIteration
+        done, total = self.position
+        if done >= total:
+            self.close()
+            raise StopIteration
+        if self._voc._handle is None or self._voc._handle.value != self._handle.value:
+            raise RuntimeError("VocoderStream: the vocoder's native handle was rebuilt (.to(), refresh(), load_state_dict) "
+                               "after the stream was opened")
+        lib = _lib.load()
+        n = self._chunk
+        wav = torch.empty(self._B, n, device=self._device)
+        mulaw = torch.empty(self._B, n, dtype=torch.int64, device=self._device) if self._return_mulaw else None
+        mp = mulaw.data_ptr() if mulaw is not None else None
+        with _lib.device_guard(self._device):
+            _lib.check(lib.vqcpc_vocoder_stream_next(self._st, n, wav.data_ptr(), mp, _lib.current_stream()))
+            try:
+                self._voc.check()
+            except RuntimeError as e:
+                import warnings
+                warnings.warn(f"VocoderStream: chunk repeated ({e})")
+                try:
+                    _lib.check(lib.vqcpc_vocoder_stream_redo(self._st, wav.data_ptr(), mp, _lib.current_stream()))
+                    self._voc.check()
+                except BaseException:
+                    self.close()                     # no good state to go on from: later chunks would decode garbage
+                    raise
+        keep = min(n, total - done)
+        wav = wav[:, :keep]
+        if mulaw is not None:
+            return wav, mulaw[:, :keep]
+        return wav
+
+    def close(self):
+        if getattr(self, "_st", None) is not None:
+            self._final = self.position
+            _lib.load().vqcpc_vocoder_stream_close(self._st)
+            self._st = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
