@@ -319,7 +319,7 @@ class Vocoder(nn.Module):
 
     @torch.no_grad()
     def forward(self, x: Tensor, z: Tensor, speaker: Tensor) -> Tensor:
-        """``network_vocoder.py:41-67``: teacher-forced energies (B, T_s, 2**bits)."""
+        """``network_vocoder.py:41-67``: teacher-forced energies (B, T_s, 2**bits).  Synchronises its stream (``check()``)."""
         z, speaker = self._prep(z, speaker)
         x = x.detach().to(device=z.device, dtype=torch.int64).contiguous()
         B, Tc = z.shape
@@ -334,28 +334,32 @@ class Vocoder(nn.Module):
         with torch.cuda.device(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_logits(self._native(), x.data_ptr(), z.data_ptr(), speaker.data_ptr(),
                                                         B, Tc, Ts, logits.data_ptr(), _lib.current_stream()))
+            self.check()              # a bad z / speaker raises here, like nn.Embedding, and is not left latched for generate()
         return logits
 
     @torch.no_grad()
     def glue(self, z: Tensor, speaker: Tensor) -> Tensor:
-        """What ``network_vocoder.py:69-77`` hands to ``rnnms``: (B, 2T', dim_i_embedding + dim_speaker_embedding)."""
+        """What ``network_vocoder.py:69-77`` hands to ``rnnms``: (B, 2T', dim_i_embedding + dim_speaker_embedding).  Synchronises
+        its stream (``check()``)."""
         z, speaker = self._prep(z, speaker)
         B, Tc = z.shape
         out = torch.empty(B, 2 * Tc, self.conf.dim_i_embedding + self.conf.dim_speaker_embedding, device=z.device)
         with torch.cuda.device(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_glue(self._native(), z.data_ptr(), speaker.data_ptr(), B, Tc, out.data_ptr(),
                                                       _lib.current_stream()))
+            self.check()
         return out
 
     @torch.no_grad()
     def condition(self, z: Tensor, speaker: Tensor) -> Tensor:
-        """PreNet output (B, 2T', dim_voc_latent) -- stage-level checks."""
+        """PreNet output (B, 2T', dim_voc_latent) -- stage-level checks.  Synchronises its stream (``check()``)."""
         z, speaker = self._prep(z, speaker)
         B, Tc = z.shape
         out = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=z.device)
         with torch.cuda.device(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_condition(self._native(), z.data_ptr(), speaker.data_ptr(), B, Tc,
                                                            out.data_ptr(), _lib.current_stream()))
+            self.check()
         return out
 
 
