@@ -146,6 +146,42 @@ int vqcpc_encoder_check(vqcpc_encoder *enc);
 int vqcpc_encoder_context(vqcpc_encoder *enc, const float *z, int B, int Tz, float *c,
                           void *stream);
 
+/* ------------------------------------------------------------------ CPC scoring ------ */
+
+/* CPCLoss.state_dict() (model.py:187-189): predictors.{i}.weight (z_dim, c_dim), predictors.{i}.bias (z_dim), DEVICE.
+ * Only the first n_steps = n_prediction_steps / 2 predictors are ever used (model.py:181, :216), so only those are read.
+ * Supported: z_dim == 64; c_dim 64, 128, 256 or 512; 1 <= n_steps <= 16; 1 <= n_negatives <= 64; n_speakers,
+ * n_utterances >= 1 (n_speakers * n_utterances <= 65535). */
+typedef struct {
+    const float *weight[16], *bias[16];
+    int n_steps, n_speakers, n_utterances, n_negatives, z_dim, c_dim;
+} vqcpc_cpc_weights;
+
+typedef struct vqcpc_cpc vqcpc_cpc;
+
+/* Replaces CPCLoss.__init__ + load_state_dict (model.py:168-189; train_cpc.py:23-29).  Copies the predictors to the current
+ * device (synchronises once). */
+int vqcpc_cpc_create(const vqcpc_cpc_weights *w, vqcpc_cpc **out);
+void vqcpc_cpc_destroy(vqcpc_cpc *cpc);
+
+/* Replaces CPCLoss.forward (model.py:191-316) under no_grad: the forward VALUE of the objective (loss and per-step prediction
+ * accuracies, what train_cpc.py:128-131 logs) -- checkpoint scoring; no gradient exists.
+ * z DEVICE (N, T, z_dim), c DEVICE (N, T, c_dim), N = n_speakers * n_utterances utterances speaker-major, T >= n_steps + 2;
+ * L = T - n_steps anchors per utterance.
+ * Negatives: utt_index DEVICE (n_steps, Utt, Neg) int64 in [0, Utt) and seq_index DEVICE (n_steps, Spk, Utt, Neg, L) int64 in
+ * [0, L) = the two index arrays of model.py:282 for every step (seq_index AFTER the remainder of model.py:272); or both NULL =
+ * drawn in the kernel from (seed, stream_id) by the project's protocol (csrc/cpc_protocol.h, synth.cpc_negatives): the
+ * reference draws them from torch's global CPU generator, which no device kernel can share.  The arithmetic is the same
+ * either way.  Caller indices are CLAMPED into range on the device, silently: an out-of-range value cannot read out of
+ * bounds, and it is the caller that rejects it (the Python wrapper raises IndexError before the call).
+ * Outputs DEVICE: loss (1) = mean of step_loss (model.py:315); step_loss (n_steps) (model.py:305); accuracy (n_steps)
+ * (model.py:307-308; a negative that ties the positive leaves the position correct, as argmax's first maximum does);
+ * correct (n_steps, N, L) uint8 or NULL; scores (n_steps, N, 1 + Neg, L) fp32 = f of model.py:291 or NULL.
+ * Sums run in a fixed order (no atomics): equal inputs give equal bits.  Enqueues on `stream`, does not synchronise. */
+int vqcpc_cpc_score(vqcpc_cpc *cpc, const float *z, const float *c, int T, const int64_t *utt_index,
+                    const int64_t *seq_index, uint64_t seed, uint32_t stream_id, float *loss, float *step_loss,
+                    float *accuracy, uint8_t *correct, float *scores, void *stream);
+
 /* ------------------------------------------------------------------ Vocoder ---------- */
 
 /* Vocoder.state_dict(): own tables (network_vocoder.py:37-38) plus the RNN_MS core the

@@ -14,6 +14,7 @@ SYMBOLS = [
     "vqcpc_abi_version", "vqcpc_last_error", "vqcpc_device_count",
     "vqcpc_encoder_create", "vqcpc_encoder_destroy", "vqcpc_encoder_encode",
     "vqcpc_encoder_forward_stats", "vqcpc_encoder_context", "vqcpc_encoder_stage", "vqcpc_encoder_vq_encode", "vqcpc_encoder_set_option",
+    "vqcpc_cpc_create", "vqcpc_cpc_destroy", "vqcpc_cpc_score",
     "vqcpc_encoder_check", "vqcpc_vocoder_check", "vqcpc_vocoder_last_path", "vqcpc_vocoder_last_slots", "vqcpc_vocoder_workspace_bytes", "vqcpc_vocoder_plan",
     "vqcpc_vocoder_create", "vqcpc_vocoder_destroy", "vqcpc_vocoder_generate",
     "vqcpc_vocoder_logits", "vqcpc_vocoder_condition", "vqcpc_vocoder_glue", "vqcpc_vocoder_set_option",
@@ -33,6 +34,12 @@ class EncoderWeights(C.Structure):
                 ("codebook", C.c_void_p), ("rnn_w_ih", C.c_void_p), ("rnn_w_hh", C.c_void_p),
                 ("rnn_b_ih", C.c_void_p), ("rnn_b_hh", C.c_void_p),
                 ("in_channels", C.c_int), ("channels", C.c_int), ("n_embeddings", C.c_int),
+                ("z_dim", C.c_int), ("c_dim", C.c_int)]
+
+
+class CPCWeights(C.Structure):
+    _fields_ = [("weight", C.c_void_p * 16), ("bias", C.c_void_p * 16),
+                ("n_steps", C.c_int), ("n_speakers", C.c_int), ("n_utterances", C.c_int), ("n_negatives", C.c_int),
                 ("z_dim", C.c_int), ("c_dim", C.c_int)]
 
 
@@ -75,6 +82,10 @@ def load():
     lib.vqcpc_encoder_vq_encode.argtypes = [vp, vp, i32, vp, i64p, vp]
     lib.vqcpc_encoder_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.vqcpc_encoder_check.argtypes = [vp]
+    lib.vqcpc_cpc_create.argtypes = [C.POINTER(CPCWeights), C.POINTER(vp)]
+    lib.vqcpc_cpc_destroy.argtypes = [vp]
+    lib.vqcpc_cpc_destroy.restype = None
+    lib.vqcpc_cpc_score.argtypes = [vp, vp, vp, i32, i64p, i64p, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_vocoder_check.argtypes = [vp]
     lib.vqcpc_vocoder_last_path.argtypes = [vp]
     lib.vqcpc_vocoder_last_slots.argtypes = [vp]

@@ -6,6 +6,12 @@
                                                  --in-dir mels/ --out-dir out/wav
                                                  [--cpc-checkpoint .. --vocoder-checkpoint .. | --random-init] [--seed 13]
 
+    python -m vectorquantizedcpc_amd.cli score   --dataset datasets/2019/english --cpc-checkpoint ckpt.pt | --random-init
+                                                 [--speakers 8 --utterances 8 --negatives 17 --sample-frames 128 --seed 13]
+
+``score`` is one pass of ``train_cpc.py:104-148`` without the optimiser: the CPC loss, VQ loss, perplexity and per-step
+prediction accuracies of a checkpoint (its ``"encoder"`` and ``"cpc"`` entries) on the utterances of ``test.json``, grouped by
+the speaker their file name starts with (``<speaker>_<utterance>``).
 ``encode`` mirrors ``encode.py:14-67``.  ``convert`` mirrors ``convert.py:17-83`` from the mel onwards: inputs are
 ``<in_dir>/<utterance>.mel.npy`` or, if absent, ``<utterance>.wav`` (16 kHz) run through the HIP mel
 front-end (``preprocess.wave_to_mel`` = ``convert.py:54-70``).  For ``.wav`` inputs the output is re-normalised
@@ -19,7 +25,7 @@ from pathlib import Path
 
 import torch
 
-from . import ConfEncoder, ConfVocoder, Encoder, Vocoder, driver, io, loudness, synth
+from . import ConfCPC, ConfEncoder, ConfVocoder, CPCLoss, Encoder, Vocoder, driver, io, loudness, synth
 
 
 def _models(args, need_vocoder):
@@ -64,6 +70,30 @@ def encode_dataset(args) -> int:
         for p, r in zip(paths, driver.encode_utterances(enc, mels, max_batch=args.max_batch)):
             io.save_frames_text(out_dir / p.stem, r["z"])
     print(f"encoded {len(paths)} utterances -> {out_dir}")
+    return 0
+
+
+def score_dataset(args) -> int:
+    paths = io.read_test_metadata(args.dataset)
+    enc, _ = _models(args, need_vocoder=False)
+    cpc = CPCLoss(ConfCPC(args.prediction_steps, args.speakers, args.utterances, args.negatives, 64, 256))
+    cpc.load_state_dict(synth.cpc_state_dict(n_prediction_steps=args.prediction_steps) if args.random_init
+                        else io.load_cpc_checkpoint(args.cpc_checkpoint))
+    cpc = cpc.to(torch.device(args.device)).eval()
+    by_speaker = {}
+    for p in paths:
+        by_speaker.setdefault(p.stem.split("_")[0], []).append(io.load_mel(p))
+    r = driver.score_batches(enc, cpc, by_speaker, sample_frames=args.sample_frames, seed=args.seed)
+    if r["batches"] == 0:
+        print(f"no batch of {args.speakers} speakers x {args.utterances} utterances could be formed; skipped speakers: "
+              f"{r['speakers_skipped']}, left over: {r['speakers_left_over']}")
+        return 1
+    # train_cpc.py:146-148
+    print(f"cpc loss:{r['cpc_loss']:.2E}, vq loss:{r['vq_loss']:.2E}, perpexlity:{r['perplexity']:.3f}")
+    print([f"{a:.3f}" for a in r["accuracies"]])
+    print(f"scored {r['utterances']} utterances in {r['batches']} batches; speakers skipped (too few long-enough utterances): "
+          f"{len(r['speakers_skipped'])} {r['speakers_skipped']}; speakers left over after the last whole batch: "
+          f"{len(r['speakers_left_over'])} {r['speakers_left_over']}")
     return 0
 
 
@@ -127,15 +157,23 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert"):
+    for name in ("encode", "convert", "score"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
-        p.add_argument("--out-dir", required=True)
+        if name != "score":
+            p.add_argument("--out-dir", required=True)
         p.add_argument("--cpc-checkpoint")
         p.add_argument("--random-init", action="store_true", help="seeded random-init weights (no checkpoint ships with the reference)")
         p.add_argument("--device", default="cuda")
         p.add_argument("--max-batch", type=int, default=64)
-        if name == "encode":
+        if name == "score":                                   # config.py:42-47, :202
+            p.add_argument("--prediction-steps", type=int, default=12)
+            p.add_argument("--speakers", type=int, default=8)
+            p.add_argument("--utterances", type=int, default=8)
+            p.add_argument("--negatives", type=int, default=17)
+            p.add_argument("--sample-frames", type=int, default=128)
+            p.add_argument("--seed", type=int, default=synth.SEED)
+        elif name == "encode":
             p.add_argument("--save-auxiliary", action="store_true")
         else:
             p.add_argument("--vocoder-checkpoint")
@@ -145,7 +183,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if not args.random_init and not args.cpc_checkpoint:
         ap.error("give --cpc-checkpoint (and --vocoder-checkpoint for convert) or --random-init")
-    return encode_dataset(args) if args.cmd == "encode" else convert_dataset(args)
+    return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,8 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from .model import Encoder
+from . import synth
+from .model import CPCLoss, Encoder
 from .network_vocoder import Vocoder
 
 
@@ -206,3 +207,64 @@ def front_end_utterances(waves, rates, device, sr: int = 16000, max_batch: int =
             ref[i] = lufs[k]
         if clock: clock("mel")
     return mels, ref
+
+
+def score_groups(lengths_by_speaker, n_speakers: int, n_utterances: int, need_frames: int):
+    """Batches of one scoring pass: ``n_speakers`` speakers x the first ``n_utterances`` utterances of each that hold at least
+    ``need_frames`` mel frames.  -> (batches = lists of (speaker, [utterance ids]), speakers skipped for having too few
+    long-enough utterances, speakers left over after the last whole batch).  Nothing is dropped without being named."""
+    ready, skipped = [], []
+    for spk, lengths in lengths_by_speaker.items():
+        ids = [i for i, t in enumerate(lengths) if t >= need_frames][:n_utterances]
+        (ready if len(ids) == n_utterances else skipped).append((spk, ids))
+    whole = len(ready) - len(ready) % n_speakers
+    batches = [ready[i:i + n_speakers] for i in range(0, whole, n_speakers)]
+    return batches, [spk for spk, _ in skipped], [spk for spk, _ in ready[whole:]]
+
+
+def cut_positions(seed: int, batch: int, lengths: Sequence[int], need_frames: int) -> List[int]:
+    """Where each utterance of batch number ``batch`` is cut to ``need_frames`` frames: slot i starts at
+    ``w mod (T_i - need_frames + 1)``, w = word ``i & 3`` of Philox4x32-10(counter = (i >> 2, 2 << 16, batch, 0), key = seed)
+    -- the generator of the negative draws (``synth.cpc_negatives``: which = 0, 1), here with which = 2."""
+    import numpy as np
+    n = len(lengths)
+    ctr = np.zeros((n, 4), np.uint32)
+    ctr[:, 0] = np.arange(n) >> 2
+    ctr[:, 1] = 2 << 16
+    ctr[:, 2] = batch & 0xFFFFFFFF
+    words = synth.philox4x32_10(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    return [int(words[i, i & 3]) % (int(t) - need_frames + 1) for i, t in enumerate(lengths)]
+
+
+@torch.no_grad()
+def score_batches(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, sample_frames: int = 128, seed: int = 13, device=None):
+    """One pass of ``train_cpc.py:104-131`` without the optimiser: checkpoint scoring.  ``mels_by_speaker``: speaker ->
+    list of (80, T) mels.  Batches of ``cpc.n_speakers_per_batch`` speakers x ``cpc.n_utterances_per_speaker`` utterances,
+    each cut to ``sample_frames + n_prediction_steps`` mel frames (``config.py:202``) at a position drawn by
+    ``cut_positions`` (stream = batch number); ``encoder(mels)`` -> ``cpc(z, c, seed=seed, stream_id=batch)``.
+
+    Returns the running means the reference logs (``train_cpc.py:128-131``) -- ``cpc_loss``, ``vq_loss``, ``perplexity``,
+    ``accuracies`` (one per prediction step) -- with ``batches``, ``utterances`` and the speakers that could not be
+    scored: ``speakers_skipped`` (fewer than Utt long-enough utterances) and ``speakers_left_over`` (after the last whole
+    batch)."""
+    need = sample_frames + cpc.conf.n_prediction_steps
+    S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
+    dev = device if device is not None else next(encoder.parameters()).device
+    lengths = {spk: [int(m.shape[-1]) for m in mels] for spk, mels in mels_by_speaker.items()}
+    batches, skipped, left = score_groups(lengths, S, U, need)
+    res = {"cpc_loss": 0.0, "vq_loss": 0.0, "perplexity": 0.0, "accuracies": None, "batches": len(batches),
+           "utterances": len(batches) * S * U, "speakers_skipped": skipped, "speakers_left_over": left}
+    for b, group in enumerate(batches):
+        picked = [mels_by_speaker[spk][i] for spk, ids in group for i in ids]
+        starts = cut_positions(seed, b, [int(m.shape[-1]) for m in picked], need)
+        mels = torch.stack([m[:, s:s + need] for m, s in zip(picked, starts)]).to(dev)
+        z, c, vq_loss, perplexity = encoder(mels)
+        loss, acc = cpc(z, c, seed=seed, stream_id=b)
+        if hasattr(encoder, "check"):
+            encoder.check()                          # nothing incomplete may be reported
+        n = b + 1                                    # running means as train_cpc.py:128-131 keeps them
+        res["cpc_loss"] += (float(loss) - res["cpc_loss"]) / n
+        res["vq_loss"] += (float(vq_loss) - res["vq_loss"]) / n
+        res["perplexity"] += (float(perplexity) - res["perplexity"]) / n
+        res["accuracies"] = list(acc) if res["accuracies"] is None else [a + (x - a) / n for a, x in zip(res["accuracies"], acc)]
+    return res

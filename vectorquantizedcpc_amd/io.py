@@ -81,6 +81,13 @@ def load_encoder_checkpoint(path) -> Dict[str, torch.Tensor]:
     return ck["encoder"] if "encoder" in ck else ck
 
 
+def load_cpc_checkpoint(path) -> Dict[str, torch.Tensor]:
+    """``checkpoint["cpc"]`` (``train_cpc.py:23-29`` saves it next to ``"encoder"``), loaded without executing anything
+    from the file."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    return ck["cpc"] if "cpc" in ck else ck
+
+
 def load_vocoder_checkpoint(path, expected: Dict[str, torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """``checkpoint["vocoder"]`` (``convert.py:45``) or a Lightning checkpoint rooted at ``VocoderModel.model``
     (``vocoder.py:47``), loaded without executing anything from the file.

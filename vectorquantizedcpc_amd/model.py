@@ -1,4 +1,4 @@
-"""Drop-in ``Encoder`` / ``VQEmbeddingEMA`` for the reference's ``model.py`` (inference path).
+"""Drop-in ``Encoder`` / ``VQEmbeddingEMA`` / ``CPCLoss`` for the reference's ``model.py`` (inference and scoring paths).
 
 Same constructor (``Encoder(conf: ConfEncoder)``, ``model.py:17-34``), same
 ``state_dict()`` key set (``model.py:43-57``), same ``encode`` / ``forward`` signatures
@@ -11,7 +11,7 @@ import ctypes as C
 import weakref
 from dataclasses import dataclass
 from itertools import chain
-from typing import Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -275,3 +275,159 @@ class Encoder(nn.Module):
                                                            z_st.data_ptr(), stats[0:].data_ptr(), stats[1:].data_ptr(), s))
                 _lib.check(lib.vqcpc_encoder_context(h, z_st.data_ptr(), B, Tz, c.data_ptr(), s))
         return z_st, c, stats[0], stats[1]
+
+
+@dataclass
+class ConfCPC:
+    """``model.py:158-165``."""
+    n_prediction_steps: int = MISSING
+    n_speakers_per_batch: int = MISSING
+    n_utterances_per_speaker: int = MISSING
+    n_negatives: int = MISSING
+    z_dim: int = MISSING
+    c_dim: int = MISSING
+
+
+class CPCLoss(nn.Module):
+    """``CPCLoss`` (``model.py:167-316``) as checkpoint SCORING on MI355X: the forward value of the objective -- InfoNCE
+    loss and per-step prediction accuracies -- in one fused HIP launch per batch.  No gradient flows: results are detached
+    and nothing here trains.
+
+    All ``n_prediction_steps`` predictors are held (the reference's 24 ``state_dict()`` keys, so
+    ``load_state_dict(checkpoint["cpc"])`` works unchanged); like the reference only the first half is ever used
+    (``model.py:181``).  The one deliberate difference is where the negatives come from: the reference draws them from
+    torch's global CPU generator, this class from a counter-based protocol keyed by ``(seed, stream_id)``
+    (``synth.cpc_negatives``), or from the caller (``negatives=``) for draw-for-draw comparisons."""
+
+    def __init__(self, conf: ConfCPC):
+        super().__init__()
+        self.conf = conf
+        self.n_speakers_per_batch = conf.n_speakers_per_batch
+        self.n_utterances_per_speaker = conf.n_utterances_per_speaker
+        self.n_prediction_steps = conf.n_prediction_steps // 2
+        self.n_negatives = conf.n_negatives
+        self.z_dim = conf.z_dim
+        self.c_dim = conf.c_dim
+        self.predictors = nn.ModuleList([nn.Linear(conf.c_dim, conf.z_dim) for _ in range(conf.n_prediction_steps)])
+        self._handle = None
+        self._handle_key = None
+
+    # ------------------------------------------------------------------ native handle
+    def _native(self):
+        slots = self.__dict__.get("_slots")
+        if slots is None:
+            names = [f"predictors.{i}.{p}" for i in range(self.n_prediction_steps) for p in ("weight", "bias")]
+            slots = self.__dict__["_slots"] = _lib.WeightSlots(self, names)
+        ws = slots.tensors()
+        if not ws:
+            raise RuntimeError("CPCLoss: n_prediction_steps // 2 must be at least 1")
+        key = _lib.WeightSlots.key(ws)
+        if self._handle is not None and key == self._handle_key:
+            return self._handle
+        for t in ws:
+            _lib.require_cuda(t, "CPCLoss parameter")
+            if t.dtype != torch.float32:
+                raise RuntimeError("CPCLoss: parameters must be float32")
+            _lib.require_same_device(t, ws[0], "a parameter")
+        self._release()
+        keep = [t.detach().contiguous() for t in ws]
+        w = _lib.CPCWeights()
+        if self.n_prediction_steps > 16:
+            raise RuntimeError(f"CPCLoss: at most 16 prediction steps are scored, got {self.n_prediction_steps}")
+        for i in range(self.n_prediction_steps):
+            w.weight[i], w.bias[i] = keep[2 * i].data_ptr(), keep[2 * i + 1].data_ptr()
+        w.n_steps, w.n_speakers, w.n_utterances = self.n_prediction_steps, self.n_speakers_per_batch, self.n_utterances_per_speaker
+        w.n_negatives, w.z_dim, w.c_dim = self.n_negatives, self.z_dim, self.c_dim
+        h = C.c_void_p()
+        with torch.cuda.device(ws[0].device):
+            torch.cuda.current_stream().synchronize()
+            _lib.check(_lib.load().vqcpc_cpc_create(C.byref(w), C.byref(h)))
+        self._handle, self._handle_key = h, key
+        return h
+
+    def _release(self):
+        if getattr(self, "_handle", None) is not None:
+            _lib.load().vqcpc_cpc_destroy(self._handle)
+            self._handle = None
+
+    def __getstate__(self):                             # the native handle is per object: a copy builds its own
+        d = self.__dict__.copy()
+        d["_handle"], d["_handle_key"] = None, None
+        d.pop("_slots", None)
+        return d
+
+    def refresh(self):
+        """Drop the native handle (it holds COPIES of the predictors) so that the next call re-reads the parameters; needed
+        only after a write through ``.data``, which moves neither storage nor ``_version`` (see ``Encoder.refresh``)."""
+        self._release()
+        self._handle_key = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ reference surface
+    def _check_negatives(self, negatives, length: int, device):
+        K, S, U, G = self.n_prediction_steps, self.n_speakers_per_batch, self.n_utterances_per_speaker, self.n_negatives
+        utt, seq = negatives
+        for name, t, shape, high in (("utt_index", utt, (K, U, G), U), ("seq_index", seq, (K, S, U, G, length), length)):
+            if not isinstance(t, Tensor) or t.dtype != torch.int64 or tuple(t.shape) != shape:
+                raise RuntimeError(f"expected negatives {name} as an int64 tensor of shape {shape}, got "
+                                   f"{tuple(t.shape) if isinstance(t, Tensor) else type(t).__name__}"
+                                   f"{' ' + str(t.dtype) if isinstance(t, Tensor) else ''}")
+            lo, hi = torch.aminmax(t)                         # a comparison entry, not a hot one: one reduction per array
+            if int(lo) < 0 or int(hi) >= high:
+                raise IndexError(f"negatives {name} holds values in [{int(lo)}, {int(hi)}], outside [0, {high})")
+        return utt.to(device).contiguous(), seq.to(device).contiguous()
+
+    @torch.no_grad()
+    def forward_detailed(self, z: Tensor, c: Tensor, negatives: Optional[Tuple[Tensor, Tensor]] = None, seed: int = 13,
+                         stream_id: int = 0, want_correct: bool = False, want_scores: bool = False) -> dict:
+        """``forward`` with everything the kernel computes, as device tensors: ``loss`` (0-dim), ``step_loss`` (K),
+        ``accuracy`` (K); on request ``correct`` (K, N, L) uint8 and ``scores`` (K, N, 1 + Neg, L) = ``f`` of
+        ``model.py:291``.  K = n_prediction_steps // 2, L = T - K.  Nothing is synchronised."""
+        _lib.require_cuda(z, "z")
+        _lib.require_cuda(c, "c")
+        K, N = self.n_prediction_steps, self.n_speakers_per_batch * self.n_utterances_per_speaker
+        if z.dim() != 3 or c.dim() != 3 or z.size(0) != N or z.size(2) != self.z_dim or tuple(c.shape) != (N, z.size(1), self.c_dim):
+            raise RuntimeError(f"expected z of shape ({N}, T, {self.z_dim}) and c of shape ({N}, T, {self.c_dim}) "
+                               f"[{self.n_speakers_per_batch} speakers x {self.n_utterances_per_speaker} utterances], "
+                               f"got {tuple(z.shape)} and {tuple(c.shape)}")
+        T = z.size(1)
+        if T < K + 2:
+            raise RuntimeError(f"expected T >= {K + 2} frames ({K} prediction steps + 2 anchors, model.py:259), got T = {T}")
+        _lib.require_same_device(z, self.predictors[0].weight, "z")
+        _lib.require_same_device(c, self.predictors[0].weight, "c")
+        dev, L = z.device, T - K
+        utt = seq = None
+        if negatives is not None:
+            utt, seq = self._check_negatives(negatives, L, dev)
+        z = z.detach().to(torch.float32).contiguous()
+        c = c.detach().to(torch.float32).contiguous()
+        h = self._native()
+        out = torch.empty(1 + 2 * K, device=dev)
+        correct = torch.empty(K, N, L, dtype=torch.uint8, device=dev) if want_correct else None
+        scores = torch.empty(K, N, 1 + self.n_negatives, L, device=dev) if want_scores else None
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().vqcpc_cpc_score(
+                h, z.data_ptr(), c.data_ptr(), T, utt.data_ptr() if utt is not None else None,
+                seq.data_ptr() if seq is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF,
+                out[0:].data_ptr(), out[1:].data_ptr(), out[1 + K:].data_ptr(),
+                correct.data_ptr() if correct is not None else None, scores.data_ptr() if scores is not None else None,
+                _lib.current_stream()))
+        return {"loss": out[0], "step_loss": out[1:1 + K], "accuracy": out[1 + K:], "correct": correct, "scores": scores}
+
+    def forward(self, z: Tensor, c: Tensor, negatives: Optional[Tuple[Tensor, Tensor]] = None, seed: int = 13,
+                stream_id: int = 0) -> Tuple[Tensor, List[float]]:
+        """``model.py:191-316`` under ``no_grad``: ``(loss, accuracies)`` -- a 0-dim tensor on ``z``'s device and a list of
+        K floats (reading them costs one synchronisation, as ``.item()`` does in the reference, ``model.py:312``).
+        z (Spk * Utt, T, z_dim), c (Spk * Utt, T, c_dim), utterances speaker-major.  The result is detached: no gradient
+        flows through this class.
+
+        negatives: None = drawn in the kernel from ``(seed, stream_id)`` (``synth.cpc_negatives`` returns the same
+        arrays), or ``(utt_index (K, Utt, Neg), seq_index (K, Spk, Utt, Neg, L))`` int64 = the index arrays of
+        ``model.py:282`` for each step, e.g. what the reference drew."""
+        r = self.forward_detailed(z, c, negatives=negatives, seed=seed, stream_id=stream_id)
+        return r["loss"], r["accuracy"].tolist()

@@ -146,3 +146,59 @@ def vocoder_state_dict(seed: int = SEED, size_i_codebook=512, dim_i_embedding=64
     sd["rnnms.ar.fc2.weight"] = _uniform("voc/ar.fc2.w", (n_cls, size_h_fc), size_h_fc ** -0.5, seed)
     sd["rnnms.ar.fc2.bias"] = _uniform("voc/ar.fc2.b", (n_cls,), size_h_fc ** -0.5, seed)
     return sd
+
+
+def cpc_state_dict(seed: int = SEED, n_prediction_steps=12, z_dim=64, c_dim=256):
+    """Random-init ``CPCLoss.state_dict()`` (``model.py:187-189``): ``predictors.{i}.weight`` (z_dim, c_dim) and
+    ``predictors.{i}.bias`` (z_dim), both U(+-1/sqrt(c_dim)) as ``nn.Linear`` initialises them, in the reference's order."""
+    sd = {}
+    for i in range(n_prediction_steps):
+        sd[f"predictors.{i}.weight"] = _uniform(f"cpc/predictors.{i}.w", (z_dim, c_dim), c_dim ** -0.5, seed)
+        sd[f"predictors.{i}.bias"] = _uniform(f"cpc/predictors.{i}.b", (z_dim,), c_dim ** -0.5, seed)
+    return sd
+
+
+def _cpc_words(which: int, k: int, n: int, seed: int, stream_id: int) -> np.ndarray:
+    i = np.arange(n, dtype=np.uint64)
+    ctr = np.zeros((n, 4), np.uint32)
+    ctr[:, 0] = (i >> np.uint64(2)).astype(np.uint32)
+    ctr[:, 1] = (which << 16) | k
+    ctr[:, 2] = stream_id & 0xFFFFFFFF
+    words = philox4x32_10(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    return words[np.arange(n), (i & np.uint64(3)).astype(np.int64)].astype(np.int64)
+
+
+def cpc_negatives(seed: int, stream_id: int, n_steps: int, n_speakers: int, n_utterances: int, n_negatives: int, length: int):
+    """The negatives ``CPCLoss.forward(z, c, seed=, stream_id=)`` draws in its kernel, as the two index arrays of
+    ``model.py:282``: ``utt_index`` (n_steps, Utt, Neg) and ``seq_index`` (n_steps, Spk, Utt, Neg, L) int64.
+
+    Protocol (``csrc/cpc_protocol.h``): for step k (1-based), draw i of that step is word ``i & 3`` of
+    Philox4x32-10(counter = (i >> 2, (which << 16) | k, stream_id, 0), key = seed); which = 0: i indexes (Utt, Neg) and
+    u = w mod Utt; which = 1: i indexes (Spk, Utt, Neg, L), r = 1 + w mod (L - 1) and s = (r + t) mod L
+    (``model.py:259-272``)."""
+    if length < 2:
+        raise ValueError("cpc_negatives: need at least 2 anchors per utterance (model.py:259 draws from [1, L))")
+    utt = np.empty((n_steps, n_utterances, n_negatives), np.int64)
+    seq = np.empty((n_steps, n_speakers, n_utterances, n_negatives, length), np.int64)
+    t = np.arange(length, dtype=np.int64)
+    for k in range(1, n_steps + 1):
+        utt[k - 1] = (_cpc_words(0, k, utt[0].size, seed, stream_id) % n_utterances).reshape(utt[0].shape)
+        r = 1 + _cpc_words(1, k, seq[0].size, seed, stream_id) % (length - 1)
+        seq[k - 1] = (r.reshape(seq[0].shape) + t) % length
+    return torch.from_numpy(utt), torch.from_numpy(seq)
+
+
+def cpc_inputs(name: str, n: int, T: int, c_dim: int = 256, n_codes: int = 512, runs: bool = False, seed: int = SEED):
+    """Synthetic ``(z (n, T, 64), c (n, T, c_dim))`` for CPC scoring: ``z`` = rows of the first ``n_codes`` entries of the
+    data-scale codebook of ``encoder_state_dict(codebook="data")`` (quantised, so equal rows repeat; ``runs``: a frame keeps
+    its predecessor's code two times out of three, as neighbouring speech frames do), ``c`` normal-ish, scaled to an LSTM
+    output's range."""
+    book = _uniform("enc/codebook.data", (512, 64), 1.5, seed)[:n_codes]
+    idx = randint(f"cpc/{name}/code", (n, T), n_codes, seed)
+    if runs:
+        hold = randint(f"cpc/{name}/hold", (n, T), 3, seed) != 0
+        hold[:, 0] = False
+        src = torch.where(hold, torch.zeros_like(idx), torch.arange(T).expand(n, T))
+        idx = torch.gather(idx, 1, torch.cummax(src, dim=1).values)
+    c = _normalish(f"cpc/{name}/c", (n, T, c_dim), seed) * 0.25
+    return book[idx].contiguous(), c
