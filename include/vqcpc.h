@@ -260,6 +260,26 @@ int vqcpc_vocoder_logits(vqcpc_vocoder *voc, const int64_t *x, const int64_t *id
                          const int64_t *speaker, int B, int Tc, int Ts, float *logits,
                          void *stream);
 
+/* Teacher-forced scoring: the number the reference trains its vocoder on (vocoder.py:62-63: the energies of the inputs
+ * audio[:, :-1] against the targets audio[:, 1:], cross-entropy), per utterance, for a padded batch of utterances of different
+ * lengths.  audio DEVICE (B, L) int64 mu-law classes; n_audio HOST (B) valid samples per row or NULL = L; n_codes HOST (B) valid
+ * codes per row or NULL = Tc.  Row b scores the positions t = 0 .. n_audio[b] - 2: input audio[b, t], target audio[b, t + 1]
+ * (the shift is done inside); n_audio[b] - 1 <= 2 * upsample_t * n_codes[b], else VQCPC_ERR_INVALID; n_audio[b] < 2 scores
+ * nothing (sum 0, count 0).  Nothing past n_audio[b] in a row is read.
+ * Outputs DEVICE: nll_sum (B) fp64 = sum over the row's scored positions of lse(e_t) - e_t[target], in nats; n_scored (B) int64;
+ * n_correct (B) int64 = positions whose target is the FIRST maximum of e_t (torch.argmax's rule); nll (B, L - 1) fp32 per
+ * position, zero outside the scored ranges, or NULL.  sum(nll_sum) / sum(n_scored) over equal-length rows is the reference's
+ * F.cross_entropy mean.
+ * Runs the teacher-forced scan of vqcpc_vocoder_logits, but every chunk ends in ONE fused kernel (nll.hip: fc1 + ReLU, fc2,
+ * log-sum-exp, gather, argmax) instead of two GEMMs: no (B, L, n_cls) energies exist anywhere, and no work buffer depends on L
+ * (the scan's slot table is one row for the whole call).  The 256 terms of a log-sum-exp are added as a fixed tree and the per-utterance sums in step order, without atomics:
+ * equal inputs give equal bits.  A class outside [0, n_cls) in a scored position is reported through the handle's status
+ * word like a bad code index (vqcpc_vocoder_check).  Supported: size_h_fc 256 and 8-bit mu-law (the reference's).  Enqueues on
+ * `stream`, does not synchronise. */
+int vqcpc_vocoder_nll(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *idx, const int64_t *speaker,
+                      int B, int Tc, int L, const int *n_codes, const int *n_audio,
+                      double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *nll, void *stream);
+
 /* The wrapper's own glue alone (network_vocoder.py:73-77 / :56-66): series DEVICE (B, 2*Tc, dz + ds) = what the reference's
  * Vocoder.generate / Vocoder.forward hand to rnnms -- [:, :, :dz] the code embedding of code t/2, [:, :, dz:] the speaker
  * embedding.  The same kernel vqcpc_vocoder_generate / _logits / _condition run first; exposed so that it can be checked

@@ -17,7 +17,7 @@ SYMBOLS = [
     "vqcpc_cpc_create", "vqcpc_cpc_destroy", "vqcpc_cpc_score",
     "vqcpc_encoder_check", "vqcpc_vocoder_check", "vqcpc_vocoder_last_path", "vqcpc_vocoder_last_slots", "vqcpc_vocoder_workspace_bytes", "vqcpc_vocoder_plan",
     "vqcpc_vocoder_create", "vqcpc_vocoder_destroy", "vqcpc_vocoder_generate",
-    "vqcpc_vocoder_logits", "vqcpc_vocoder_condition", "vqcpc_vocoder_glue", "vqcpc_vocoder_set_option",
+    "vqcpc_vocoder_logits", "vqcpc_vocoder_nll", "vqcpc_vocoder_condition", "vqcpc_vocoder_glue", "vqcpc_vocoder_set_option",
     "vqcpc_vocoder_last_timing", "vqcpc_vocoder_kernel_times",
     "vqcpc_vocoder_stream_open", "vqcpc_vocoder_stream_next", "vqcpc_vocoder_stream_redo", "vqcpc_vocoder_stream_position",
     "vqcpc_vocoder_stream_close",
@@ -97,6 +97,7 @@ def load():
     lib.vqcpc_vocoder_generate.argtypes = [vp, i64p, i64p, i32, i32, C.POINTER(C.c_int), C.c_uint64, C.c_uint32,
                                            C.POINTER(C.c_uint32), vp, i64p, i32, vp]
     lib.vqcpc_vocoder_logits.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, vp, vp]
+    lib.vqcpc_vocoder_nll.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, i64p, i64p, vp, vp]
     lib.vqcpc_vocoder_condition.argtypes = [vp, i64p, i64p, i32, i32, vp, vp]
     lib.vqcpc_vocoder_glue.argtypes = [vp, i64p, i64p, i32, i32, vp, vp]
     lib.vqcpc_vocoder_set_option.argtypes = [vp, C.c_char_p, i32]

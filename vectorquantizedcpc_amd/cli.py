@@ -9,6 +9,13 @@
     python -m vectorquantizedcpc_amd.cli score   --dataset datasets/2019/english --cpc-checkpoint ckpt.pt | --random-init
                                                  [--speakers 8 --utterances 8 --negatives 17 --sample-frames 128 --seed 13]
 
+    python -m vectorquantizedcpc_amd.cli score-vocoder --dataset datasets/2019/english --in-dir wavs/
+                                                 [--cpc-checkpoint .. --vocoder-checkpoint .. | --random-init] [--per-utterance]
+
+``score-vocoder`` is the validation number the reference's vocoder training never computes (``vocoder.py:68-94``): the
+teacher-forced cross-entropy of ``vocoder.py:62-63`` on ``<in_dir>/<utterance>.wav`` of every entry of ``test.json``, speaker id
+from ``speakers.json`` by the file name's prefix: loss in nats per sample, bits per sample and top-1 accuracy
+(``driver.score_vocoder``, one fused HIP head per chunk of the scan).
 ``score`` is one pass of ``train_cpc.py:104-148`` without the optimiser: the CPC loss, VQ loss, perplexity and per-step
 prediction accuracies of a checkpoint (its ``"encoder"`` and ``"cpc"`` entries) on the utterances of ``test.json``, grouped by
 the speaker their file name starts with (``<speaker>_<utterance>``).
@@ -97,6 +104,36 @@ def score_dataset(args) -> int:
     return 0
 
 
+def score_vocoder_dataset(args) -> int:
+    import json
+    from . import preprocess
+    paths = io.read_test_metadata(args.dataset)
+    with open(Path(args.dataset) / "speakers.json") as f:
+        names = sorted(json.load(f))
+    enc, voc = _models(args, need_vocoder=True)
+    dev = next(enc.parameters()).device
+    waves, speakers = [], []
+    for p in paths:
+        prefix = p.stem.split("_")[0]
+        if prefix not in names:
+            print(f"{p.stem}: speaker {prefix!r} is not in speakers.json")
+            return 1
+        rate, a = io.read_wav_file(Path(args.in_dir) / p.stem)
+        if rate != 16000:                                      # the resampling of librosa.load(sr=16000), convert.py:54-56
+            a = preprocess.resample(torch.as_tensor(a, dtype=torch.float32, device=dev)[None], rate, 16000)[0].cpu().numpy()
+        waves.append(a)
+        speakers.append(names.index(prefix))
+    records, tot = driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)
+    if args.per_utterance:
+        for p, r in zip(paths, records):
+            loss = r["nll_sum"] / r["n_scored"] if r["n_scored"] else float("nan")
+            print(f"{p.stem}: loss:{loss:.4f} nats/sample over {r['n_scored']} samples, correct {r['n_correct']}, "
+                  f"codes {r['n_codes']}, samples cut {r['n_cut']}")
+    print(f"vocoder loss:{tot['loss']:.4f} nats/sample, {tot['bits_per_sample']:.4f} bits/sample, top-1 accuracy:{tot['accuracy']:.4f} "
+          f"over {tot['n_scored']} samples of {tot['n_utterances']} utterances ({tot['n_cut']} samples past the codes cut)")
+    return 0
+
+
 def convert_files(enc, voc, entries, out_dir, seed, max_batch: int = 64, slots: int = 0, timings=None):
     """``convert.py:52-83`` over ``entries`` = [(input path without suffix, speaker id, output name)]: ``.mel.npy`` inputs
     are used as they are; ``.wav`` inputs go through the batched HIP front end (resample at load, reference loudness, log-mel:
@@ -157,10 +194,10 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert", "score"):
+    for name in ("encode", "convert", "score", "score-vocoder"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
-        if name != "score":
+        if name in ("encode", "convert"):
             p.add_argument("--out-dir", required=True)
         p.add_argument("--cpc-checkpoint")
         p.add_argument("--random-init", action="store_true", help="seeded random-init weights (no checkpoint ships with the reference)")
@@ -175,6 +212,10 @@ def main(argv=None) -> int:
             p.add_argument("--seed", type=int, default=synth.SEED)
         elif name == "encode":
             p.add_argument("--save-auxiliary", action="store_true")
+        elif name == "score-vocoder":
+            p.add_argument("--vocoder-checkpoint")
+            p.add_argument("--in-dir", required=True, help="directory of <utterance>.wav files")
+            p.add_argument("--per-utterance", action="store_true", help="also print one line per file")
         else:
             p.add_argument("--vocoder-checkpoint")
             p.add_argument("--synthesis-list", required=True)
@@ -183,7 +224,10 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if not args.random_init and not args.cpc_checkpoint:
         ap.error("give --cpc-checkpoint (and --vocoder-checkpoint for convert) or --random-init")
-    return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset}[args.cmd](args)
+    if args.cmd == "score-vocoder" and not args.random_init and not args.vocoder_checkpoint:
+        ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
+    return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,
+            "score-vocoder": score_vocoder_dataset}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "ar_shared.h"
 #include "ar_xcd.h"
+#include "nll.h"
 #include <math.h>
 #include <stdio.h>
 #include <limits.h>
@@ -97,6 +98,10 @@ struct ArCall {
     const int *x_in;           // [B]
     float *h_out;              // [B][Hr] or null
     int s0;
+    // A scoring call (vqcpc_vocoder_nll): every utterance starts at step 0 in its own slot, so `slots` holds ONE row for all replays
+    // and a slot goes idle (row -1, what the full table says) once its utterance's steps are done: the table does not grow with
+    // the length of the call.  0 for every other call.
+    int one_row;
 };
 
 // Timeline stamps of workgroup (0, 0) (100 MHz wall clock) for tools/decode_timeline.py: compiled in only
@@ -767,7 +772,8 @@ __global__ __launch_bounds__(256) void ar_next_row_kernel(ArModel m, const ArCal
         __syncthreads();
     }
     if (r >= c.n_rep) return;
-    const ArSlot sl = c.slots[(size_t)r * c.Sp + sg];
+    ArSlot sl = c.slots[(size_t)(c.one_row ? 0 : r) * c.Sp + sg];
+    if (c.one_row && c.t_base - sl.t0 >= sl.len) sl.row = -1;
     if (threadIdx.x == 0) m.cur[sg] = sl;
     if (c.h_in && sl.row >= 0 && c.t_base - sl.t0 == c.s0) {
         // stream chunk: a resumed utterance starts in this replay (at local step 0: state parity 0) -- its first step is then an
@@ -950,6 +956,7 @@ struct vqcpc_vocoder {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     DevBuf series, gi, out0, cond, gcond, gbase, hseq, len;
     DevBuf hall, a1c;                    // teacher-forced scan: h_t and fc1 outputs of one chunk
+    DevBuf nll_part, nll_len;            // scoring (vqcpc_vocoder_nll): one chunk's (utterance, workgroup) records; scored steps per utterance
     unsigned *status_host = nullptr;     // the handle's status word: pinned host memory the kernels write and the host reads without a HIP call
     unsigned *status_dev = nullptr;      // the device's view of it
     HostStage stage;
@@ -1006,7 +1013,7 @@ static void clear_graphs(vqcpc_vocoder *v) {
 
 // The handle's grow-only work buffers: freed by vqcpc_vocoder_destroy, counted by vqcpc_vocoder_workspace_bytes.
 static std::vector<DevBuf *> work_buffers(vqcpc_vocoder *v) {
-    std::vector<DevBuf *> b = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c,
+    std::vector<DevBuf *> b = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c, &v->nll_part, &v->nll_len,
                                &v->xd_x, &v->xd_segs};
     for (auto &G : v->grp) b.insert(b.end(), {&G.har, &G.a1, &G.cand_s, &G.cand_k, &G.slot_tab, &G.cur, &G.gcur, &G.candg});
     return b;
@@ -1103,6 +1110,7 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
     HIP_TRY(hipMalloc((void **)&v->mulaw_tab, tab.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(v->mulaw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     for (auto &g : v->grp) HIP_TRY(hipMalloc((void **)&g.call, sizeof(ArCall)));
+    if (w->Hf == NLL_HF && w->n_cls == NLL_CLS) TRY(vq_tf_nll_prepare());      // the scoring head's LDS attribute, once per handle
     HIP_TRY(hipHostMalloc((void **)&v->status_host, 64, hipHostMallocMapped));
     *v->status_host = 0u;
     HIP_TRY(hipHostGetDevicePointer((void **)&v->status_dev, v->status_host, 0));
@@ -1207,7 +1215,8 @@ static int status_check(vqcpc_vocoder *v, bool synced) {
     if (ep) snprintf(which, sizeof which, "call #%u of this handle", ep);
     else snprintf(which, sizeof which, "an earlier call of this handle");
     if (code & STATUS_BAD_INDEX) {
-        vq_set_error("index out of range in self (%s): a code index or speaker id outside its embedding table (network_vocoder.py:73,75)", which);
+        vq_set_error("index out of range in self (%s): a code index or speaker id outside its embedding table (network_vocoder.py:73,75), "
+                     "or a sample class outside [0, n_cls) in a scored position of vqcpc_vocoder_nll", which);
         return VQCPC_ERR_INVALID;
     }
     if (code & STATUS_MISPLACED) {
@@ -1383,6 +1392,25 @@ static int tf_chunk_gemms(vqcpc_vocoder *v, int B, int Ts, int CH, int chunk, fl
     return VQCPC_OK;
 }
 
+// What a scoring call (vqcpc_vocoder_nll) hands the teacher-forced scan: its chunks end in the fused head of nll.hip instead of
+// the two GEMMs, and nothing of size (B, Ts, n_cls) exists.
+struct NllCall {
+    const int64_t *audio;                // DEVICE (B, L): step t reads audio[b, t], its target is audio[b, t + 1]
+    int L;
+    std::vector<int> slen;               // scored steps per utterance: n_audio[b] - 1, at least 0
+    float *nll;                          // DEVICE (B, L - 1) or null
+    double *nll_sum; int64_t *n_scored, *n_correct;   // DEVICE (B)
+};
+
+static int tf_chunk_nll(vqcpc_vocoder *v, int B, int CH, int chunk, const NllCall &nc, hipStream_t s) {
+    NllHead h{};
+    h.hall = v->hall.as<float>(); h.w1 = v->w_fc1; h.b1 = v->b_fc1; h.w2 = v->w_fc2; h.b2 = v->b_fc2;
+    h.audio = nc.audio; h.slen = v->nll_len.as<int>(); h.nll = nc.nll; h.part = v->nll_part.as<NllPart>();
+    h.status = v->status_dev; h.status_tag = v->epoch << 8;
+    h.B = B; h.L = nc.L; h.CH = CH; h.t0 = chunk * CH; h.Hr = v->d.Hr;
+    return vq_tf_nll_chunk(h, nc.nll_sum, nc.n_scored, nc.n_correct, s);
+}
+
 // Which decode loop takes a call, and the resident decoders' slot schedule: pure host arithmetic (no HIP call), so that it can be
 // tested without a GPU (vqcpc_vocoder_plan).  samples[b] = samples utterance b produces; `order` = utterances longest first.
 // path 2 / 3: the per-XCD decoders (VALU / matrix-core form) through `xs` slots, slot q running lists[q] back to back;
@@ -1474,7 +1502,7 @@ struct CallPlan {
 static int plan_launch_tables(const vqcpc_vocoder *v, const int *samples, const std::vector<int> &order, bool tf, int B, int s0,
                               CallPlan &cp);
 static int plan_call(const vqcpc_vocoder *v, int B, int Tc, const int *n_codes_host, bool tf, int Ts, int max_steps,
-                     unsigned utt_base, const uint32_t *utt_ids_host, CallPlan &cp) {
+                     unsigned utt_base, const uint32_t *utt_ids_host, CallPlan &cp, const int *tf_len = nullptr) {
     const auto &d = v->d;
     const int Bp = (B + 15) / 16 * 16;
     // per-utterance lengths: frames for the prenet, samples for the AR loop
@@ -1486,6 +1514,7 @@ static int plan_call(const vqcpc_vocoder *v, int B, int Tc, const int *n_codes_h
         cp.lens[b] = 2 * nc;
         int ns = d.upsample_t * 2 * nc;
         if (tf) ns = ns < Ts ? ns : Ts;
+        if (tf && tf_len) ns = ns < tf_len[b] ? ns : tf_len[b];      // a scoring call: the utterance's own scored length
         if (max_steps > 0 && ns > max_steps) ns = max_steps;
         cp.lens[Bp + b] = ns;
         cp.utt[b] = utt_ids_host ? utt_ids_host[b] : utt_base + (unsigned)b;
@@ -1635,7 +1664,8 @@ static int group_graph(vqcpc_vocoder *v, int g, const ArModel &m, int nbt, bool 
 // The launch-per-step kernels: per tile group its state buffers, call record (ArCall) and model (ArModel), then the replays of
 // steps_per_graph steps each -- captured graphs, or plain launches with use_graph = 0.
 static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs, int T2, int Ts, unsigned long long seed,
-                           float *wav, int64_t *mulaw, float *logits, hipStream_t s, const Resume *rs = nullptr) {
+                           float *wav, int64_t *mulaw, float *logits, hipStream_t s, const Resume *rs = nullptr,
+                           const NllCall *nc = nullptr) {
     const auto &d = v->d;
     const int Hr = d.Hr, S = v->steps_per_graph, B = (int)cp.utt.size(), n_slots = cp.dp.xs, max_t = (int)cp.dp.longest;
     const bool tf = inputs != nullptr;     // teacher-forced scan: one group, GRU steps only, chunked GEMMs for fc1 / fc2
@@ -1644,9 +1674,11 @@ static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *
     for (int g = 0; g < cp.n_grp; ++g) {
         auto &G = v->grp[g];
         const int nb = cp.tiles[g], Spg = nb * 16, slot0 = g * cp.tiles[0] * 16;
-        TRY(G.slot_tab.reserve(cp.table[g].size() * sizeof(ArSlot)));
+        // a scoring call uploads the table's first row only (ArCall::one_row): its work space does not depend on the call's length
+        const size_t tab_n = nc ? (size_t)Spg : cp.table[g].size();
+        TRY(G.slot_tab.reserve(tab_n * sizeof(ArSlot)));
         TRY(G.cur.reserve((size_t)Spg * sizeof(ArSlot)));
-        TRY(v->stage.upload(G.slot_tab.p, cp.table[g].data(), cp.table[g].size() * sizeof(ArSlot), s));
+        TRY(v->stage.upload(G.slot_tab.p, cp.table[g].data(), tab_n * sizeof(ArSlot), s));
         TRY(v->stage.upload(G.cur.p, cp.table[g].data(), (size_t)Spg * sizeof(ArSlot), s));
         const size_t hsz = (size_t)nb * Hr * 16 * sizeof(float);
         TRY(G.har.reserve(2 * hsz));
@@ -1676,7 +1708,10 @@ static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *
         if (tf) {
             c.CH = v->tf_chunk_replays * S;
             TRY(v->hall.reserve((size_t)B * c.CH * Hr * sizeof(float)));
-            TRY(v->a1c.reserve((size_t)B * c.CH * d.Hf * sizeof(float)));
+            if (nc) {                                 // scoring: the chunk ends in the fused head; audio rows are L apart
+                c.Ts = nc->L; c.one_row = 1;
+                TRY(v->nll_part.reserve((size_t)B * vq_tf_nll_tiles(c.CH) * sizeof(NllPart)));
+            } else TRY(v->a1c.reserve((size_t)B * c.CH * d.Hf * sizeof(float)));
             c.hall = v->hall.as<float>(); c.hall_t0 = 0;
             c.logits = nullptr;                       // written by the chunk GEMMs, not by ar_fc2_kernel
         }
@@ -1714,7 +1749,8 @@ static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *
             if (r < cp.rep[0]) HIP_TRY(hipGraphLaunch(exec[0], s));
             if (cp.n_grp == 2 && r < cp.rep[1]) HIP_TRY(hipGraphLaunch(exec[1], v->side_stream));
             if (tf && ((r + 1) % v->tf_chunk_replays == 0 || r + 1 == nr))
-                TRY(tf_chunk_gemms(v, B, Ts, calls[0].CH, r / v->tf_chunk_replays, logits, s));
+                TRY(nc ? tf_chunk_nll(v, B, calls[0].CH, r / v->tf_chunk_replays, *nc, s)
+                       : tf_chunk_gemms(v, B, Ts, calls[0].CH, r / v->tf_chunk_replays, logits, s));
         }
         if (cp.n_grp == 2) {
             HIP_TRY(hipEventRecord(v->ev_join, v->side_stream));
@@ -1724,7 +1760,8 @@ static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *
         for (int t0 = 0, r = 0; t0 < max_t; t0 += S, ++r) {
             TRY(launch_ar_steps(v, models[0], v->grp[0].call, cp.tiles[0], S, tf, s));
             if (tf && ((r + 1) % v->tf_chunk_replays == 0 || t0 + S >= max_t))
-                TRY(tf_chunk_gemms(v, B, Ts, calls[0].CH, r / v->tf_chunk_replays, logits, s));
+                TRY(nc ? tf_chunk_nll(v, B, calls[0].CH, r / v->tf_chunk_replays, *nc, s)
+                       : tf_chunk_gemms(v, B, Ts, calls[0].CH, r / v->tf_chunk_replays, logits, s));
         }
     }
     HIP_TRY(hipEventRecord(v->ev1, s));
@@ -1740,18 +1777,18 @@ static int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *
 static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int B, int Tc, const int *n_codes_host,
                   const int64_t *inputs, int Ts, unsigned long long seed, unsigned utt_base,
                   const uint32_t *utt_ids_host, float *wav,
-                  int64_t *mulaw, float *logits, int max_steps, hipStream_t s) {
+                  int64_t *mulaw, float *logits, int max_steps, hipStream_t s, const NllCall *nc = nullptr) {
     const auto &d = v->d;
     const int Hr = d.Hr, dl = 2 * d.Hp, Lout = d.upsample_t * 2 * Tc;
     CallPlan cp;
-    TRY(plan_call(v, B, Tc, n_codes_host, inputs != nullptr, Ts, max_steps, utt_base, utt_ids_host, cp));
+    TRY(plan_call(v, B, Tc, n_codes_host, inputs != nullptr, Ts, max_steps, utt_base, utt_ids_host, cp, nc ? nc->slen.data() : nullptr));
     TRY(status_check(v, false));          // has an earlier call's hand-off reported already?  (nothing is cleared without a sync)
     v->epoch = (v->epoch + 1u) & 0xffffffu;
     if (v->epoch == 0) v->epoch = 1;
     // upload through the pinned arena: no synchronisation of the caller's stream
     TRY(v->stage.begin(cp.lens.size() * sizeof(int) + (cp.table[0].size() + cp.table[1].size()) * sizeof(ArSlot) +
                        (size_t)(cp.tiles[0] + cp.tiles[1]) * 16 * sizeof(ArSlot) + 2 * sizeof(ArCall) + 256 +
-                       (size_t)8 * XM_BX * (B + 1) * sizeof(XdSeg) + (size_t)2 * (B + 16) * sizeof(int)));
+                       (size_t)8 * XM_BX * (B + 1) * sizeof(XdSeg) + (size_t)3 * (B + 16) * sizeof(int)));
     TRY(v->len.reserve(cp.lens.size() * sizeof(int)));
     TRY(v->stage.upload(v->len.p, cp.lens.data(), cp.lens.size() * sizeof(int), s));
     TRY(v->gbase.reserve(cp.gbase.size() * sizeof(int)));
@@ -1765,8 +1802,13 @@ static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int 
     if (wav) HIP_TRY(hipMemsetAsync(wav, 0, (size_t)B * Lout * sizeof(float), s));
     if (mulaw) HIP_TRY(hipMemsetAsync(mulaw, 0, (size_t)B * Lout * sizeof(int64_t), s));
     if (v->last_path != 0) v->last_path = 1;      // a call that fails from here on ran no decode loop
+    VQ_REQUIRE(!nc || cp.dp.path == 0, "vocoder.nll: a scoring call must take the launch path (planned path %d)", cp.dp.path);
     if (cp.dp.path != 0) return run_resident(v, cp, 2 * Tc, seed, wav, mulaw, s);
-    return run_launch_path(v, cp, inputs, 2 * Tc, Ts, seed, wav, mulaw, logits, s);
+    if (nc) {
+        TRY(v->nll_len.reserve((size_t)B * sizeof(int)));
+        TRY(v->stage.upload(v->nll_len.p, nc->slen.data(), (size_t)B * sizeof(int), s));
+    }
+    return run_launch_path(v, cp, inputs, 2 * Tc, Ts, seed, wav, mulaw, logits, s, nullptr, nc);
 }
 
 extern "C" int vqcpc_vocoder_generate(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc,
@@ -1785,6 +1827,34 @@ extern "C" int vqcpc_vocoder_logits(vqcpc_vocoder *v, const int64_t *x, const in
                "vocoder.forward: Ts=%d must be in (0, %d]", Ts, 2 * v->d.upsample_t * Tc);
     VQ_REQUIRE(((uintptr_t)logits & 15) == 0, "vocoder.forward: logits must be 16-byte aligned");
     return run_ar(v, idx, speaker, B, Tc, nullptr, x, Ts, 0, 0, nullptr, nullptr, nullptr, logits, 0, (hipStream_t)stream);
+}
+
+extern "C" int vqcpc_vocoder_nll(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                                 int L, const int *n_codes, const int *n_audio, double *nll_sum, int64_t *n_scored,
+                                 int64_t *n_correct, float *nll, void *stream) {
+    VQ_REQUIRE(v && audio && idx && speaker && nll_sum && n_scored && n_correct, "vqcpc_vocoder_nll: null argument");
+    VQ_REQUIRE(B > 0 && Tc > 0 && L > 0, "vocoder.nll: need B > 0, Tc > 0 and L > 0 (got %d, %d, %d)", B, Tc, L);
+    const auto &d = v->d;
+    VQ_REQUIRE(d.Hf == NLL_HF && d.n_cls == NLL_CLS, "vocoder.nll: the scoring head is built for size_h_fc %d and %d classes "
+               "(config.py:69,77), this model has %d and %d", NLL_HF, NLL_CLS, d.Hf, d.n_cls);
+    hipStream_t s = (hipStream_t)stream;
+    NllCall nc{audio, L, std::vector<int>(B, 0), nll, nll_sum, n_scored, n_correct};
+    int longest = 0;
+    for (int b = 0; b < B; ++b) {
+        const int na = n_audio ? n_audio[b] : L, ncd = n_codes ? n_codes[b] : Tc;
+        VQ_REQUIRE(na >= 0 && na <= L, "vocoder.nll: n_audio[%d] = %d outside [0, %d]", b, na, L);
+        VQ_REQUIRE(ncd >= 0 && ncd <= Tc, "vocoder: n_codes[%d] = %d outside [0, %d]", b, ncd, Tc);
+        VQ_REQUIRE((long)na - 1 <= (long)2 * d.upsample_t * ncd, "vocoder.nll: utterance %d has %d samples to score but its %d codes "
+                   "cover %ld (n_audio - 1 <= 2 * upsample_t * n_codes)", b, na - 1, ncd, (long)2 * d.upsample_t * ncd);
+        nc.slen[b] = na >= 2 ? na - 1 : 0;
+        longest = nc.slen[b] > longest ? nc.slen[b] : longest;
+    }
+    HIP_TRY(hipMemsetAsync(nll_sum, 0, (size_t)B * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(n_scored, 0, (size_t)B * sizeof(int64_t), s));
+    HIP_TRY(hipMemsetAsync(n_correct, 0, (size_t)B * sizeof(int64_t), s));
+    if (nll && L > 1) HIP_TRY(hipMemsetAsync(nll, 0, (size_t)B * (L - 1) * sizeof(float), s));
+    if (longest == 0) return VQCPC_OK;         // no row has two samples: nothing to score
+    return run_ar(v, idx, speaker, B, Tc, n_codes, audio, longest, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, s, &nc);
 }
 
 // Average wall time of `reps` back-to-back launches of each per-sample kernel (HIP events on

@@ -268,3 +268,85 @@ def score_batches(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, sample_frames
         res["perplexity"] += (float(perplexity) - res["perplexity"]) / n
         res["accuracies"] = list(acc) if res["accuracies"] is None else [a + (x - a) / n for a, x in zip(res["accuracies"], acc)]
     return res
+
+
+# ---------------------------------------------------------------------------------------- vocoder scoring
+def mulaw_classes(wave, bits: int = 8):
+    """Mu-law classes of a 16 kHz waveform as the reference makes its vocoder targets (``preprocess.py:20-27, :90-91``): peak
+    normalisation to 0.999, then ``preprocess.mulaw_encode`` -- the host formula itself (numpy, elementwise, not a hot path)."""
+    import numpy as np
+    from . import preprocess
+    w = np.asarray(torch.as_tensor(wave).detach().cpu().numpy() if isinstance(wave, torch.Tensor) else wave)
+    return preprocess.mulaw_encode(w / np.abs(w).max() * 0.999, 2 ** bits).astype(np.int64)
+
+
+def scored_samples(n_audio: int, n_codes: int, upsample: int = 160) -> int:
+    """Samples of an utterance that a scoring call takes: ``min(len, 2 * upsample * n_codes + 1)`` -- the encoder halves the frame
+    rate, so the codes may cover a few hundred samples fewer than the file holds; one sample more than they cover is kept, as
+    the last target."""
+    return min(int(n_audio), 2 * upsample * int(n_codes) + 1)
+
+
+@torch.no_grad()
+def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speakers: Sequence[int], max_batch: int = 64,
+                  max_pad_frac: float = 0.25, conf=None):
+    """Teacher-forced score of a vocoder checkpoint on held-out utterances -- the validation number the reference does not
+    compute (its ``validation_step`` returns 0 because whole utterances do not batch there, ``vocoder.py:68-94``).
+
+    ``waves_or_mels``: per utterance a 1-D waveform at the front end's rate (16 kHz: after any resampling, before pre-emphasis)
+    or a (n_mels, T) log-mel.  ``audio``: per utterance the int mu-law classes to score, or None with waveforms: then they are
+    ``mulaw_classes`` of the same waveform.  mel -> ``Encoder.encode`` -> code indices -> length buckets -> ``Vocoder.nll`` with
+    ``n_codes`` / ``lengths`` per bucket.  Returns ``(records, totals)``: one dict per utterance (``nll_sum``, ``n_scored``,
+    ``n_correct``, ``n_codes``, ``indices`` = the code indices it was conditioned on, ``n_cut`` = samples of the utterance that
+    the codes do not cover and that were cut) and the
+    corpus totals (``loss`` in nats per sample, ``bits_per_sample``, ``accuracy``, ``n_scored``, ``n_correct``, ``nll_sum``,
+    ``n_cut``, ``n_utterances``)."""
+    import math
+    from . import preprocess
+    dev = next(encoder.parameters()).device
+    up = vocoder.conf.rnnms.upsampling_t
+    n = len(waves_or_mels)
+    if len(speakers) != n or (audio is not None and len(audio) != n):
+        raise ValueError("score_vocoder: one speaker (and one audio array) per utterance")
+    mels = list(waves_or_mels)
+    is_wave = [torch.as_tensor(m).dim() == 1 for m in mels]
+    if audio is None:
+        if not all(is_wave):
+            raise ValueError("score_vocoder: audio=None needs waveforms (the classes are made from them)")
+        audio = [mulaw_classes(w, vocoder.conf.rnnms.bits_mu_law) for w in mels]
+    wave_ids = [i for i in range(n) if is_wave[i]]
+    if wave_ids:
+        lens = [int(len(mels[i])) for i in wave_ids]
+        hop = (conf or preprocess.ConfPreprocessing()).hop_length
+        for ids in make_buckets(lens, [0] * len(lens), max_batch, max_pad_frac):
+            L = max(lens[k] for k in ids)
+            batch = torch.zeros(len(ids), L, device=dev)
+            for r, k in enumerate(ids):
+                batch[r, : lens[k]] = torch.as_tensor(mels[wave_ids[k]], dtype=torch.float32)
+            mel = preprocess.wave_to_mel(batch, conf, lengths=[lens[k] for k in ids])
+            for r, k in enumerate(ids):
+                mels[wave_ids[k]] = mel[r, :, : 1 + lens[k] // hop]
+    codes = encode_utterances(encoder, mels, max_batch=max_batch, max_pad_frac=max_pad_frac)
+    n_codes = [int(c["indices"].numel()) for c in codes]
+    audio = [torch.as_tensor(a).to(torch.int64).reshape(-1) for a in audio]
+    keep = [scored_samples(a.numel(), nc, up) for a, nc in zip(audio, n_codes)]
+    records: List[Optional[dict]] = [None] * n
+    for ids in make_buckets(keep, [0] * n, max_batch, max_pad_frac):
+        Tc, L = max(max(n_codes[i] for i in ids), 1), max(max(keep[i] for i in ids), 1)
+        z = torch.zeros(len(ids), Tc, dtype=torch.int64, device=dev)
+        a = torch.zeros(len(ids), L, dtype=torch.int64)
+        for r, i in enumerate(ids):
+            z[r, : n_codes[i]] = codes[i]["indices"]
+            a[r, : keep[i]] = audio[i][: keep[i]]
+        spk = torch.tensor([int(speakers[i]) for i in ids], device=dev)
+        res = vocoder.nll(a.to(dev), z, spk, lengths=[keep[i] for i in ids], n_codes=[n_codes[i] for i in ids])
+        sums, cnt, ok = res.nll_sum.tolist(), res.n_scored.tolist(), res.n_correct.tolist()
+        for r, i in enumerate(ids):
+            records[i] = {"nll_sum": sums[r], "n_scored": cnt[r], "n_correct": ok[r], "n_codes": n_codes[i],
+                          "n_cut": int(audio[i].numel()) - keep[i], "indices": codes[i]["indices"]}
+    tot = {k: sum(r[k] for r in records) for k in ("nll_sum", "n_scored", "n_correct", "n_cut")}
+    tot["n_utterances"] = n
+    tot["loss"] = tot["nll_sum"] / tot["n_scored"] if tot["n_scored"] else float("nan")
+    tot["bits_per_sample"] = tot["loss"] / math.log(2.0)
+    tot["accuracy"] = tot["n_correct"] / tot["n_scored"] if tot["n_scored"] else float("nan")
+    return records, tot

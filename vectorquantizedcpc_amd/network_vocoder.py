@@ -338,6 +338,49 @@ class Vocoder(nn.Module):
         return logits
 
     @torch.no_grad()
+    def nll(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, per_sample: bool = False) -> "VocoderNLL":
+        """Teacher-forced negative log-likelihood per utterance: the vocoder's training objective (``vocoder.py:62-63``: the
+        energies of ``audio[:, :-1]`` against the targets ``audio[:, 1:]``) as a number for held-out data, without the
+        ``(B, T_s, 2**bits)`` energies ever existing (``vqcpc_vocoder_nll``).
+
+        ``audio`` (B, L) integer mu-law classes; ``lengths`` valid samples per row of a padded batch (default L): row b scores
+        the positions ``0 .. lengths[b] - 2`` and nothing behind them is read; ``n_codes`` valid codes per row (default T'),
+        with ``lengths[b] - 1 <= 2 * upsampling_t * n_codes[b]``.  ``per_sample=True`` also returns the (B, L - 1) fp32 values.
+        A class outside ``[0, 2**bits)`` in a scored position raises ``IndexError``.  Synchronises its stream (``check()``)."""
+        z, speaker = self._prep(z, speaker)
+        _lib.require_cuda(audio, "audio")
+        _lib.require_same_device(audio, self.code_embedding.weight, "audio")
+        B, Tc = z.shape
+        if audio.dim() != 2 or audio.size(0) != B or audio.size(1) < 1:
+            raise RuntimeError(f"expected audio (B, L) with B = {B} and L >= 1, got {tuple(audio.shape)}")
+        if audio.is_floating_point() or audio.dtype == torch.bool:
+            raise RuntimeError("audio must be an integer tensor of mu-law classes (the targets of F.cross_entropy, vocoder.py:63)")
+        audio = audio.detach().to(torch.int64).contiguous()
+        L = audio.size(1)
+
+        def host_ints(v, what):
+            if v is None:
+                return None
+            v = [int(x) for x in (v.tolist() if isinstance(v, Tensor) else v)]
+            if len(v) != B:
+                raise RuntimeError(f"{what} must have one entry per utterance ({B}), got {len(v)}")
+            return (C.c_int * B)(*v)
+
+        na, nc = host_ints(lengths, "lengths"), host_ints(n_codes, "n_codes")
+        dev = z.device
+        nll_sum = torch.empty(B, dtype=torch.float64, device=dev)
+        n_scored = torch.empty(B, dtype=torch.int64, device=dev)
+        n_correct = torch.empty(B, dtype=torch.int64, device=dev)
+        nll = torch.empty(B, L - 1, device=dev) if per_sample else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().vqcpc_vocoder_nll(
+                self._native(), audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, nll_sum.data_ptr(),
+                n_scored.data_ptr(), n_correct.data_ptr(), nll.data_ptr() if per_sample and L > 1 else None,
+                _lib.current_stream()))
+            self.check()              # a bad class / code / speaker raises here and is not left latched
+        return VocoderNLL(nll_sum, n_scored, n_correct, nll)
+
+    @torch.no_grad()
     def glue(self, z: Tensor, speaker: Tensor) -> Tensor:
         """What ``network_vocoder.py:69-77`` hands to ``rnnms``: (B, 2T', dim_i_embedding + dim_speaker_embedding).  Synchronises
         its stream (``check()``)."""
@@ -361,6 +404,21 @@ class Vocoder(nn.Module):
                                                            out.data_ptr(), _lib.current_stream()))
             self.check()
         return out
+
+
+@dataclass
+class VocoderNLL:
+    """What ``Vocoder.nll`` returns: per utterance the summed negative log-likelihood in nats (float64), the number of scored
+    samples and of samples whose target was the first maximum of the energies (int64), and per sample (B, L - 1) fp32 or None."""
+    nll_sum: Tensor
+    n_scored: Tensor
+    n_correct: Tensor
+    nll: object = None
+
+    @property
+    def loss(self) -> Tensor:
+        """Mean over every scored sample; with equal lengths exactly the reference's ``F.cross_entropy`` mean (``vocoder.py:63``)."""
+        return self.nll_sum.sum() / self.n_scored.sum()
 
 
 class VocoderStream:
