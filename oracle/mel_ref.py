@@ -69,12 +69,25 @@ def stft_mag(y, n_fft=2048, hop=160, win=400):
     return np.abs(np.fft.rfft(yp[idx] * w[None, :], axis=1)).T
 
 
-def wave_to_mel(wave, sr=16000, n_fft=2048, n_mels=80, hop=160, win=400, fmin=50.0, preemph=0.97, top_db=80.0):
-    """``preprocess.py:53-75`` -> float32 (n_mels, T) normalised log-mel."""
+def mel_amplitude(wave, sr=16000, n_fft=2048, n_mels=80, hop=160, win=400, fmin=50.0, preemph=0.97):
+    """The mel spectrogram (power 1) of the peak-normalised, pre-emphasised wave -> float64 (n_mels, T)."""
     wave = np.asarray(wave, dtype=np.float64)
     ws = wave / np.abs(wave).max() * 0.999
     S = stft_mag(preemphasis(ws, preemph), n_fft, hop, win)
-    mel = mel_filterbank(sr, n_fft, n_mels, fmin).astype(np.float64) @ S
+    return mel_filterbank(sr, n_fft, n_mels, fmin).astype(np.float64) @ S
+
+
+def wave_to_mel(wave, sr=16000, n_fft=2048, n_mels=80, hop=160, win=400, fmin=50.0, preemph=0.97, top_db=80.0):
+    """``preprocess.py:53-75`` -> float32 (n_mels, T) normalised log-mel."""
+    mel = mel_amplitude(wave, sr, n_fft, n_mels, hop, win, fmin, preemph)
     logspec = 10.0 * np.log10(np.maximum(1e-10, mel * mel))          # amplitude_to_db: amin 1e-5, ref 1.0
     logspec = np.maximum(logspec, logspec.max() - top_db)
     return (logspec / top_db + 1.0).astype(np.float32)
+
+
+def clamp_shares(wave, top_db=80.0, **conf):
+    """-> (share of cells that ``top_db`` clamps, share of cells on the ``amin`` floor) in the float64 reference."""
+    mel = mel_amplitude(wave, **conf)
+    p = mel * mel
+    logspec = 10.0 * np.log10(np.maximum(1e-10, p))
+    return float(np.mean(logspec < logspec.max() - top_db)), float(np.mean(p < 1e-10))

@@ -1,7 +1,10 @@
 """-m gpu: the HIP resampler (vqcpc_resampler_*, preprocess.resample) against the float64 oracle.
 PARITY UNPINNED (resampy / librosa absent): oracle/resample_ref.py restates the published kaiser_best algorithm.
-Tolerance: the kernel computes the output time as t * increment, resampy accumulates it -- the two differ by rounding
-only, so 2e-6 absolute on signals of unit amplitude (fp32 output)."""
+Tolerance: the kernel replays the reference's accumulated output clock (time_register += time_increment, summed once on the
+host) and sums both wings in float64 in the reference's order, then rounds once to float32.  So every output is within one
+float32 ulp of float32(want) (1e-12 absolute where the sum cancels) and at least 99.9 % are bit-equal
+(resample_ref.compare_rounded; tests/test_gpu_resample_f64.py holds the wider cases and what the MI355X showed).  Until the
+kernel had that clock these tests allowed 2e-6 absolute."""
 import numpy as np
 import pytest
 import torch
@@ -20,7 +23,9 @@ def test_resample_matches_oracle(sr_in, sr_out):
     got = preprocess.resample(torch.from_numpy(x).cuda(), sr_in, sr_out).cpu().numpy()
     want = R.resample(x, sr_in, sr_out)
     assert got.shape == want.shape and got.dtype == np.float32
-    assert np.abs(got - want).max() <= 2e-6
+    ok, share, ulp, _ = R.compare_rounded(got, want)
+    print("\nresample %d->%d: max ulp %d, bit-equal %.5f, max |diff| %.2e" % (sr_in, sr_out, ulp, share, np.abs(got - want).max()))
+    assert ok and share >= 0.999, (ulp, share)
 
 
 def test_ragged_batch_and_load_wav(tmp_path):
@@ -32,11 +37,13 @@ def test_ragged_batch_and_load_wav(tmp_path):
     assert got.shape == (3, int(np.ceil(2000 * 16000 / 44100)))
     for b, n in enumerate(lens):
         want = R.resample(x[b, :n], 44100, 16000)
-        assert np.abs(got[b, : len(want)] - want).max() <= 2e-6 and not got[b, len(want):].any()
+        ok, share, _, _ = R.compare_rounded(got[b, : len(want)], want)
+        assert ok and share >= 0.999 and not got[b, len(want):].any()
     from scipy.io import wavfile
     wavfile.write(tmp_path / "a.wav", 22050, x[0])
     w = io.load_wav(tmp_path / "a", 16000)
     assert w.shape == (int(np.ceil(2000 * 16000 / 22050)),) and not w.is_cuda
-    assert np.abs(w.numpy() - R.resample(x[0], 22050, 16000)).max() <= 2e-6
+    ok, share, _, _ = R.compare_rounded(w.numpy(), R.resample(x[0], 22050, 16000))
+    assert ok and share >= 0.999
     wavfile.write(tmp_path / "b.wav", 16000, x[0])
     assert torch.equal(io.load_wav(tmp_path / "b", 16000), torch.from_numpy(x[0]))

@@ -47,3 +47,17 @@ def test_gating():
     x = _sine(rate, dur=2.0, amp=0.3)
     y = L.normalize_loudness(x, L.integrated_loudness(x, rate), -30.0)
     assert abs(L.integrated_loudness(y, rate) + 30.0) < 1e-9
+
+
+def test_longdouble_run_measures_scipys_own_error():
+    """The long-double recurrence is the same filter (1e-12 on ordinary blocks) and shows what float64 costs scipy in the
+    ringing after digital silence; the GPU test bounds the kernel by ten times that figure, measured per case."""
+    from oracle import zoo
+    rate = 8000
+    x = zoo.make("dc_rumble", 2 * rate, rate)
+    assert np.abs(L.block_energies(x, rate) / L.block_energies_longdouble(x, rate) - 1).max() < 1e-12
+    x = zoo.make("tone_silence", 2 * rate, rate)
+    zw, zl = L.block_energies(x, rate), L.block_energies_longdouble(x, rate)
+    u = np.abs(zw / zl - 1)
+    print("\nscipy float64 vs long double on tone_silence @ 8 kHz: max %.2e at block %d (energy %.1e)" % (u.max(), u.argmax(), zl[u.argmax()]))
+    assert zl.min() < 1e-100 and 1e-13 < u.max() < 1e-9 and u[:8].max() < 1e-12

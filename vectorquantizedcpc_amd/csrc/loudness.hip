@@ -10,6 +10,10 @@
 // Pass 1 runs every chunk from a zero state (r), a short scan over the chunks of an utterance fixes the
 // start states, pass 2 re-runs the chunks from them and stores the squared output; one workgroup per
 // gating block sums its 0.4 s of squares, one thread per utterance applies the two gates.
+// The scan carries the state and P as double-double: the high-pass poles are a near-double pole at 1, P's
+// entries cancel in P * state, and in plain fp64 every chunk lost about 70 times what the serial filter
+// loses over the same samples (4.9e-8 relative in the ringing after digital silence at 96 kHz;
+// tests/test_gpu_loudness_f64.py).  P itself comes from the same recurrence run in long double on the host.
 // pyloudnorm is absent offline: checked against oracle/loudness_ref.py (float64) -- parity unpinned.
 #include "common.h"
 #include <math.h>
@@ -23,7 +27,7 @@ constexpr double BLOCK_S = 0.400, STEP = 1.0 - 0.75, GAMMA_ABS = -70.0;
 
 struct KW {                                // the K-weighting cascade, normalised by a0
     double b[2][3], a[2][2];
-    double P[16];                          // LC-sample homogeneous transition of the 4-vector state
+    double P[16], Plo[16];                 // LC-sample homogeneous transition of the 4-vector state, P + Plo (double-double)
 };
 
 struct vqcpc_loudness {
@@ -61,20 +65,39 @@ __global__ void ld_chunk_kernel(const float *__restrict__ wav, const int *__rest
     if (!APPLY) { rec[0] = s[0]; rec[1] = s[1]; rec[2] = s[2]; rec[3] = s[3]; }
 }
 
-// One thread per utterance: start state of chunk c = P * start(c-1) + r(c-1).  r is overwritten by the start states.
+// double-double: value = hi + lo, |lo| <= ulp(hi) / 2 (Dekker / Knuth error-free transformations; fma gives the product's error)
+struct DD { double hi, lo; };
+__device__ __forceinline__ DD dd_add(DD a, DD b) {
+    const double s = a.hi + b.hi, v = s - a.hi;
+    const double e = ((a.hi - (s - v)) + (b.hi - v)) + (a.lo + b.lo);
+    const double hi = s + e;
+    return {hi, e - (hi - s)};
+}
+__device__ __forceinline__ DD dd_mul(DD a, DD b) {
+    const double p = a.hi * b.hi;
+    const double e = fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
+    const double hi = p + e;
+    return {hi, e - (hi - p)};
+}
+
+// One thread per utterance: start state of chunk c = P * start(c-1) + r(c-1), carried as double-double and handed to
+// pass 2 rounded to fp64.  r is overwritten by the start states.
 __global__ void ld_scan_kernel(const int *__restrict__ len, int B, int nchmax, KW k, double *__restrict__ st) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int nch = (len[b] + LC - 1) / LC;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    DD s[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
     for (int c = 0; c < nch; ++c) {
         double *rec = st + ((size_t)b * nchmax + c) * 4;
-        const double r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-        rec[0] = s[0]; rec[1] = s[1]; rec[2] = s[2]; rec[3] = s[3];
-        double n[4];
-        for (int i = 0; i < 4; ++i)
-            n[i] = ((k.P[i * 4 + 0] * s[0] + k.P[i * 4 + 1] * s[1]) + (k.P[i * 4 + 2] * s[2] + k.P[i * 4 + 3] * s[3]));
-        s[0] = n[0] + r0; s[1] = n[1] + r1; s[2] = n[2] + r2; s[3] = n[3] + r3;
+        const double r[4] = {rec[0], rec[1], rec[2], rec[3]};
+        rec[0] = s[0].hi; rec[1] = s[1].hi; rec[2] = s[2].hi; rec[3] = s[3].hi;
+        DD n[4];
+        for (int i = 0; i < 4; ++i) {
+            DD acc = {r[i], 0.0};
+            for (int j = 0; j < 4; ++j) acc = dd_add(acc, dd_mul(DD{k.P[i * 4 + j], k.Plo[i * 4 + j]}, s[j]));
+            n[i] = acc;
+        }
+        for (int i = 0; i < 4; ++i) s[i] = n[i];
     }
 }
 
@@ -172,11 +195,22 @@ extern "C" int vqcpc_loudness_create(int rate, vqcpc_loudness **out) {
     m->rate = rate;
     biquad(true, 4.0, 1.0 / sqrt(2.0), 1500.0, rate, m->k.b[0], m->k.a[0]);
     biquad(false, 0.0, 0.5, 38.0, rate, m->k.b[1], m->k.a[1]);
-    for (int col = 0; col < 4; ++col) {                      // P column = LC zero-input steps from a unit state
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        s[col] = 1.0;
-        for (int i = 0; i < LC; ++i) (void)kw_step(m->k, 0.0, s);
-        for (int row = 0; row < 4; ++row) m->k.P[row * 4 + col] = s[row];
+    for (int col = 0; col < 4; ++col) {                      // P column = LC zero-input steps from a unit state, in long double
+        long double s[4] = {0.0L, 0.0L, 0.0L, 0.0L};
+        s[col] = 1.0L;
+        const KW &k = m->k;
+        for (int i = 0; i < LC; ++i) {                       // kw_step with x = 0
+            const long double y1 = s[0];
+            s[0] = -(long double)k.a[0][0] * y1 + s[1];
+            s[1] = -(long double)k.a[0][1] * y1;
+            const long double y2 = (long double)k.b[1][0] * y1 + s[2];
+            s[2] = (long double)k.b[1][1] * y1 - (long double)k.a[1][0] * y2 + s[3];
+            s[3] = (long double)k.b[1][2] * y1 - (long double)k.a[1][1] * y2;
+        }
+        for (int row = 0; row < 4; ++row) {
+            m->k.P[row * 4 + col] = (double)s[row];
+            m->k.Plo[row * 4 + col] = (double)(s[row] - (long double)m->k.P[row * 4 + col]);
+        }
     }
     *out = m;
     return VQCPC_OK;
