@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One line per kernel of a .hip file: VGPRs, SGPRs, spills, scratch, occupancy (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python tools/kernel_resources.py vectorquantizedcpc_amd/csrc/ar_xcd.hip [name filter]
+    python tools/kernel_resources.py vectorquantizedcpc_amd/csrc/ar_xcd.hip [name filter [extra compiler flags, e.g. -DXD_A16=0]]
 
 Rows are keyed on the MANGLED name (kernels in an anonymous namespace demangle to names that all begin with "(anonymous
 namespace)::", and template instantiations share everything in front of their arguments); the demangled name is what is printed.
@@ -12,7 +12,7 @@ import sys
 
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
-out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
+out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", *sys.argv[3:],
                       "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
 cur = None
 rows = {}

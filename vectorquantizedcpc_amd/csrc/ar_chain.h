@@ -18,10 +18,12 @@ constexpr int NT_A = HF / 8;           // terms of a chain over a: 32
 
 // exchange area of one XCD, in granules
 __host__ __device__ constexpr int xg_h(int bxt) { return NW * bxt * 32; }         // [rank][slot][32] (28 used: two whole lines)
-__host__ __device__ constexpr int xg_a(int bxt) { return NW * bxt * FPB; }        // [rank][slot][8]
+__host__ __device__ constexpr int xg_a(int bxt) { return bxt * NW * FPB; }        // [slot][rank][8]: the 256 granules of a slot are one run of 2 KB
 __host__ __device__ constexpr int xg_c() { return NW * 16; }                      // [slot < 16][rank]: a slot's 32 candidates are contiguous
 __host__ __device__ constexpr int xg_region(int bxt) { return xg_h(bxt) + xg_a(bxt) + xg_c(); }
 constexpr int CTL_WORDS = 64;          // u32: arrivals per XCC [0..7], total [8]
+// byte offset of a_t row `row` (0..7) of worker `rank`, slot `slot`, in the a_t region
+__device__ __forceinline__ unsigned xg_a_off(unsigned rank, unsigned row, unsigned slot) { return (((slot * NW + rank) << 3) + row) * 8u; }
 
 
 
@@ -46,11 +48,12 @@ __device__ __forceinline__ void gran_load4(u64 (&v)[4], const u64 *base, unsigne
                  "global_load_dwordx2 %2, %4, %5 offset:%7 sc1\n\tglobal_load_dwordx2 %3, %4, %5 offset:%8 sc1\n\ts_waitcnt vmcnt(0)"
                  : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(off), "s"(base), "i"(STEP), "i"(2 * STEP), "i"(3 * STEP) : "memory");
 }
-template <int STEP>     // granules at off, off + STEP (from base) and the same two from base2
-__device__ __forceinline__ void gran_load4b(u64 (&v)[4], const u64 *base, const u64 *base2, unsigned off) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %4, %5 sc1\n\tglobal_load_dwordx2 %1, %4, %5 offset:%7 sc1\n\t"
-                 "global_load_dwordx2 %2, %4, %6 sc1\n\tglobal_load_dwordx2 %3, %4, %6 offset:%7 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(off), "s"(base), "s"(base2), "i"(STEP) : "memory");
+// Two 16-byte chunks 1 KB apart, each TWO neighbouring granules, each granule validated by its own tag as ever (its publisher wrote it
+// with one 8-byte store): from L2 an 8-byte sc1 access moves 0.54..0.70 of what a 16-byte one does.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void gran_chunks2(u32x4 (&v)[2], const u64 *base, unsigned off) {
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %3 sc1\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024 sc1\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]) : "v"(off), "s"(base) : "memory");
 }
 template <int STEP>     // the same for two slots (second slot SLOT2 bytes further): eight granules in flight together
 __device__ __forceinline__ void gran_load8b(u64 (&v)[2][4], const u64 *base, const u64 *base2, unsigned off) {

@@ -36,6 +36,9 @@
 //                next step's Gumbel noise (Philox + two logs per class); x_t from the slot's 32 candidates, picked up
 //                before barrier B
 //   all waves    sweep h_t into LDS
+// Exchange regions of an XCD (ar_chain.h): h_t [rank][slot][32 units], swept with 8-byte loads; a_t [slot][rank][8] -- a slot's 256
+// granules in one run, which a lane of the slot's fc2 wave takes as two 16-byte loads of two granules each; candidates [slot][rank].
+// Every granule is published by one 8-byte store and validated by its own tag, whatever the width of the load that fetched it.
 // Four slots per XCD, what differs: every wave runs ONE dependent chain of 112 matrix instructions per step (waves 2..11 rows
 // 0..79 with pinned weights, wave 0 fc1 for all four slots and wave 1 W_hh rows 80..83, both with weights streamed from LDS);
 // fc2 + draw of slots 0..3 on waves 2, 3, 6, 7; waves 4 and 8 -- fc1's SIMD mates -- start their chains when a_t is out (two
@@ -104,6 +107,12 @@ extern "C" int vqcpc_debug_xd_bars(unsigned long long *out) {
 // four slots per XCD: the two chain waves on fc1's SIMD start their chains when a_t is out (0: at once -- A/B builds, profiles/r04_mfma_chains.txt)
 #ifndef XD_HOLD
 #define XD_HOLD 1
+#endif
+
+// the a_t sweep of an fc2 wave takes its four granules as two 16-byte loads (0: as four 8-byte loads of the same region -- A/B builds,
+// profiles/r07_ab_exchange_sweeps.txt)
+#ifndef XD_A16
+#define XD_A16 1
 #endif
 
 namespace {
@@ -265,7 +274,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 float v = chain_combine(chain_regs<NT_H>(w1, opnd));
                 v += b1;
                 v = v > 0.f ? v : 0.f;
-                if (sum_lane) xd_put(ga, (((unsigned)(rank * BXT) << 3) + r8) * 8u, ((u64)tag << 32) | __float_as_uint(v), agent);
+                if (sum_lane) xd_put(ga, xg_a_off((unsigned)rank, r8, 0u), ((u64)tag << 32) | __float_as_uint(v), agent);
                 XD_STAMP(1, 10);
                 XD_BARRIVE();
                 ps_barrier();                                            // B
@@ -302,18 +311,39 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
             XD_BLEAVE(0);
             if (*s_abort) break;
             auto fc2_and_draw = [&]() {
-                // ---- a_t of slot `wave` (256 granules, 4 per lane) -> fc2 -> Gumbel-max candidate of the 8 owned classes
-                const unsigned aoff = (((((lane >> 3) * BXT) + (unsigned)fs) << 3) + (lane & 7u)) * 8u;
+                // ---- a_t of slot fs (256 granules in one run, 4 per lane) -> fc2 -> Gumbel-max candidate of the 8 owned classes
+#if XD_A16
+                // the lane's granules are the 16-byte chunks lane and lane + 64 of the run: a_t[2 lane], a_t[2 lane + 1] and the same 128 further
+                const unsigned aoff = xg_a_off(0u, 0u, (unsigned)fs) + lane * 16u;
+                const unsigned adst = (unsigned)chain_pos<HF / 64>(2 * (int)lane, 48);   // a_t[k + 1]: the chain next door (48 further), a_t[k + 128]: 192 further
+#else
+                const unsigned aoff = xg_a_off(0u, 0u, (unsigned)fs) + lane * 8u;
                 const unsigned adst = (unsigned)chain_pos<HF / 64>((int)lane, 48);      // a_t[lane + 64 i]: chain 2 i + (lane & 1), i.e. 96 i further
+#endif
                 float4 wa = wp2[0], wb = wp2[64];                    // first weights and the noise: on their way during the sweep
                 unsigned lno = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));      // the lane id, from the hardware
                 asm volatile("" : "+v"(lno));      // opaque, and rebuilt: the hoisted address of this read -- then r8, then the lane id
                 const unsigned r8o = ((lno >> 5) << 2) | (lno & 3u);      // itself -- was spilled to scratch and reloaded at every step
                 const float nz = noise[(t & 1) * (BXT * 8) + fs * 8 + r8o];
+#if XD_A16
+                u32x4 va[2];
+                wt.start();
+                for (unsigned spins = 0;; ++spins) {
+                    gran_chunks2(va, ga, aoff);
+                    const bool ok = va[0][1] == tag && va[0][3] == tag && va[1][1] == tag && va[1][3] == tag;
+                    if ((XD_ABLATE & 2) || __all(ok)) break;
+                    if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    ac[fs * (8 * 48) + 192 * i + adst] = __uint_as_float(va[i][0]);
+                    ac[fs * (8 * 48) + 192 * i + 48 + adst] = __uint_as_float(va[i][2]);
+                }
+#else
                 u64 va[4];
                 wt.start();
                 for (unsigned spins = 0;; ++spins) {
-                    gran_load4b<512 * BXT>(va, ga, ga + 128 * BXT, aoff);
+                    gran_load4<512>(va, ga, aoff);
                     bool ok = true;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ok &= (unsigned)(va[i] >> 32) == tag;
@@ -322,6 +352,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ac[fs * (8 * 48) + 96 * i + adst] = __uint_as_float((unsigned)va[i]);
+#endif
                 XD_STAMP(2, 8);
                 const float4 a0 = *(const float4 *)opnd2, a1 = *(const float4 *)(opnd2 + 16);
                 const float hv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -571,7 +602,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                         float v = chain_combine(a4[i]);                  // fc1 row 4 rq + i of slot j
                         v += b1q[i];
                         v = v > 0.f ? v : 0.f;
-                        if (sum_lane && (int)j < bx) xd_put(ga, (((unsigned)(rank * BXT) + j) << 3) * 8u + (4u * rq + (unsigned)i) * 8u, ((u64)tag << 32) | __float_as_uint(v), agent);
+                        if (sum_lane && (int)j < bx) xd_put(ga, xg_a_off((unsigned)rank, 4u * rq + (unsigned)i, j), ((u64)tag << 32) | __float_as_uint(v), agent);
                     }
 #if XD_HOLD
                     if (lane == 0) __hip_atomic_store(s_ctl + 5, (int)tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // a_t is out: waves 4 and 8 may start
@@ -590,12 +621,12 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 float v = chain_combine(accA);
                 v += b1;
                 v = v > 0.f ? v : 0.f;
-                if (sum_lane) xd_put(ga, (((unsigned)(rank * BXT + sv) << 3) + r8) * 8u, ((u64)tag << 32) | __float_as_uint(v), agent);
+                if (sum_lane) xd_put(ga, xg_a_off((unsigned)rank, r8, (unsigned)sv), ((u64)tag << 32) | __float_as_uint(v), agent);
                 if (n_own > 1) {
                     float v2 = chain_combine(accB);
                     v2 += b1;
                     v2 = v2 > 0.f ? v2 : 0.f;
-                    if (sum_lane) xd_put(ga, (((unsigned)(rank * BXT + sv + 2) << 3) + r8) * 8u, ((u64)tag << 32) | __float_as_uint(v2), agent);
+                    if (sum_lane) xd_put(ga, xg_a_off((unsigned)rank, r8, (unsigned)sv + 2u), ((u64)tag << 32) | __float_as_uint(v2), agent);
                 }
             }
             XD_STAMP(0, 5); if (wave == 0) XD_WSTAMP(2);
