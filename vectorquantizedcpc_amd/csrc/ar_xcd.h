@@ -1,4 +1,4 @@
-// One resident, weight-stationary sample-loop decoder per XCD (ar_xcd.hip) -- interface towards vocoder.hip.
+// One resident, weight-stationary sample-loop decoder per XCD (ar_xcd.hip) -- interface towards vocoder_host.hip (XdSeg is also the slot record of the launch path, ar_step.h).
 #pragma once
 #include "common.h"
 

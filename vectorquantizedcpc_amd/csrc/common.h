@@ -25,6 +25,9 @@ void vq_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
         }                                       \
     } while (0)
 
+// propagate a VQCPC_* status (encoder.hip and scan.hip spell out the same definition)
+#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -45,6 +48,7 @@ struct DevBuf {
         return VQCPC_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T **fresh() { release(); return (T **)&p; }    // for a callee that hipMallocs into *out (cap stays 0: size unrecorded)
     template <class T> T *as() const { return (T *)p; }
 };
 

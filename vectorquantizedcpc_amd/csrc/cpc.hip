@@ -19,8 +19,6 @@
 #include "cpc_protocol.h"
 
 int vq_require_gfx950();
-#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
 namespace {
 
 constexpr int CPC_TT = 16;           // anchors per workgroup

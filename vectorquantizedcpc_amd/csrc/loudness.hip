@@ -20,8 +20,6 @@
 #include <vector>
 
 int vq_require_gfx950();
-#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
 constexpr int LC = 128;                    // samples per chunk
 constexpr double BLOCK_S = 0.400, STEP = 1.0 - 0.75, GAMMA_ABS = -70.0;
 

@@ -13,8 +13,6 @@
 #include <vector>
 
 int vq_require_gfx950();
-#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
 struct vqcpc_melfront {
     int sr, n_fft, n_mels, hop, win;
     float fmin, preemph, top_db;

@@ -1,4 +1,4 @@
-// Vocoder scoring head (nll.hip): what vocoder.hip hands it after every chunk of the teacher-forced scan.
+// Vocoder scoring head (nll.hip): what vocoder_host.hip hands it after every chunk of the teacher-forced scan.
 #pragma once
 #include "common.h"
 

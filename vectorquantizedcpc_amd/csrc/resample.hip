@@ -10,8 +10,6 @@
 #include <vector>
 
 int vq_require_gfx950();
-#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
 struct vqcpc_resampler {
     int sr_in, sr_out;
     double ratio, scale, time_increment;
