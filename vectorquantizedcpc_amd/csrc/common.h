@@ -5,7 +5,9 @@
 #include <stddef.h>
 #include "../../include/vqcpc.h"
 
+// runtime.hip: the per-thread error string behind vqcpc_last_error, and the check every create call starts with
 void vq_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+int vq_require_gfx950();             // VQCPC_OK, or VQCPC_ERR_NO_DEVICE with the error set: the current device is not a gfx950
 
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
@@ -25,7 +27,7 @@ void vq_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
         }                                       \
     } while (0)
 
-// propagate a VQCPC_* status (encoder.hip and scan.hip spell out the same definition)
+// propagate a VQCPC_* status
 #define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -51,8 +53,16 @@ struct DevBuf {
     template <class T> T **fresh() { release(); return (T **)&p; }    // for a callee that hipMallocs into *out (cap stays 0: size unrecorded)
     template <class T> T *as() const { return (T *)p; }
 };
+// An owning device pointer: a DevBuf that reads as a T * and frees itself with the handle it is a member of.
+template <class T> struct DevPtr : DevBuf {
+    DevPtr() = default;
+    DevPtr(const DevPtr &) = delete;
+    DevPtr &operator=(const DevPtr &) = delete;
+    ~DevPtr() { release(); }
+    operator T *() const { return (T *)p; }
+};
 
-// ---- exact-chain GEMM (encoder.hip), also used for the hoisted projections of the vocoder.
+// ---- exact-chain GEMM (gemm_chain.hip), also used for the hoisted projections of the vocoder.
 // Y[m, n] = fold over K blocks of KC of an fp32 fma chain (k ascending, from 0) of
 // A[m, k] * W[n, k]; first block: (bias ? bias[n] + chain : chain), later: tot + chain.
 // A dense row-major (lda) ; W (N, K) row-major ; N % 64 == 0 ; K % 32 == 0 ; KC % 32 == 0.

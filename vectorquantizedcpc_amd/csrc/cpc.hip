@@ -18,7 +18,6 @@
 // tree) -- no float atomics anywhere, so equal inputs give equal bits.  Correct counts are integers.
 #include "cpc_protocol.h"
 
-int vq_require_gfx950();
 namespace {
 
 constexpr int CPC_TT = 16;           // anchors per workgroup

@@ -1,282 +1,26 @@
-// encoder.hip -- Encoder.encode / Encoder.forward on gfx950 (reference: model.py:43-155).
+// encoder.hip -- the kernels of Encoder.encode / Encoder.forward on gfx950 (reference: model.py:43-155); the handle and the
+// vqcpc_encoder_* entry points are in encoder_host.hip, the layered schedule's GEMM in gemm_chain.hip.
 //
 // Every kernel here reproduces the rounding sequence of the reference's PyTorch-CPU path
 // (oracle/vqcpc_oracle.c documents each order and tests pin it against the reference):
-//   * contractions are fp32 MFMA chains (v_mfma_f32_32x32x2_f32 == a k-ordered fmaf chain),
+//   * contractions are fp32 MFMA chains (v_mfma_f32_16x16x4_f32 == a k-ordered fmaf chain),
 //     restarted at the K-block boundaries the reference's MKL / oneDNN kernels use;
 //   * LayerNorm moments follow ATen's 8-lane Welford cascade;
 //   * |x|^2 follows ATen's cascade_sum order; the VQ distance is one fma per (row, code).
 // Build with -ffp-contract=off: every fused multiply-add below is written explicitly.
-#include "common.h"
+#include "encoder_internal.h"
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-#include <vector>
-
-// ------------------------------------------------------------------------------------------
-// error plumbing + device query
-// ------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void vq_set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-extern "C" const char *vqcpc_last_error(void) { return g_err; }
-extern "C" int vqcpc_abi_version(void) { return VQCPC_ABI_VERSION; }
-extern "C" int vqcpc_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    int ok = 0;
-    for (int i = 0; i < n; ++i) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, i) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++ok;
-    }
-    return ok;
-}
-static int require_gfx950() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        vq_set_error("no HIP device: libvqcpc_hip has no CPU fallback");
-        return VQCPC_ERR_NO_DEVICE;
-    }
-    hipDeviceProp_t p;
-    HIP_TRY(hipGetDeviceProperties(&p, dev));
-    if (strncmp(p.gcnArchName, "gfx950", 6) != 0) {
-        vq_set_error("device %d is %s; this library is built for gfx950 (MI355X) only", dev, p.gcnArchName);
-        return VQCPC_ERR_NO_DEVICE;
-    }
-    return VQCPC_OK;
-}
-int vq_require_gfx950() { return require_gfx950(); }
-
-// ------------------------------------------------------------------------------------------
-// Exact-chain GEMM: 64x64 output tile per 256-thread workgroup, 4 waves as 2x2 of 32x32,
-// one v_mfma_f32_32x32x2_f32 per two k.  LDS tiles are k-major ([k][row], stride 65) so the
-// MFMA operand reads are conflict-free row-contiguous b32 reads.
-// ------------------------------------------------------------------------------------------
-#define GT_BM 64
-#define GT_BN 64
-#define GT_BK 32
-#define GT_LD 65
-
-struct GemmP {
-    const float *A; int lda;
-    const float *W;            // (N, K) row-major
-    const float *bias;         // (N) or null
-    float *Y; int ldy;
-    int M, N, K, KC;
-    // im2col source (AMODE 1/2): mel (B, C, T)
-    const float *x; int C, T, To;
-    // epilogue extras (vq_gemm_chain_ex): ReLU; output row m -> (m / ydiv) * ystride + yoff + m % ydiv, rows whose
-    // yoff + m % ydiv >= ylim are not stored (ydiv == 0: row m)
-    int relu, ydiv, ystride, yoff, ylim;
-};
-
-template <int AMODE>
-__device__ __forceinline__ void fetch_a(const GemmP &p, int m0, int k0, int tid, float (&v)[8]) {
-    const int row = tid >> 2, kq = (tid & 3) * 8;
-    const int m = m0 + row;
-    if (AMODE == 0) {
-        if (m < p.M) {
-            const float4 *src = (const float4 *)(p.A + (size_t)m * p.lda + k0 + kq);
-            float4 a = src[0], b = src[1];
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = 0.f;
-        }
-    } else {
-        int b = 0, tt = 0;
-        if (m < p.M) { b = m / p.To; tt = m - b * p.To; }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int kidx = k0 + kq + i;
-            int c, tap;
-            if (AMODE == 1) { c = kidx >> 2; tap = kidx & 3; }
-            else { const int rem = kidx & 63; tap = rem >> 4; c = (kidx >> 6) * 16 + (rem & 15); }
-            const int ti = 2 * tt + tap - 1;
-            v[i] = (m < p.M && ti >= 0 && ti < p.T) ? p.x[((size_t)b * p.C + c) * p.T + ti] : 0.f;
-        }
-    }
-}
-__device__ __forceinline__ void fetch_w(const GemmP &p, int n0, int k0, int tid, float (&v)[8]) {
-    const int row = tid >> 2, kq = (tid & 3) * 8;
-    const float4 *src = (const float4 *)(p.W + (size_t)(n0 + row) * p.K + k0 + kq);
-    float4 a = src[0], b = src[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void stage(float (*T)[GT_LD], int tid, const float (&v)[8]) {
-    const int row = tid >> 2, kq = (tid & 3) * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) T[kq + i][row] = v[i];
-}
-
-__device__ __forceinline__ void gemm_epilogue(const GemmP &p, const f32x16 &tot, int m0, int wm, int half, int col) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (m >= p.M) continue;
-        size_t row = (size_t)m;
-        if (p.ydiv > 0) {
-            const int q = m / p.ydiv, t = p.yoff + (m - q * p.ydiv);
-            if (t >= p.ylim) continue;
-            row = (size_t)q * p.ystride + t;
-        }
-        const float v = tot[r];
-        p.Y[row * p.ldy + col] = (p.relu && v < 0.f) ? 0.f : v;
-    }
-}
-
-// Software pipeline.  A loop that does, per k tile, {wait for global loads, 16 LDS stores, barrier, 32 LDS
-// operand reads} and then its 16 MFMAs pays for both halves: measured on MI355X, 17 us of MFMA + 16 us of
-// LDS work for a 4096 x 512 x 512 layer that ran 28.6 us (tools/microbench_mfma.hip).  Here the
-// LDS tiles are double-buffered and every MFMA gap carries its share of the other work, in program order
-// (pinned with sched_barrier): MFMAs 0-7 of tile k are interleaved with the LDS stores of tile k+1, then the
-// global loads of tile k+2 are requested, one barrier, and MFMAs 8-15 are interleaved with the operand
-// reads of tile k+1 into a second register set.  22.5 us for the same layer, same k order, same bits.
-template <int AMODE, int C>
-__device__ __forceinline__ void pipe_body(const GemmP &p, float (*As)[GT_BK][GT_LD], float (*Ws)[GT_BK][GT_LD], int tid,
-                                          int m0, int n0, int k2, float (&va)[8], float (&vw)[8], float (&oa)[2][16],
-                                          float (&ob)[2][16], f32x16 &acc, int acol, int bcol, int half) {
-    const int row = tid >> 2, kq = (tid & 3) * 8;
-    float (*An)[GT_LD] = As[C ^ 1];
-    float (*Wn)[GT_LD] = Ws[C ^ 1];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(oa[C][j], ob[C][j], acc, 0, 0, 0);
-        An[kq + j][row] = va[j];
-        Wn[kq + j][row] = vw[j];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    fetch_a<AMODE>(p, m0, k2, tid, va);
-    fetch_w(p, n0, k2, tid, vw);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(oa[C][8 + j], ob[C][8 + j], acc, 0, 0, 0);
-        oa[C ^ 1][2 * j] = An[4 * j + half][acol];
-        oa[C ^ 1][2 * j + 1] = An[4 * j + 2 + half][acol];
-        ob[C ^ 1][2 * j] = Wn[4 * j + half][bcol];
-        ob[C ^ 1][2 * j + 1] = Wn[4 * j + 2 + half][bcol];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-__device__ __forceinline__ void fold_chain(const GemmP &p, f32x16 &acc, f32x16 &tot, bool &first, float bv) {
-    if (first) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot[r] = p.bias ? bv + acc[r] : acc[r];
-        first = false;
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot[r] = tot[r] + acc[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-}
-
-template <int AMODE>
-__global__ __launch_bounds__(256) void gemm_chain_kernel(GemmP p) {
-    __shared__ float As[2][GT_BK][GT_LD];
-    __shared__ float Ws[2][GT_BK][GT_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, half = lane >> 5, li = lane & 31;
-    const int n0 = blockIdx.x * GT_BN, m0 = blockIdx.y * GT_BM;
-    const int col = n0 + wn * 32 + li, acol = wm * 32 + li, bcol = wn * 32 + li;
-    const int nt = p.K / GT_BK, tpb = p.KC / GT_BK;
-
-    f32x16 acc, tot;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; tot[r] = 0.f; }
-    bool first = true;
-    const float bv = p.bias ? p.bias[col] : 0.f;
-
-    float va[8], vw[8], oa[2][16], ob[2][16];
-    fetch_a<AMODE>(p, m0, 0, tid, va);
-    fetch_w(p, n0, 0, tid, vw);
-    stage(As[0], tid, va);
-    stage(Ws[0], tid, vw);
-    const int k1 = nt > 1 ? GT_BK : 0;
-    fetch_a<AMODE>(p, m0, k1, tid, va);
-    fetch_w(p, n0, k1, tid, vw);
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-        oa[0][kk] = As[0][2 * kk + half][acol];
-        ob[0][kk] = Ws[0][2 * kk + half][bcol];
-    }
-
-    int k = 0;
-    for (; k + 2 < nt; k += 2) {
-        pipe_body<AMODE, 0>(p, As, Ws, tid, m0, n0, (k + 2) * GT_BK, va, vw, oa, ob, acc, acol, bcol, half);
-        if ((k + 1) % tpb == 0) fold_chain(p, acc, tot, first, bv);
-        pipe_body<AMODE, 1>(p, As, Ws, tid, m0, n0, (k + 3 < nt ? k + 3 : nt - 1) * GT_BK, va, vw, oa, ob, acc, acol, bcol, half);
-        if ((k + 2) % tpb == 0) fold_chain(p, acc, tot, first, bv);
-    }
-    if (k + 1 < nt) {                                                 // two tiles left
-        pipe_body<AMODE, 0>(p, As, Ws, tid, m0, n0, (nt - 1) * GT_BK, va, vw, oa, ob, acc, acol, bcol, half);
-        if ((k + 1) % tpb == 0) fold_chain(p, acc, tot, first, bv);
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(oa[1][kk], ob[1][kk], acc, 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(oa[0][kk], ob[0][kk], acc, 0, 0, 0);
-    }
-    fold_chain(p, acc, tot, first, bv);
-
-    gemm_epilogue(p, tot, m0, wm, half, col);
-}
-
-template <int AMODE>
-static int launch_gemm(const GemmP &p, hipStream_t s) {
-    VQ_REQUIRE(p.N % GT_BN == 0 && p.K % GT_BK == 0 && p.KC % GT_BK == 0 && p.M > 0,
-               "gemm_chain: unsupported shape M=%d N=%d K=%d KC=%d", p.M, p.N, p.K, p.KC);
-    dim3 grid(p.N / GT_BN, (p.M + GT_BM - 1) / GT_BM);
-    hipLaunchKernelGGL((gemm_chain_kernel<AMODE>), grid, dim3(256), 0, s, p);
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
-
-int vq_gemm_chain(const float *A, int lda, const float *W, const float *bias, float *Y, int ldy,
-                  int M, int N, int K, int KC, hipStream_t s) {
-    VQ_REQUIRE(lda % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
-               "gemm_chain: operands must be 16-byte aligned");
-    GemmP p{};
-    p.A = A; p.lda = lda; p.W = W; p.bias = bias; p.Y = Y; p.ldy = ldy;
-    p.M = M; p.N = N; p.K = K; p.KC = KC;
-    return launch_gemm<0>(p, s);
-}
-
-int vq_gemm_chain_ex(const float *A, int lda, const float *W, const float *bias, float *Y, int ldy,
-                     int M, int N, int K, int KC, int relu, int ydiv, int ystride, int yoff, int ylim, hipStream_t s) {
-    VQ_REQUIRE(lda % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
-               "gemm_chain: operands must be 16-byte aligned");
-    GemmP p{};
-    p.A = A; p.lda = lda; p.W = W; p.bias = bias; p.Y = Y; p.ldy = ldy;
-    p.M = M; p.N = N; p.K = K; p.KC = KC;
-    p.relu = relu; p.ydiv = ydiv; p.ystride = ystride; p.yoff = yoff; p.ylim = ylim;
-    return launch_gemm<0>(p, s);
-}
 
 // ------------------------------------------------------------------------------------------
 // LayerNorm(512) + optional ReLU, ATen CPU order (see oracle orc_ln_moments).
 // One half-wave (32 lanes) per row: lane = chunk*8 + l runs the Welford chain of vector lane
 // l over chunk `chunk` (16 vectors of 8), merges by shuffles, then all lanes normalise.
 // ------------------------------------------------------------------------------------------
-struct LnConst { float inv[16]; float sc[8]; };
-
-__global__ __launch_bounds__(256) void ln512_kernel(const float *__restrict__ X, const float *__restrict__ g,
-                                                    const float *__restrict__ b, float *__restrict__ Y, int M,
-                                                    float eps, int relu, LnConst k) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int half = lane >> 5, ll = lane & 31;
-    const int row = (blockIdx.x * 4 + wave) * 2 + half;
-    const int rr = row < M ? row : M - 1;
-    const float *x = X + (size_t)rr * 512;
+// (mean, rstd) of the 512-float row x (global or LDS) on the calling thread's half-wave; every lane of it returns them.
+// (The half-wave and the lane in it are taken from threadIdx here: handed in as arguments, the same values cost ln512_kernel
+// 15 instructions and enc_fused_kernel 4 VGPRs -- and with them its third wave per SIMD.)
+__device__ __forceinline__ float2 ln512_moments(const float *x, const LnConst &k, float eps) {
+    const int lane = threadIdx.x & 63, half = lane >> 5, ll = lane & 31;
     const int chunk = ll >> 3, l = ll & 7;
     float m1 = 0.f, m2 = 0.f;
 #pragma unroll
@@ -311,10 +55,22 @@ __global__ __launch_bounds__(256) void ln512_kernel(const float *__restrict__ X,
         M1 = __builtin_fmaf(k.sc[q], delta, M1);
         M2 = M2 + __builtin_fmaf((delta * delta) * k.sc[q], (float)(64 * q), s2);
     }
-    const float mean = M1, var = M2 / 512.0f;
+    const float var = M2 / 512.0f;
     // 1 / sqrt(var + eps), both correctly rounded in fp32 (via fp64: innocuous double rounding)
     const float sd = (float)sqrt((double)(var + eps));
-    const float rstd = (float)(1.0 / (double)sd);
+    return make_float2(M1, (float)(1.0 / (double)sd));
+}
+
+__global__ __launch_bounds__(256) void ln512_kernel(const float *__restrict__ X, const float *__restrict__ g,
+                                                    const float *__restrict__ b, float *__restrict__ Y, int M,
+                                                    float eps, int relu, LnConst k) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int half = lane >> 5, ll = lane & 31;
+    const int row = (blockIdx.x * 4 + wave) * 2 + half;
+    const int rr = row < M ? row : M - 1;
+    const float *x = X + (size_t)rr * 512;
+    const float2 mr = ln512_moments(x, k, eps);
+    const float mean = mr.x, rstd = mr.y;
     if (row < M) {
         float *y = Y + (size_t)row * 512;
 #pragma unroll
@@ -386,6 +142,21 @@ __device__ __forceinline__ void vq_take(const f32x4 &acc, int code, float e2, co
     for (int r = 0; r < 4; ++r) {
         const float d = __builtin_fmaf(-2.0f, acc[r], e2 + x2[r]);
         if (d < bd[r]) { bd[r] = d; bj[r] = code; }
+    }
+}
+
+// Waves of a 512-thread workgroup that search: all 8 when the 16-code tiles divide among them, else 4 (vq_encode_kernel has 4).
+__device__ __forceinline__ int vq_search_waves(int n_emb) { return n_emb % 128 == 0 ? 8 : 4; }
+// The first two codebook tiles of a searching wave, requested ahead of the rows (vq_rows16 takes them as f0_in / f1_in): a wave
+// owns n_emb / (16 nwv) consecutive tiles, and one with a single tile gets it twice.
+__device__ __forceinline__ void vq_first_tiles(const float4 *__restrict__ Ef, int n_emb, int nwv, int wave, int lane, float4 (&f0)[4],
+                                               float4 (&f1)[4]) {
+    const int tpw = n_emb / (16 * nwv), t0 = wave * tpw;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) f0[q] = f1[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (wave < nwv) {
+        vq_load_tile(Ef, t0, lane, f0);
+        vq_load_tile(Ef, tpw > 1 ? t0 + 1 : t0, lane, f1);
     }
 }
 
@@ -495,13 +266,39 @@ __global__ __launch_bounds__(256) void vq_encode_kernel(const float *__restrict_
         sm.xs[row][4 * c4 + 0] = v.x; sm.xs[row][4 * c4 + 1] = v.y; sm.xs[row][4 * c4 + 2] = v.z; sm.xs[row][4 * c4 + 3] = v.w;
     }
     if (tid < 16) sm.x2s[tid] = r0 + tid < N ? sumsq64(X + (size_t)(r0 + tid) * 64) : 0.f;
-    const int tpw = n_emb / 64, t0 = wave * tpw;
     float4 f0[4], f1[4];
-    vq_load_tile(Ef, t0, lane, f0);
-    if (tpw > 1) vq_load_tile(Ef, t0 + 1, lane, f1);
-    else vq_load_tile(Ef, t0, lane, f1);
+    vq_first_tiles(Ef, n_emb, 4, wave, lane, f0, f1);
     __syncthreads();
     vq_rows16(sm, r0, N, Ef, E, e2, n_emb, idx, zq, tid, f0, f1);
+}
+
+// encoder.14's tail for a 512-thread workgroup whose wave ct + 4 kh holds chain kh (k < 256, k >= 256) of column tile ct in zt:
+// the reference's fold is (bias + c0) + c1, so c1 is handed over through the LDS scratch `part` (element [ct][row][col] at
+// ct * TS + row * RS + col), the kh = 0 waves write z to sm.xs (and z_pre), and the VQ search runs on all of it (model.py:103-115).
+// stop_at_z: z_pre is all the caller wants.
+template <int TS, int RS>
+__device__ __forceinline__ void rows16_finish_z(const FusedP &p, VqSmem &sm, float *part, const f32x4 &zt, int ct, int kh, int r0,
+                                                int tid, const float4 (&f0)[4], const float4 (&f1)[4], int nwv, bool stop_at_z) {
+    const int lane = tid & 63;
+    if (kh == 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[ct * TS + (4 * (lane >> 4) + r) * RS + (lane & 15)] = zt[r];
+    }
+    __syncthreads();
+    if (kh == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * (lane >> 4) + r, col = 16 * ct + (lane & 15);
+            const float z = zt[r] + part[ct * TS + row * RS + (lane & 15)];
+            sm.xs[row][col] = z;
+            if (p.z_pre && r0 + row < p.N) p.z_pre[(size_t)(r0 + row) * 64 + col] = z;
+        }
+    }
+    __syncthreads();
+    if (stop_at_z) return;
+    if (tid < 16) sm.x2s[tid] = r0 + tid < p.N ? sumsq64(&sm.xs[tid][0]) : 0.f;
+    __syncthreads();
+    vq_rows16(sm, r0, p.N, p.Ef, p.E, p.e2, p.n_emb, p.idx, p.z_q, tid, f0, f1, nwv);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -530,19 +327,6 @@ __global__ void frag16_build_kernel(const float *__restrict__ W, int N, int K, f
     const float *r = W + (size_t)(16 * ct + (lane & 15)) * K + 16 * q + (lane >> 4);
     Wf[id] = make_float4(r[0], r[4], r[8], r[12]);
 }
-
-struct FusedP {
-    const float *mel; int C, T, To, N;
-    int conv_mode;                      // 1 im2col order (one chain), 2 direct order (chain restarted every 64 k)
-    const float4 *conv_f;               // conv weight fragments in that order: [32 ct][K/16][64]
-    const float *ln_g[5], *ln_b[5];
-    const float4 *fc_f[4];              // [32 ct][32][64]
-    const float4 *out_f; const float *out_b;   // [4 ct][32][64]
-    const float4 *Ef; const float *E, *e2; int n_emb;
-    float *z_pre; float *z_q; int64_t *idx;
-    float *stage_out; int stage;        // stage dump (vqcpc_encoder_stage): -1 = none
-    float eps; LnConst lnc;
-};
 
 // One GEMM stage for this wave: tile (LDS, 16 rows x K) x NT column tiles starting at ct0.  tot = fold over K blocks of
 // kcq q-steps (16 k each) of zero-started chains: first block (bias ? bias + chain : chain), later blocks tot + chain.
@@ -625,76 +409,25 @@ __device__ __forceinline__ void rows16_store(float *tile, const f32x4 (&tot)[NT]
         for (int r = 0; r < 4; ++r) tile[(4 * (lane >> 4) + r) * FE_LD + 16 * (ct0 + j) + (lane & 15)] = tot[j][r];
 }
 
-// LayerNorm(512) + ReLU of the tile in place: the half-wave-per-row procedure of ln512_kernel (ATen's order).  A half-wave
-// owns rows r and r + 8 and runs their two (serial, latency-bound) moment cascades interleaved; it then normalises both
-// (R = 2, 256-thread workgroups); with 512 threads every half-wave has one row (R = 1).
-template <int R>
+// LayerNorm(512) + ReLU of the tile in place, a half-wave per row as ln512_kernel (512 threads: 16 half-waves, 16 rows).
 __device__ __forceinline__ void rows16_layernorm(float *tile, const float *__restrict__ g, const float *__restrict__ b,
                                                  float eps, const LnConst &k, int tid) {
     const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, ll = lane & 31;
-    const int chunk = ll >> 3, l = ll & 7;
-    float *x[2] = {tile + (wave * 2 + half) * FE_LD, tile + ((R == 2 ? 8 : 0) + wave * 2 + half) * FE_LD};
-    float m1[2] = {0.f, 0.f}, m2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float xv = x[r][(chunk * 16 + j) * 8 + l];
-            const float d = xv - m1[r];
-            m1[r] = __builtin_fmaf(d, k.inv[j], m1[r]);
-            m2[r] = __builtin_fmaf(d, xv - m1[r], m2[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {                                       // chunk 1 -> 0, 3 -> 2 (16 + 16 vectors)
-        const float a1 = __shfl_down(m1[r], 8), a2 = __shfl_down(m2[r], 8);
-        const float delta = a1 - m1[r];
-        const float n1 = __builtin_fmaf(0.5f, delta, m1[r]);
-        m2[r] = __builtin_fmaf((0.5f * 16.0f) * delta, delta, m2[r] + a2);
-        m1[r] = n1;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {                                       // (chunks 2, 3) -> (chunks 0, 1) (32 + 32 vectors)
-        const float a1 = __shfl_down(m1[r], 16), a2 = __shfl_down(m2[r], 16);
-        const float delta = a1 - m1[r];
-        const float n1 = __builtin_fmaf(0.5f, delta, m1[r]);
-        m2[r] = __builtin_fmaf((0.5f * 32.0f) * delta, delta, m2[r] + a2);
-        m1[r] = n1;
-    }
-    float M1[2] = {0.f, 0.f}, M2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {                                       // the 8 vector lanes, serially
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float s1 = __shfl(m1[r], half * 32 + q), s2 = __shfl(m2[r], half * 32 + q);
-            const float delta = s1 - M1[r];
-            M1[r] = __builtin_fmaf(k.sc[q], delta, M1[r]);
-            M2[r] = M2[r] + __builtin_fmaf((delta * delta) * k.sc[q], (float)(64 * q), s2);
-        }
-    }
-    float mean[2], rstd[2];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        mean[r] = M1[r];
-        const float var = M2[r] / 512.0f;
-        const float sd = (float)sqrt((double)(var + eps));              // both correctly rounded in fp32 (via fp64)
-        rstd[r] = (float)(1.0 / (double)sd);
-    }
+    float *x = tile + (wave * 2 + half) * FE_LD;
+    const float2 mr = ln512_moments(x, k, eps);
+    const float mean = mr.x, rstd = mr.y;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int e = q * 64 + ll * 2;                                  // 8-byte LDS accesses (the row stride is 8 mod 16)
         const float2 gv = *(const float2 *)(g + e);
         const float2 bb = *(const float2 *)(b + e);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float2 xv = *(const float2 *)(x[r] + e);
-            float2 o;
-            o.x = __builtin_fmaf((xv.x - mean[r]) * rstd[r], gv.x, bb.x);
-            o.y = __builtin_fmaf((xv.y - mean[r]) * rstd[r], gv.y, bb.y);
-            o.x = o.x < 0.f ? 0.f : o.x;
-            o.y = o.y < 0.f ? 0.f : o.y;
-            *(float2 *)(x[r] + e) = o;
-        }
+        const float2 xv = *(const float2 *)(x + e);
+        float2 o;
+        o.x = __builtin_fmaf((xv.x - mean) * rstd, gv.x, bb.x);
+        o.y = __builtin_fmaf((xv.y - mean) * rstd, gv.y, bb.y);
+        o.x = o.x < 0.f ? 0.f : o.x;
+        o.y = o.y < 0.f ? 0.f : o.y;
+        *(float2 *)(x + e) = o;
     }
 }
 
@@ -721,7 +454,7 @@ __global__ __launch_bounds__(512) void enc_fused_kernel(FusedP p) {
     float4 fr[RD][NT];
     rows16_prefetch<NT, RD>(p.conv_f, NT * wave, K0 / 16, fr, lane);      // the first conv fragments fly under the gather
 
-    // ---- im2col of the 16 rows (model.py:65), k order of the reference back end (fetch_a).  When the 16 rows are consecutive
+    // ---- im2col of the 16 rows (model.py:65), k order of the reference back end (im2col_ct).  When the 16 rows are consecutive
     // frames of ONE utterance (always at configs[1]: 64 frames per utterance) their taps are a window of 34 mel frames per
     // channel: it is loaded ONCE, coalesced along T (136 contiguous bytes per channel instead of 16 x 4 scalar loads 8 bytes
     // apart), into LDS and the tile is built from there.  A tile that straddles two utterances (or the end) gathers from global.
@@ -739,22 +472,13 @@ __global__ __launch_bounds__(512) void enc_fused_kernel(FusedP p) {
         for (int e = tid; e < 16 * K0; e += 512) {
             const int i = e & 15, kidx = e >> 4;
             int c, tap;
-            if (p.conv_mode == 1) { c = kidx >> 2; tap = kidx & 3; }
-            else { const int rem = kidx & 63; tap = rem >> 4; c = (kidx >> 6) * 16 + (rem & 15); }
+            im2col_ct(p.conv_mode, kidx, c, tap);
             tile[i * FE_LD + kidx] = win[c * 36 + 2 * i + tap];
         }
     } else {
         for (int e = tid; e < 16 * K0; e += 512) {
-            const int i = e & 15, kidx = e >> 4, m = r0 + i;
-            int c, tap;
-            if (p.conv_mode == 1) { c = kidx >> 2; tap = kidx & 3; }
-            else { const int rem = kidx & 63; tap = rem >> 4; c = (kidx >> 6) * 16 + (rem & 15); }
-            float v = 0.f;
-            if (m < p.N) {
-                const int b = m / p.To, tt = m - b * p.To, ti = 2 * tt + tap - 1;
-                if (ti >= 0 && ti < p.T) v = p.mel[((size_t)b * p.C + c) * p.T + ti];
-            }
-            tile[i * FE_LD + kidx] = v;
+            const int i = e & 15, kidx = e >> 4;
+            tile[i * FE_LD + kidx] = im2col_at(p.mel, p.C, p.T, p.To, p.N, r0 + i, kidx, p.conv_mode);
         }
     }
     __syncthreads();
@@ -767,7 +491,7 @@ __global__ __launch_bounds__(512) void enc_fused_kernel(FusedP p) {
     if (rows16_dump(p, tile, 0, r0, tid)) return;
 
     // ---- seg-FC stack (model.py:46-55)
-    rows16_layernorm<1>(tile, p.ln_g[0], p.ln_b[0], p.eps, p.lnc, tid);
+    rows16_layernorm(tile, p.ln_g[0], p.ln_b[0], p.eps, p.lnc, tid);
     __syncthreads();
     if (rows16_dump(p, tile, 1, r0, tid)) return;
     for (int l = 0; l < 4; ++l) {
@@ -777,7 +501,7 @@ __global__ __launch_bounds__(512) void enc_fused_kernel(FusedP p) {
         rows16_store<NT>(tile, tot, NT * wave, lane);
         __syncthreads();
         if (rows16_dump(p, tile, 2 + 2 * l, r0, tid)) return;
-        rows16_layernorm<1>(tile, p.ln_g[l + 1], p.ln_b[l + 1], p.eps, p.lnc, tid);
+        rows16_layernorm(tile, p.ln_g[l + 1], p.ln_b[l + 1], p.eps, p.lnc, tid);
         __syncthreads();
         if (rows16_dump(p, tile, 3 + 2 * l, r0, tid)) return;
     }
@@ -786,39 +510,15 @@ __global__ __launch_bounds__(512) void enc_fused_kernel(FusedP p) {
     // zero-started chains (k < 256, k >= 256): wave w runs c0 of tile w, wave w + 4 runs c1 -- half the dependent MFMA chain
     // each -- and hands it over through LDS.  The VQ codebook tiles stream in underneath.
     const int ctw = wave & 3, kh = wave >> 2;
-    const int nwv = p.n_emb % 128 == 0 ? 8 : 4;          // waves of the VQ search
-    const int tpw = p.n_emb / (16 * nwv), t0 = (wave < nwv ? wave : 0) * tpw;
-    float4 f0[4] = {}, f1[4] = {};
-    if (wave < nwv) {
-        vq_load_tile(p.Ef, t0, lane, f0);
-        vq_load_tile(p.Ef, tpw > 1 ? t0 + 1 : t0, lane, f1);
-    }
+    const int nwv = vq_search_waves(p.n_emb);
+    float4 f0[4], f1[4];
+    vq_first_tiles(p.Ef, p.n_emb, nwv, wave, lane, f0, f1);
     f32x4 zt[1];
     float4 fr1[4][1];
     rows16_prefetch<1, 4>(p.out_f, ctw, 16, fr1, lane, 16 * kh, 32);
     rows16_gemm<1, 4>(tile, p.out_f, ctw, 16, 16, kh == 0 ? p.out_b : nullptr, zt, lane, fr1, 16 * kh, 32);
-    float (*c1s)[68] = (float (*)[68])tile;              // the activation tile is dead once every wave is past its chain
-    __syncthreads();
-    if (kh == 1) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c1s[4 * (lane >> 4) + r][16 * ctw + (lane & 15)] = zt[0][r];
-    }
-    __syncthreads();
-    if (kh == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 4 * (lane >> 4) + r, col = 16 * ctw + (lane & 15);
-            const float z = zt[0][r] + c1s[row][col];
-            sm.xs[row][col] = z;
-            if (p.z_pre && r0 + row < p.N) p.z_pre[(size_t)(r0 + row) * 64 + col] = z;
-        }
-    }
-    __syncthreads();
-    if (p.stage == 10) return;                           // z_pre is the stage output
-    // ---- VQ (model.py:103-115)
-    if (tid < 16) sm.x2s[tid] = r0 + tid < p.N ? sumsq64(&sm.xs[tid][0]) : 0.f;
-    __syncthreads();
-    vq_rows16(sm, r0, p.N, p.Ef, p.E, p.e2, p.n_emb, p.idx, p.z_q, tid, f0, f1, nwv);
+    __syncthreads();                                     // the activation tile is dead once every wave is past its chain:
+    rows16_finish_z<16, 68>(p, sm, tile, zt[0], ctw, kh, r0, tid, f0, f1, nwv, p.stage == 10);   // c1 goes through it as [16][68]
 }
 
 // ------------------------------------------------------------------------------------------
@@ -875,6 +575,31 @@ __device__ __forceinline__ f32x4 rows16_gemm_pre(const float *tile, const float4
     return tot;
 }
 
+// Prologue of a 512-thread launch that takes raw rows: rows r0 .. r0 + 15 of `in` (N x 512, zero past N) into the LDS tile, then
+// LayerNorm + ReLU in place.  vmcnt retires in order, so the rows' loads are issued FIRST and `issue_weights` -- the caller's
+// loads of its weight slice -- behind them: waiting for the rows then leaves the weights in flight under the LayerNorm.
+template <class F>
+__device__ __forceinline__ void rows16_load_ln(const float *__restrict__ in, int r0, int N, float *tile, const float *__restrict__ g,
+                                               const float *__restrict__ b, float eps, const LnConst &k, int tid, F issue_weights) {
+    float4 av[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int e = tid + 512 * n, row = e >> 7, c4 = e & 127;
+        av[n] = r0 + row < N ? ((const float4 *)in)[(size_t)(r0 + row) * 128 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    issue_weights();
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int e = tid + 512 * n, row = e >> 7, c4 = e & 127;
+        float *d = tile + row * FE_LD + 4 * c4;
+        *(float2 *)d = make_float2(av[n].x, av[n].y);
+        *(float2 *)(d + 2) = make_float2(av[n].z, av[n].w);
+    }
+    __syncthreads();
+    rows16_layernorm(tile, g, b, eps, k, tid);
+    __syncthreads();
+}
+
 // The three layer kinds of the split schedule for column group `cg` of the row tile at r0 (bodies of the enc_split_*_kernel launches):
 // conv (layer 0), Linear l = 1..4 (LayerNorm l-1 on load); encoder.14 + VQ (LayerNorm 4 on load) has a launch shape of its own.
 __device__ __forceinline__ void split_conv(const FusedP &p, float *__restrict__ out, int cg, int r0, float *tile) {
@@ -886,16 +611,8 @@ __device__ __forceinline__ void split_conv(const FusedP &p, float *__restrict__ 
     float gv[20];
 #pragma unroll
     for (int n = 0; n < 20; ++n) {
-        const int e = tid + 256 * n, i = e & 15, kidx = e >> 4, m = r0 + i;
-        int c, tap;
-        if (p.conv_mode == 1) { c = kidx >> 2; tap = kidx & 3; }
-        else { const int rem = kidx & 63; tap = rem >> 4; c = (kidx >> 6) * 16 + (rem & 15); }
-        float v = 0.f;
-        if (e < 16 * K0 && m < p.N) {
-            const int b = m / p.To, tt = m - b * p.To, ti = 2 * tt + tap - 1;
-            if (ti >= 0 && ti < p.T) v = p.mel[((size_t)b * p.C + c) * p.T + ti];
-        }
-        gv[n] = v;
+        const int e = tid + 256 * n;
+        gv[n] = e < 16 * K0 ? im2col_at(p.mel, p.C, p.T, p.To, p.N, r0 + (e & 15), e >> 4, p.conv_mode) : 0.f;
     }
     float4 wc[20];
     if (nq == 20) rows16_load_w<20>(p.conv_f, ct, lane, wc);          // C = 80 (the reference): whole slice up front
@@ -905,16 +622,7 @@ __device__ __forceinline__ void split_conv(const FusedP &p, float *__restrict__ 
         if (e < 16 * K0) tile[(e & 15) * FE_LD + (e >> 4)] = gv[n];
     }
     for (int e = tid + 256 * 20; e < 16 * K0; e += 256) {             // more than 80 channels: the rest, plainly
-        const int i = e & 15, kidx = e >> 4, m = r0 + i;
-        int c, tap;
-        if (p.conv_mode == 1) { c = kidx >> 2; tap = kidx & 3; }
-        else { const int rem = kidx & 63; tap = rem >> 4; c = (kidx >> 6) * 16 + (rem & 15); }
-        float v = 0.f;
-        if (m < p.N) {
-            const int b = m / p.To, tt = m - b * p.To, ti = 2 * tt + tap - 1;
-            if (ti >= 0 && ti < p.T) v = p.mel[((size_t)b * p.C + c) * p.T + ti];
-        }
-        tile[i * FE_LD + kidx] = v;
+        tile[(e & 15) * FE_LD + (e >> 4)] = im2col_at(p.mel, p.C, p.T, p.To, p.N, r0 + (e & 15), e >> 4, p.conv_mode);
     }
     __syncthreads();
     f32x4 tot;
@@ -940,27 +648,10 @@ __device__ __forceinline__ void split_conv(const FusedP &p, float *__restrict__ 
 __device__ __forceinline__ void split_fc(const FusedP &p, int layer, const float *__restrict__ in, float *__restrict__ out, int cg,
                                          int r0, float *tile, float (*part)[16][17]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // (vmcnt retires in order: the rows' loads go first, the weight slice behind them)
-    float4 av[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int e = tid + 512 * n, row = e >> 7, c4 = e & 127;
-        av[n] = r0 + row < p.N ? ((const float4 *)in)[(size_t)(r0 + row) * 128 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
     const int cl = wave & 3, ct = 4 * cg + cl, kh = wave >> 2;
     float4 wh[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) wh[q] = p.fc_f[layer - 1][((size_t)ct * 32 + 16 * kh + q) * 64 + lane];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int e = tid + 512 * n, row = e >> 7, c4 = e & 127;
-        float *d = tile + row * FE_LD + 4 * c4;
-        *(float2 *)d = make_float2(av[n].x, av[n].y);
-        *(float2 *)(d + 2) = make_float2(av[n].z, av[n].w);
-    }
-    __syncthreads();
-    rows16_layernorm<1>(tile, p.ln_g[layer - 1], p.ln_b[layer - 1], p.eps, p.lnc, tid);
-    __syncthreads();
+    rows16_load_ln(in, r0, p.N, tile, p.ln_g[layer - 1], p.ln_b[layer - 1], p.eps, p.lnc, tid,
+                   [&] { rows16_load_w<16>(p.fc_f[layer - 1], 2 * ct + kh, lane, wh); });
     const f32x4 acc = rows16_gemm_pre<1, 16>(tile + 256 * kh, wh, ct, nullptr, lane);      // k in [256 kh, 256 kh + 256)
     if (kh == 1) {
 #pragma unroll
@@ -983,54 +674,16 @@ __global__ __launch_bounds__(512) void enc_split_tail_kernel(FusedP p, const flo
     __shared__ VqSmem sm;
     __shared__ float part[4][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r0 = blockIdx.y * 16;
-    // (vmcnt retires in order: the rows' loads go first, the weight slice behind them)
-    float4 av[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int e = tid + 512 * n, row = e >> 7, c4 = e & 127;
-        av[n] = r0 + row < p.N ? ((const float4 *)in)[(size_t)(r0 + row) * 128 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
     const int ct = wave & 3, kh = wave >> 2;
     float4 wh[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) wh[q] = p.out_f[((size_t)ct * 32 + 16 * kh + q) * 64 + lane];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int e = tid + 512 * n, row = e >> 7, c4 = e & 127;
-        float *d = tile + row * FE_LD + 4 * c4;
-        *(float2 *)d = make_float2(av[n].x, av[n].y);
-        *(float2 *)(d + 2) = make_float2(av[n].z, av[n].w);
-    }
-    __syncthreads();
-    rows16_layernorm<1>(tile, p.ln_g[4], p.ln_b[4], p.eps, p.lnc, tid);
-    __syncthreads();
-    const int nwv = p.n_emb % 128 == 0 ? 8 : 4;          // waves of the VQ search
-    const int tpw = p.n_emb / (16 * nwv), t0 = (wave < nwv ? wave : 0) * tpw;
-    float4 f0[4] = {}, f1[4] = {};
-    if (wave < nwv) {
-        vq_load_tile(p.Ef, t0, lane, f0);
-        vq_load_tile(p.Ef, tpw > 1 ? t0 + 1 : t0, lane, f1);
-    }
+    rows16_load_ln(in, r0, p.N, tile, p.ln_g[4], p.ln_b[4], p.eps, p.lnc, tid,
+                   [&] { rows16_load_w<16>(p.out_f, 2 * ct + kh, lane, wh); });
+    const int nwv = vq_search_waves(p.n_emb);
+    float4 f0[4], f1[4];
+    vq_first_tiles(p.Ef, p.n_emb, nwv, wave, lane, f0, f1);
     // (bias + c0) + c1: wave w < 4 runs c0 of column tile w, wave w + 4 runs c1
     const f32x4 zt = rows16_gemm_pre<1, 16>(tile + 256 * kh, wh, ct, kh == 0 ? p.out_b : nullptr, lane);
-    if (kh == 1) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[ct][4 * (lane >> 4) + r][lane & 15] = zt[r];
-    }
-    __syncthreads();
-    if (kh == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 4 * (lane >> 4) + r, col = 16 * ct + (lane & 15);
-            const float z = zt[r] + part[ct][row][lane & 15];
-            sm.xs[row][col] = z;
-            if (p.z_pre && r0 + row < p.N) p.z_pre[(size_t)(r0 + row) * 64 + col] = z;
-        }
-    }
-    __syncthreads();
-    if (tid < 16) sm.x2s[tid] = r0 + tid < p.N ? sumsq64(&sm.xs[tid][0]) : 0.f;
-    __syncthreads();
-    vq_rows16(sm, r0, p.N, p.Ef, p.E, p.e2, p.n_emb, p.idx, p.z_q, tid, f0, f1, nwv);
+    rows16_finish_z<16 * 17, 17>(p, sm, &part[0][0][0], zt, ct, kh, r0, tid, f0, f1, nwv, false);
 }
 
 __global__ __launch_bounds__(256) void enc_split_conv_kernel(FusedP p, float *__restrict__ out) {
@@ -1101,299 +754,47 @@ __global__ void conv_weight_permute_kernel(const float *__restrict__ w, float *_
     if (i >= O * K) return;
     const int o = i / K, kidx = i - o * K;
     w1[i] = w[i];                                          // mode 1: kidx = c*4 + tap (native layout)
-    const int rem = kidx & 63, tap = rem >> 4, c = (kidx >> 6) * 16 + (rem & 15);
+    int c, tap;
+    im2col_ct(2, kidx, c, tap);
     w2[i] = w[((size_t)o * C + c) * 4 + tap];              // mode 2: [block of 16 c][tap][c in block]
 }
 
 // ------------------------------------------------------------------------------------------
-// handle + ABI
+// launches (encoder_internal.h)
 // ------------------------------------------------------------------------------------------
-struct vqcpc_encoder {
-    int in_channels, channels, n_emb, z_dim, c_dim;
-    float *conv_w1 = nullptr, *conv_w2 = nullptr;
-    float *ln_g[5] = {}, *ln_b[5] = {};
-    float *fc_w[4] = {};
-    float *out_w = nullptr, *out_b = nullptr;
-    float *codebook = nullptr, *e2 = nullptr, *cbfrag = nullptr;
-    LstmPlan *lstm = nullptr;
-    int dbg_drop = -1, dbg_timeout_ms = 1000;      // tests of the resident scan's abort path
-    LnConst lnc;
-    DevBuf bufA, bufB, zpre, stats;
-    // fused front end (enc_fused_kernel): weights in 16x16x4 fragment order
-    float4 *conv_f[2] = {nullptr, nullptr}, *fc_f[4] = {}, *out_f = nullptr;
-    int fused = -1;                      // -1 auto (split below split_max_tiles row tiles, else fused), 0 layered kernels,
-                                         // 1 one-launch fused kernel, 2 six-launch column-split kernels
-    int split_max_tiles = 80;            // auto: calls of up to this many 16-row tiles take the column-split launches
-    int last_schedule = -1;              // vqcpc_encoder_last_schedule: what the last front end ran (0 / 1 / 2 as `fused`), -1 none yet
-};
-
-static int dev_copy(float **dst, const float *src, size_t n) {
-    HIP_TRY(hipMalloc((void **)dst, n * sizeof(float)));
-    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
-    return VQCPC_OK;
+void launch_ln512(const float *X, const float *g, const float *b, float *Y, int M, float eps, int relu, const LnConst &k, hipStream_t s) {
+    hipLaunchKernelGGL(ln512_kernel, dim3((M + 7) / 8), dim3(256), 0, s, X, g, b, Y, M, eps, relu, k);
 }
-#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
-extern "C" void vqcpc_encoder_destroy(vqcpc_encoder *e) {
-    if (!e) return;
-    float *ptrs[] = {e->conv_w1, e->conv_w2, e->out_w, e->out_b, e->codebook, e->e2, e->cbfrag};
-    for (float *p : ptrs) if (p) (void)hipFree(p);
-    for (int i = 0; i < 5; ++i) { if (e->ln_g[i]) (void)hipFree(e->ln_g[i]); if (e->ln_b[i]) (void)hipFree(e->ln_b[i]); }
-    for (int i = 0; i < 4; ++i) if (e->fc_w[i]) (void)hipFree(e->fc_w[i]);
-    if (e->lstm) vq_lstm_plan_destroy(e->lstm);
-    float4 *fr[] = {e->conv_f[0], e->conv_f[1], e->fc_f[0], e->fc_f[1], e->fc_f[2], e->fc_f[3], e->out_f};
-    for (float4 *q : fr) if (q) (void)hipFree(q);
-    e->bufA.release(); e->bufB.release();
-    e->zpre.release(); e->stats.release();
-    delete e;
+void launch_vq_encode(const float *X, int N, const float4 *Ef, const float *E, const float *e2, int n_emb, int64_t *idx, float *zq, hipStream_t s) {
+    hipLaunchKernelGGL(vq_encode_kernel, dim3((N + 15) / 16), dim3(256), 0, s, X, N, Ef, E, e2, n_emb, idx, zq);
 }
-
-static int build_frag16(const float *W, int N, int K, float4 **out) {
-    VQ_REQUIRE(N % 16 == 0 && K % 64 == 0, "build_frag16: unsupported shape (%d, %d)", N, K);
+void launch_enc_fused(const FusedP &p, hipStream_t s) {
+    hipLaunchKernelGGL(enc_fused_kernel, dim3((p.N + 15) / 16), dim3(512), 0, s, p);
+}
+void launch_enc_split(const FusedP &p, float *a, float *b, hipStream_t s) {
+    const int ntiles = (p.N + 15) / 16;
+    hipLaunchKernelGGL(enc_split_conv_kernel, dim3(8, ntiles), dim3(256), 0, s, p, a);
+    for (int l = 1; l <= 4; ++l) {
+        hipLaunchKernelGGL(enc_split_fc_kernel, dim3(8, ntiles), dim3(512), 0, s, p, l, (const float *)a, b);
+        float *t = a; a = b; b = t;
+    }
+    hipLaunchKernelGGL(enc_split_tail_kernel, dim3(1, ntiles), dim3(512), 0, s, p, (const float *)a);
+}
+void launch_vq_stats(const float *x, const float *q, const int64_t *idx, int n_rows, float *zst, double *part, int nparts, unsigned *hist,
+                     int n_emb, float *loss, float *ppl, hipStream_t s) {
+    hipLaunchKernelGGL(vq_stats_partial_kernel, dim3(nparts), dim3(256), 0, s, x, q, idx, n_rows, zst, part, hist);
+    hipLaunchKernelGGL(vq_stats_final_kernel, dim3(1), dim3(256), 0, s, part, nparts, hist, n_emb, n_rows, loss, ppl);
+}
+void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C) {
+    hipLaunchKernelGGL(conv_weight_permute_kernel, dim3((unsigned)(((size_t)O * C * 4 + 255) / 256)), dim3(256), 0, 0, w, w1, w2, O, C);
+}
+void launch_rowsumsq64(const float *X, float *out, int n) {
+    hipLaunchKernelGGL(rowsumsq64_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, X, out, n);
+}
+void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb) {
+    hipLaunchKernelGGL(vq_build_frag_kernel, dim3((n_emb * 16 + 255) / 256), dim3(256), 0, 0, E, Ef, n_emb);
+}
+void launch_frag16_build(const float *W, int N, int K, float4 *Wf) {
     const size_t n4 = (size_t)(N / 16) * (K / 16) * 64;
-    HIP_TRY(hipMalloc((void **)out, n4 * sizeof(float4)));
-    hipLaunchKernelGGL(frag16_build_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, N, K, *out);
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
-
-static int encoder_create_impl(const vqcpc_encoder_weights *w, vqcpc_encoder *e) {
-    const int C = w->in_channels, CH = w->channels;
-    e->in_channels = C; e->channels = CH; e->n_emb = w->n_embeddings; e->z_dim = w->z_dim; e->c_dim = w->c_dim;
-    for (int j = 0; j < 16; ++j) e->lnc.inv[j] = 1.0f / (float)(j + 1);
-    for (int q = 0; q < 8; ++q) e->lnc.sc[q] = (float)64 / (float)(64 * (q + 1));
-    const size_t nconv = (size_t)CH * C * 4;
-    HIP_TRY(hipMalloc((void **)&e->conv_w1, nconv * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&e->conv_w2, nconv * sizeof(float)));
-    hipLaunchKernelGGL(conv_weight_permute_kernel, dim3((unsigned)((nconv + 255) / 256)), dim3(256), 0, 0,
-                       w->conv_weight, e->conv_w1, e->conv_w2, CH, C);
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < 5; ++i) { TRY(dev_copy(&e->ln_g[i], w->ln_weight[i], CH)); TRY(dev_copy(&e->ln_b[i], w->ln_bias[i], CH)); }
-    for (int i = 0; i < 4; ++i) TRY(dev_copy(&e->fc_w[i], w->fc_weight[i], (size_t)CH * CH));
-    TRY(dev_copy(&e->out_w, w->out_weight, (size_t)w->z_dim * CH));
-    TRY(dev_copy(&e->out_b, w->out_bias, w->z_dim));
-    TRY(dev_copy(&e->codebook, w->codebook, (size_t)w->n_embeddings * w->z_dim));
-    HIP_TRY(hipMalloc((void **)&e->e2, w->n_embeddings * sizeof(float)));
-    hipLaunchKernelGGL(rowsumsq64_kernel, dim3((w->n_embeddings + 63) / 64), dim3(64), 0, 0, e->codebook, e->e2,
-                       w->n_embeddings);
-    HIP_TRY(hipMalloc((void **)&e->cbfrag, (size_t)w->n_embeddings * 64 * sizeof(float)));
-    hipLaunchKernelGGL(vq_build_frag_kernel, dim3((w->n_embeddings * 16 + 255) / 256), dim3(256), 0, 0, e->codebook,
-                       (float4 *)e->cbfrag, w->n_embeddings);
-    HIP_TRY(hipGetLastError());
-    TRY(vq_lstm_plan_create(w->rnn_w_ih, w->rnn_w_hh, w->rnn_b_ih, w->rnn_b_hh, w->z_dim, w->c_dim, &e->lstm));
-
-    // fragment-ordered copies for the fused front end (the activation tile is 512 wide: 4 C <= 512)
-    if (4 * C <= 512) {
-        TRY(build_frag16(e->conv_w1, CH, 4 * C, &e->conv_f[0]));
-        TRY(build_frag16(e->conv_w2, CH, 4 * C, &e->conv_f[1]));
-        for (int i = 0; i < 4; ++i) TRY(build_frag16(e->fc_w[i], CH, CH, &e->fc_f[i]));
-        TRY(build_frag16(e->out_w, w->z_dim, CH, &e->out_f));
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return VQCPC_OK;
-}
-
-extern "C" int vqcpc_encoder_create(const vqcpc_encoder_weights *w, vqcpc_encoder **out) {
-    VQ_REQUIRE(w && out, "vqcpc_encoder_create: null argument");
-    *out = nullptr;
-    TRY(require_gfx950());
-    VQ_REQUIRE(w->channels == 512 && w->z_dim == 64, "encoder: channels must be 512 and z_dim 64 (got %d, %d)",
-               w->channels, w->z_dim);
-    VQ_REQUIRE(w->in_channels % 16 == 0 && w->in_channels > 0 && w->in_channels <= 256,
-               "encoder: in_channels must be a multiple of 16 in (0, 256] (got %d)", w->in_channels);
-    VQ_REQUIRE(w->n_embeddings % 64 == 0 && w->n_embeddings > 0 && w->n_embeddings <= 4096,
-               "encoder: n_embeddings must be a multiple of 64 in (0, 4096] (got %d)", w->n_embeddings);
-    VQ_REQUIRE(w->c_dim % 64 == 0 && w->c_dim > 0 && w->c_dim <= 1024, "encoder: c_dim must be a multiple of 64 (got %d)", w->c_dim);
-    vqcpc_encoder *e = new vqcpc_encoder();
-    int rc = encoder_create_impl(w, e);
-    if (rc != VQCPC_OK) { vqcpc_encoder_destroy(e); return rc; }
-    *out = e;
-    return VQCPC_OK;
-}
-
-// conv + seg-FC stack up to `stop_stage` (0 conv, 1 LN0+ReLU, 2+2l FC_l, 3+2l LN_l+ReLU, 10 z_pre).
-// Returns the device buffer holding that stage's rows in *stage_out.
-static int encoder_front(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, int stop_stage,
-                         float *zp, const float **stage_out, hipStream_t s) {
-    const int C = e->in_channels, CH = e->channels, To = (T - 2) / 2 + 1, N = B * To;
-    if (conv_mode == VQCPC_CONV_AUTO)
-        conv_mode = (B > 1 || (long)B * C * T > 20480) ? VQCPC_CONV_DIRECT : VQCPC_CONV_IM2COL;
-    TRY(e->bufA.reserve((size_t)N * CH * sizeof(float)));
-    TRY(e->bufB.reserve((size_t)N * CH * sizeof(float)));
-    float *a = e->bufA.as<float>(), *b = e->bufB.as<float>();
-    e->last_schedule = 0;
-
-    // conv (model.py:65) as an im2col GEMM in the reference back-end's summation order
-    GemmP p{};
-    p.W = conv_mode == VQCPC_CONV_IM2COL ? e->conv_w1 : e->conv_w2;
-    p.Y = a; p.ldy = CH; p.M = N; p.N = CH; p.K = 4 * C;
-    p.KC = conv_mode == VQCPC_CONV_IM2COL ? 4 * C : 64;
-    p.x = mel; p.C = C; p.T = T; p.To = To;
-    if (conv_mode == VQCPC_CONV_IM2COL) TRY((launch_gemm<1>(p, s)));
-    else TRY((launch_gemm<2>(p, s)));
-    *stage_out = a;
-    if (stop_stage == 0) return VQCPC_OK;
-
-    // seg-FC stack (model.py:46-55, :67)
-    const dim3 lng((N + 7) / 8), lnb(256);
-    hipLaunchKernelGGL(ln512_kernel, lng, lnb, 0, s, a, e->ln_g[0], e->ln_b[0], b, N, 1e-5f, 1, e->lnc);
-    *stage_out = b;
-    if (stop_stage == 1) return VQCPC_OK;
-    for (int l = 0; l < 4; ++l) {
-        TRY(vq_gemm_chain(b, CH, e->fc_w[l], nullptr, a, CH, N, CH, CH, 256, s));
-        *stage_out = a;
-        if (stop_stage == 2 + 2 * l) return VQCPC_OK;
-        hipLaunchKernelGGL(ln512_kernel, lng, lnb, 0, s, a, e->ln_g[l + 1], e->ln_b[l + 1], b, N, 1e-5f, 1, e->lnc);
-        *stage_out = b;
-        if (stop_stage == 3 + 2 * l) return VQCPC_OK;
-    }
-    TRY(vq_gemm_chain(b, CH, e->out_w, e->out_b, zp, 64, N, 64, CH, 256, s));
-    *stage_out = zp;
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
-
-static bool use_fused(const vqcpc_encoder *e) { return e->fused != 0 && e->conv_f[0] != nullptr; }
-
-// The whole front end + VQ in one launch (stage < 0), or up to `stage` with that stage's rows in stage_out.
-static int encoder_fused(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, float *z_pre, float *z_q,
-                         int64_t *idx, int stage, float *stage_out, hipStream_t s) {
-    const int C = e->in_channels, To = (T - 2) / 2 + 1, N = B * To;
-    if (conv_mode == VQCPC_CONV_AUTO)
-        conv_mode = (B > 1 || (long)B * C * T > 20480) ? VQCPC_CONV_DIRECT : VQCPC_CONV_IM2COL;
-    FusedP p{};
-    p.mel = mel; p.C = C; p.T = T; p.To = To; p.N = N; p.conv_mode = conv_mode;
-    p.conv_f = e->conv_f[conv_mode == VQCPC_CONV_IM2COL ? 0 : 1];
-    for (int i = 0; i < 5; ++i) { p.ln_g[i] = e->ln_g[i]; p.ln_b[i] = e->ln_b[i]; }
-    for (int i = 0; i < 4; ++i) p.fc_f[i] = e->fc_f[i];
-    p.out_f = e->out_f; p.out_b = e->out_b;
-    p.Ef = (const float4 *)e->cbfrag; p.E = e->codebook; p.e2 = e->e2; p.n_emb = e->n_emb;
-    p.z_pre = z_pre; p.z_q = z_q; p.idx = idx; p.stage_out = stage_out; p.stage = stage;
-    p.eps = 1e-5f; p.lnc = e->lnc;
-    const int ntiles = (N + 15) / 16;
-    const bool split = stage < 0 && (e->fused == 2 || (e->fused != 1 && ntiles <= e->split_max_tiles));
-    e->last_schedule = split ? 2 : 1;
-    if (split) {                                          // small call: six column-split launches (enc_split_*_kernel)
-        TRY(e->bufA.reserve((size_t)N * 512 * sizeof(float)));
-        TRY(e->bufB.reserve((size_t)N * 512 * sizeof(float)));
-        float *a = e->bufA.as<float>(), *b = e->bufB.as<float>();
-        hipLaunchKernelGGL(enc_split_conv_kernel, dim3(8, ntiles), dim3(256), 0, s, p, a);
-        for (int l = 1; l <= 4; ++l) {
-            hipLaunchKernelGGL(enc_split_fc_kernel, dim3(8, ntiles), dim3(512), 0, s, p, l, (const float *)a, b);
-            float *t = a; a = b; b = t;
-        }
-        hipLaunchKernelGGL(enc_split_tail_kernel, dim3(1, ntiles), dim3(512), 0, s, p, (const float *)a);
-    } else {
-        hipLaunchKernelGGL(enc_fused_kernel, dim3(ntiles), dim3(512), 0, s, p);
-    }
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
-
-extern "C" int vqcpc_encoder_set_option(vqcpc_encoder *e, const char *name, int value) {
-    VQ_REQUIRE(e && name, "vqcpc_encoder_set_option: null argument");
-    if (!strcmp(name, "fused")) {
-        VQ_REQUIRE(value >= -1 && value <= 2, "fused must be -1 (auto), 0, 1 or 2");
-        VQ_REQUIRE(value < 1 || e->conv_f[0], "fused front end needs 4 * in_channels <= 512");
-        e->fused = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "split_max_tiles")) {
-        VQ_REQUIRE(value >= 0, "split_max_tiles must be >= 0");
-        e->split_max_tiles = value;
-        return VQCPC_OK;
-    }
-    if (!strcmp(name, "persistent_context")) return vq_lstm_set_persistent(e->lstm, value == 2 ? 2 : (value != 0 ? -1 : 0));
-    if (!strcmp(name, "context_debug_drop_step")) { e->dbg_drop = value; return vq_lstm_set_debug(e->lstm, e->dbg_drop, e->dbg_timeout_ms); }
-    if (!strcmp(name, "context_timeout_ms")) {
-        VQ_REQUIRE(value >= 1 && value <= 10000, "context_timeout_ms must be in [1, 10000]");
-        e->dbg_timeout_ms = value;
-        return vq_lstm_set_debug(e->lstm, e->dbg_drop, e->dbg_timeout_ms);
-    }
-    vq_set_error("unknown option %s", name);
-    return VQCPC_ERR_INVALID;
-}
-
-extern "C" int vqcpc_encoder_last_schedule(vqcpc_encoder *e) { return e ? e->last_schedule : -1; }
-
-extern "C" int vqcpc_encoder_encode(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode,
-                                    float *z_q, float *c, int64_t *idx, float *z_pre, void *stream) {
-    VQ_REQUIRE(e && mel && z_q && idx, "vqcpc_encoder_encode: null argument");
-    VQ_REQUIRE(B > 0 && T >= 2, "encoder.encode: need B > 0 and T >= 2 (got B=%d T=%d)", B, T);
-    VQ_REQUIRE(conv_mode >= 0 && conv_mode <= 2, "encoder.encode: conv_mode must be 0, 1 or 2");
-    hipStream_t s = (hipStream_t)stream;
-    const int To = (T - 2) / 2 + 1, N = B * To;
-    float *zp = z_pre;
-    if (!zp && !use_fused(e)) { TRY(e->zpre.reserve((size_t)N * 64 * sizeof(float))); zp = e->zpre.as<float>(); }
-    VQ_REQUIRE(((uintptr_t)zp & 15) == 0 && ((uintptr_t)z_q & 15) == 0, "encoder.encode: outputs must be 16-byte aligned");
-    if (use_fused(e)) {
-        TRY(encoder_fused(e, mel, B, T, conv_mode, z_pre, z_q, idx, -1, nullptr, s));     // z_pre only if asked for
-    } else {
-        const float *unused = nullptr;
-        TRY(encoder_front(e, mel, B, T, conv_mode, 10, zp, &unused, s));
-        // VQ (model.py:103-115)
-        hipLaunchKernelGGL(vq_encode_kernel, dim3((N + 15) / 16), dim3(256), 0, s, zp, N, (const float4 *)e->cbfrag, e->codebook,
-                           e->e2, e->n_emb, idx, z_q);
-        HIP_TRY(hipGetLastError());
-    }
-    if (c) TRY(vq_lstm_run(e->lstm, z_q, B, To, c, s));
-    return VQCPC_OK;
-}
-
-extern "C" int vqcpc_encoder_check(vqcpc_encoder *e) {
-    VQ_REQUIRE(e, "vqcpc_encoder_check: null argument");
-    return vq_lstm_check(e->lstm);
-}
-
-extern "C" int vqcpc_encoder_vq_encode(vqcpc_encoder *e, const float *x, int n_rows, float *z_q, int64_t *idx,
-                                       void *stream) {
-    VQ_REQUIRE(e && x && z_q && idx && n_rows > 0, "vqcpc_encoder_vq_encode: bad argument");
-    VQ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)z_q & 15) == 0, "vqcpc_encoder_vq_encode: rows must be 16-byte aligned");
-    hipLaunchKernelGGL(vq_encode_kernel, dim3((n_rows + 15) / 16), dim3(256), 0, (hipStream_t)stream, x, n_rows,
-                       (const float4 *)e->cbfrag, e->codebook, e->e2, e->n_emb, idx, z_q);
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
-}
-
-extern "C" int vqcpc_encoder_stage(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, int stage,
-                                   float *out, void *stream) {
-    VQ_REQUIRE(e && mel && out, "vqcpc_encoder_stage: null argument");
-    VQ_REQUIRE(B > 0 && T >= 2 && stage >= 0 && stage <= 10, "vqcpc_encoder_stage: bad shape or stage");
-    hipStream_t s = (hipStream_t)stream;
-    const int N = B * ((T - 2) / 2 + 1);
-    if (use_fused(e))                                    // the fused kernel stops after `stage` and dumps its tile
-        return encoder_fused(e, mel, B, T, conv_mode, stage == 10 ? out : nullptr, nullptr, nullptr, stage,
-                             stage == 10 ? nullptr : out, s);
-    const float *src = nullptr;
-    float *zp = nullptr;
-    if (stage == 10) {
-        VQ_REQUIRE(((uintptr_t)out & 15) == 0, "vqcpc_encoder_stage: out must be 16-byte aligned");
-        zp = out;
-    }
-    TRY(encoder_front(e, mel, B, T, conv_mode, stage, zp, &src, s));
-    if (stage != 10)
-        HIP_TRY(hipMemcpyAsync(out, src, (size_t)N * e->channels * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return VQCPC_OK;
-}
-
-extern "C" int vqcpc_encoder_context(vqcpc_encoder *e, const float *z, int B, int Tz, float *c, void *stream) {
-    VQ_REQUIRE(e && z && c && B > 0 && Tz > 0, "vqcpc_encoder_context: bad argument");
-    return vq_lstm_run(e->lstm, z, B, Tz, c, (hipStream_t)stream);
-}
-
-extern "C" int vqcpc_encoder_forward_stats(vqcpc_encoder *e, const float *z_pre, const float *z_q,
-                                           const int64_t *idx, int n_rows, float *z_st, float *loss,
-                                           float *perplexity, void *stream) {
-    VQ_REQUIRE(e && z_pre && z_q && idx && loss && perplexity && n_rows > 0, "vqcpc_encoder_forward_stats: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int nblk = 64;
-    const size_t hist_bytes = (size_t)e->n_emb * sizeof(unsigned);
-    TRY(e->stats.reserve(hist_bytes + nblk * sizeof(double) + 64));
-    unsigned *hist = e->stats.as<unsigned>();
-    double *part = (double *)((char *)e->stats.p + ((hist_bytes + 15) / 16) * 16);
-    HIP_TRY(hipMemsetAsync(hist, 0, hist_bytes, s));
-    hipLaunchKernelGGL(vq_stats_partial_kernel, dim3(nblk), dim3(256), 0, s, z_pre, z_q, idx, n_rows, z_st, part, hist);
-    hipLaunchKernelGGL(vq_stats_final_kernel, dim3(1), dim3(256), 0, s, part, nblk, hist, e->n_emb, n_rows, loss, perplexity);
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
+    hipLaunchKernelGGL(frag16_build_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, N, K, Wf);
 }

@@ -1,0 +1,273 @@
+// encoder_host.hip -- the encoder handle (struct vqcpc_encoder), the choice among the three schedules of its front end
+// (layered kernels, one fused launch, six column-split launches: encoder.hip) and every vqcpc_encoder_* entry point.
+#include "encoder_internal.h"
+#include <string.h>
+
+struct vqcpc_encoder {
+    int in_channels, channels, n_emb, z_dim, c_dim;
+    DevPtr<float> conv_w1, conv_w2;      // conv.weight as a GEMM operand in the k order of conv mode 1, 2
+    DevPtr<float> ln_g[5], ln_b[5];
+    DevPtr<float> fc_w[4];
+    DevPtr<float> out_w, out_b;
+    DevPtr<float> codebook, e2;
+    DevPtr<float4> cbfrag;
+    LstmPlan *lstm = nullptr;
+    int dbg_drop = -1, dbg_timeout_ms = 1000;      // tests of the resident scan's abort path
+    LnConst lnc;
+    DevPtr<float> bufA, bufB, zpre;
+    DevPtr<char> stats;
+    // fused and column-split schedules: weights in 16x16x4 fragment order (only when 4 * in_channels <= 512, the width of
+    // their activation tile), and the model's half of their kernel argument
+    DevPtr<float4> conv_f[2], fc_f[4], out_f;
+    FusedP fp{};
+    int fused = -1;                      // -1 auto (split below split_max_tiles row tiles, else fused), 0 layered kernels,
+                                         // 1 one-launch fused kernel, 2 six-launch column-split kernels
+    int split_max_tiles = 80;            // auto: calls of up to this many 16-row tiles take the column-split launches
+    int last_schedule = -1;              // vqcpc_encoder_last_schedule: what the last front end ran (0 / 1 / 2 as `fused`), -1 none yet
+    ~vqcpc_encoder() { if (lstm) vq_lstm_plan_destroy(lstm); }
+};
+
+extern "C" void vqcpc_encoder_destroy(vqcpc_encoder *e) { delete e; }
+
+static int dev_copy(DevPtr<float> &dst, const float *src, size_t n) {
+    TRY(dst.reserve(n * sizeof(float)));
+    HIP_TRY(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
+    return VQCPC_OK;
+}
+
+static int build_frag16(const float *W, int N, int K, DevPtr<float4> &out) {
+    VQ_REQUIRE(N % 16 == 0 && K % 64 == 0, "build_frag16: unsupported shape (%d, %d)", N, K);
+    TRY(out.reserve((size_t)(N / 16) * (K / 16) * 64 * sizeof(float4)));
+    launch_frag16_build(W, N, K, out);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+static int encoder_create_impl(const vqcpc_encoder_weights *w, vqcpc_encoder *e) {
+    const int C = w->in_channels, CH = w->channels;
+    e->in_channels = C; e->channels = CH; e->n_emb = w->n_embeddings; e->z_dim = w->z_dim; e->c_dim = w->c_dim;
+    for (int j = 0; j < 16; ++j) e->lnc.inv[j] = 1.0f / (float)(j + 1);
+    for (int q = 0; q < 8; ++q) e->lnc.sc[q] = (float)64 / (float)(64 * (q + 1));
+    const size_t nconv = (size_t)CH * C * 4;
+    TRY(e->conv_w1.reserve(nconv * sizeof(float)));
+    TRY(e->conv_w2.reserve(nconv * sizeof(float)));
+    launch_conv_weight_permute(w->conv_weight, e->conv_w1, e->conv_w2, CH, C);
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < 5; ++i) { TRY(dev_copy(e->ln_g[i], w->ln_weight[i], CH)); TRY(dev_copy(e->ln_b[i], w->ln_bias[i], CH)); }
+    for (int i = 0; i < 4; ++i) TRY(dev_copy(e->fc_w[i], w->fc_weight[i], (size_t)CH * CH));
+    TRY(dev_copy(e->out_w, w->out_weight, (size_t)w->z_dim * CH));
+    TRY(dev_copy(e->out_b, w->out_bias, w->z_dim));
+    TRY(dev_copy(e->codebook, w->codebook, (size_t)w->n_embeddings * w->z_dim));
+    TRY(e->e2.reserve(w->n_embeddings * sizeof(float)));
+    launch_rowsumsq64(e->codebook, e->e2, w->n_embeddings);
+    TRY(e->cbfrag.reserve((size_t)w->n_embeddings * 64 * sizeof(float)));
+    launch_vq_build_frag(e->codebook, e->cbfrag, w->n_embeddings);
+    HIP_TRY(hipGetLastError());
+    TRY(vq_lstm_plan_create(w->rnn_w_ih, w->rnn_w_hh, w->rnn_b_ih, w->rnn_b_hh, w->z_dim, w->c_dim, &e->lstm));
+
+    // fragment-ordered copies for the fused front end (the activation tile is 512 wide: 4 C <= 512)
+    if (4 * C <= 512) {
+        TRY(build_frag16(e->conv_w1, CH, 4 * C, e->conv_f[0]));
+        TRY(build_frag16(e->conv_w2, CH, 4 * C, e->conv_f[1]));
+        for (int i = 0; i < 4; ++i) TRY(build_frag16(e->fc_w[i], CH, CH, e->fc_f[i]));
+        TRY(build_frag16(e->out_w, w->z_dim, CH, e->out_f));
+    }
+    FusedP &p = e->fp;
+    p.C = C;
+    for (int i = 0; i < 5; ++i) { p.ln_g[i] = e->ln_g[i]; p.ln_b[i] = e->ln_b[i]; }
+    for (int i = 0; i < 4; ++i) p.fc_f[i] = e->fc_f[i];
+    p.out_f = e->out_f; p.out_b = e->out_b;
+    p.Ef = e->cbfrag; p.E = e->codebook; p.e2 = e->e2; p.n_emb = e->n_emb;
+    p.eps = 1e-5f; p.lnc = e->lnc;
+    HIP_TRY(hipDeviceSynchronize());
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_create(const vqcpc_encoder_weights *w, vqcpc_encoder **out) {
+    VQ_REQUIRE(w && out, "vqcpc_encoder_create: null argument");
+    *out = nullptr;
+    TRY(vq_require_gfx950());
+    VQ_REQUIRE(w->channels == 512 && w->z_dim == 64, "encoder: channels must be 512 and z_dim 64 (got %d, %d)",
+               w->channels, w->z_dim);
+    VQ_REQUIRE(w->in_channels % 16 == 0 && w->in_channels > 0 && w->in_channels <= 256,
+               "encoder: in_channels must be a multiple of 16 in (0, 256] (got %d)", w->in_channels);
+    VQ_REQUIRE(w->n_embeddings % 64 == 0 && w->n_embeddings > 0 && w->n_embeddings <= 4096,
+               "encoder: n_embeddings must be a multiple of 64 in (0, 4096] (got %d)", w->n_embeddings);
+    VQ_REQUIRE(w->c_dim % 64 == 0 && w->c_dim > 0 && w->c_dim <= 1024, "encoder: c_dim must be a multiple of 64 (got %d)", w->c_dim);
+    vqcpc_encoder *e = new vqcpc_encoder();
+    int rc = encoder_create_impl(w, e);
+    if (rc != VQCPC_OK) { vqcpc_encoder_destroy(e); return rc; }
+    *out = e;
+    return VQCPC_OK;
+}
+
+// Output frames of a T-frame utterance: Conv1d(k = 4, stride 2, padding 1) (model.py:43).
+static int frames_of(int T) { return (T - 2) / 2 + 1; }
+
+// VQCPC_CONV_AUTO: the order the reference's back end would pick for this call.
+static int resolve_conv_mode(const vqcpc_encoder *e, int conv_mode, int B, int T) {
+    if (conv_mode != VQCPC_CONV_AUTO) return conv_mode;
+    return (B > 1 || (long)B * e->in_channels * T > 20480) ? VQCPC_CONV_DIRECT : VQCPC_CONV_IM2COL;
+}
+
+// conv + seg-FC stack up to `stop_stage` (0 conv, 1 LN0+ReLU, 2+2l FC_l, 3+2l LN_l+ReLU, 10 z_pre).
+// Returns the device buffer holding that stage's rows in *stage_out.
+static int encoder_front(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, int stop_stage,
+                         float *zp, const float **stage_out, hipStream_t s) {
+    const int C = e->in_channels, CH = e->channels, To = frames_of(T), N = B * To;
+    conv_mode = resolve_conv_mode(e, conv_mode, B, T);
+    TRY(e->bufA.reserve((size_t)N * CH * sizeof(float)));
+    TRY(e->bufB.reserve((size_t)N * CH * sizeof(float)));
+    float *a = e->bufA, *b = e->bufB;
+    e->last_schedule = 0;
+
+    // conv (model.py:65) as an im2col GEMM in the reference back-end's summation order
+    const bool one_chain = conv_mode == VQCPC_CONV_IM2COL;
+    TRY(vq_gemm_chain_im2col(mel, C, T, To, one_chain ? e->conv_w1 : e->conv_w2, a, N, CH, one_chain ? 4 * C : 64, conv_mode, s));
+    *stage_out = a;
+    if (stop_stage == 0) return VQCPC_OK;
+
+    // seg-FC stack (model.py:46-55, :67)
+    launch_ln512(a, e->ln_g[0], e->ln_b[0], b, N, 1e-5f, 1, e->lnc, s);
+    *stage_out = b;
+    if (stop_stage == 1) return VQCPC_OK;
+    for (int l = 0; l < 4; ++l) {
+        TRY(vq_gemm_chain(b, CH, e->fc_w[l], nullptr, a, CH, N, CH, CH, 256, s));
+        *stage_out = a;
+        if (stop_stage == 2 + 2 * l) return VQCPC_OK;
+        launch_ln512(a, e->ln_g[l + 1], e->ln_b[l + 1], b, N, 1e-5f, 1, e->lnc, s);
+        *stage_out = b;
+        if (stop_stage == 3 + 2 * l) return VQCPC_OK;
+    }
+    TRY(vq_gemm_chain(b, CH, e->out_w, e->out_b, zp, 64, N, 64, CH, 256, s));
+    *stage_out = zp;
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+static bool use_fused(const vqcpc_encoder *e) { return e->fused != 0 && e->conv_f[0] != nullptr; }
+
+// The whole front end + VQ in one launch (stage < 0), or up to `stage` with that stage's rows in stage_out.
+static int encoder_fused(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, float *z_pre, float *z_q,
+                         int64_t *idx, int stage, float *stage_out, hipStream_t s) {
+    FusedP p = e->fp;
+    p.mel = mel; p.T = T; p.To = frames_of(T); p.N = B * p.To;
+    p.conv_mode = resolve_conv_mode(e, conv_mode, B, T);
+    p.conv_f = e->conv_f[p.conv_mode == VQCPC_CONV_IM2COL ? 0 : 1];
+    p.z_pre = z_pre; p.z_q = z_q; p.idx = idx; p.stage_out = stage_out; p.stage = stage;
+    const int ntiles = (p.N + 15) / 16;
+    const bool split = stage < 0 && (e->fused == 2 || (e->fused != 1 && ntiles <= e->split_max_tiles));
+    e->last_schedule = split ? 2 : 1;
+    if (split) {                                          // small call: six column-split launches (enc_split_*_kernel)
+        TRY(e->bufA.reserve((size_t)p.N * 512 * sizeof(float)));
+        TRY(e->bufB.reserve((size_t)p.N * 512 * sizeof(float)));
+        launch_enc_split(p, e->bufA, e->bufB, s);
+    } else {
+        launch_enc_fused(p, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_set_option(vqcpc_encoder *e, const char *name, int value) {
+    VQ_REQUIRE(e && name, "vqcpc_encoder_set_option: null argument");
+    if (!strcmp(name, "fused")) {
+        VQ_REQUIRE(value >= -1 && value <= 2, "fused must be -1 (auto), 0, 1 or 2");
+        VQ_REQUIRE(value < 1 || e->conv_f[0], "fused front end needs 4 * in_channels <= 512");
+        e->fused = value;
+        return VQCPC_OK;
+    }
+    if (!strcmp(name, "split_max_tiles")) {
+        VQ_REQUIRE(value >= 0, "split_max_tiles must be >= 0");
+        e->split_max_tiles = value;
+        return VQCPC_OK;
+    }
+    if (!strcmp(name, "persistent_context")) return vq_lstm_set_persistent(e->lstm, value == 2 ? 2 : (value != 0 ? -1 : 0));
+    if (!strcmp(name, "context_debug_drop_step")) { e->dbg_drop = value; return vq_lstm_set_debug(e->lstm, e->dbg_drop, e->dbg_timeout_ms); }
+    if (!strcmp(name, "context_timeout_ms")) {
+        VQ_REQUIRE(value >= 1 && value <= 10000, "context_timeout_ms must be in [1, 10000]");
+        e->dbg_timeout_ms = value;
+        return vq_lstm_set_debug(e->lstm, e->dbg_drop, e->dbg_timeout_ms);
+    }
+    vq_set_error("unknown option %s", name);
+    return VQCPC_ERR_INVALID;
+}
+
+extern "C" int vqcpc_encoder_last_schedule(vqcpc_encoder *e) { return e ? e->last_schedule : -1; }
+
+extern "C" int vqcpc_encoder_encode(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode,
+                                    float *z_q, float *c, int64_t *idx, float *z_pre, void *stream) {
+    VQ_REQUIRE(e && mel && z_q && idx, "vqcpc_encoder_encode: null argument");
+    VQ_REQUIRE(B > 0 && T >= 2, "encoder.encode: need B > 0 and T >= 2 (got B=%d T=%d)", B, T);
+    VQ_REQUIRE(conv_mode >= 0 && conv_mode <= 2, "encoder.encode: conv_mode must be 0, 1 or 2");
+    hipStream_t s = (hipStream_t)stream;
+    const int To = frames_of(T), N = B * To;
+    float *zp = z_pre;
+    if (!zp && !use_fused(e)) { TRY(e->zpre.reserve((size_t)N * 64 * sizeof(float))); zp = e->zpre; }
+    VQ_REQUIRE(((uintptr_t)zp & 15) == 0 && ((uintptr_t)z_q & 15) == 0, "encoder.encode: outputs must be 16-byte aligned");
+    if (use_fused(e)) {
+        TRY(encoder_fused(e, mel, B, T, conv_mode, z_pre, z_q, idx, -1, nullptr, s));     // z_pre only if asked for
+    } else {
+        const float *unused = nullptr;
+        TRY(encoder_front(e, mel, B, T, conv_mode, 10, zp, &unused, s));
+        launch_vq_encode(zp, N, e->cbfrag, e->codebook, e->e2, e->n_emb, idx, z_q, s);    // VQ (model.py:103-115)
+        HIP_TRY(hipGetLastError());
+    }
+    if (c) TRY(vq_lstm_run(e->lstm, z_q, B, To, c, s));
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_check(vqcpc_encoder *e) {
+    VQ_REQUIRE(e, "vqcpc_encoder_check: null argument");
+    return vq_lstm_check(e->lstm);
+}
+
+extern "C" int vqcpc_encoder_vq_encode(vqcpc_encoder *e, const float *x, int n_rows, float *z_q, int64_t *idx,
+                                       void *stream) {
+    VQ_REQUIRE(e && x && z_q && idx && n_rows > 0, "vqcpc_encoder_vq_encode: bad argument");
+    VQ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)z_q & 15) == 0, "vqcpc_encoder_vq_encode: rows must be 16-byte aligned");
+    launch_vq_encode(x, n_rows, e->cbfrag, e->codebook, e->e2, e->n_emb, idx, z_q, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_stage(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, int stage,
+                                   float *out, void *stream) {
+    VQ_REQUIRE(e && mel && out, "vqcpc_encoder_stage: null argument");
+    VQ_REQUIRE(B > 0 && T >= 2 && stage >= 0 && stage <= 10, "vqcpc_encoder_stage: bad shape or stage");
+    hipStream_t s = (hipStream_t)stream;
+    if (use_fused(e))                                    // the fused kernel stops after `stage` and dumps its tile
+        return encoder_fused(e, mel, B, T, conv_mode, stage == 10 ? out : nullptr, nullptr, nullptr, stage,
+                             stage == 10 ? nullptr : out, s);
+    const float *src = nullptr;
+    float *zp = nullptr;
+    if (stage == 10) {
+        VQ_REQUIRE(((uintptr_t)out & 15) == 0, "vqcpc_encoder_stage: out must be 16-byte aligned");
+        zp = out;
+    }
+    TRY(encoder_front(e, mel, B, T, conv_mode, stage, zp, &src, s));
+    if (stage != 10)
+        HIP_TRY(hipMemcpyAsync(out, src, (size_t)B * frames_of(T) * e->channels * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_context(vqcpc_encoder *e, const float *z, int B, int Tz, float *c, void *stream) {
+    VQ_REQUIRE(e && z && c && B > 0 && Tz > 0, "vqcpc_encoder_context: bad argument");
+    return vq_lstm_run(e->lstm, z, B, Tz, c, (hipStream_t)stream);
+}
+
+extern "C" int vqcpc_encoder_forward_stats(vqcpc_encoder *e, const float *z_pre, const float *z_q,
+                                           const int64_t *idx, int n_rows, float *z_st, float *loss,
+                                           float *perplexity, void *stream) {
+    VQ_REQUIRE(e && z_pre && z_q && idx && loss && perplexity && n_rows > 0, "vqcpc_encoder_forward_stats: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = 64;
+    const size_t hist_bytes = (size_t)e->n_emb * sizeof(unsigned);
+    TRY(e->stats.reserve(hist_bytes + nblk * sizeof(double) + 64));
+    unsigned *hist = e->stats.as<unsigned>();
+    double *part = (double *)(e->stats + ((hist_bytes + 15) / 16) * 16);
+    HIP_TRY(hipMemsetAsync(hist, 0, hist_bytes, s));
+    launch_vq_stats(z_pre, z_q, idx, n_rows, z_st, part, nblk, hist, e->n_emb, loss, perplexity, s);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}

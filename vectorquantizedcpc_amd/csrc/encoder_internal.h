@@ -1,0 +1,61 @@
+// What the encoder's kernels (encoder.hip), its handle (encoder_host.hip) and the exact-chain GEMM (gemm_chain.hip) share.
+#pragma once
+#include "common.h"
+
+// ------------------------------------------------------------------------------------------
+// im2col of Conv1d(k = 4, stride 2, padding 1) over mel (B, C, T) (model.py:43, :65): GEMM row m = b * To + tt, column kidx.
+// mode 1 (VQCPC_CONV_IM2COL): kidx = 4 c + tap, the native layout of conv.weight; mode 2 (VQCPC_CONV_DIRECT): blocks of
+// 16 channels, [block][tap][c in block], the k order of the reference's direct back end.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void im2col_ct(int mode, int kidx, int &c, int &tap) {
+    if (mode == 1) { c = kidx >> 2; tap = kidx & 3; }
+    else { const int rem = kidx & 63; tap = rem >> 4; c = (kidx >> 6) * 16 + (rem & 15); }
+}
+// Element (m, kidx) of the im2col matrix of N rows: zero in the padding and for rows m >= N.
+__device__ __forceinline__ float im2col_at(const float *mel, int C, int T, int To, int N, int m, int kidx, int mode) {
+    int c, tap;
+    im2col_ct(mode, kidx, c, tap);
+    const int b = m / To, tt = m - b * To, ti = 2 * tt + tap - 1;
+    return (m < N && ti >= 0 && ti < T) ? mel[((size_t)b * C + c) * T + ti] : 0.f;
+}
+
+// The conv of the layered schedule: Y (M, N) = im2col(mel) (M, 4 C) x W (N, 4 C)^T in the k order `mode` W is arranged in, as an
+// exact chain restarted every KC (gemm_chain.hip).
+int vq_gemm_chain_im2col(const float *mel, int C, int T, int To, const float *W, float *Y, int M, int N, int KC, int mode, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// launches of encoder.hip
+// ------------------------------------------------------------------------------------------
+struct LnConst { float inv[16]; float sc[8]; };      // 1 / (j + 1); 64 / (64 (q + 1)): the weights of ATen's Welford cascade
+
+// One front-end call of the fused / column-split schedules.  The handle fills the model's half once; a call sets mel, the
+// shape, the conv order, the outputs and stage.
+struct FusedP {
+    const float *mel; int C, T, To, N;
+    int conv_mode;                      // 1 im2col order (one chain), 2 direct order (chain restarted every 64 k)
+    const float4 *conv_f;               // conv weight fragments in that order: [32 ct][K/16][64]
+    const float *ln_g[5], *ln_b[5];
+    const float4 *fc_f[4];              // [32 ct][32][64]
+    const float4 *out_f; const float *out_b;   // [4 ct][32][64]
+    const float4 *Ef; const float *E, *e2; int n_emb;
+    float *z_pre; float *z_q; int64_t *idx;
+    float *stage_out; int stage;        // stage dump (vqcpc_encoder_stage): -1 = none
+    float eps; LnConst lnc;
+};
+
+// Y = LayerNorm(512)(X) (+ ReLU), M rows.
+void launch_ln512(const float *X, const float *g, const float *b, float *Y, int M, float eps, int relu, const LnConst &k, hipStream_t s);
+// VQEmbeddingEMA.encode of N rows of 64: Ef codebook fragments (launch_vq_build_frag), e2 = |E|^2 (launch_rowsumsq64).
+void launch_vq_encode(const float *X, int N, const float4 *Ef, const float *E, const float *e2, int n_emb, int64_t *idx, float *zq, hipStream_t s);
+// The whole front end + VQ in one launch (p.stage < 0), or up to p.stage with that stage's rows in p.stage_out.
+void launch_enc_fused(const FusedP &p, hipStream_t s);
+// The same (p.stage < 0 only) in six column-split launches; a, b: two work buffers of N x 512 floats.
+void launch_enc_split(const FusedP &p, float *a, float *b, hipStream_t s);
+// Eval-branch statistics of VQEmbeddingEMA.forward; hist [n_emb] zeroed by the caller, part [nparts].
+void launch_vq_stats(const float *x, const float *q, const int64_t *idx, int n_rows, float *zst, double *part, int nparts, unsigned *hist,
+                     int n_emb, float *loss, float *ppl, hipStream_t s);
+// Weight arrangement at create (default stream).
+void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C);   // conv.weight (O, C, 4) -> (O, 4 C) in the k order of mode 1, 2
+void launch_rowsumsq64(const float *X, float *out, int n);
+void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb);
+void launch_frag16_build(const float *W, int N, int K, float4 *Wf);                     // N % 16 == 0, K % 64 == 0: (N / 16) (K / 16) 64 float4

@@ -19,7 +19,6 @@
 #include <math.h>
 #include <vector>
 
-int vq_require_gfx950();
 constexpr int LC = 128;                    // samples per chunk
 constexpr double BLOCK_S = 0.400, STEP = 1.0 - 0.75, GAMMA_ABS = -70.0;
 

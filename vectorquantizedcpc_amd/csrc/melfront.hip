@@ -6,13 +6,12 @@
 // utterance maximum), / top_db + 1.  Parameters config.py:103-112.
 //
 // The window is only 400 samples wide, so a frame's DFT is a 400-term sum: both contractions
-// (frames x [cos|sin] matrix, magnitudes x mel filterbank) run on the fp32 MFMA GEMM of encoder.hip.
+// (frames x [cos|sin] matrix, magnitudes x mel filterbank) run on the fp32 MFMA GEMM of gemm_chain.hip.
 // librosa is absent offline: checked against oracle/mel_ref.py (numpy float64) -- parity unpinned.
 #include "common.h"
 #include <math.h>
 #include <vector>
 
-int vq_require_gfx950();
 struct vqcpc_melfront {
     int sr, n_fft, n_mels, hop, win;
     float fmin, preemph, top_db;

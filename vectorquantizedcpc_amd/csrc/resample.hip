@@ -9,7 +9,6 @@
 #include <math.h>
 #include <vector>
 
-int vq_require_gfx950();
 struct vqcpc_resampler {
     int sr_in, sr_out;
     double ratio, scale, time_increment;

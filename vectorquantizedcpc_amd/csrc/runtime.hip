@@ -1,0 +1,40 @@
+// runtime.hip -- what every part of libvqcpc_hip.so shares at run time: the per-thread error string, the ABI version and
+// the device query (the library is built for gfx950 only and has no CPU fallback).
+#include "common.h"
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+static thread_local char g_err[512] = "";
+void vq_set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+}
+extern "C" const char *vqcpc_last_error(void) { return g_err; }
+extern "C" int vqcpc_abi_version(void) { return VQCPC_ABI_VERSION; }
+extern "C" int vqcpc_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    int ok = 0;
+    for (int i = 0; i < n; ++i) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, i) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++ok;
+    }
+    return ok;
+}
+int vq_require_gfx950() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        vq_set_error("no HIP device: libvqcpc_hip has no CPU fallback");
+        return VQCPC_ERR_NO_DEVICE;
+    }
+    hipDeviceProp_t p;
+    HIP_TRY(hipGetDeviceProperties(&p, dev));
+    if (strncmp(p.gcnArchName, "gfx950", 6) != 0) {
+        vq_set_error("device %d is %s; this library is built for gfx950 (MI355X) only", dev, p.gcnArchName);
+        return VQCPC_ERR_NO_DEVICE;
+    }
+    return VQCPC_OK;
+}

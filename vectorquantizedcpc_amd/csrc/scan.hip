@@ -7,8 +7,6 @@
 #include "ar_shared.h"
 #include <math.h>
 
-#define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
-
 // ------------------------------------------------------------------------------------------
 // Fragment-ordered weights.  For row group `rg` (16 rows, row_of(rg, i) or -1 = zero row),
 // K split over `ksplit` waves, super-step S = 16 consecutive k:

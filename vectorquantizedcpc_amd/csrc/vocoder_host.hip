@@ -6,7 +6,6 @@
 #include <stdio.h>
 #include <limits.h>
 
-int vq_require_gfx950();
 
 // [rows][3][H] -> unit quads [rows][H/4][4] float4 (r, z, n, 0)
 __global__ void quads_build_kernel(const float *__restrict__ src, float4 *__restrict__ dst, int rows, int H) {

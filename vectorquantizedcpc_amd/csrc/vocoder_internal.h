@@ -55,9 +55,6 @@ struct HostStage {
 // Defaults of the decode-loop options: the handle starts with them, and vqcpc_vocoder_plan takes them for -1 / 0.
 constexpr int XCM_MIN_DEFAULT = 68, XCM_MAX_DEFAULT = 512, XCD_SLOTS_DEFAULT = 8 * XD_MAX_BX, XCM_SLOTS_DEFAULT = 8 * XM_BX;
 
-// An owning device pointer: a DevBuf that reads as a T * (the handle's weights and call records).
-template <class T> struct DevPtr : DevBuf { operator T *() const { return (T *)p; } };
-
 struct vqcpc_vocoder {
     vqcpc_vocoder_weights d;             // dims only (the weights below are owned copies: fixed_buffers)
     DevPtr<float> code_emb, spk_emb;
