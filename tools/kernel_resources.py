@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One line per kernel of a .hip file: VGPRs, SGPRs, spills, scratch, occupancy (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python tools/kernel_resources.py vectorquantizedcpc_amd/csrc/ar_xcd.hip [name filter [extra compiler flags, e.g. -DXD_A16=0]]
+    python tools/kernel_resources.py vectorquantizedcpc_amd/csrc/ar_xcd.hip [name filter [extra compiler flags, e.g. -DXD_HOLD=0]]
 
 Rows are keyed on the MANGLED name (kernels in an anonymous namespace demangle to names that all begin with "(anonymous
 namespace)::", and template instantiations share everything in front of their arguments); the demangled name is what is printed.

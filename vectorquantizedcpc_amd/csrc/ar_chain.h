@@ -1,5 +1,6 @@
-// Device helpers of the per-XCD resident decoders on the vector ALU (ar_xcd.hip; the pipelined variant of round 4, measured and
-// dropped: profiles/r04_xcp_experiment.md): dimensions, granule loads, and a row's fp32 fma chains on v_fmac_f32_dpp -- the same 8
+// Device helpers of the per-XCD resident decoders (ar_xcd.hip, and ar_xcm.hip for the dimensions and the placement check; the
+// pipelined variant of round 4, measured and dropped: profiles/r04_xcp_experiment.md): dimensions, the placement check, granule
+// loads, and a row's fp32 fma chains on the vector ALU, on v_fmac_f32_dpp -- the same 8
 // chains per row as the MFMA schedule of the launch-per-step kernels (ar_shared.h), combined in the same order.
 #pragma once
 #include "ar_xcd.h"
@@ -25,7 +26,29 @@ constexpr int CTL_WORDS = 64;          // u32: arrivals per XCC [0..7], total [8
 // byte offset of a_t row `row` (0..7) of worker `rank`, slot `slot`, in the a_t region
 __device__ __forceinline__ unsigned xg_a_off(unsigned rank, unsigned row, unsigned slot) { return (((slot * NW + rank) << 3) + row) * 8u; }
 
-
+// Placement, run by ONE thread per workgroup: which XCD am I on (xid), which of its workers am I (rank, a ticket)?  Waits, bounded, until
+// the whole grid has taken its tickets; false unless every XCD was dealt exactly `nw` workgroups (STATUS_MISPLACED is then set).  The
+// control words are the first CTL_WORDS of the exchange area, zeroed by the launcher.
+__device__ __forceinline__ bool xd_place(const XdParams &p, int nw, unsigned &xid, unsigned &rank) {
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xid));
+    xid &= 7u;
+    if (p.dbg_misplace && blockIdx.x == 0) xid = (xid + 1u) & 7u;      // tests: one workgroup reports the wrong XCD
+    unsigned *ctl = (unsigned *)p.xg;
+    rank = __hip_atomic_fetch_add(ctl + xid, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(ctl + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool ok = true;
+    const u64 t0 = __builtin_amdgcn_s_memrealtime();
+    for (unsigned spins = 0; __hip_atomic_load(ctl + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x; ++spins) {
+        if ((spins & 63) == 63 && (__builtin_amdgcn_s_memrealtime() - t0 > (u64)p.timeout_ticks ||
+                                   __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) { ok = false; break; }
+        __builtin_amdgcn_s_sleep(2);
+    }
+    if (ok)
+        for (int x = 0; x < 8; ++x)
+            if (__hip_atomic_load(ctl + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)nw) ok = false;
+    if (!ok) __hip_atomic_store(p.status, p.status_tag | STATUS_MISPLACED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return ok;
+}
 
 // Granule traffic is addressed as (uniform 64-bit base in SGPRs) + (32-bit byte offset in a VGPR) + immediate: a 64-bit
 // address per lane and granule costs two VGPRs each, and the chain waves have none to spare.  The loads are sc1 (served by
@@ -54,15 +77,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void gran_chunks2(u32x4 (&v)[2], const u64 *base, unsigned off) {
     asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %3 sc1\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024 sc1\n\ts_waitcnt vmcnt(0)"
                  : "=&v"(v[0]), "=&v"(v[1]) : "v"(off), "s"(base) : "memory");
-}
-template <int STEP>     // the same for two slots (second slot SLOT2 bytes further): eight granules in flight together
-__device__ __forceinline__ void gran_load8b(u64 (&v)[2][4], const u64 *base, const u64 *base2, unsigned off) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %8, %9 sc1\n\tglobal_load_dwordx2 %1, %8, %9 offset:%11 sc1\n\t"
-                 "global_load_dwordx2 %2, %8, %10 sc1\n\tglobal_load_dwordx2 %3, %8, %10 offset:%11 sc1\n\t"
-                 "global_load_dwordx2 %4, %8, %9 offset:128 sc1\n\tglobal_load_dwordx2 %5, %8, %9 offset:%12 sc1\n\t"
-                 "global_load_dwordx2 %6, %8, %10 offset:128 sc1\n\tglobal_load_dwordx2 %7, %8, %10 offset:%12 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(v[0][0]), "=&v"(v[0][1]), "=&v"(v[0][2]), "=&v"(v[0][3]), "=&v"(v[1][0]), "=&v"(v[1][1]), "=&v"(v[1][2]), "=&v"(v[1][3])
-                 : "v"(off), "s"(base), "s"(base2), "i"(STEP), "i"(STEP + 128) : "memory");
 }
 // 2 N granules: N at `off` + i STEP and N at `off2` + i STEP, all in flight together
 template <int N, int STEP>

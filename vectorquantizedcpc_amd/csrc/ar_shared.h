@@ -1,7 +1,11 @@
 // Device helpers shared by the decode kernels of vocoder.hip (launch per step), ar_xcd.hip / ar_xcm.hip (one resident
 // decoder per XCD) and the scans of scan.hip.  Everything that decides a BIT of the result lives here once, so that
-// an utterance decoded on any of the paths gives the same samples: the Philox stream of the sampling protocol, the
-// gate non-linearities, and the order in which a row's fp32 fma chains are loaded and combined.
+// an utterance decoded on any of the paths gives the same samples: the Philox stream of the sampling protocol and the noise of
+// a draw (draw_noise), the gate non-linearities and the cell update (gru_cell), the four-MFMA step of a row's fp32 fma chains
+// (mfma_k4) and the order in which the chains are loaded and combined (sum4), the first argmax over candidates (first_max and its
+// 16-lane DPP form ordered / row_max / row_min), the launch path's candidate granules (cand_*) and a sample going out (emit_sample).
+// NOT here: the prenet GRU and LSTM cells of scan.hip.  They are another specification -- libm gates, g + (W_hh h + b) in one
+// bracket, pinned against the reference's own fixtures -- and stay written out where they are.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -27,22 +31,39 @@ __device__ __forceinline__ void load_wfrag(const float *Wf, int rg, int ksplit, 
     for (int s = 0; s < SW; ++s) wf[s] = p[s * 64];
 }
 
-// 16 rows x 16 utterances partial product over this wave's K quarter.
+// ((q0 + q1) + q2) + q3: a row's sum over its four K quarters, on every path
+__device__ __forceinline__ float sum4(float q0, float q1, float q2, float q3) { return ((q0 + q1) + q2) + q3; }
+// One 16-column block of a K quarter on v_mfma_f32_16x16x4_f32: components x, z feed accumulator a0 and y, w feed a1 (two fma chains
+// per row and quarter); the quarter's sum is a0 + a1.
+__device__ __forceinline__ void mfma_k4(f32x4 &a0, f32x4 &a1, const float4 &w4, const float4 &h4) {
+    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4.x, h4.x, a0, 0, 0, 0);
+    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4.y, h4.y, a1, 0, 0, 0);
+    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4.z, h4.z, a0, 0, 0, 0);
+    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4.w, h4.w, a1, 0, 0, 0);
+}
+// `live` = columns (decode slots) of tile bt in use: a lane of a dead column re-reads column 0 of its k group
+// (same address as a live lane, so it costs no traffic) instead of streaming padding -- at one utterance
+// that is 15/16 of the state bytes.
 template <int SW>
-__device__ __forceinline__ f32x4 mv16(const float4 (&wf)[SW], const float *hL, int K, int bt, int wave, int lane) {
-    const float4 *hp = (const float4 *)hL + ((size_t)bt * (K >> 2)) * 16 + (size_t)wave * SW * 64 + lane;
-    float4 hv[SW];
+__device__ __forceinline__ void load_hfrag(const float *hL, int K, int bt, int wave, int lane, int live, float4 (&hv)[SW]) {
+    const int hl = (lane & 15) < live ? lane : (lane & 48);
+    const float4 *hp = (const float4 *)hL + ((size_t)bt * (K >> 2)) * 16 + (size_t)wave * SW * 64 + hl;
 #pragma unroll
     for (int s = 0; s < SW; ++s) hv[s] = hp[s * 64];
+}
+template <int SW>
+__device__ __forceinline__ f32x4 mfma_frag(const float4 (&wf)[SW], const float4 (&hv)[SW]) {
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < SW; ++s) {
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, hv[s].x, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, hv[s].y, a1, 0, 0, 0);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].z, hv[s].z, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].w, hv[s].w, a1, 0, 0, 0);
-    }
+    for (int s = 0; s < SW; ++s) mfma_k4(a0, a1, wf[s], hv[s]);
     return a0 + a1;
+}
+// 16 rows x 16 utterances partial product over this wave's K quarter, every column live.
+template <int SW>
+__device__ __forceinline__ f32x4 mv16(const float4 (&wf)[SW], const float *hL, int K, int bt, int wave, int lane) {
+    float4 hv[SW];
+    load_hfrag<SW>(hL, K, bt, wave, lane, 16, hv);
+    return mfma_frag<SW>(wf, hv);
 }
 
 // cross-wave reduction of the 4 K-quarters: red[wave][row][b] -> returns sum for (row=tid>>4, b=tid&15)
@@ -51,7 +72,7 @@ __device__ __forceinline__ float reduce4(float (*red)[16][17], const f32x4 &acc,
     for (int r = 0; r < 4; ++r) red[wave][(lane >> 4) * 4 + r][lane & 15] = acc[r];
     __syncthreads();
     const int row = tid >> 4, b = tid & 15;
-    return ((red[0][row][b] + red[1][row][b]) + red[2][row][b]) + red[3][row][b];
+    return sum4(red[0][row][b], red[1][row][b], red[2][row][b], red[3][row][b]);
 }
 
 
@@ -83,6 +104,14 @@ __device__ __forceinline__ float gate_tanh(float v) {            // 1 - 2 / (1 +
     const float q = __builtin_amdgcn_rcpf(1.0f + e);
     return 1.0f - 2.0f * q;
 }
+// The cell update (PyTorch GRUCell equations, gate order r, z, n): e = the embedding row of the sample fed in, g = the conditioning
+// row, s = W_hh h of the unit's three gate rows (sum4 of their K quarters; 0 on an utterance's first step), b = b_hh, hold = h_{t-1}.
+__device__ __forceinline__ float gru_cell(const float (&e)[3], const float (&g)[3], const float (&s)[3], const float (&b)[3], float hold) {
+    const float r = gate_sigmoid((e[0] + g[0]) + (s[0] + b[0]));
+    const float z = gate_sigmoid((e[1] + g[1]) + (s[1] + b[1]));
+    const float n = gate_tanh((e[2] + g[2]) + r * (s[2] + b[2]));
+    return (1.0f - z) * n + z * hold;
+}
 
 // Philox4x32-10, word `k & 3` of counter (t, utt, k >> 2, 0): the sampling protocol's stream.
 __device__ __forceinline__ unsigned philox_word(unsigned c0, unsigned c1, unsigned c2, unsigned k0, unsigned k1, int w) {
@@ -102,6 +131,46 @@ __device__ __forceinline__ unsigned philox_word(unsigned c0, unsigned c1, unsign
 // (0, 1) (a 24-bit form rounds to 1.0f at the top word, i.e. +inf noise that wins whatever the logit is).
 __device__ __forceinline__ float gumbel_from_word(unsigned w) {
     return -logf(-logf(((float)(w >> 9) + 0.5f) * (1.0f / 8388608.0f)));
+}
+// the noise of class `cls` in the draw of sample `lt` of utterance `utt`
+__device__ __forceinline__ float draw_noise(unsigned lt, unsigned utt, unsigned cls, u64 seed) {
+    return gumbel_from_word(philox_word(lt, utt, cls >> 2, (unsigned)seed, (unsigned)(seed >> 32), (int)(cls & 3u)));
+}
+
+// First argmax over candidates taken in class order: a later candidate wins only if it is strictly greater.
+__device__ __forceinline__ void first_max(float &best, int &k, float score, int cls) {
+    if (score > best) { best = score; k = cls; }
+}
+// The same over the 16 lanes of a DPP row, on the order-preserving integer image of the score: m = row_max(ordered(score)), then
+// row_min over the classes of the lanes that hold m.
+__device__ __forceinline__ unsigned ordered(unsigned u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ unsigned row_max(unsigned m) {             // result in all 16 lanes
+    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));      // quad_perm [1,0,3,2]
+    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));      // quad_perm [2,3,0,1]
+    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));     // row_half_mirror
+    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));     // row_mirror
+    return m;
+}
+__device__ __forceinline__ unsigned row_min(unsigned m) {
+    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));
+    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));
+    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));
+    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
+    return m;
+}
+
+// Candidate granule of the launch path's fused schedule: {tag = step mod 2^22 (CAND_TAG_BITS), class < 1024, score}
+__device__ __forceinline__ u64 cand_pack(unsigned tag, unsigned cls, float score) { return ((u64)((tag << 10) | cls) << 32) | __float_as_uint(score); }
+__device__ __forceinline__ unsigned cand_tag(u64 g) { return (unsigned)(g >> 42); }
+__device__ __forceinline__ int cand_class(u64 g) { return (int)((g >> 32) & 1023u); }
+__device__ __forceinline__ float cand_score(u64 g) { return __uint_as_float((unsigned)g); }
+
+// Sample x goes out (network_vocoder.py:78 output): its mu-law decoded value and, if asked for, the class itself.  The pointers keep
+// their types (address spaces), so each site stores as it did.
+template <class PW, class PM, class TB>
+__device__ __forceinline__ void emit_sample(PW wav, PM mulaw, size_t at, int x, TB tab) {
+    if (wav) wav[at] = tab[x];
+    if (mulaw) mulaw[at] = x;
 }
 
 // A row's dot product over K = 64 NS runs as 8 fp32 fma chains, exactly those of the v_mfma_f32_16x16x4_f32 schedule of

@@ -109,12 +109,6 @@ extern "C" int vqcpc_debug_xd_bars(unsigned long long *out) {
 #define XD_HOLD 1
 #endif
 
-// the a_t sweep of an fc2 wave takes its four granules as two 16-byte loads (0: as four 8-byte loads of the same region -- A/B builds,
-// profiles/r07_ab_exchange_sweeps.txt)
-#ifndef XD_A16
-#define XD_A16 1
-#endif
-
 namespace {
 
 // LDS carve, in floats (ints behind them)
@@ -152,24 +146,8 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
 
     // ---- placement: which XCD am I on, which of its 32 workers am I?
     if (tid == 0) {
-        unsigned xid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xid));
-        xid &= 7u;
-        if (p.dbg_misplace && blockIdx.x == 0) xid = (xid + 1u) & 7u;      // tests: one workgroup reports the wrong XCD
-        unsigned *ctl = (unsigned *)p.xg;
-        const unsigned r = __hip_atomic_fetch_add(ctl + xid, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(ctl + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int ok = 1;
-        const u64 t0 = __builtin_amdgcn_s_memrealtime();
-        for (unsigned spins = 0; __hip_atomic_load(ctl + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x; ++spins) {
-            if ((spins & 63) == 63 && (__builtin_amdgcn_s_memrealtime() - t0 > (u64)p.timeout_ticks ||
-                                       __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) { ok = 0; break; }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (ok)
-            for (int x = 0; x < 8; ++x)
-                if (__hip_atomic_load(ctl + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)NW) ok = 0;
-        if (!ok) __hip_atomic_store(p.status, p.status_tag | STATUS_MISPLACED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        unsigned xid, r;
+        const int ok = xd_place(p, NW, xid, r);
         s_ctl[0] = (int)xid; s_ctl[1] = (int)r; s_ctl[2] = ok; s_ctl[3] = 0; s_ctl[4] = (int)p.status_tag; s_ctl[5] = 0;
     }
     __syncthreads();
@@ -312,20 +290,14 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
             if (*s_abort) break;
             auto fc2_and_draw = [&]() {
                 // ---- a_t of slot fs (256 granules in one run, 4 per lane) -> fc2 -> Gumbel-max candidate of the 8 owned classes
-#if XD_A16
                 // the lane's granules are the 16-byte chunks lane and lane + 64 of the run: a_t[2 lane], a_t[2 lane + 1] and the same 128 further
                 const unsigned aoff = xg_a_off(0u, 0u, (unsigned)fs) + lane * 16u;
                 const unsigned adst = (unsigned)chain_pos<HF / 64>(2 * (int)lane, 48);   // a_t[k + 1]: the chain next door (48 further), a_t[k + 128]: 192 further
-#else
-                const unsigned aoff = xg_a_off(0u, 0u, (unsigned)fs) + lane * 8u;
-                const unsigned adst = (unsigned)chain_pos<HF / 64>((int)lane, 48);      // a_t[lane + 64 i]: chain 2 i + (lane & 1), i.e. 96 i further
-#endif
                 float4 wa = wp2[0], wb = wp2[64];                    // first weights and the noise: on their way during the sweep
                 unsigned lno = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));      // the lane id, from the hardware
                 asm volatile("" : "+v"(lno));      // opaque, and rebuilt: the hoisted address of this read -- then r8, then the lane id
                 const unsigned r8o = ((lno >> 5) << 2) | (lno & 3u);      // itself -- was spilled to scratch and reloaded at every step
                 const float nz = noise[(t & 1) * (BXT * 8) + fs * 8 + r8o];
-#if XD_A16
                 u32x4 va[2];
                 wt.start();
                 for (unsigned spins = 0;; ++spins) {
@@ -339,20 +311,6 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     ac[fs * (8 * 48) + 192 * i + adst] = __uint_as_float(va[i][0]);
                     ac[fs * (8 * 48) + 192 * i + 48 + adst] = __uint_as_float(va[i][2]);
                 }
-#else
-                u64 va[4];
-                wt.start();
-                for (unsigned spins = 0;; ++spins) {
-                    gran_load4<512>(va, ga, aoff);
-                    bool ok = true;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) ok &= (unsigned)(va[i] >> 32) == tag;
-                    if ((XD_ABLATE & 2) || __all(ok)) break;
-                    if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ac[fs * (8 * 48) + 96 * i + adst] = __uint_as_float((unsigned)va[i]);
-#endif
                 XD_STAMP(2, 8);
                 const float4 a0 = *(const float4 *)opnd2, a1 = *(const float4 *)(opnd2 + 16);
                 const float hv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -418,8 +376,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     const int b = (int)(ln >> 3);
                     if (ln < 32 && b < bx) {
                         const unsigned cls = FPB * rank + (ln & 7u);
-                        const unsigned wd = philox_word((unsigned)sinfo[b * 2], (unsigned)sinfo[b * 2 + 1], cls >> 2, (unsigned)p.seed, (unsigned)(p.seed >> 32), (int)(cls & 3u));
-                        noise[((t + 1) & 1) * (BXT * 8) + b * 8 + (ln & 7u)] = gumbel_from_word(wd);
+                        noise[((t + 1) & 1) * (BXT * 8) + b * 8 + (ln & 7u)] = draw_noise((unsigned)sinfo[b * 2], (unsigned)sinfo[b * 2 + 1], cls, p.seed);
                     }
                 }
             } else {
@@ -520,7 +477,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
             }
         };
         // the Gumbel noise of step `tn`'s draw (it does not depend on the data): class lane & 7 of slot sv + 2 ((lane >> 3) & 1)
-        auto draw_noise = [&](int tn) {
+        auto post_noise = [&](int tn) {
             const int lt_b = __builtin_amdgcn_readlane(st_lt, 0), lt_b2 = __builtin_amdgcn_readlane(st_lt, 32);
             const unsigned ut_b = __builtin_amdgcn_readlane(st_utt, 0), ut_b2 = __builtin_amdgcn_readlane(st_utt, 32);
             unsigned ln = lane;
@@ -529,14 +486,12 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 const int which = (int)(ln >> 3), b = sv + 2 * which;
                 if (b < bx) {
                     const unsigned cls = FPB * rank + (ln & 7u);
-                    const unsigned wd = philox_word((unsigned)(which ? lt_b2 : lt_b), which ? ut_b2 : ut_b, cls >> 2,
-                                                    (unsigned)p.seed, (unsigned)(p.seed >> 32), (int)(cls & 3u));
-                    noise[(tn & 1) * (BXT * 8) + b * 8 + (ln & 7u)] = gumbel_from_word(wd);
+                    noise[(tn & 1) * (BXT * 8) + b * 8 + (ln & 7u)] = draw_noise((unsigned)(which ? lt_b2 : lt_b), which ? ut_b2 : ut_b, cls, p.seed);
                 }
             }
         };
         advance(0);
-        draw_noise(0);
+        post_noise(0);
         ps_barrier();                                                    // state and noise of step 0 posted
 
         int x = NC / 2;
@@ -556,7 +511,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 if (st_active && cu < UPB) {
                     const int xe = st_first ? (RESUME ? st_xin : NC / 2) : x;
                     const float e0 = gemb[(xe * 3 + 0) * UPB + cu], e1 = gemb[(xe * 3 + 1) * UPB + cu], e2 = gemb[(xe * 3 + 2) * UPB + cu];
-                    const float r = gate_sigmoid((e0 + g0) + s0);
+                    const float r = gate_sigmoid((e0 + g0) + s0);            // gru_cell, written out (s = W_hh h + b_hh)
                     const float z = gate_sigmoid((e1 + g1) + s1);
                     const float nn = gate_tanh((e2 + g2) + r * sn);
                     hn = (1.0f - z) * nn + z * hold;
@@ -572,7 +527,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
             // ---- in the shadow of the h_t exchange: the sample x_{t-1} goes out (network_vocoder.py:78 output), the slot's state
             // and the noise for step t + 1, the first phase of the fc1 weights
             if (st_emit && cu == 0 && rank == (cb & 31)) {
-                if (p.wav) p.wav[(size_t)st_erow * p.Lout + st_eidx] = mtab[x];
+                if (p.wav) p.wav[(size_t)st_erow * p.Lout + st_eidx] = mtab[x];      // emit_sample, written out
                 if (p.mulaw) p.mulaw[(size_t)st_erow * p.Lout + st_eidx] = x;
             }
             advance(t + 1);
@@ -645,7 +600,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
             }
             XD_STAMP(0, 7);
             XD_STAMP(1, 11);
-            if (BXT != 4) draw_noise(t + 1);                             // idle time: the candidates are still on their way (four slots: wave 11 draws)
+            if (BXT != 4) post_noise(t + 1);                             // idle time: the candidates are still on their way (four slots: wave 11 draws)
             XD_STAMP(0, 13);
             // ---- x_t: the slot's 32 candidates (tag t + 1, from the chain waves' fc2), picked up BEFORE barrier B
             __builtin_amdgcn_s_setprio(3);
@@ -658,13 +613,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }
                 }
                 // first argmax per half of 32 lanes (classes ascend with the rank): order-preserving integer image of the score
-                unsigned u = (unsigned)g;
-                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-                unsigned m = u;
-                m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));
-                m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));
-                m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));
-                m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
+                const unsigned u = ordered((unsigned)g), m = row_max(u);
                 const unsigned m0 = __builtin_amdgcn_readlane(m, 0), m1 = __builtin_amdgcn_readlane(m, 16),
                                m2 = __builtin_amdgcn_readlane(m, 32), m3 = __builtin_amdgcn_readlane(m, 48);
                 const unsigned b01 = max(m0, m1), b23 = max(m2, m3);

@@ -34,8 +34,7 @@
 // quarter of tile 4 behind x_t instead of behind the fc1 publish: 11.2 us.
 // Exchanges are the 8-byte {tag, value} granules of ar_xcd.hip, two per 16-byte load, laid out so that every sweep reads
 // a linear array.  Every wait is wall-clock bounded (STATUS_TIMEOUT, vqcpc_vocoder_check); placement is checked as there.
-#include "ar_xcd.h"
-#include "ar_shared.h"
+#include "ar_chain.h"
 
 // Timeline stamps of worker 5 of XCD 0 (100 MHz wall clock), steps 256..383, for tools/xcm_timeline.py: compiled in only
 // with -DVQCPC_XD_STAMPS (a debug build under build/stamps/, never the shipped library).
@@ -52,11 +51,7 @@ extern "C" int vqcpc_debug_xm_stamps(unsigned long long *out) {
 
 namespace {
 
-constexpr int HR = 896, HF = 256, NC = 256;
-constexpr int NW = 32;                 // workgroups per XCD
-constexpr int UPB = 28;                // hidden units per workgroup
-constexpr int FPB = 8;                 // fc1 rows / fc2 classes per workgroup
-constexpr int THREADS = 768;
+// HR, HF, NC, NW, UPB, FPB, THREADS, CTL_WORDS: ar_chain.h
 constexpr int BX = XM_BX;              // decode slots per XCD = columns of an MFMA tile
 constexpr int LROWS = 96;              // rows of a workgroup: 84 of W_hh [gate][unit], 8 of fc1, 4 of padding
 // Slot strides of h_t / a_t in LDS (floats): 2 units of 16 bytes mod 16.  A B fragment is read by ds_read_b128 with lane = (slot, aq) at
@@ -71,15 +66,11 @@ constexpr int ASD = HF + 8;
 constexpr int CELLS = UPB * BX;        // cell-update threads: (unit, slot)
 constexpr int BOOK = 11;               // the wave that keeps the slots' books (the youngest: it has nothing else to do behind its MFMAs)
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // exchange area of one XCD, in granules
 constexpr int XM_H = HR * BX;          // [column = 28 rank + unit][slot]
 constexpr int XM_A = HF * BX;          // [row = 8 rank + f][slot]
 constexpr int XM_C = BX * NW;          // [slot][rank]
 constexpr int XM_REGION = XM_H + XM_A + XM_C;
-constexpr int CTL_WORDS = 64;          // u32: arrivals per XCC [0..7], total [8]
 
 // LDS carve, in floats (ints behind them)
 struct Lds {
@@ -120,45 +111,10 @@ __device__ __forceinline__ void chunks8(u32x4 (&v)[8], const u64 *b, unsigned of
 __device__ __forceinline__ void chunks1(u32x4 (&v)[1], const u64 *b, unsigned off) {
     asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v[0]) : "v"(off), "s"(b) : "memory");
 }
-// three chunks from three uniform bases
-__device__ __forceinline__ void chunks3(u32x4 (&v)[3], const u64 *b0, const u64 *b1, const u64 *b2, unsigned off) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %3, %4 sc1\n\tglobal_load_dwordx4 %1, %3, %5 sc1\n\tglobal_load_dwordx4 %2, %3, %6 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]) : "v"(off), "s"(b0), "s"(b1), "s"(b2) : "memory");
-}
-// four chunks 1 KB apart from one base
-__device__ __forceinline__ void chunks4(u32x4 (&v)[4], const u64 *b, unsigned off) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %4, %5 sc1\n\tglobal_load_dwordx4 %1, %4, %5 offset:1024 sc1\n\t"
-                 "global_load_dwordx4 %2, %4, %5 offset:2048 sc1\n\tglobal_load_dwordx4 %3, %4, %5 offset:3072 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(off), "s"(b) : "memory");
-}
-__device__ __forceinline__ void chunks2(u32x4 (&v)[2], const u64 *b, unsigned off0, unsigned off1) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %4 sc1\n\tglobal_load_dwordx4 %1, %3, %4 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]) : "v"(off0), "v"(off1), "s"(b) : "memory");
-}
-
-// max / min over the 16 lanes of a DPP row, result in all of them
-__device__ __forceinline__ unsigned row_max(unsigned m) {
-    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));      // quad_perm [1,0,3,2]
-    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));      // quad_perm [2,3,0,1]
-    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));     // row_half_mirror
-    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));     // row_mirror
-    return m;
-}
-__device__ __forceinline__ unsigned row_min(unsigned m) {
-    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));
-    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));
-    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));
-    m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
-    return m;
-}
-__device__ __forceinline__ unsigned ordered(unsigned u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }     // order-preserving image of a float
-
 // A value the optimiser must recompute behind this point: the sample loop keeps 112 weight registers per lane for the whole
 // call, and every loop-invariant address hipcc hoists out of it (it finds dozens) is spilled to scratch.  Each phase of a
 // step derives its addressing from an opaque copy of the thread index instead.
 __device__ __forceinline__ unsigned opq(unsigned x) { asm volatile("" : "+v"(x)); return x; }
-
-#define XM_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // Kernel arguments that are needed once per sample step or less live in LDS (ints) and are read where they are used: held in
 // SGPRs for the whole call they were spilled to VGPR lanes.  (Read through the __shared__ array's own address space: a struct
@@ -183,24 +139,8 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
 
     // ---- placement: which XCD am I on, which of its 32 workers am I?  (as ar_xcd.hip)
     if (tid == 0) {
-        unsigned xid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xid));
-        xid &= 7u;
-        if (p.dbg_misplace && blockIdx.x == 0) xid = (xid + 1u) & 7u;      // tests: one workgroup reports the wrong XCD
-        unsigned *ctl = (unsigned *)p.xg;
-        const unsigned r = __hip_atomic_fetch_add(ctl + xid, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(ctl + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int ok = 1;
-        const u64 t0 = __builtin_amdgcn_s_memrealtime();
-        for (unsigned spins = 0; __hip_atomic_load(ctl + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x; ++spins) {
-            if ((spins & 63) == 63 && (__builtin_amdgcn_s_memrealtime() - t0 > (u64)p.timeout_ticks ||
-                                       __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) { ok = 0; break; }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (ok)
-            for (int x = 0; x < 8; ++x)
-                if (__hip_atomic_load(ctl + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)NW) ok = 0;
-        if (!ok) __hip_atomic_store(p.status, p.status_tag | STATUS_MISPLACED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        unsigned xid, r;
+        const int ok = xd_place(p, NW, xid, r);
         par_set(par, PAR_WAV, (unsigned long long)p.wav); par_set(par, PAR_MULAW, (unsigned long long)p.mulaw); par_set(par, PAR_SEGS, (unsigned long long)p.segs);
         par_set(par, PAR_GCOND, (unsigned long long)p.Gcond); par_set(par, PAR_SEED, p.seed); par_set(par, PAR_GEMB, (unsigned long long)p.Gemb);
         par[PAR_LOUT] = p.Lout; par[PAR_MAXSEG] = p.max_seg; par[PAR_F] = p.F; par[PAR_UPS] = p.upsample; par[PAR_DROP] = p.dbg_drop_step;
@@ -322,7 +262,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
             if (b < bx) {
                 const unsigned cls = FPB * rank + (ln & 7u);
                 const unsigned long long seed = par_q(par, PAR_SEED);
-                const unsigned wd = philox_word((unsigned)sn[b * 8 + 2], (unsigned)sn[b * 8 + 3], cls >> 2, (unsigned)seed, (unsigned)(seed >> 32), (int)(cls & 3u));
+                const unsigned wd = philox_word((unsigned)sn[b * 8 + 2], (unsigned)sn[b * 8 + 3], cls >> 2, (unsigned)seed, (unsigned)(seed >> 32), (int)(cls & 3u));      // draw_noise, written out
                 noise[((tn & 1) * BX + b) * 8 + (ln & 7u)] = gumbel_from_word(wd);
             }
         }
@@ -357,16 +297,16 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
                 if (active && !first) {
                     const float *pp = part + cu * BX + cs;
                     constexpr int Q = LROWS * BX;
-                    s0 = ((pp[0] + pp[Q]) + pp[2 * Q]) + pp[3 * Q];
-                    s1 = ((pp[UPB * BX] + pp[Q + UPB * BX]) + pp[2 * Q + UPB * BX]) + pp[3 * Q + UPB * BX];
-                    sn = ((pp[2 * UPB * BX] + pp[Q + 2 * UPB * BX]) + pp[2 * Q + 2 * UPB * BX]) + pp[3 * Q + 2 * UPB * BX];
+                    s0 = sum4(pp[0], pp[Q], pp[2 * Q], pp[3 * Q]);
+                    s1 = sum4(pp[UPB * BX], pp[Q + UPB * BX], pp[2 * Q + UPB * BX], pp[3 * Q + UPB * BX]);
+                    sn = sum4(pp[2 * UPB * BX], pp[Q + 2 * UPB * BX], pp[2 * Q + 2 * UPB * BX], pp[3 * Q + 2 * UPB * BX]);
                     hold = hprev;
                 }
                 s0 += bqs[cu]; s1 += bqs[32 + cu]; sn += bqs[64 + cu];
                 float hn = 0.f;
                 if (active) {
                     const float *cp = gcl + cs * 84 + cu;
-                    const float r = gate_sigmoid((e0 + cp[0]) + s0);
+                    const float r = gate_sigmoid((e0 + cp[0]) + s0);         // gru_cell, written out (s = W_hh h + b_hh)
                     const float z = gate_sigmoid((e1 + cp[UPB]) + s1);
                     const float nn = gate_tanh((e2 + cp[2 * UPB]) + r * sn);
                     hn = (1.0f - z) * nn + z * hold;
@@ -420,10 +360,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
             for (int b = 0; b < 14; ++b) {
                 if (b + 2 < 14) q[(b + 2) % 3] = hb[4 * (b + 2)];
                 const float4 hv = q[b % 3];
-                acc0 = XM_MFMA(wq[4 * b + 0], hv.x, acc0);
-                acc1 = XM_MFMA(wq[4 * b + 1], hv.y, acc1);
-                acc0 = XM_MFMA(wq[4 * b + 2], hv.z, acc0);
-                acc1 = XM_MFMA(wq[4 * b + 3], hv.w, acc1);
+                mfma_k4(acc0, acc1, make_float4(wq[4 * b + 0], wq[4 * b + 1], wq[4 * b + 2], wq[4 * b + 3]), hv);
             }
             const v4f qs = acc0 + acc1;
             float *pw = part + ((size_t)kwq * LROWS + 16 * tlq + 4 * (ln >> 4)) * BX + (ln & 15u);
@@ -453,7 +390,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int f = 4 * ((int)aq - 1) + i;
-                        float v = ((qA[i] + pr[Q + i * BX]) + pr[2 * Q + i * BX]) + pr[3 * Q + i * BX];
+                        float v = sum4(qA[i], pr[Q + i * BX], pr[2 * Q + i * BX], pr[3 * Q + i * BX]);
                         v += bqs[96 + f];
                         v = v > 0.f ? v : 0.f;
                         xd_put(ga, ((unsigned)(FPB * rank + f) * BX + XM_SLOT(arow)) * 8u, ((u64)tag << 32) | __float_as_uint(v), agent);
@@ -504,13 +441,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
                 const float4 *ab = (const float4 *)(aT + (ln & 15u) * ASD + 64 * wave + 4 * (ln >> 4));
                 const float4 *wb = (const float4 *)f2a + (4 * wave) * 64 + ln;
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const float4 av = ab[4 * b], wv = wb[64 * b];
-                    a0 = XM_MFMA(wv.x, av.x, a0);
-                    a1 = XM_MFMA(wv.y, av.y, a1);
-                    a0 = XM_MFMA(wv.z, av.z, a0);
-                    a1 = XM_MFMA(wv.w, av.w, a1);
-                }
+                for (int b = 0; b < 4; ++b) mfma_k4(a0, a1, wb[64 * b], ab[4 * b]);
                 fq = a0 + a1;
             }
             XM_STAMP(0, 20);
@@ -537,7 +468,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             const float *fp = fcx + (4 * aq + i) * BX + arow;
-                            float v = ((fq[i] + fp[8 * BX]) + fp[16 * BX]) + fp[24 * BX];
+                            float v = sum4(fq[i], fp[8 * BX], fp[16 * BX], fp[24 * BX]);
                             v += bqs[104 + 4 * aq + i];
                             const float sc = v + nz[i];
                             if (i == 0 || sc > best) { best = sc; kb = 4 * (int)aq + i; }
@@ -579,7 +510,7 @@ __global__ __launch_bounds__(THREADS) void ar_xcm_kernel(XdParams p) {
                             const size_t at = (size_t)si[b * 8 + 4] * par_i(par, PAR_LOUT) + si[b * 8 + 2];
                             auto wav = PAR_GLOBAL(float, par, PAR_WAV);
                             auto mulaw = PAR_GLOBAL(int64_t, par, PAR_MULAW);
-                            if (wav) wav[at] = mtab[x];
+                            if (wav) wav[at] = mtab[x];                         // emit_sample, written out
                             if (mulaw) mulaw[at] = (int64_t)x;
                         }
                     }

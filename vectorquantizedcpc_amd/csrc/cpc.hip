@@ -17,6 +17,7 @@
 // cpc_finish_kernel, one workgroup: adds the partials of each step in a fixed order (strided per thread, then an LDS
 // tree) -- no float atomics anywhere, so equal inputs give equal bits.  Correct counts are integers.
 #include "cpc_protocol.h"
+#include "ar_shared.h"
 
 namespace {
 
@@ -55,13 +56,7 @@ __global__ __launch_bounds__(256) void cpc_score_kernel(CpcArgs a) {
         const float4 *wp = (const float4 *)(a.W + ((size_t)(k - 1) * CPC_D + wave * 16 + (lane & 15)) * C) + (lane >> 4);
         const float4 *cp = (const float4 *)(a.c + ((size_t)n * a.T + ta) * C) + (lane >> 4);
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-        for (int s = 0; s < (C >> 4); ++s) {
-            const float4 wv = wp[s * 4], cv = cp[s * 4];
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.x, cv.x, a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.y, cv.y, a1, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.z, cv.z, a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, cv.w, a1, 0, 0, 0);
-        }
+        for (int s = 0; s < (C >> 4); ++s) mfma_k4(a0, a1, wp[s * 4], cp[s * 4]);
         const f32x4 acc = a0 + a1;                       // C/D map: column = lane & 15 (anchor), row = 4 (lane >> 4) + r (feature)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {

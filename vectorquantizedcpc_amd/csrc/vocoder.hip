@@ -75,7 +75,7 @@ __device__ __forceinline__ void load_candidates16(const ArModel &m, int sg, int 
 __device__ __forceinline__ void merge16(const Cand16 &cd, float &best, int &k) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        if (cd.s[q].x > best) { best = cd.s[q].x; k = cd.k[q].x; }
+        if (cd.s[q].x > best) { best = cd.s[q].x; k = cd.k[q].x; }      // first_max, written out
         if (cd.s[q].y > best) { best = cd.s[q].y; k = cd.k[q].y; }
         if (cd.s[q].z > best) { best = cd.s[q].z; k = cd.k[q].z; }
         if (cd.s[q].w > best) { best = cd.s[q].w; k = cd.k[q].w; }
@@ -111,7 +111,7 @@ __device__ __forceinline__ int wait_candidates(const ArModel &m, int sg, int t, 
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 gv[q] = ps_load(cg + q * 16);
-                ok &= (unsigned)(gv[q] >> 42) == tag;
+                ok &= cand_tag(gv[q]) == tag;
             }
             if (__all(ok || !need)) break;
             if ((spins & 255) == 255 && __builtin_amdgcn_s_memrealtime() - t0 > (u64)m.timeout_ticks) {      // default 0.25 s
@@ -124,34 +124,11 @@ __device__ __forceinline__ int wait_candidates(const ArModel &m, int sg, int t, 
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {                               // row groups are in class order: first argmax
-            const float sq = __uint_as_float((unsigned)gv[q]);
-            if (!gave_up && sq > best) { best = sq; xf = (int)((gv[q] >> 32) & 1023u); }
+            const float sq = cand_score(gv[q]);
+            if (!gave_up && sq > best) { best = sq; xf = cand_class(gv[q]); }      // first_max, written out
         }
     }
     return xf;
-}
-
-// `live` = columns (decode slots) of tile bt in use: a lane of a dead column re-reads column 0 of its k group
-// (same address as a live lane, so it costs no traffic) instead of streaming padding -- at one utterance
-// that is 15/16 of the state bytes.
-template <int SW>
-__device__ __forceinline__ void load_hfrag(const float *hL, int K, int bt, int wave, int lane, int live, float4 (&hv)[SW]) {
-    const int hl = (lane & 15) < live ? lane : (lane & 48);
-    const float4 *hp = (const float4 *)hL + ((size_t)bt * (K >> 2)) * 16 + (size_t)wave * SW * 64 + hl;
-#pragma unroll
-    for (int s = 0; s < SW; ++s) hv[s] = hp[s * 64];
-}
-template <int SW>
-__device__ __forceinline__ f32x4 mfma_frag(const float4 (&wf)[SW], const float4 (&hv)[SW]) {
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < SW; ++s) {
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, hv[s].x, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, hv[s].y, a1, 0, 0, 0);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].z, hv[s].z, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].w, hv[s].w, a1, 0, 0, 0);
-    }
-    return a0 + a1;
 }
 
 // Scheduling notes (checked in the .s and with tools/decode_timeline.py): hipcc otherwise sinks each fragment
@@ -170,19 +147,6 @@ __device__ __forceinline__ f32x4 mfma_frag(const float4 (&wf)[SW], const float4 
 // (1.6 us after a cold start) off the critical path of a sample step.  Every wait is wall-clock bounded; a timeout sets
 // an abort word that makes every later wait of the call return at once, and the host reports it.
 // FUSED = 0 (teacher-forced scan, eager timing, > 4 tiles): candidates come from the previous launch's plain arrays.
-// fc2 over one 16-class row group + its Gumbel-max candidate per utterance, for local step `ts` (Hf = 256: SW = 4).
-// Used by ar_fc2_kernel (plain candidate arrays) and by the fused launch (granules).  All threads of the workgroup must
-// call it (two barriers); threads >= 256 only take part in those.
-// Bounded wait shared by the in-kernel hand-offs: true once `deadline` has passed (the abort words are then set).
-__device__ __forceinline__ bool handoff_timed_out(const ArModel &m, u64 t0, unsigned spins, int lane) {
-    if ((spins & 255) != 255 || __builtin_amdgcn_s_memrealtime() - t0 <= (u64)m.timeout_ticks) return false;      // default 0.25 s
-    if (lane == 0) {
-        __hip_atomic_store(m.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(m.abort_host, STATUS_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return true;
-}
-
 // fc1 + ReLU over ROWS rows x one utterance tile for local step `ts` (the GRU of that step has written its state).
 // `tid` / `worker` as in fc2_body.
 template <int SW, int ROWS>
@@ -209,7 +173,7 @@ __device__ __forceinline__ void fc1_body(const ArModel &m, const ArCall *__restr
     __syncthreads();
     if (worker && valid && own) {
         const int rr = (tid >> 4) & 15, bb = tid & 15;
-        float v = ((red[0][rr][bb] + red[1][rr][bb]) + red[2][rr][bb]) + red[3][rr][bb];
+        float v = sum4(red[0][rr][bb], red[1][rr][bb], red[2][rr][bb], red[3][rr][bb]);
         v += bias;
         v = v > 0.f ? v : 0.f;
         const size_t at = hl_index(m.Hf, bt * 16 + bb, row);
@@ -217,6 +181,9 @@ __device__ __forceinline__ void fc1_body(const ArModel &m, const ArCall *__restr
     }
 }
 
+// fc2 over one 16-class row group + its Gumbel-max candidate per utterance, for local step `ts` (Hf = 256: SW = 4).
+// Used by ar_fc2_kernel (plain candidate arrays) and by the fused launch (granules).  All threads of the workgroup must
+// call it (two barriers); threads >= 256 only take part in those.
 // `tid` = index inside the 256-thread team that computes (rg, bt); `worker` = false for threads that only keep the
 // workgroup's barriers company (the tail of a 320/384-thread block, teams past the last (rg, bt) of a 1024-thread block).
 template <int GRANULES>
@@ -241,17 +208,13 @@ __device__ __forceinline__ void fc2_body(const ArModel &m, const ArCall *__restr
     const XdSeg sl = m.cur[bg];
     const int lt = t - sl.t0;
     // noise of (class, utterance, sample) while the loads fly
-    const unsigned w = philox_word((unsigned)lt, sl.utt, (unsigned)(cls >> 2), (unsigned)c.seed,
-                                   (unsigned)(c.seed >> 32), cls & 3);
-    // 23 random bits + 0.5: every value is exact in fp32 and strictly inside (0, 1) -- a 24-bit form rounds to 1.0f
-    // at w >> 8 == 0xFFFFFF, i.e. +inf noise that wins whatever the logit is
-    const float g = gumbel_from_word(w);
+    const float g = draw_noise((unsigned)lt, sl.utt, (unsigned)cls, c.seed);
     const bool live = ts >= 0 && t < c.max_t && sl.row >= 0 && lt >= 0 && lt < sl.len;
     __builtin_amdgcn_sched_barrier(0);
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
     for (int s0 = 0;;) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < 4; ++q) {                                    // mfma_k4, written out
             a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q].x, hv[q].x, a0, 0, 0, 0);
             a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q].y, hv[q].y, a1, 0, 0, 0);
             a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q].z, hv[q].z, a0, 0, 0, 0);
@@ -269,7 +232,7 @@ __device__ __forceinline__ void fc2_body(const ArModel &m, const ArCall *__restr
     }
     __syncthreads();
     if (worker) {
-        float v = ((red[0][rr][bb] + red[1][rr][bb]) + red[2][rr][bb]) + red[3][rr][bb];
+        float v = sum4(red[0][rr][bb], red[1][rr][bb], red[2][rr][bb], red[3][rr][bb]);
         v += bias;
         if (c.logits && live) c.logits[((size_t)sl.row * c.Ts + lt) * m.n_cls + cls] = v;
         sc[rr][bb] = v + g;
@@ -279,12 +242,11 @@ __device__ __forceinline__ void fc2_body(const ArModel &m, const ArCall *__restr
         float best = sc[0][bb];
         int k = 0;
 #pragma unroll
-        for (int r = 1; r < 16; ++r)
-            if (sc[r][bb] > best) { best = sc[r][bb]; k = r; }
+        for (int r = 1; r < 16; ++r) first_max(best, k, sc[r][bb], r);
         if (GRANULES) {
             const unsigned tag = (unsigned)(t + 1) & ((1u << CAND_TAG_BITS) - 1u);
             if (!(m.dbg_drop_t >= 0 && t == m.dbg_drop_t && rg == 3 && bt == 0))
-            ps_store(m.candg + ((size_t)(bt * nrg + rg) * 16 + bb), ((u64)((tag << 10) | (unsigned)(16 * rg + k)) << 32) | __float_as_uint(best));
+            ps_store(m.candg + ((size_t)(bt * nrg + rg) * 16 + bb), cand_pack(tag, (unsigned)(16 * rg + k), best));
         } else {
             m.cand_s[(size_t)bg * nrg + rg] = best;
             m.cand_k[(size_t)bg * nrg + rg] = 16 * rg + k;
@@ -326,7 +288,7 @@ __global__ __launch_bounds__(64 * (4 + NB)) void ar_gru_kernel(ArModel m, const 
     {
         const int bt0 = pass * NB;
         bool active = false, first = false;
-        float ge0 = 0.f, ge1 = 0.f, ge2 = 0.f, gc0 = 0.f, gc1 = 0.f, gc2 = 0.f, bh0 = 0.f, bh1 = 0.f, bh2 = 0.f, hold = 0.f;
+        float ge[3] = {0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f}, bh[3] = {0.f, 0.f, 0.f}, hold = 0.f;
         size_t hi = 0;
         int xraw = 0;
         bool emit = false;
@@ -368,7 +330,7 @@ __global__ __launch_bounds__(64 * (4 + NB)) void ar_gru_kernel(ArModel m, const 
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int q = 0; q < NB; ++q) {                           // same chains as mfma_frag: (x, z) -> a0, (y, w) -> a1
+                for (int q = 0; q < NB; ++q) {                           // mfma_k4, written out
                     a0[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, hv[q][s].x, a0[q], 0, 0, 0);
                     a1[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, hv[q][s].y, a1[q], 0, 0, 0);
                     a0[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].z, hv[q][s].z, a0[q], 0, 0, 0);
@@ -397,8 +359,8 @@ __global__ __launch_bounds__(64 * (4 + NB)) void ar_gru_kernel(ArModel m, const 
             hi = hl_index(Hr, sg, unit);
             const float hprev = hin[hi];
             const float4 gq = m.gcur4[((size_t)rg * (nbt * 16) + sg) * 4 + u];     // no branch around loads: gcur4 always exists
-            bh0 = bq.x; bh1 = bq.y; bh2 = bq.z;
-            gc0 = gq.x; gc1 = gq.y; gc2 = gq.z;
+            bh[0] = bq.x; bh[1] = bq.y; bh[2] = bq.z;
+            gc[0] = gq.x; gc[1] = gq.y; gc[2] = gq.z;
             float4 mtl = make_float4(0.f, 0.f, 0.f, 0.f);
             if (rg == 0 && wave == 0) mtl = ((const float4 *)m.mulaw_tab)[4 * lane < m.n_cls ? lane : 0];
             __builtin_amdgcn_sched_barrier(0);
@@ -422,10 +384,10 @@ __global__ __launch_bounds__(64 * (4 + NB)) void ar_gru_kernel(ArModel m, const 
                 }
                 x = x < 0 ? 0 : (x >= m.n_cls ? m.n_cls - 1 : x);
                 const float4 eq = m.Gemb4[((size_t)x * (Hr >> 2) + rg) * 4 + u];
-                ge0 = eq.x; ge1 = eq.y; ge2 = eq.z;
+                ge[0] = eq.x; ge[1] = eq.y; ge[2] = eq.z;
                 if (!m.gc_replay) {
-                    const float *gc = c.Gcond + ((size_t)c.gbase[sl.row] + lt / m.upsample) * 3 * Hr + unit;
-                    gc0 = gc[0]; gc1 = gc[Hr]; gc2 = gc[2 * Hr];
+                    const float *pg = c.Gcond + ((size_t)c.gbase[sl.row] + lt / m.upsample) * 3 * Hr + unit;
+                    gc[0] = pg[0]; gc[1] = pg[Hr]; gc[2] = pg[2 * Hr];
                 }
                 hold = first ? 0.f : hprev;                     // a new utterance starts from h = 0
                 if (c.hall) hallp = c.hall + ((size_t)sl.row * c.CH + (lt - c.hall_t0)) * Hr + unit;
@@ -435,18 +397,18 @@ __global__ __launch_bounds__(64 * (4 + NB)) void ar_gru_kernel(ArModel m, const 
         }
         __syncthreads();
         // cell update (PyTorch GRUCell equations, gate order r, z, n), K quarters summed in fixed order
-        if (emit) {                                  // network_vocoder.py:78 output: the sample the candidates decided
-            if (wavp) *wavp = m.n_cls <= 256 ? mt[xraw] : m.mulaw_tab[xraw];
+        if (emit) {                                  // the sample the candidates decided
+            if (wavp) *wavp = m.n_cls <= 256 ? mt[xraw] : m.mulaw_tab[xraw];      // emit_sample with the table picked per store
             if (mulp) *mulp = xraw;
         }
         if (active) {
             // the slot's previous occupant left its state in the MFMA operand: W_hh . 0 = 0 on a first step
-            const float gr = first ? 0.f : ((red[g][0][u][b] + red[g][1][u][b]) + red[g][2][u][b]) + red[g][3][u][b];
-            const float gz = first ? 0.f : ((red[g][0][4 + u][b] + red[g][1][4 + u][b]) + red[g][2][4 + u][b]) + red[g][3][4 + u][b];
-            const float gn = first ? 0.f : ((red[g][0][8 + u][b] + red[g][1][8 + u][b]) + red[g][2][8 + u][b]) + red[g][3][8 + u][b];
-            const float r = gate_sigmoid((ge0 + gc0) + (gr + bh0));
-            const float z = gate_sigmoid((ge1 + gc1) + (gz + bh1));
-            const float n = gate_tanh((ge2 + gc2) + r * (gn + bh2));
+            const float gr = first ? 0.f : sum4(red[g][0][u][b], red[g][1][u][b], red[g][2][u][b], red[g][3][u][b]);
+            const float gz = first ? 0.f : sum4(red[g][0][4 + u][b], red[g][1][4 + u][b], red[g][2][4 + u][b], red[g][3][4 + u][b]);
+            const float gn = first ? 0.f : sum4(red[g][0][8 + u][b], red[g][1][8 + u][b], red[g][2][8 + u][b], red[g][3][8 + u][b]);
+            const float r = gate_sigmoid((ge[0] + gc[0]) + (gr + bh[0]));      // gru_cell, written out
+            const float z = gate_sigmoid((ge[1] + gc[1]) + (gz + bh[1]));
+            const float n = gate_tanh((ge[2] + gc[2]) + r * (gn + bh[2]));
             const float hn = (1.0f - z) * n + z * hold;
             hout[hi] = hn;
             if (hallp) *hallp = hn;
@@ -562,7 +524,7 @@ __global__ __launch_bounds__(1024) void ar_gru_big_kernel(ArModel m, const ArCal
             else {
                 x = FUSED ? xf : merge_candidates(m, sg, cd);
                 if (blk == 0 && uh == 0 && u == 0) {             // emit sample lt-1 (network_vocoder.py:78 output)
-                    if (c.wav) c.wav[(size_t)sl.row * c.Lout + lt - 1] = m.mulaw_tab[x];
+                    if (c.wav) c.wav[(size_t)sl.row * c.Lout + lt - 1] = m.mulaw_tab[x];      // emit_sample, written out
                     if (c.mulaw) c.mulaw[(size_t)sl.row * c.Lout + lt - 1] = x;
                 }
             }
@@ -592,10 +554,10 @@ __global__ __launch_bounds__(1024) void ar_gru_big_kernel(ArModel m, const ArCal
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 const int ul = 8 * uh + 4 * p + u;
-                const float gr = first ? 0.f : ((red[q][0][0][ul][b] + red[q][0][1][ul][b]) + red[q][0][2][ul][b]) + red[q][0][3][ul][b];
-                const float gz = first ? 0.f : ((red[q][1][0][ul][b] + red[q][1][1][ul][b]) + red[q][1][2][ul][b]) + red[q][1][3][ul][b];
-                const float gn = first ? 0.f : ((red[q][2][0][ul][b] + red[q][2][1][ul][b]) + red[q][2][2][ul][b]) + red[q][2][3][ul][b];
-                const float rr = gate_sigmoid((ge[p][0] + gc[p][0]) + (gr + bh[p][0]));
+                const float gr = first ? 0.f : sum4(red[q][0][0][ul][b], red[q][0][1][ul][b], red[q][0][2][ul][b], red[q][0][3][ul][b]);
+                const float gz = first ? 0.f : sum4(red[q][1][0][ul][b], red[q][1][1][ul][b], red[q][1][2][ul][b], red[q][1][3][ul][b]);
+                const float gn = first ? 0.f : sum4(red[q][2][0][ul][b], red[q][2][1][ul][b], red[q][2][2][ul][b], red[q][2][3][ul][b]);
+                const float rr = gate_sigmoid((ge[p][0] + gc[p][0]) + (gr + bh[p][0]));      // gru_cell, written out
                 const float z = gate_sigmoid((ge[p][1] + gc[p][1]) + (gz + bh[p][1]));
                 const float n = gate_tanh((ge[p][2] + gc[p][2]) + rr * (gn + bh[p][2]));
                 const float hn = (1.0f - z) * n + z * hold[p];
@@ -622,7 +584,7 @@ __global__ __launch_bounds__(1024) void ar_gru_big_kernel(ArModel m, const ArCal
             const float4 *hp = hs + (size_t)qq * t4 + (size_t)kq * SW * 64 + lane;
             f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < SW; ++s) {
+            for (int s = 0; s < SW; ++s) {                               // mfma_k4, written out
                 const float4 hv = hp[s * 64];
                 a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, hv.x, a0, 0, 0, 0);
                 a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, hv.y, a1, 0, 0, 0);
@@ -693,7 +655,7 @@ __global__ __launch_bounds__(256) void ar_next_row_kernel(ArModel m, const ArCal
         for (int q = threadIdx.x; q < nrg; q += 256) {
             if (m.fused) {
                 const unsigned tag = (unsigned)c.t_base & ((1u << CAND_TAG_BITS) - 1u);
-                m.candg[((size_t)(sg >> 4) * nrg + q) * 16 + (sg & 15)] = ((u64)((tag << 10) | (unsigned)x) << 32) | __float_as_uint(0.f);
+                m.candg[((size_t)(sg >> 4) * nrg + q) * 16 + (sg & 15)] = cand_pack(tag, (unsigned)x, 0.f);
             } else {
                 m.cand_s[(size_t)sg * nrg + q] = 0.f;
                 m.cand_k[(size_t)sg * nrg + q] = x;
@@ -732,23 +694,18 @@ __global__ void ar_finalize_kernel(ArModel m, const ArCall *__restrict__ cp) {
     if (m.fused) {
         const u64 *cg = m.candg + ((size_t)(sg >> 4) * nrg) * 16 + (sg & 15);
         u64 gq = ps_load(cg);
-        best = __uint_as_float((unsigned)gq);
-        x = (int)((gq >> 32) & 1023u);
+        best = cand_score(gq);
+        x = cand_class(gq);
         for (int q = 1; q < nrg; ++q) {
             gq = ps_load(cg + q * 16);
-            const float sc = __uint_as_float((unsigned)gq);
-            if (sc > best) { best = sc; x = (int)((gq >> 32) & 1023u); }
+            first_max(best, x, cand_score(gq), cand_class(gq));
         }
     } else {
         best = m.cand_s[(size_t)sg * nrg];
         x = m.cand_k[(size_t)sg * nrg];
-        for (int q = 1; q < nrg; ++q) {
-            const float sc = m.cand_s[(size_t)sg * nrg + q];
-            if (sc > best) { best = sc; x = m.cand_k[(size_t)sg * nrg + q]; }
-        }
+        for (int q = 1; q < nrg; ++q) first_max(best, x, m.cand_s[(size_t)sg * nrg + q], m.cand_k[(size_t)sg * nrg + q]);
     }
-    if (c.wav) c.wav[(size_t)sl.row * c.Lout + sl.len - 1] = m.mulaw_tab[x];
-    if (c.mulaw) c.mulaw[(size_t)sl.row * c.Lout + sl.len - 1] = x;
+    emit_sample(c.wav, c.mulaw, (size_t)sl.row * c.Lout + sl.len - 1, x, m.mulaw_tab);
 }
 
 // Hidden sizes the per-sample kernels are instantiated for (size_h_rnn = 64 SW): 512, 896 (the reference's, config.py:76), 1024.
