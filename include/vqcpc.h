@@ -187,6 +187,52 @@ int vqcpc_cpc_score(vqcpc_cpc *cpc, const float *z, const float *c, int T, const
                     const int64_t *seq_index, uint64_t seed, uint32_t stream_id, float *loss, float *step_loss,
                     float *accuracy, uint8_t *correct, float *scores, void *stream);
 
+/* ------------------------------------------------------------------ ABX scoring ------ */
+
+/* Own protocol (parity unpinned).  Stands in for the step the reference leaves to an outside package: README
+ * 4-B "Run ABX evaluation script" on the per-frame text files that encode.py:48-52 writes.  The reference holds no ABX code and
+ * no equality with any outside tool is claimed.
+ *
+ * Bytes of the `work` buffer of vqcpc_abx_score for n_frames frames of D components (the normalised copy of the frames). */
+int vqcpc_abx_workspace_bytes(int n_frames, int D, uint64_t *bytes);
+
+/* Own protocol; stands in for README 4-B's outside ABX script over the frames of encode.py:48-52.  Batched DTW distances between
+ * tokens (runs of frames) and the integer ABX counts, for any number of blocks: one normalisation launch, one DTW launch, one
+ * count launch on `stream`, no synchronisation, no atomics (equal inputs give equal bits).
+ *
+ * feats DEVICE (n_frames, D) fp32, 16-byte aligned.  Supported: D % 4 == 0, 4 <= D <= 512.  Each frame is normalised once (a
+ * zero-norm frame stays zero); frame distance = 2 atan2(|u - v|, |u + v|) / pi in [0, 1], the angular distance arccos(cos) / pi
+ * in a form that is exact 0 for bit-equal frames.  A zero frame is at 0.5 from every non-zero frame and at 0 from a zero frame.
+ * Components are assumed to stay inside sqrt of the fp32 range (no rescaling before the squares).
+ * tokens DEVICE (n_tokens, 2) int32 (first_row, n_frames), 1 <= n_frames <= 64 (T_MAX).
+ * DTW: C[i][j] = d[i][j] + min(C[i-1][j-1], C[i-1][j], C[i][j-1]), predecessor = the first minimum in that order,
+ * L[i][j] = L[pred] + 1, L[0][0] = 1; a pair's distance is C[Ta-1][Tb-1] / L[Ta-1][Tb-1].
+ *
+ * The block table: blocks DEVICE (n_blocks, 12) int32, one row per dense block
+ *   [0] a_off   first entry in `lists` of the block's nA A/B token ids, sorted by phone
+ *   [1] nA      [2] x_off  first entry in `lists` of its nX X token ids     [3] nX
+ *   [4] seg_off first entry in `segs` of its n_seg + 1 ascending segment offsets into the A/B list (0 ... nA), one per phone
+ *   [5] n_seg   [6] dist_base  first element of the block's (nA, nX) row-major tables in cost / path_len / dist
+ *   [7] out_base  first element of its (nX, n_seg) table in twice_wins
+ *   [8] xseg_off  first entry in `lists` of, per X token, the segment of its own phone
+ *   [9] wg_base   sum over the earlier blocks of nX * ceil(nA / 4): the block's first workgroup of the DTW launch
+ *   [10], [11]  0
+ * out_base and wg_base ascend.  lists DEVICE (n_lists) int32, segs DEVICE (n_segs) int32.  HOST scalars: n_workgroups = the sum
+ * that wg_base runs over, n_dist = sum nA * nX, n_out = sum nX * n_seg; each below 2^31 (cut larger work into several calls).
+ * work DEVICE, vqcpc_abx_workspace_bytes(n_frames, D) bytes, 16-byte aligned.
+ * Outputs DEVICE: cost (n_dist) fp32 or NULL, path_len (n_dist) int32 or NULL, dist (n_dist) fp32 = cost / path_len;
+ * twice_wins (n_out) int32: for X token x of phone segment p and segment q != p,
+ *   sum over a in segment p whose token id differs from x's, b in segment q of 2 [dist(a, x) < dist(b, x)] + [... == ...],
+ * and 0 for q == p.
+ * VQCPC_ERR_INVALID before anything is enqueued for whatever the host can see: D, the counts, NULL, alignment.  What lives in
+ * DEVICE tables (token rows and lengths, list entries, offsets) is CLAMPED into range on the device, silently, and every store
+ * is guarded by n_dist / n_out: a bad value cannot read or write out of bounds, and it is the caller that rejects it (the
+ * Python wrapper raises before the call) -- the rule of vqcpc_cpc_score. */
+int vqcpc_abx_score(const float *feats, int n_frames, int D, const int32_t *tokens, int n_tokens, const int32_t *lists,
+                    int n_lists, const int32_t *segs, int n_segs, const int32_t *blocks, int n_blocks, int n_workgroups,
+                    int64_t n_dist, int64_t n_out, void *work, float *cost, int32_t *path_len, float *dist,
+                    int32_t *twice_wins, void *stream);
+
 /* ------------------------------------------------------------------ Vocoder ---------- */
 
 /* Vocoder.state_dict(): own tables (network_vocoder.py:37-38) plus the RNN_MS core the

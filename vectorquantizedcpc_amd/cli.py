@@ -12,6 +12,13 @@
     python -m vectorquantizedcpc_amd.cli score-vocoder --dataset datasets/2019/english --in-dir wavs/
                                                  [--cpc-checkpoint .. --vocoder-checkpoint .. | --random-init] [--per-utterance]
 
+    python -m vectorquantizedcpc_amd.cli abx     --items FILE --mode within|across [--frame-shift 0.02 --frame-offset 0.01]
+                                                 --features DIR | --dataset datasets/2019/english
+                                                                  [--cpc-checkpoint ckpt.pt | --random-init] [--feature z|c]
+
+``abx`` stands in for the outside "ABX evaluation script" of the reference's README 4-B (own protocol, ``abx.py``): the ABX
+error rate of the units on an items file (``file onset offset phone prev next speaker`` per line), from the ``.txt`` frames
+``encode`` wrote (``--features``) or straight from the mels of ``test.json`` (``--dataset``, ``driver.score_abx``).
 ``score-vocoder`` is the validation number the reference's vocoder training never computes (``vocoder.py:68-94``): the
 teacher-forced cross-entropy of ``vocoder.py:62-63`` on ``<in_dir>/<utterance>.wav`` of every entry of ``test.json``, speaker id
 from ``speakers.json`` by the file name's prefix: loss in nats per sample, bits per sample and top-1 accuracy
@@ -134,6 +141,30 @@ def score_vocoder_dataset(args) -> int:
     return 0
 
 
+def abx_line(r) -> str:
+    return (f"abx {r['mode']}: error rate {r['error_rate']:.4f} % over {r['n_triples']} triples, {r['n_pairs']} pairs, "
+            f"{r['n_blocks']} blocks")
+
+
+def abx_dataset(args) -> int:
+    from . import abx
+    items = abx.read_items(args.items)
+    if args.features:
+        dev = torch.device(args.device)
+        feats = {f: torch.from_numpy(io.load_frames_text(Path(args.features) / f)).to(dev) for f in sorted({it.file for it in items})}
+        r = abx.score(feats, items, mode=args.mode, frame_shift=args.frame_shift, frame_offset=args.frame_offset)
+    else:
+        enc, _ = _models(args, need_vocoder=False)
+        mels = {p.stem: io.load_mel(p) for p in io.read_test_metadata(args.dataset)}
+        r = driver.score_abx(enc, mels, items, feature=args.feature, mode=args.mode, frame_shift=args.frame_shift,
+                             frame_offset=args.frame_offset, max_batch=args.max_batch)
+    if r["n_triples"] == 0:
+        print(f"abx {args.mode}: no (A, B, X) triple could be formed from {len(items)} items")
+        return 1
+    print(abx_line(r))
+    return 0
+
+
 def convert_files(enc, voc, entries, out_dir, seed, max_batch: int = 64, slots: int = 0, timings=None):
     """``convert.py:52-83`` over ``entries`` = [(input path without suffix, speaker id, output name)]: ``.mel.npy`` inputs
     are used as they are; ``.wav`` inputs go through the batched HIP front end (resample at load, reference loudness, log-mel:
@@ -221,7 +252,25 @@ def main(argv=None) -> int:
             p.add_argument("--synthesis-list", required=True)
             p.add_argument("--in-dir", required=True)
             p.add_argument("--seed", type=int, default=synth.SEED)
+    p = sub.add_parser("abx")
+    p.add_argument("--items", required=True, help="items file: '#' header, then file onset offset phone prev next speaker")
+    p.add_argument("--mode", choices=("within", "across"), default="within")
+    p.add_argument("--frame-shift", type=float, default=0.02, help="seconds between frames (10 ms mel hop x the encoder's stride 2)")
+    p.add_argument("--frame-offset", type=float, default=0.01, help="time of frame 0 in seconds")
+    p.add_argument("--features", help="directory of <file>.txt frames, as `encode` writes them")
+    p.add_argument("--dataset", help="datasets/<name> directory (test.json): encode its mels in-process")
+    p.add_argument("--cpc-checkpoint", "--checkpoint", dest="cpc_checkpoint")
+    p.add_argument("--random-init", action="store_true")
+    p.add_argument("--feature", choices=("z", "c"), default="z")
+    p.add_argument("--device", default="cuda")
+    p.add_argument("--max-batch", type=int, default=64)
     args = ap.parse_args(argv)
+    if args.cmd == "abx":
+        if bool(args.features) == bool(args.dataset):
+            ap.error("abx: give --features DIR or --dataset DIR")
+        if args.dataset and not args.random_init and not args.cpc_checkpoint:
+            ap.error("abx --dataset: give --cpc-checkpoint or --random-init")
+        return abx_dataset(args)
     if not args.random_init and not args.cpc_checkpoint:
         ap.error("give --cpc-checkpoint (and --vocoder-checkpoint for convert) or --random-init")
     if args.cmd == "score-vocoder" and not args.random_init and not args.vocoder_checkpoint:
