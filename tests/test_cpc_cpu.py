@@ -44,28 +44,31 @@ def case_inputs(g, name):
     return sd, z, c
 
 
-def f64_cpc(z, c, sd, utt, seq):
+def f64_cpc(z, c, sd, utt, seq, dtype=np.float64):
     """Steps 1-5 of ``CPCLoss.forward`` in float64 numpy.  -> dict: ``f`` scores (K, N, 1 + Neg, L); ``mag`` = the magnitude
-    sum of the score tolerance, (sum_d |z_d| (|W_k| |c| + |b_k|)_d + sum_d |z_d Wc_d|) / 8; ``step_loss`` (K), ``loss``."""
+    sum of the score tolerance, (sum_d |z_d| (|W_k| |c| + |b_k|)_d + sum_d |z_d Wc_d|) / 8; ``step_loss`` (K), ``loss``;
+    ``pos_loss`` = lse - f[:, :, 0] per position (K, N, L).  ``dtype=np.float32``: the same statements with every array and
+    every operation in fp32 -- the plain fp32 restatement whose distance from float64 tests/cpc_cases.py calls ``err32``."""
     K, Spk, Utt, Neg, L = seq.shape
-    z, c = np.asarray(z, np.float64), np.asarray(c, np.float64)
+    z, c = np.asarray(z, dtype), np.asarray(c, dtype)
     zs = z.reshape(Spk, Utt, -1, z.shape[-1])
-    f, mag = np.empty((K, Spk * Utt, 1 + Neg, L)), np.empty((K, Spk * Utt, 1 + Neg, L))
+    f, mag = np.empty((K, Spk * Utt, 1 + Neg, L), dtype), np.empty((K, Spk * Utt, 1 + Neg, L), dtype)
     spk = np.arange(Spk).reshape(-1, 1, 1, 1)
     for k in range(1, K + 1):
-        W = sd[f"predictors.{k - 1}.weight"].numpy().astype(np.float64)
-        b = sd[f"predictors.{k - 1}.bias"].numpy().astype(np.float64)
+        W = sd[f"predictors.{k - 1}.weight"].numpy().astype(dtype)
+        b = sd[f"predictors.{k - 1}.bias"].numpy().astype(dtype)
         wc = c[:, :L] @ W.T + b                                                       # 1.
         wc_abs = np.abs(c[:, :L]) @ np.abs(W).T + np.abs(b)
         shift = zs[:, :, k:L + k]                                                     # 2. positives z[n, t + k]
         neg = shift[spk, utt[k - 1][None, :, :, None], seq[k - 1]]                    # 3. within speaker
         rows = np.concatenate([shift[:, :, None], neg], axis=2).reshape(Spk * Utt, 1 + Neg, L, -1)
-        f[k - 1] = (rows * wc[:, None]).sum(-1) / 8.0                                 # 4.
-        mag[k - 1] = ((np.abs(rows) * wc_abs[:, None]).sum(-1) + np.abs(rows * wc[:, None]).sum(-1)) / 8.0
+        f[k - 1] = (rows * wc[:, None]).sum(-1) / dtype(8.0)                          # 4.
+        mag[k - 1] = ((np.abs(rows) * wc_abs[:, None]).sum(-1) + np.abs(rows * wc[:, None]).sum(-1)) / dtype(8.0)
     m = f.max(axis=2, keepdims=True)                                                  # 5.
     lse = m[:, :, 0] + np.log(np.exp(f - m).sum(axis=2))
-    step_loss = (lse - f[:, :, 0]).reshape(K, -1).mean(axis=1)
-    return {"f": f, "mag": mag, "step_loss": step_loss, "loss": step_loss.mean()}
+    pos_loss = lse - f[:, :, 0]
+    step_loss = pos_loss.reshape(K, -1).mean(axis=1)
+    return {"f": f, "mag": mag, "step_loss": step_loss, "loss": step_loss.mean(), "pos_loss": pos_loss}
 
 
 # ------------------------------------------------------------------ module surface

@@ -13,7 +13,12 @@ shape's ``seq_index`` is 418 KB of incompressible values below 64, more than any
 are stored one step per file (``cpc_train_draws_k<k>.npz``, ~53 KB each) and shared by ``train_shape`` and ``train_e2e``
 (recorded once, replayed for the second): every step stays checked position by position.
 
+``cpc_f64_pins.npz``: the float64 step losses and accuracies of the reference's ``CPCLoss(...).double()`` at the five protocol
+cases of tests/cpc_cases.py, with the protocol's own draws replayed (raw sequence draw r = (seq - t) mod L); it pins
+``test_cpc_cpu.f64_cpc`` to the reference at those shapes (tests/test_cpc_f64_cpu.py).
+
 Usage:  python tools/gen_cpc_golden.py            (writes tests/golden/cpc_*.npz)
+        python tools/gen_cpc_golden.py --pins     (writes tests/golden/cpc_f64_pins.npz only)
 """
 import os
 import sys
@@ -170,11 +175,39 @@ def fixture(model, name, z, c, conf, sd, draws=None, full=True, extra=None):
     return raw, utt, seq
 
 
+def pins(model):
+    """K float64 step losses and K accuracies per protocol case of tests/cpc_cases.py, from the reference on the protocol's draws."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cpc_cases
+    out = {}
+    for name in cpc_cases.PROTOCOL_CASES:
+        g = cpc_cases.case(name)
+        z, c = cpc_cases.inputs(g)
+        utt, seq = cpc_cases.negatives(g)
+        raw = []
+        for k in range(g["K"]):
+            r = torch.remainder(seq[k] - torch.arange(g["L"]), g["L"])
+            assert int(r.min()) >= 1 and int(r.max()) < g["L"]                    # what randint(1, length) can return
+            raw += [utt[k].clone(), r]
+        conf = (g["n_pred"], g["Spk"], g["Utt"], g["Neg"], 64, g["c_dim"])
+        _, tap, _, acc = run_reference(model, conf, cpc_cases.state_dict(g), z, c, replay=raw, double=True)
+        assert not tap.replay and len(tap.losses) == g["K"]
+        out[f"{name}_step_loss64"] = np.array([l.item() for l in tap.losses], np.float64)
+        out[f"{name}_accuracy"] = np.array(acc, np.float64)
+        print(f"{name}: step_loss64 = {np.round(out[f'{name}_step_loss64'], 6).tolist()} accuracy = {np.round(acc, 4).tolist()}")
+    path = os.path.join(GOLD, "cpc_f64_pins.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < MAX_BYTES
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(1)
     model = import_reference()
     print("reference imported from", model.__file__, "| torch", torch.__version__)
+    if "--pins" in sys.argv[1:]:
+        return pins(model)
     train_raw = None
     for i, (name, (Spk, Utt, Neg, T, n_pred, c_dim, n_codes, runs)) in enumerate(CASES.items()):
         torch.manual_seed(1000 + i)
@@ -200,6 +233,7 @@ def main():
             full=False, extra={"mel": np.array("cpc_e2e"), "source": np.array(
                 "reference Encoder.forward on synth.mel('cpc_e2e', 64, 140) (ln_affine random, data codebook) -> reference "
                 "CPCLoss.forward with the train shape's recorded draws")})
+    pins(model)
     print("wrote", sorted(f for f in os.listdir(GOLD) if f.startswith("cpc_")))
 
 
