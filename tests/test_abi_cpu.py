@@ -125,3 +125,9 @@ def test_weight_slots_follow_the_module_without_state_dict():
     vs = _lib.WeightSlots(voc, list(voc.state_dict().keys()))
     assert [t.shape for t in vs.tensors()] == [t.shape for t in voc.state_dict().values()]
     assert "_slots" not in copy.deepcopy(enc).__dict__ and copy.deepcopy(enc).codebook._owner() is not enc
+    assert voc._WEIGHT_NAMES == list(voc.state_dict().keys())
+    # one lifecycle: the three classes take it from _lib.NativeModule and define none of it themselves
+    for cls in (V.Encoder, V.CPCLoss, V.Vocoder):
+        assert issubclass(cls, _lib.NativeModule) and issubclass(_lib.NativeModule, torch.nn.Module)
+        for name in ("_native", "refresh", "__getstate__", "__del__"):
+            assert name not in vars(cls) and getattr(cls, name) is getattr(_lib.NativeModule, name), (cls.__name__, name)

@@ -189,7 +189,7 @@ def test_handoff_timeout_is_reported_by_the_same_call_and_the_rerun_is_right():
     voc3.set_option("xcd_timeout_ms", 20)
     voc3.set_option("xcd_debug_drop_step", 100)
     with pytest.warns(UserWarning, match="decode repeated"):
-        wav3 = driver.generate_checked(voc3, z, spk, seed=9, utt_base=0)
+        wav3 = voc3.generate(z, spk, seed=9, utt_base=0)
     assert torch.equal(wav3.cpu(), want[0])
 
 

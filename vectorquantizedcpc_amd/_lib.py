@@ -3,8 +3,14 @@
 There is no CPU fallback: if the shared library is missing this module raises, and every
 compute entry point fails on a machine without a gfx950 device.
 """
+import contextlib
 import ctypes as C
 import os
+import warnings
+
+import numpy as np
+import torch
+import torch.nn as nn
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvqcpc_hip.so")
@@ -142,7 +148,6 @@ def check(rc: int):
 
 
 def current_stream() -> int:
-    import torch
     return torch.cuda.current_stream().cuda_stream
 
 
@@ -186,8 +191,6 @@ class WeightSlots:
 
 def device_guard(dev):
     """``torch.cuda.device(dev)`` only when ``dev`` is not already current (the context manager costs ~5 us)."""
-    import contextlib
-    import torch
     return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
@@ -202,3 +205,152 @@ def require_cuda(t, what: str):
     if not t.is_cuda:
         raise RuntimeError(f"{what} is on {t.device}: vectorquantizedcpc_amd runs on MI355X only "
                            "(move the module and its inputs with .to('cuda')); there is no CPU fallback")
+
+
+def int_array(values, n: int, what: str, ctype=C.c_int):
+    """Per-utterance host integers (list or Tensor; ``None`` stays ``None``) -> ``ctype[n]`` for the C ABI.  A list of the wrong
+    length raises: ctypes would zero-fill a short one without a word, so those utterances would run as empty."""
+    if values is None:
+        return None
+    v = values.tolist() if isinstance(values, torch.Tensor) else values
+    if len(v) != n:
+        raise RuntimeError(f"{what} must have one entry per utterance ({n}), got {len(v)}")
+    return (ctype * n)(*map(int, v))
+
+
+def wave_batch(wave, lengths, what: str = "wave"):
+    """A waveform argument of the front ends -> ``(single, w, lens, c_int[B])``: ``w`` (B, Lmax) fp32, contiguous, on its HIP
+    device -- a numpy waveform is moved to the current one, (L,) becomes (1, L) and ``single`` says so -- and ``lens`` the
+    valid samples per row (default Lmax), as a list and as the array the C calls take."""
+    if isinstance(wave, np.ndarray):
+        wave = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).cuda()
+    require_cuda(wave, what)
+    single = wave.dim() == 1
+    w = wave[None] if single else wave
+    if w.dim() != 2:
+        raise ValueError("mono audio only: (L,) or (B, Lmax) with lengths")
+    B, Lmax = w.shape
+    lens = [Lmax] * B if lengths is None else [int(v) for v in lengths]
+    if len(lens) != B:
+        raise ValueError("lengths must have one entry per row")
+    return single, w.detach().to(torch.float32).contiguous(), lens, int_array(lens, B, "lengths")
+
+
+def cached_handle(cache: dict, device, create: str, *args):
+    """The process-wide handle of a front end (mel, loudness, resampler): ``cache[args + (device.index,)]``, made on first use
+    by the library's ``create(*args, &handle)`` on ``device``.  Such handles hold only tables and live as long as the process."""
+    key = args + (device.index,)
+    h = cache.get(key)
+    if h is None:
+        h = C.c_void_p()
+        with device_guard(device):
+            check(getattr(load(), create)(*args, C.byref(h)))
+        cache[key] = h
+    return h
+
+
+def run_checked(run, check, message: str):
+    """The repeat-once policy of every call whose result the host takes right away: ``out = run()``, then ``check()`` (one
+    stream synchronisation and the handle's status word).  A ``RuntimeError`` there means an in-kernel exchange gave up (a shared
+    GPU) and the handle has fallen back to its launch-per-step path: warn with ``message`` (``{}`` = the error), run ONCE more
+    and check again.  Anything else ``check()`` raises (``IndexError`` for a bad index) passes straight through."""
+    out = run()
+    try:
+        check()
+    except RuntimeError as e:
+        warnings.warn(message.format(e))
+        out = run()
+        check()
+    return out
+
+
+class NativeModule(nn.Module):
+    """An ``nn.Module`` whose arithmetic runs behind one native handle of ``libvqcpc_hip.so``: the lifecycle of that handle.
+    The handle holds re-laid COPIES of the weights; it is built at the first call that needs it (``_native()``), keyed on
+    ``WeightSlots.key`` of the weights, rebuilt when that key moves (``load_state_dict``, ``.to``, optimizer steps) -- with the
+    options set so far applied again -- and never copied or pickled with the module.
+
+    A subclass states what differs: ``_NAME`` for the messages, ``_WEIGHT_NAMES`` (``state_dict()`` names; or
+    ``_weight_names()`` where they depend on the instance), the library symbols ``_CREATE``, ``_DESTROY`` and, if it has options,
+    ``_SET_OPTION``, and ``_weights(p)``: its ctypes weights struct, filled, with ``p(name)`` = the device pointer of weight
+    ``name``."""
+    _NAME = _CREATE = _DESTROY = _SET_OPTION = None
+    _WEIGHT_NAMES = ()
+
+    def __init__(self):
+        super().__init__()
+        self._handle = None
+        self._handle_key = None
+
+    def _weight_names(self):
+        return self._WEIGHT_NAMES
+
+    def _weights(self, p):
+        raise NotImplementedError
+
+    def _native(self):
+        slots = self.__dict__.get("_slots")
+        if slots is None:                       # resolved once: state_dict() costs more than a short call's launch
+            slots = self.__dict__["_slots"] = WeightSlots(self, self._weight_names())
+        ws = slots.tensors()
+        key = WeightSlots.key(ws)
+        if self._handle is not None and key == self._handle_key:
+            return self._handle
+        for t in ws:
+            require_cuda(t, f"{self._NAME} parameter")
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"{self._NAME}: parameters must be float32")
+            require_same_device(t, ws[0], "a parameter")
+        self._release()
+        sd = dict(zip(slots.names, ws))
+        keep = []                               # contiguous copies stay alive until create has re-laid them
+
+        def p(name):
+            t = sd[name].detach().contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        w = self._weights(p)
+        lib = load()
+        h = C.c_void_p()
+        with device_guard(ws[0].device):
+            torch.cuda.current_stream().synchronize()
+            check(getattr(lib, self._CREATE)(C.byref(w), C.byref(h)))
+        self._handle, self._handle_key = h, key
+        for name, value in self.__dict__.get("_options", {}).items():     # options survive a rebuild of the handle
+            check(getattr(lib, self._SET_OPTION)(h, name.encode(), value))
+        return h
+
+    def _release(self):
+        if getattr(self, "_handle", None) is not None:
+            getattr(load(), self._DESTROY)(self._handle)
+            self._handle = None
+
+    def __getstate__(self):                             # the native handle is per object: a copy builds its own
+        d = self.__dict__.copy()
+        d["_handle"], d["_handle_key"] = None, None
+        d.pop("_slots", None)
+        return d
+
+    def set_option(self, name: str, value: int):
+        """The subclass's ``vqcpc_*_set_option``.  ``Encoder``: ``fused`` (-1 auto, 0 layered kernels, 1 fused front end);
+        ``Vocoder``: the decode-loop options (``use_graph``, ``steps_per_graph``, ``xcd``, ...).  Options are kept on the
+        Python object and re-applied when the native handle is rebuilt (``.to()``, ``load_state_dict``)."""
+        if self._SET_OPTION is None:
+            raise AttributeError(f"{self._NAME} has no options")
+        check(getattr(load(), self._SET_OPTION)(self._native(), name.encode(), int(value)))
+        self.__dict__.setdefault("_options", {})[name] = int(value)
+
+    def refresh(self):
+        """Drop the native handle so that the next call re-reads the parameters.  The handle holds re-laid
+        COPIES of the weights and is rebuilt automatically when a parameter's storage or ``_version`` changes
+        (``load_state_dict``, ``.to``, optimizer steps); a write through ``.data`` bumps neither -- call this
+        after one."""
+        self._release()
+        self._handle_key = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass

@@ -39,7 +39,7 @@ from pathlib import Path
 
 import torch
 
-from . import ConfCPC, ConfEncoder, ConfVocoder, CPCLoss, Encoder, Vocoder, driver, io, loudness, synth
+from . import ConfCPC, ConfEncoder, ConfVocoder, CPCLoss, Encoder, Vocoder, _lib, driver, io, loudness, synth
 
 
 def _models(args, need_vocoder):
@@ -68,13 +68,11 @@ def encode_dataset(args) -> int:
     if args.save_auxiliary:
         # the hook delivers one batch at a time: keep the reference's one-utterance-per-call order
         for p, mel in zip(paths, mels):
-            z, c, _ = enc.encode(mel[None].to(args.device))
-            try:
-                enc.check()                                    # nothing incomplete may be written
-            except RuntimeError:
-                aux.clear()
-                z, c, _ = enc.encode(mel[None].to(args.device))
-                enc.check()
+            def run():
+                aux.clear()                                    # a repeat leaves one captured batch, as a single call does
+                return enc.encode(mel[None].to(args.device))
+
+            z, c, _ = _lib.run_checked(run, enc.check, "encode repeated on the fallback path: {}")   # nothing incomplete is written
             io.save_frames_text(out_dir / p.stem, z[0])
             for name, t in (("auxiliary_embedding1", c[0]), ("auxiliary_embedding2", aux.pop()[0])):
                 d = out_dir.parent / name

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import synth
+from . import _lib, synth
 from .model import CPCLoss, Encoder
 from .network_vocoder import Vocoder
 
@@ -51,19 +51,14 @@ def make_buckets(lengths: Sequence[int], modes: Sequence[int], max_batch: int, m
     return buckets
 
 
-def generate_checked(vocoder: Vocoder, idx, spk, **kw):
-    """``Vocoder.generate`` with its default check: one stream synchronisation, the handle's status word read, and the call
-    repeated ONCE if an in-kernel hand-off of the resident decoders gave up (``convert.py:75-83`` writes the waveform right
-    after ``generate``; nothing incomplete may reach it).  Kept as a name for the callers that must not pass ``async_``."""
-    kw.pop("async_", None)
-    return vocoder.generate(idx, spk, **kw)
-
-
-def _pad_stack(mels: Sequence[torch.Tensor], ids: Sequence[int], device) -> torch.Tensor:
-    T = max(int(mels[i].shape[-1]) for i in ids)
-    out = torch.zeros(len(ids), mels[ids[0]].shape[0], T, device=device)
-    for k, i in enumerate(ids):
-        out[k, :, : mels[i].shape[-1]] = mels[i].to(device)
+def _pad_batch(rows, device, dtype=torch.float32, min_len: int = 0, non_blocking: bool = False) -> torch.Tensor:
+    """Rows (tensors or arrays, anywhere) that differ in their last dimension only -> one zero-initialised batch
+    (len(rows), ..., longest) of ``dtype`` on ``device``, every row at the front of its slot (one copy per row)."""
+    rows = [torch.as_tensor(r, dtype=dtype) for r in rows]
+    longest = max(min_len, max(int(r.shape[-1]) for r in rows))
+    out = torch.zeros(len(rows), *rows[0].shape[:-1], longest, dtype=dtype, device=device)
+    for k, r in enumerate(rows):
+        out[k, ..., : r.shape[-1]].copy_(r, non_blocking=non_blocking)
     return out
 
 
@@ -78,16 +73,12 @@ def encode_utterances(encoder: Encoder, mels: Sequence[torch.Tensor], want_conte
     modes = [batch1_conv_mode(C, t) for t in lengths]
     out: List[Optional[dict]] = [None] * len(mels)
     for ids in make_buckets(lengths, modes, max_batch, max_pad_frac):
-        batch = _pad_stack(mels, ids, dev)
-        z, c, idx, _ = encoder._encode_native(batch, want_c=want_context, conv_mode=modes[ids[0]])
+        batch = _pad_batch([mels[i] for i in ids], dev)
+        run = lambda: encoder._encode_native(batch, want_c=want_context, conv_mode=modes[ids[0]])
         if want_context:                         # the resident context scan of a one-utterance call may have given up
-            try:
-                encoder.check()
-            except RuntimeError as e:
-                import warnings
-                warnings.warn(f"encode repeated on the fallback path: {e}")
-                z, c, idx, _ = encoder._encode_native(batch, want_c=True, conv_mode=modes[ids[0]])
-                encoder.check()
+            z, c, idx, _ = _lib.run_checked(run, encoder.check, "encode repeated on the fallback path: {}")
+        else:
+            z, c, idx, _ = run()
         for k, i in enumerate(ids):
             n = out_frames(lengths[i])
             out[i] = {"z": z[k, :n], "indices": idx[k, :n], "c": c[k, :n] if want_context else None}
@@ -116,7 +107,7 @@ def convert_utterances(encoder: Encoder, vocoder: Vocoder, mels: Sequence[torch.
     out: List[Optional[torch.Tensor]] = [None] * len(mels)
     codes: List[Optional[torch.Tensor]] = [None] * len(mels)
     for ids in make_buckets(lengths, modes, max_batch, max_pad_frac):
-        batch = _pad_stack(mels, ids, dev)
+        batch = _pad_batch([mels[i] for i in ids], dev)
         idx = encoder._encode_native(batch, want_c=False, conv_mode=modes[ids[0]])[2]
         if clock: clock("encode")
         if slots > 0:
@@ -125,7 +116,7 @@ def convert_utterances(encoder: Encoder, vocoder: Vocoder, mels: Sequence[torch.
             continue
         n_codes = [n_codes_all[i] for i in ids]
         spk = torch.tensor([int(speakers[i]) for i in ids], device=dev)
-        wav = generate_checked(vocoder, idx, spk, n_codes=n_codes, seed=seed, utt_ids=[utt_ids[i] for i in ids])
+        wav = vocoder.generate(idx, spk, n_codes=n_codes, seed=seed, utt_ids=[utt_ids[i] for i in ids])
         if clock: clock("decode")
         for k, i in enumerate(ids):
             out[i] = wav[k, : 2 * up * n_codes[k]]
@@ -133,11 +124,9 @@ def convert_utterances(encoder: Encoder, vocoder: Vocoder, mels: Sequence[torch.
         vocoder.set_option("slots", slots)
         try:
             for ids in decode_chunks(n_codes_all, mem_budget_bytes, up):
-                idx = torch.zeros(len(ids), max(n_codes_all[i] for i in ids), dtype=torch.int64, device=dev)
-                for k, i in enumerate(ids):
-                    idx[k, : codes[i].numel()] = codes[i]
+                idx = _pad_batch([codes[i] for i in ids], dev, torch.int64)
                 spk = torch.tensor([int(speakers[i]) for i in ids], device=dev)
-                wav = generate_checked(vocoder, idx, spk, n_codes=[n_codes_all[i] for i in ids], seed=seed, utt_ids=[utt_ids[i] for i in ids])
+                wav = vocoder.generate(idx, spk, n_codes=[n_codes_all[i] for i in ids], seed=seed, utt_ids=[utt_ids[i] for i in ids])
                 for k, i in enumerate(ids):
                     out[i] = wav[k, : 2 * up * n_codes_all[i]].clone() if len(ids) < len(mels) else wav[k, : 2 * up * n_codes_all[i]]
         finally:
@@ -188,10 +177,7 @@ def front_end_utterances(waves, rates, device, sr: int = 16000, max_batch: int =
     hop = (conf or preprocess.ConfPreprocessing()).hop_length
     for ids in make_buckets(lens_in, [int(r) for r in rates], max_batch, max_pad_frac):
         rate = int(rates[ids[0]])
-        L = max(lens_in[i] for i in ids)
-        batch = torch.zeros(len(ids), L, device=device)               # each utterance straight into its padded row (one copy)
-        for k, i in enumerate(ids):
-            batch[k, : lens_in[i]].copy_(torch.as_tensor(waves[i], dtype=torch.float32), non_blocking=True)
+        batch = _pad_batch([waves[i] for i in ids], device, non_blocking=True)    # each utterance straight into its padded row
         lens = [lens_in[i] for i in ids]
         if clock: clock("upload")
         if rate != sr:
@@ -319,10 +305,7 @@ def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, spea
         lens = [int(len(mels[i])) for i in wave_ids]
         hop = (conf or preprocess.ConfPreprocessing()).hop_length
         for ids in make_buckets(lens, [0] * len(lens), max_batch, max_pad_frac):
-            L = max(lens[k] for k in ids)
-            batch = torch.zeros(len(ids), L, device=dev)
-            for r, k in enumerate(ids):
-                batch[r, : lens[k]] = torch.as_tensor(mels[wave_ids[k]], dtype=torch.float32)
+            batch = _pad_batch([mels[wave_ids[k]] for k in ids], dev)
             mel = preprocess.wave_to_mel(batch, conf, lengths=[lens[k] for k in ids])
             for r, k in enumerate(ids):
                 mels[wave_ids[k]] = mel[r, :, : 1 + lens[k] // hop]
@@ -332,12 +315,8 @@ def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, spea
     keep = [scored_samples(a.numel(), nc, up) for a, nc in zip(audio, n_codes)]
     records: List[Optional[dict]] = [None] * n
     for ids in make_buckets(keep, [0] * n, max_batch, max_pad_frac):
-        Tc, L = max(max(n_codes[i] for i in ids), 1), max(max(keep[i] for i in ids), 1)
-        z = torch.zeros(len(ids), Tc, dtype=torch.int64, device=dev)
-        a = torch.zeros(len(ids), L, dtype=torch.int64)
-        for r, i in enumerate(ids):
-            z[r, : n_codes[i]] = codes[i]["indices"]
-            a[r, : keep[i]] = audio[i][: keep[i]]
+        z = _pad_batch([codes[i]["indices"] for i in ids], dev, torch.int64, min_len=1)
+        a = _pad_batch([audio[i][: keep[i]] for i in ids], "cpu", torch.int64, min_len=1)       # one upload for the batch
         spk = torch.tensor([int(speakers[i]) for i in ids], device=dev)
         res = vocoder.nll(a.to(dev), z, spk, lengths=[keep[i] for i in ids], n_codes=[n_codes[i] for i in ids])
         sums, cnt, ok = res.nll_sum.tolist(), res.n_scored.tolist(), res.n_correct.tolist()

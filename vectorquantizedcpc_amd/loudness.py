@@ -11,9 +11,6 @@ Both also take a padded batch (``lengths=``) and then stay on the device (fp64 t
 ``vqcpc_loudness_*``; pyloudnorm is not available offline, so parity is against ``oracle/loudness_ref.py``
 (BS.1770-4 as pyloudnorm 0.1 states it) -- parity unpinned.
 """
-import ctypes as C
-
-import numpy as np
 import torch
 
 from . import _lib
@@ -22,27 +19,7 @@ _handles = {}
 
 
 def _handle(rate: int, device):
-    key = (int(rate), device.index)
-    if key not in _handles:
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(_lib.load().vqcpc_loudness_create(int(rate), C.byref(h)))
-        _handles[key] = h
-    return _handles[key]
-
-
-def _as_batch(data, lengths):
-    if isinstance(data, np.ndarray):
-        data = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)).cuda()
-    _lib.require_cuda(data, "data")
-    single = data.dim() == 1
-    w = data[None] if single else data
-    if w.dim() != 2:
-        raise ValueError("mono audio only: (L,) or (B, Lmax) with lengths")
-    lens = [w.shape[1]] * w.shape[0] if lengths is None else [int(v) for v in lengths]
-    if len(lens) != w.shape[0]:
-        raise ValueError("lengths must have one entry per row")
-    return single, w, lens
+    return _lib.cached_handle(_handles, device, "vqcpc_loudness_create", int(rate))
 
 
 class Meter:
@@ -57,8 +34,7 @@ class Meter:
 
         Raises ``ValueError`` for audio shorter than one 400 ms block, as pyloudnorm's ``valid_audio`` does.
         """
-        single, w, lens = _as_batch(data, lengths)
-        w = w.detach().to(torch.float32).contiguous()
+        single, w, lens, arr = _lib.wave_batch(data, lengths, "data")
         B, Lmax = w.shape
         lib = _lib.load()
         h = _handle(self.rate, w.device)
@@ -67,8 +43,8 @@ class Meter:
             raise ValueError("Audio must have length greater than the block size.")
         lufs = torch.empty(B, dtype=torch.float64, device=w.device)
         z = torch.empty(sum(nblk), dtype=torch.float64, device=w.device) if return_blocks else None
-        with torch.cuda.device(w.device):
-            _lib.check(lib.vqcpc_loudness_integrated(h, w.data_ptr(), (C.c_int * B)(*lens), B, Lmax, lufs.data_ptr(),
+        with _lib.device_guard(w.device):
+            _lib.check(lib.vqcpc_loudness_integrated(h, w.data_ptr(), arr, B, Lmax, lufs.data_ptr(),
                                                      z.data_ptr() if return_blocks else None, _lib.current_stream()))
         out = float(lufs.item()) if single else lufs
         return (out, list(torch.split(z, nblk))) if return_blocks else out
@@ -80,15 +56,15 @@ def loudness(data, input_loudness, target_loudness, lengths=None, rate: int = 16
 
     Loudness values are floats or (B,) tensors; the result is a new tensor on the device of ``data``.
     """
-    single, w, lens = _as_batch(data, lengths)
-    out = w.detach().to(torch.float32).clone().contiguous()
+    single, w, _, arr = _lib.wave_batch(data, lengths, "data")
+    out = w.clone()                                      # scaled in place: never the caller's tensor
     B, Lmax = out.shape
     meas = torch.as_tensor(input_loudness, dtype=torch.float64).to(out.device).reshape(-1).contiguous()
     targ = torch.as_tensor(target_loudness, dtype=torch.float64).to(out.device).reshape(-1).contiguous()
     if meas.numel() != B or targ.numel() != B:
         raise ValueError("one input and one target loudness per row")
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.load().vqcpc_loudness_normalize(_handle(rate, out.device), out.data_ptr(), (C.c_int * B)(*lens), B, Lmax,
+    with _lib.device_guard(out.device):
+        _lib.check(_lib.load().vqcpc_loudness_normalize(_handle(rate, out.device), out.data_ptr(), arr, B, Lmax,
                                                         meas.data_ptr(), targ.data_ptr(), _lib.current_stream()))
     return out[0] if single else out
 

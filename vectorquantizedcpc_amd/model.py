@@ -7,7 +7,6 @@ Same constructor (``Encoder(conf: ConfEncoder)``, ``model.py:17-34``), same
 ``encoder.encoder[-1]`` forward hook of ``encode.py:34-40`` keep working); all arithmetic
 runs in ``libvqcpc_hip.so`` through the C ABI of ``include/vqcpc.h``.
 """
-import ctypes as C
 import weakref
 from dataclasses import dataclass
 from itertools import chain
@@ -68,7 +67,7 @@ class VQEmbeddingEMA(nn.Module):
         q = torch.empty_like(xf)
         idx = torch.empty(xf.size(0), dtype=torch.int64, device=x.device)
         h = owner._native()
-        with torch.cuda.device(x.device):
+        with _lib.device_guard(x.device):
             _lib.check(_lib.load().vqcpc_encoder_vq_encode(h, xf.data_ptr(), xf.size(0), q.data_ptr(), idx.data_ptr(),
                                                            _lib.current_stream()))
         return owner, h, xf, q, idx
@@ -88,14 +87,14 @@ class VQEmbeddingEMA(nn.Module):
             _, h, xf, q, idx = self._rows(x)
             z_st = torch.empty_like(xf)
             stats = torch.empty(2, device=x.device)
-            with torch.cuda.device(x.device):
+            with _lib.device_guard(x.device):
                 _lib.check(_lib.load().vqcpc_encoder_forward_stats(h, xf.data_ptr(), q.data_ptr(), idx.data_ptr(), xf.size(0),
                                                                    z_st.data_ptr(), stats[0:].data_ptr(), stats[1:].data_ptr(),
                                                                    _lib.current_stream()))
         return z_st.view_as(x), stats[0], stats[1]
 
 
-class Encoder(nn.Module):
+class Encoder(_lib.NativeModule):
     """Spec-Conv1d/k4s2-LN-ReLU-[FC-LN-ReLU]x4-FC-VQ + LSTM (``model.py:33-86``) on MI355X."""
 
     def __init__(self, conf: ConfEncoder):
@@ -109,36 +108,14 @@ class Encoder(nn.Module):
         self.codebook = VQEmbeddingEMA(conf.n_embeddings, conf.z_dim)
         self.codebook._owner = weakref.ref(self)
         self.rnn = nn.LSTM(conf.z_dim, conf.c_dim, batch_first=True)
-        self._handle = None
-        self._handle_key = None
 
-    # ------------------------------------------------------------------ native handle
+    # ------------------------------------------------------------------ native handle (lifecycle: _lib.NativeModule)
+    _NAME, _CREATE, _DESTROY, _SET_OPTION = "Encoder", "vqcpc_encoder_create", "vqcpc_encoder_destroy", "vqcpc_encoder_set_option"
     _WEIGHT_NAMES = (["conv.weight"] + [f"encoder.{n}.{k}" for n in (0, 3, 6, 9, 12) for k in ("weight", "bias")] +
                      [f"encoder.{n}.weight" for n in (2, 5, 8, 11)] + ["encoder.14.weight", "encoder.14.bias",
                       "codebook.embedding", "rnn.weight_ih_l0", "rnn.weight_hh_l0", "rnn.bias_ih_l0", "rnn.bias_hh_l0"])
 
-    def _native(self):
-        slots = self.__dict__.get("_slots")
-        if slots is None:
-            slots = self.__dict__["_slots"] = _lib.WeightSlots(self, self._WEIGHT_NAMES)
-        ws = slots.tensors()
-        key = _lib.WeightSlots.key(ws)
-        if self._handle is not None and key == self._handle_key:
-            return self._handle
-        for w in ws:
-            _lib.require_cuda(w, "Encoder parameter")
-            if w.dtype != torch.float32:
-                raise RuntimeError("Encoder: parameters must be float32")
-            _lib.require_same_device(w, ws[0], "a parameter")
-        self._release()
-        sd = dict(zip(slots.names, ws))
-        keep = []
-
-        def p(name):
-            t = sd[name].detach().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
+    def _weights(self, p):
         w = _lib.EncoderWeights()
         w.conv_weight = p("conv.weight")
         for i, n in enumerate((0, 3, 6, 9, 12)):
@@ -152,35 +129,11 @@ class Encoder(nn.Module):
         c = self.conf
         w.in_channels, w.channels, w.n_embeddings, w.z_dim, w.c_dim = (
             c.in_channels, c.channels, c.n_embeddings, c.z_dim, c.c_dim)
-        h = C.c_void_p()
-        with torch.cuda.device(ws[0].device):
-            torch.cuda.current_stream().synchronize()
-            _lib.check(_lib.load().vqcpc_encoder_create(C.byref(w), C.byref(h)))
-        self._handle, self._handle_key = h, key
-        for name, value in self.__dict__.get("_options", {}).items():     # options survive a rebuild of the handle
-            _lib.check(_lib.load().vqcpc_encoder_set_option(h, name.encode(), value))
-        return h
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            _lib.load().vqcpc_encoder_destroy(self._handle)
-            self._handle = None
-
-    def __getstate__(self):                             # the native handle is per object: a copy builds its own
-        d = self.__dict__.copy()
-        d["_handle"], d["_handle_key"] = None, None
-        d.pop("_slots", None)
-        return d
+        return w
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self.codebook._owner = weakref.ref(self)
-
-    def set_option(self, name: str, value: int):
-        """``vqcpc_encoder_set_option`` (``fused``: -1 auto, 0 layered kernels, 1 fused front end).  Options are kept on
-        the Python object and re-applied when the native handle is rebuilt (``.to()``, ``load_state_dict``)."""
-        _lib.check(_lib.load().vqcpc_encoder_set_option(self._native(), name.encode(), int(value)))
-        self.__dict__.setdefault("_options", {})[name] = int(value)
 
     def last_schedule(self) -> int:
         """Schedule the front end of the last ``encode`` / ``stage`` call ran (``vqcpc_encoder_last_schedule``): 2 the six
@@ -195,20 +148,6 @@ class Encoder(nn.Module):
             return
         torch.cuda.current_stream().synchronize()
         _lib.check(_lib.load().vqcpc_encoder_check(self._handle))
-
-    def refresh(self):
-        """Drop the native handle so that the next call re-reads the parameters.  The handle holds re-laid
-        COPIES of the weights and is rebuilt automatically when a parameter's storage or ``_version`` changes
-        (``load_state_dict``, ``.to``, optimizer steps); a write through ``.data`` bumps neither -- call this
-        after one."""
-        self._release()
-        self._handle_key = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ reference surface
     def _encode_native(self, mel: Tensor, want_c: bool, conv_mode: int = 0, want_pre: bool = False):
@@ -258,7 +197,7 @@ class Encoder(nn.Module):
         B, _, T = mel.shape
         F = self.conf.z_dim if stage == 10 else self.conf.channels
         out = torch.empty(B, (T - 2) // 2 + 1, F, device=mel.device)
-        with torch.cuda.device(mel.device):
+        with _lib.device_guard(mel.device):
             _lib.check(_lib.load().vqcpc_encoder_stage(self._native(), mel.data_ptr(), B, T, conv_mode, stage,
                                                        out.data_ptr(), _lib.current_stream()))
         return out
@@ -275,7 +214,7 @@ class Encoder(nn.Module):
             stats = torch.empty(2, device=zq.device)
             c = torch.empty(B, Tz, self.conf.c_dim, device=zq.device)
             lib, h, s = _lib.load(), self._native(), _lib.current_stream()
-            with torch.cuda.device(zq.device):
+            with _lib.device_guard(zq.device):
                 _lib.check(lib.vqcpc_encoder_forward_stats(h, z_pre.data_ptr(), zq.data_ptr(), idx.data_ptr(), B * Tz,
                                                            z_st.data_ptr(), stats[0:].data_ptr(), stats[1:].data_ptr(), s))
                 _lib.check(lib.vqcpc_encoder_context(h, z_st.data_ptr(), B, Tz, c.data_ptr(), s))
@@ -293,7 +232,7 @@ class ConfCPC:
     c_dim: int = MISSING
 
 
-class CPCLoss(nn.Module):
+class CPCLoss(_lib.NativeModule):
     """``CPCLoss`` (``model.py:167-316``) as checkpoint SCORING on MI355X: the forward value of the objective -- InfoNCE
     loss and per-step prediction accuracies -- in one fused HIP launch per batch.  No gradient flows: results are detached
     and nothing here trains.
@@ -314,64 +253,25 @@ class CPCLoss(nn.Module):
         self.z_dim = conf.z_dim
         self.c_dim = conf.c_dim
         self.predictors = nn.ModuleList([nn.Linear(conf.c_dim, conf.z_dim) for _ in range(conf.n_prediction_steps)])
-        self._handle = None
-        self._handle_key = None
 
-    # ------------------------------------------------------------------ native handle
-    def _native(self):
-        slots = self.__dict__.get("_slots")
-        if slots is None:
-            names = [f"predictors.{i}.{p}" for i in range(self.n_prediction_steps) for p in ("weight", "bias")]
-            slots = self.__dict__["_slots"] = _lib.WeightSlots(self, names)
-        ws = slots.tensors()
-        if not ws:
+    # ------------------------------------------------------------------ native handle (lifecycle: _lib.NativeModule;
+    # refresh() is needed only after a write through ``.data``, the handle holds COPIES of the predictors)
+    _NAME, _CREATE, _DESTROY = "CPCLoss", "vqcpc_cpc_create", "vqcpc_cpc_destroy"
+
+    def _weight_names(self):
+        if self.n_prediction_steps < 1:
             raise RuntimeError("CPCLoss: n_prediction_steps // 2 must be at least 1")
-        key = _lib.WeightSlots.key(ws)
-        if self._handle is not None and key == self._handle_key:
-            return self._handle
-        for t in ws:
-            _lib.require_cuda(t, "CPCLoss parameter")
-            if t.dtype != torch.float32:
-                raise RuntimeError("CPCLoss: parameters must be float32")
-            _lib.require_same_device(t, ws[0], "a parameter")
-        self._release()
-        keep = [t.detach().contiguous() for t in ws]
+        return [f"predictors.{i}.{p}" for i in range(self.n_prediction_steps) for p in ("weight", "bias")]
+
+    def _weights(self, p):
         w = _lib.CPCWeights()
         if self.n_prediction_steps > 16:
             raise RuntimeError(f"CPCLoss: at most 16 prediction steps are scored, got {self.n_prediction_steps}")
         for i in range(self.n_prediction_steps):
-            w.weight[i], w.bias[i] = keep[2 * i].data_ptr(), keep[2 * i + 1].data_ptr()
+            w.weight[i], w.bias[i] = p(f"predictors.{i}.weight"), p(f"predictors.{i}.bias")
         w.n_steps, w.n_speakers, w.n_utterances = self.n_prediction_steps, self.n_speakers_per_batch, self.n_utterances_per_speaker
         w.n_negatives, w.z_dim, w.c_dim = self.n_negatives, self.z_dim, self.c_dim
-        h = C.c_void_p()
-        with torch.cuda.device(ws[0].device):
-            torch.cuda.current_stream().synchronize()
-            _lib.check(_lib.load().vqcpc_cpc_create(C.byref(w), C.byref(h)))
-        self._handle, self._handle_key = h, key
-        return h
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            _lib.load().vqcpc_cpc_destroy(self._handle)
-            self._handle = None
-
-    def __getstate__(self):                             # the native handle is per object: a copy builds its own
-        d = self.__dict__.copy()
-        d["_handle"], d["_handle_key"] = None, None
-        d.pop("_slots", None)
-        return d
-
-    def refresh(self):
-        """Drop the native handle (it holds COPIES of the predictors) so that the next call re-reads the parameters; needed
-        only after a write through ``.data``, which moves neither storage nor ``_version`` (see ``Encoder.refresh``)."""
-        self._release()
-        self._handle_key = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        return w
 
     # ------------------------------------------------------------------ reference surface
     def _check_negatives(self, negatives, length: int, device):

@@ -76,7 +76,7 @@ class RNNMSVocoder(nn.Module):
         self.ar = _WaveAR(conf.dim_voc_latent, conf.wave_ar, 2 ** conf.bits_mu_law)
 
 
-class Vocoder(nn.Module):
+class Vocoder(_lib.NativeModule):
     """bidirectional_PreNet + WaveRNN (=RNN_MS) conditioned on VQ-CPC codes (``network_vocoder.py:26-78``)."""
 
     def __init__(self, conf: ConfVocoder):
@@ -87,33 +87,17 @@ class Vocoder(nn.Module):
         if conf.rnnms.dim_i_feature != conf.dim_i_embedding + conf.dim_speaker_embedding:
             raise ValueError("rnnms.dim_i_feature must equal dim_i_embedding + dim_speaker_embedding (config.py:198-199)")
         self.rnnms = RNNMSVocoder(conf.rnnms)
-        self._handle = None
-        self._handle_key = None
         self._utterances_done = 0
 
-    # ------------------------------------------------------------------ native handle
-    def _native(self):
-        slots = self.__dict__.get("_slots")
-        if slots is None:                       # resolved once: state_dict() costs more than a short decode call's launch
-            slots = self.__dict__["_slots"] = _lib.WeightSlots(self, list(self.state_dict().keys()))
-        ws = slots.tensors()
-        key = _lib.WeightSlots.key(ws)
-        if self._handle is not None and key == self._handle_key:
-            return self._handle
-        for w in ws:
-            _lib.require_cuda(w, "Vocoder parameter")
-            if w.dtype != torch.float32:
-                raise RuntimeError("Vocoder: parameters must be float32")
-            _lib.require_same_device(w, ws[0], "a parameter")
-        self._release()
-        sd = dict(zip(slots.names, ws))
-        keep = []
+    # ------------------------------------------------------------------ native handle (lifecycle: _lib.NativeModule)
+    _NAME, _CREATE, _DESTROY, _SET_OPTION = "Vocoder", "vqcpc_vocoder_create", "vqcpc_vocoder_destroy", "vqcpc_vocoder_set_option"
+    _WEIGHT_NAMES = (["code_embedding.weight", "speaker_embedding.weight"] +                    # = list(state_dict())
+                     [f"rnnms.prenet.{k}_l{layer}{suf}" for layer in range(2) for suf in ("", "_reverse")
+                      for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] +
+                     ["rnnms.ar.embedding.weight"] + [f"rnnms.ar.rnn.{k}_l0" for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] +
+                     [f"rnnms.ar.{fc}.{k}" for fc in ("fc1", "fc2") for k in ("weight", "bias")])
 
-        def p(name):
-            t = sd[name].detach().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
+    def _weights(self, p):
         w = _lib.VocoderWeights()
         w.code_embedding, w.speaker_embedding = p("code_embedding.weight"), p("speaker_embedding.weight")
         for layer in range(2):
@@ -131,43 +115,7 @@ class Vocoder(nn.Module):
         w.n_codes, w.dz, w.n_speakers, w.ds = c.size_i_codebook, c.dim_i_embedding, c.n_speakers, c.dim_speaker_embedding
         w.Hp, w.de, w.Hr, w.Hf = r.dim_voc_latent // 2, r.wave_ar.size_i_embed_ar, r.wave_ar.size_h_rnn, r.wave_ar.size_h_fc
         w.n_cls, w.upsample_t, w.bits_mu_law = 2 ** r.bits_mu_law, r.upsampling_t, r.bits_mu_law
-        h = C.c_void_p()
-        with torch.cuda.device(ws[0].device):
-            torch.cuda.current_stream().synchronize()
-            _lib.check(_lib.load().vqcpc_vocoder_create(C.byref(w), C.byref(h)))
-        self._handle, self._handle_key = h, key
-        for name, value in self.__dict__.get("_options", {}).items():     # options survive a rebuild of the handle
-            _lib.check(_lib.load().vqcpc_vocoder_set_option(h, name.encode(), value))
-        return h
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            _lib.load().vqcpc_vocoder_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def __getstate__(self):                             # the native handle is per object: a copy builds its own
-        d = self.__dict__.copy()
-        d["_handle"], d["_handle_key"] = None, None
-        d.pop("_slots", None)
-        return d
-
-    def refresh(self):
-        """Drop the native handle (re-laid COPIES of the weights) so the next call re-reads the parameters: needed
-        after an in-place write through ``.data``, which changes neither a parameter's storage nor its ``_version``."""
-        self._release()
-        self._handle_key = None
-
-    def set_option(self, name: str, value: int):
-        """Decode-loop options of ``vqcpc_vocoder_set_option`` (``use_graph``, ``steps_per_graph``, ``xcd``, ...).  They are
-        kept on the Python object and re-applied when the native handle is rebuilt (``.to()``, ``load_state_dict``)."""
-        _lib.check(_lib.load().vqcpc_vocoder_set_option(self._native(), name.encode(), int(value)))
-        self.__dict__.setdefault("_options", {})[name] = int(value)
+        return w
 
     def check(self):
         """Synchronise the current stream and raise if a call since the last check went wrong in a way only the device
@@ -230,6 +178,19 @@ class Vocoder(nn.Module):
         # no device synchronisation here (round 3 read min / max back on every call).
         return z, speaker
 
+    def _sampling_args(self, B: int, seed, utt_base, utt_ids, n_codes):
+        """``(n_codes, seed, utt_base, utt_ids)`` as ``vqcpc_vocoder_generate`` / ``_stream_open`` take them, from the keyword
+        arguments of the sampling protocol: the default seed is torch's, the default stream ids are the next ``B`` of this
+        module's count (``_utterances_done`` moves only when neither ``utt_base`` nor ``utt_ids`` is given)."""
+        seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        nc = _lib.int_array(n_codes, B, "n_codes")
+        ids = _lib.int_array(None if utt_ids is None else [int(v) & 0xFFFFFFFF for v in utt_ids], B, "utt_ids", C.c_uint32)
+        if utt_base is None:
+            utt_base = self._utterances_done
+            if utt_ids is None:
+                self._utterances_done += B
+        return nc, seed, int(utt_base) & 0xFFFFFFFF, ids
+
     @torch.no_grad()
     def generate(self, z: Tensor, speaker: Tensor, *, n_codes=None, seed=None, utt_base=None, utt_ids=None,
                  return_mulaw: bool = False, max_steps: int = 0, async_: bool = False):
@@ -252,14 +213,8 @@ class Vocoder(nn.Module):
             kw = dict(n_codes=n_codes, seed=seed, utt_base=utt_base, utt_ids=utt_ids, return_mulaw=return_mulaw, max_steps=max_steps)
             if utt_base is None:
                 kw["utt_base"] = self._utterances_done             # a repeat must draw from the same streams
-            out = self.generate(z, speaker, async_=True, **kw)
-            try:
-                self.check()
-            except RuntimeError as e:
-                import warnings
-                warnings.warn(f"Vocoder.generate: decode repeated ({e})")
-                out = self.generate(z, speaker, async_=True, **kw)
-                self.check()
+            out = _lib.run_checked(lambda: self.generate(z, speaker, async_=True, **kw), self.check,
+                                   "Vocoder.generate: decode repeated ({})")
             if utt_base is None and utt_ids is None:
                 self._utterances_done += int(z.size(0))
             return out
@@ -269,20 +224,10 @@ class Vocoder(nn.Module):
         L = 2 * self.conf.rnnms.upsampling_t * Tc
         wav = torch.empty(B, L, device=z.device)
         mulaw = torch.empty(B, L, dtype=torch.int64, device=z.device) if return_mulaw else None
-        seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
-        if utt_base is None:
-            utt_base = self._utterances_done
-            if utt_ids is None:
-                self._utterances_done += B
-        ids = None
-        if utt_ids is not None:
-            ids = (C.c_uint32 * B)(*[int(v) & 0xFFFFFFFF for v in utt_ids])
-        nc = None
-        if n_codes is not None:
-            nc = (C.c_int * B)(*[int(v) for v in n_codes])
+        sampling = self._sampling_args(B, seed, utt_base, utt_ids, n_codes)
         with _lib.device_guard(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_generate(
-                h, z.data_ptr(), speaker.data_ptr(), B, Tc, nc, seed, int(utt_base) & 0xFFFFFFFF, ids, wav.data_ptr(),
+                h, z.data_ptr(), speaker.data_ptr(), B, Tc, *sampling, wav.data_ptr(),
                 mulaw.data_ptr() if return_mulaw else None, int(max_steps), _lib.current_stream()))
         return (wav, mulaw) if return_mulaw else wav
 
@@ -299,22 +244,11 @@ class Vocoder(nn.Module):
         z, speaker = self._prep(z, speaker)
         B, Tc = z.shape
         h = self._native()
-        seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
-        if utt_base is None:
-            utt_base = self._utterances_done
-            if utt_ids is None:
-                self._utterances_done += B
-        ids = None
-        if utt_ids is not None:
-            ids = (C.c_uint32 * B)(*[int(v) & 0xFFFFFFFF for v in utt_ids])
-        nc = None
-        if n_codes is not None:
-            nc = (C.c_int * B)(*[int(v) for v in n_codes])
+        sampling = self._sampling_args(B, seed, utt_base, utt_ids, n_codes)
         st = C.c_void_p()
         with _lib.device_guard(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_stream_open(
-                h, z.data_ptr(), speaker.data_ptr(), B, Tc, nc, seed, int(utt_base) & 0xFFFFFFFF, ids, C.byref(st),
-                _lib.current_stream()))
+                h, z.data_ptr(), speaker.data_ptr(), B, Tc, *sampling, C.byref(st), _lib.current_stream()))
         return VocoderStream(self, h, st, B, int(chunk_samples), z.device, return_mulaw)
 
     @torch.no_grad()
@@ -331,7 +265,7 @@ class Vocoder(nn.Module):
         if x.min().item() < 0 or x.max().item() >= 2 ** self.conf.rnnms.bits_mu_law:
             raise IndexError("index out of range in self")
         logits = torch.empty(B, Ts, 2 ** self.conf.rnnms.bits_mu_law, device=z.device)
-        with torch.cuda.device(z.device):
+        with _lib.device_guard(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_logits(self._native(), x.data_ptr(), z.data_ptr(), speaker.data_ptr(),
                                                         B, Tc, Ts, logits.data_ptr(), _lib.current_stream()))
             self.check()              # a bad z / speaker raises here, like nn.Embedding, and is not left latched for generate()
@@ -357,22 +291,13 @@ class Vocoder(nn.Module):
             raise RuntimeError("audio must be an integer tensor of mu-law classes (the targets of F.cross_entropy, vocoder.py:63)")
         audio = audio.detach().to(torch.int64).contiguous()
         L = audio.size(1)
-
-        def host_ints(v, what):
-            if v is None:
-                return None
-            v = [int(x) for x in (v.tolist() if isinstance(v, Tensor) else v)]
-            if len(v) != B:
-                raise RuntimeError(f"{what} must have one entry per utterance ({B}), got {len(v)}")
-            return (C.c_int * B)(*v)
-
-        na, nc = host_ints(lengths, "lengths"), host_ints(n_codes, "n_codes")
+        na, nc = _lib.int_array(lengths, B, "lengths"), _lib.int_array(n_codes, B, "n_codes")
         dev = z.device
         nll_sum = torch.empty(B, dtype=torch.float64, device=dev)
         n_scored = torch.empty(B, dtype=torch.int64, device=dev)
         n_correct = torch.empty(B, dtype=torch.int64, device=dev)
         nll = torch.empty(B, L - 1, device=dev) if per_sample else None
-        with torch.cuda.device(dev):
+        with _lib.device_guard(dev):
             _lib.check(_lib.load().vqcpc_vocoder_nll(
                 self._native(), audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, nll_sum.data_ptr(),
                 n_scored.data_ptr(), n_correct.data_ptr(), nll.data_ptr() if per_sample and L > 1 else None,
@@ -387,7 +312,7 @@ class Vocoder(nn.Module):
         z, speaker = self._prep(z, speaker)
         B, Tc = z.shape
         out = torch.empty(B, 2 * Tc, self.conf.dim_i_embedding + self.conf.dim_speaker_embedding, device=z.device)
-        with torch.cuda.device(z.device):
+        with _lib.device_guard(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_glue(self._native(), z.data_ptr(), speaker.data_ptr(), B, Tc, out.data_ptr(),
                                                       _lib.current_stream()))
             self.check()
@@ -399,7 +324,7 @@ class Vocoder(nn.Module):
         z, speaker = self._prep(z, speaker)
         B, Tc = z.shape
         out = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=z.device)
-        with torch.cuda.device(z.device):
+        with _lib.device_guard(z.device):
             _lib.check(_lib.load().vqcpc_vocoder_condition(self._native(), z.data_ptr(), speaker.data_ptr(), B, Tc,
                                                            out.data_ptr(), _lib.current_stream()))
             self.check()
