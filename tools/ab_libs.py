@@ -29,4 +29,10 @@ print(sys.argv[1], " ".join(out), flush=True)
 ''' % ROOT
 for rnd in range(2):
     for lib in sys.argv[1:]:
-        subprocess.run([sys.executable, "-c", CHILD, os.path.abspath(lib)], check=False)
+        # a child that fails or hangs ends the comparison: nothing more is started on a GPU that may have faulted
+        try:
+            rc = subprocess.run([sys.executable, "-c", CHILD, os.path.abspath(lib)], check=False, timeout=300).returncode
+        except subprocess.TimeoutExpired:
+            sys.exit(f"{lib}: child still running after 300 s")
+        if rc != 0:
+            sys.exit(f"{lib}: child exited with {rc}")

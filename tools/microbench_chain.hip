@@ -5,6 +5,12 @@
 //   variant 1: two slots per pass, their phases interleaved (two accumulators)
 //   variant 2: the four slots at once on the matrix pipe: 112 dependent v_mfma_f32_4x4x1_16B_f32 (block = quad: A = the quad's four rows,
 //              B = the four slots; lane 4 b + j reads slot j's 112 operands itself: 28 ds_read_b128), four combines
+//   variant 3: variant 2 with ONE operand read per group of 8 terms: the halves of the wave read different words and the B lane-group
+//              pattern picks the half (csrc/ar_chain.h chain_mfma_regs, the decoder's own code): 14 ds_read_b128
+//   variant 4: variant 2 with the decoder's ORDER of requests (a group's two operand words requested BEHIND the previous group's terms, as
+//              chain_mfma_regs does for the sake of the other waves on the pipe): what variant 3 is to be compared with -- variant 2 asks
+//              in front of the terms and so hides a read behind a whole group
+// The last columns are the mean per wave POSITION on its SIMD (wave / 4: the oldest wave of a SIMD first).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I vectorquantizedcpc_amd/csrc -o /tmp/mb_chain tools/microbench_chain.hip && /tmp/mb_chain
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -58,6 +64,24 @@ __device__ __forceinline__ v4f chain_mfma(const float *w, const float *op) {
     return acc;
 }
 
+__device__ __forceinline__ v4f chain_mfma_behind(const float *w, const float *op) {
+    v4f acc = {0.f, 0.f, 0.f, 0.f};
+    float4 cur[2], nxt[2];
+    cur[0] = *(const float4 *)op; cur[1] = *(const float4 *)(op + 4);
+#pragma unroll
+    for (int g = 0; g < 14; ++g) {
+        nxt[0] = cur[0]; nxt[1] = cur[1];
+        const float hv[8] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w};
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[8 * g + i], hv[i], acc, 0, 0, 0);
+        if (g + 1 < 14) { nxt[0] = *(const float4 *)(op + 8 * (g + 1)); nxt[1] = *(const float4 *)(op + 8 * (g + 1) + 4); }
+        __builtin_amdgcn_sched_barrier(0);
+        cur[0] = nxt[0]; cur[1] = nxt[1];
+    }
+    return acc;
+}
+
 template <int VAR>
 __global__ void __launch_bounds__(768) k(const float *in, float *out, int rounds, unsigned long long *ticks) {
     __shared__ float hc[4 * MHS];
@@ -79,12 +103,22 @@ __global__ void __launch_bounds__(768) k(const float *in, float *out, int rounds
                 const float v = chain_combine(acc);
                 if (sum_lane) gsum[b * 96 + 8 * (wave % 12) + (lane >> 4) * 2 + (lane & 1u)] = v;
             }
-        } else if (VAR == 2) {
-            const v4f a4 = chain_mfma(w, hc + j * MHS + cid * MS);
+        } else if (VAR == 2 || VAR == 4) {
+            const v4f a4 = VAR == 2 ? chain_mfma(w, hc + j * MHS + cid * MS) : chain_mfma_behind(w, hc + j * MHS + cid * MS);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float v = chain_combine(a4[i]);
                 if (sum_lane) gsum[j * 96 + 8 * (wave % 12) + (lane >> 5) * 4 + i] = v;      // rows 4 rq + i of slot j (either c0 lane row holds it)
+            }
+        } else if (VAR == 3) {
+            const float *op = hc + j * MHS + cid * MS + 4 * (lane >> 5);
+            v4f a4 = {0.f, 0.f, 0.f, 0.f};
+            float4 cur = *(const float4 *)op;
+            chain_mfma_regs<0, NG_H>(a4, w, op, cur);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float v = chain_combine(a4[i]);
+                if (sum_lane) gsum[j * 96 + 8 * (wave % 12) + (lane >> 5) * 4 + i] = v;
             }
         } else {
             for (int b = 0; b < 4; b += 2) {
@@ -108,20 +142,22 @@ int main() {
     CK(hipMemset(in, 0, 8192 * 4));
     const int rounds = 2000;
     static unsigned long long h[256 * 12];
-    printf("variant,waves_per_simd,us_per_pass_of_one_slot_mean,slowest_wave,fastest_wave\n");
-    for (int var = 0; var < 3; ++var)
+    printf("variant,waves_per_simd,us_per_pass_of_one_slot_mean,slowest_wave,fastest_wave,mean_position_0,mean_position_1,mean_position_2\n");
+    for (int var = 0; var < 5; ++var)
         for (int thr = 256; thr <= 768; thr += 256) {
             for (int rep = 0; rep < 2; ++rep) {
                 CK(hipMemset(ticks, 0, 256 * 12 * 8));
                 if (var == 0) hipLaunchKernelGGL(k<0>, dim3(256), dim3(thr), 0, 0, in, out, rounds, ticks);
                 else if (var == 1) hipLaunchKernelGGL(k<1>, dim3(256), dim3(thr), 0, 0, in, out, rounds, ticks);
-                else hipLaunchKernelGGL(k<2>, dim3(256), dim3(thr), 0, 0, in, out, rounds, ticks);
+                else if (var == 2) hipLaunchKernelGGL(k<2>, dim3(256), dim3(thr), 0, 0, in, out, rounds, ticks);
+                else if (var == 3) hipLaunchKernelGGL(k<3>, dim3(256), dim3(thr), 0, 0, in, out, rounds, ticks);
+                else hipLaunchKernelGGL(k<4>, dim3(256), dim3(thr), 0, 0, in, out, rounds, ticks);
                 CK(hipDeviceSynchronize());
             }
             CK(hipMemcpy(h, ticks, sizeof(h), hipMemcpyDeviceToHost));
-            double sum = 0, mx = 0, mn = 1e30; int n = 0;
-            for (int b = 0; b < 256; ++b) for (int wv = 0; wv < thr / 64; ++wv) { const double us = h[b * 12 + wv] * 0.01 / (rounds * 4.0); sum += us; ++n; if (us > mx) mx = us; if (us < mn) mn = us; }
-            printf("%d,%d,%.3f,%.3f,%.3f\n", var, thr / 256, sum / n, mx, mn);
+            double sum = 0, mx = 0, mn = 1e30, pos[3] = {0, 0, 0}; int n = 0;
+            for (int b = 0; b < 256; ++b) for (int wv = 0; wv < thr / 64; ++wv) { const double us = h[b * 12 + wv] * 0.01 / (rounds * 4.0); sum += us; pos[wv / 4] += us / (256 * 4); ++n; if (us > mx) mx = us; if (us < mn) mn = us; }
+            printf("%d,%d,%.3f,%.3f,%.3f,%.3f,%.3f,%.3f\n", var, thr / 256, sum / n, mx, mn, pos[0], pos[1], pos[2]);
         }
     return 0;
 }

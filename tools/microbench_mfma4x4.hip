@@ -2,7 +2,10 @@
 //   hipcc --offload-arch=gfx950 -O3 -o /tmp/mb4 tools/microbench_mfma4x4.hip && /tmp/mb4
 // (1) operand layout: which lane supplies A / B of which block, where D[i][j] lands;
 // (2) D = fmaf(A, B, C) bit for bit (one rounding), also for denormal / huge operands;
-// (3) cost of a DEPENDENT chain of 112 of them (the accumulator of one is srcC of the next), 1..3 waves per SIMD.
+// (3) cost of a DEPENDENT chain of 112 of them (the accumulator of one is srcC of the next), 1..3 waves per SIMD;
+// (6) B lane-group patterns 1 and 2 (one half of the wave supplies B for both): layout, that the other half's register is IGNORED
+//     (NaN / Inf there change nothing), and that a chain alternating the two costs what a plain one does -- what ar_chain.h's
+//     one-operand-read-per-group chains rest on.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -25,6 +28,42 @@ __global__ void blgp_kernel(const float *a, const float *b, float *d) {
     v4f acc = {0.f, 0.f, 0.f, 0.f};
     acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a[l], b[l], acc, 0, 0, 1);
     for (int i = 0; i < 4; ++i) d[4 * l + i] = acc[i];
+}
+
+// B lane-group pattern 2: the lower 32 lanes take their B operand from the upper 32
+__global__ void blgp2_kernel(const float *a, const float *b, const float *c, float *d) {
+    const int l = threadIdx.x;
+    v4f acc = {c[4 * l], c[4 * l + 1], c[4 * l + 2], c[4 * l + 3]};
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a[l], b[l], acc, 0, 0, 2);
+    for (int i = 0; i < 4; ++i) d[4 * l + i] = acc[i];
+}
+__global__ void blgp1c_kernel(const float *a, const float *b, const float *c, float *d) {
+    const int l = threadIdx.x;
+    v4f acc = {c[4 * l], c[4 * l + 1], c[4 * l + 2], c[4 * l + 3]};
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a[l], b[l], acc, 0, 0, 1);
+    for (int i = 0; i < 4; ++i) d[4 * l + i] = acc[i];
+}
+// the chain of (3) with the patterns of ar_chain.h's mfma_group8: four terms with pattern 1, four with pattern 2
+template <int N, bool ALT>
+__global__ __launch_bounds__(768) void chain_blgp_kernel(const float *a, const float *b, float *d, long long *cycles, int reps) {
+    const int l = threadIdx.x;
+    float w[N], h[4];
+    for (int i = 0; i < N; ++i) w[i] = a[(l * 131 + i * 7) % 4096];
+    for (int i = 0; i < 4; ++i) h[i] = b[(l * 17 + i * 3) % 4096];
+    v4f acc = {0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    const long long t0 = clock64();
+    for (int r = 0; r < reps; ++r) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (!ALT) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[i], h[i & 3], acc, 0, 0, 0);
+            else if ((i & 4) == 0) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[i], h[i & 3], acc, 0, 0, 1);
+            else acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[i], h[i & 3], acc, 0, 0, 2);
+        }
+    }
+    const long long t1 = clock64();
+    if ((l & 63) == 0) cycles[blockIdx.x * (blockDim.x / 64) + l / 64] = t1 - t0;
+    for (int i = 0; i < 4; ++i) d[(blockIdx.x * blockDim.x + l) * 4 + i] = acc[i];
 }
 
 template <int N>
@@ -242,5 +281,58 @@ int main() {
         run(2, "4 accumulators, B fragments from LDS ");
         run(3, "2 accumulators, B fragments from LDS ");
     }
-    return layout_ok && bad == 0 ? 0 : 1;
+    // ---- (6) B lane-group patterns 1 and 2
+    bool blgp_ok = true;
+    {
+        auto bits_equal = [](const float *x, const float *y, int n2) { return memcmp(x, y, 4 * n2) == 0; };
+        std::vector<float> ref(256), got(256);
+        for (int pat = 1; pat <= 2; ++pat) {
+            // the half that supplies B: lanes 0..31 (pattern 1) or 32..63 (pattern 2); A and C stay per lane
+            const int src = pat == 1 ? 0 : 32, ign = 32 - src;
+            srand(11 + pat);
+            for (int e = 0; e < 64; ++e) { ha[e] = (float)rand() / RAND_MAX * 2.f - 1.f; hb[e] = (float)rand() / RAND_MAX * 2.f - 1.f; }
+            for (int e = 0; e < 256; ++e) hc[e] = (float)rand() / RAND_MAX * 2.f - 1.f;
+            auto run = [&](std::vector<float> &out) {
+                hipMemcpy(a, ha.data(), 256, hipMemcpyHostToDevice); hipMemcpy(b, hb.data(), 256, hipMemcpyHostToDevice);
+                hipMemcpy(c, hc.data(), 1024, hipMemcpyHostToDevice);
+                if (pat == 1) blgp1c_kernel<<<1, 64>>>(a, b, c, d); else blgp2_kernel<<<1, 64>>>(a, b, c, d);
+                hipMemcpy(out.data(), d, 1024, hipMemcpyDeviceToHost);
+            };
+            run(ref);
+            bool lay = true;
+            for (int l = 0; l < 64; ++l)
+                for (int i = 0; i < 4; ++i) {
+                    const float want = fmaf(ha[4 * (l / 4) + i], hb[src + (l & 31)], hc[4 * l + i]);
+                    lay &= memcmp(&want, &ref[4 * l + i], 4) == 0;
+                }
+            printf("blgp = %d: every lane l uses the B operand of lane %d + (l & 31), A and C unchanged, bit for bit fmaf: %s\n", pat, src, lay ? "CONFIRMED" : "NOT AS EXPECTED");
+            blgp_ok &= lay;
+            const float poison[4] = {NAN, INFINITY, -INFINITY, 3.0e38f};
+            const char *pname[4] = {"NaN", "+Inf", "-Inf", "3e38"};
+            for (int k = 0; k < 4; ++k) {
+                std::vector<float> keep(hb.begin(), hb.begin() + 64);
+                for (int e = 0; e < 32; ++e) hb[ign + e] = poison[k];
+                run(got);
+                std::copy(keep.begin(), keep.end(), hb.begin());
+                const bool same = bits_equal(ref.data(), got.data(), 256);
+                printf("blgp = %d: %s in the B register of lanes %d..%d (the ignored half): results %s\n", pat, pname[k], ign, ign + 31, same ? "bit-equal to the finite run: IGNORED" : "DIFFER: the ignored half LEAKS");
+                blgp_ok &= same;
+            }
+        }
+        for (int e = 0; e < 4096; ++e) { ha[e] = (float)rand() / RAND_MAX - 0.5f; hb[e] = (float)rand() / RAND_MAX - 0.5f; }
+        hipMemcpy(a, ha.data(), 4096 * 4, hipMemcpyHostToDevice); hipMemcpy(b, hb.data(), 4096 * 4, hipMemcpyHostToDevice);
+        for (int waves : {4, 8, 12})
+            for (int alt = 0; alt < 2; ++alt) {
+                for (int rep = 0; rep < 2; ++rep) {
+                    if (alt) chain_blgp_kernel<112, true><<<256, 64 * waves>>>(a, b, d, cyc, reps);
+                    else chain_blgp_kernel<112, false><<<256, 64 * waves>>>(a, b, d, cyc, reps);
+                }
+                hipDeviceSynchronize();
+                hipMemcpy(hcyc.data(), cyc, 256 * waves * 8, hipMemcpyDeviceToHost);
+                double s2 = 0; for (int i = 0; i < 256 * waves; ++i) s2 += hcyc[i];
+                printf("chain of 112 dependent mfma 4x4x1, %s, %d waves per SIMD: %.2f shader cycles per instruction per wave\n",
+                       alt ? "patterns 1,1,1,1,2,2,2,2" : "pattern 0               ", waves / 4, s2 / (256.0 * waves) / reps / 112);
+            }
+    }
+    return layout_ok && blgp_ok && bad == 0 ? 0 : 1;
 }

@@ -271,9 +271,10 @@ __device__ __forceinline__ int chain_pos(int k, int stride) {
 // twelve passes of a 4-slot step 3.3 us -- the step was vector-ALU bound behind barrier A (tools/xcd_barriers.py: the youngest
 // wave of every SIMD reaches barrier B 3.6 us after A, with or without the exchange waits); the matrix pipe does the four
 // slots' chains of three waves in 1.5 us and leaves the vector ALU to the serial work.
-// Operands: the lane reads ITS slot's copy of the chain itself, terms in plain order (28 ds_read_b128 per step -- as many as the
-// dpp form's 4 x 7): hc[j * HS4 + cid * NT_H + n].  Slot stride HS4 = HR + 4: the four lanes of a quad start one 16-byte unit
-// apart, the four quads of a ds_read_b128 lane group (chains {0,6,3,5} or {2,4,1,7}, 28 units apart) 4 units apart -- 64 banks.
+// Operands: the lane reads ITS slot's copy of the chain itself, terms in plain order: hc[j * HS4 + cid * NT_H + n] -- 14
+// ds_read_b128 per step, each half of the wave one word of a group's two (below; the dpp form reads 4 x 7).  Slot stride
+// HS4 = HR + 4: the four lanes of a quad start one 16-byte unit apart, the four quads of a ds_read_b128 lane group (chains
+// {0,6,3,5} or {2,4,1,7}, 28 units apart) 4 units apart -- 64 banks.
 typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int HS4 = HR + 4;
 constexpr int NG_H = NT_H / 8;         // groups of 8 terms (two 16-byte operand words)
@@ -283,50 +284,66 @@ __device__ __forceinline__ int chain_pos_plain(int k, int stride) {
     const int q = (k >> 2) & 3, c0 = k & 1, ci = (k >> 1) & 1;
     return (2 * kw + c0) * stride + 8 * s + 4 * ci + q;
 }
-// groups [G0, G1) of the chain, weights pinned (w[n] = term n); cur = the operands of group G0, already requested (it leaves
-// with those of group G1: a chain can pause between two calls without losing its prefetch)
+// ONE operand word per lane and group of 8 terms, not two.  A lane's operand depends on (kw, c0, j) and not on rq: lanes 32..63 would
+// read exactly what lanes 0..31 read.  So the halves read DIFFERENT words -- lanes 0..31 terms 8 g .. 8 g + 3, lanes 32..63 terms
+// 8 g + 4 .. 8 g + 7 (`op` carries the half's offset, 4 rq floats) -- and the instruction's B lane-group pattern picks the half that
+// holds the term: pattern 1 = both halves take B from lanes 0..31, pattern 2 = both take it from lanes 32..63; the other half's
+// register is ignored, whatever it holds (tools/microbench_mfma4x4.hip).  A stays per lane.  Same bits: every accumulator still sees
+// fmaf(w[n], h[n], acc) for n = 0 .. 111 in order, with the values it saw before -- only the register the value comes from differs.
+// 14 operand reads per wave and step instead of 28; inside each 16-lane group of a ds_read_b128 all lanes moved by the same 16 bytes,
+// so the bank picture above holds.
+__device__ __forceinline__ void mfma_group8(v4f &acc, const float *w, const float4 &h) {
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[0], h.x, acc, 0, 0, 1);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[1], h.y, acc, 0, 0, 1);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[2], h.z, acc, 0, 0, 1);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[3], h.w, acc, 0, 0, 1);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[4], h.x, acc, 0, 0, 2);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[5], h.y, acc, 0, 0, 2);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[6], h.z, acc, 0, 0, 2);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[7], h.w, acc, 0, 0, 2);
+}
+// groups [G0, G1) of the chain, weights pinned (w[n] = term n); cur = this half's operand word of group G0, already requested (it
+// leaves with that of group G1: a chain can pause between two calls without losing its prefetch)
 template <int G0, int G1>
-__device__ __forceinline__ void chain_mfma_regs(v4f &acc, const float *w, const float *op, float4 (&cur)[2]) {
-    float4 nxt[2];
+__device__ __forceinline__ void chain_mfma_regs(v4f &acc, const float *w, const float *op, float4 &cur) {
 #pragma unroll
     for (int g = G0; g < G1; ++g) {
-        nxt[0] = cur[0]; nxt[1] = cur[1];
-        const float hv[8] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w};
+        float4 nxt = cur;
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w[8 * g + i], hv[i], acc, 0, 0, 0);
+        mfma_group8(acc, w + 8 * g, cur);
         // the next group's operands are requested BEHIND this group's terms (in front of them: 3.73 instead of 3.69 us per step at 32
         // utterances): three waves share the pipe, the read comes back while the other two run their groups
-        if (g + 1 < NG_H) { nxt[0] = *(const float4 *)(op + 8 * (g + 1)); nxt[1] = *(const float4 *)(op + 8 * (g + 1) + 4); }
+        if (g + 1 < NG_H) nxt = *(const float4 *)(op + 8 * (g + 1));
         __builtin_amdgcn_sched_barrier(0);
-        cur[0] = nxt[0]; cur[1] = nxt[1];
+        cur = nxt;
     }
 }
 // the whole chain with its weights streamed from the word-interleaved LDS copy (word i of the lane's chain at wp[i * WS]), D groups
 // ahead of their use -- weights AND operands: behind barrier A a ds_read_b128 comes back after ~300 cycles (twelve waves read), a
 // group's 8 dependent matrix instructions take ~140, and with one group of prefetch the chain ran at the LDS latency (fc1, the first
 // thing on the step's critical path: 1.9 us; profiles/r04_mfma_chains.txt).  wpre = words 0 .. 2 D - 1, requested before the barrier
-// the chain waits behind.
+// the chain waits behind.  A group is THREE reads -- the half's operand word (mfma_group8) and the lane's two weight words: A is not
+// shared between the halves (WS = 32, rows 80..83: both halves read lane & 31's chain and run the same products) -- so five groups
+// fit under the 4-bit lgkmcnt counter where four reads per group allowed three.
 template <int WS, int D>
 __device__ __forceinline__ v4f chain_mfma_lds(const float4 *wp, const float4 *wpre, const float *op) {
+    static_assert(3 * D <= 15, "reads in flight: lgkmcnt counts to 15");
     v4f acc = {0.f, 0.f, 0.f, 0.f};
-    float4 hb[D][2], wb[D][2];
+    float4 hb[D], wb[D][2];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-        hb[d][0] = *(const float4 *)(op + 8 * d); hb[d][1] = *(const float4 *)(op + 8 * d + 4);
+        hb[d] = *(const float4 *)(op + 8 * d);
         wb[d][0] = wpre[2 * d]; wb[d][1] = wpre[2 * d + 1];
     }
 #pragma unroll
     for (int g = 0; g < NG_H; ++g) {
         const int s = g % D;
         __builtin_amdgcn_sched_barrier(0);
-        const float hv[8] = {hb[s][0].x, hb[s][0].y, hb[s][0].z, hb[s][0].w, hb[s][1].x, hb[s][1].y, hb[s][1].z, hb[s][1].w};
         const float wv[8] = {wb[s][0].x, wb[s][0].y, wb[s][0].z, wb[s][0].w, wb[s][1].x, wb[s][1].y, wb[s][1].z, wb[s][1].w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[i], hv[i], acc, 0, 0, 0);
+        mfma_group8(acc, wv, hb[s]);
         __builtin_amdgcn_sched_barrier(0);
         if (g + D < NG_H) {                                     // refill the buffer just used with group g + D
-            hb[s][0] = *(const float4 *)(op + 8 * (g + D)); hb[s][1] = *(const float4 *)(op + 8 * (g + D) + 4);
+            hb[s] = *(const float4 *)(op + 8 * (g + D));
             wb[s][0] = wp[(2 * (g + D)) * WS]; wb[s][1] = wp[(2 * (g + D) + 1) * WS];
         }
     }

@@ -229,7 +229,8 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
     } while (0)
 
     const float *opnd = hc + cid * NT_H + 4 * j;                       // dpp chains: the quad's lane j reads word j of a phase
-    const float *opm = hc + j * L::HS + cid * NT_H;                     // matrix-pipe chains (four slots): lane j reads slot j's chain
+    // matrix-pipe chains (four slots): lane j reads slot j's chain, the upper half wave the second word of a group
+    const float *opm = hc + j * L::HS + cid * NT_H + 4 * rq;
     bool fc1_role = false;
     if constexpr (BXT == 1) fc1_role = wave == 1;
     if (fc1_role) {
@@ -346,8 +347,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 // ---- the four slots at once on the matrix pipe (ar_chain.h); the wave of slot cw looks for a_t after XD_GSPLIT of the
                 // chain's 14 groups: fc1 is out about then
                 v4f a4 = {0.f, 0.f, 0.f, 0.f};
-                float4 cur[2];
-                cur[0] = *(const float4 *)opm; cur[1] = *(const float4 *)(opm + 4);
+                float4 cur = *(const float4 *)opm;
                 // waves 4 and 8 share fc1's SIMD (wave 0): they stand back until a_t is out.  Three dependent-chain waves keep a SIMD's issue port
                 // busy; fc1 -- the head of the step's critical path -- ran at a third of the matrix pipe, and the 60 vector instructions between its
                 // last term and the a_t stores took 0.4..0.7 us among the others' matrix instructions (profiles/r04_mfma_chains.txt)
