@@ -233,6 +233,43 @@ int vqcpc_abx_score(const float *feats, int n_frames, int D, const int32_t *toke
                     int64_t n_dist, int64_t n_out, void *work, float *cost, int32_t *path_len, float *dist,
                     int32_t *twice_wins, void *stream);
 
+/* The index form of ABX scoring: the frames of quantised units are rows of a codebook, so a call's frame distances are M x M
+ * values.  vqcpc_abx_code_table makes them once, vqcpc_abx_score_indices scores runs of indices with them (or, under the edit
+ * metric, without them).
+ *
+ * Bytes of `work` (M * D * 4, the normalised codebook) plus `table` (M * M * 4) of vqcpc_abx_code_table. */
+int vqcpc_abx_index_workspace_bytes(int M, int D, uint64_t *bytes);
+
+/* codebook DEVICE (M, D) fp32, 1 <= M <= 4096, D % 4 == 0, 4 <= D <= 512 -> table DEVICE (M, M) fp32: table[i][j] = the frame
+ * distance of vqcpc_abx_score between an A frame equal to row i and an X frame equal to row j, BIT FOR BIT (the same sums in the
+ * same order, by the same device code), so index runs score exactly as their frames would.  Symmetric, 0 on the diagonal.
+ * work DEVICE, M * D * 4 bytes.  codebook, work and table 16-byte aligned.  One normalisation launch and one table launch on
+ * `stream`, no synchronisation.  VQCPC_ERR_INVALID before anything is enqueued for NULL, M, D and alignment. */
+int vqcpc_abx_code_table(const float *codebook, int M, int D, void *work, float *table, void *stream);
+
+/* metric of vqcpc_abx_score_indices */
+#define VQCPC_ABX_ANGULAR 0 /* DTW over table[code_a][code_x]: cost, path_len, dist and twice_wins of vqcpc_abx_score on the frames */
+#define VQCPC_ABX_EDIT 1    /* Levenshtein distance between the raw index runs (repeats are not collapsed) */
+
+/* vqcpc_abx_score on runs of codebook indices: codes DEVICE (n_frames) int32 in [0, M), tokens (first_row, n_frames) as rows of
+ * `codes`; lists, segs, blocks, the HOST scalars, the outputs and their layout are those of vqcpc_abx_score (same block table,
+ * same workgroup numbering, a block lands where it lands there).  One DTW launch and the count launch of vqcpc_abx_score on
+ * `stream`, no synchronisation, no atomics.
+ * VQCPC_ABX_ANGULAR: table DEVICE (M, M) from vqcpc_abx_code_table, 16-byte aligned; a pair's tile is
+ *   d[i][j] = table[code_a[i] * M + code_x[j]], then the DTW of vqcpc_abx_score: every output has the bits vqcpc_abx_score gives
+ *   on feats[f] = codebook[codes[f]].
+ * VQCPC_ABX_EDIT: table may be NULL, M only bounds the codes.  E(0, 0) = 0, E(i, 0) = i, E(0, j) = j,
+ *   E(i, j) = min(E(i-1, j-1) + [a_i != x_j], E(i-1, j) + 1, E(i, j-1) + 1) on the INDICES (two equal codebook rows with
+ *   different indices differ).  cost = E(Ta, Tb) (exact in fp32), path_len = max(Ta, Tb), dist = cost / path_len in [0, 1];
+ *   fp32 division is correctly rounded, so equal ratios have equal bits and the counts' tie term is exact.
+ * VQCPC_ERR_INVALID before anything is enqueued for NULL (table only under VQCPC_ABX_ANGULAR), M outside [1, 4096], the
+ * counts, an unknown metric, a misaligned table.  What lives in DEVICE tables is clamped as in vqcpc_abx_score, codes into
+ * [0, M): the caller rejects bad values (the Python wrapper raises IndexError before the call). */
+int vqcpc_abx_score_indices(const float *table, int M, const int32_t *codes, int n_frames, const int32_t *tokens, int n_tokens,
+                            const int32_t *lists, int n_lists, const int32_t *segs, int n_segs, const int32_t *blocks,
+                            int n_blocks, int n_workgroups, int64_t n_dist, int64_t n_out, float *cost, int32_t *path_len,
+                            float *dist, int32_t *twice_wins, void *stream, int metric);
+
 /* ------------------------------------------------------------------ Vocoder ---------- */
 
 /* Vocoder.state_dict(): own tables (network_vocoder.py:37-38) plus the RNN_MS core the

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Times of ABX scoring on one synthetic workload: the three-launch call ``vqcpc_abx_score`` against (a) the float64 numpy
-restatement of ``tests/abx_ref.py`` spread over the host's threads and (b) a batched PyTorch composition of the same protocol on
+"""Times of ABX scoring on one synthetic workload: the three-launch call ``vqcpc_abx_score`` and, on the same units given as
+codebook indices, ``vqcpc_abx_score_indices`` (angular metric from the code table, edit metric) and the table build
+``vqcpc_abx_code_table`` on its own, with the device bytes each path holds -- against (a) the float64 numpy restatement of ``tests/abx_ref.py`` spread over the host's threads and (b) a batched PyTorch composition of the same protocol on
 the same GPU (one ``bmm`` for the frame cosines, ``acos``, and one anti-diagonal DP step per torch op group).
 
     python tools/abx_times.py [--out profiles/abx_times.txt] [--windows 20] [--window-ms 40] [--threads 16]
@@ -43,13 +44,13 @@ def workload():
                     on = 0.01 + 0.02 * j
                     items.append(abx.Item(f"f{s}", round(on - 0.005, 4), round(on + 0.02 * (n - 1) + 0.005, 4), f"p{p}", f"l{c}", f"r{c}", f"s{s}"))
     book = synth._normalish("abx/times/book", (CODEBOOK, D), synth.SEED).numpy()
-    feats = {f"f{s}": book[synth.randint(f"abx/times/codes{s}", (FRAMES_PER_FILE,), CODEBOOK).numpy()].astype(np.float32)
-             for s in range(SPEAKERS)}
+    idx = {f"f{s}": synth.randint(f"abx/times/codes{s}", (FRAMES_PER_FILE,), CODEBOOK).numpy() for s in range(SPEAKERS)}
+    feats = {f: book[v].astype(np.float32) for f, v in idx.items()}
     files = sorted(feats)
     first = np.cumsum([0] + [feats[f].shape[0] for f in files])
     tok = abx.tokens_of(items, {f: feats[f].shape[0] for f in files})
     tokens = [(int(first[files.index(it.file)]) + lo, n) for it, (lo, n) in zip(items, tok)]
-    return items, np.concatenate([feats[f] for f in files]), tokens
+    return items, np.concatenate([feats[f] for f in files]), tokens, book.astype(np.float32), np.concatenate([idx[f] for f in files])
 
 
 def window_ms(fn, reps):
@@ -93,7 +94,41 @@ def fused_call(frames, tokens, blocks, dev):
         _lib.check(lib.vqcpc_abx_score(f.data_ptr(), f.shape[0], f.shape[1], t[0].data_ptr(), tok.shape[0], t[1].data_ptr(), lists.size,
                                        t[2].data_ptr(), segs.size, t[3].data_ptr(), rows.shape[0], wg, nd, no, work.data_ptr(), None, None,
                                        dist.data_ptr(), tw.data_ptr(), stream))
-    return call, dist, tw, (f, work, t)
+    held = {"frames": f.numel() * 4, "normalised copy of the frames": work.numel() * 4}
+    common = sum(a.numel() * 4 for a in t) + dist.numel() * 4 + tw.numel() * 4
+    return call, dist, tw, (f, work, t), held, common
+
+
+def table_call(book, dev):
+    """The code table of the workload's codebook and a closure that enqueues its two launches."""
+    lib = _lib.load()
+    b = torch.from_numpy(book).to(dev)
+    M, Dm = b.shape
+    work = torch.empty(M * Dm, device=dev)
+    table = torch.empty(M, M, device=dev)
+    stream = _lib.current_stream()
+
+    def call():
+        _lib.check(lib.vqcpc_abx_code_table(b.data_ptr(), M, Dm, work.data_ptr(), table.data_ptr(), stream))
+    return call, table, (b, work)
+
+
+def index_call(codes, table, tokens, blocks, dev, metric):
+    """The same tables on the indices: a closure that enqueues the two launches of ``vqcpc_abx_score_indices``."""
+    lib = _lib.load()
+    tok, lists, segs, rows, wg, nd, no = abx._tables(tokens, blocks, codes.shape[0])
+    t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (tok, lists, segs, rows)]
+    c = torch.from_numpy(codes.astype(np.int32)).to(dev)
+    dist = torch.empty(nd, device=dev)
+    tw = torch.empty(no, dtype=torch.int32, device=dev)
+    stream = _lib.current_stream()
+    M = table.shape[0]
+
+    def call():
+        _lib.check(lib.vqcpc_abx_score_indices(table.data_ptr() if metric == 0 else None, M, c.data_ptr(), c.shape[0], t[0].data_ptr(),
+                                               tok.shape[0], t[1].data_ptr(), lists.size, t[2].data_ptr(), segs.size, t[3].data_ptr(),
+                                               rows.shape[0], wg, nd, no, None, None, dist.data_ptr(), tw.data_ptr(), stream, metric))
+    return call, dist, tw, (c, t)
 
 
 def torch_call(frames, tokens, blocks, dev):
@@ -168,7 +203,7 @@ def main():
     args = ap.parse_args()
     import multiprocessing as mp
     dev = torch.device("cuda:0")
-    items, frames, tokens = workload()
+    items, frames, tokens, book, codes = workload()
     lens = [n for _, n in tokens]
     lines = [f"ABX scoring, HIP-event ms per call: median [min .. max] over {args.windows} windows of >= {args.window_ms:g} ms, GPU variants alternated",
              "device: (filled in below)",
@@ -189,18 +224,25 @@ def main():
                 runs.append(1e3 * (time.perf_counter() - t0))
             host[mode] = runs
     lines[1] = f"device: {torch.cuda.get_device_name(0)}"
+    FUSED, INDEX, EDIT, TABLE = ("fused three-launch call", "indices (table gather + DTW, count)", "indices, edit metric",
+                                 "code table build (once per score)")
+    build, table, keep_table = table_call(book, dev)
+    build()
     for mode in ("within", "across"):
         pl = abx.plan(items, mode)
-        fused, dist, tw, keep = fused_call(frames, tokens, pl.blocks, dev)
+        fused, dist, tw, keep, held, common = fused_call(frames, tokens, pl.blocks, dev)
+        icall, idist, itw, ikeep = index_call(codes, table, tokens, pl.blocks, dev, 0)
+        ecall, edist, etw, ekeep = index_call(codes, table, tokens, pl.blocks, dev, 1)
         tcall = torch_call(frames, tokens, pl.blocks, dev)
-        fused()
+        fused(); icall(); ecall()
         torch.cuda.synchronize()
+        same = bool(torch.equal(dist.view(torch.int32), idist.view(torch.int32)) and torch.equal(tw, itw))
         want = np.concatenate([t.reshape(-1) for t in host_tw[mode]])
         got = tw.cpu().numpy()
         td, tout = tcall()
         ttw = torch.cat([o.reshape(-1) for o in tout]).cpu().numpy()
         flop = sum(lens[a] * lens[x] for b in pl.blocks for a in b.a for x in b.x) * D * 8
-        r = measure({"fused three-launch call": fused, "torch on the GPU (bmm + DP as torch ops)": lambda: tcall()},
+        r = measure({FUSED: fused, INDEX: icall, EDIT: ecall, TABLE: build, "torch on the GPU (bmm + DP as torch ops)": lambda: tcall()},
                     args.windows, args.window_ms)
         lines.append(f"\n{mode}: {len(pl.blocks)} blocks, {pl.n_pairs} pairs, {int(abx.aggregate(pl, got)['n_triples'])} triples, "
                      f"{flop / 1e9:.2f} GFLOP of frame distances")
@@ -209,11 +251,20 @@ def main():
         h = host[mode]
         lines.append(f"  {'float64 numpy restatement, ' + str(args.threads) + ' processes':44s} {statistics.median(h):10.1f} ms  [{min(h):.1f} .. {max(h):.1f}]  "
                      f"{len(h)} runs, wall time")
-        fm = r["fused three-launch call"][0]
+        fm = r[FUSED][0]
+        once = r[INDEX][0] + r[TABLE][0]
+        lines.append(f"  indices + one table build = {once:.4f} ms (medians) against the fused call's fastest window {r[FUSED][1]:.4f} ms: "
+                     f"{r[FUSED][1] / once:.2f}x; fused / indices = {fm / r[INDEX][0]:.2f}x, fused / edit = {fm / r[EDIT][0]:.2f}x")
+        lines.append(f"  indices against the fused call, dist and twice_wins bit for bit: {'equal' if same else 'DIFFERENT'}; "
+                     f"edit-metric score {abx.aggregate(pl, etw.cpu().numpy())['score']:.6f}")
+        ibytes = {"codes": codes.size * 4, "code table": table.numel() * 4, "normalised codebook": book.size * 4}
+        lines.append(f"  device bytes held: fused {sum(held.values())} (" + ", ".join(f"{k} {v}" for k, v in held.items()) + f"); indices "
+                     f"{sum(ibytes.values())} (" + ", ".join(f"{k} {v}" for k, v in ibytes.items()) + f"; edit: codes only); both: {common} "
+                     "of token / block tables, dist and twice_wins")
         lines.append(f"  torch / fused = {r['torch on the GPU (bmm + DP as torch ops)'][0] / fm:.1f}x, numpy / fused = {statistics.median(h) / fm:.0f}x")
         lines.append(f"  counts differing from float64: fused {int((got != want).sum())} of {want.size} (scores {abx.aggregate(pl, got)['score']:.6f} / "
                      f"{abx.aggregate(pl, want)['score']:.6f}), torch composition {int((ttw != want).sum())} (score {abx.aggregate(pl, ttw)['score']:.6f})")
-        del keep
+        del keep, ikeep, ekeep
     res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
                           os.path.join(ROOT, "vectorquantizedcpc_amd", "csrc", "abx.hip")], capture_output=True, text=True)
     lines.append("\nkernel resources (tools/kernel_resources.py vectorquantizedcpc_amd/csrc/abx.hip):")

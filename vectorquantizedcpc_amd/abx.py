@@ -6,8 +6,12 @@ The reference judges a checkpoint's units by an outside package: README 4-B "Run
 call (``csrc/abx.hip``), and the score as a mean over contexts, speakers and ordered phone pairs.  No equality with any outside
 tool is claimed.
 
-Pure-host parts (no GPU): ``read_items``, ``tokens_of``, ``plan``, ``aggregate``.  Device parts: ``pair_distances``, ``score``
-(no CPU fallback).
+The units are discrete, so the same protocol also takes them as codebook INDICES (``code_table``, ``pair_distances_indices``,
+``score_indices``): every frame distance of a call is one of ``M x M`` table entries with the bits the frames would give, or,
+with ``metric="edit"``, the tokens are compared by the Levenshtein distance of their index runs.
+
+Pure-host parts (no GPU): ``read_items``, ``tokens_of``, ``plan``, ``aggregate``.  Device parts: ``pair_distances``, ``score``,
+``code_table``, ``pair_distances_indices``, ``score_indices`` (no CPU fallback).
 """
 import ctypes as C
 from collections import namedtuple
@@ -23,6 +27,8 @@ A_TILE = 4                       # A tokens per workgroup of the DTW launch (csr
 # halved in rate by the encoder's Conv1d(k=4, s=2, p=1) (model.py:43)
 FRAME_SHIFT = 0.02
 FRAME_OFFSET = 0.01
+M_MAX = 4096                     # codebook rows of the index form (include/vqcpc.h)
+METRICS = {"angular": 0, "edit": 1}   # VQCPC_ABX_ANGULAR, VQCPC_ABX_EDIT
 
 Item = namedtuple("Item", "file onset offset phone prev next speaker")
 
@@ -270,28 +276,137 @@ def pair_distances(feats, tokens, blocks: Sequence[Block], want_cost: bool = Tru
         raise ValueError(f"abx: D = {D}, supported: a multiple of 4 in [4, 512]")
     if n_frames < 1:
         raise ValueError("abx: no frames")
-    tok, lists, segs, rows, wg, nd, no = _tables(tokens, blocks, n_frames)
-    lib = _lib.load()
-    dev = feats.device
     feats = feats.contiguous()
+    work = torch.empty(n_frames * D, dtype=torch.float32, device=feats.device)
+    lib = _lib.load()
+    return _enqueue(feats.device, tokens, blocks, n_frames, want_cost, (feats, work),
+                    lambda t, n, out, stream: lib.vqcpc_abx_score(feats.data_ptr(), n_frames, D, *t, *n, work.data_ptr(), *out, stream))
+
+
+def _enqueue(dev, tokens, blocks, n_frames, want_cost, borrowed, call) -> PairTables:
+    """What every pair call shares: ``_tables``, one upload of all four tables, the outputs, ``call(tables, counts, outputs,
+    stream)`` with the arguments in the C ABI's order, and ``record_stream`` on what the enqueued work borrows."""
+    import torch
+    tok, lists, segs, rows, wg, nd, no = _tables(tokens, blocks, n_frames)
     with _lib.device_guard(dev):
-        # one upload of all four tables
         flat = np.concatenate([tok.reshape(-1), lists, segs, rows.reshape(-1)])
         d = torch.from_numpy(flat).to(dev)
         o1 = tok.size; o2 = o1 + lists.size; o3 = o2 + segs.size
-        t_tok, t_lists, t_segs, t_rows = d[:o1], d[o1:o2], d[o2:o3], d[o3:]
-        work = torch.empty(n_frames * D, dtype=torch.float32, device=dev)
         cost = torch.empty(nd, dtype=torch.float32, device=dev) if want_cost else None
         plen = torch.empty(nd, dtype=torch.int32, device=dev) if want_cost else None
         dist = torch.empty(nd, dtype=torch.float32, device=dev)
         twice = torch.empty(no, dtype=torch.int32, device=dev)
-        _lib.check(lib.vqcpc_abx_score(feats.data_ptr(), n_frames, D, t_tok.data_ptr(), tok.shape[0], t_lists.data_ptr(), lists.size,
-                                       t_segs.data_ptr(), segs.size, t_rows.data_ptr(), rows.shape[0], wg, nd, no, work.data_ptr(),
-                                       cost.data_ptr() if want_cost else None, plen.data_ptr() if want_cost else None,
-                                       dist.data_ptr(), twice.data_ptr(), _lib.current_stream()))
-        for t in (feats, d, work):                       # borrowed until the enqueued work is done
-            t.record_stream(torch.cuda.current_stream())
+        t = (d[:o1].data_ptr(), tok.shape[0], d[o1:o2].data_ptr(), lists.size, d[o2:o3].data_ptr(), segs.size, d[o3:].data_ptr(), rows.shape[0])
+        out = (cost.data_ptr() if want_cost else None, plen.data_ptr() if want_cost else None, dist.data_ptr(), twice.data_ptr())
+        _lib.check(call(t, (wg, nd, no), out, _lib.current_stream()))
+        for b in borrowed + (d,):                        # borrowed until the enqueued work is done
+            b.record_stream(torch.cuda.current_stream())
     return PairTables(cost, plen, dist, twice, [int(r[6]) for r in rows], [int(r[7]) for r in rows])
+
+
+def code_table(codebook):
+    """``codebook`` (M, D) fp32 on the device -> the (M, M) device table of frame distances between its rows, each with the bits
+    ``pair_distances`` computes for that pair of frames (``vqcpc_abx_code_table``: two launches, no synchronisation)."""
+    import torch
+    if not isinstance(codebook, torch.Tensor):
+        raise TypeError("abx.code_table: codebook must be a torch tensor on the device")
+    _lib.require_cuda(codebook, "abx codebook")
+    if codebook.dim() != 2 or codebook.dtype != torch.float32:
+        raise ValueError(f"abx: codebook must be (M, D) float32, got {tuple(codebook.shape)} {codebook.dtype}")
+    M, D = int(codebook.shape[0]), int(codebook.shape[1])
+    if not 1 <= M <= M_MAX:
+        raise ValueError(f"abx: codebook of {M} rows, supported 1..{M_MAX}")
+    if D % 4 or not 4 <= D <= 512:
+        raise ValueError(f"abx: D = {D}, supported: a multiple of 4 in [4, 512]")
+    lib = _lib.load()
+    book = codebook.detach().contiguous()
+    n = C.c_uint64()
+    _lib.check(lib.vqcpc_abx_index_workspace_bytes(M, D, C.byref(n)))
+    with _lib.device_guard(book.device):
+        buf = torch.empty(n.value // 4, dtype=torch.float32, device=book.device)      # work (M, D), then the table
+        table = buf[M * D:].view(M, M)
+        _lib.check(lib.vqcpc_abx_code_table(book.data_ptr(), M, D, buf.data_ptr(), table.data_ptr(), _lib.current_stream()))
+        book.record_stream(torch.cuda.current_stream())
+    return table
+
+
+def _metric(metric):
+    if metric not in METRICS:
+        raise ValueError(f"abx: metric must be one of {sorted(METRICS)}, got {metric!r}")
+    return METRICS[metric]
+
+
+def pair_distances_indices(codes, tokens, blocks: Sequence[Block], table=None, n_codes=None, metric: str = "angular",
+                           want_cost: bool = True) -> PairTables:
+    """``pair_distances`` on runs of codebook indices: ``codes`` (n_frames,) integer device tensor, ``tokens`` rows of it.
+    ``metric="angular"``: ``table`` = ``code_table(codebook)``; every output has the bits ``pair_distances(codebook[codes], ..)``
+    gives.  ``metric="edit"``: Levenshtein distance of the raw runs, ``cost`` = the distance, ``path_len`` = max(Ta, Tb),
+    ``dist`` = cost / path_len; no table is needed, ``n_codes`` (default: the table's M) bounds the codes.  Does not
+    synchronise, so codes outside [0, n_codes) are clamped on the device, not reported (``score_indices`` checks them)."""
+    import torch
+    m = _metric(metric)
+    if not isinstance(codes, torch.Tensor):
+        raise TypeError("abx.pair_distances_indices: codes must be a torch tensor on the device")
+    _lib.require_cuda(codes, "abx codes")
+    if codes.dim() != 1 or codes.dtype.is_floating_point or codes.dtype.is_complex or codes.dtype == torch.bool:
+        raise ValueError(f"abx: codes must be a 1-D integer tensor, got {tuple(codes.shape)} {codes.dtype}")
+    if table is not None:
+        _lib.require_cuda(table, "abx code table")
+        _lib.require_same_device(table, codes, "the code table")
+        if table.dim() != 2 or table.shape[0] != table.shape[1] or table.dtype != torch.float32 or not table.is_contiguous():
+            raise ValueError(f"abx: table must be a contiguous (M, M) float32 tensor, got {tuple(table.shape)} {table.dtype}")
+        if n_codes is not None and int(n_codes) != table.shape[0]:
+            raise ValueError(f"abx: n_codes = {n_codes}, but the table has {table.shape[0]} rows")
+        n_codes = int(table.shape[0])
+    elif m == METRICS["angular"]:
+        raise ValueError("abx: metric 'angular' needs table = code_table(codebook)")
+    elif n_codes is None:
+        raise ValueError("abx: give n_codes (or a table) with metric 'edit'")
+    M = int(n_codes)
+    if not 1 <= M <= M_MAX:
+        raise ValueError(f"abx: n_codes = {M}, supported 1..{M_MAX}")
+    n_frames = int(codes.shape[0])
+    if n_frames < 1:
+        raise ValueError("abx: no frames")
+    codes = codes.to(torch.int32).contiguous()
+    tab = table if m == METRICS["angular"] else None
+    lib = _lib.load()
+    return _enqueue(codes.device, tokens, blocks, n_frames, want_cost, (codes,) + ((tab,) if tab is not None else ()),
+                    lambda t, n, out, stream: lib.vqcpc_abx_score_indices(tab.data_ptr() if tab is not None else None, M, codes.data_ptr(),
+                                                                          n_frames, *t, *n, *out, stream, m))
+
+
+def _layout(by_file, items, frame_shift, frame_offset, what):
+    """The files the items name, in order, checked to be device tensors, and the items' tokens as rows of their concatenation."""
+    import torch
+    files = sorted({it.file for it in items})
+    for f in files:
+        if f not in by_file:
+            raise KeyError(f"abx.score: no {what} for file {f!r}")
+        t = by_file[f]
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"abx.score: {what} of {f!r} must be a torch tensor on the device")
+        _lib.require_cuda(t, f"abx {what} of {f!r}")
+    first, rows = {}, 0
+    for f in files:
+        first[f] = rows
+        rows += int(by_file[f].shape[0])
+    tok = tokens_of(items, {f: int(by_file[f].shape[0]) for f in files}, frame_shift, frame_offset)
+    return files, [(first[it.file] + lo, n) for it, (lo, n) in zip(items, tok)]
+
+
+def _score_chunks(items, mode, mem_budget_bytes, prepare):
+    """plan -> chunks of blocks -> ``run = prepare()`` once, ``run(blocks)`` -> twice_wins per chunk -> ``aggregate``."""
+    import torch
+    pl = plan(items, mode)
+    res_tw = np.zeros(pl.n_out, np.int32)
+    chunks = block_chunks(pl.blocks, mem_budget_bytes) if pl.blocks else []
+    if chunks:
+        run = prepare()
+        res_tw = torch.cat([run([pl.blocks[i] for i in ids]) for ids in chunks]).cpu().numpy()
+    res = aggregate(pl, res_tw)
+    res.update(twice_wins=res_tw, n_blocks=len(pl.blocks), n_chunks=len(chunks), mode=mode)
+    return res
 
 
 def score(features_by_file, items, mode: str = "within", frame_shift: float = FRAME_SHIFT, frame_offset: float = FRAME_OFFSET,
@@ -303,27 +418,50 @@ def score(features_by_file, items, mode: str = "within", frame_shift: float = FR
     import torch
     if not isinstance(items, (list, tuple)):
         items = read_items(items)
-    files = sorted({it.file for it in items})
-    for f in files:
-        if f not in features_by_file:
-            raise KeyError(f"abx.score: no features for file {f!r}")
-        t = features_by_file[f]
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"abx.score: features of {f!r} must be a torch tensor on the device")
-        _lib.require_cuda(t, f"abx features of {f!r}")
-    first, rows = {}, 0
-    for f in files:
-        first[f] = rows
-        rows += int(features_by_file[f].shape[0])
-    tok = tokens_of(items, {f: int(features_by_file[f].shape[0]) for f in files}, frame_shift, frame_offset)
-    tokens = [(first[it.file] + lo, n) for it, (lo, n) in zip(items, tok)]
-    pl = plan(items, mode)
-    res_tw = np.zeros(pl.n_out, np.int32)
-    chunks = block_chunks(pl.blocks, mem_budget_bytes) if pl.blocks else []
-    if chunks:
+    files, tokens = _layout(features_by_file, items, frame_shift, frame_offset, "features")
+
+    def prepare():
         feats = torch.cat([features_by_file[f].to(torch.float32) for f in files], dim=0).contiguous()
-        parts = [pair_distances(feats, tokens, [pl.blocks[i] for i in ids], want_cost=False).twice_wins for ids in chunks]
-        res_tw = torch.cat(parts).cpu().numpy()
-    res = aggregate(pl, res_tw)
-    res.update(twice_wins=res_tw, n_blocks=len(pl.blocks), n_chunks=len(chunks), mode=mode)
+        return lambda blocks: pair_distances(feats, tokens, blocks, want_cost=False).twice_wins
+    return _score_chunks(items, mode, mem_budget_bytes, prepare)
+
+
+def score_indices(codebook, indices_by_file, items, mode: str = "within", metric: str = "angular", frame_shift: float = FRAME_SHIFT,
+                  frame_offset: float = FRAME_OFFSET, mem_budget_bytes: int = 1 << 30) -> dict:
+    """``score`` on the units' indices: ``indices_by_file`` (file -> (T,) integer device tensor), ``codebook`` (M, D) fp32 on the
+    device.  ``metric="angular"``: the counts, and so the score, are those of ``score`` on ``codebook[indices]``, bit for bit;
+    the device holds 4 bytes per frame and one (M, M) table, built once per call.  ``metric="edit"``: tokens are compared by the
+    Levenshtein distance of their index runs over the longer run's length; ``codebook`` may be None (the number of codes is
+    then the largest index + 1).  An index outside [0, M) raises IndexError naming the file before anything is scored.  The
+    result gains ``metric``."""
+    import torch
+    m = _metric(metric)
+    if not isinstance(items, (list, tuple)):
+        items = read_items(items)
+    files, tokens = _layout(indices_by_file, items, frame_shift, frame_offset, "indices")
+    for f in files:
+        t = indices_by_file[f]
+        if t.dim() != 1 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError(f"abx.score_indices: indices of {f!r} must be a 1-D integer tensor, got {tuple(t.shape)} {t.dtype}")
+    if codebook is None and m == METRICS["angular"]:
+        raise ValueError("abx.score_indices: metric 'angular' needs the codebook")
+    if codebook is not None:
+        if not isinstance(codebook, torch.Tensor):
+            raise TypeError("abx.score_indices: codebook must be a torch tensor on the device")
+        _lib.require_cuda(codebook, "abx codebook")
+
+    def prepare():
+        codes = torch.cat([indices_by_file[f].to(torch.int64) for f in files])
+        lo, hi = torch.stack([codes.min(), codes.max()]).tolist()                     # the one range check, on the device
+        M = int(codebook.shape[0]) if codebook is not None else max(hi, 0) + 1
+        if lo < 0 or hi >= M:
+            for f in files:
+                t = indices_by_file[f]
+                if t.numel() and (int(t.min()) < 0 or int(t.max()) >= M):
+                    raise IndexError(f"abx.score_indices: file {f!r} holds an index outside [0, {M}): {int(t.min())}..{int(t.max())}")
+        table = code_table(codebook) if m == METRICS["angular"] else None
+        codes = codes.to(torch.int32)
+        return lambda blocks: pair_distances_indices(codes, tokens, blocks, table=table, n_codes=M, metric=metric, want_cost=False).twice_wins
+    res = _score_chunks(items, mode, mem_budget_bytes, prepare)
+    res["metric"] = metric
     return res

@@ -14,11 +14,14 @@
 
     python -m vectorquantizedcpc_amd.cli abx     --items FILE --mode within|across [--frame-shift 0.02 --frame-offset 0.01]
                                                  --features DIR | --dataset datasets/2019/english
-                                                                  [--cpc-checkpoint ckpt.pt | --random-init] [--feature z|c]
+                                                                  [--cpc-checkpoint ckpt.pt | --random-init]
+                                                                  [--feature z|c|indices] [--metric angular|edit]
 
 ``abx`` stands in for the outside "ABX evaluation script" of the reference's README 4-B (own protocol, ``abx.py``): the ABX
 error rate of the units on an items file (``file onset offset phone prev next speaker`` per line), from the ``.txt`` frames
-``encode`` wrote (``--features``) or straight from the mels of ``test.json`` (``--dataset``, ``driver.score_abx``).
+``encode`` wrote (``--features``) or straight from the mels of ``test.json`` (``--dataset``, ``driver.score_abx``);
+``--feature indices`` scores the units as codebook indices (the numbers of ``z`` from a distance table, or ``--metric edit``:
+the edit distance between index runs).
 ``score-vocoder`` is the validation number the reference's vocoder training never computes (``vocoder.py:68-94``): the
 teacher-forced cross-entropy of ``vocoder.py:62-63`` on ``<in_dir>/<utterance>.wav`` of every entry of ``test.json``, speaker id
 from ``speakers.json`` by the file name's prefix: loss in nats per sample, bits per sample and top-1 accuracy
@@ -140,8 +143,9 @@ def score_vocoder_dataset(args) -> int:
 
 
 def abx_line(r) -> str:
+    metric = r.get("metric", "angular")
     return (f"abx {r['mode']}: error rate {r['error_rate']:.4f} % over {r['n_triples']} triples, {r['n_pairs']} pairs, "
-            f"{r['n_blocks']} blocks")
+            f"{r['n_blocks']} blocks" + ("" if metric == "angular" else f", metric {metric}"))
 
 
 def abx_dataset(args) -> int:
@@ -155,7 +159,7 @@ def abx_dataset(args) -> int:
         enc, _ = _models(args, need_vocoder=False)
         mels = {p.stem: io.load_mel(p) for p in io.read_test_metadata(args.dataset)}
         r = driver.score_abx(enc, mels, items, feature=args.feature, mode=args.mode, frame_shift=args.frame_shift,
-                             frame_offset=args.frame_offset, max_batch=args.max_batch)
+                             frame_offset=args.frame_offset, max_batch=args.max_batch, metric=args.metric)
     if r["n_triples"] == 0:
         print(f"abx {args.mode}: no (A, B, X) triple could be formed from {len(items)} items")
         return 1
@@ -259,7 +263,8 @@ def main(argv=None) -> int:
     p.add_argument("--dataset", help="datasets/<name> directory (test.json): encode its mels in-process")
     p.add_argument("--cpc-checkpoint", "--checkpoint", dest="cpc_checkpoint")
     p.add_argument("--random-init", action="store_true")
-    p.add_argument("--feature", choices=("z", "c"), default="z")
+    p.add_argument("--feature", choices=("z", "c", "indices"), default="z")
+    p.add_argument("--metric", choices=("angular", "edit"), default="angular", help="edit: Levenshtein distance between index runs (--feature indices)")
     p.add_argument("--device", default="cuda")
     p.add_argument("--max-batch", type=int, default=64)
     args = ap.parse_args(argv)
@@ -268,6 +273,10 @@ def main(argv=None) -> int:
             ap.error("abx: give --features DIR or --dataset DIR")
         if args.dataset and not args.random_init and not args.cpc_checkpoint:
             ap.error("abx --dataset: give --cpc-checkpoint or --random-init")
+        if args.features and args.feature == "indices":
+            ap.error("abx --feature indices needs --dataset: `encode` writes frames, not indices")
+        if args.metric != "angular" and args.feature != "indices":
+            ap.error(f"abx --metric {args.metric} needs --feature indices")
         return abx_dataset(args)
     if not args.random_init and not args.cpc_checkpoint:
         ap.error("give --cpc-checkpoint (and --vocoder-checkpoint for convert) or --random-init")

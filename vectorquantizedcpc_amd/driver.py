@@ -334,20 +334,30 @@ def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, spea
 # ---------------------------------------------------------------------------------------- ABX scoring
 @torch.no_grad()
 def score_abx(encoder: Encoder, mels_by_file, items, feature: str = "z", mode: str = "within", frame_shift: float = None,
-              frame_offset: float = None, max_batch: int = 64, max_pad_frac: float = 0.25, mem_budget_bytes: int = 1 << 30):
+              frame_offset: float = None, max_batch: int = 64, max_pad_frac: float = 0.25, mem_budget_bytes: int = 1 << 30,
+              metric: str = "angular"):
     """encode -> ABX in one process, without the text files of ``encode.py:48-52`` and the outside script of the reference's
     README 4-B (own protocol: ``abx.py``).  ``mels_by_file``: file name (as the items file names it) -> (80, T)
-    mel; ``items``: a path or a list of ``abx.Item``; ``feature``: "z" (the quantised units) or "c" (the context).  The
+    mel; ``items``: a path or a list of ``abx.Item``; ``feature``: "z" (the quantised units), "c" (the context) or "indices"
+    (the units as codebook indices: ``abx.score_indices`` with the encoder's codebook -- with ``metric="angular"`` the counts of
+    "z", from 4 bytes per frame and one table; ``metric="edit"``: the edit distance between index runs, "indices" only).  The
     utterances go through ``encode_utterances`` and ``encoder.check()`` before anything is scored.  Returns ``abx.score``'s
     dict."""
     from . import abx
-    if feature not in ("z", "c"):
-        raise ValueError(f"score_abx: feature must be 'z' or 'c', got {feature!r}")
+    if feature not in ("z", "c", "indices"):
+        raise ValueError(f"score_abx: feature must be 'z', 'c' or 'indices', got {feature!r}")
+    if metric not in abx.METRICS:
+        raise ValueError(f"score_abx: metric must be one of {sorted(abx.METRICS)}, got {metric!r}")
+    if metric != "angular" and feature != "indices":
+        raise ValueError(f"score_abx: metric {metric!r} is defined on feature 'indices', not on {feature!r}")
     files = sorted(mels_by_file)
     enc = encode_utterances(encoder, [mels_by_file[f] for f in files], want_context=feature == "c", max_batch=max_batch,
                             max_pad_frac=max_pad_frac)
     if hasattr(encoder, "check"):
         encoder.check()                              # nothing incomplete may be scored
     feats = {f: r[feature] for f, r in zip(files, enc)}
-    return abx.score(feats, items, mode=mode, frame_shift=abx.FRAME_SHIFT if frame_shift is None else frame_shift,
-                     frame_offset=abx.FRAME_OFFSET if frame_offset is None else frame_offset, mem_budget_bytes=mem_budget_bytes)
+    kw = dict(mode=mode, frame_shift=abx.FRAME_SHIFT if frame_shift is None else frame_shift,
+              frame_offset=abx.FRAME_OFFSET if frame_offset is None else frame_offset, mem_budget_bytes=mem_budget_bytes)
+    if feature == "indices":
+        return abx.score_indices(encoder.codebook.embedding, feats, items, metric=metric, **kw)
+    return abx.score(feats, items, **kw)
