@@ -138,6 +138,32 @@ int vqcpc_encoder_forward_stats(vqcpc_encoder *enc, const float *z_pre, const fl
                                 const int64_t *idx, int n_rows, float *z_st, float *loss,
                                 float *perplexity, void *stream);
 
+/* Replaces the training branch of VQEmbeddingEMA.forward (model.py:117-155 with the EMA update of
+ * model.py:136-145): no gradient, a forward pass plus the moving average over the three buffers.
+ * x DEVICE (n_rows, z_dim) fp32 rows, 16-byte aligned.  idx (n_rows int64), z_st = x + (q - x) (both DEVICE, or NULL),
+ * loss and perplexity (DEVICE scalars) come from the OLD codebook, exactly as vqcpc_encoder_vq_encode +
+ * vqcpc_encoder_forward_stats give them.  Then, every step a separately rounded fp32 operation:
+ *   count = (float)decay * ema_count + (float)(1.0 - decay) * hist;  n = sum(count);
+ *   ema_count = (count + (float)epsilon) / (n + (float)(n_embeddings * epsilon)) * n;
+ *   ema_weight = (float)decay * ema_weight + (float)(1.0 - decay) * dw,  dw[m] = sum of the rows x[r] with idx[r] == m
+ *   (64-row chunks in ascending row order, chunk partials combined by the adjacent-pair tree);
+ *   embedding = ema_weight / ema_count[:, None].
+ * embedding (n_embeddings, z_dim), ema_count (n_embeddings), ema_weight (n_embeddings, z_dim): DEVICE fp32, updated in
+ * place; embedding must hold, on entry, what the handle was created from.  On return (in stream order) embedding AND the
+ * handle's own codebook copy, |e|^2 and search fragments hold the new values: the handle equals one created from the new
+ * buffers.  No synchronisation.  VQCPC_ERR_INVALID before anything is enqueued for a NULL argument, n_rows outside
+ * [1, 2^24] (the histogram must be exact in fp32), decay outside (0, 1) or epsilon <= 0.
+ * The work space (quantised rows, indices, counts, histogram) belongs to the handle and is shared by its calls: like every
+ * other entry of a handle, one handle serves ONE stream at a time -- two calls on different streams need an event between
+ * them or a handle each. */
+int vqcpc_encoder_vq_adapt(vqcpc_encoder *enc, const float *x, int n_rows, double decay, double epsilon,
+                           float *embedding, float *ema_count, float *ema_weight,
+                           float *z_st, int64_t *idx, float *loss, float *perplexity, void *stream);
+
+/* Device memory the handle's grow-only work buffers hold at the moment (front-end activations, statistics, the work space
+ * of vqcpc_encoder_vq_adapt: the peak of the calls so far; the weights are not counted). */
+int vqcpc_encoder_workspace_bytes(vqcpc_encoder *enc, uint64_t *bytes);
+
 /* After the caller has synchronised the stream that carried vqcpc_encoder_encode / _context: did the resident context
  * scan of that call (persistent_context) give up on an in-kernel exchange?  VQCPC_OK, or VQCPC_ERR_HIP: the context `c`
  * of that call is incomplete, the handle now runs one launch per time step, and the call should be repeated.  Reads a

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libvqcpc_hip.so")
 SYMBOLS = [
     "vqcpc_abi_version", "vqcpc_last_error", "vqcpc_device_count",
     "vqcpc_encoder_create", "vqcpc_encoder_destroy", "vqcpc_encoder_encode",
-    "vqcpc_encoder_forward_stats", "vqcpc_encoder_context", "vqcpc_encoder_stage", "vqcpc_encoder_vq_encode", "vqcpc_encoder_set_option", "vqcpc_encoder_last_schedule",
+    "vqcpc_encoder_forward_stats", "vqcpc_encoder_context", "vqcpc_encoder_stage", "vqcpc_encoder_vq_encode", "vqcpc_encoder_vq_adapt", "vqcpc_encoder_workspace_bytes", "vqcpc_encoder_set_option", "vqcpc_encoder_last_schedule",
     "vqcpc_cpc_create", "vqcpc_cpc_destroy", "vqcpc_cpc_score",
     "vqcpc_abx_workspace_bytes", "vqcpc_abx_score", "vqcpc_abx_index_workspace_bytes", "vqcpc_abx_code_table", "vqcpc_abx_score_indices",
     "vqcpc_encoder_check", "vqcpc_vocoder_check", "vqcpc_vocoder_last_path", "vqcpc_vocoder_last_slots", "vqcpc_vocoder_workspace_bytes", "vqcpc_vocoder_plan",
@@ -87,6 +87,8 @@ def load():
     lib.vqcpc_encoder_context.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.vqcpc_encoder_stage.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     lib.vqcpc_encoder_vq_encode.argtypes = [vp, vp, i32, vp, i64p, vp]
+    lib.vqcpc_encoder_vq_adapt.argtypes = [vp, vp, i32, C.c_double, C.c_double, vp, vp, vp, vp, i64p, vp, vp, vp]
+    lib.vqcpc_encoder_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.vqcpc_encoder_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.vqcpc_encoder_check.argtypes = [vp]
     lib.vqcpc_encoder_last_schedule.argtypes = [vp]

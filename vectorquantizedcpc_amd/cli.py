@@ -17,6 +17,12 @@
                                                                   [--cpc-checkpoint ckpt.pt | --random-init]
                                                                   [--feature z|c|indices] [--metric angular|edit]
 
+    python -m vectorquantizedcpc_amd.cli adapt-codebook --dataset datasets/2019/english --cpc-checkpoint in.pt | --random-init
+                                                 --out-checkpoint out.pt [--epochs 1]
+
+``adapt-codebook`` fits a checkpoint's codebook to the mels of ``test.json`` with the EMA update of ``model.py:136-145`` (no
+gradient: ``driver.adapt_codebook``), prints loss, perplexity and codes in use per epoch and writes a checkpoint whose
+``"encoder"`` entry has the reference's keys: ``encode``, ``abx`` and ``score`` run on it as on any other.
 ``abx`` stands in for the outside "ABX evaluation script" of the reference's README 4-B (own protocol, ``abx.py``): the ABX
 error rate of the units on an items file (``file onset offset phone prev next speaker`` per line), from the ``.txt`` frames
 ``encode`` wrote (``--features``) or straight from the mels of ``test.json`` (``--dataset``, ``driver.score_abx``);
@@ -142,6 +148,19 @@ def score_vocoder_dataset(args) -> int:
     return 0
 
 
+def adapt_codebook_dataset(args) -> int:
+    paths = io.read_test_metadata(args.dataset)
+    enc, _ = _models(args, need_vocoder=False)
+    r = driver.adapt_codebook(enc, [io.load_mel(p) for p in paths], epochs=args.epochs, max_batch=args.max_batch)
+    for e, (loss, ppl, used) in enumerate(zip(r["loss"], r["perplexity"], r["codes_in_use"])):
+        w = r["rows"]                                          # batch means weighted by their rows
+        print(f"epoch {e + 1}: vq loss:{sum(l * n for l, n in zip(loss, w)) / sum(w):.2E}, "
+              f"perpexlity:{sum(q * n for q, n in zip(ppl, w)) / sum(w):.3f}, codes in use:{used}/{enc.conf.n_embeddings}")
+    io.save_adapted_checkpoint(args.out_checkpoint, enc.state_dict(), None if args.random_init else args.cpc_checkpoint)
+    print(f"adapted the codebook on {len(paths)} utterances ({sum(r['rows'])} frames) x {args.epochs} epochs -> {args.out_checkpoint}")
+    return 0
+
+
 def abx_line(r) -> str:
     metric = r.get("metric", "angular")
     return (f"abx {r['mode']}: error rate {r['error_rate']:.4f} % over {r['n_triples']} triples, {r['n_pairs']} pairs, "
@@ -227,7 +246,7 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert", "score", "score-vocoder"):
+    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
         if name in ("encode", "convert"):
@@ -245,6 +264,9 @@ def main(argv=None) -> int:
             p.add_argument("--seed", type=int, default=synth.SEED)
         elif name == "encode":
             p.add_argument("--save-auxiliary", action="store_true")
+        elif name == "adapt-codebook":
+            p.add_argument("--out-checkpoint", required=True)
+            p.add_argument("--epochs", type=int, default=1)
         elif name == "score-vocoder":
             p.add_argument("--vocoder-checkpoint")
             p.add_argument("--in-dir", required=True, help="directory of <utterance>.wav files")
@@ -283,7 +305,7 @@ def main(argv=None) -> int:
     if args.cmd == "score-vocoder" and not args.random_init and not args.vocoder_checkpoint:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,
-            "score-vocoder": score_vocoder_dataset}[args.cmd](args)
+            "score-vocoder": score_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -788,11 +788,11 @@ void launch_vq_stats(const float *x, const float *q, const int64_t *idx, int n_r
 void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C) {
     hipLaunchKernelGGL(conv_weight_permute_kernel, dim3((unsigned)(((size_t)O * C * 4 + 255) / 256)), dim3(256), 0, 0, w, w1, w2, O, C);
 }
-void launch_rowsumsq64(const float *X, float *out, int n) {
-    hipLaunchKernelGGL(rowsumsq64_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, X, out, n);
+void launch_rowsumsq64(const float *X, float *out, int n, hipStream_t s) {
+    hipLaunchKernelGGL(rowsumsq64_kernel, dim3((n + 63) / 64), dim3(64), 0, s, X, out, n);
 }
-void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb) {
-    hipLaunchKernelGGL(vq_build_frag_kernel, dim3((n_emb * 16 + 255) / 256), dim3(256), 0, 0, E, Ef, n_emb);
+void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb, hipStream_t s) {
+    hipLaunchKernelGGL(vq_build_frag_kernel, dim3((n_emb * 16 + 255) / 256), dim3(256), 0, s, E, Ef, n_emb);
 }
 void launch_frag16_build(const float *W, int N, int K, float4 *Wf) {
     const size_t n4 = (size_t)(N / 16) * (K / 16) * 64;

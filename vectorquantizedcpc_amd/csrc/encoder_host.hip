@@ -16,6 +16,7 @@ struct vqcpc_encoder {
     LnConst lnc;
     DevPtr<float> bufA, bufB, zpre;
     DevPtr<char> stats;
+    DevPtr<char> adapt;                  // work space of vqcpc_encoder_vq_adapt, grown on demand: q, idx, 16-bit idx, counts
     // fused and column-split schedules: weights in 16x16x4 fragment order (only when 4 * in_channels <= 512, the width of
     // their activation tile), and the model's half of their kernel argument
     DevPtr<float4> conv_f[2], fc_f[4], out_f;
@@ -269,5 +270,57 @@ extern "C" int vqcpc_encoder_forward_stats(vqcpc_encoder *e, const float *z_pre,
     HIP_TRY(hipMemsetAsync(hist, 0, hist_bytes, s));
     launch_vq_stats(z_pre, z_q, idx, n_rows, z_st, part, nblk, hist, e->n_emb, loss, perplexity, s);
     HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+// Bytes of the adapt work space for n_rows rows: quantised rows, int64 indices (when the caller keeps none), 16-bit indices,
+// counts -- each part 16-byte aligned.
+static size_t adapt_offsets(int n_rows, int n_emb, size_t (&off)[4]) {
+    const size_t sz[4] = {(size_t)n_rows * 64 * sizeof(float), (size_t)n_rows * sizeof(int64_t), (size_t)n_rows * sizeof(uint16_t),
+                          (size_t)n_emb * sizeof(float)};
+    size_t at = 0;
+    for (int i = 0; i < 4; ++i) { off[i] = at; at += (sz[i] + 15) / 16 * 16; }
+    return at;
+}
+
+extern "C" int vqcpc_encoder_vq_adapt(vqcpc_encoder *e, const float *x, int n_rows, double decay, double epsilon,
+                                      float *embedding, float *ema_count, float *ema_weight,
+                                      float *z_st, int64_t *idx, float *loss, float *perplexity, void *stream) {
+    VQ_REQUIRE(e && x && embedding && ema_count && ema_weight && loss && perplexity, "vqcpc_encoder_vq_adapt: null argument");
+    VQ_REQUIRE(n_rows >= 1 && n_rows <= (1 << 24), "vqcpc_encoder_vq_adapt: n_rows must be in [1, 2^24] (got %d)", n_rows);
+    VQ_REQUIRE(decay > 0.0 && decay < 1.0, "vqcpc_encoder_vq_adapt: decay must be in (0, 1) (got %g)", decay);
+    VQ_REQUIRE(epsilon > 0.0, "vqcpc_encoder_vq_adapt: epsilon must be > 0 (got %g)", epsilon);
+    VQ_REQUIRE(((uintptr_t)x & 15) == 0, "vqcpc_encoder_vq_adapt: rows must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    size_t off[4];
+    TRY(e->adapt.reserve(adapt_offsets(n_rows, e->n_emb, off)));
+    float *q = (float *)(e->adapt + off[0]);
+    int64_t *ix = idx ? idx : (int64_t *)(e->adapt + off[1]);
+    uint16_t *idx16 = (uint16_t *)(e->adapt + off[2]);
+    float *cnt = (float *)(e->adapt + off[3]);
+
+    // the eval forward from the OLD codebook (model.py:126-134, :147-153); its integer histogram stays in e->stats
+    launch_vq_encode(x, n_rows, e->cbfrag, e->codebook, e->e2, e->n_emb, ix, q, s);
+    HIP_TRY(hipGetLastError());
+    TRY(vqcpc_encoder_forward_stats(e, x, q, ix, n_rows, z_st, loss, perplexity, stream));
+
+    // the update (model.py:136-145)
+    EmaP p{};
+    p.x = x; p.idx16 = idx16; p.n_rows = n_rows; p.cnt = cnt; p.n_emb = e->n_emb;
+    p.decay = (float)decay; p.omd = (float)(1.0 - decay);              // 1 - decay in double, as Python forms it
+    p.eps = (float)epsilon; p.meps = (float)((double)e->n_emb * epsilon);
+    p.ema_count = ema_count; p.ema_weight = ema_weight; p.embedding = embedding; p.codebook = e->codebook;
+    launch_ema_prep(ix, n_rows, e->stats.as<unsigned>(), ema_count, e->n_emb, p.decay, p.omd, idx16, cnt, s);
+    launch_ema_update(p, s);
+    // the handle follows: |e|^2 and the search fragments as create builds them
+    launch_rowsumsq64(e->codebook, e->e2, e->n_emb, s);
+    launch_vq_build_frag(e->codebook, e->cbfrag, e->n_emb, s);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_workspace_bytes(vqcpc_encoder *e, uint64_t *bytes) {
+    VQ_REQUIRE(e && bytes, "vqcpc_encoder_workspace_bytes: null argument");
+    *bytes = (uint64_t)(e->bufA.cap + e->bufB.cap + e->zpre.cap + e->stats.cap + e->adapt.cap);
     return VQCPC_OK;
 }

@@ -56,6 +56,21 @@ void launch_vq_stats(const float *x, const float *q, const int64_t *idx, int n_r
                      int n_emb, float *loss, float *ppl, hipStream_t s);
 // Weight arrangement at create (default stream).
 void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C);   // conv.weight (O, C, 4) -> (O, 4 C) in the k order of mode 1, 2
-void launch_rowsumsq64(const float *X, float *out, int n);
-void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb);
+void launch_rowsumsq64(const float *X, float *out, int n, hipStream_t s = 0);          // also after a codebook update, on its stream
+void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb, hipStream_t s = 0);
 void launch_frag16_build(const float *W, int N, int K, float4 *Wf);                     // N % 16 == 0, K % 64 == 0: (N / 16) (K / 16) 64 float4
+
+// ------------------------------------------------------------------------------------------
+// launches of codebook.hip: the EMA update of VQEmbeddingEMA.forward in training mode (model.py:136-145)
+// ------------------------------------------------------------------------------------------
+// idx16 [n_rows] = idx narrowed; cnt [n_emb] = decay * ema_count + omd * hist (hist: what launch_vq_stats counted).
+void launch_ema_prep(const int64_t *idx, int n_rows, const unsigned *hist, const float *ema_count, int n_emb, float decay, float omd,
+                     uint16_t *idx16, float *cnt, hipStream_t s);
+struct EmaP {
+    const float *x; const uint16_t *idx16; int n_rows;        // rows (n_rows, 64) and their codes
+    const float *cnt; int n_emb;                              // launch_ema_prep's counts
+    float decay, omd, eps, meps;                              // (float)decay, (float)(1.0 - decay), (float)epsilon, (float)(n_emb * epsilon)
+    float *ema_count, *ema_weight, *embedding;                // the module's buffers, updated in place
+    float *codebook;                                          // the handle's copy of embedding
+};
+void launch_ema_update(const EmaP &p, hipStream_t s);

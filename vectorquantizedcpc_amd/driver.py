@@ -86,6 +86,35 @@ def encode_utterances(encoder: Encoder, mels: Sequence[torch.Tensor], want_conte
 
 
 @torch.no_grad()
+def adapt_codebook(encoder: Encoder, mels: Sequence[torch.Tensor], epochs: int = 1, max_batch: int = 64,
+                   max_pad_frac: float = 0.25):
+    """Fit the encoder's codebook to a corpus: ``Encoder.adapt_codebook`` (front end + the EMA update of ``model.py:136-145``,
+    no gradient) over the length buckets of ``encode_utterances``, ``epochs`` times, in a fixed order -- buckets by
+    (conv mode, length), the same every epoch -- so a run is reproducible.  Padding rows take no part (``n_frames``).  Returns
+    ``{"loss": [[...] per epoch], "perplexity": ..., "rows": rows per batch, "codes_in_use": per epoch}``: loss / perplexity of
+    every batch under the codebook as it was before that batch; ``codes_in_use`` = the distinct codes the rows of that epoch
+    were assigned to, from the indices of the update calls themselves (``ema_count`` cannot tell: a code no row reaches settles
+    at epsilon / (1 - decay), not at zero).  Everything is read back once at the end."""
+    dev = next(encoder.parameters()).device
+    C = encoder.conf.in_channels
+    lengths = [int(m.shape[-1]) for m in mels]
+    modes = [batch1_conv_mode(C, t) for t in lengths]
+    buckets = make_buckets(lengths, modes, max_batch, max_pad_frac)
+    batches = [(_pad_batch([mels[i] for i in ids], dev), [out_frames(lengths[i]) for i in ids], modes[ids[0]]) for ids in buckets]
+    n_epochs = int(epochs)
+    stats = torch.zeros(n_epochs, len(batches), 2, device=dev)
+    hit = torch.zeros(n_epochs, encoder.conf.n_embeddings, dtype=torch.bool, device=dev)
+    for e in range(n_epochs):
+        for k, (batch, n_frames, mode) in enumerate(batches):
+            loss, ppl, idx = encoder.adapt_codebook(batch, n_frames, conv_mode=mode, return_indices=True)
+            stats[e, k, 0], stats[e, k, 1] = loss, ppl
+            hit[e, idx] = True
+    host, used = stats.cpu(), hit.sum(dim=1).cpu()
+    return {"loss": host[..., 0].tolist(), "perplexity": host[..., 1].tolist(), "rows": [sum(n) for _, n, _ in batches],
+            "codes_in_use": [int(u) for u in used]}
+
+
+@torch.no_grad()
 def convert_utterances(encoder: Encoder, vocoder: Vocoder, mels: Sequence[torch.Tensor], speakers: Sequence[int],
                        seed: int, utt_ids: Optional[Sequence[int]] = None, max_batch: int = 64,
                        max_pad_frac: float = 0.25, slots: int = 0, clock=None,

@@ -81,6 +81,19 @@ def load_encoder_checkpoint(path) -> Dict[str, torch.Tensor]:
     return ck["encoder"] if "encoder" in ck else ck
 
 
+def save_adapted_checkpoint(path, encoder_state: Dict[str, torch.Tensor], source=None):
+    """Write ``{"encoder": state_dict}`` with the reference's keys (``train_cpc.py:23-29``), every tensor on the CPU; the other
+    entries of the checkpoint ``source`` was loaded from (``"cpc"``, ...) are carried over unchanged, so ``score`` still finds
+    its predictors.  ``encode``, ``abx`` and ``score`` read the result like any checkpoint."""
+    ck = {}
+    if source is not None:
+        old = torch.load(source, map_location="cpu", weights_only=True)
+        if "encoder" in old:
+            ck = {k: v for k, v in old.items() if k != "encoder"}
+    ck["encoder"] = {k: v.detach().cpu().clone() for k, v in encoder_state.items()}
+    torch.save(ck, path)
+
+
 def load_cpc_checkpoint(path) -> Dict[str, torch.Tensor]:
     """``checkpoint["cpc"]`` (``train_cpc.py:23-29`` saves it next to ``"encoder"``), loaded without executing anything
     from the file."""

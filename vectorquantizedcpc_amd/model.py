@@ -32,10 +32,11 @@ class ConfEncoder:
 
 
 class VQEmbeddingEMA(nn.Module):
-    """Codebook buffers (``model.py:89-101``) + the reference's public ``encode`` / eval-mode ``forward``
-    (``model.py:103-155``) as thin wrappers over the owning ``Encoder``'s native handle (the same VQ kernel
-    ``Encoder.encode`` runs).  The EMA update of training mode (``model.py:136-145``) is outside the
-    inference path.
+    """Codebook buffers (``model.py:89-101``) + the reference's public ``encode`` / ``forward`` (``model.py:103-155``) as thin
+    wrappers over the owning ``Encoder``'s native handle (the same VQ kernel ``Encoder.encode`` runs).  In training mode
+    ``forward`` also runs the EMA update of ``model.py:136-145`` (``vqcpc_encoder_vq_adapt``): no gradient is involved, the three
+    buffers are updated IN PLACE (the reference rebinds them) and the native handle follows without being rebuilt.  The
+    straight-through gradient of ``model.py:150`` is not provided.
     """
 
     def __init__(self, n_embeddings, embedding_dim, commitment_cost=0.25, decay=0.999, epsilon=1e-5):
@@ -53,7 +54,8 @@ class VQEmbeddingEMA(nn.Module):
         d["_owner"] = None
         return d
 
-    def _rows(self, x: Tensor):
+    def _flat(self, x: Tensor):
+        """The owning Encoder and x as contiguous fp32 rows (N, D) (``model.py:124``), after the checks every entry shares."""
         owner = self._owner() if self._owner is not None else None
         if owner is None:
             raise RuntimeError("VQEmbeddingEMA: the MI355X path serves the codebook through its owning Encoder "
@@ -63,7 +65,10 @@ class VQEmbeddingEMA(nn.Module):
         D = self.embedding.size(1)
         if x.dim() < 2 or x.size(-1) != D:
             raise RuntimeError(f"expected x of shape (Batch, Time, {D}), got {tuple(x.shape)}")
-        xf = x.detach().to(torch.float32).reshape(-1, D).contiguous()
+        return owner, x.detach().to(torch.float32).reshape(-1, D).contiguous()
+
+    def _rows(self, x: Tensor):
+        owner, xf = self._flat(x)
         q = torch.empty_like(xf)
         idx = torch.empty(xf.size(0), dtype=torch.int64, device=x.device)
         h = owner._native()
@@ -79,10 +84,18 @@ class VQEmbeddingEMA(nn.Module):
         return q.view_as(x), idx.view(x.size(0), x.size(1))
 
     def forward(self, x: Tensor):
-        """``model.py:117-155`` in eval mode: (x + (q - x), 0.25 * mse, perplexity)."""
+        """``model.py:117-155``: (x + (q - x), 0.25 * mse, perplexity), all three from the codebook as it is on entry.  In
+        training mode the EMA update (``model.py:136-145``) follows, in place; no gradient flows either way."""
         if self.training:
-            raise NotImplementedError("VQEmbeddingEMA: the EMA update of training mode (model.py:136-145) is outside "
-                                      "the inference path; call .eval()")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise NotImplementedError("VQEmbeddingEMA: the straight-through gradient of training mode (model.py:150) is "
+                                          "not implemented; the codebook update itself needs none -- call it under "
+                                          "torch.no_grad() or on a detached x")
+            with torch.no_grad():
+                owner, xf = self._flat(x)
+                z_st = torch.empty_like(xf)
+                stats = owner._adapt_rows(xf, z_st)
+            return z_st.view_as(x), stats[0], stats[1]
         with torch.no_grad():
             _, h, xf, q, idx = self._rows(x)
             z_st = torch.empty_like(xf)
@@ -139,6 +152,14 @@ class Encoder(_lib.NativeModule):
         """Schedule the front end of the last ``encode`` / ``stage`` call ran (``vqcpc_encoder_last_schedule``): 2 the six
         column-split launches, 1 the one-launch fused kernel, 0 the layered kernels; -1 before the first call."""
         return -1 if self._handle is None else int(_lib.load().vqcpc_encoder_last_schedule(self._handle))
+
+    def workspace_bytes(self) -> int:
+        """Device bytes of the native handle's grow-only work buffers (``vqcpc_encoder_workspace_bytes``): front-end activations,
+        statistics and the work space of the codebook update -- the peak of the calls so far, weights not counted."""
+        import ctypes
+        n = ctypes.c_uint64()
+        _lib.check(_lib.load().vqcpc_encoder_workspace_bytes(self._native(), ctypes.byref(n)))
+        return int(n.value)
 
     def check(self):
         """Synchronise the current stream and raise ``RuntimeError`` if the resident context scan of the last ``encode``
@@ -201,6 +222,53 @@ class Encoder(_lib.NativeModule):
             _lib.check(_lib.load().vqcpc_encoder_stage(self._native(), mel.data_ptr(), B, T, conv_mode, stage,
                                                        out.data_ptr(), _lib.current_stream()))
         return out
+
+    def _adapt_rows(self, xf: Tensor, z_st: Optional[Tensor] = None, idx: Optional[Tensor] = None) -> Tensor:
+        """One codebook update (``vqcpc_encoder_vq_adapt``) over the rows xf (N, z_dim) fp32, contiguous, on the module's device
+        -> a 2-element device tensor (loss, perplexity) from the codebook as it was (and, into ``z_st`` (N, z_dim) / ``idx`` (N) int64
+        if given, the straight-through rows and the code indices of that codebook).  The three buffers are written through
+        their ``data_ptr()``: their ``_version`` stays, so the handle -- which the call itself brings up to date -- is not rebuilt."""
+        cb = self.codebook
+        for name in ("embedding", "ema_count", "ema_weight"):
+            t = getattr(cb, name)
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != xf.device:
+                raise RuntimeError(f"codebook.{name} must be a contiguous float32 tensor on {xf.device} "
+                                   f"(got {t.dtype}, contiguous={t.is_contiguous()}, {t.device})")
+        if xf.size(0) < 1:
+            raise RuntimeError("codebook update: no rows")
+        h = self._native()
+        stats = torch.empty(2, device=xf.device)
+        with _lib.device_guard(xf.device):
+            _lib.check(_lib.load().vqcpc_encoder_vq_adapt(
+                h, xf.data_ptr(), xf.size(0), float(cb.decay), float(cb.epsilon), cb.embedding.data_ptr(),
+                cb.ema_count.data_ptr(), cb.ema_weight.data_ptr(), z_st.data_ptr() if z_st is not None else None,
+                idx.data_ptr() if idx is not None else None,
+                stats[0:].data_ptr(), stats[1:].data_ptr(), _lib.current_stream()))
+        return stats
+
+    @torch.no_grad()
+    def adapt_codebook(self, mels: Tensor, n_frames: Optional[List[int]] = None, conv_mode: int = 0,
+                       return_indices: bool = False):
+        """Fit the codebook to a batch: the front end up to ``z_pre`` (stage 10), then the EMA update of ``model.py:136-145``
+        over the valid rows -- what one training step of the reference does to the codebook, without the gradient step on the
+        other weights.  mels (B, in_channels, T); ``n_frames``: valid OUTPUT frames per utterance (a host list, each in
+        [0, T // 2]; default all), rows behind them are padding and take no part.  Returns ``(loss, perplexity)`` of the batch
+        under the codebook as it was, 0-dim device tensors; nothing is synchronised.  Works in either mode.  ``conv_mode``: as
+        ``encode``.  ``return_indices``: also return the code every valid row was assigned to under that codebook, (N,) int64 on
+        the device, utterance after utterance."""
+        z_pre = self.stage(mels, 10, conv_mode)
+        B, To, D = z_pre.shape
+        if n_frames is None:
+            rows = z_pre.view(-1, D)
+        else:
+            n = [int(v) for v in n_frames]
+            if len(n) != B or any(v < 0 or v > To for v in n):
+                raise RuntimeError(f"n_frames must hold one count in [0, {To}] per utterance ({B}), got {n}")
+            rows = z_pre.view(-1, D) if all(v == To for v in n) else torch.cat([z_pre[b, :v] for b, v in enumerate(n)])
+        rows = rows.contiguous()
+        idx = torch.empty(rows.size(0), dtype=torch.int64, device=rows.device) if return_indices else None
+        stats = self._adapt_rows(rows, idx=idx)
+        return (stats[0], stats[1], idx) if return_indices else (stats[0], stats[1])
 
     def forward(self, mels: Tensor):
         """``model.py:72-86`` in eval mode: (z, c, vq_loss, perplexity)."""
