@@ -3,7 +3,7 @@
 of ONE worker say about a sample step ("the matrix pipe works 5.1 of 10.3 us", "the step is vector-issue bound on two service
 waves"), stated by the hardware counters for ALL workers.
 
-    python3 tools/collect_sq.py [--mode xcd|xcm] [--utterances 32|128] [--out profiles/r04_pmc_sq_xcd32.json]
+    python3 tools/collect_sq.py [--mode xcd|xcm] [--utterances 32|128] [--out profiles/r04_pmc_sq_xcd32.json] [--lib build/exp/X/libvqcpc_hip.so]
 
 Separate `rocprofv3 --pmc` passes of at most 8 SQ counters each (MI355X_MICROARCH.md "rocprofv3 PMC slots"), each a fresh child
 with the program itself behind `--`; only --pmc (no trace domains).  The decode is one call of --codes codes per utterance
@@ -30,8 +30,11 @@ PASSES = [
 ]
 
 
-def target(mode, n_utt, codes):
+def target(mode, n_utt, codes, lib):
     import torch
+    if lib:                                        # an A/B build (tools/build_variant.sh) instead of the shipped library
+        from vectorquantizedcpc_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(lib)
     import vectorquantizedcpc_amd as V
     from vectorquantizedcpc_amd import synth
     voc = V.Vocoder(V.ConfVocoder())
@@ -65,11 +68,12 @@ def main():
     ap.add_argument("--mode", default="xcd", choices=("xcd", "xcm"))
     ap.add_argument("--target", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--out", default="")
+    ap.add_argument("--lib", default="")
     args = ap.parse_args()
     if args.utterances <= 0:
         args.utterances = 32 if args.mode == "xcd" else 128
     if args.target:
-        return target(args.mode, args.utterances, args.codes)
+        return target(args.mode, args.utterances, args.codes, args.lib)
     out_path = args.out or os.path.join(ROOT, "profiles", f"r04_pmc_sq_{args.mode}{args.utterances}.json")
 
     import bench                                   # kernel_source_sha(): imports torch, makes no GPU call
@@ -82,7 +86,7 @@ def main():
         out_dir = os.path.join(scratch, f"{args.mode}_{args.utterances}_p{i}")
         cmd = ["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", out_dir, "--",
                sys.executable, os.path.abspath(__file__), "--target", "--mode", args.mode,
-               "--utterances", str(args.utterances), "--codes", str(args.codes)]
+               "--utterances", str(args.utterances), "--codes", str(args.codes)] + (["--lib", os.path.abspath(args.lib)] if args.lib else [])
         print("[collect_sq]", " ".join(cmd), file=sys.stderr, flush=True)
         logp = os.path.join(scratch, f"{args.mode}_{args.utterances}_p{i}.log")
         with open(logp, "w") as log:
@@ -106,7 +110,7 @@ def main():
            "us_per_step_profiled": us_per_step,
            "workgroups": 256, "waves_per_workgroup": 12, "simds": 1024,
            "kernel_source_sha": bench.kernel_source_sha(),
-           "command": "python3 tools/collect_sq.py --mode %s --utterances %d" % (args.mode, args.utterances)}
+           "command": "python3 tools/collect_sq.py --mode %s --utterances %d" % (args.mode, args.utterances) + (" --lib " + args.lib if args.lib else "")}
     d = {}
     wc = c.get("SQ_WAVE_CYCLES")
     if wc:

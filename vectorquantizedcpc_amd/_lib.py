@@ -142,6 +142,7 @@ def load():
     lib.vqcpc_resampler_out_len.argtypes = [vp, i32]
     lib.vqcpc_resampler_run.argtypes = [vp, vp, C.POINTER(C.c_int), i32, i32, vp, i32, vp]
     lib.vqcpc_probe_gates.argtypes = [vp, i32, vp, vp]          # test surface of csrc/gate_probe.hip, not in include/vqcpc.h
+    lib.vqcpc_probe_draw.argtypes = [vp, i32, vp, vp, vp]       # likewise
     _lib = lib
     return lib
 

@@ -284,6 +284,32 @@ __device__ __forceinline__ int chain_pos_plain(int k, int stride) {
     const int q = (k >> 2) & 3, c0 = k & 1, ci = (k >> 1) & 1;
     return (2 * kw + c0) * stride + 8 * s + 4 * ci + q;
 }
+// chain_combine of the FOUR accumulators of fc1's matrix-pipe chain at once, in ONE statement: the same adds in the same order per
+// accumulator, interleaved -- the four are independent, so each fills the others' wait states and no s_nop is left between them.
+// Hazards inside the statement, which hipcc does not pad: the matrix instruction that wrote `a` -> its first VALU read (four states
+// for this two-pass instruction: s_nop 3); VALU write -> v_permlane16_swap or DPP read of the same register (two states; three
+// instructions lie between each pair).  The swap takes the accumulator itself as its first operand: rows 0 and 2 of it, where the sum
+// lanes and the lanes they shift in are, stay what they were; rows 1 and 3 are not used afterwards.
+// fc1's epilogue rides along: s[i] = max(0, row sum i + b[i]), the v_add_f32 / v_max_f32 pair hipcc emits for `v += b; v = v > 0.f ? v : 0.f`
+// (left to hipcc behind the statement they became packed adds, compare / select pairs with their own wait states, or a canonicalising
+// v_max_f32 v, v, v in front of each ReLU).
+__device__ __forceinline__ void fc1_finish4(const v4f &a, const float (&b)[4], float (&s)[4]) {
+    float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], q0, q1, q2, q3;
+#define XD_SHL(N) " row_shl:" #N " row_mask:0xf bank_mask:0xf\n\t"
+    asm("s_nop 3\n\t"
+        "v_mov_b32 %4, %8\n\tv_mov_b32 %5, %9\n\tv_mov_b32 %6, %10\n\tv_mov_b32 %7, %11\n\t"
+        "v_permlane16_swap_b32 %8, %4\n\tv_permlane16_swap_b32 %9, %5\n\tv_permlane16_swap_b32 %10, %6\n\tv_permlane16_swap_b32 %11, %7\n\t"
+        "v_add_f32 %4, %8, %4\n\tv_add_f32 %5, %9, %5\n\tv_add_f32 %6, %10, %6\n\tv_add_f32 %7, %11, %7\n\t"
+        "v_add_f32_dpp %0, %4, %4" XD_SHL(4) "v_add_f32_dpp %1, %5, %5" XD_SHL(4) "v_add_f32_dpp %2, %6, %6" XD_SHL(4) "v_add_f32_dpp %3, %7, %7" XD_SHL(4)
+        "v_add_f32_dpp %0, %4, %0" XD_SHL(8) "v_add_f32_dpp %1, %5, %1" XD_SHL(8) "v_add_f32_dpp %2, %6, %2" XD_SHL(8) "v_add_f32_dpp %3, %7, %3" XD_SHL(8)
+        "v_add_f32_dpp %0, %4, %0" XD_SHL(12) "v_add_f32_dpp %1, %5, %1" XD_SHL(12) "v_add_f32_dpp %2, %6, %2" XD_SHL(12) "v_add_f32_dpp %3, %7, %3" XD_SHL(12)
+        "v_add_f32 %0, %0, %12\n\tv_add_f32 %1, %1, %13\n\tv_add_f32 %2, %2, %14\n\tv_add_f32 %3, %3, %15\n\t"
+        "v_max_f32 %0, 0, %0\n\tv_max_f32 %1, 0, %1\n\tv_max_f32 %2, 0, %2\n\tv_max_f32 %3, 0, %3"
+        : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
+        : "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));
+#undef XD_SHL
+}
+
 // ONE operand word per lane and group of 8 terms, not two.  A lane's operand depends on (kw, c0, j) and not on rq: lanes 32..63 would
 // read exactly what lanes 0..31 read.  So the halves read DIFFERENT words -- lanes 0..31 terms 8 g .. 8 g + 3, lanes 32..63 terms
 // 8 g + 4 .. 8 g + 7 (`op` carries the half's offset, 4 rq floats) -- and the instruction's B lane-group pattern picks the half that

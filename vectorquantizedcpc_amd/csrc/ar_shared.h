@@ -158,6 +158,25 @@ __device__ __forceinline__ unsigned row_min(unsigned m) {
     m = min(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
     return m;
 }
+// first_max over the 8 scores of a resident decoder's draw, where chain_combine leaves them: classes 0..3 in lanes 0..3, classes 4..7
+// in lanes 32..35 (the other lanes hold anything).  Returns, wave-uniform, the winner's class kb and its score `best` (that lane's own
+// bits), as first_max taken over classes 0..7 gives them: the quad maximum of the ordered image by two DPP steps, the larger of the
+// two quads' maxima, and the lowest class among the lanes that hold it.  `sc + 0.0f` turns -0 into +0 first, so that the two
+// zeros tie as they do under `>` (and the lower class wins); the returned bits are the untouched ones.  Equal to first_max for every
+// input without NaN, +-inf included.  With a NaN it is not: first_max never lets a NaN in behind class 0 and never replaces one at
+// class 0, here a NaN's image orders it above +inf (sign clear) or below -inf (sign set) like any other bit pattern.  Logits and
+// noise are finite whenever weights and state are.  Denormal scores keep their order because `sc + 0.0f` keeps them: the library is
+// built with fp32 denormals preserved (hipcc's default); flushed, they would all tie with zero (the probe's denormal cases guard it).
+__device__ __forceinline__ void first_max_8lanes(float sc, float &best, int &kb) {
+    const unsigned u = ordered(__float_as_uint(sc + 0.0f));
+    unsigned m = max(u, (unsigned)__builtin_amdgcn_update_dpp(0, (int)u, 0xB1, 0xF, 0xF, false));      // quad_perm [1,0,3,2]
+    m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));               // quad_perm [2,3,0,1]
+    const unsigned mx = max((unsigned)__builtin_amdgcn_readlane((int)m, 0), (unsigned)__builtin_amdgcn_readlane((int)m, 32));
+    const unsigned long long hit = __ballot(u == mx);
+    const unsigned hit8 = ((unsigned)hit & 0xFu) | ((unsigned)(hit >> 28) & 0xF0u);                     // bit k: class k holds the maximum
+    kb = __ffs((int)hit8) - 1;                                                                          // some lane holds the maximum: hit8 != 0
+    best = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc), kb < 4 ? kb : 28 + kb));
+}
 
 // Candidate granule of the launch path's fused schedule: {tag = step mod 2^22 (CAND_TAG_BITS), class < 1024, score}
 __device__ __forceinline__ u64 cand_pack(unsigned tag, unsigned cls, float score) { return ((u64)((tag << 10) | cls) << 32) | __float_as_uint(score); }
@@ -200,6 +219,17 @@ __device__ __forceinline__ void ps_load_weights(const float *Wrow, int kw, int c
 __device__ __forceinline__ void xd_put(u64 *base, unsigned byte_off, u64 v, int agent) {
     if (agent) asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2 sc1" :: "v"(byte_off), "v"(v), "s"(base) : "memory");
     else asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2 sc0" :: "v"(byte_off), "v"(v), "s"(base) : "memory");   // stays in this XCD's L2
+}
+
+// four granules STEP bytes apart in ONE statement: one base register, immediate offsets, the five wait states once
+template <int STEP>
+__device__ __forceinline__ void xd_put4(u64 *base, unsigned byte_off, u64 v0, u64 v1, u64 v2, u64 v3, int agent) {
+    if (agent) asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %5 sc1\n\tglobal_store_dwordx2 %0, %2, %5 offset:%6 sc1\n\t"
+                            "global_store_dwordx2 %0, %3, %5 offset:%7 sc1\n\tglobal_store_dwordx2 %0, %4, %5 offset:%8 sc1"
+                            :: "v"(byte_off), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(base), "i"(STEP), "i"(2 * STEP), "i"(3 * STEP) : "memory");
+    else asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %5 sc0\n\tglobal_store_dwordx2 %0, %2, %5 offset:%6 sc0\n\t"
+                      "global_store_dwordx2 %0, %3, %5 offset:%7 sc0\n\tglobal_store_dwordx2 %0, %4, %5 offset:%8 sc0"
+                      :: "v"(byte_off), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(base), "i"(STEP), "i"(2 * STEP), "i"(3 * STEP) : "memory");
 }
 
 struct Waiter {                      // bounded spinning shared by all sweeps of the kernel

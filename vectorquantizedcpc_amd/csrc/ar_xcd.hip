@@ -40,7 +40,8 @@
 // granules in one run, which a lane of the slot's fc2 wave takes as two 16-byte loads of two granules each; candidates [slot][rank].
 // Every granule is published by one 8-byte store and validated by its own tag, whatever the width of the load that fetched it.
 // Four slots per XCD, what differs: every wave runs ONE dependent chain of 112 matrix instructions per step (waves 2..11 rows
-// 0..79 with pinned weights, wave 0 fc1 for all four slots and wave 1 W_hh rows 80..83, both with weights streamed from LDS);
+// 0..79 with pinned weights, wave 0 fc1 for all four slots -- its four accumulators combined, biased, rectified and stored together
+// (fc1_finish4, xd_put4) -- and wave 1 W_hh rows 80..83, both with weights streamed from LDS);
 // fc2 + draw of slots 0..3 on waves 2, 3, 6, 7; waves 4 and 8 -- fc1's SIMD mates -- start their chains when a_t is out (two
 // dependent-chain waves keep a SIMD's issue port ~80 % busy, whatever s_setprio says); wave 11 draws the next step's noise
 // behind its chain from the slots' clocks the service waves post in LDS.
@@ -330,13 +331,9 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 float v2 = chain_combine(acc2);
                 v2 += b2;
                 const float sc = v2 + nz;                                // classes 0..3 of the 8 in lanes 0..3, 4..7 in lanes 32..35
-                float best = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc), 0));
-                int kb = 0;
-#pragma unroll
-                for (int k = 1; k < 8; ++k) {
-                    const float sk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc), k < 4 ? k : 28 + k));
-                    if (sk > best) { best = sk; kb = k; }
-                }
+                float best;
+                int kb;
+                first_max_8lanes(sc, best, kb);                          // first argmax in lanes, not 8 v_readlane and a scalar compare / select chain (profiles/r13_ab_at_handoff.txt)
                 const bool drop = p.dbg_drop_step >= 0 && t == p.dbg_drop_step && rank == 3 && xcc == 0;
                 if (lane == 0 && !drop)
                     xd_put(gc, ((unsigned)fs * NW + (unsigned)rank) * 8u, ((u64)((tag << 8) | (unsigned)(FPB * rank + kb)) << 32) | __float_as_uint(best), agent);
@@ -552,13 +549,13 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     { const int done = __builtin_amdgcn_readfirstlane(__float_as_int(a4[0])); asm volatile("" :: "s"(done)); }      // the last term's RESULT is there
                     XD_STAMP(0, 15);
 #endif
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float v = chain_combine(a4[i]);                  // fc1 row 4 rq + i of slot j
-                        v += b1q[i];
-                        v = v > 0.f ? v : 0.f;
-                        if (sum_lane && (int)j < bx) xd_put(ga, xg_a_off((unsigned)rank, 4u * rq + (unsigned)i, j), ((u64)tag << 32) | __float_as_uint(v), agent);
-                    }
+                    // fc1 rows 4 rq + 0..3 of slot j together: one statement for the combines, bias and ReLU, one exec region, one
+                    // statement of four stores 8 bytes apart (profiles/r13_ab_at_handoff.txt)
+                    float v[4];
+                    fc1_finish4(a4, b1q, v);
+                    if (sum_lane && (int)j < bx)
+                        xd_put4<8>(ga, xg_a_off((unsigned)rank, 4u * rq, j), ((u64)tag << 32) | __float_as_uint(v[0]), ((u64)tag << 32) | __float_as_uint(v[1]),
+                                   ((u64)tag << 32) | __float_as_uint(v[2]), ((u64)tag << 32) | __float_as_uint(v[3]), agent);
 #if XD_HOLD
                     if (lane == 0) __hip_atomic_store(s_ctl + 5, (int)tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // a_t is out: waves 4 and 8 may start
 #endif

@@ -1,6 +1,7 @@
-// Element-wise probe of the gate non-linearities (test surface, not on any decode path): the hardware gates of the sample loop's
-// GRU cell update (gate_sigmoid / gate_tanh, ar_shared.h) and the libm gates of scan.hip's sequence scans (sigmoidf_ / tanhf),
-// evaluated exactly as the kernels inline them, so a test can compare them with a float64 reference over every fp32 range.
+// Probes of device helpers (test surface, not on any decode path).  Element-wise, the gate non-linearities: the hardware gates of
+// the sample loop's GRU cell update (gate_sigmoid / gate_tanh, ar_shared.h) and the libm gates of scan.hip's sequence scans
+// (sigmoidf_ / tanhf), evaluated exactly as the kernels inline them, so a test can compare them with a float64 reference over every
+// fp32 range.
 #include "ar_shared.h"
 
 __global__ void __launch_bounds__(256) probe_gates_kernel(const float *__restrict__ v, int n, float *__restrict__ out) {
@@ -18,6 +19,28 @@ extern "C" int vqcpc_probe_gates(const float *v, int n, float *out, void *stream
     VQ_REQUIRE(v && out && n > 0, "vqcpc_probe_gates: bad argument");
     const int blocks = n / 256 + 1 < 4096 ? n / 256 + 1 : 4096;
     hipLaunchKernelGGL(probe_gates_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, v, n, out);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+// The resident decoders' draw (first_max_8lanes, ar_shared.h): one wave per case, its 8 scores placed where chain_combine leaves them
+// -- classes 0..3 in lanes 0..3, 4..7 in lanes 32..35 -- and +inf in every other lane, which must not matter.
+__global__ void __launch_bounds__(64) probe_draw_kernel(const float *__restrict__ sc, int n, int *__restrict__ cls, unsigned *__restrict__ bits) {
+    const unsigned lane = threadIdx.x;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const bool holds = (lane & 0x1Cu) == 0;
+        const float v = holds ? sc[(size_t)i * 8 + ((lane >> 5) << 2) + (lane & 3u)] : __builtin_inff();
+        float best;
+        int kb;
+        first_max_8lanes(v, best, kb);
+        if (lane == 0) { cls[i] = kb; bits[i] = __float_as_uint(best); }
+    }
+}
+
+// sc (n, 8) device floats -> cls (n) int32, bits (n) uint32: the winning class and its score's bits; enqueued on `stream`.
+extern "C" int vqcpc_probe_draw(const float *sc, int n, int *cls, unsigned *bits, void *stream) {
+    VQ_REQUIRE(sc && cls && bits && n > 0, "vqcpc_probe_draw: bad argument");
+    hipLaunchKernelGGL(probe_draw_kernel, dim3(n < 4096 ? n : 4096), dim3(64), 0, (hipStream_t)stream, sc, n, cls, bits);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }
