@@ -196,7 +196,7 @@ int vqcpc_cpc_create(const vqcpc_cpc_weights *w, vqcpc_cpc **out);
 void vqcpc_cpc_destroy(vqcpc_cpc *cpc);
 
 /* Replaces CPCLoss.forward (model.py:191-316) under no_grad: the forward VALUE of the objective (loss and per-step prediction
- * accuracies, what train_cpc.py:128-131 logs) -- checkpoint scoring; no gradient exists.
+ * accuracies, what train_cpc.py:128-131 logs) -- checkpoint scoring; the gradient is vqcpc_cpc_grad's.
  * z DEVICE (N, T, z_dim), c DEVICE (N, T, c_dim), N = n_speakers * n_utterances utterances speaker-major, T >= n_steps + 2;
  * L = T - n_steps anchors per utterance.
  * Negatives: utt_index DEVICE (n_steps, Utt, Neg) int64 in [0, Utt) and seq_index DEVICE (n_steps, Spk, Utt, Neg, L) int64 in
@@ -212,6 +212,23 @@ void vqcpc_cpc_destroy(vqcpc_cpc *cpc);
 int vqcpc_cpc_score(vqcpc_cpc *cpc, const float *z, const float *c, int T, const int64_t *utt_index,
                     const int64_t *seq_index, uint64_t seed, uint32_t stream_id, float *loss, float *step_loss,
                     float *accuracy, uint8_t *correct, float *scores, void *stream);
+
+/* vqcpc_cpc_score followed by the gradients of `loss` (upstream gradient 1) with respect to z, c and the first n_steps
+ * predictors: the backward of CPCLoss.forward (what loss.backward() leaves in train_cpc.py:116), csrc/cpc_grad.hip.
+ * z, c, T, the negatives (given or drawn), clamping, seed and stream_id, stream semantics and the device check are those of
+ * vqcpc_cpc_score; loss, step_loss and accuracy have the BITS vqcpc_cpc_score gives for the same predictors.
+ * W DEVICE (n_steps, 64, c_dim) and bias DEVICE (n_steps, 64): the predictors this call uses, stacked -- the caller's, so that an
+ * optimizer step costs no new handle; both NULL = the handle's copies.  The handle gives sizes and work space only.
+ * Gradients DEVICE, each may be NULL = not wanted (its launches are skipped): grad_z (N, T, 64), grad_c (N, T, c_dim), grad_W
+ * (n_steps, 64, c_dim), grad_bias (n_steps, 64).  Every element is written, the zeros too (grad_z[:, 0], grad_c[:, L:]).
+ * Every sum runs in one fixed order (no floating-point atomics; csrc/cpc_grad.hip lists the orders): equal inputs give equal
+ * bits.  The work space lives on the handle and grows to the largest call.
+ * VQCPC_ERR_INVALID before anything is enqueued: T < n_steps + 2, exactly one of W / bias NULL, exactly one index array NULL, a
+ * handle of another device. */
+int vqcpc_cpc_grad(vqcpc_cpc *cpc, const float *z, const float *c, int T, const float *W, const float *bias,
+                   const int64_t *utt_index, const int64_t *seq_index, uint64_t seed, uint32_t stream_id, float *loss,
+                   float *step_loss, float *accuracy, float *grad_z, float *grad_c, float *grad_W, float *grad_bias,
+                   void *stream);
 
 /* ------------------------------------------------------------------ ABX scoring ------ */
 

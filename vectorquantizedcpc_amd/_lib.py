@@ -20,7 +20,7 @@ SYMBOLS = [
     "vqcpc_abi_version", "vqcpc_last_error", "vqcpc_device_count",
     "vqcpc_encoder_create", "vqcpc_encoder_destroy", "vqcpc_encoder_encode",
     "vqcpc_encoder_forward_stats", "vqcpc_encoder_context", "vqcpc_encoder_stage", "vqcpc_encoder_vq_encode", "vqcpc_encoder_vq_adapt", "vqcpc_encoder_workspace_bytes", "vqcpc_encoder_set_option", "vqcpc_encoder_last_schedule",
-    "vqcpc_cpc_create", "vqcpc_cpc_destroy", "vqcpc_cpc_score",
+    "vqcpc_cpc_create", "vqcpc_cpc_destroy", "vqcpc_cpc_score", "vqcpc_cpc_grad",
     "vqcpc_abx_workspace_bytes", "vqcpc_abx_score", "vqcpc_abx_index_workspace_bytes", "vqcpc_abx_code_table", "vqcpc_abx_score_indices",
     "vqcpc_encoder_check", "vqcpc_vocoder_check", "vqcpc_vocoder_last_path", "vqcpc_vocoder_last_slots", "vqcpc_vocoder_workspace_bytes", "vqcpc_vocoder_plan",
     "vqcpc_vocoder_create", "vqcpc_vocoder_destroy", "vqcpc_vocoder_generate",
@@ -96,6 +96,7 @@ def load():
     lib.vqcpc_cpc_destroy.argtypes = [vp]
     lib.vqcpc_cpc_destroy.restype = None
     lib.vqcpc_cpc_score.argtypes = [vp, vp, vp, i32, i64p, i64p, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    lib.vqcpc_cpc_grad.argtypes = [vp, vp, vp, i32, vp, vp, i64p, i64p, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_abx_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
     lib.vqcpc_abx_score.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_abx_index_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_uint64)]

@@ -20,6 +20,13 @@
     python -m vectorquantizedcpc_amd.cli adapt-codebook --dataset datasets/2019/english --cpc-checkpoint in.pt | --random-init
                                                  --out-checkpoint out.pt [--epochs 1]
 
+    python -m vectorquantizedcpc_amd.cli fit-predictors --dataset datasets/2019/english --cpc-checkpoint in.pt | --random-init
+                                                 --out-checkpoint out.pt [--steps 200 --lr 4e-4] [the options of score]
+
+``fit-predictors`` refits the K linear predictors of a checkpoint's ``"cpc"`` entry on its frozen encoder
+(``driver.fit_predictors``: the gradient is ``vqcpc_cpc_grad``'s, the optimizer torch's Adam) -- what an adapted codebook needs
+before ``score`` means anything again.  It prints the ``score`` lines before and after the fit and writes a checkpoint with
+``"encoder"`` untouched and ``"cpc"`` replaced.
 ``adapt-codebook`` fits a checkpoint's codebook to the mels of ``test.json`` with the EMA update of ``model.py:136-145`` (no
 gradient: ``driver.adapt_codebook``), prints loss, perplexity and codes in use per epoch and writes a checkpoint whose
 ``"encoder"`` entry has the reference's keys: ``encode``, ``abx`` and ``score`` run on it as on any other.
@@ -94,7 +101,8 @@ def encode_dataset(args) -> int:
     return 0
 
 
-def score_dataset(args) -> int:
+def _score_setup(args):
+    """Encoder, CPCLoss and the mels of ``test.json`` by speaker, for ``score`` and ``fit-predictors``."""
     paths = io.read_test_metadata(args.dataset)
     enc, _ = _models(args, need_vocoder=False)
     cpc = CPCLoss(ConfCPC(args.prediction_steps, args.speakers, args.utterances, args.negatives, 64, 256))
@@ -104,6 +112,10 @@ def score_dataset(args) -> int:
     by_speaker = {}
     for p in paths:
         by_speaker.setdefault(p.stem.split("_")[0], []).append(io.load_mel(p))
+    return enc, cpc, by_speaker
+
+
+def _print_score(args, enc, cpc, by_speaker) -> int:
     r = driver.score_batches(enc, cpc, by_speaker, sample_frames=args.sample_frames, seed=args.seed)
     if r["batches"] == 0:
         print(f"no batch of {args.speakers} speakers x {args.utterances} utterances could be formed; skipped speakers: "
@@ -116,6 +128,26 @@ def score_dataset(args) -> int:
           f"{len(r['speakers_skipped'])} {r['speakers_skipped']}; speakers left over after the last whole batch: "
           f"{len(r['speakers_left_over'])} {r['speakers_left_over']}")
     return 0
+
+
+def score_dataset(args) -> int:
+    return _print_score(args, *_score_setup(args))
+
+
+def fit_predictors_dataset(args) -> int:
+    enc, cpc, by_speaker = _score_setup(args)
+    print("before the fit:")
+    if _print_score(args, enc, cpc, by_speaker):
+        return 1
+    r = driver.fit_predictors(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed)
+    print(f"fitted {cpc.n_prediction_steps} predictors in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches: "
+          f"cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}")
+    print("after the fit:")
+    rc = _print_score(args, enc, cpc, by_speaker)
+    io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
+                              encoder_state=enc.state_dict() if args.random_init else None)
+    print(f"wrote {args.out_checkpoint}: \"encoder\" as it was, \"cpc\" replaced ({len(cpc.state_dict())} keys)")
+    return rc
 
 
 def score_vocoder_dataset(args) -> int:
@@ -246,7 +278,7 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook"):
+    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook", "fit-predictors"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
         if name in ("encode", "convert"):
@@ -255,13 +287,17 @@ def main(argv=None) -> int:
         p.add_argument("--random-init", action="store_true", help="seeded random-init weights (no checkpoint ships with the reference)")
         p.add_argument("--device", default="cuda")
         p.add_argument("--max-batch", type=int, default=64)
-        if name == "score":                                   # config.py:42-47, :202
+        if name in ("score", "fit-predictors"):               # config.py:42-47, :202
             p.add_argument("--prediction-steps", type=int, default=12)
             p.add_argument("--speakers", type=int, default=8)
             p.add_argument("--utterances", type=int, default=8)
             p.add_argument("--negatives", type=int, default=17)
             p.add_argument("--sample-frames", type=int, default=128)
             p.add_argument("--seed", type=int, default=synth.SEED)
+            if name == "fit-predictors":
+                p.add_argument("--out-checkpoint", required=True)
+                p.add_argument("--steps", type=int, default=200)
+                p.add_argument("--lr", type=float, default=4e-4, help="Adam's learning rate (config.py's CPC training rate)")
         elif name == "encode":
             p.add_argument("--save-auxiliary", action="store_true")
         elif name == "adapt-codebook":
@@ -305,7 +341,8 @@ def main(argv=None) -> int:
     if args.cmd == "score-vocoder" and not args.random_init and not args.vocoder_checkpoint:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,
-            "score-vocoder": score_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset}[args.cmd](args)
+            "score-vocoder": score_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset,
+            "fit-predictors": fit_predictors_dataset}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -251,6 +251,22 @@ def cut_positions(seed: int, batch: int, lengths: Sequence[int], need_frames: in
     return [int(words[i, i & 3]) % (int(t) - need_frames + 1) for i, t in enumerate(lengths)]
 
 
+def _score_plan(cpc, mels_by_speaker, sample_frames: int, seed: int, dev):
+    """The batching ``score_batches`` and ``fit_predictors`` share.  -> (n batches, skipped speakers, left-over speakers,
+    ``mels(b)`` = the (Spk * Utt, 80, need) mel batch number ``b`` on ``dev``, cut by ``cut_positions`` with stream = b)."""
+    need = sample_frames + cpc.conf.n_prediction_steps
+    S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
+    lengths = {spk: [int(m.shape[-1]) for m in mels] for spk, mels in mels_by_speaker.items()}
+    batches, skipped, left = score_groups(lengths, S, U, need)
+
+    def mels(b):
+        picked = [mels_by_speaker[spk][i] for spk, ids in batches[b] for i in ids]
+        starts = cut_positions(seed, b, [int(m.shape[-1]) for m in picked], need)
+        return torch.stack([m[:, s:s + need] for m, s in zip(picked, starts)]).to(dev)
+
+    return len(batches), skipped, left, mels
+
+
 @torch.no_grad()
 def score_batches(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, sample_frames: int = 128, seed: int = 13, device=None):
     """One pass of ``train_cpc.py:104-131`` without the optimiser: checkpoint scoring.  ``mels_by_speaker``: speaker ->
@@ -262,18 +278,13 @@ def score_batches(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, sample_frames
     ``accuracies`` (one per prediction step) -- with ``batches``, ``utterances`` and the speakers that could not be
     scored: ``speakers_skipped`` (fewer than Utt long-enough utterances) and ``speakers_left_over`` (after the last whole
     batch)."""
-    need = sample_frames + cpc.conf.n_prediction_steps
     S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
     dev = device if device is not None else next(encoder.parameters()).device
-    lengths = {spk: [int(m.shape[-1]) for m in mels] for spk, mels in mels_by_speaker.items()}
-    batches, skipped, left = score_groups(lengths, S, U, need)
-    res = {"cpc_loss": 0.0, "vq_loss": 0.0, "perplexity": 0.0, "accuracies": None, "batches": len(batches),
-           "utterances": len(batches) * S * U, "speakers_skipped": skipped, "speakers_left_over": left}
-    for b, group in enumerate(batches):
-        picked = [mels_by_speaker[spk][i] for spk, ids in group for i in ids]
-        starts = cut_positions(seed, b, [int(m.shape[-1]) for m in picked], need)
-        mels = torch.stack([m[:, s:s + need] for m, s in zip(picked, starts)]).to(dev)
-        z, c, vq_loss, perplexity = encoder(mels)
+    n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
+    res = {"cpc_loss": 0.0, "vq_loss": 0.0, "perplexity": 0.0, "accuracies": None, "batches": n_batches,
+           "utterances": n_batches * S * U, "speakers_skipped": skipped, "speakers_left_over": left}
+    for b in range(n_batches):
+        z, c, vq_loss, perplexity = encoder(batch_mels(b))
         loss, acc = cpc(z, c, seed=seed, stream_id=b)
         if hasattr(encoder, "check"):
             encoder.check()                          # nothing incomplete may be reported
@@ -282,6 +293,49 @@ def score_batches(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, sample_frames
         res["vq_loss"] += (float(vq_loss) - res["vq_loss"]) / n
         res["perplexity"] += (float(perplexity) - res["perplexity"]) / n
         res["accuracies"] = list(acc) if res["accuracies"] is None else [a + (x - a) / n for a, x in zip(res["accuracies"], acc)]
+    return res
+
+
+def fit_predictors(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 200, lr: float = 4e-4, optimizer=torch.optim.Adam,
+                   sample_frames: int = 128, seed: int = 13, device=None):
+    """Refit the K linear predictors of ``cpc`` on a FROZEN ``encoder`` -- what an adapted codebook needs before its CPC
+    score means anything again (``adapt_codebook`` -> ``fit_predictors`` -> ``score_batches``).  Log-sum-exp of affine functions
+    is convex in ``(W_k, b_k)``, so this is a convex fit.
+
+    The batches, the cuts and ``stream_id`` = batch number are those of ``score_batches``; step i takes batch ``i mod batches``.
+    The encoder runs under ``no_grad``, once per batch (it does not change; the encoded ``z``, ``c`` are kept on the device);
+    ``cpc(z, c, seed=seed, stream_id=batch, differentiable=True)`` and ``backward()`` are one ``vqcpc_cpc_grad`` call asking
+    for dW and db only; ``optimizer(params, lr=lr)`` -- torch's, as glue -- is given ``cpc.predictors[:K]`` alone, the K
+    predictors the loss never reads stay as they are.
+
+    Returns ``losses`` and ``accuracies`` (per step; reading them synchronises once per step), ``steps``, ``batches``,
+    ``utterances`` and the speakers ``score_batches`` would name: ``speakers_skipped``, ``speakers_left_over``."""
+    S, U, K = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker, cpc.n_prediction_steps
+    dev = device if device is not None else next(encoder.parameters()).device
+    n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
+    res = {"losses": [], "accuracies": [], "steps": 0, "batches": n_batches, "utterances": n_batches * S * U,
+           "speakers_skipped": skipped, "speakers_left_over": left}
+    if n_batches == 0 or steps <= 0:
+        return res
+    opt = optimizer([p for m in cpc.predictors[:K] for p in m.parameters()], lr=lr)
+    encoded = {}
+    for step in range(steps):
+        b = step % n_batches
+        if b not in encoded:
+            with torch.no_grad():
+                z, c, _, _ = encoder(batch_mels(b))
+                if hasattr(encoder, "check"):
+                    encoder.check()
+            encoded[b] = (z.detach(), c.detach())
+        z, c = encoded[b]
+        opt.zero_grad(set_to_none=True)
+        with torch.enable_grad():
+            loss, acc = cpc(z, c, seed=seed, stream_id=b, differentiable=True)
+            loss.backward()
+        opt.step()
+        res["losses"].append(float(loss.detach()))
+        res["accuracies"].append(list(acc))
+        res["steps"] = step + 1
     return res
 
 

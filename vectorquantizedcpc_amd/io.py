@@ -94,6 +94,20 @@ def save_adapted_checkpoint(path, encoder_state: Dict[str, torch.Tensor], source
     torch.save(ck, path)
 
 
+def save_fitted_checkpoint(path, cpc_state: Dict[str, torch.Tensor], source=None, encoder_state=None):
+    """Write a checkpoint whose ``"cpc"`` entry is ``cpc_state`` -- all ``CPCLoss.state_dict()`` keys, the refitted predictors
+    and the unused ones alike (``driver.fit_predictors``), every tensor on the CPU -- with the other entries of the checkpoint
+    ``source`` was loaded from (``"encoder"``, ...) carried over untouched.  Without a ``source`` (seeded weights),
+    ``encoder_state`` becomes the ``"encoder"`` entry.  The counterpart of ``save_adapted_checkpoint``."""
+    ck = {}
+    if source is not None:
+        ck = {k: v for k, v in torch.load(source, map_location="cpu", weights_only=True).items() if k != "cpc"}
+    elif encoder_state is not None:
+        ck["encoder"] = {k: v.detach().cpu().clone() for k, v in encoder_state.items()}
+    ck["cpc"] = {k: v.detach().cpu().clone() for k, v in cpc_state.items()}
+    torch.save(ck, path)
+
+
 def load_cpc_checkpoint(path) -> Dict[str, torch.Tensor]:
     """``checkpoint["cpc"]`` (``train_cpc.py:23-29`` saves it next to ``"encoder"``), loaded without executing anything
     from the file."""

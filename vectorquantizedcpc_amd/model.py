@@ -301,15 +301,20 @@ class ConfCPC:
 
 
 class CPCLoss(_lib.NativeModule):
-    """``CPCLoss`` (``model.py:167-316``) as checkpoint SCORING on MI355X: the forward value of the objective -- InfoNCE
-    loss and per-step prediction accuracies -- in one fused HIP launch per batch.  No gradient flows: results are detached
-    and nothing here trains.
+    """``CPCLoss`` (``model.py:167-316``) on MI355X: the InfoNCE loss and per-step prediction accuracies in one fused HIP
+    launch per batch, and -- on request -- its gradient.
+
+    ``forward(z, c)`` is checkpoint SCORING: the value of the objective, detached.  ``forward(z, c, differentiable=True)`` under
+    grad mode returns a loss that ``backward()`` can be called on: ``vqcpc_cpc_grad`` (``csrc/cpc_grad.hip``) computes the loss
+    and the gradients with respect to ``z``, ``c`` and the first K predictors in one call, every sum in a fixed order, so equal
+    inputs give equal bits.  That is what ``driver.fit_predictors`` refits the predictors with on a frozen encoder; the encoder,
+    the VQ straight-through estimator and the context LSTM have no backward here, and the optimizer is torch's.
 
     All ``n_prediction_steps`` predictors are held (the reference's 24 ``state_dict()`` keys, so
     ``load_state_dict(checkpoint["cpc"])`` works unchanged); like the reference only the first half is ever used
-    (``model.py:181``).  The one deliberate difference is where the negatives come from: the reference draws them from
-    torch's global CPU generator, this class from a counter-based protocol keyed by ``(seed, stream_id)``
-    (``synth.cpc_negatives``), or from the caller (``negatives=``) for draw-for-draw comparisons."""
+    (``model.py:181``), and only that half ever receives a gradient.  The one deliberate difference is where the negatives
+    come from: the reference draws them from torch's global CPU generator, this class from a counter-based protocol keyed by
+    ``(seed, stream_id)`` (``synth.cpc_negatives``), or from the caller (``negatives=``) for draw-for-draw comparisons."""
 
     def __init__(self, conf: ConfCPC):
         super().__init__()
@@ -355,12 +360,8 @@ class CPCLoss(_lib.NativeModule):
                 raise IndexError(f"negatives {name} holds values in [{int(lo)}, {int(hi)}], outside [0, {high})")
         return utt.to(device).contiguous(), seq.to(device).contiguous()
 
-    @torch.no_grad()
-    def forward_detailed(self, z: Tensor, c: Tensor, negatives: Optional[Tuple[Tensor, Tensor]] = None, seed: int = 13,
-                         stream_id: int = 0, want_correct: bool = False, want_scores: bool = False) -> dict:
-        """``forward`` with everything the kernel computes, as device tensors: ``loss`` (0-dim), ``step_loss`` (K),
-        ``accuracy`` (K); on request ``correct`` (K, N, L) uint8 and ``scores`` (K, N, 1 + Neg, L) = ``f`` of
-        ``model.py:291``.  K = n_prediction_steps // 2, L = T - K.  Nothing is synchronised."""
+    def _check_inputs(self, z: Tensor, c: Tensor, negatives):
+        """The checks every call starts with.  -> (T, L, device, utt_index, seq_index), the index arrays on the device or None."""
         _lib.require_cuda(z, "z")
         _lib.require_cuda(c, "c")
         K, N = self.n_prediction_steps, self.n_speakers_per_batch * self.n_utterances_per_speaker
@@ -377,6 +378,16 @@ class CPCLoss(_lib.NativeModule):
         utt = seq = None
         if negatives is not None:
             utt, seq = self._check_negatives(negatives, L, dev)
+        return T, L, dev, utt, seq
+
+    @torch.no_grad()
+    def forward_detailed(self, z: Tensor, c: Tensor, negatives: Optional[Tuple[Tensor, Tensor]] = None, seed: int = 13,
+                         stream_id: int = 0, want_correct: bool = False, want_scores: bool = False) -> dict:
+        """``forward`` with everything the kernel computes, as device tensors: ``loss`` (0-dim), ``step_loss`` (K),
+        ``accuracy`` (K); on request ``correct`` (K, N, L) uint8 and ``scores`` (K, N, 1 + Neg, L) = ``f`` of
+        ``model.py:291``.  K = n_prediction_steps // 2, L = T - K.  Nothing is synchronised."""
+        K, N = self.n_prediction_steps, self.n_speakers_per_batch * self.n_utterances_per_speaker
+        T, L, dev, utt, seq = self._check_inputs(z, c, negatives)
         z = z.detach().to(torch.float32).contiguous()
         c = c.detach().to(torch.float32).contiguous()
         h = self._native()
@@ -392,15 +403,89 @@ class CPCLoss(_lib.NativeModule):
                 _lib.current_stream()))
         return {"loss": out[0], "step_loss": out[1:1 + K], "accuracy": out[1 + K:], "correct": correct, "scores": scores}
 
+    def _sizes_handle(self, dev):
+        """The handle for a call that reads the predictors from the CALLER's pointers (``vqcpc_cpc_grad``): it gives sizes and
+        work space only, so any live handle on ``dev`` serves -- also one whose copies an optimizer step has made stale.
+        ``_native()`` would answer the moved ``WeightSlots.key`` with destroy, create and a synchronisation per step; scoring
+        (``forward_detailed``) still goes through ``_native()`` and so never reads stale copies."""
+        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
+            return self._handle
+        return self._native()
+
+    def _grad_call(self, z, c, W, b, utt, seq, seed, stream_id, want):
+        """One ``vqcpc_cpc_grad`` call on contiguous fp32 device tensors.  want = (z, c, W, b) booleans.
+        -> (out = [loss, step_loss (K), accuracy (K)], the four gradients or None)."""
+        K, dev = self.n_prediction_steps, z.device
+        h = self._sizes_handle(dev)
+        out = torch.empty(1 + 2 * K, device=dev)
+        grads = [torch.empty_like(t) if w else None for t, w in zip((z, c, W, b), want)]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().vqcpc_cpc_grad(
+                h, z.data_ptr(), c.data_ptr(), z.size(1), W.data_ptr(), b.data_ptr(), ptr(utt), ptr(seq),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, out[0:].data_ptr(), out[1:].data_ptr(),
+                out[1 + K:].data_ptr(), *[ptr(g) for g in grads], _lib.current_stream()))
+        return out, grads
+
+    @torch.no_grad()
+    def gradients(self, z: Tensor, c: Tensor, negatives: Optional[Tuple[Tensor, Tensor]] = None, seed: int = 13, stream_id: int = 0,
+                  wrt: Tuple[str, ...] = ("z", "c", "W", "b")) -> dict:
+        """The ``vqcpc_cpc_grad`` call without autograd, as device tensors: ``loss`` (0-dim), ``step_loss`` (K), ``accuracy`` (K)
+        and, for every name in ``wrt``, the gradient of ``loss`` -- ``z`` (N, T, 64), ``c`` (N, T, c_dim), ``W`` (K, 64, c_dim) and
+        ``b`` (K, 64), the first K predictors stacked; a name not asked for maps to None.  Nothing is synchronised."""
+        K = self.n_prediction_steps
+        _, _, _, utt, seq = self._check_inputs(z, c, negatives)
+        W = torch.stack([m.weight for m in self.predictors[:K]]).to(torch.float32)
+        b = torch.stack([m.bias for m in self.predictors[:K]]).to(torch.float32)
+        out, grads = self._grad_call(z.detach().to(torch.float32).contiguous(), c.detach().to(torch.float32).contiguous(), W, b, utt, seq,
+                                     seed, stream_id, tuple(k in wrt for k in ("z", "c", "W", "b")))
+        return dict(zip(("z", "c", "W", "b"), grads), loss=out[0], step_loss=out[1:1 + K], accuracy=out[1 + K:])
+
     def forward(self, z: Tensor, c: Tensor, negatives: Optional[Tuple[Tensor, Tensor]] = None, seed: int = 13,
-                stream_id: int = 0) -> Tuple[Tensor, List[float]]:
-        """``model.py:191-316`` under ``no_grad``: ``(loss, accuracies)`` -- a 0-dim tensor on ``z``'s device and a list of
-        K floats (reading them costs one synchronisation, as ``.item()`` does in the reference, ``model.py:312``).
-        z (Spk * Utt, T, z_dim), c (Spk * Utt, T, c_dim), utterances speaker-major.  The result is detached: no gradient
-        flows through this class.
+                stream_id: int = 0, *, differentiable: bool = False) -> Tuple[Tensor, List[float]]:
+        """``model.py:191-316``: ``(loss, accuracies)`` -- a 0-dim tensor on ``z``'s device and a list of K floats (reading
+        them costs one synchronisation, as ``.item()`` does in the reference, ``model.py:312``).
+        z (Spk * Utt, T, z_dim), c (Spk * Utt, T, c_dim), utterances speaker-major.
+
+        differentiable=False (the default): scoring under ``no_grad``; the result is detached.  differentiable=True, grad mode on
+        and any of ``z``, ``c`` or the first K predictors requiring grad: the loss carries a ``grad_fn``; one ``vqcpc_cpc_grad``
+        call computes it together with the gradients that ``backward()`` will hand out (only those that are needed), and its
+        bits are those of the default call.  Predictors K .. 2K - 1 are not used and get no gradient.  Under ``torch.no_grad()``
+        the flag changes nothing.
 
         negatives: None = drawn in the kernel from ``(seed, stream_id)`` (``synth.cpc_negatives`` returns the same
         arrays), or ``(utt_index (K, Utt, Neg), seq_index (K, Spk, Utt, Neg, L))`` int64 = the index arrays of
         ``model.py:282`` for each step, e.g. what the reference drew."""
+        K = self.n_prediction_steps
+        if differentiable and torch.is_grad_enabled() and (
+                z.requires_grad or c.requires_grad or any(p.requires_grad for m in self.predictors[:K] for p in m.parameters())):
+            _, _, _, utt, seq = self._check_inputs(z, c, negatives)
+            W = torch.stack([m.weight for m in self.predictors[:K]])          # glue: autograd hands each predictor its slice
+            b = torch.stack([m.bias for m in self.predictors[:K]])
+            if W.dtype != torch.float32:
+                raise RuntimeError("CPCLoss: parameters must be float32")
+            loss, acc = _CPCGrad.apply(self, z.to(torch.float32), c.to(torch.float32), W, b, utt, seq, seed, stream_id)
+            return loss, acc.tolist()
         r = self.forward_detailed(z, c, negatives=negatives, seed=seed, stream_id=stream_id)
         return r["loss"], r["accuracy"].tolist()
+
+
+class _CPCGrad(torch.autograd.Function):
+    """``CPCLoss.forward(..., differentiable=True)``: ``forward`` makes the single ``vqcpc_cpc_grad`` call, asking for the
+    gradients ``needs_input_grad`` names, and keeps them; ``backward`` multiplies them by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, module, z, c, W, b, utt, seq, seed, stream_id):
+        want = ctx.needs_input_grad[1:5]
+        out, grads = module._grad_call(z.detach().contiguous(), c.detach().contiguous(), W.detach().contiguous(),
+                                       b.detach().contiguous(), utt, seq, seed, stream_id, want)
+        ctx.kept = grads
+        K = module.n_prediction_steps
+        loss, acc = out[0], out[1 + K:]
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_acc):
+        return (None,) + tuple(g * grad_loss if g is not None else None for g in ctx.kept) + (None, None, None, None)
