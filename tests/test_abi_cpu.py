@@ -91,6 +91,28 @@ def test_product_never_imports_oracle():
                 assert "#include \"../../oracle" not in text and "dlopen" not in text, f
 
 
+def test_device_memory_has_one_owner():
+    """All device and pinned memory of the library is a ``DevBuf`` / ``HostBuf`` (``csrc/common.h``) that frees itself: the
+    allocation calls appear in that file only, and no handle struct declares a raw device pointer of its own."""
+    csrc = os.path.join(ROOT, "vectorquantizedcpc_amd", "csrc")
+    borrowed = set()                  # "struct.member": raw pointers a handle may declare because it does not own them (none today)
+    structs = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        if f != "common.h":
+            found = re.findall(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\b", text)
+            assert not found, f"{f}: {sorted(set(found))} outside common.h"
+        for m in re.finditer(r"^struct (vqcpc_\w+|LstmPlan) \{\n(.*?)^\};", text, flags=re.M | re.S):
+            structs += 1
+            for decl in re.finditer(r"\b(?:float|double|unsigned)\s*\*[^;(]*=\s*nullptr[^;]*;", m.group(2)):
+                names = re.findall(r"\*\s*(\w+)\s*=\s*nullptr", decl.group(0))
+                raw = [n for n in names if f"{m.group(1)}.{n}" not in borrowed]
+                assert not raw, f"{f}: struct {m.group(1)} declares raw pointer member(s) {raw}"
+    assert structs >= 8               # the seven handle types and LstmPlan were seen
+
+
 def test_synth_is_deterministic():
     a = synth.encoder_state_dict()["encoder.2.weight"]
     b = synth.encoder_state_dict()["encoder.2.weight"]

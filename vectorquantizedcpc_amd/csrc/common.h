@@ -33,33 +33,65 @@ int vq_require_gfx950();             // VQCPC_OK, or VQCPC_ERR_NO_DEVICE with th
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Grow-only device buffer.
-struct DevBuf {
+// runtime.hip: bytes held by the live DevBufs / HostBufs of this process (vqcpc_debug_live_bytes)
+void vq_count_bytes(bool pinned, long long delta);
+
+// Grow-only memory that frees itself: device memory (DevBuf) or page-locked host memory (HostBuf; `host_flags` are
+// hipHostMalloc's and mean nothing to a DevBuf).  All device and pinned memory of the library is one of the two, a member of
+// a handle or a local: destroying a handle is `delete`.  Contents are not kept across a growth.
+template <bool PINNED> struct OwnedBuf {
     void *p = nullptr;
     size_t cap = 0;
-    int reserve(size_t bytes) {
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf &) = delete;
+    OwnedBuf &operator=(const OwnedBuf &) = delete;
+    ~OwnedBuf() { release(); }
+    int reserve(size_t bytes, unsigned host_flags = hipHostMallocDefault) {
         if (bytes <= cap) return VQCPC_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
+        release();
+        hipError_t e = PINNED ? hipHostMalloc(&p, bytes, host_flags) : hipMalloc(&p, bytes);
         if (e != hipSuccess) {
-            vq_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+            p = nullptr;
+            vq_set_error("%s(%zu) failed: %s", PINNED ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
             return VQCPC_ERR_ALLOC;
         }
         cap = bytes;
+        vq_count_bytes(PINNED, (long long)bytes);
         return VQCPC_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T **fresh() { release(); return (T **)&p; }    // for a callee that hipMallocs into *out (cap stays 0: size unrecorded)
+    void release() {
+        if (!p) return;
+        (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        vq_count_bytes(PINNED, -(long long)cap);
+        p = nullptr; cap = 0;
+    }
     template <class T> T *as() const { return (T *)p; }
 };
-// An owning device pointer: a DevBuf that reads as a T * and frees itself with the handle it is a member of.
+using DevBuf = OwnedBuf<false>;
+using HostBuf = OwnedBuf<true>;
+// The typed view: a DevBuf that reads as a T *.
 template <class T> struct DevPtr : DevBuf {
-    DevPtr() = default;
-    DevPtr(const DevPtr &) = delete;
-    DevPtr &operator=(const DevPtr &) = delete;
-    ~DevPtr() { release(); }
     operator T *() const { return (T *)p; }
+};
+// reserve, then copy `bytes` from src (host or device, by `kind`) with a blocking hipMemcpy
+inline int dev_copy(DevBuf &dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+    TRY(dst.reserve(bytes));
+    HIP_TRY(hipMemcpy(dst.p, src, bytes, kind));
+    return VQCPC_OK;
+}
+
+// A host-mapped word (on a 64-byte line of its own) that kernels write through `dev` and the host reads through `host`
+// without a HIP call: the status word of a vocoder, the abort flag of the resident context scan.
+struct PinnedWord {
+    HostBuf mem;
+    unsigned *host = nullptr, *dev = nullptr;
+    int create() {
+        TRY(mem.reserve(64, hipHostMallocMapped));
+        host = (unsigned *)mem.p;
+        *host = 0u;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        return VQCPC_OK;
+    }
 };
 
 // ---- exact-chain GEMM (gemm_chain.hip), also used for the hoisted projections of the vocoder.
@@ -75,8 +107,8 @@ int vq_gemm_chain_ex(const float *A, int lda, const float *W, const float *bias,
                      int M, int N, int K, int KC, int relu, int ydiv, int ystride, int yoff, int ylim, hipStream_t s);
 
 // ---- recurrent scans (scan.hip): the encoder's context LSTM and the vocoder prenet's bidirectional GRU layers.
-// W (n_rg row groups x K) in fragment order for the launch-per-step MFMA kernels; rowmode and layout: scan.hip.  *out is hipMalloc'ed.
-int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, float **out);
+// W (n_rg row groups x K) in fragment order for the launch-per-step MFMA kernels; rowmode and layout: scan.hip.  `out` is reserved here.
+int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, DevBuf &out);
 // One bidirectional GRU layer's T steps from zero state.  Gi: hoisted input projection [rows][2][3H] (+ b_ih); Wf: both directions'
 // W_hh, each from vq_build_wfrag(rowmode 3); b_hh [2][3H]; hbuf: 4 * ceil(B / 16) * 16 * H floats of state; out [rows][2H].
 // len / row0: valid steps and first row of every utterance (ragged rows), or null = T steps from row b * T.

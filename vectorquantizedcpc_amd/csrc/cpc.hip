@@ -41,13 +41,20 @@ __global__ __launch_bounds__(256) void cpc_score_kernel(CpcArgs a) {
 
 }  // namespace
 
-extern "C" void vqcpc_cpc_destroy(vqcpc_cpc *cpc) {
-    if (!cpc) return;
-    if (cpc->W) (void)hipFree(cpc->W);
-    if (cpc->bias) (void)hipFree(cpc->bias);
-    cpc->part_loss.release();
-    cpc->part_correct.release();
-    delete cpc;
+extern "C" void vqcpc_cpc_destroy(vqcpc_cpc *cpc) { delete cpc; }
+
+static int cpc_create_impl(const vqcpc_cpc_weights *w, vqcpc_cpc *h) {
+    h->n_steps = w->n_steps; h->Spk = w->n_speakers; h->Utt = w->n_utterances; h->Neg = w->n_negatives; h->C = w->c_dim;
+    HIP_TRY(hipGetDevice(&h->device));
+    const size_t wb = (size_t)CPC_D * h->C * sizeof(float), bb = CPC_D * sizeof(float);
+    TRY(h->W.reserve(wb * h->n_steps));
+    TRY(h->bias.reserve(bb * h->n_steps));
+    for (int k = 0; k < h->n_steps; ++k) {
+        HIP_TRY(hipMemcpy((char *)h->W.p + wb * k, w->weight[k], wb, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy((char *)h->bias.p + bb * k, w->bias[k], bb, hipMemcpyDeviceToDevice));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return VQCPC_OK;
 }
 
 extern "C" int vqcpc_cpc_create(const vqcpc_cpc_weights *w, vqcpc_cpc **out) {
@@ -63,19 +70,8 @@ extern "C" int vqcpc_cpc_create(const vqcpc_cpc_weights *w, vqcpc_cpc **out) {
                "vqcpc_cpc_create: n_speakers, n_utterances must be >= 1 and their product <= 65535");
     for (int k = 0; k < w->n_steps; ++k) VQ_REQUIRE(w->weight[k] && w->bias[k], "vqcpc_cpc_create: predictor %d is null", k);
     vqcpc_cpc *h = new vqcpc_cpc();
-    h->n_steps = w->n_steps; h->Spk = w->n_speakers; h->Utt = w->n_utterances; h->Neg = w->n_negatives; h->C = w->c_dim;
-    (void)hipGetDevice(&h->device);
-    const size_t wb = (size_t)CPC_D * h->C * sizeof(float), bb = CPC_D * sizeof(float);
-    bool ok = hipMalloc((void **)&h->W, wb * h->n_steps) == hipSuccess && hipMalloc((void **)&h->bias, bb * h->n_steps) == hipSuccess;
-    for (int k = 0; ok && k < h->n_steps; ++k)
-        ok = hipMemcpy((char *)h->W + wb * k, w->weight[k], wb, hipMemcpyDeviceToDevice) == hipSuccess &&
-             hipMemcpy((char *)h->bias + bb * k, w->bias[k], bb, hipMemcpyDeviceToDevice) == hipSuccess;
-    if (ok) ok = hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
-        vq_set_error("vqcpc_cpc_create: device allocation or copy failed: %s", hipGetErrorString(hipGetLastError()));
-        vqcpc_cpc_destroy(h);
-        return VQCPC_ERR_ALLOC;
-    }
+    int rc = cpc_create_impl(w, h);
+    if (rc != VQCPC_OK) { vqcpc_cpc_destroy(h); return rc; }
     *out = h;
     return VQCPC_OK;
 }
@@ -84,29 +80,14 @@ extern "C" int vqcpc_cpc_score(vqcpc_cpc *cpc, const float *z, const float *c, i
                                const int64_t *seq_index, uint64_t seed, uint32_t stream_id, float *loss, float *step_loss,
                                float *accuracy, uint8_t *correct, float *scores, void *stream) {
     VQ_REQUIRE(cpc && z && c && loss && step_loss && accuracy, "vqcpc_cpc_score: null argument");
-    VQ_REQUIRE((utt_index == nullptr) == (seq_index == nullptr), "vqcpc_cpc_score: give utt_index and seq_index together, or neither");
-    const int K = cpc->n_steps;
-    VQ_REQUIRE(T >= K + 2, "vqcpc_cpc_score: T = %d, need at least n_steps + 2 = %d frames (model.py:259 draws from [1, T - n_steps))", T, K + 2);
-    const int L = T - K, N = cpc->Spk * cpc->Utt;
-    VQ_REQUIRE((long long)N * cpc->Neg * L < (1ll << 31), "vqcpc_cpc_score: Spk * Utt * Neg * L = %lld does not fit the draw counter",
-               (long long)N * cpc->Neg * L);
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    VQ_REQUIRE(dev == cpc->device, "vqcpc_cpc_score: handle belongs to device %d, current device is %d", cpc->device, dev);
-    const int tiles = (L + CPC_TT - 1) / CPC_TT;
-    const size_t P = (size_t)N * tiles;
-    TRY(cpc->part_loss.reserve(P * K * sizeof(double)));
-    TRY(cpc->part_correct.reserve(P * K * sizeof(int)));
     CpcArgs a;
-    a.z = z; a.c = c; a.W = cpc->W; a.bias = cpc->bias;
-    a.utt_index = utt_index; a.seq_index = seq_index;
+    size_t P = 0;
+    TRY(cpc_begin(cpc, "vqcpc_cpc_score", z, c, T, nullptr, nullptr, utt_index, seq_index, seed, stream_id, a, P));
     a.scores = scores; a.correct = correct;
-    a.part_loss = cpc->part_loss.as<double>(); a.part_correct = cpc->part_correct.as<int>();
-    a.T = T; a.L = L; a.C = cpc->C; a.Spk = cpc->Spk; a.Utt = cpc->Utt; a.Neg = cpc->Neg; a.tiles = tiles;
-    a.stream_id = stream_id; a.key0 = (unsigned)(seed & 0xFFFFFFFFu); a.key1 = (unsigned)(seed >> 32);
+    const int K = cpc->n_steps, N = a.Spk * a.Utt;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cpc_score_kernel, dim3(tiles, N, K), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(cpc_finish_kernel, dim3(1), dim3(256), 0, s, a.part_loss, a.part_correct, K, (int)P, N * L, loss, step_loss,
+    hipLaunchKernelGGL(cpc_score_kernel, dim3(a.tiles, N, K), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(cpc_finish_kernel, dim3(1), dim3(256), 0, s, a.part_loss, a.part_correct, K, (int)P, N * a.L, loss, step_loss,
                        accuracy);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;

@@ -260,18 +260,12 @@ extern "C" int vqcpc_cpc_grad(vqcpc_cpc *cpc, const float *z, const float *c, in
                               void *stream) {
     VQ_REQUIRE(cpc && z && c && loss && step_loss && accuracy, "vqcpc_cpc_grad: null argument");
     VQ_REQUIRE((W == nullptr) == (bias == nullptr), "vqcpc_cpc_grad: give W and bias together, or neither (the handle's copies)");
-    VQ_REQUIRE((utt_index == nullptr) == (seq_index == nullptr), "vqcpc_cpc_grad: give utt_index and seq_index together, or neither");
-    const int K = cpc->n_steps;
-    VQ_REQUIRE(T >= K + 2, "vqcpc_cpc_grad: T = %d, need at least n_steps + 2 = %d frames (model.py:259 draws from [1, T - n_steps))", T, K + 2);
-    const int L = T - K, N = cpc->Spk * cpc->Utt, C = cpc->C, J = 1 + cpc->Neg;
-    VQ_REQUIRE((long long)N * cpc->Neg * L < (1ll << 31), "vqcpc_cpc_grad: Spk * Utt * Neg * L = %lld does not fit the draw counter",
-               (long long)N * cpc->Neg * L);
+    CpcGradArgs ga;
+    CpcArgs &a = ga.f;
+    size_t P = 0;
+    TRY(cpc_begin(cpc, "vqcpc_cpc_grad", z, c, T, W, bias, utt_index, seq_index, seed, stream_id, a, P));
+    const int K = cpc->n_steps, L = a.L, N = a.Spk * a.Utt, C = a.C, J = 1 + a.Neg, tiles = a.tiles;
     VQ_REQUIRE((long long)N * T < (1ll << 31), "vqcpc_cpc_grad: Spk * Utt * T = %lld rows do not fit a 32-bit row index", (long long)N * T);
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    VQ_REQUIRE(dev == cpc->device, "vqcpc_cpc_grad: handle belongs to device %d, current device is %d", cpc->device, dev);
-    const int tiles = (L + CPC_TT - 1) / CPC_TT;
-    const size_t P = (size_t)N * tiles;
     const int slabs = (int)(((long long)N * L + GW_SLAB - 1) / GW_SLAB);
     VQ_REQUIRE(slabs <= 65535, "vqcpc_cpc_grad: Spk * Utt * L = %lld rows, more than 65535 slabs of %d", (long long)N * L, GW_SLAB);
     const bool want_w = grad_W || grad_bias;
@@ -279,8 +273,6 @@ extern "C" int vqcpc_cpc_grad(vqcpc_cpc *cpc, const float *z, const float *c, in
     const size_t b_rows = up256((size_t)K * N * L * CPC_D * sizeof(float)), b_g = up256((size_t)K * N * J * L * sizeof(float));
     const size_t b_s = up256((size_t)K * N * cpc->Neg * L * sizeof(int)), b_u = up256((size_t)K * cpc->Utt * cpc->Neg * sizeof(int));
     const size_t b_part = up256((size_t)K * slabs * CPC_D * (C + 16) * sizeof(float));
-    TRY(cpc->part_loss.reserve(P * K * sizeof(double)));
-    TRY(cpc->part_correct.reserve(P * K * sizeof(int)));
     TRY(cpc->grad_work.reserve(b_rows + (grad_z ? 2 * b_rows + b_g + b_s + b_u : 0) + (want_w ? b_part : 0)));
     char *w = cpc->grad_work.as<char>();
     float *dWc = (float *)w; w += b_rows;
@@ -294,14 +286,6 @@ extern "C" int vqcpc_cpc_grad(vqcpc_cpc *cpc, const float *z, const float *c, in
         u_buf = (int *)w; w += b_u;
     }
     if (want_w) part = (float *)w;
-    CpcGradArgs ga;
-    CpcArgs &a = ga.f;
-    a.z = z; a.c = c; a.W = W ? W : cpc->W; a.bias = W ? bias : cpc->bias;
-    a.utt_index = utt_index; a.seq_index = seq_index;
-    a.scores = nullptr; a.correct = nullptr;
-    a.part_loss = cpc->part_loss.as<double>(); a.part_correct = cpc->part_correct.as<int>();
-    a.T = T; a.L = L; a.C = C; a.Spk = cpc->Spk; a.Utt = cpc->Utt; a.Neg = cpc->Neg; a.tiles = tiles;
-    a.stream_id = stream_id; a.key0 = (unsigned)(seed & 0xFFFFFFFFu); a.key1 = (unsigned)(seed >> 32);
     ga.dWc = dWc; ga.Wc = Wc; ga.g = g; ga.u_out = u_buf; ga.s_out = s_buf;
     ga.count = (float)((double)K * N * L);
     hipStream_t s = (hipStream_t)stream;

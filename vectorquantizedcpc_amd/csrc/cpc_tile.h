@@ -160,7 +160,34 @@ __global__ __launch_bounds__(256) void cpc_finish_kernel(const double *part_loss
 struct vqcpc_cpc {
     int device = 0;
     int n_steps = 0, Spk = 0, Utt = 0, Neg = 0, C = 0;
-    float *W = nullptr, *bias = nullptr;
+    DevPtr<float> W, bias;           // the handle's copies of the first n_steps predictors, stacked
     DevBuf part_loss, part_correct;
-    DevPtr<char> grad_work;          // vqcpc_cpc_grad's work space (cpc_grad.hip); frees itself with the handle
+    DevPtr<char> grad_work;          // vqcpc_cpc_grad's work space (cpc_grad.hip)
 };
+
+// What vqcpc_cpc_score and vqcpc_cpc_grad (`what`: the entry's name, for the messages) share before their launches: the
+// checks of the shape, the draw counter, the index pair and the device, the two partial buffers (P partials per step), and
+// the kernel argument -- reading the handle's predictors unless the caller gives W and bias; scores / correct left null.
+static int cpc_begin(vqcpc_cpc *cpc, const char *what, const float *z, const float *c, int T, const float *W, const float *bias,
+                     const int64_t *utt_index, const int64_t *seq_index, uint64_t seed, uint32_t stream_id, CpcArgs &a, size_t &P) {
+    VQ_REQUIRE((utt_index == nullptr) == (seq_index == nullptr), "%s: give utt_index and seq_index together, or neither", what);
+    const int K = cpc->n_steps;
+    VQ_REQUIRE(T >= K + 2, "%s: T = %d, need at least n_steps + 2 = %d frames (model.py:259 draws from [1, T - n_steps))", what, T, K + 2);
+    const int L = T - K, N = cpc->Spk * cpc->Utt;
+    VQ_REQUIRE((long long)N * cpc->Neg * L < (1ll << 31), "%s: Spk * Utt * Neg * L = %lld does not fit the draw counter", what,
+               (long long)N * cpc->Neg * L);
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    VQ_REQUIRE(dev == cpc->device, "%s: handle belongs to device %d, current device is %d", what, cpc->device, dev);
+    const int tiles = (L + CPC_TT - 1) / CPC_TT;
+    P = (size_t)N * tiles;
+    TRY(cpc->part_loss.reserve(P * K * sizeof(double)));
+    TRY(cpc->part_correct.reserve(P * K * sizeof(int)));
+    a.z = z; a.c = c; a.W = W ? W : cpc->W.as<float>(); a.bias = W ? bias : cpc->bias.as<float>();
+    a.utt_index = utt_index; a.seq_index = seq_index;
+    a.scores = nullptr; a.correct = nullptr;
+    a.part_loss = cpc->part_loss.as<double>(); a.part_correct = cpc->part_correct.as<int>();
+    a.T = T; a.L = L; a.C = cpc->C; a.Spk = cpc->Spk; a.Utt = cpc->Utt; a.Neg = cpc->Neg; a.tiles = tiles;
+    a.stream_id = stream_id; a.key0 = (unsigned)(seed & 0xFFFFFFFFu); a.key1 = (unsigned)(seed >> 32);
+    return VQCPC_OK;
+}

@@ -30,12 +30,6 @@ struct vqcpc_encoder {
 
 extern "C" void vqcpc_encoder_destroy(vqcpc_encoder *e) { delete e; }
 
-static int dev_copy(DevPtr<float> &dst, const float *src, size_t n) {
-    TRY(dst.reserve(n * sizeof(float)));
-    HIP_TRY(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
-    return VQCPC_OK;
-}
-
 static int build_frag16(const float *W, int N, int K, DevPtr<float4> &out) {
     VQ_REQUIRE(N % 16 == 0 && K % 64 == 0, "build_frag16: unsupported shape (%d, %d)", N, K);
     TRY(out.reserve((size_t)(N / 16) * (K / 16) * 64 * sizeof(float4)));
@@ -54,11 +48,15 @@ static int encoder_create_impl(const vqcpc_encoder_weights *w, vqcpc_encoder *e)
     TRY(e->conv_w2.reserve(nconv * sizeof(float)));
     launch_conv_weight_permute(w->conv_weight, e->conv_w1, e->conv_w2, CH, C);
     HIP_TRY(hipGetLastError());
-    for (int i = 0; i < 5; ++i) { TRY(dev_copy(e->ln_g[i], w->ln_weight[i], CH)); TRY(dev_copy(e->ln_b[i], w->ln_bias[i], CH)); }
-    for (int i = 0; i < 4; ++i) TRY(dev_copy(e->fc_w[i], w->fc_weight[i], (size_t)CH * CH));
-    TRY(dev_copy(e->out_w, w->out_weight, (size_t)w->z_dim * CH));
-    TRY(dev_copy(e->out_b, w->out_bias, w->z_dim));
-    TRY(dev_copy(e->codebook, w->codebook, (size_t)w->n_embeddings * w->z_dim));
+    const hipMemcpyKind D2D = hipMemcpyDeviceToDevice;
+    for (int i = 0; i < 5; ++i) {
+        TRY(dev_copy(e->ln_g[i], w->ln_weight[i], CH * sizeof(float), D2D));
+        TRY(dev_copy(e->ln_b[i], w->ln_bias[i], CH * sizeof(float), D2D));
+    }
+    for (int i = 0; i < 4; ++i) TRY(dev_copy(e->fc_w[i], w->fc_weight[i], (size_t)CH * CH * sizeof(float), D2D));
+    TRY(dev_copy(e->out_w, w->out_weight, (size_t)w->z_dim * CH * sizeof(float), D2D));
+    TRY(dev_copy(e->out_b, w->out_bias, w->z_dim * sizeof(float), D2D));
+    TRY(dev_copy(e->codebook, w->codebook, (size_t)w->n_embeddings * w->z_dim * sizeof(float), D2D));
     TRY(e->e2.reserve(w->n_embeddings * sizeof(float)));
     launch_rowsumsq64(e->codebook, e->e2, w->n_embeddings);
     TRY(e->cbfrag.reserve((size_t)w->n_embeddings * 64 * sizeof(float)));

@@ -176,12 +176,7 @@ static int blocks_of(int n, int rate, std::vector<int> *l, std::vector<int> *u, 
     return nb;
 }
 
-extern "C" void vqcpc_loudness_destroy(vqcpc_loudness *m) {
-    if (!m) return;
-    DevBuf *bufs[] = {&m->lens, &m->r, &m->sq, &m->z, &m->bl, &m->bu, &m->bb, &m->boff, &m->gain};
-    for (DevBuf *b : bufs) b->release();
-    delete m;
-}
+extern "C" void vqcpc_loudness_destroy(vqcpc_loudness *m) { delete m; }
 
 extern "C" int vqcpc_loudness_create(int rate, vqcpc_loudness **out) {
     VQ_REQUIRE(out, "vqcpc_loudness_create: null argument");

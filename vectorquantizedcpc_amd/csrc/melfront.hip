@@ -16,7 +16,7 @@ struct vqcpc_melfront {
     int sr, n_fft, n_mels, hop, win;
     float fmin, preemph, top_db;
     int Kp, nbins, nbp, nmp;              // padded window, bins, padded bins, padded mels
-    float *dftW = nullptr, *melW = nullptr;
+    DevPtr<float> dftW, melW;             // [cos | sin] x Hann matrix (2 nbp, Kp); mel filterbank (nmp, nbp)
     DevBuf frames, spec, mag, melraw, peak, maxdb, lens;
 };
 
@@ -124,14 +124,7 @@ static double mel2hz(double m) {
     return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
 
-extern "C" void vqcpc_melfront_destroy(vqcpc_melfront *f) {
-    if (!f) return;
-    if (f->dftW) (void)hipFree(f->dftW);
-    if (f->melW) (void)hipFree(f->melW);
-    DevBuf *bufs[] = {&f->frames, &f->spec, &f->mag, &f->melraw, &f->peak, &f->maxdb, &f->lens};
-    for (DevBuf *b : bufs) b->release();
-    delete f;
-}
+extern "C" void vqcpc_melfront_destroy(vqcpc_melfront *f) { delete f; }
 
 extern "C" int vqcpc_melfront_create(int sr, int n_fft, int n_mels, int hop, int win, float fmin, float preemph,
                                      float top_db, vqcpc_melfront **out) {
@@ -167,14 +160,8 @@ extern "C" int vqcpc_melfront_create(int sr, int n_fft, int n_mels, int hop, int
             Mw[(size_t)i * nbp + k] = (float)(v * enorm);
         }
     }
-    int rc = VQCPC_OK;
-    if (hipMalloc((void **)&f->dftW, W.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&f->melW, Mw.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->dftW, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->melW, Mw.data(), Mw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        vq_set_error("vqcpc_melfront_create: device allocation or copy failed");
-        rc = VQCPC_ERR_ALLOC;
-    }
+    int rc = dev_copy(f->dftW, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (rc == VQCPC_OK) rc = dev_copy(f->melW, Mw.data(), Mw.size() * sizeof(float), hipMemcpyHostToDevice);
     if (rc != VQCPC_OK) { vqcpc_melfront_destroy(f); return rc; }
     *out = f;
     return VQCPC_OK;

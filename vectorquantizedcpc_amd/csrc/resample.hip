@@ -13,7 +13,7 @@ struct vqcpc_resampler {
     int sr_in, sr_out;
     double ratio, scale, time_increment;
     int num_table, index_step, nwin;
-    double *win = nullptr, *delta = nullptr;     // device, nwin entries each
+    DevPtr<double> win, delta;                   // nwin entries each
     // resampy advances its output clock by repeated fp64 addition (time_register += time_increment); t * increment
     // differs from that sum in the last bits, and where the clock lands within rounding of an integer the two pick
     // different filter phases (resampy's integer index step makes that a 5e-4 jump).  So the clock values are produced
@@ -75,13 +75,7 @@ static double bessel_i0(double x) {                              // power series
     return sum;
 }
 
-extern "C" void vqcpc_resampler_destroy(vqcpc_resampler *r) {
-    if (!r) return;
-    if (r->win) (void)hipFree(r->win);
-    if (r->delta) (void)hipFree(r->delta);
-    r->treg.release();
-    delete r;
-}
+extern "C" void vqcpc_resampler_destroy(vqcpc_resampler *r) { delete r; }
 
 extern "C" int vqcpc_resampler_create(int sr_in, int sr_out, vqcpc_resampler **out) {
     VQ_REQUIRE(out, "vqcpc_resampler_create: null argument");
@@ -100,7 +94,11 @@ extern "C" int vqcpc_resampler_create(int sr_in, int sr_out, vqcpc_resampler **o
     r->index_step = (int)(r->scale * r->num_table);
     const int n = r->num_table * num_zeros;
     r->nwin = n + 1;
-    if (r->index_step < 1) { delete r; vq_set_error("vqcpc_resampler_create: rate ratio %g too small", r->ratio); return VQCPC_ERR_INVALID; }
+    if (r->index_step < 1) {
+        vq_set_error("vqcpc_resampler_create: rate ratio %g too small", r->ratio);
+        vqcpc_resampler_destroy(r);
+        return VQCPC_ERR_INVALID;
+    }
     std::vector<double> win(n + 1), delta(n + 1, 0.0);
     const double i0b = bessel_i0(beta);
     for (int i = 0; i <= n; ++i) {
@@ -113,14 +111,8 @@ extern "C" int vqcpc_resampler_create(int sr_in, int sr_out, vqcpc_resampler **o
         if (r->ratio < 1.0) win[i] *= r->ratio;
     }
     for (int i = 0; i < n; ++i) delta[i] = win[i + 1] - win[i];
-    int rc = VQCPC_OK;
-    if (hipMalloc((void **)&r->win, win.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&r->delta, delta.size() * sizeof(double)) != hipSuccess ||
-        hipMemcpy(r->win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r->delta, delta.data(), delta.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        vq_set_error("vqcpc_resampler_create: device allocation or copy failed");
-        rc = VQCPC_ERR_ALLOC;
-    }
+    int rc = dev_copy(r->win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (rc == VQCPC_OK) rc = dev_copy(r->delta, delta.data(), delta.size() * sizeof(double), hipMemcpyHostToDevice);
     if (rc != VQCPC_OK) { vqcpc_resampler_destroy(r); return rc; }
     *out = r;
     return VQCPC_OK;
@@ -146,8 +138,7 @@ extern "C" int vqcpc_resampler_run(vqcpc_resampler *r, const float *wav_in, cons
         double acc = 0.0;
         for (int t = 0; t < want; ++t) { tr[t] = acc; acc += r->time_increment; }
         HIP_TRY(hipStreamSynchronize(s));                       // earlier launches may still read the old table
-        TRY(r->treg.reserve((size_t)want * sizeof(double)));
-        HIP_TRY(hipMemcpy(r->treg.p, tr.data(), (size_t)want * sizeof(double), hipMemcpyHostToDevice));
+        TRY(dev_copy(r->treg, tr.data(), (size_t)want * sizeof(double), hipMemcpyHostToDevice));
         r->treg_len = want;
     }
     for (int b0 = 0; b0 < B; b0 += RS_MAXB) {                    // lengths travel as kernel arguments: no host-table upload, no sync

@@ -1,6 +1,7 @@
 // runtime.hip -- what every part of libvqcpc_hip.so shares at run time: the per-thread error string, the ABI version and
 // the device query (the library is built for gfx950 only and has no CPU fallback).
 #include "common.h"
+#include <atomic>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -24,6 +25,19 @@ extern "C" int vqcpc_device_count(void) {
     }
     return ok;
 }
+
+// Device and pinned bytes the library holds: every DevBuf / HostBuf reports what it allocates and frees (one atomic add per
+// (re)allocation, nothing on a call that grows no buffer).  Test surface beside vqcpc_probe_gates, not in include/vqcpc.h:
+// once every handle made since a reading is destroyed, both counts are back at that reading, exactly.
+static std::atomic<long long> g_live_bytes[2];
+void vq_count_bytes(bool pinned, long long delta) { g_live_bytes[pinned].fetch_add(delta, std::memory_order_relaxed); }
+extern "C" int vqcpc_debug_live_bytes(uint64_t *device, uint64_t *pinned) {
+    VQ_REQUIRE(device && pinned, "vqcpc_debug_live_bytes: null argument");
+    *device = (uint64_t)g_live_bytes[0].load(std::memory_order_relaxed);
+    *pinned = (uint64_t)g_live_bytes[1].load(std::memory_order_relaxed);
+    return VQCPC_OK;
+}
+
 int vq_require_gfx950() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) {

@@ -36,11 +36,11 @@ __global__ void build_wfrag_kernel(const float *__restrict__ W, int ldw, float *
     ((float4 *)Wf)[id] = v;
 }
 
-int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, float **out) {
+int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, DevBuf &out) {
     VQ_REQUIRE(K % (16 * ksplit) == 0 && ldw % 4 == 0, "build_wfrag: K=%d not a multiple of %d", K, 16 * ksplit);
     const size_t n4 = (size_t)n_rg * (K / 16) * 64;
-    HIP_TRY(hipMalloc((void **)out, n4 * sizeof(float4)));
-    hipLaunchKernelGGL(build_wfrag_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, ldw, *out, n_rg, K,
+    TRY(out.reserve(n4 * sizeof(float4)));
+    hipLaunchKernelGGL(build_wfrag_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, ldw, out.as<float>(), n_rg, K,
                        ksplit, rowmode, H);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
@@ -153,26 +153,17 @@ __global__ void add_vec_kernel(const float *a, const float *b, float *o, int n) 
 // ---- encoder LSTM plan (model.py:57)
 struct LstmPlan {
     int D, H;
-    float *w_ih = nullptr, *bias = nullptr, *Wf = nullptr;
-    float *w_hh = nullptr;               // plain [4H][H] copy for the persistent single-utterance scan
+    DevPtr<float> w_ih, bias, Wf;
+    DevPtr<float> w_hh;                  // plain [4H][H] copy for the persistent single-utterance scan
     DevBuf gi, hbuf, cbuf, px;
-    unsigned *abort_host = nullptr;      // pinned, host-mapped: a timed-out exchange of the persistent scan is reported by the next call
+    PinnedWord abort;                    // a timed-out exchange of the persistent scan is reported by the next call
     int persistent = -1;                 // -1 auto (one utterance, H = 256), 0 off, 2 = auto with agent-scope stores forced (tests)
     bool pending = false;                // a persistent scan may have raised the flag
     int dbg_drop_step = -1;              // tests: worker 3 skips its publish at this step -> the others time out
     int timeout_ms = 1000;               // bound of the scan's in-kernel waits
 };
 static int lstm_persist_launch(LstmPlan *p, int T, float *out, hipStream_t s);
-void vq_lstm_plan_destroy(LstmPlan *p) {
-    if (!p) return;
-    if (p->w_ih) (void)hipFree(p->w_ih);
-    if (p->bias) (void)hipFree(p->bias);
-    if (p->Wf) (void)hipFree(p->Wf);
-    if (p->w_hh) (void)hipFree(p->w_hh);
-    if (p->abort_host) (void)hipHostFree(p->abort_host);
-    p->gi.release(); p->hbuf.release(); p->cbuf.release(); p->px.release();
-    delete p;
-}
+void vq_lstm_plan_destroy(LstmPlan *p) { delete p; }
 int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int D, int H,
                         LstmPlan **out) {
     VQ_REQUIRE(D % 32 == 0 && (H == 64 || H == 128 || H == 256 || H == 512), "LSTM: need D %% 32 == 0 and a hidden size of 64, 128, 256 "
@@ -180,17 +171,13 @@ int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih,
     LstmPlan *p = new LstmPlan();
     p->D = D; p->H = H;
     *out = p;
-    HIP_TRY(hipMalloc((void **)&p->w_ih, (size_t)4 * H * D * sizeof(float)));
-    HIP_TRY(hipMemcpy(p->w_ih, w_ih, (size_t)4 * H * D * sizeof(float), hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMalloc((void **)&p->bias, (size_t)4 * H * sizeof(float)));
-    hipLaunchKernelGGL(add_vec_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, 0, b_ih, b_hh, p->bias, 4 * H);
+    TRY(dev_copy(p->w_ih, w_ih, (size_t)4 * H * D * sizeof(float), hipMemcpyDeviceToDevice));
+    TRY(p->bias.reserve((size_t)4 * H * sizeof(float)));
+    hipLaunchKernelGGL(add_vec_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, 0, b_ih, b_hh, p->bias.as<float>(), 4 * H);
     HIP_TRY(hipGetLastError());
-    TRY(vq_build_wfrag(w_hh, H, H / 4, H, 4, 4, H, &p->Wf));
-    HIP_TRY(hipMalloc((void **)&p->w_hh, (size_t)4 * H * H * sizeof(float)));
-    HIP_TRY(hipMemcpy(p->w_hh, w_hh, (size_t)4 * H * H * sizeof(float), hipMemcpyDeviceToDevice));
-    HIP_TRY(hipHostMalloc((void **)&p->abort_host, 64, hipHostMallocMapped));
-    *p->abort_host = 0u;
-    return VQCPC_OK;
+    TRY(vq_build_wfrag(w_hh, H, H / 4, H, 4, 4, H, p->Wf));
+    TRY(dev_copy(p->w_hh, w_hh, (size_t)4 * H * H * sizeof(float), hipMemcpyDeviceToDevice));
+    return p->abort.create();
 }
 int vq_lstm_set_persistent(LstmPlan *p, int value) { p->persistent = value; return VQCPC_OK; }
 int vq_lstm_set_debug(LstmPlan *p, int drop_step, int timeout_ms) { p->dbg_drop_step = drop_step; p->timeout_ms = timeout_ms; return VQCPC_OK; }
@@ -199,8 +186,8 @@ int vq_lstm_set_debug(LstmPlan *p, int drop_step, int timeout_ms) { p->dbg_drop_
 int vq_lstm_check(LstmPlan *p) {
     if (!p->pending) return VQCPC_OK;
     p->pending = false;
-    if (*(volatile unsigned *)p->abort_host != 0u) {
-        *p->abort_host = 0u;
+    if (*(volatile unsigned *)p->abort.host != 0u) {
+        *p->abort.host = 0u;
         p->persistent = 0;
         vq_set_error("encoder LSTM: an in-kernel exchange of the resident scan timed out (the context of that call is incomplete); "
                      "this handle now uses one launch per time step -- call again");
@@ -408,7 +395,7 @@ static int lstm_persist_launch(LstmPlan *p, int T, float *out, hipStream_t s) {
     q.force_agent = p->persistent == 2;
     q.dbg_drop_step = p->dbg_drop_step;
     q.timeout_ticks = (unsigned)p->timeout_ms * 100000u;
-    HIP_TRY(hipHostGetDevicePointer((void **)&q.abort_flag, p->abort_host, 0));
+    q.abort_flag = p->abort.dev;
     hipLaunchKernelGGL(lstm_persist_kernel, dim3(8 * LP_NW), dim3(256), 0, s, q);
     HIP_TRY(hipGetLastError());
     p->pending = true;

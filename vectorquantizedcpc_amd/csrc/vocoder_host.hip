@@ -64,42 +64,32 @@ static void clear_graphs(vqcpc_vocoder *v) {
     for (auto &G : v->grp) clear_graphs(G);
 }
 
-// Every device allocation of the handle, freed by vqcpc_vocoder_destroy: the grow-only work buffers, which
-// vqcpc_vocoder_workspace_bytes counts, and with `fixed` the weights and call records made at create, which it does not.
-static std::vector<DevBuf *> device_buffers(vqcpc_vocoder *v, bool fixed) {
-    std::vector<DevBuf *> b = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c, &v->nll_part, &v->nll_len,
-                               &v->xd_x, &v->xd_segs};
+// The grow-only work buffers, which vqcpc_vocoder_workspace_bytes sums (the weights and call records made at create are not
+// counted).  Nothing is freed through this list: every buffer is an owning member.
+static std::vector<const DevBuf *> work_buffers(const vqcpc_vocoder *v) {
+    std::vector<const DevBuf *> b = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c, &v->nll_part,
+                                     &v->nll_len, &v->xd_x, &v->xd_segs};
     for (auto &G : v->grp) b.insert(b.end(), {&G.har, &G.a1, &G.cand_s, &G.cand_k, &G.slot_tab, &G.cur, &G.gcur, &G.candg});
-    if (!fixed) return b;
-    b.insert(b.end(), {&v->code_emb, &v->spk_emb, &v->w_cond, &v->b_ih, &v->Gemb, &v->Gemb4, &v->bh4, &v->Wf_hh12, &v->Wf_hh16, &v->b_hh, &v->Wf_fc1,
-                       &v->Wf_fc1h, &v->b_fc1, &v->Wf_fc2, &v->b_fc2, &v->w_fc1, &v->w_fc2, &v->mulaw_tab, &v->w_hh, &v->grp[0].call, &v->grp[1].call});
-    for (int l = 0; l < 2; ++l) b.insert(b.end(), {&v->p_wih[l], &v->p_bih[l], &v->p_bhh[l], &v->p_wf[l]});
     return b;
 }
 
-static int dcopy(DevBuf &dst, const float *src, size_t n) {
-    TRY(dst.reserve(n * sizeof(float)));
-    HIP_TRY(hipMemcpy(dst.p, src, n * sizeof(float), hipMemcpyDeviceToDevice));
-    return VQCPC_OK;
+// The members free their memory; what is not memory goes here, before they die.
+vqcpc_vocoder::~vqcpc_vocoder() {
+    clear_graphs(this);
+    stage.drain();
+    for (hipStream_t st : {side_stream, cap_stream}) if (st) (void)hipStreamDestroy(st);
+    for (hipEvent_t e : {ev_fork, ev_join, ev0, ev1}) if (e) (void)hipEventDestroy(e);
 }
 
-extern "C" void vqcpc_vocoder_destroy(vqcpc_vocoder *v) {
-    if (!v) return;
-    clear_graphs(v);
-    for (DevBuf *b : device_buffers(v, true)) b->release();
-    v->stage.release();
-    if (v->status_host) (void)hipHostFree(v->status_host);
-    for (hipStream_t st : {v->side_stream, v->cap_stream}) if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : {v->ev_fork, v->ev_join, v->ev0, v->ev1}) if (e) (void)hipEventDestroy(e);
-    delete v;
-}
+extern "C" void vqcpc_vocoder_destroy(vqcpc_vocoder *v) { delete v; }
 
 static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v) {
     v->d = *w;
     const int F = w->dz + w->ds, Hp = w->Hp, dl = 2 * Hp, Hr = w->Hr, de = w->de;
-    struct Temps { DevBuf w_emb, emb, frag; ~Temps() { w_emb.release(); emb.release(); frag.release(); } } tmp;   // freed on every way out
-    TRY(dcopy(v->code_emb, w->code_embedding, (size_t)w->n_codes * w->dz));
-    TRY(dcopy(v->spk_emb, w->speaker_embedding, (size_t)w->n_speakers * w->ds));
+    const hipMemcpyKind D2D = hipMemcpyDeviceToDevice;
+    DevBuf w_emb, emb;                   // temporaries of the Gemb table
+    TRY(dev_copy(v->code_emb, w->code_embedding, (size_t)w->n_codes * w->dz * sizeof(float), D2D));
+    TRY(dev_copy(v->spk_emb, w->speaker_embedding, (size_t)w->n_speakers * w->ds * sizeof(float), D2D));
     for (int l = 0; l < 2; ++l) {
         const int I = l == 0 ? F : dl;
         TRY(v->p_wih[l].reserve((size_t)6 * Hp * I * sizeof(float)));
@@ -107,42 +97,42 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
         TRY(v->p_bhh[l].reserve((size_t)6 * Hp * sizeof(float)));
         TRY(v->p_wf[l].reserve((size_t)2 * (Hp / 4) * (Hp / 16) * 64 * sizeof(float4)));
         for (int d = 0; d < 2; ++d) {
-            HIP_TRY(hipMemcpy(v->p_wih[l] + (size_t)d * 3 * Hp * I, w->prenet_w_ih[l][d], (size_t)3 * Hp * I * sizeof(float), hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(v->p_bih[l] + (size_t)d * 3 * Hp, w->prenet_b_ih[l][d], (size_t)3 * Hp * sizeof(float), hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(v->p_bhh[l] + (size_t)d * 3 * Hp, w->prenet_b_hh[l][d], (size_t)3 * Hp * sizeof(float), hipMemcpyDeviceToDevice));
-            TRY(vq_build_wfrag(w->prenet_w_hh[l][d], Hp, Hp / 4, Hp, 4, 3, Hp, tmp.frag.fresh<float>()));
-            const size_t nb = (size_t)(Hp / 4) * (Hp / 16) * 64 * sizeof(float4);
-            HIP_TRY(hipMemcpy((char *)v->p_wf[l].p + d * nb, tmp.frag.p, nb, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(v->p_wih[l] + (size_t)d * 3 * Hp * I, w->prenet_w_ih[l][d], (size_t)3 * Hp * I * sizeof(float), D2D));
+            HIP_TRY(hipMemcpy(v->p_bih[l] + (size_t)d * 3 * Hp, w->prenet_b_ih[l][d], (size_t)3 * Hp * sizeof(float), D2D));
+            HIP_TRY(hipMemcpy(v->p_bhh[l] + (size_t)d * 3 * Hp, w->prenet_b_hh[l][d], (size_t)3 * Hp * sizeof(float), D2D));
+            DevBuf frag;                 // one direction's W_hh in fragment order
+            TRY(vq_build_wfrag(w->prenet_w_hh[l][d], Hp, Hp / 4, Hp, 4, 3, Hp, frag));
+            HIP_TRY(hipMemcpy((char *)v->p_wf[l].p + d * frag.cap, frag.p, frag.cap, D2D));
         }
     }
     // AR input weights split: [:, :de] feeds the sample embedding (-> lookup table Gemb), [:, de:] the conditioning
-    TRY(tmp.w_emb.reserve((size_t)3 * Hr * de * sizeof(float)));
+    TRY(w_emb.reserve((size_t)3 * Hr * de * sizeof(float)));
     TRY(v->w_cond.reserve((size_t)3 * Hr * dl * sizeof(float)));
     hipLaunchKernelGGL(copy_submatrix_kernel, dim3((unsigned)(((size_t)3 * Hr * de + 255) / 256)), dim3(256), 0, 0,
-                       w->ar_w_ih, de + dl, 0, tmp.w_emb.as<float>(), 3 * Hr, de);
+                       w->ar_w_ih, de + dl, 0, w_emb.as<float>(), 3 * Hr, de);
     hipLaunchKernelGGL(copy_submatrix_kernel, dim3((unsigned)(((size_t)3 * Hr * dl + 255) / 256)), dim3(256), 0, 0,
                        w->ar_w_ih, de + dl, de, v->w_cond.as<float>(), 3 * Hr, dl);
     HIP_TRY(hipGetLastError());
-    TRY(dcopy(v->b_ih, w->ar_b_ih, (size_t)3 * Hr));
-    TRY(dcopy(v->b_hh, w->ar_b_hh, (size_t)3 * Hr));
+    TRY(dev_copy(v->b_ih, w->ar_b_ih, (size_t)3 * Hr * sizeof(float), D2D));
+    TRY(dev_copy(v->b_hh, w->ar_b_hh, (size_t)3 * Hr * sizeof(float), D2D));
     TRY(v->Gemb.reserve((size_t)w->n_cls * 3 * Hr * sizeof(float)));
-    TRY(dcopy(tmp.emb, w->ar_embedding, (size_t)w->n_cls * de));
-    TRY(vq_gemm_chain(tmp.emb.as<float>(), de, tmp.w_emb.as<float>(), nullptr, v->Gemb, 3 * Hr, w->n_cls, 3 * Hr, de, de, 0));
+    TRY(dev_copy(emb, w->ar_embedding, (size_t)w->n_cls * de * sizeof(float), D2D));
+    TRY(vq_gemm_chain(emb.as<float>(), de, w_emb.as<float>(), nullptr, v->Gemb, 3 * Hr, w->n_cls, 3 * Hr, de, de, 0));
     TRY(v->Gemb4.reserve((size_t)w->n_cls * Hr * sizeof(float4)));
     TRY(v->bh4.reserve((size_t)Hr * sizeof(float4)));
     hipLaunchKernelGGL(quads_build_kernel, dim3((unsigned)(((size_t)w->n_cls * Hr + 255) / 256)), dim3(256), 0, 0, v->Gemb.as<float>(), v->Gemb4.as<float4>(), w->n_cls, Hr);
     hipLaunchKernelGGL(quads_build_kernel, dim3((unsigned)((Hr + 255) / 256)), dim3(256), 0, 0, v->b_hh.as<float>(), v->bh4.as<float4>(), 1, Hr);
     HIP_TRY(hipGetLastError());
-    TRY(build_wfrag12(w->ar_w_hh, Hr, Hr / 4, Hr, Hr, v->Wf_hh12.fresh<float>()));
-    if (Hr % 16 == 0) TRY(vq_build_wfrag(w->ar_w_hh, Hr, 3 * (Hr / 16), Hr, 4, 16, Hr, v->Wf_hh16.fresh<float>()));
-    TRY(vq_build_wfrag(w->fc1_weight, Hr, w->Hf / 16, Hr, 4, 0, 0, v->Wf_fc1.fresh<float>()));
-    TRY(vq_build_wfrag(w->fc1_weight, Hr, w->Hf / 8, Hr, 4, 8, 0, v->Wf_fc1h.fresh<float>()));
-    TRY(vq_build_wfrag(w->fc2_weight, w->Hf, w->n_cls / 16, w->Hf, 1, 0, 0, v->Wf_fc2.fresh<float>()));
-    TRY(dcopy(v->w_hh, w->ar_w_hh, (size_t)3 * Hr * Hr));
-    TRY(dcopy(v->w_fc1, w->fc1_weight, (size_t)w->Hf * Hr));
-    TRY(dcopy(v->w_fc2, w->fc2_weight, (size_t)w->n_cls * w->Hf));
-    TRY(dcopy(v->b_fc1, w->fc1_bias, w->Hf));
-    TRY(dcopy(v->b_fc2, w->fc2_bias, w->n_cls));
+    TRY(build_wfrag12(w->ar_w_hh, Hr, Hr / 4, Hr, Hr, v->Wf_hh12));
+    if (Hr % 16 == 0) TRY(vq_build_wfrag(w->ar_w_hh, Hr, 3 * (Hr / 16), Hr, 4, 16, Hr, v->Wf_hh16));
+    TRY(vq_build_wfrag(w->fc1_weight, Hr, w->Hf / 16, Hr, 4, 0, 0, v->Wf_fc1));
+    TRY(vq_build_wfrag(w->fc1_weight, Hr, w->Hf / 8, Hr, 4, 8, 0, v->Wf_fc1h));
+    TRY(vq_build_wfrag(w->fc2_weight, w->Hf, w->n_cls / 16, w->Hf, 1, 0, 0, v->Wf_fc2));
+    TRY(dev_copy(v->w_hh, w->ar_w_hh, (size_t)3 * Hr * Hr * sizeof(float), D2D));
+    TRY(dev_copy(v->w_fc1, w->fc1_weight, (size_t)w->Hf * Hr * sizeof(float), D2D));
+    TRY(dev_copy(v->w_fc2, w->fc2_weight, (size_t)w->n_cls * w->Hf * sizeof(float), D2D));
+    TRY(dev_copy(v->b_fc1, w->fc1_bias, w->Hf * sizeof(float), D2D));
+    TRY(dev_copy(v->b_fc2, w->fc2_bias, w->n_cls * sizeof(float), D2D));
     // mu-law decode table (preprocess.py:30-35, evaluated in float64 like the reference's numpy)
     std::vector<float> tab(w->n_cls);
     const double mu = (double)((1 << w->bits_mu_law) - 1);
@@ -150,13 +140,10 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
         const double y = 2.0 * (double)s / mu - 1.0, sg = (y > 0) - (y < 0);
         tab[s] = (float)(sg / mu * (pow(1.0 + mu, fabs(y)) - 1.0));
     }
-    TRY(v->mulaw_tab.reserve(tab.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(v->mulaw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    TRY(dev_copy(v->mulaw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     for (auto &g : v->grp) TRY(g.call.reserve(sizeof(ArCall)));
     if (w->Hf == NLL_HF && w->n_cls == NLL_CLS) TRY(vq_tf_nll_prepare());      // the scoring head's LDS attribute, once per handle
-    HIP_TRY(hipHostMalloc((void **)&v->status_host, 64, hipHostMallocMapped));
-    *v->status_host = 0u;
-    HIP_TRY(hipHostGetDevicePointer((void **)&v->status_dev, v->status_host, 0));
+    TRY(v->status.create());
     HIP_TRY(hipStreamCreateWithFlags(&v->side_stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&v->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&v->ev_join, hipEventDisableTiming));
@@ -240,7 +227,7 @@ static void fall_back(vqcpc_vocoder *v) {          // resident decoders off; wha
 }
 static int status_check(vqcpc_vocoder *v, bool synced) {
     if (!v->status_pending) return VQCPC_OK;
-    const unsigned flag = *(volatile unsigned *)v->status_host;        // written by the kernel; no HIP call
+    const unsigned flag = *(volatile unsigned *)v->status.host;        // written by the kernel; no HIP call
     if (flag == 0) {
         if (synced) {
             v->status_pending = false;
@@ -253,7 +240,7 @@ static int status_check(vqcpc_vocoder *v, bool synced) {
         }
         return VQCPC_OK;
     }
-    *(volatile unsigned *)v->status_host = 0u;
+    *(volatile unsigned *)v->status.host = 0u;
     v->status_pending = false;
     const unsigned code = flag & 0xffu, ep = flag >> 8;
     char which[64];
@@ -299,7 +286,7 @@ extern "C" int vqcpc_vocoder_last_slots(vqcpc_vocoder *v) {
 extern "C" int vqcpc_vocoder_workspace_bytes(vqcpc_vocoder *v, uint64_t *bytes) {
     VQ_REQUIRE(v && bytes, "vqcpc_vocoder_workspace_bytes: null argument");
     uint64_t n = 0;
-    for (DevBuf *b : device_buffers(v, false)) n += b->cap;
+    for (const DevBuf *b : work_buffers(v)) n += b->cap;
     *bytes = n;
     return VQCPC_OK;
 }
@@ -328,7 +315,7 @@ static int run_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *sp
     TRY(v->hseq.reserve(2 * hsz));
     const size_t ng = (size_t)B * T2 * F;
     hipLaunchKernelGGL(glue_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, idx, spk, v->code_emb,
-                       v->spk_emb, v->series.as<float>(), B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status_dev, v->epoch << 8,
+                       v->spk_emb, v->series.as<float>(), B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status.dev, v->epoch << 8,
                        frames_dev, row0_dev);
     v->status_pending = true;            // an index outside its table is reported through the status word
     for (int l = 0; l < 2; ++l) {
@@ -369,7 +356,7 @@ static int tf_chunk_nll(vqcpc_vocoder *v, int B, int CH, int chunk, const NllCal
     NllHead h{};
     h.hall = v->hall.as<float>(); h.w1 = v->w_fc1; h.b1 = v->b_fc1; h.w2 = v->w_fc2; h.b2 = v->b_fc2;
     h.audio = nc.audio; h.slen = v->nll_len.as<int>(); h.nll = nc.nll; h.part = v->nll_part.as<NllPart>();
-    h.status = v->status_dev; h.status_tag = v->epoch << 8;
+    h.status = v->status.dev; h.status_tag = v->epoch << 8;
     h.B = B; h.L = nc.L; h.CH = CH; h.t0 = chunk * CH; h.Hr = v->d.Hr;
     return vq_tf_nll_chunk(h, nc.nll_sum, nc.n_scored, nc.n_correct, s);
 }
@@ -397,7 +384,7 @@ int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long lon
     TRY(v->stage.upload(v->xd_segs.p, tab.data(), tab_bytes, s));
     xp.w_hh = v->w_hh; xp.w_fc1 = v->w_fc1; xp.b_fc1 = v->b_fc1; xp.w_fc2 = v->w_fc2; xp.b_fc2 = v->b_fc2;
     xp.Gemb = v->Gemb; xp.b_hh = v->b_hh; xp.Gcond = v->gcond.as<float>(); xp.mulaw_tab = v->mulaw_tab;
-    xp.segs = v->xd_segs.as<XdSeg>(); xp.xg = v->xd_x.as<unsigned long long>(); xp.status = v->status_dev;
+    xp.segs = v->xd_segs.as<XdSeg>(); xp.xg = v->xd_x.as<unsigned long long>(); xp.status = v->status.dev;
     xp.status_tag = v->epoch << 8;
     xp.wav = wav; xp.mulaw = mulaw; xp.seed = seed; xp.max_seg = (int)max_seg; xp.n_slots = pl.xs; xp.bxt = pl.bxt;
     xp.Lout = d.upsample_t * T2; xp.F = T2; xp.upsample = d.upsample_t; xp.agent_stores = v->xcd_agent_stores;
@@ -511,7 +498,7 @@ int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs,
         m.lead6 = cp.n_grp == 2 && nb <= 2;
         m.candg = G.candg.as<u64>();
         m.abort_dev = (unsigned *)((char *)G.candg.p + cg_bytes);
-        m.abort_host = v->status_dev;
+        m.abort_host = v->status.dev;
         m.timeout_ticks = (unsigned)v->handoff_timeout_ms * 100000u;
         m.dbg_drop_t = v->handoff_debug_drop_step;
         m.fused = (v->fuse_fc2 && !tf && cp.gmax[g] < (1 << CAND_TAG_BITS)) ? 1 : 0;
@@ -715,7 +702,7 @@ extern "C" int vqcpc_vocoder_glue(vqcpc_vocoder *v, const int64_t *idx, const in
     const auto &d = v->d;
     const size_t ng = (size_t)B * 2 * Tc * (d.dz + d.ds);
     hipLaunchKernelGGL(glue_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, speaker, v->code_emb,
-                       v->spk_emb, series, B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status_dev, v->epoch << 8, nullptr, nullptr);
+                       v->spk_emb, series, B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status.dev, v->epoch << 8, nullptr, nullptr);
     v->status_pending = true;
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;

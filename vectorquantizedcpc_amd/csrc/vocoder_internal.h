@@ -14,38 +14,35 @@
 // and uploaded from there with hipMemcpyAsync, so a decode call never synchronises the caller's stream ("no
 // hidden sync").  The arena is reused by the next call only after the event recorded behind this call's uploads.
 struct HostStage {
-    char *p = nullptr;
-    size_t cap = 0, used = 0;
+    HostBuf mem;
+    size_t used = 0;
     hipEvent_t ev = nullptr;
     bool pending = false;
+    ~HostStage() {
+        drain();
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    void drain() {                       // wait for the uploads still reading the arena
+        if (pending && ev) (void)hipEventSynchronize(ev);
+        pending = false;
+    }
     int begin(size_t need) {
         if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         if (pending) { HIP_TRY(hipEventSynchronize(ev)); pending = false; }       // the PREVIOUS call's uploads only
-        if (need > cap) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr; cap = 0;
-            const size_t want = need + need / 2 + 4096;
-            HIP_TRY(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-            cap = want;
-        }
+        if (need > mem.cap) TRY(mem.reserve(need + need / 2 + 4096));
         used = 0;
         return VQCPC_OK;
     }
     int upload(void *dst, const void *src, size_t n, hipStream_t s) {
         const size_t at = (used + 15) & ~(size_t)15;
-        VQ_REQUIRE(at + n <= cap, "host staging arena too small (%zu + %zu > %zu)", at, n, cap);
+        VQ_REQUIRE(at + n <= mem.cap, "host staging arena too small (%zu + %zu > %zu)", at, n, mem.cap);
+        char *p = (char *)mem.p;
         memcpy(p + at, src, n);
         used = at + n;
         HIP_TRY(hipMemcpyAsync(dst, p + at, n, hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(ev, s));
         pending = true;
         return VQCPC_OK;
-    }
-    void release() {
-        if (pending && ev) (void)hipEventSynchronize(ev);
-        if (p) (void)hipHostFree(p);
-        if (ev) (void)hipEventDestroy(ev);
-        p = nullptr; ev = nullptr; cap = 0; pending = false;
     }
 };
 
@@ -56,7 +53,8 @@ struct HostStage {
 constexpr int XCM_MIN_DEFAULT = 68, XCM_MAX_DEFAULT = 512, XCD_SLOTS_DEFAULT = 8 * XD_MAX_BX, XCM_SLOTS_DEFAULT = 8 * XM_BX;
 
 struct vqcpc_vocoder {
-    vqcpc_vocoder_weights d;             // dims only (the weights below are owned copies: fixed_buffers)
+    ~vqcpc_vocoder();                    // what is not memory: graphs, the arena's pending uploads, streams, events (vocoder_host.hip)
+    vqcpc_vocoder_weights d;             // dims only (the weights below are owned copies)
     DevPtr<float> code_emb, spk_emb;
     DevPtr<float> p_wih[2], p_bih[2], p_bhh[2], p_wf[2];   // per layer, both directions stacked
     DevPtr<float> w_cond, b_ih, Gemb;
@@ -79,8 +77,7 @@ struct vqcpc_vocoder {
     DevBuf series, gi, out0, cond, gcond, gbase, hseq, len;
     DevBuf hall, a1c;                    // teacher-forced scan: h_t and fc1 outputs of one chunk
     DevBuf nll_part, nll_len;            // scoring (vqcpc_vocoder_nll): one chunk's (utterance, workgroup) records; scored steps per utterance
-    unsigned *status_host = nullptr;     // the handle's status word: pinned host memory the kernels write and the host reads without a HIP call
-    unsigned *status_dev = nullptr;      // the device's view of it
+    PinnedWord status;                   // the handle's status word: the kernels write it, the host reads it without a HIP call
     HostStage stage;
     DevPtr<float> w_hh;                  // plain (3Hr, Hr) copy of W_hh for the resident decoders
     int fuse_fc2 = 1;                    // fc2 + draw of step t-1 and the GRU step t share one launch

@@ -116,8 +116,4 @@ extern "C" int vqcpc_vocoder_stream_position(const vqcpc_vocoder_stream *st, int
     return VQCPC_OK;
 }
 
-extern "C" void vqcpc_vocoder_stream_close(vqcpc_vocoder_stream *st) {
-    if (!st) return;
-    for (DevBuf *b : {&st->cond, &st->gcond, &st->gbase_dev, &st->h, &st->x, &st->owav, &st->omul}) b->release();
-    delete st;
-}
+extern "C" void vqcpc_vocoder_stream_close(vqcpc_vocoder_stream *st) { delete st; }
