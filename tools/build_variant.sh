@@ -6,4 +6,4 @@ cd "$(dirname "$0")/.."
 C=vectorquantizedcpc_amd/csrc
 mkdir -p build/exp/$1
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off $2 -c $C/ar_xcd.hip -o build/exp/$1/ar_xcd.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/exp/$1/libvqcpc_hip.so $C/runtime.o $C/gemm_chain.o $C/encoder.o $C/encoder_host.o $C/codebook.o $C/vocoder.o $C/vocoder_host.o $C/vocoder_plan.o $C/vocoder_stream.o $C/nll.o $C/scan.o build/exp/$1/ar_xcd.o $C/ar_xcm.o $C/melfront.o $C/loudness.o $C/resample.o $C/cpc.o $C/abx.o $C/gate_probe.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/exp/$1/libvqcpc_hip.so $C/runtime.o $C/gemm_chain.o $C/encoder.o $C/encoder_host.o $C/codebook.o $C/vocoder.o $C/vocoder_host.o $C/vocoder_plan.o $C/vocoder_stream.o $C/nll.o $C/scan.o build/exp/$1/ar_xcd.o $C/ar_xcm.o $C/melfront.o $C/loudness.o $C/resample.o $C/cpc.o $C/cpc_grad.o $C/abx.o $C/gate_probe.o

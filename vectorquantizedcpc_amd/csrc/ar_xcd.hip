@@ -35,7 +35,8 @@
 //                -> publish a_t; W_hh rows 80..83 for the OTHER wave's slots (one chain pass: a half wave per slot); the
 //                next step's Gumbel noise (Philox + two logs per class); x_t from the slot's 32 candidates, picked up
 //                before barrier B
-//   all waves    sweep h_t into LDS
+//   all waves    sweep h_t into LDS (four slots: the chain waves, which publish nothing, nap first -- XD_HNAP -- so that their first round
+//                is not issued before the data can exist)
 // Exchange regions of an XCD (ar_chain.h): h_t [rank][slot][32 units], swept with 8-byte loads; a_t [slot][rank][8] -- a slot's 256
 // granules in one run, which a lane of the slot's fc2 wave takes as two 16-byte loads of two granules each; candidates [slot][rank].
 // Every granule is published by one 8-byte store and validated by its own tag, whatever the width of the load that fetched it.
@@ -88,6 +89,22 @@ extern "C" int vqcpc_debug_xd_bars(unsigned long long *out) {
 #define XD_BLEAVE(i) do { } while (0)
 #endif
 
+// -DVQCPC_XD_POLLS (alone): rounds of the three exchange polls, every wave of worker 5 of XCD 0, summed over steps 256..383, for
+// tools/xcd_polls.py: [wave][h_t sweep, a_t poll, candidate poll][failed rounds, all rounds].  Each wave adds to words of its own.
+#ifdef VQCPC_XD_POLLS
+__device__ unsigned g_xd_polls[12 * 3 * 2];
+#define XD_POLLS(ex, failed) do { if (rank == 5 && xcc == 0 && lane == 0 && t >= 256 && t < 384) { \
+        g_xd_polls[(wave * 3 + (ex)) * 2] += (failed); g_xd_polls[(wave * 3 + (ex)) * 2 + 1] += (failed) + 1u; } } while (0)
+// reads the counters and clears them for the next call
+extern "C" int vqcpc_debug_xd_polls(unsigned *out) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_xd_polls), sizeof(g_xd_polls)) != hipSuccess) return -1;
+    void *d = nullptr;
+    return hipGetSymbolAddress(&d, HIP_SYMBOL(g_xd_polls)) == hipSuccess && hipMemset(d, 0, sizeof(g_xd_polls)) == hipSuccess ? 0 : -1;
+}
+#else
+#define XD_POLLS(ex, failed) do { } while (0)
+#endif
+
 #include "ar_chain.h"
 
 // Ablation of the exchange WAITS, for timing only (results are garbage: stale granules are used as they are found): bit 0 the
@@ -108,6 +125,17 @@ extern "C" int vqcpc_debug_xd_bars(unsigned long long *out) {
 // four slots per XCD: the two chain waves on fc1's SIMD start their chains when a_t is out (0: at once -- A/B builds, profiles/r04_mfma_chains.txt)
 #ifndef XD_HOLD
 #define XD_HOLD 1
+#endif
+// four slots per XCD: the chain waves, which publish no h_t, nap XD_HNAP x 64 clocks behind barrier B before the first round of their
+// h_t sweep (0: none -- A/B builds).  A round issued at B is answered by L2 before any worker has stored (the service waves publish
+// 0.33 us later): it is lost by construction -- 1.0 failed round per chain wave and step, 10 x 2 KB of loads per workgroup on the path the
+// publishers' stores travel -- and the second round can start only when the first is back.  With the nap the first round finds everything
+// (0.00 failed rounds) and the step is 0.04..0.056 us shorter.  The optimum is sharp: 8 / 10 / 12 / 14 / 17 gave 3.23 / 3.21 / 3.24 / 3.27 / 3.34 us
+// against 3.26 without; the load must be on its way BEFORE the workgroup's own h_t is out -- waiting for a word in LDS that says so, with or
+// without a nap around it, gave the gain back (profiles/r14_ab_poll_gates.txt).  A timing hint only: every granule is validated by its tag.
+// One and two slots per XCD: no gain (the same file), so those kernels do not nap.
+#ifndef XD_HNAP
+#define XD_HNAP 10
 #endif
 
 namespace {
@@ -212,6 +240,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
 #define XD_SWEEP_H()                                                                                              \
     do {                                                                                                          \
         u64 v1[BXT], v2[BXT];                                                                                     \
+        if (BXT == 4 && XD_HNAP > 0 && wave >= 2) __builtin_amdgcn_s_sleep(XD_HNAP);                              \
         wt.start();                                                                                               \
         for (unsigned spins = 0;; ++spins) {                                                                      \
             bool ok = true;                                                                                       \
@@ -220,7 +249,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 _Pragma("unroll") for (int b = 0; b < BXT; ++b) ok &= b >= bx || (unsigned)(v2[b] >> 32) == tag;  \
             } else gran_load<BXT, 256>(v1, gh, hoff1);                                                            \
             _Pragma("unroll") for (int b = 0; b < BXT; ++b) ok &= b >= bx || (unsigned)(v1[b] >> 32) == tag;      \
-            if ((XD_ABLATE & 4) || __all(ok)) break;                                                         \
+            if ((XD_ABLATE & 4) || __all(ok)) { XD_POLLS(0, spins); break; }                                      \
             if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }                                                 \
             __builtin_amdgcn_s_sleep(1);                                                                          \
         }                                                                                                         \
@@ -305,7 +334,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 for (unsigned spins = 0;; ++spins) {
                     gran_chunks2(va, ga, aoff);
                     const bool ok = va[0][1] == tag && va[0][3] == tag && va[1][1] == tag && va[1][3] == tag;
-                    if ((XD_ABLATE & 2) || __all(ok)) break;
+                    if ((XD_ABLATE & 2) || __all(ok)) { XD_POLLS(1, spins); break; }
                     if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }
                 }
 #pragma unroll
@@ -606,7 +635,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 wt.start();
                 for (unsigned spins = 0;; ++spins) {
                     g = ps_load(csrc);
-                    if ((XD_ABLATE & 1) || __all(!cell_on || (unsigned)(g >> 40) == tag)) break;
+                    if ((XD_ABLATE & 1) || __all(!cell_on || (unsigned)(g >> 40) == tag)) { XD_POLLS(2, spins); break; }
                     if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }
                 }
                 // first argmax per half of 32 lanes (classes ascend with the rank): order-preserving integer image of the score
