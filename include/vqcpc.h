@@ -161,7 +161,7 @@ int vqcpc_encoder_vq_adapt(vqcpc_encoder *enc, const float *x, int n_rows, doubl
                            float *z_st, int64_t *idx, float *loss, float *perplexity, void *stream);
 
 /* Device memory the handle's grow-only work buffers hold at the moment (front-end activations, statistics, the work space
- * of vqcpc_encoder_vq_adapt: the peak of the calls so far; the weights are not counted). */
+ * of vqcpc_encoder_vq_adapt and of vqcpc_encoder_context_fwd / _bwd: the peak of the calls so far; the weights are not counted). */
 int vqcpc_encoder_workspace_bytes(vqcpc_encoder *enc, uint64_t *bytes);
 
 /* After the caller has synchronised the stream that carried vqcpc_encoder_encode / _context: did the resident context
@@ -176,6 +176,39 @@ int vqcpc_encoder_check(vqcpc_encoder *enc);
 /* nn.LSTM over z (B, Tz, z_dim) -> c (B, Tz, c_dim)  (model.py:69 / :85). */
 int vqcpc_encoder_context(vqcpc_encoder *enc, const float *z, int B, int Tz, float *c,
                           void *stream);
+
+/* Bytes of the `saved` buffer that vqcpc_encoder_context_fwd fills for B utterances of Tz steps (its layout is private). */
+int vqcpc_encoder_context_saved_bytes(vqcpc_encoder *enc, int B, int Tz, uint64_t *bytes);
+
+/* vqcpc_encoder_context (model.py:57, :69, :85) as the forward of a training step: c (B, Tz, c_dim) DEVICE, and into `saved` --
+ * DEVICE, the caller's, vqcpc_encoder_context_saved_bytes bytes, 16-byte aligned -- what vqcpc_encoder_context_bwd reads again
+ * (the activated gates, the cell state and its tanh of every row).  c has the BITS vqcpc_encoder_context gives for the same
+ * weights at every B (always one launch per time step; the resident single-utterance scan is not used).
+ * w_ih (4 c_dim, z_dim), w_hh (4 c_dim, c_dim), b_ih, b_hh (4 c_dim) DEVICE: the LSTM's weights this call uses -- the caller's,
+ * so that an optimizer step costs no new handle; the call builds b_ih + b_hh and the W_hh fragments from them in stream order.
+ * All four NULL = the handle's copies.  The handle gives sizes and work space only.  Two forwards may precede their two
+ * backwards: everything a backward needs is in z, c, saved and the weights.
+ * VQCPC_ERR_INVALID before anything is enqueued: a NULL z, c or saved, B < 1 or Tz < 1, only some of the four weight pointers
+ * given, a pointer that is not 16-byte aligned, a handle of another device.  Enqueues on `stream`, does not synchronise; the work
+ * space belongs to the handle (one stream at a time, as every other entry). */
+int vqcpc_encoder_context_fwd(vqcpc_encoder *enc, const float *z, int B, int Tz, const float *w_ih, const float *w_hh,
+                              const float *b_ih, const float *b_hh, float *c, void *saved, void *stream);
+
+/* Back-propagation through time of the context LSTM: what loss.backward() leaves in encoder.rnn in train_cpc.py:116-124, given
+ * grad_c (B, Tz, c_dim) DEVICE = the gradient of the loss with respect to c (vqcpc_cpc_grad's grad_c), csrc/context_grad.hip.
+ * z, c, saved: the input, the output and the saved state of the vqcpc_encoder_context_fwd call; w_ih, w_hh: the weights of
+ * that call (both NULL = the handle's copies).
+ * Gradients DEVICE, each may be NULL = not wanted (its launches are skipped): grad_z (B, Tz, z_dim), grad_w_ih (4 c_dim, z_dim),
+ * grad_w_hh (4 c_dim, c_dim), grad_bias (4 c_dim) -- b_ih and b_hh both receive grad_bias.  Every element of a requested gradient
+ * is written (Tz = 1: grad_w_hh is all +0).  One launch per time step, then fixed-order split-K products; every sum runs in one
+ * fixed order (no floating-point atomics; csrc/context_grad.hip lists the orders): equal inputs give equal bits, whatever an
+ * earlier call left in the work space.  The work space lives on the handle, grows to the largest call and is counted by
+ * vqcpc_encoder_workspace_bytes.
+ * VQCPC_ERR_INVALID before anything is enqueued: a NULL z, c, saved or grad_c, B < 1 or Tz < 1, exactly one of w_ih / w_hh
+ * NULL, a pointer that is not 16-byte aligned, a handle of another device. */
+int vqcpc_encoder_context_bwd(vqcpc_encoder *enc, const float *z, int B, int Tz, const float *w_ih, const float *w_hh,
+                              const float *c, const void *saved, const float *grad_c, float *grad_z, float *grad_w_ih,
+                              float *grad_w_hh, float *grad_bias, void *stream);
 
 /* ------------------------------------------------------------------ CPC scoring ------ */
 

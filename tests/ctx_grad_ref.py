@@ -1,0 +1,358 @@
+"""Shared by the context-LSTM gradient tests (plain module, not a conftest): the cases, the float64 reference, the judge, and two
+fp32 numpy restatements that show on the CPU that the judge rests on nothing the GPU does.
+
+Reference: ``torch.nn.LSTM(D, H, batch_first=True).double()`` on the CPU -- what ``model.py:57`` constructs -- with the loss
+``sum(c * G)`` for a seeded upstream ``G`` and gradients by autograd.  tests/golden/ctx_grad_pins.npz
+(``tools/gen_ctx_grad_golden.py``) pins it: 64 sampled elements, the sum and the sum of squares per tensor, within 1e-12 relative,
+and holds ``e_ref = max |G_ref32 - G_ref64|``, the same module's own fp32 CPU error, per tensor.
+
+Judge, per tensor (c, z, W_ih, W_hh, b), the same for every case: ``max |G - G64| <= 4 max(e_ref, 2^-24 max |G64|)`` (DESIGN 2.6,
+the rule of tests/cpc_grad_ref.py); where ``G64`` is identically zero the result must be exact ``+0``.  Nothing in it is measured
+on the code under test.
+
+``chain``: the composition ``cpc_grad_ref.loss_torch`` o ``nn.LSTM`` on the CPC fixture ``small_odd`` (its ``z``, index arrays and
+predictors; a seeded LSTM), judged by the same rule with ``e_ref`` from the same composition in torch fp32 on the CPU.
+"""
+import os
+
+import numpy as np
+import torch
+
+import cpc_grad_ref
+from vectorquantizedcpc_amd import synth
+
+U32 = 2.0 ** -24
+f32, f64 = np.float32, np.float64
+TENSORS = ("c", "z", "W_ih", "W_hh", "b")
+GRADS = TENSORS[1:]
+N_SAMPLES = 64
+PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ctx_grad_pins.npz")
+
+# name -> B, T, D, H, weight scale
+CASES = {
+    "partial_tile": (3, 5, 64, 256, 1),        # a partly filled tile
+    "two_tiles": (17, 33, 64, 256, 1),         # two tiles, the second nearly empty; 561 rows, no multiple of any chunk
+    "train": (64, 70, 64, 256, 1),             # the train shape
+    "long_one": (1, 300, 64, 256, 1),          # long scan, one utterance
+    "saturated": (16, 70, 64, 256, 4),         # saturated gates
+    "h64": (5, 20, 32, 64, 1),                 # smallest H
+    "h128": (33, 12, 64, 128, 1),              # another H
+    "h512": (2, 9, 64, 512, 1),                # largest H
+    "t1": (4, 1, 64, 256, 1),                  # T = 1: dW_hh must be exactly zero
+}
+ALL_CASES = list(CASES)
+CHAIN = "chain"                                # the composition with CPCLoss on small_odd
+
+_cases, _refs, _pins = {}, {}, None
+
+
+def _u(name, shape, bound):
+    n = int(np.prod(shape))
+    return torch.from_numpy(((synth.uniform01("ctx_grad/" + name, n) * 2.0 - 1.0) * bound).astype(f32).reshape(shape))
+
+
+def lstm_weights(name, D, H, scale=1):
+    """Seeded ``nn.LSTM`` parameters, U(+-1 / sqrt(H)) as it initialises them, times ``scale``."""
+    k = scale / np.sqrt(H)
+    return {"w_ih": _u(name + "/w_ih", (4 * H, D), k), "w_hh": _u(name + "/w_hh", (4 * H, H), k),
+            "b_ih": _u(name + "/b_ih", (4 * H,), k), "b_hh": _u(name + "/b_hh", (4 * H,), k)}
+
+
+def load(name):
+    """A case as a dict of fp32 torch tensors: ``z`` (B, T, D), ``w_ih`` ``w_hh`` ``b_ih`` ``b_hh``, upstream ``G`` (B, T, H), and its
+    sizes.  Computed once and shared (treat as read-only)."""
+    if name not in _cases:
+        B, T, D, H, scale = CASES[name]
+        g = dict(name=name, B=B, T=T, D=D, H=H, scale=scale, z=_u(name + "/z", (B, T, D), 1.0), G=_u(name + "/G", (B, T, H), 1.0))
+        g.update(lstm_weights(name, D, H, scale))
+        _cases[name] = g
+    return _cases[name]
+
+
+def module(g, dtype=torch.float64):
+    m = torch.nn.LSTM(g["D"], g["H"], batch_first=True)
+    with torch.no_grad():
+        for dst, src in ((m.weight_ih_l0, "w_ih"), (m.weight_hh_l0, "w_hh"), (m.bias_ih_l0, "b_ih"), (m.bias_hh_l0, "b_hh")):
+            dst.copy_(g[src])
+    return m.to(dtype)
+
+
+def torch_grads(name, dtype=torch.float64):
+    """``nn.LSTM`` on the CPU in ``dtype``: dict c, z, W_ih, W_hh, b as numpy float64."""
+    g = load(name)
+    m = module(g, dtype)
+    z = g["z"].to(dtype).requires_grad_(True)
+    c = m(z)[0]
+    (c * g["G"].to(dtype)).sum().backward()
+    if dtype == torch.float64:             # one mathematical quantity; torch sums it twice, in orders of its own
+        assert torch.allclose(m.bias_ih_l0.grad, m.bias_hh_l0.grad, rtol=1e-9, atol=1e-12)
+    out = {"c": c.detach(), "z": z.grad, "W_ih": m.weight_ih_l0.grad, "W_hh": m.weight_hh_l0.grad, "b": m.bias_ih_l0.grad}
+    return {k: v.numpy().astype(f64) for k, v in out.items()}
+
+
+def grads64(name):
+    if name not in _refs:
+        _refs[name] = chain_grads(torch.float64) if name == CHAIN else torch_grads(name)
+    return _refs[name]
+
+
+def sample_positions(name, tensor, numel):
+    return synth.randint(f"ctx_grad/{name}/{tensor}/pins", (N_SAMPLES,), numel).numpy()
+
+
+def pins():
+    global _pins
+    if _pins is None:
+        _pins = dict(np.load(PINS))
+    return _pins
+
+
+def bound(name, tensor):
+    """The judge's right-hand side for one tensor of one case."""
+    p = pins()
+    return 4.0 * max(float(p[f"{name}_{tensor}_e_ref"]), U32 * float(p[f"{name}_{tensor}_max"]))
+
+
+def judge(name, got, what):
+    """Every tensor of ``got`` (dict of arrays; missing or None = not asked for) against float64: prints each figure, then asserts."""
+    ref, p = grads64(name), pins()
+    bad = []
+    for k in ref:
+        if got.get(k) is None:
+            continue
+        a = np.asarray(got[k])
+        assert a.shape == ref[k].shape, (k, a.shape, ref[k].shape)
+        if not ref[k].any():                                         # identically zero: exact +0, bit for bit
+            ok = a.dtype == f32 and not a.view(np.uint32).any()
+            print(f"{what} {name} d{k}: reference identically zero, result all +0: {ok}")
+            if not ok:
+                bad.append((k, "not +0"))
+            continue
+        a = a.astype(f64)
+        err, e_ref = float(np.abs(a - ref[k]).max()), float(p[f"{name}_{k}_e_ref"])
+        print(f"{what} {name} {k}: max|G - G64| = {err:.3g}, e_ref = {e_ref:.3g}, ratio {err / e_ref if e_ref else float('inf'):.3f}, "
+              f"bound {bound(name, k):.3g}, max|G64| = {np.abs(ref[k]).max():.3g}")
+        if not (np.isfinite(a).all() and err <= bound(name, k)):
+            bad.append((k, err, bound(name, k)))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------ the composition with CPCLoss (small_odd)
+def chain_case():
+    """``small_odd`` of the CPC tests with a seeded LSTM in front of its ``c``: z, index arrays and predictors are the fixture's."""
+    if CHAIN not in _cases:
+        s = cpc_grad_ref.load("small_odd")
+        g = dict(s, D=64, H=s["c_dim"], rows=cpc_grad_ref.row_index(s))
+        g.update(lstm_weights(CHAIN, 64, s["c_dim"]))
+        _cases[CHAIN] = g
+    return _cases[CHAIN]
+
+
+_chain_modules = {}
+CHAIN_PARAMS = ("w_ih", "w_hh", "b_ih", "b_hh", "W", "b")
+
+
+def chain_loss(g, z, params):
+    """``loss_torch(z, LSTM(z), W, b)`` in the dtype of ``params`` (dict of the six tensors).  -> (loss, c)."""
+    m = _chain_modules.get(z.dtype)
+    if m is None:
+        m = _chain_modules[z.dtype] = torch.nn.LSTM(64, g["H"], batch_first=True).to(z.dtype)
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+    c = torch.func.functional_call(m, dict(zip(names, (params[k] for k in CHAIN_PARAMS[:4]))), (z,))[0]
+    return cpc_grad_ref.loss_torch(z, c, params["W"], params["b"], g["rows"])[0], c
+
+
+def chain_params(g, dtype):
+    return {k: g[k].to(dtype).clone().requires_grad_(True) for k in CHAIN_PARAMS}
+
+
+def chain_grads(dtype=torch.float64):
+    """Gradients of the composition with respect to the LSTM's tensors (and the value of c): numpy float64."""
+    g = chain_case()
+    p = chain_params(g, dtype)
+    loss, c = chain_loss(g, g["z"].to(dtype), p)
+    loss.backward()
+    if dtype == torch.float64:
+        assert torch.allclose(p["b_ih"].grad, p["b_hh"].grad, rtol=1e-9, atol=1e-12)
+    out = {"c": c.detach(), "W_ih": p["w_ih"].grad, "W_hh": p["w_hh"].grad, "b": p["b_ih"].grad}
+    return {k: v.numpy().astype(f64) for k, v in out.items()}
+
+
+def chain_sgd(dtype, steps, lr):
+    """``steps`` of plain SGD on the six tensors of the composition, on the CPU in ``dtype``.  -> (losses, final tensors float64)."""
+    g = chain_case()
+    p = chain_params(g, dtype)
+    z, losses = g["z"].to(dtype), []
+    for _ in range(steps):
+        loss, _ = chain_loss(g, z, p)
+        grads = torch.autograd.grad(loss, [p[k] for k in CHAIN_PARAMS])
+        losses.append(float(loss.detach()))
+        with torch.no_grad():
+            for k, gr in zip(CHAIN_PARAMS, grads):
+                p[k] -= lr * gr
+    return losses, {k: v.detach().numpy().astype(f64) for k, v in p.items()}
+
+
+# ------------------------------------------------------------------ fp32 restatements
+def fma(a, b, c):
+    """fp32 fused multiply-add: the product is exact in float64, the sum is rounded to float64 and then to fp32 (a double rounding
+    that differs from the hardware's single one in rare ties: these restatements are judged by the bound, not by bits)."""
+    return (a.astype(f64) * b.astype(f64) + c.astype(f64)).astype(f32)
+
+
+def split_k_dot(A, Bm):
+    """(M, K) x (K, N) in the order of the step kernels (csrc/context_grad.hip, seq_step.h): K over four waves, NS = K / 64
+    super-steps of 16 k per wave; MFMA c of super-step s takes k = 16 (w NS + s) + 4 q + c, q = 0 .. 3 in order, into accumulator
+    c mod 2; a wave's sum is a0 + a1, the waves are combined ((w0 + w1) + w2) + w3."""
+    M, K = A.shape
+    N = Bm.shape[1]
+    NS = K // 64
+    A5 = np.ascontiguousarray(A.astype(f64).reshape(M, 4, NS, 4, 4).transpose(2, 3, 4, 1, 0))[..., None]    # [s, q, c, w, m, 1]
+    B5 = np.ascontiguousarray(Bm.astype(f64).reshape(4, NS, 4, 4, N).transpose(1, 2, 3, 0, 4))[:, :, :, :, None]   # [s, q, c, w, 1, n]
+    acc, tmp = np.zeros((2, 4, M, N), f32), np.empty((4, M, N), f64)
+    for s in range(NS):
+        for c in range(4):
+            for q in range(4):                                                 # fma(), without its temporaries
+                np.multiply(A5[s, q, c], B5[s, q, c], out=tmp)
+                tmp += acc[c & 1]
+                acc[c & 1][...] = tmp
+    w = acc[0] + acc[1]
+    return ((w[0] + w[1]) + w[2]) + w[3]
+
+
+def sigmoid32(v):
+    return (f32(1) / (f32(1) + np.exp(-v))).astype(f32)
+
+
+def forward32(g, dot):
+    """The LSTM forward in fp32 numpy, the recurrent product by ``dot``: the input projection is ``bias + chain`` with the chain an
+    fma chain over k ascending (vq_gemm_chain), the cell update as seq_step.h writes it (numpy's exp / tanh for libm's)."""
+    (B, T, D), H = g["z"].shape, g["H"]
+    z, w_ih, w_hh = g["z"].numpy(), g["w_ih"].numpy(), g["w_hh"].numpy()
+    bias = g["b_ih"].numpy() + g["b_hh"].numpy()
+    chain, tmp = np.zeros((B * T, 4 * H), f32), np.empty((B * T, 4 * H), f64)
+    zr, w64 = z.reshape(B * T, D).astype(f64), w_ih.astype(f64)
+    for k in range(D):
+        np.multiply(zr[:, k, None], w64[None, :, k], out=tmp)
+        tmp += chain
+        chain[...] = tmp
+    gi = (bias[None] + chain).reshape(B, T, 4 * H)
+    gates, cell, tanhc, out = (np.zeros((B, T, n), f32) for n in (4 * H, H, H, H))
+    h, cs = np.zeros((B, H), f32), np.zeros((B, H), f32)
+    for t in range(T):
+        a = gi[:, t] + dot(w_hh, np.ascontiguousarray(h.T)).T
+        i, f, gg, o = sigmoid32(a[:, :H]), sigmoid32(a[:, H:2 * H]), np.tanh(a[:, 2 * H:3 * H]), sigmoid32(a[:, 3 * H:])
+        cs = f * cs + i * gg
+        tc = np.tanh(cs)
+        h = o * tc
+        gates[:, t], cell[:, t], tanhc[:, t], out[:, t] = np.concatenate([i, f, gg, o], axis=1), cs, tc, h
+    assert out.dtype == f32 and cell.dtype == f32
+    return gates, cell, tanhc, out
+
+
+def scan32(g, gates, cell, tanhc, grad_c, dot):
+    """The backward scan in the order of ctx_bwd_step_kernel: dA (B, T, 4H) fp32."""
+    B, T, H = grad_c.shape
+    w_hh = g["w_hh"].numpy()
+    w_hhT = np.ascontiguousarray(w_hh.T)
+    dA = np.zeros((B, T, 4 * H), f32)
+    carry = np.zeros((B, H), f32)
+    one = f32(1)
+    for t in range(T - 1, -1, -1):
+        dh_rec = dot(w_hhT, np.ascontiguousarray(dA[:, t + 1].T)).T if t + 1 < T else np.zeros((B, H), f32)
+        i, f, gg, o = (gates[:, t, q * H:(q + 1) * H] for q in range(4))
+        tc = tanhc[:, t]
+        cp = cell[:, t - 1] if t > 0 else np.zeros((B, H), f32)
+        dh = grad_c[:, t] + dh_rec
+        do_ = dh * tc
+        dct = (dh * o) * (one - tc * tc) + carry
+        dA[:, t, :H] = (dct * gg) * (i * (one - i))
+        dA[:, t, H:2 * H] = (dct * cp) * (f * (one - f))
+        dA[:, t, 2 * H:3 * H] = (dct * i) * (one - gg * gg)
+        dA[:, t, 3 * H:] = do_ * (o * (one - o))
+        carry = dct * f
+    return dA
+
+
+def slab_dot(A, X, slab=1024):
+    """A^T X over the rows in the order of ctx_grad_w_kernel + ctx_grad_w_finish_kernel: slabs of 1024 rows added in slab order; in a
+    slab MFMA (s, c) takes rows r0 + 16 s + 4 q + c, q = 0 .. 3 in order, into accumulator c mod 2; the two added at the end."""
+    R, M = A.shape
+    total = np.zeros((M, X.shape[1]), f32)
+    A64, X64, tmp = A.astype(f64), X.astype(f64), np.empty((M, X.shape[1]), f64)
+    for r0 in range(0, R, slab):
+        acc = np.zeros((2, M, X.shape[1]), f32)
+        for s in range((min(slab, R - r0) + 15) // 16):
+            for c in range(4):
+                for q in range(4):
+                    r = r0 + 16 * s + 4 * q + c
+                    if r < R:                                                  # fma(), without its temporaries
+                        np.multiply(A64[r][:, None], X64[r][None, :], out=tmp)
+                        tmp += acc[c & 1]
+                        acc[c & 1][...] = tmp
+        total = total + (acc[0] + acc[1])
+    return total
+
+
+def slab_colsum(A, slab=1024):
+    """Column sums in the order of ctx_grad_b_kernel + the finish kernel: per slab, rows r0 + rg + 4 i into accumulator i mod 4,
+    (a0 + a1) + (a2 + a3), the four row groups combined the same way."""
+    R, M = A.shape
+    total = np.zeros(M, f32)
+    for r0 in range(0, R, slab):
+        blk = np.zeros((slab, M), f32)
+        blk[:min(slab, R - r0)] = A[r0:r0 + slab]
+        blk = blk.reshape(slab // 16, 4, 4, M)                                 # r - r0 = 16 i' + 4 q + rg
+        a = np.zeros((4, 4, M), f32)
+        for i in range(slab // 16):
+            a = a + blk[i]
+        per_rg = (a[0] + a[1]) + (a[2] + a[3])
+        total = total + ((per_rg[0] + per_rg[1]) + (per_rg[2] + per_rg[3]))
+    return total
+
+
+def products32(g, dA, out, wdot, colsum, dot):
+    B, T, H4 = dA.shape
+    H, D = H4 // 4, g["D"]
+    A = dA.reshape(B * T, H4)
+    h_prev = np.zeros_like(out)
+    h_prev[:, 1:] = out[:, :-1]
+    X = np.concatenate([g["z"].numpy().reshape(B * T, D), h_prev.reshape(B * T, H)], axis=1)
+    dW = wdot(A, X)
+    res = {"W_ih": dW[:, :D], "W_hh": dW[:, D:], "b": colsum(A), "z": dot(A, g["w_ih"].numpy()).reshape(B, T, D)}
+    assert all(v.dtype == f32 for v in res.values())
+    return res
+
+
+def kernel_order32(name, grad_c=None):
+    """fp32 numpy in the kernels' documented orders (csrc/context_grad.hip): dict c, z, W_ih, W_hh, b."""
+    g = chain_case() if name == CHAIN else load(name)
+    gates, cell, tanhc, out = forward32(g, split_k_dot)
+    dA = scan32(g, gates, cell, tanhc, g["G"].numpy() if grad_c is None else grad_c, split_k_dot)
+    return dict(products32(g, dA, out, slab_dot, slab_colsum, split_k_dot), c=out)
+
+
+def chunk_dot(A, Bm):
+    """Another order: 16-wide k chunks, each a BLAS product, added in order."""
+    out = np.zeros((A.shape[0], Bm.shape[1]), f32)
+    for k in range(0, A.shape[1], 16):
+        out = out + A[:, k:k + 16] @ Bm[k:k + 16]
+    return out
+
+
+def _tree(parts):
+    while len(parts) > 1:
+        parts = [parts[i] + parts[i + 1] if i + 1 < len(parts) else parts[i] for i in range(0, len(parts), 2)]
+    return parts[0]
+
+
+def reordered32(name):
+    """fp32 numpy in orders that are NOT the kernels': 16-wide k chunks for the products, 64-row chunks and an adjacent-pair tree for
+    the weight sums."""
+    g = load(name)
+    gates, cell, tanhc, out = forward32(g, chunk_dot)
+    dA = scan32(g, gates, cell, tanhc, g["G"].numpy(), chunk_dot)
+    # added to a zeroed gradient, as an accumulating .grad is
+    wdot = lambda A, X: np.zeros((A.shape[1], X.shape[1]), f32) + _tree([A[r:r + 64].T @ X[r:r + 64] for r in range(0, A.shape[0], 64)])
+    colsum = lambda A: np.zeros(A.shape[1], f32) + _tree([A[r:r + 64].sum(axis=0) for r in range(0, A.shape[0], 64)])
+    return dict(products32(g, dA, out, wdot, colsum, chunk_dot), c=out)

@@ -1,0 +1,175 @@
+"""CPU-side checks of the context-LSTM gradients: the float64 reference of tests/ctx_grad_ref.py against its pins
+(tests/golden/ctx_grad_pins.npz), the judge held by an fp32 numpy restatement in the kernels' documented order and by a differently
+ordered one (so the bound is shown passable before a GPU is involved, and rests on nothing the GPU does), the ABI addition and the
+command line."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import cpc_grad_ref
+import ctx_grad_ref as R
+import vectorquantizedcpc_amd as V
+from vectorquantizedcpc_amd import _lib, cli, driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("vqcpc_encoder_context_saved_bytes", "vqcpc_encoder_context_fwd", "vqcpc_encoder_context_bwd")
+
+
+# ------------------------------------------------------------------ reference
+@pytest.mark.parametrize("name", R.ALL_CASES + [R.CHAIN])
+def test_pins_reproduce_from_the_float64_reference(name):
+    ref, p = R.grads64(name), R.pins()
+    for k, G in ref.items():
+        top = float(p[f"{name}_{k}_max"])
+        assert abs(np.abs(G).max() - top) <= 1e-12 * top
+        samples = G.reshape(-1)[R.sample_positions(name, k, G.size)]
+        assert np.abs(samples - p[f"{name}_{k}_samples"]).max() <= 1e-12 * top, k
+        s, ss = p[f"{name}_{k}_sums"]
+        assert abs(G.sum() - s) <= 1e-12 * np.abs(G).sum() and abs((G ** 2).sum() - ss) <= 1e-12 * ss, k
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_kernel_order_fp32_restatement_stays_within_the_judge(name):
+    R.judge(name, R.kernel_order32(name), "kernel-order fp32 numpy")
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_reordered_fp32_restatement_stays_within_the_judge(name):
+    R.judge(name, R.reordered32(name), "reordered fp32 numpy")
+
+
+def test_kernel_order_restatement_of_the_chain_stays_within_the_judge():
+    """The composition with the CPC loss: dc from float64 autograd of the loss at the restatement's own fp32 c."""
+    g = R.chain_case()
+    c32 = R.kernel_order32(R.CHAIN, grad_c=np.zeros(g["c"].shape, np.float32))["c"]
+    c = torch.from_numpy(c32).double().requires_grad_(True)
+    cpc_grad_ref.loss_torch(g["z"].double(), c, g["W"].double(), g["b"].double(), g["rows"])[0].backward()
+    got = R.kernel_order32(R.CHAIN, grad_c=c.grad.numpy().astype(np.float32))
+    R.judge(R.CHAIN, {k: got[k] for k in ("c", "W_ih", "W_hh", "b")}, "kernel-order fp32 numpy")
+
+
+def test_structure_of_the_reference():
+    assert not R.grads64("t1")["W_hh"].any()                         # no previous step: h_prev is zero
+    assert all(R.grads64("t1")[k].any() for k in ("z", "W_ih", "b"))
+
+
+# ------------------------------------------------------------------ ABI
+def test_abi_addition():
+    text = open(os.path.join(ROOT, "include", "vqcpc.h")).read()
+    lib = _lib.load()
+    for name in ENTRIES:
+        assert re.search(r"\b%s\s*\(" % name, text) and name in _lib.SYMBOLS and hasattr(lib, name), name
+    assert "#define VQCPC_ABI_VERSION 1" in text
+    for cite in ("model.py:57", ":69", ":85", "train_cpc.py:116-124"):
+        assert cite in text, cite
+
+
+def test_header_compiles_as_c99_with_the_context_calls(tmp_path):
+    src = tmp_path / "use_context_grad.c"
+    src.write_text('''#include "vqcpc.h"
+#include <stddef.h>
+int use(vqcpc_encoder *enc, const float *z, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, float *c,
+        void *saved, const float *gc, float *gz, float *gwi, float *gwh, float *gb, void *st) {
+    uint64_t n = 0;
+    int rc = vqcpc_encoder_context_saved_bytes(enc, 64, 70, &n);
+    rc |= vqcpc_encoder_context_fwd(enc, z, 64, 70, w_ih, w_hh, b_ih, b_hh, c, saved, st);
+    rc |= vqcpc_encoder_context_fwd(enc, z, 64, 70, NULL, NULL, NULL, NULL, c, saved, st);
+    rc |= vqcpc_encoder_context_bwd(enc, z, 64, 70, w_ih, w_hh, c, saved, gc, gz, gwi, gwh, gb, st);
+    rc |= vqcpc_encoder_context_bwd(enc, z, 64, 70, NULL, NULL, c, saved, gc, NULL, gwi, NULL, NULL, st);
+    return rc;
+}
+''')
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only",
+                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_kernel_source_has_no_atomics_or_spin_waits():
+    for name in ("context_grad.hip", "seq_step.h", "grad_slab.h"):
+        text = open(os.path.join(ROOT, "vectorquantizedcpc_amd", "csrc", name)).read()
+        code = re.sub(r"//.*", "", text)
+        assert not re.search(r"atomic|while\s*\((?!0\))|s_sleep|memrealtime|asm", code), name
+
+
+# ------------------------------------------------------------------ module surface and command line
+def test_context_has_no_cpu_fallback():
+    enc = V.Encoder(V.ConfEncoder(80, 512, 512, 64, 256))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        enc.context(torch.zeros(2, 5, 64), differentiable=True)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        enc.context(torch.zeros(2, 5, 64))
+    assert "context LSTM have no backward" not in " ".join(V.CPCLoss.__doc__.split())
+
+
+def test_cli_fit_context_help_parses(capsys):
+    with pytest.raises(SystemExit) as e:
+        cli.main(["fit-context", "--help"])
+    assert e.value.code == 0
+    text = capsys.readouterr().out
+    assert "--out-checkpoint" in text and "--steps" in text and "--freeze-predictors" in text
+
+
+class _Enc(torch.nn.Module):
+    """Stand-in for Encoder in ``fit_context``: ``rnn`` is one weight, ``context`` a plain function of it."""
+
+    def __init__(self):
+        super().__init__()
+        self.rnn = torch.nn.Linear(1, 1, bias=False)
+        self.calls = []
+
+    def forward(self, mels):
+        self.calls.append(("enc", torch.is_grad_enabled()))
+        return mels[:, :1, ::2], mels[:, :2, ::2], torch.tensor(0.5), torch.tensor(10.0)
+
+    def context(self, z, *, differentiable=False):
+        self.calls.append(("ctx", differentiable, torch.is_grad_enabled()))
+        return z * self.rnn.weight[0, 0]
+
+
+class _Cpc(torch.nn.Module):
+    def __init__(self, S, U, n_pred):
+        super().__init__()
+        self.n_speakers_per_batch, self.n_utterances_per_speaker, self.n_prediction_steps = S, U, n_pred // 2
+        self.conf = V.ConfCPC(n_pred, S, U, 3, 64, 256)
+        self.predictors = torch.nn.ModuleList([torch.nn.Linear(2, 1) for _ in range(n_pred)])
+
+    def forward(self, z, c, seed, stream_id, differentiable=False):
+        assert differentiable and c.requires_grad
+        return (c ** 2).mean() + sum((p.weight ** 2).sum() for p in self.predictors[:self.n_prediction_steps]), [0.5]
+
+
+def test_fit_context_wiring():
+    S, U, n_pred, frames = 2, 2, 4, 8
+    mk = lambda tag, T: torch.full((80, T), 0.05 * tag) + torch.arange(T) * 1e-3
+    data = {"a": [mk(1, 40), mk(2, 30)], "b": [mk(4, 21), mk(5, 30)], "c": [mk(6, 20), mk(7, 21)], "d": [mk(9, 25), mk(10, 26)]}
+    for train_predictors in (True, False):
+        enc, cpc = _Enc(), _Cpc(S, U, n_pred)
+        made = []
+        before = [p.weight.detach().clone() for p in cpc.predictors]
+        r = driver.fit_context(enc, cpc, data, steps=5, lr=0.1, optimizer=lambda ps, lr: (made.append([id(p) for p in ps]),
+                               torch.optim.SGD(ps, lr=lr))[1], sample_frames=frames, seed=13, device="cpu", train_predictors=train_predictors)
+        K = n_pred // 2
+        want = [id(p) for p in enc.rnn.parameters()] + ([id(p) for m in cpc.predictors[:K] for p in m.parameters()] if train_predictors else [])
+        assert made == [want]
+        assert set(r) == {"losses", "accuracies", "steps", "batches", "utterances", "speakers_skipped", "speakers_left_over"}
+        assert r["steps"] == 5 and r["batches"] == 2 and all(a > b for a, b in zip(r["losses"], r["losses"][2:]))
+        assert [c for c in enc.calls if c[0] == "enc"] == [("enc", False)] * 2             # front end once per batch, no_grad
+        assert [c for c in enc.calls if c[0] == "ctx"] == [("ctx", True, True)] * 5        # the context every step, differentiable
+        for k, p in enumerate(cpc.predictors):
+            assert torch.equal(p.weight, before[k]) != (train_predictors and k < K)
+
+
+def test_fitted_checkpoint_with_an_encoder_update(tmp_path):
+    from vectorquantizedcpc_amd import io, synth
+    src, out = tmp_path / "in.pt", tmp_path / "out.pt"
+    cpc_sd = synth.cpc_state_dict()
+    torch.save({"encoder": {"w": torch.arange(3.0), "rnn.weight_ih_l0": torch.zeros(2)}, "cpc": cpc_sd, "epoch": 3}, src)
+    io.save_fitted_checkpoint(out, cpc_sd, src, encoder_update={"rnn.weight_ih_l0": torch.ones(2)})
+    ck = torch.load(out, map_location="cpu", weights_only=True)
+    assert ck["epoch"] == 3 and torch.equal(ck["encoder"]["w"], torch.arange(3.0)) and torch.equal(ck["encoder"]["rnn.weight_ih_l0"], torch.ones(2))
+    with pytest.raises(KeyError):
+        io.save_fitted_checkpoint(out, cpc_sd, src, encoder_update={"rnn.nope": torch.ones(2)})

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libvqcpc_hip.so")
 SYMBOLS = [
     "vqcpc_abi_version", "vqcpc_last_error", "vqcpc_device_count",
     "vqcpc_encoder_create", "vqcpc_encoder_destroy", "vqcpc_encoder_encode",
-    "vqcpc_encoder_forward_stats", "vqcpc_encoder_context", "vqcpc_encoder_stage", "vqcpc_encoder_vq_encode", "vqcpc_encoder_vq_adapt", "vqcpc_encoder_workspace_bytes", "vqcpc_encoder_set_option", "vqcpc_encoder_last_schedule",
+    "vqcpc_encoder_forward_stats", "vqcpc_encoder_context", "vqcpc_encoder_context_saved_bytes", "vqcpc_encoder_context_fwd", "vqcpc_encoder_context_bwd", "vqcpc_encoder_stage", "vqcpc_encoder_vq_encode", "vqcpc_encoder_vq_adapt", "vqcpc_encoder_workspace_bytes", "vqcpc_encoder_set_option", "vqcpc_encoder_last_schedule",
     "vqcpc_cpc_create", "vqcpc_cpc_destroy", "vqcpc_cpc_score", "vqcpc_cpc_grad",
     "vqcpc_abx_workspace_bytes", "vqcpc_abx_score", "vqcpc_abx_index_workspace_bytes", "vqcpc_abx_code_table", "vqcpc_abx_score_indices",
     "vqcpc_encoder_check", "vqcpc_vocoder_check", "vqcpc_vocoder_last_path", "vqcpc_vocoder_last_slots", "vqcpc_vocoder_workspace_bytes", "vqcpc_vocoder_plan",
@@ -85,6 +85,9 @@ def load():
     lib.vqcpc_encoder_encode.argtypes = [vp, vp, i32, i32, i32, vp, vp, i64p, vp, vp]
     lib.vqcpc_encoder_forward_stats.argtypes = [vp, vp, vp, i64p, i32, vp, vp, vp, vp]
     lib.vqcpc_encoder_context.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.vqcpc_encoder_context_saved_bytes.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
+    lib.vqcpc_encoder_context_fwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.vqcpc_encoder_context_bwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_encoder_stage.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     lib.vqcpc_encoder_vq_encode.argtypes = [vp, vp, i32, vp, i64p, vp]
     lib.vqcpc_encoder_vq_adapt.argtypes = [vp, vp, i32, C.c_double, C.c_double, vp, vp, vp, vp, i64p, vp, vp, vp]

@@ -23,6 +23,14 @@
     python -m vectorquantizedcpc_amd.cli fit-predictors --dataset datasets/2019/english --cpc-checkpoint in.pt | --random-init
                                                  --out-checkpoint out.pt [--steps 200 --lr 4e-4] [the options of score]
 
+    python -m vectorquantizedcpc_amd.cli fit-context --dataset datasets/2019/english --cpc-checkpoint in.pt | --random-init
+                                                 --out-checkpoint out.pt [--steps 200 --lr 4e-4] [--freeze-predictors]
+                                                 [the options of score]
+
+``fit-context`` refits the context LSTM ``encoder.rnn`` together with the K predictors (``driver.fit_context``: back-propagation
+through time is ``vqcpc_encoder_context_bwd``'s, the optimizer torch's Adam over both, as ``train_cpc.py:53-55`` has them) on the
+frozen front end and codebook -- the step after ``adapt-codebook``.  It prints the ``score`` lines before and after and writes a
+checkpoint in which only ``encoder.rnn.*`` and the K predictors in use differ.
 ``fit-predictors`` refits the K linear predictors of a checkpoint's ``"cpc"`` entry on its frozen encoder
 (``driver.fit_predictors``: the gradient is ``vqcpc_cpc_grad``'s, the optimizer torch's Adam) -- what an adapted codebook needs
 before ``score`` means anything again.  It prints the ``score`` lines before and after the fit and writes a checkpoint with
@@ -147,6 +155,26 @@ def fit_predictors_dataset(args) -> int:
     io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
                               encoder_state=enc.state_dict() if args.random_init else None)
     print(f"wrote {args.out_checkpoint}: \"encoder\" as it was, \"cpc\" replaced ({len(cpc.state_dict())} keys)")
+    return rc
+
+
+def fit_context_dataset(args) -> int:
+    enc, cpc, by_speaker = _score_setup(args)
+    print("before the fit:")
+    if _print_score(args, enc, cpc, by_speaker):
+        return 1
+    r = driver.fit_context(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed,
+                           train_predictors=not args.freeze_predictors)
+    what = "the context LSTM" + ("" if args.freeze_predictors else f" and {cpc.n_prediction_steps} predictors")
+    print(f"fitted {what} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches: "
+          f"cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}")
+    print("after the fit:")
+    rc = _print_score(args, enc, cpc, by_speaker)
+    rnn = {f"rnn.{k}": v for k, v in enc.rnn.state_dict().items()}
+    io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
+                              encoder_state=enc.state_dict() if args.random_init else None,
+                              encoder_update=None if args.random_init else rnn)
+    print(f"wrote {args.out_checkpoint}: \"encoder\" with rnn.* replaced ({len(rnn)} keys), \"cpc\" replaced ({len(cpc.state_dict())} keys)")
     return rc
 
 
@@ -278,7 +306,7 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook", "fit-predictors"):
+    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook", "fit-predictors", "fit-context"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
         if name in ("encode", "convert"):
@@ -287,17 +315,19 @@ def main(argv=None) -> int:
         p.add_argument("--random-init", action="store_true", help="seeded random-init weights (no checkpoint ships with the reference)")
         p.add_argument("--device", default="cuda")
         p.add_argument("--max-batch", type=int, default=64)
-        if name in ("score", "fit-predictors"):               # config.py:42-47, :202
+        if name in ("score", "fit-predictors", "fit-context"):               # config.py:42-47, :202
             p.add_argument("--prediction-steps", type=int, default=12)
             p.add_argument("--speakers", type=int, default=8)
             p.add_argument("--utterances", type=int, default=8)
             p.add_argument("--negatives", type=int, default=17)
             p.add_argument("--sample-frames", type=int, default=128)
             p.add_argument("--seed", type=int, default=synth.SEED)
-            if name == "fit-predictors":
+            if name != "score":
                 p.add_argument("--out-checkpoint", required=True)
                 p.add_argument("--steps", type=int, default=200)
                 p.add_argument("--lr", type=float, default=4e-4, help="Adam's learning rate (config.py's CPC training rate)")
+            if name == "fit-context":
+                p.add_argument("--freeze-predictors", action="store_true", help="step the LSTM alone")
         elif name == "encode":
             p.add_argument("--save-auxiliary", action="store_true")
         elif name == "adapt-codebook":
@@ -342,7 +372,7 @@ def main(argv=None) -> int:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,
             "score-vocoder": score_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset,
-            "fit-predictors": fit_predictors_dataset}[args.cmd](args)
+            "fit-predictors": fit_predictors_dataset, "fit-context": fit_context_dataset}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -108,7 +108,7 @@ int vq_gemm_chain_ex(const float *A, int lda, const float *W, const float *bias,
 
 // ---- recurrent scans (scan.hip): the encoder's context LSTM and the vocoder prenet's bidirectional GRU layers.
 // W (n_rg row groups x K) in fragment order for the launch-per-step MFMA kernels; rowmode and layout: scan.hip.  `out` is reserved here.
-int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, DevBuf &out);
+int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, DevBuf &out, hipStream_t s = 0);
 // One bidirectional GRU layer's T steps from zero state.  Gi: hoisted input projection [rows][2][3H] (+ b_ih); Wf: both directions'
 // W_hh, each from vq_build_wfrag(rowmode 3); b_hh [2][3H]; hbuf: 4 * ceil(B / 16) * 16 * H floats of state; out [rows][2H].
 // len / row0: valid steps and first row of every utterance (ragged rows), or null = T steps from row b * T.
@@ -123,3 +123,30 @@ int vq_lstm_run(LstmPlan *p, const float *x, int B, int T, float *out, hipStream
 int vq_lstm_set_persistent(LstmPlan *p, int value);                  // -1 auto (one utterance: the resident scan), 0 one launch per time step
 int vq_lstm_set_debug(LstmPlan *p, int drop_step, int timeout_ms);   // tests of the abort path
 int vq_lstm_check(LstmPlan *p);            // after the caller's sync: did the resident scan of the last call time out?
+void vq_add_vec(const float *a, const float *b, float *o, int n, hipStream_t s);      // o = a + b, n floats
+// The weights an LSTM computes with: the plan's copies, or a caller's tensors with the sums and fragments built from them.
+struct LstmWeights {
+    const float *w_ih, *w_hh;      // (4H, D), (4H, H) row-major
+    const float *bias;             // b_ih + b_hh (4H)
+    const float *Wf;               // w_hh in fragment order: vq_build_wfrag(w_hh, H, H / 4, H, 4, 4, H)
+    int D, H;
+};
+LstmWeights vq_lstm_plan_weights(const LstmPlan *p);
+
+// ---- gradients of the context LSTM (context_grad.hip): a forward that keeps state, and back-propagation through time.
+// The work space of both, grow-only, a member of the encoder handle.
+struct CtxGradWork {
+    DevBuf gi, hbuf, cbuf;         // forward: hoisted projection, h and cell tiles (as vq_lstm_run's)
+    DevBuf bias, Wf;               // forward, caller's weights: b_ih + b_hh and the W_hh fragments
+    DevBuf WfT;                    // backward: W_hh^T fragments
+    DevBuf dA, carry, part;        // backward: pre-activation gradients (B T, 4H), the cell carry (B, H), slab partials
+    size_t bytes() const { return gi.cap + hbuf.cap + cbuf.cap + bias.cap + Wf.cap + WfT.cap + dA.cap + carry.cap + part.cap; }
+};
+size_t vq_ctx_saved_bytes(int B, int T, int H);
+// c (B, T, H) with the bits of vq_lstm_run's launch-per-step path; `saved` receives what vq_ctx_bwd reads again.
+// own_weights: w.bias and w.Wf are not given -- they are built from b_ih, b_hh, w.w_hh into the work space, in stream order.
+int vq_ctx_fwd(CtxGradWork &k, LstmWeights w, bool own_weights, const float *b_ih, const float *b_hh, const float *z, int B, int T,
+               float *c, float *saved, hipStream_t s);
+// Each gradient may be null: grad_z (B T, D), grad_w_ih (4H, D), grad_w_hh (4H, H), grad_bias (4H).
+int vq_ctx_bwd(CtxGradWork &k, LstmWeights w, const float *z, int B, int T, const float *c, const float *saved, const float *grad_c,
+               float *grad_z, float *grad_w_ih, float *grad_w_hh, float *grad_bias, hipStream_t s);

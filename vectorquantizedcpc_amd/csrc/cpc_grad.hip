@@ -14,7 +14,7 @@
 //     Stores dWc (K, N, L, 64) and, when grad_z is wanted, Wc (K, N, L, 64), g (K, N, J, L) and the negatives' indices u
 //     (K, Utt, Neg), s (K, N, Neg, L) as int32: the dz pass repeats no Philox draw.
 //   dW: cpc_grad_w_kernel, grid (C / 16, slabs, n_steps): a split-K GEMM on v_mfma_f32_16x16x4_f32, A = dWc^T, B = c.  A slab is
-//     GW_SLAB = 1024 consecutive rows r = n L + t.  Inside a slab MFMA (s, q) takes rows r0 + 16 s + 4 kslot + q, kslot 0 .. 3
+//     GRAD_SLAB = 1024 consecutive rows r = n L + t.  Inside a slab MFMA (s, q) takes rows r0 + 16 s + 4 kslot + q, kslot 0 .. 3
 //     summed inside the instruction; q even goes to accumulator 0, q odd to accumulator 1, s ascending, the two added once at
 //     the end.  cpc_grad_w_finish_kernel adds the slab partials in slab order.
 //   db: cpc_grad_b_kernel, grid (slabs, n_steps), the same slabs: thread (feature d, row group rg) adds rows r0 + rg + 4 i, i
@@ -30,11 +30,10 @@
 //     cpc_grad_z_sum_kernel: dz[n, tau, :] = sum of the partials [k][n][tau - k] for k = 1 .. n_steps ascending (those with
 //     0 <= tau - k < L), from 0: row 0 has no term and is an exact zero.
 #include "cpc_tile.h"
+#include "grad_slab.h"
 
 namespace {
 
-constexpr int GW_SLAB = 1024;        // rows of dWc / c per dW slab
-constexpr int GW_AHEAD = 4;          // MFMA steps of a dW wave whose operand loads are issued together
 constexpr int GZ_ROWS = 64;          // destination positions per dz workgroup
 constexpr int GZ_FLIGHT = 8;         // contribution rows a dz wave loads before it adds them
 
@@ -100,30 +99,12 @@ __global__ __launch_bounds__(256) void cpc_grad_tile_kernel(CpcGradArgs ga) {
 __global__ __launch_bounds__(256) void cpc_grad_w_kernel(const float *dWc, const float *c, float *part, int N, int L, int T, int C) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, ks = lane >> 4;
     const int ct = blockIdx.x, slab = blockIdx.y, k = blockIdx.z, S = gridDim.y;
-    const int R = N * L, r0 = slab * GW_SLAB;            // N L < 2^31 (the entry checks it)
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-    for (int s0 = 0; s0 < GW_SLAB / 16 && r0 + 16 * s0 < R; s0 += GW_AHEAD) {
-        float av[GW_AHEAD][4], bv[GW_AHEAD][4];
+    const int R = N * L;                                 // N L < 2^31 (the entry checks it)
+    const f32x4 acc = slab_mfma_tile(R, slab * GRAD_SLAB, ks,
+        [&](int r) { return dWc[((size_t)k * R + r) * CPC_D + wave * 16 + i]; },
+        [&](int r) { const int n = r / L, t = r - n * L; return c[((size_t)n * T + t) * C + ct * 16 + i]; });
 #pragma unroll
-        for (int u = 0; u < GW_AHEAD; ++u) {             // the loads of GW_AHEAD steps in flight together, then their MFMAs in order
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = r0 + 16 * (s0 + u) + 4 * ks + q;
-                av[u][q] = bv[u][q] = 0.f;               // rows past N L add exact zeros
-                if (r < R) {
-                    const int n = r / L, t = r - n * L;
-                    av[u][q] = dWc[((size_t)k * R + r) * CPC_D + wave * 16 + i];
-                    bv[u][q] = c[((size_t)n * T + t) * C + ct * 16 + i];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < GW_AHEAD; ++u)
-            mfma_k4(a0, a1, make_float4(av[u][0], av[u][1], av[u][2], av[u][3]), make_float4(bv[u][0], bv[u][1], bv[u][2], bv[u][3]));
-    }
-    const f32x4 acc = a0 + a1;                           // row = feature 16 wave + 4 ks + r, column = ct * 16 + i
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
+    for (int r = 0; r < 4; ++r)                          // row = feature 16 wave + 4 ks + r, column = ct * 16 + i
         part[(((size_t)k * S + slab) * CPC_D + wave * 16 + ks * 4 + r) * (C + 16) + ct * 16 + i] = acc[r];
 }
 
@@ -131,19 +112,9 @@ __global__ __launch_bounds__(256) void cpc_grad_b_kernel(const float *dWc, float
     __shared__ float red[4][CPC_D];
     const int d = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int slab = blockIdx.x, k = blockIdx.y, S = gridDim.x;
-    const long long R = (long long)N * L, r0 = (long long)slab * GW_SLAB;
-    const float *src = dWc + (size_t)k * R * CPC_D + d;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < GW_SLAB / 4 && r0 + 4 * i < R; i += 4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const long long r = r0 + rg + 4 * (i + q);
-            a[q] += r < R ? src[(size_t)r * CPC_D] : 0.f;            // rows past N L add exact zeros
-        }
-    }
-    red[rg][d] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (rg == 0) part[(((size_t)k * S + slab) * CPC_D + d) * (C + 16) + C] = (red[0][d] + red[1][d]) + (red[2][d] + red[3][d]);
+    const long long R = (long long)N * L;
+    const float sum = slab_column_sum(dWc + (size_t)k * R * CPC_D + d, CPC_D, R, (long long)slab * GRAD_SLAB, rg, d, red);
+    if (rg == 0) part[(((size_t)k * S + slab) * CPC_D + d) * (C + 16) + C] = sum;
 }
 
 __global__ __launch_bounds__(256) void cpc_grad_w_finish_kernel(const float *part, float *dW, float *db, int K, int S, int C) {
@@ -266,8 +237,8 @@ extern "C" int vqcpc_cpc_grad(vqcpc_cpc *cpc, const float *z, const float *c, in
     TRY(cpc_begin(cpc, "vqcpc_cpc_grad", z, c, T, W, bias, utt_index, seq_index, seed, stream_id, a, P));
     const int K = cpc->n_steps, L = a.L, N = a.Spk * a.Utt, C = a.C, J = 1 + a.Neg, tiles = a.tiles;
     VQ_REQUIRE((long long)N * T < (1ll << 31), "vqcpc_cpc_grad: Spk * Utt * T = %lld rows do not fit a 32-bit row index", (long long)N * T);
-    const int slabs = (int)(((long long)N * L + GW_SLAB - 1) / GW_SLAB);
-    VQ_REQUIRE(slabs <= 65535, "vqcpc_cpc_grad: Spk * Utt * L = %lld rows, more than 65535 slabs of %d", (long long)N * L, GW_SLAB);
+    const int slabs = (int)(((long long)N * L + GRAD_SLAB - 1) / GRAD_SLAB);
+    VQ_REQUIRE(slabs <= 65535, "vqcpc_cpc_grad: Spk * Utt * L = %lld rows, more than 65535 slabs of %d", (long long)N * L, GRAD_SLAB);
     const bool want_w = grad_W || grad_bias;
     // work space: dWc | Wc, g, s, u, dz partials (grad_z) | dW slab partials (grad_W, grad_bias)
     const size_t b_rows = up256((size_t)K * N * L * CPC_D * sizeof(float)), b_g = up256((size_t)K * N * J * L * sizeof(float));

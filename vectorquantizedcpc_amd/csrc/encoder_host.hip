@@ -17,6 +17,8 @@ struct vqcpc_encoder {
     DevPtr<float> bufA, bufB, zpre;
     DevPtr<char> stats;
     DevPtr<char> adapt;                  // work space of vqcpc_encoder_vq_adapt, grown on demand: q, idx, 16-bit idx, counts
+    CtxGradWork ctx;                     // work space of vqcpc_encoder_context_fwd / _bwd (context_grad.hip)
+    int device = 0;                      // the device the handle was created on
     // fused and column-split schedules: weights in 16x16x4 fragment order (only when 4 * in_channels <= 512, the width of
     // their activation tile), and the model's half of their kernel argument
     DevPtr<float4> conv_f[2], fc_f[4], out_f;
@@ -41,6 +43,7 @@ static int build_frag16(const float *W, int N, int K, DevPtr<float4> &out) {
 static int encoder_create_impl(const vqcpc_encoder_weights *w, vqcpc_encoder *e) {
     const int C = w->in_channels, CH = w->channels;
     e->in_channels = C; e->channels = CH; e->n_emb = w->n_embeddings; e->z_dim = w->z_dim; e->c_dim = w->c_dim;
+    HIP_TRY(hipGetDevice(&e->device));
     for (int j = 0; j < 16; ++j) e->lnc.inv[j] = 1.0f / (float)(j + 1);
     for (int q = 0; q < 8; ++q) e->lnc.sc[q] = (float)64 / (float)(64 * (q + 1));
     const size_t nconv = (size_t)CH * C * 4;
@@ -255,6 +258,55 @@ extern "C" int vqcpc_encoder_context(vqcpc_encoder *e, const float *z, int B, in
     return vq_lstm_run(e->lstm, z, B, Tz, c, (hipStream_t)stream);
 }
 
+// The checks vqcpc_encoder_context_fwd / _bwd share; nothing is enqueued before they pass.
+static int context_grad_begin(vqcpc_encoder *e, const char *what, int B, int Tz, const float *w_ih, const float *w_hh, const float *b_ih,
+                              const float *b_hh, bool need_bias, LstmWeights &w, bool &own) {
+    VQ_REQUIRE(B >= 1 && Tz >= 1, "%s: need B >= 1 and Tz >= 1 (got B=%d Tz=%d)", what, B, Tz);
+    const int given = (w_ih != nullptr) + (w_hh != nullptr) + (need_bias ? (b_ih != nullptr) + (b_hh != nullptr) : 0);
+    own = given != 0;
+    VQ_REQUIRE(given == 0 || given == (need_bias ? 4 : 2), "%s: give all of the LSTM's weight tensors, or none of them (the handle's copies)", what);
+    VQ_REQUIRE((long long)B * Tz <= 65535ll * 1024 && B <= 65535 * 16, "%s: B * Tz = %lld rows, more than 65535 slabs of 1024", what,
+               (long long)B * Tz);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    VQ_REQUIRE(dev == e->device, "%s: handle belongs to device %d, current device is %d", what, e->device, dev);
+    w = vq_lstm_plan_weights(e->lstm);
+    if (own) { w.w_ih = w_ih; w.w_hh = w_hh; w.bias = nullptr; w.Wf = nullptr; }
+    return VQCPC_OK;
+}
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int vqcpc_encoder_context_saved_bytes(vqcpc_encoder *e, int B, int Tz, uint64_t *bytes) {
+    VQ_REQUIRE(e && bytes, "vqcpc_encoder_context_saved_bytes: null argument");
+    VQ_REQUIRE(B >= 1 && Tz >= 1, "vqcpc_encoder_context_saved_bytes: need B >= 1 and Tz >= 1 (got B=%d Tz=%d)", B, Tz);
+    *bytes = (uint64_t)vq_ctx_saved_bytes(B, Tz, e->c_dim);
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_context_fwd(vqcpc_encoder *e, const float *z, int B, int Tz, const float *w_ih, const float *w_hh,
+                                         const float *b_ih, const float *b_hh, float *c, void *saved, void *stream) {
+    VQ_REQUIRE(e && z && c && saved, "vqcpc_encoder_context_fwd: null argument");
+    LstmWeights w;
+    bool own = false;
+    TRY(context_grad_begin(e, "vqcpc_encoder_context_fwd", B, Tz, w_ih, w_hh, b_ih, b_hh, true, w, own));
+    VQ_REQUIRE(aligned16(z) && aligned16(c) && aligned16(saved) && aligned16(w.w_ih) && aligned16(w.w_hh),
+               "vqcpc_encoder_context_fwd: z, c, saved and the weights must be 16-byte aligned");
+    return vq_ctx_fwd(e->ctx, w, own, b_ih, b_hh, z, B, Tz, c, (float *)saved, (hipStream_t)stream);
+}
+
+extern "C" int vqcpc_encoder_context_bwd(vqcpc_encoder *e, const float *z, int B, int Tz, const float *w_ih, const float *w_hh,
+                                         const float *c, const void *saved, const float *grad_c, float *grad_z, float *grad_w_ih,
+                                         float *grad_w_hh, float *grad_bias, void *stream) {
+    VQ_REQUIRE(e && z && c && saved && grad_c, "vqcpc_encoder_context_bwd: null argument");
+    LstmWeights w;
+    bool own = false;
+    TRY(context_grad_begin(e, "vqcpc_encoder_context_bwd", B, Tz, w_ih, w_hh, nullptr, nullptr, false, w, own));
+    VQ_REQUIRE(aligned16(z) && aligned16(c) && aligned16(saved) && aligned16(grad_c) && aligned16(w.w_ih) && aligned16(w.w_hh) &&
+               aligned16(grad_z) && aligned16(grad_w_ih) && aligned16(grad_w_hh) && aligned16(grad_bias),
+               "vqcpc_encoder_context_bwd: z, c, saved, the weights and the gradients must be 16-byte aligned");
+    return vq_ctx_bwd(e->ctx, w, z, B, Tz, c, (const float *)saved, grad_c, grad_z, grad_w_ih, grad_w_hh, grad_bias, (hipStream_t)stream);
+}
+
 extern "C" int vqcpc_encoder_forward_stats(vqcpc_encoder *e, const float *z_pre, const float *z_q,
                                            const int64_t *idx, int n_rows, float *z_st, float *loss,
                                            float *perplexity, void *stream) {
@@ -319,6 +371,6 @@ extern "C" int vqcpc_encoder_vq_adapt(vqcpc_encoder *e, const float *x, int n_ro
 
 extern "C" int vqcpc_encoder_workspace_bytes(vqcpc_encoder *e, uint64_t *bytes) {
     VQ_REQUIRE(e && bytes, "vqcpc_encoder_workspace_bytes: null argument");
-    *bytes = (uint64_t)(e->bufA.cap + e->bufB.cap + e->zpre.cap + e->stats.cap + e->adapt.cap);
+    *bytes = (uint64_t)(e->bufA.cap + e->bufB.cap + e->zpre.cap + e->stats.cap + e->adapt.cap + e->ctx.bytes());
     return VQCPC_OK;
 }

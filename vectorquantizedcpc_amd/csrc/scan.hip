@@ -5,6 +5,7 @@
 // resident kernel instead (lstm_persist_kernel).
 #include "common.h"
 #include "ar_shared.h"
+#include "seq_step.h"
 #include <math.h>
 
 // ------------------------------------------------------------------------------------------
@@ -36,11 +37,11 @@ __global__ void build_wfrag_kernel(const float *__restrict__ W, int ldw, float *
     ((float4 *)Wf)[id] = v;
 }
 
-int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, DevBuf &out) {
+int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int rowmode, int H, DevBuf &out, hipStream_t s) {
     VQ_REQUIRE(K % (16 * ksplit) == 0 && ldw % 4 == 0, "build_wfrag: K=%d not a multiple of %d", K, 16 * ksplit);
     const size_t n4 = (size_t)n_rg * (K / 16) * 64;
     TRY(out.reserve(n4 * sizeof(float4)));
-    hipLaunchKernelGGL(build_wfrag_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, ldw, out.as<float>(), n_rg, K,
+    hipLaunchKernelGGL(build_wfrag_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, W, ldw, out.as<float>(), n_rg, K,
                        ksplit, rowmode, H);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
@@ -49,76 +50,9 @@ int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int row
 // ------------------------------------------------------------------------------------------
 // Sequence recurrences with a hoisted input projection (prenet bi-GRU, encoder LSTM).
 // ------------------------------------------------------------------------------------------
-struct SeqP {
-    const float *Wf;      // [dir][H/4 row groups][4 waves][SW][64] float4
-    const float *b_hh;    // GRU: [dir][3H]; LSTM: unused (folded into Gi)
-    const float *Gi;      // [B*T][ndir*G*H]  input projection (+ biases)
-    float *hbuf;          // [2][ndir][nbt][H*16]
-    float *cbuf;          // LSTM cell state [ndir][nbt][H*16]
-    float *out;           // [B][T][ndir*H]
-    const int *len;       // valid steps per utterance (nbt*16) or null = T for b < B
-    const int *row0;      // first row of every utterance in Gi / out (ragged rows) or null = b * T
-    int H, nbt, B, T, ndir;
-};
-
-template <int G, int SW>   // G = 3 GRU, 4 LSTM
+template <int G, int SW>   // G = 3 GRU, 4 LSTM; the step itself: seq_step.h
 __global__ __launch_bounds__(256) void seq_step_kernel(SeqP p, int step) {
-    __shared__ float red[4][16][17];
-    __shared__ float gate[16][17];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int rg = blockIdx.x, dir = blockIdx.y, H = p.H;
-    const size_t hsz = (size_t)p.nbt * H * 16;
-    const float *hin = p.hbuf + ((size_t)(step & 1) * p.ndir + dir) * hsz;
-    float *hout = p.hbuf + ((size_t)((step + 1) & 1) * p.ndir + dir) * hsz;
-    const int bt = blockIdx.z;                     // one utterance tile per workgroup
-    // cell-update operands of wave 0's lanes are requested first: they do not depend on this step's
-    // W_hh h, so their latency hides under the fragment loads and the MFMAs
-    const int u = (tid >> 4) & 3, b = tid & 15, bg = bt * 16 + b, unit = 4 * rg + u;
-    bool act = false;
-    int tpos = 0;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f, bh0 = 0.f, bh1 = 0.f, bh2 = 0.f, hold = 0.f, cold = 0.f;
-    const size_t hi = hl_index(H, bg, unit);
-    if (tid < 64) {
-        const int L = p.len ? p.len[bg] : (bg < p.B ? p.T : 0);
-        if (step < L) {
-            act = true;
-            tpos = dir == 0 ? step : L - 1 - step;
-            const float *gi = p.Gi + ((p.row0 ? (size_t)p.row0[bg] : (size_t)bg * p.T) + tpos) * (p.ndir * G * H) + (size_t)dir * G * H + unit;
-            g0 = gi[0]; g1 = gi[H]; g2 = gi[2 * H];
-            if (G == 3) {
-                const float *bh = p.b_hh + (size_t)dir * 3 * H + unit;
-                bh0 = bh[0]; bh1 = bh[H]; bh2 = bh[2 * H];
-                hold = hin[hi];
-            } else {
-                g3 = gi[3 * H];
-                cold = p.cbuf[(size_t)dir * hsz + hi];
-            }
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float4 wf[SW];
-    load_wfrag<SW>(p.Wf + (size_t)dir * (H / 4) * (H / 16) * 64 * 4, rg, 4, wave, lane, wf);
-    const f32x4 acc = mv16<SW>(wf, hin, H, bt, wave, lane);
-    const float v = reduce4(red, acc, wave, lane, tid);
-    gate[tid >> 4][tid & 15] = v;
-    __syncthreads();
-    if (act) {
-        float hn;
-        if (G == 3) {
-            const float r = sigmoidf_(g0 + (gate[u][b] + bh0));
-            const float z = sigmoidf_(g1 + (gate[4 + u][b] + bh1));
-            const float n = tanhf(g2 + r * (gate[8 + u][b] + bh2));
-            hn = (1.0f - z) * n + z * hold;
-        } else {
-            const float ig = sigmoidf_(g0 + gate[u][b]), fg = sigmoidf_(g1 + gate[4 + u][b]);
-            const float gg = tanhf(g2 + gate[8 + u][b]), og = sigmoidf_(g3 + gate[12 + u][b]);
-            const float cn = fg * cold + ig * gg;
-            p.cbuf[(size_t)dir * hsz + hi] = cn;
-            hn = og * tanhf(cn);
-        }
-        hout[hi] = hn;
-        p.out[((p.row0 ? (size_t)p.row0[bg] : (size_t)bg * p.T) + tpos) * (p.ndir * H) + (size_t)dir * H + unit] = hn;
-    }
+    seq_step_body<G, SW, false>(p, step, SeqSave{});
 }
 
 template <int G>
@@ -164,6 +98,10 @@ struct LstmPlan {
 };
 static int lstm_persist_launch(LstmPlan *p, int T, float *out, hipStream_t s);
 void vq_lstm_plan_destroy(LstmPlan *p) { delete p; }
+void vq_add_vec(const float *a, const float *b, float *o, int n, hipStream_t s) {
+    hipLaunchKernelGGL(add_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, b, o, n);
+}
+LstmWeights vq_lstm_plan_weights(const LstmPlan *p) { return LstmWeights{p->w_ih, p->w_hh, p->bias, p->Wf, p->D, p->H}; }
 int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int D, int H,
                         LstmPlan **out) {
     VQ_REQUIRE(D % 32 == 0 && (H == 64 || H == 128 || H == 256 || H == 512), "LSTM: need D %% 32 == 0 and a hidden size of 64, 128, 256 "
@@ -173,7 +111,7 @@ int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih,
     *out = p;
     TRY(dev_copy(p->w_ih, w_ih, (size_t)4 * H * D * sizeof(float), hipMemcpyDeviceToDevice));
     TRY(p->bias.reserve((size_t)4 * H * sizeof(float)));
-    hipLaunchKernelGGL(add_vec_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, 0, b_ih, b_hh, p->bias.as<float>(), 4 * H);
+    vq_add_vec(b_ih, b_hh, p->bias.as<float>(), 4 * H, 0);
     HIP_TRY(hipGetLastError());
     TRY(vq_build_wfrag(w_hh, H, H / 4, H, 4, 4, H, p->Wf));
     TRY(dev_copy(p->w_hh, w_hh, (size_t)4 * H * H * sizeof(float), hipMemcpyDeviceToDevice));

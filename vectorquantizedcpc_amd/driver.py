@@ -310,14 +310,23 @@ def fit_predictors(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int =
 
     Returns ``losses`` and ``accuracies`` (per step; reading them synchronises once per step), ``steps``, ``batches``,
     ``utterances`` and the speakers ``score_batches`` would name: ``speakers_skipped``, ``speakers_left_over``."""
-    S, U, K = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker, cpc.n_prediction_steps
+    K = cpc.n_prediction_steps
+    return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device,
+                [p for m in cpc.predictors[:K] for p in m.parameters()], lambda z, c: c)
+
+
+def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params, context):
+    """The loop ``fit_predictors`` and ``fit_context`` share: the batches of ``_score_plan``, step i on batch ``i mod batches``,
+    every batch encoded once under ``no_grad`` and kept on the device, then per step ``context(z, c)`` -> the contexts the loss
+    reads, ``cpc(..., differentiable=True)``, ``backward()`` and one step of ``optimizer(params, lr=lr)``."""
+    S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
     dev = device if device is not None else next(encoder.parameters()).device
     n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
     res = {"losses": [], "accuracies": [], "steps": 0, "batches": n_batches, "utterances": n_batches * S * U,
            "speakers_skipped": skipped, "speakers_left_over": left}
     if n_batches == 0 or steps <= 0:
         return res
-    opt = optimizer([p for m in cpc.predictors[:K] for p in m.parameters()], lr=lr)
+    opt = optimizer(params, lr=lr)
     encoded = {}
     for step in range(steps):
         b = step % n_batches
@@ -330,13 +339,34 @@ def fit_predictors(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int =
         z, c = encoded[b]
         opt.zero_grad(set_to_none=True)
         with torch.enable_grad():
-            loss, acc = cpc(z, c, seed=seed, stream_id=b, differentiable=True)
+            loss, acc = cpc(z, context(z, c), seed=seed, stream_id=b, differentiable=True)
             loss.backward()
         opt.step()
         res["losses"].append(float(loss.detach()))
         res["accuracies"].append(list(acc))
         res["steps"] = step + 1
     return res
+
+
+def fit_context(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 200, lr: float = 4e-4, optimizer=torch.optim.Adam,
+                sample_frames: int = 128, seed: int = 13, device=None, train_predictors: bool = True):
+    """Refit the context LSTM ``encoder.rnn`` -- and, with ``train_predictors``, the K predictors of ``cpc`` with it, under one
+    optimizer as ``train_cpc.py:53-55`` has them -- on a frozen front end and codebook: after the codebook moves the LSTM sees units
+    it was never trained on (``adapt_codebook`` -> ``fit_context`` -> ``score_batches``).
+
+    The batches, the cuts and ``stream_id`` = batch number are those of ``score_batches`` and ``fit_predictors``.  The front end
+    and the VQ run under ``no_grad``, once per batch (they do not change; ``z`` is kept on the device).  Every step runs
+    ``c = encoder.context(z, differentiable=True)``, ``cpc(z, c, seed=seed, stream_id=batch, differentiable=True)`` and
+    ``backward()`` -- one ``vqcpc_cpc_grad`` call for dc (and dW, db), one ``vqcpc_encoder_context_bwd`` call for the LSTM's
+    gradients, dz not asked for -- then one step of ``optimizer(params, lr=lr)`` over ``encoder.rnn.parameters()`` (+
+    ``cpc.predictors[:K]``).  The native handles are not rebuilt between steps; the next ``encode`` / ``forward`` rebuilds the
+    encoder's once.
+
+    Returns what ``fit_predictors`` returns."""
+    K = cpc.n_prediction_steps
+    params = list(encoder.rnn.parameters()) + ([p for m in cpc.predictors[:K] for p in m.parameters()] if train_predictors else [])
+    return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params,
+                lambda z, c: encoder.context(z, differentiable=True))
 
 
 # ---------------------------------------------------------------------------------------- vocoder scoring

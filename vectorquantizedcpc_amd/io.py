@@ -94,16 +94,24 @@ def save_adapted_checkpoint(path, encoder_state: Dict[str, torch.Tensor], source
     torch.save(ck, path)
 
 
-def save_fitted_checkpoint(path, cpc_state: Dict[str, torch.Tensor], source=None, encoder_state=None):
+def save_fitted_checkpoint(path, cpc_state: Dict[str, torch.Tensor], source=None, encoder_state=None, encoder_update=None):
     """Write a checkpoint whose ``"cpc"`` entry is ``cpc_state`` -- all ``CPCLoss.state_dict()`` keys, the refitted predictors
     and the unused ones alike (``driver.fit_predictors``), every tensor on the CPU -- with the other entries of the checkpoint
     ``source`` was loaded from (``"encoder"``, ...) carried over untouched.  Without a ``source`` (seeded weights),
-    ``encoder_state`` becomes the ``"encoder"`` entry.  The counterpart of ``save_adapted_checkpoint``."""
+    ``encoder_state`` becomes the ``"encoder"`` entry.  The counterpart of ``save_adapted_checkpoint``.
+    ``encoder_update`` (``driver.fit_context``: the refitted ``rnn.*`` tensors): entries of ``"encoder"`` to replace, each of which
+    must already be there; the rest of ``"encoder"`` stays as it was."""
     ck = {}
     if source is not None:
         ck = {k: v for k, v in torch.load(source, map_location="cpu", weights_only=True).items() if k != "cpc"}
     elif encoder_state is not None:
         ck["encoder"] = {k: v.detach().cpu().clone() for k, v in encoder_state.items()}
+    if encoder_update:
+        missing = [k for k in encoder_update if k not in ck.get("encoder", {})]
+        if missing:
+            raise KeyError(f"save_fitted_checkpoint: the checkpoint's \"encoder\" entry has no {missing}")
+        ck["encoder"] = dict(ck["encoder"])
+        ck["encoder"].update({k: v.detach().cpu().clone() for k, v in encoder_update.items()})
     ck["cpc"] = {k: v.detach().cpu().clone() for k, v in cpc_state.items()}
     torch.save(ck, path)
 

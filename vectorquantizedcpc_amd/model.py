@@ -155,7 +155,8 @@ class Encoder(_lib.NativeModule):
 
     def workspace_bytes(self) -> int:
         """Device bytes of the native handle's grow-only work buffers (``vqcpc_encoder_workspace_bytes``): front-end activations,
-        statistics and the work space of the codebook update -- the peak of the calls so far, weights not counted."""
+        statistics and the work spaces of the codebook update and of the context gradients -- the peak of the calls so far, weights
+        not counted."""
         import ctypes
         n = ctypes.c_uint64()
         _lib.check(_lib.load().vqcpc_encoder_workspace_bytes(self._native(), ctypes.byref(n)))
@@ -270,6 +271,80 @@ class Encoder(_lib.NativeModule):
         stats = self._adapt_rows(rows, idx=idx)
         return (stats[0], stats[1], idx) if return_indices else (stats[0], stats[1])
 
+    # ------------------------------------------------------------------ the context LSTM and its gradient
+    _RNN_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+    def _sizes_handle(self, dev):
+        """The handle for a call that reads the LSTM's weights from the CALLER's pointers (``vqcpc_encoder_context_fwd`` /
+        ``_bwd``): it gives sizes and work space only, so any live handle on ``dev`` serves -- also one whose copies an optimizer
+        step has made stale (``CPCLoss._sizes_handle`` is the same rule).  ``encode`` / ``forward`` still go through ``_native()``,
+        which rebuilds once when it sees the moved ``_version``."""
+        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
+            return self._handle
+        return self._native()
+
+    def _rnn_weights(self, dev):
+        ws = [getattr(self.rnn, n) for n in self._RNN_NAMES]
+        for n, t in zip(self._RNN_NAMES, ws):
+            if t.dtype != torch.float32 or t.device != dev:
+                raise RuntimeError(f"rnn.{n} must be a float32 tensor on {dev} (got {t.dtype}, {t.device})")
+        return ws
+
+    def _context_fwd(self, z: Tensor, weights=None):
+        """One ``vqcpc_encoder_context_fwd`` call on contiguous fp32 device tensors -> (c, saved).  ``weights``: the four LSTM
+        tensors (contiguous), or None = the handle's copies."""
+        import ctypes
+        B, T, _ = z.shape
+        dev = z.device
+        h = self._sizes_handle(dev) if weights is not None else self._native()
+        lib = _lib.load()
+        n = ctypes.c_uint64()
+        _lib.check(lib.vqcpc_encoder_context_saved_bytes(h, B, T, ctypes.byref(n)))
+        c = torch.empty(B, T, self.conf.c_dim, device=dev)
+        saved = torch.empty(int(n.value) // 4, device=dev)
+        wp = [w.data_ptr() for w in weights] if weights is not None else [None] * 4
+        with _lib.device_guard(dev):
+            _lib.check(lib.vqcpc_encoder_context_fwd(h, z.data_ptr(), B, T, *wp, c.data_ptr(), saved.data_ptr(), _lib.current_stream()))
+        return c, saved
+
+    def _context_bwd(self, z: Tensor, c: Tensor, saved: Tensor, grad_c: Tensor, weights=None, want=(True, True, True, True)):
+        """One ``vqcpc_encoder_context_bwd`` call.  want = (z, w_ih, w_hh, bias) booleans -> the four gradients or None."""
+        B, T, _ = z.shape
+        dev = z.device
+        h = self._sizes_handle(dev) if weights is not None else self._native()
+        H, D = self.conf.c_dim, self.conf.z_dim
+        shapes = ((B, T, D), (4 * H, D), (4 * H, H), (4 * H,))
+        grads = [torch.empty(sh, device=dev) if w else None for sh, w in zip(shapes, want)]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        wp = [weights[0].data_ptr(), weights[1].data_ptr()] if weights is not None else [None, None]
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().vqcpc_encoder_context_bwd(h, z.data_ptr(), B, T, *wp, c.data_ptr(), saved.data_ptr(),
+                                                             grad_c.data_ptr(), *[ptr(g) for g in grads], _lib.current_stream()))
+        return grads
+
+    def context(self, z: Tensor, *, differentiable: bool = False) -> Tensor:
+        """``self.rnn(z)[0]`` (``model.py:69`` / ``:85``): z (B, T, z_dim) on the module's device -> c (B, T, c_dim).
+
+        differentiable=False (the default): ``vqcpc_encoder_context``, detached.  differentiable=True, grad mode on and ``z`` or any
+        ``rnn`` parameter requiring grad: ``c`` carries a ``grad_fn``.  Its forward is ``vqcpc_encoder_context_fwd`` on the
+        parameters as they are (an optimizer step costs no new handle) and keeps the gates and cell states; its backward is one
+        ``vqcpc_encoder_context_bwd`` call (``csrc/context_grad.hip``: back-propagation through time, one launch per step, every
+        sum in a fixed order) asking only for the gradients that are needed; ``bias_ih_l0`` and ``bias_hh_l0`` receive the same
+        values.  The value has the bits of the default call.  Under ``torch.no_grad()`` the flag changes nothing."""
+        _lib.require_cuda(z, "z")
+        _lib.require_same_device(z, self.rnn.weight_ih_l0, "z")
+        if z.dim() != 3 or z.size(2) != self.conf.z_dim or z.size(0) < 1 or z.size(1) < 1:
+            raise RuntimeError(f"expected z of shape (B, T, {self.conf.z_dim}), got {tuple(z.shape)}")
+        if differentiable and torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in self.rnn.parameters())):
+            ws = self._rnn_weights(z.device)
+            return _ContextGrad.apply(self, z.to(torch.float32), *ws)
+        zf = z.detach().to(torch.float32).contiguous()
+        B, T, _ = zf.shape
+        c = torch.empty(B, T, self.conf.c_dim, device=zf.device)
+        with _lib.device_guard(zf.device):
+            _lib.check(_lib.load().vqcpc_encoder_context(self._native(), zf.data_ptr(), B, T, c.data_ptr(), _lib.current_stream()))
+        return c
+
     def forward(self, mels: Tensor):
         """``model.py:72-86`` in eval mode: (z, c, vq_loss, perplexity)."""
         if self.training:
@@ -307,8 +382,9 @@ class CPCLoss(_lib.NativeModule):
     ``forward(z, c)`` is checkpoint SCORING: the value of the objective, detached.  ``forward(z, c, differentiable=True)`` under
     grad mode returns a loss that ``backward()`` can be called on: ``vqcpc_cpc_grad`` (``csrc/cpc_grad.hip``) computes the loss
     and the gradients with respect to ``z``, ``c`` and the first K predictors in one call, every sum in a fixed order, so equal
-    inputs give equal bits.  That is what ``driver.fit_predictors`` refits the predictors with on a frozen encoder; the encoder,
-    the VQ straight-through estimator and the context LSTM have no backward here, and the optimizer is torch's.
+    inputs give equal bits.  That is what ``driver.fit_predictors`` refits the predictors with on a frozen encoder, and what
+    ``driver.fit_context`` hands to ``Encoder.context(z, differentiable=True)`` to refit the context LSTM with them; the encoder's
+    front end and the VQ straight-through estimator have no backward here, and the optimizer is torch's.
 
     All ``n_prediction_steps`` predictors are held (the reference's 24 ``state_dict()`` keys, so
     ``load_state_dict(checkpoint["cpc"])`` works unchanged); like the reference only the first half is ever used
@@ -468,6 +544,31 @@ class CPCLoss(_lib.NativeModule):
             return loss, acc.tolist()
         r = self.forward_detailed(z, c, negatives=negatives, seed=seed, stream_id=stream_id)
         return r["loss"], r["accuracy"].tolist()
+
+
+class _ContextGrad(torch.autograd.Function):
+    """``Encoder.context(z, differentiable=True)``: ``forward`` is ``vqcpc_encoder_context_fwd`` and keeps ``saved``; ``backward``
+    is one ``vqcpc_encoder_context_bwd`` call asking for the gradients ``needs_input_grad`` names."""
+
+    @staticmethod
+    def forward(ctx, module, z, w_ih, w_hh, b_ih, b_hh):
+        z = z.detach().contiguous()
+        ws = [w.detach().contiguous() for w in (w_ih, w_hh, b_ih, b_hh)]
+        c, saved = module._context_fwd(z, ws)
+        ctx.module, ctx.kept = module, (z, saved)
+        ctx.save_for_backward(w_ih, w_hh, c)             # torch refuses the backward if an in-place step has moved them since
+        ctx.want = (ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3],
+                    ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+        return c
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_c):
+        (z, saved), (w_ih, w_hh, c) = ctx.kept, ctx.saved_tensors
+        gz, gi, gh, gb = ctx.module._context_bwd(z, c, saved, grad_c.to(torch.float32).contiguous(),
+                                                 (w_ih.detach().contiguous(), w_hh.detach().contiguous()), ctx.want)
+        need = ctx.needs_input_grad
+        return None, gz, gi, gh, gb if need[4] else None, gb if need[5] else None
 
 
 class _CPCGrad(torch.autograd.Function):
