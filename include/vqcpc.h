@@ -373,7 +373,19 @@ typedef struct {
 
 typedef struct vqcpc_vocoder vqcpc_vocoder;
 
-/* Replaces Vocoder.__init__ + load_state_dict (network_vocoder.py:31-39; convert.py:33,45). */
+/* Replaces Vocoder.__init__ + load_state_dict (network_vocoder.py:31-39; convert.py:33,45).
+ * Accepted sizes (anything else: VQCPC_ERR_INVALID with a message that names the field):
+ *   bits_mu_law            8 (config.py:69), 9, 10, with n_cls = 2^bits_mu_law
+ *   Hf  = size_h_fc        256 (config.py:77), 512, 768, 1024
+ *   Hr  = size_h_rnn       512, 896 (config.py:76), 1024
+ *   Hp  = dim_voc_latent/2 64, 128 (config.py:68), 256, 512
+ *   de  = size_i_embed_ar  any multiple of 32 (config.py:75: 256)
+ *   dz + ds                any multiple of 32 (config.py:65-66: 64 + 64)
+ *   upsample_t             any value > 0 (config.py:70: 160)
+ *   n_codes, n_speakers    any value > 0
+ * Every value of every list, and widths and hops from the smallest up, are checked against a float64 statement of the model
+ * on every decode path they reach (tests/test_gpu_vocoder_sizes.py).  vqcpc_vocoder_nll additionally needs Hf 256 and 8 bits
+ * (any listed Hr); the resident decoders need Hr 896, Hf 256 and 8 bits and take any de, Hp, dz + ds and upsample_t. */
 int vqcpc_vocoder_create(const vqcpc_vocoder_weights *w, vqcpc_vocoder **out);
 void vqcpc_vocoder_destroy(vqcpc_vocoder *voc);
 

@@ -10,6 +10,9 @@ every product and sum is float64, so a GPU error is bounded directly, not throug
   tabled: ``emb @ W_ih[:, :256]^T`` (256 rows) and ``cond @ W_ih[:, 256:]^T + b_ih`` (one row per frame), so a step is one
   ``h @ W_hh^T``, the gates, and a copy of h; fc1 / fc2 run afterwards as one GEMM per chunk of steps.
 * Speed (8 host threads, one CPU process): B = 8 at ~2 900 steps/s, B = 1 at ~6 500 steps/s.
+* Every size comes from the state dict and the hop (160 above) is the ``upsample`` argument.  ``dtype=torch.float32`` turns the
+  class into an fp32 yardstick of itself, and ``generate`` runs it free (Gumbel-max on the protocol's noise): what
+  tests/vocoder_size_cases.py sets its tolerances from at model sizes no other CPU statement covers.
 
 ``stressed(sd)`` is a second weight set that drives the decode into saturation without making the recurrence chaotic:
 AR GRU W_ih, b_ih, b_hh x10, W_hh x0.7, fc2 weight and bias x16; prenet W_ih and biases x4.  W_hh of both GRUs stays at or
@@ -54,8 +57,8 @@ def stressed(sd):
     return out
 
 
-def _d(t):
-    return torch.as_tensor(t).detach().cpu().to(torch.float64)
+def _d(t, dtype=torch.float64):
+    return torch.as_tensor(t).detach().cpu().to(dtype)
 
 
 def _gru_update(gi, gh, h):
@@ -67,29 +70,38 @@ def _gru_update(gi, gh, h):
 
 
 class F64Vocoder:
-    def __init__(self, sd, upsample=160):
+    """Every size comes from the state dict; ``upsample`` is ``upsampling_t``.  ``dtype=torch.float32`` runs the very same
+    statements in fp32 on the CPU: the yardstick whose distance from float64 sets a GPU tolerance at sizes nothing else covers
+    (tests/vocoder_size_cases.py)."""
+
+    def __init__(self, sd, upsample=160, dtype=torch.float64):
         self.up = upsample
-        self.code_emb = _d(sd["code_embedding.weight"])
-        self.spk_emb = _d(sd["speaker_embedding.weight"])
+        self.dtype = dtype
+
+        def w(t):
+            return _d(t, dtype)
+
+        self.code_emb = w(sd["code_embedding.weight"])
+        self.spk_emb = w(sd["speaker_embedding.weight"])
         self.prenet = []
         for layer in range(2):
             dirs = []
             for suf in ("", "_reverse"):
                 p = f"rnnms.prenet.%s_l{layer}{suf}"
-                dirs.append((_d(sd[p % "weight_ih"]), _d(sd[p % "weight_hh"]), _d(sd[p % "bias_ih"]), _d(sd[p % "bias_hh"])))
+                dirs.append((w(sd[p % "weight_ih"]), w(sd[p % "weight_hh"]), w(sd[p % "bias_ih"]), w(sd[p % "bias_hh"])))
             self.prenet.append(dirs)
-        emb = _d(sd[_AR + "embedding.weight"])
-        w_ih = _d(sd[_AR + "rnn.weight_ih_l0"])
+        emb = w(sd[_AR + "embedding.weight"])
+        w_ih = w(sd[_AR + "rnn.weight_ih_l0"])
         de = emb.shape[1]
         self.n_cls = emb.shape[0]
         self.emb_tab = emb @ w_ih[:, :de].T                       # (n_cls, 3 Hr)
         self.w_ih_cond = w_ih[:, de:]
-        self.b_ih = _d(sd[_AR + "rnn.bias_ih_l0"])
-        self.w_hh_t = _d(sd[_AR + "rnn.weight_hh_l0"]).T.contiguous()
-        self.b_hh = _d(sd[_AR + "rnn.bias_hh_l0"])
+        self.b_ih = w(sd[_AR + "rnn.bias_ih_l0"])
+        self.w_hh_t = w(sd[_AR + "rnn.weight_hh_l0"]).T.contiguous()
+        self.b_hh = w(sd[_AR + "rnn.bias_hh_l0"])
         self.Hr = self.w_hh_t.shape[0]
-        self.fc1_w, self.fc1_b = _d(sd[_AR + "fc1.weight"]), _d(sd[_AR + "fc1.bias"])
-        self.fc2_w, self.fc2_b = _d(sd[_AR + "fc2.weight"]), _d(sd[_AR + "fc2.bias"])
+        self.fc1_w, self.fc1_b = w(sd[_AR + "fc1.weight"]), w(sd[_AR + "fc1.bias"])
+        self.fc2_w, self.fc2_b = w(sd[_AR + "fc2.weight"]), w(sd[_AR + "fc2.bias"])
 
     # ------------------------------------------------------------------ prenet
     def _scan(self, x, w_ih, w_hh, b_ih, b_hh):
@@ -97,8 +109,8 @@ class F64Vocoder:
         B, T, _ = x.shape
         gi = x @ w_ih.T + b_ih
         w_hh_t = w_hh.T.contiguous()
-        h = torch.zeros(B, w_hh.shape[1], dtype=torch.float64)
-        out = torch.empty(B, T, w_hh.shape[1], dtype=torch.float64)
+        h = torch.zeros(B, w_hh.shape[1], dtype=self.dtype)
+        out = torch.empty(B, T, w_hh.shape[1], dtype=self.dtype)
         for t in range(T):
             h = _gru_update(gi[:, t], torch.addmm(b_hh, h, w_hh_t), h)
             out[:, t] = h
@@ -114,7 +126,7 @@ class F64Vocoder:
 
     @torch.no_grad()
     def condition(self, z, spk, n_codes=None):
-        """Prenet output per utterance: a list of (2 n_codes[b], 256) float64 tensors."""
+        """Prenet output per utterance: a list of (2 n_codes[b], dim_voc_latent) tensors of the model's dtype."""
         z = torch.as_tensor(z).long().cpu()
         spk = torch.as_tensor(spk).long().cpu()
         B, Tc = z.shape
@@ -140,18 +152,18 @@ class F64Vocoder:
             assert lengths[b] <= self.up * cond[b].shape[0], "history longer than the conditioning covers"
         # per-frame input half of the gates, padded with the last frame of each utterance (values past lengths[b] unused)
         nf = max(c.shape[0] for c in cond)
-        ctab = torch.empty(B, nf, 3 * self.Hr, dtype=torch.float64)
+        ctab = torch.empty(B, nf, 3 * self.Hr, dtype=self.dtype)
         for b, c in enumerate(cond):
             ctab[b, : c.shape[0]] = c @ self.w_ih_cond.T + self.b_ih
             ctab[b, c.shape[0]:] = ctab[b, c.shape[0] - 1]
-        out = torch.zeros(B, T, self.n_cls, dtype=torch.float64)
-        h = torch.zeros(B, self.Hr, dtype=torch.float64)
+        out = torch.zeros(B, T, self.n_cls, dtype=self.dtype)
+        h = torch.zeros(B, self.Hr, dtype=self.dtype)
         rows = torch.arange(B)[:, None]
         for t0 in range(0, max(lengths), chunk):
             n = min(chunk, T - t0)
             t = torch.arange(t0, t0 + n)
             gi = (self.emb_tab[inputs[:, t0:t0 + n]] + ctab[rows, t // self.up]).transpose(0, 1).contiguous()   # (n, B, 3Hr)
-            hs = torch.empty(n, B, self.Hr, dtype=torch.float64)
+            hs = torch.empty(n, B, self.Hr, dtype=self.dtype)
             for s in range(n):
                 h = _gru_update(gi[s], torch.addmm(self.b_hh, h, self.w_hh_t), h)
                 hs[s] = h
@@ -160,6 +172,31 @@ class F64Vocoder:
         for b in range(B):
             out[b, lengths[b]:] = 0.0
         return out
+
+    @torch.no_grad()
+    def generate(self, cond, seed, utt_ids, lengths=None):
+        """Free-running Gumbel-max decode in the model's dtype: (samples (B, T) int64, logits (B, T, n_cls)), T = the longest
+        row; the first input is n_cls / 2, scores are logit + the protocol's fp32 noise, the draw is the first argmax.  Steps at
+        or past ``lengths[b]`` (default: all the conditioning covers) are left at 0."""
+        B = len(cond)
+        full = [self.up * c.shape[0] for c in cond]
+        lengths = full if lengths is None else [min(int(n), f) for n, f in zip(lengths, full)]
+        T = max(lengths)
+        gc = [c @ self.w_ih_cond.T + self.b_ih for c in cond]
+        nz = torch.from_numpy(np.stack([noise(seed, [utt_ids[b]], 0, T, self.n_cls)[0] for b in range(B)])).to(self.dtype)
+        x = torch.full((B,), self.n_cls // 2, dtype=torch.long)
+        h = torch.zeros(B, self.Hr, dtype=self.dtype)
+        samples = torch.zeros(B, T, dtype=torch.long)
+        logits = torch.zeros(B, T, self.n_cls, dtype=self.dtype)
+        for t in range(T):
+            gi = self.emb_tab[x] + torch.stack([g[min(t // self.up, g.shape[0] - 1)] for g in gc])
+            h = _gru_update(gi, torch.addmm(self.b_hh, h, self.w_hh_t), h)
+            lg = torch.addmm(self.fc2_b, torch.relu(torch.addmm(self.fc1_b, h, self.fc1_w.T)), self.fc2_w.T)
+            x = torch.argmax(lg + nz[:, t], dim=1)
+            live = torch.tensor([t < n for n in lengths])
+            samples[:, t] = torch.where(live, x, torch.zeros_like(x))
+            logits[:, t] = lg * live[:, None].to(self.dtype)
+        return samples, logits
 
 
 # ---------------------------------------------------------------------- sampling protocol

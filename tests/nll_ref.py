@@ -52,18 +52,21 @@ class Ref:
     """The float64 reference of one scoring call and what the checks derive from it.  Arrays are (B, L - 1); `mask` marks the
     scored positions of every row."""
 
-    def __init__(self, name, audio, z, spk, n_codes=None, lengths=None):
+    def __init__(self, name, audio, z, spk, n_codes=None, lengths=None, sd=None, upsample=160, tol=None):
+        """`name`: one of the two weight sets of this module -- or, with a state dict `sd`, only a label: the model is then
+        F64Vocoder(sd, upsample) at whatever sizes `sd` has, and `tol` its logit tolerance E."""
         audio = torch.as_tensor(audio).long().cpu()
         B, L = audio.shape
         self.name = name
         self.lengths = [L] * B if lengths is None else [int(n) for n in lengths]
         self.n_scored = np.array([max(n - 1, 0) for n in self.lengths], np.int64)
-        f = f64_model(name)
-        lg = f.logits(audio[:, :-1].clamp(0, 255), f.condition(z, spk, n_codes), list(self.n_scored))
-        self.nll, self.lse, self.et, self.gap_target, self.gap_second = nll_from_energies(lg, audio[:, 1:].clamp(0, 255))
+        f = f64_model(name) if sd is None else f64_ref.F64Vocoder(sd, upsample=upsample)
+        top = f.n_cls - 1
+        lg = f.logits(audio[:, :-1].clamp(0, top), f.condition(z, spk, n_codes), list(self.n_scored))
+        self.nll, self.lse, self.et, self.gap_target, self.gap_second = nll_from_energies(lg, audio[:, 1:].clamp(0, top))
         self.mask = np.arange(L - 1)[None, :] < self.n_scored[:, None]
         self.nll = np.where(self.mask, self.nll, 0.0)
-        tol = LOGIT_TOL[name]
+        tol = LOGIT_TOL[name] if tol is None else tol
         r = 16.0 * f64_ref.ulp_f32(np.maximum(1.0, np.maximum(np.abs(self.lse), np.abs(self.et))))
         self.R = np.where(self.mask, r, 0.0)
         self.bound = np.where(self.mask, 2.0 * tol + r, 0.0)            # per sample

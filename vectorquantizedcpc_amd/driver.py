@@ -174,7 +174,12 @@ BYTES_PER_PADDED_SAMPLE = 4
 
 def decode_chunks(n_codes: Sequence[int], mem_budget_bytes: int, upsample: int = 160) -> List[List[int]]:
     """Utterance ids, in order, cut into decode calls whose device work space stays under ``mem_budget_bytes`` (at least one
-    utterance per call).  Sizes for the reference's dimensions (``config.py:62-77``)."""
+    utterance per call).  Sizes for the reference's dimensions (``config.py:62-77``).
+
+    Assumes: ``BYTES_PER_OWN_FRAME`` counts a glue width of 128, ``dim_voc_latent`` 256 and ``size_h_rnn`` 896 -- per frame
+    ``4 * ((dz + ds) + 6 Hp + 2 * 2 Hp + 3 Hr)`` bytes in general, so a model with a wider prenet or GRU (up to 2.1x at
+    256 / 1024 / 1024) needs a budget scaled by that ratio; only ``upsample`` is an argument.  The padded grids do not depend
+    on the model's widths."""
     chunks, cur, own, tmax = [], [], 0, 0
     for i, nc in enumerate(n_codes):
         f = 2 * int(nc)
