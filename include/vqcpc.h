@@ -20,7 +20,10 @@
  *    finished.  vqcpc_vocoder_generate / _logits do NOT synchronise the stream: their host-built
  *    tables (lengths, decode-slot schedule, call records) go through a pinned staging arena owned by
  *    the handle, and a call waits only for the event behind the PREVIOUS call's uploads before it
- *    reuses that arena.
+ *    reuses that arena.  "Does not synchronise" speaks of the library: the HIP runtime holds a bounded number of commands per
+ *    stream, and a call that enqueues thousands of launches (a use_graph = 0 decode: three per sample) behind work that has not
+ *    started waits on the host for room, as any such sequence of launches does (MI355X: between 1 920 and 2 880 of them).
+ *    Held on a caller's stream, entry by entry, by tests/test_gpu_stream_contract.py.
  *  - Return 0 on success, a negative vqcpc_status otherwise; never throws.
  *    vqcpc_last_error() returns a thread-local message for the last failure.
  *  - One handle per device; a handle is not thread-safe; distinct handles are independent.

@@ -1,9 +1,20 @@
 #!/bin/sh
-# A/B builds of the per-XCD decoder: build/exp/NAME/libvqcpc_hip.so = the current objects with ar_xcd.hip recompiled with extra defines.
-# usage: tools/build_variant.sh NAME "-DXD_GSPLIT=8 ..."   (then: python tools/ab_libs.py build/exp/A/libvqcpc_hip.so build/exp/B/libvqcpc_hip.so)
+# A/B and mutation builds: build/exp/NAME/libvqcpc_hip.so = the current objects with ONE translation unit recompiled.
+# usage: tools/build_variant.sh NAME "-DXD_GSPLIT=8 ..." [UNIT [SOURCE]]
+#   UNIT    the translation unit to recompile, without .hip (default ar_xcd: the A/B builds of the per-XCD decoder)
+#   SOURCE  the file to compile in its place (default csrc/UNIT.hip), e.g. a copy with one line changed, to show that a test
+#           file notices the fault; such copies and libraries live under build/ and are never committed
+# then: python tools/ab_libs.py build/exp/A/libvqcpc_hip.so build/exp/B/libvqcpc_hip.so
+# Build the library first (make -C vectorquantizedcpc_amd/csrc): the other units are linked from its objects.
 set -e
 cd "$(dirname "$0")/.."
 C=vectorquantizedcpc_amd/csrc
+U=${3:-ar_xcd}
+SRC=${4:-$C/$U.hip}
 mkdir -p build/exp/$1
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off $2 -c $C/ar_xcd.hip -o build/exp/$1/ar_xcd.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/exp/$1/libvqcpc_hip.so $C/runtime.o $C/gemm_chain.o $C/encoder.o $C/encoder_host.o $C/codebook.o $C/vocoder.o $C/vocoder_host.o $C/vocoder_plan.o $C/vocoder_stream.o $C/nll.o $C/scan.o build/exp/$1/ar_xcd.o $C/ar_xcm.o $C/melfront.o $C/loudness.o $C/resample.o $C/cpc.o $C/cpc_grad.o $C/abx.o $C/gate_probe.o
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I$C $2 -c $SRC -o build/exp/$1/$U.o
+OBJS=
+for o in runtime gemm_chain encoder encoder_host codebook vocoder vocoder_host vocoder_plan vocoder_stream nll scan ar_xcd ar_xcm melfront loudness resample cpc cpc_grad context_grad abx gate_probe; do
+    if [ $o = $U ]; then OBJS="$OBJS build/exp/$1/$U.o"; else OBJS="$OBJS $C/$o.o"; fi
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/exp/$1/libvqcpc_hip.so $OBJS

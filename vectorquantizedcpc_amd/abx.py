@@ -290,7 +290,9 @@ def _enqueue(dev, tokens, blocks, n_frames, want_cost, borrowed, call) -> PairTa
     tok, lists, segs, rows, wg, nd, no = _tables(tokens, blocks, n_frames)
     with _lib.device_guard(dev):
         flat = np.concatenate([tok.reshape(-1), lists, segs, rows.reshape(-1)])
-        d = torch.from_numpy(flat).to(dev)
+        # through pinned memory: a copy from pageable memory ends in a stream synchronisation, and these calls promise none
+        # (torch's host allocator keeps the pinned block until the copy has run)
+        d = torch.from_numpy(flat).pin_memory().to(dev, non_blocking=True)
         o1 = tok.size; o2 = o1 + lists.size; o3 = o2 + segs.size
         cost = torch.empty(nd, dtype=torch.float32, device=dev) if want_cost else None
         plen = torch.empty(nd, dtype=torch.int32, device=dev) if want_cost else None
