@@ -10,6 +10,14 @@ Judge, per tensor (c, z, W_ih, W_hh, b), the same for every case: ``max |G - G64
 the rule of tests/cpc_grad_ref.py); where ``G64`` is identically zero the result must be exact ``+0``.  Nothing in it is measured
 on the code under test.
 
+``WIDE_CASES`` (tests/golden/ctx_grad_wide_pins.npz, the same tool): twelve more cases at D = 64 -- nine utterance tiles, row counts
+on and one past a slab edge, three tiles at H = 512, thirteen slabs at H = 64, 3 000 steps, the forward suite's ``stressed`` weight
+set, and upstream gradients that are zero but for late steps, as ``CPCLoss`` hands them over.  They are judged by the rule above and
+by ``judge_steps``: the same rule per time step for ``c`` and ``dz``, ``max_{b,d} |G[:, t] - G64[:, t]| <= 4 max(e_ref[t], 2^-24
+max |G64[:, t]|)`` with ``e_ref[t]`` the fp32 CPU error of that step, so that a step whose values are orders of magnitude below the
+tensor's largest is held to its own size; a step whose float64 values are all zero must come back zero.  ``FAULTS``: mistakes
+seeded into the restatements by a switch, which tests/test_ctx_grad_cpu.py shows the judges to notice.
+
 ``chain``: the composition ``cpc_grad_ref.loss_torch`` o ``nn.LSTM`` on the CPC fixture ``small_odd`` (its ``z``, index arrays and
 predictors; a seeded LSTM), judged by the same rule with ``e_ref`` from the same composition in torch fp32 on the CPU.
 """
@@ -27,6 +35,8 @@ TENSORS = ("c", "z", "W_ih", "W_hh", "b")
 GRADS = TENSORS[1:]
 N_SAMPLES = 64
 PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ctx_grad_pins.npz")
+WIDE_PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ctx_grad_wide_pins.npz")
+STEP_TENSORS = ("c", "z")                      # (B, T, .): judged per time step as well, on the wide cases
 
 # name -> B, T, D, H, weight scale
 CASES = {
@@ -41,6 +51,23 @@ CASES = {
     "t1": (4, 1, 64, 256, 1),                  # T = 1: dW_hh must be exactly zero
 }
 ALL_CASES = list(CASES)
+
+# name -> B, T, H, stressed weights, upstream gradient ("dense", "last" = zero except t = T - 1, or the first t that is zero); D = 64
+WIDE_CASES = {
+    "b130": (130, 40, 256, False, "dense"),           # nine tiles, 2 live columns in the last; 5200 rows: six slabs, 80 rows in the last
+    "slab_exact": (16, 64, 256, False, "dense"),      # 1024 rows: one full slab, a full tile
+    "slab_plus_one": (25, 41, 256, False, "dense"),   # 1025 rows: the second slab holds one row
+    "h512_tiles": (33, 40, 512, False, "dense"),      # three tiles at NS = 32
+    "h64_slabs": (130, 100, 64, False, "dense"),      # smallest H, 13 slabs
+    "long": (2, 3000, 256, False, "dense"),           # 3000 steps of BPTT
+    "long_stressed": (2, 3000, 256, True, "dense"),   # saturated gates, a long carry chain
+    "b17_stressed": (17, 500, 256, True, "dense"),    # the same across a tile edge
+    "tail": (3, 60, 256, False, "last"),              # max |dz[t]| from 0.24 down to 1.7e-13
+    "tail_stressed": (3, 200, 256, True, "last"),     # max |dz[t]| from 1.76 down to 1.5e-4
+    "tail_h64": (18, 60, 64, False, "last"),          # the same at H = 64, two tiles
+    "cpc_shaped": (8, 70, 256, False, 64),            # zero for t >= 64: what CPCLoss (K = 6) hands over
+}
+ALL_WIDE = list(WIDE_CASES)
 CHAIN = "chain"                                # the composition with CPCLoss on small_odd
 
 _cases, _refs, _pins = {}, {}, None
@@ -61,12 +88,31 @@ def lstm_weights(name, D, H, scale=1):
 def load(name):
     """A case as a dict of fp32 torch tensors: ``z`` (B, T, D), ``w_ih`` ``w_hh`` ``b_ih`` ``b_hh``, upstream ``G`` (B, T, H), and its
     sizes.  Computed once and shared (treat as read-only)."""
+    if name not in _cases and name in WIDE_CASES:
+        _cases[name] = _load_wide(name)
     if name not in _cases:
         B, T, D, H, scale = CASES[name]
         g = dict(name=name, B=B, T=T, D=D, H=H, scale=scale, z=_u(name + "/z", (B, T, D), 1.0), G=_u(name + "/G", (B, T, H), 1.0))
         g.update(lstm_weights(name, D, H, scale))
         _cases[name] = g
     return _cases[name]
+
+
+def _load_wide(name):
+    B, T, H, stress, upstream = WIDE_CASES[name]
+    D = 64
+    G = _u(name + "/G", (B, T, H), 1.0)
+    if upstream == "last":
+        G[:, :T - 1] = 0.0
+    elif upstream != "dense":
+        G[:, upstream:] = 0.0
+    g = dict(name=name, B=B, T=T, D=D, H=H, scale=1, z=_u(name + "/z", (B, T, D), 1.0), G=G)
+    g.update(lstm_weights(name, D, H))
+    if stress:                                 # oracle/f64_enc_ref.py: stressed
+        for k in ("w_ih", "b_ih", "b_hh"):
+            g[k] = g[k] * 8.0
+        g["b_ih"][H:2 * H] += 3.0
+    return g
 
 
 def module(g, dtype=torch.float64):
@@ -103,7 +149,7 @@ def sample_positions(name, tensor, numel):
 def pins():
     global _pins
     if _pins is None:
-        _pins = dict(np.load(PINS))
+        _pins = {**np.load(PINS), **np.load(WIDE_PINS)}            # keys start with the case's name: the two files share none
     return _pins
 
 
@@ -134,6 +180,36 @@ def judge(name, got, what):
               f"bound {bound(name, k):.3g}, max|G64| = {np.abs(ref[k]).max():.3g}")
         if not (np.isfinite(a).all() and err <= bound(name, k)):
             bad.append((k, err, bound(name, k)))
+    assert not bad, bad
+
+
+def step_max(a):
+    """(B, T, n) -> (T,): the largest magnitude of every time step."""
+    return np.abs(a).max(axis=(0, 2))
+
+
+def judge_steps(name, got, what):
+    """``c`` and ``dz`` of a wide case against float64 step by step: for every t, ``max_{b,d} |G[:, t] - G64[:, t]| <=
+    4 max(e_ref[t], 2^-24 max |G64[:, t]|)``, and a step that is identically zero in float64 comes back zero.  Prints the worst
+    ratio to the bound and its t, then asserts."""
+    ref, p = grads64(name), pins()
+    bad = []
+    for k in STEP_TENSORS:
+        if got.get(k) is None:
+            continue
+        a = np.asarray(got[k]).astype(f64)
+        assert a.shape == ref[k].shape, (k, a.shape, ref[k].shape)
+        top, e_ref = p[f"{name}_{k}_step_max"], p[f"{name}_{k}_step_e_ref"]
+        limit = 4.0 * np.maximum(e_ref, U32 * top)
+        zero = top == 0.0
+        with np.errstate(invalid="ignore"):
+            err = np.where(np.isfinite(a).all(axis=(0, 2)), step_max(a - ref[k]), np.inf)
+        ratio = np.where(zero, np.where(err == 0.0, 0.0, np.inf), err / np.where(zero, 1.0, limit))
+        t = int(ratio.argmax())
+        print(f"{what} {name} {k} per step: worst err / bound = {ratio[t]:.3f} at t = {t} (err {err[t]:.3g}, e_ref[t] {e_ref[t]:.3g}, "
+              f"max|G64[:, t]| = {top[t]:.3g}); max|G64[:, t]| spans {top.min():.3g} .. {top.max():.3g}; {int(zero.sum())} zero steps")
+        if not ratio[t] <= 1.0:
+            bad.append((k, t, float(err[t]), float(limit[t])))
     assert not bad, bad
 
 
@@ -250,16 +326,25 @@ def forward32(g, dot):
     return gates, cell, tanhc, out
 
 
-def scan32(g, gates, cell, tanhc, grad_c, dot):
-    """The backward scan in the order of ctx_bwd_step_kernel: dA (B, T, 4H) fp32."""
+FAULTS = ("drop_rec", "flush_small", "masked_reads_col0", "skip_short_slab")     # seeded into the restatements only: scan32, products32, reordered32
+DROP_REC_STEPS, FLUSH_BELOW = 30, 1e-6
+
+
+def scan32(g, gates, cell, tanhc, grad_c, dot, fault=None):
+    """The backward scan in the order of ctx_bwd_step_kernel: dA (B, T, 4H) fp32.  ``fault``: "drop_rec" leaves the recurrent term
+    out for t < T - 30; "flush_small" stores as zero every dA value below 1e-6 of the largest stored so far (the scan starts at the
+    largest where the upstream gradient sits on the last step)."""
     B, T, H = grad_c.shape
     w_hh = g["w_hh"].numpy()
     w_hhT = np.ascontiguousarray(w_hh.T)
     dA = np.zeros((B, T, 4 * H), f32)
     carry = np.zeros((B, H), f32)
     one = f32(1)
+    top = 0.0
     for t in range(T - 1, -1, -1):
         dh_rec = dot(w_hhT, np.ascontiguousarray(dA[:, t + 1].T)).T if t + 1 < T else np.zeros((B, H), f32)
+        if fault == "drop_rec" and t < T - DROP_REC_STEPS:
+            dh_rec = np.zeros((B, H), f32)
         i, f, gg, o = (gates[:, t, q * H:(q + 1) * H] for q in range(4))
         tc = tanhc[:, t]
         cp = cell[:, t - 1] if t > 0 else np.zeros((B, H), f32)
@@ -270,6 +355,9 @@ def scan32(g, gates, cell, tanhc, grad_c, dot):
         dA[:, t, H:2 * H] = (dct * cp) * (f * (one - f))
         dA[:, t, 2 * H:3 * H] = (dct * i) * (one - gg * gg)
         dA[:, t, 3 * H:] = do_ * (o * (one - o))
+        if fault == "flush_small":
+            top = max(top, float(np.abs(dA[:, t]).max()))
+            dA[:, t][np.abs(dA[:, t]) < FLUSH_BELOW * top] = 0.0
         carry = dct * f
     return dA
 
@@ -311,15 +399,17 @@ def slab_colsum(A, slab=1024):
     return total
 
 
-def products32(g, dA, out, wdot, colsum, dot):
+def products32(g, dA, out, wdot, colsum, dot, fault=None):
+    """``fault`` "skip_short_slab": a last slab of fewer than 16 rows is left out of the weight and bias sums."""
     B, T, H4 = dA.shape
     H, D = H4 // 4, g["D"]
     A = dA.reshape(B * T, H4)
     h_prev = np.zeros_like(out)
     h_prev[:, 1:] = out[:, :-1]
     X = np.concatenate([g["z"].numpy().reshape(B * T, D), h_prev.reshape(B * T, H)], axis=1)
-    dW = wdot(A, X)
-    res = {"W_ih": dW[:, :D], "W_hh": dW[:, D:], "b": colsum(A), "z": dot(A, g["w_ih"].numpy()).reshape(B, T, D)}
+    summed = B * T - B * T % 1024 if fault == "skip_short_slab" and B * T % 1024 < 16 else B * T
+    dW = wdot(A[:summed], X[:summed])
+    res = {"W_ih": dW[:, :D], "W_hh": dW[:, D:], "b": colsum(A[:summed]), "z": dot(A, g["w_ih"].numpy()).reshape(B, T, D)}
     assert all(v.dtype == f32 for v in res.values())
     return res
 
@@ -346,13 +436,25 @@ def _tree(parts):
     return parts[0]
 
 
-def reordered32(name):
+def reordered32(name, fault=None):
     """fp32 numpy in orders that are NOT the kernels': 16-wide k chunks for the products, 64-row chunks and an adjacent-pair tree for
-    the weight sums."""
+    the weight sums.
+
+    ``fault`` (one of ``FAULTS``) seeds a mistake a kernel could make, to show that the judges notice it.  "masked_reads_col0": the
+    columns b >= B of the last 16-utterance tile carry utterance 0 where the kernels put zeros.  Inside the scan that is invisible by
+    construction (an output column depends on its own input column only, and the masked columns are not stored); it shows where the
+    masked columns' rows enter a sum over rows, so the restatement runs the batch padded to whole tiles with copies of utterance 0,
+    sums dW and db over all of it, and returns ``c`` and ``dz`` of the first B."""
     g = load(name)
+    B = g["B"]
+    if fault == "masked_reads_col0":
+        pad = [0] * (-B % 16)
+        g = dict(g, z=torch.cat([g["z"], g["z"][pad]]), G=torch.cat([g["G"], g["G"][pad]]))
     gates, cell, tanhc, out = forward32(g, chunk_dot)
-    dA = scan32(g, gates, cell, tanhc, g["G"].numpy(), chunk_dot)
+    dA = scan32(g, gates, cell, tanhc, g["G"].numpy(), chunk_dot, fault)
     # added to a zeroed gradient, as an accumulating .grad is
     wdot = lambda A, X: np.zeros((A.shape[1], X.shape[1]), f32) + _tree([A[r:r + 64].T @ X[r:r + 64] for r in range(0, A.shape[0], 64)])
     colsum = lambda A: np.zeros(A.shape[1], f32) + _tree([A[r:r + 64].sum(axis=0) for r in range(0, A.shape[0], 64)])
-    return dict(products32(g, dA, out, wdot, colsum, chunk_dot), c=out)
+    res = dict(products32(g, dA, out, wdot, colsum, chunk_dot, fault), c=out)
+    res["c"], res["z"] = res["c"][:B], res["z"][:B]
+    return res

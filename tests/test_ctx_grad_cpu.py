@@ -1,7 +1,11 @@
 """CPU-side checks of the context-LSTM gradients: the float64 reference of tests/ctx_grad_ref.py against its pins
 (tests/golden/ctx_grad_pins.npz), the judge held by an fp32 numpy restatement in the kernels' documented order and by a differently
 ordered one (so the bound is shown passable before a GPU is involved, and rests on nothing the GPU does), the ABI addition and the
-command line."""
+command line.
+
+The wide cases (tests/golden/ctx_grad_wide_pins.npz): their pins, the condition that the fp32 reference has kept its digits, both
+restatements under the whole-tensor and the per-step judge, and four faults seeded into the restatement that the judges must
+notice -- among them a scan that stops propagating 30 steps from the end, which the whole-tensor judge alone lets pass."""
 import os
 import re
 import subprocess
@@ -55,6 +59,108 @@ def test_kernel_order_restatement_of_the_chain_stays_within_the_judge():
 def test_structure_of_the_reference():
     assert not R.grads64("t1")["W_hh"].any()                         # no previous step: h_prev is zero
     assert all(R.grads64("t1")[k].any() for k in ("z", "W_ih", "b"))
+
+
+# ------------------------------------------------------------------ the wide cases (tests/golden/ctx_grad_wide_pins.npz)
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_wide_pins_reproduce_from_the_float64_reference(name):
+    ref, p = R.grads64(name), R.pins()
+    T = R.load(name)["T"]
+    for k, G in ref.items():
+        top = float(p[f"{name}_{k}_max"])
+        assert abs(np.abs(G).max() - top) <= 1e-12 * top
+        samples = G.reshape(-1)[R.sample_positions(name, k, G.size)]
+        assert np.abs(samples - p[f"{name}_{k}_samples"]).max() <= 1e-12 * top, k
+        s, ss = p[f"{name}_{k}_sums"]
+        assert abs(G.sum() - s) <= 1e-12 * np.abs(G).sum() and abs((G ** 2).sum() - ss) <= 1e-12 * ss, k
+        if k in R.STEP_TENSORS:
+            steps, e_ref = p[f"{name}_{k}_step_max"], p[f"{name}_{k}_step_e_ref"]
+            assert steps.shape == e_ref.shape == (T,)
+            assert (np.abs(R.step_max(G) - steps) <= 1e-12 * steps).all(), k       # step by step: a zero step is pinned as zero
+            assert steps.max() == top and e_ref.max() == float(p[f"{name}_{k}_e_ref"]), k
+
+
+def test_structure_of_the_wide_cases():
+    """The table of the cases holds what it says: tiles, slabs, and the shape of the upstream gradient and of dz."""
+    rows = {n: R.load(n)["B"] * R.load(n)["T"] for n in R.ALL_WIDE}
+    assert rows["slab_exact"] == 1024 and rows["slab_plus_one"] == 1025 and rows["b130"] == 5 * 1024 + 80 and rows["h64_slabs"] > 12 * 1024
+    assert all(R.load(n)["D"] == 64 for n in R.ALL_WIDE)
+    p = R.pins()
+    for n in ("tail", "tail_stressed", "tail_h64"):
+        G, dz = R.load(n)["G"], p[f"{n}_z_step_max"]
+        assert not G[:, :-1].any() and G[:, -1].all()
+        assert dz.argmax() == len(dz) - 1 and dz.argmin() == 0 and dz.min() > 0.0
+    assert p["tail_z_step_max"][0] < 1e-11 * p["tail_z_step_max"][-1] and p["tail_z_step_max"][0] > 1e-20     # far above fp32's subnormals
+    assert p["tail_stressed_z_step_max"][0] < 1e-3 * p["tail_stressed_z_step_max"][-1]
+    G, dz = R.load("cpc_shaped")["G"], p["cpc_shaped_z_step_max"]
+    assert G[:, :64].all() and not G[:, 64:].any() and dz[:64].all() and not dz[64:].any()
+    g = R.load("long_stressed")
+    plain = R.lstm_weights("long_stressed", 64, 256)
+    H = g["H"]
+    lift = torch.zeros(4 * H)
+    lift[H:2 * H] = 3.0
+    assert torch.equal(g["w_ih"], plain["w_ih"] * 8) and torch.equal(g["w_hh"], plain["w_hh"]) and torch.equal(g["b_hh"], plain["b_hh"] * 8)
+    assert torch.equal(g["b_ih"], plain["b_ih"] * 8 + lift)
+
+
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_fp32_reference_of_the_wide_cases_has_not_drifted(name):
+    """The condition on the inputs: e_ref <= 1e-5 max |G64| for every tensor, so the judge's bound is a statement about fp32 and not
+    about a reference that lost its digits."""
+    p = R.pins()
+    for k in R.TENSORS:
+        e_ref, top = float(p[f"{name}_{k}_e_ref"]), float(p[f"{name}_{k}_max"])
+        print(f"{name} {k}: e_ref / max|G64| = {e_ref / top:.3g}")
+        assert 0.0 < e_ref <= 1e-5 * top, (k, e_ref, top)
+
+
+def both_judges(name, got, what):
+    R.judge(name, got, what)
+    R.judge_steps(name, got, what)
+
+
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_reordered_fp32_restatement_stays_within_both_judges(name):
+    both_judges(name, R.reordered32(name), "reordered fp32 numpy")
+
+
+@pytest.mark.parametrize("name", [n for n in R.ALL_WIDE if R.WIDE_CASES[n][1] <= 500])      # at T = 3000 its loops take most of a minute
+def test_kernel_order_fp32_restatement_stays_within_both_judges(name):
+    both_judges(name, R.kernel_order32(name), "kernel-order fp32 numpy")
+
+
+# ------------------------------------------------------------------ would the judges notice?  Faults seeded into the restatement
+def fails(judge, name, got, what):
+    try:
+        judge(name, got, what)
+    except AssertionError as e:
+        print(f"{what} {name}: {judge.__name__} fails: {e}")
+        return True
+    return False
+
+
+def test_a_scan_that_stops_propagating_passes_the_whole_tensor_judge_and_fails_the_per_step_one():
+    """The gap the per-step judge closes, in one assertion: the recurrent term dropped for t < T - 30 on ``tail``."""
+    got = R.reordered32("tail", fault="drop_rec")
+    R.judge("tail", got, "dh_rec dropped for t < T - 30:")                           # the largest elements are all at late steps
+    assert fails(R.judge_steps, "tail", got, "dh_rec dropped for t < T - 30:")
+
+
+def test_flushed_small_dA_values_are_noticed():
+    got = R.reordered32("tail_stressed", fault="flush_small")
+    fails(R.judge, "tail_stressed", got, "dA below 1e-6 of its maximum flushed:")    # printed, not required: the values are small
+    assert fails(R.judge_steps, "tail_stressed", got, "dA below 1e-6 of its maximum flushed:")
+
+
+def test_masked_columns_that_carry_column_0_are_noticed():
+    got = R.reordered32("b130", fault="masked_reads_col0")
+    R.judge_steps("b130", got, "masked columns carry utterance 0:")                  # c and dz of a live column do not see them
+    assert fails(R.judge, "b130", got, "masked columns carry utterance 0:")          # the sums over rows do
+
+
+def test_a_skipped_short_last_slab_is_noticed():
+    got = R.reordered32("slab_plus_one", fault="skip_short_slab")
+    assert fails(R.judge, "slab_plus_one", got, "last slab of one row skipped:")
 
 
 # ------------------------------------------------------------------ ABI

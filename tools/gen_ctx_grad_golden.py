@@ -1,12 +1,17 @@
-"""Writes tests/golden/ctx_grad_pins.npz: what tests/ctx_grad_ref.py's float64 reference of the context-LSTM gradients gave when
-this ran -- per case and tensor 64 sampled elements, the sum and the sum of squares, the largest magnitude -- and
-``e_ref = max |G_ref32 - G_ref64|``, the error of the same ``torch.nn.LSTM`` (and, for ``chain``, of the same composition with the
-CPC loss) run in fp32 on the CPU.  The judge of the tests is built from these alone.
+"""Writes the pins of tests/ctx_grad_ref.py's float64 reference of the context-LSTM gradients: per case and tensor 64 sampled
+elements, the sum and the sum of squares, the largest magnitude -- and ``e_ref = max |G_ref32 - G_ref64|``, the error of the same
+``torch.nn.LSTM`` (and, for ``chain``, of the same composition with the CPC loss) run in fp32 on the CPU.  The judges of the tests
+are built from these alone.
 
-    python tools/gen_ctx_grad_golden.py
+tests/golden/ctx_grad_wide_pins.npz: the wide cases; for ``c`` and ``z`` also, per time step, ``max |G64[:, t]|`` and
+``e_ref[t] = max |G32[:, t] - G64[:, t]|``, both (T,).  Written with fixed archive dates: the same bytes at every run.
+tests/golden/ctx_grad_pins.npz: the nine cases and ``chain``; left as it is unless ``--nine`` is given.
+
+    python tools/gen_ctx_grad_golden.py [--nine]
 """
 import os
 import sys
+import zipfile
 
 import numpy as np
 import torch
@@ -17,10 +22,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import ctx_grad_ref as R  # noqa: E402
 
 
-def main():
-    torch.set_num_threads(1)                                        # one summation order for the recorded fp32 error
+def pins_of(names, per_step):
     out = {}
-    for name in R.ALL_CASES + [R.CHAIN]:
+    for name in names:
         ref = R.grads64(name)
         low = R.chain_grads(torch.float32) if name == R.CHAIN else R.torch_grads(name, torch.float32)
         for k, G in ref.items():
@@ -29,8 +33,29 @@ def main():
             out[f"{name}_{k}_max"] = np.float64(np.abs(G).max())
             out[f"{name}_{k}_e_ref"] = np.float64(np.abs(low[k] - G).max())
             print(f"{name} {k}: max {out[f'{name}_{k}_max']:.3g}, e_ref {out[f'{name}_{k}_e_ref']:.3g}")
-    np.savez(R.PINS, **out)
-    print(f"wrote {R.PINS} ({os.path.getsize(R.PINS)} bytes)")
+            if per_step and k in R.STEP_TENSORS:
+                top, err = R.step_max(G), R.step_max(low[k] - G)
+                out[f"{name}_{k}_step_max"], out[f"{name}_{k}_step_e_ref"] = top, err
+                print(f"{name} {k} per step: max {top.min():.3g} .. {top.max():.3g}, e_ref {err.min():.3g} .. {err.max():.3g}")
+    return out
+
+
+def write_npz(path, arrays):
+    """An uncompressed .npz as ``np.load`` reads it, with the archive's dates fixed (``np.savez`` stamps the time of writing)."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as zf:
+        for key, value in arrays.items():
+            with zf.open(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(value), allow_pickle=False)
+    print(f"wrote {path} ({os.path.getsize(path)} bytes)")
+
+
+def main():
+    torch.set_num_threads(1)                                        # one summation order for the recorded fp32 error
+    if "--nine" in sys.argv[1:]:
+        out = pins_of(R.ALL_CASES + [R.CHAIN], per_step=False)
+        np.savez(R.PINS, **out)
+        print(f"wrote {R.PINS} ({os.path.getsize(R.PINS)} bytes)")
+    write_npz(R.WIDE_PINS, pins_of(R.ALL_WIDE, per_step=True))
 
 
 if __name__ == "__main__":
