@@ -14,3 +14,4 @@ from .ref import (  # noqa: F401
     linear, lstm, sumsq64, philox4x32_10, sample_noise, noise_from_word, mulaw_decode,
     vocoder_generate, vocoder_condition, sample_from_logits,
 )
+from .judge import judge_draws  # noqa: F401

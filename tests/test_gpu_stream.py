@@ -8,51 +8,17 @@ import ctypes as C
 import pytest
 import torch
 
+import decode_harness as H
 import vectorquantizedcpc_amd as V
 from vectorquantizedcpc_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
-_cache = {}
+vocoder = H.Handles()
 
 
-def vocoder(fresh=False, conf=None, sd=None):
-    if fresh or conf is not None or "v" not in _cache:
-        v = V.Vocoder(conf or V.ConfVocoder())
-        v.load_state_dict(sd or synth.vocoder_state_dict())
-        v = v.to("cuda").eval()
-        if fresh or conf is not None:
-            return v
-        _cache["v"] = v
-    return _cache["v"]
-
-
-def inputs(tag, B, Tc, ragged=True, n_cls_codes=512):
-    z = synth.randint(f"st/z{tag}{B}", (B, Tc), n_cls_codes).cuda()
-    spk = synth.randint(f"st/s{tag}{B}", (B,), 102).cuda()
-    n_codes = [max(1, Tc - (b % Tc)) for b in range(B)] if ragged and B > 1 else None
-    return z, spk, n_codes
-
-
-def streamed(voc, z, spk, chunk, path=None, **kw):
-    st = voc.generate_stream(z, spk, chunk_samples=chunk, return_mulaw=True, **kw)
-    ws, ms = [], []
-    total = st.position[1]
-    for w, m in st:
-        if path is not None:
-            assert voc.last_path() == path
-        assert w.shape[1] == min(chunk, total - sum(x.shape[1] for x in ws))
-        ws.append(w)
-        ms.append(m)
-    return torch.cat(ws, 1), torch.cat(ms, 1)
-
-
-def assert_same(voc, z, spk, chunk, path=None, seed=17, utt_base=5, **kw):
-    want_w, want_m = voc.generate(z, spk, return_mulaw=True, seed=seed, utt_base=utt_base, **kw)
-    got_w, got_m = streamed(voc, z, spk, chunk, path=path, seed=seed, utt_base=utt_base, **kw)
-    assert got_w.shape == want_w.shape
-    assert torch.equal(got_m, want_m) and torch.equal(got_w, want_w)
-    assert int((got_m != 0).sum()) > 0.9 * int((want_m != 0).sum()) > 0
-    return want_w, want_m
+def inputs(tag, B, Tc, ragged=True):
+    z, spk = H.inputs(f"st/?{tag}{B}", B, Tc)
+    return z, spk, H.ragged_countdown(B, Tc) if ragged and B > 1 else None
 
 
 @pytest.mark.parametrize("B,slots", [(1, (1, 1)), (5, (5, 5)), (12, (9, 16)), (20, (17, 32)), (32, (32, 32))])
@@ -60,41 +26,41 @@ def assert_same(voc, z, spk, chunk, path=None, seed=17, utt_base=5, **kw):
 def test_resident_decoders(B, slots, chunk):
     """The slot layout follows the slots in use (xd_pick_bxt of slots per XCD): B = 1 and 5 run ar_xcd_resume_kernel<1> (one slot
     per XCD, some XCDs idle at 5), 12 <2> (two per XCD), 20 <4>, 32 <4> with all four MFMA columns live."""
-    voc = vocoder()
+    voc, _ = vocoder()
     z, spk, n_codes = inputs("r", B, 4)
     st = voc.generate_stream(z, spk, chunk_samples=chunk, seed=17, utt_base=5, n_codes=n_codes)
     next(st)                                              # the first chunk: every utterance live
     assert voc.last_path() == 2 and slots[0] <= voc.last_slots() <= slots[1]
     st.close()
     assert st.position == (chunk, 1280)
-    assert_same(voc, z, spk, chunk, path=2, n_codes=n_codes)
+    H.assert_same(voc, z, spk, chunk, path=2, n_codes=n_codes)
 
 
 @pytest.mark.parametrize("B,fuse", [(1, 1), (3, 0), (3, 1), (17, 1), (40, 0), (80, 1)])
 def test_launch_path(B, fuse):
     """xcd = 0: ar_gru_kernel (one and two tiles, fused and three-launch), two tile groups on two streams at 40 three-launch
     (three tiles: 2 + 1, each group with its own state, slot table and call record), ar_gru_big_kernel at 80 (five tiles)."""
-    voc = vocoder(fresh=True)
+    voc, _ = vocoder(fresh=True)
     voc.set_option("xcd", 0)
     voc.set_option("fuse_fc2", fuse)
     z, spk, n_codes = inputs("l", B, 4)
     for chunk in (160, 480):
-        assert_same(voc, z, spk, chunk, path=0, n_codes=n_codes)
+        H.assert_same(voc, z, spk, chunk, path=0, n_codes=n_codes)
 
 
 def test_launch_path_back_to_back_slots():
-    voc = vocoder(fresh=True)
+    voc, _ = vocoder(fresh=True)
     voc.set_option("xcd", 0)
     voc.set_option("slots", 4)
     z, spk, n_codes = inputs("b", 6, 4)
-    assert_same(voc, z, spk, 480, path=0, n_codes=n_codes)
+    H.assert_same(voc, z, spk, 480, path=0, n_codes=n_codes)
     assert voc.last_slots() == 4
 
 
 @pytest.mark.parametrize("B", [40, 100])
 def test_more_utterances_than_slots(B):
     """Resumed segments back to back in the 32 slots of ar_xcd.hip; the one-shot call at 100 runs on ar_xcm.hip."""
-    voc = vocoder()
+    voc, _ = vocoder()
     z, spk, n_codes = inputs("m", B, 3)
     voc.generate(z, spk, seed=3, utt_base=0, n_codes=n_codes)
     assert voc.last_path() == (2 if B <= 68 else 3)
@@ -102,7 +68,7 @@ def test_more_utterances_than_slots(B):
     next(st)
     assert voc.last_slots() == 32                          # the first chunk: every utterance live, 32 slots, the rest behind them
     st.close()
-    assert_same(voc, z, spk, 640, path=2, n_codes=n_codes)
+    H.assert_same(voc, z, spk, 640, path=2, n_codes=n_codes)
 
 
 def test_other_sizes_launch_path():
@@ -111,23 +77,23 @@ def test_other_sizes_launch_path():
     conf.rnnms.bits_mu_law = 9
     conf.rnnms.wave_ar.size_h_rnn = 512
     conf.rnnms.wave_ar.size_h_fc = 512
-    voc = vocoder(conf=conf, sd=sd)
+    voc, _ = vocoder(conf=conf, sd=sd)
     z, spk, n_codes = inputs("o", 3, 3)
     for chunk in (160, 320):
-        assert_same(voc, z, spk, chunk, path=0, n_codes=n_codes)
+        H.assert_same(voc, z, spk, chunk, path=0, n_codes=n_codes)
 
 
 @pytest.mark.parametrize("B,chunk", [(1, 1600), (32, 3200), (1, 32000)])
 def test_full_size(B, chunk):
     """1 x 32 000 and the benchmark's 32 x 32 000 (Tc = 100 codes), and one chunk for the whole utterance."""
-    voc = vocoder()
+    voc, _ = vocoder()
     z = synth.randint(f"st/full{B}", (B, 100), 512).cuda()
     spk = synth.randint(f"st/fulls{B}", (B,), 102).cuda()
-    assert_same(voc, z, spk, chunk, path=2, seed=11, utt_base=0)
+    H.assert_same(voc, z, spk, chunk, path=2, seed=11, utt_base=0)
 
 
 def test_interleaved_streams_and_calls():
-    voc = vocoder(fresh=True)
+    voc, _ = vocoder(fresh=True)
     za, sa, na = inputs("ia", 3, 4)
     zb, sb, _ = inputs("ib", 2, 3, ragged=False)
     zc, sc, _ = inputs("ic", 5, 2, ragged=False)
@@ -153,7 +119,7 @@ def test_interleaved_streams_and_calls():
 
 
 def test_reported_chunk_is_decoded_again():
-    voc = vocoder(fresh=True)
+    voc, _ = vocoder(fresh=True)
     z, spk, n_codes = inputs("re", 4, 4)
     want_w, want_m = voc.generate(z, spk, return_mulaw=True, seed=9, utt_base=0, n_codes=n_codes)
     # Python: the stream repeats the chunk once, with a warning
@@ -190,7 +156,7 @@ def test_reported_chunk_is_decoded_again():
 def test_a_chunk_that_fails_twice_ends_the_stream(monkeypatch):
     """If the repeat of a reported chunk is reported as well, the state the next chunk would start from is not there: the stream
     closes, raises, and refuses to go on."""
-    voc = vocoder(fresh=True)
+    voc, _ = vocoder(fresh=True)
     z, spk, n_codes = inputs("f", 3, 2)
     st = voc.generate_stream(z, spk, chunk_samples=160, seed=9, utt_base=0, n_codes=n_codes)
     next(st)

@@ -15,23 +15,18 @@ import numpy as np
 import pytest
 import torch
 
+import decode_harness as H
 import oracle
 import vectorquantizedcpc_amd as V
 from vectorquantizedcpc_amd import synth
 
 pytestmark = pytest.mark.gpu
-_cache = {}
+# this file exercises the launch-per-step kernels; the per-XCD resident decoders (the default up to 64 utterances) are in test_gpu_xcd.py
+vocoder = H.Handles(xcd=0)
 
 
-def vocoder():
-    if "v" not in _cache:
-        sd = synth.vocoder_state_dict()
-        v = V.Vocoder(V.ConfVocoder())
-        v.load_state_dict(sd)
-        v = v.to("cuda").eval()
-        v.set_option("xcd", 0)          # this file exercises the launch-per-step kernels;
-        _cache["v"] = (v, sd)           # the per-XCD resident decoders (the default up to 64 utterances) are in test_gpu_xcd.py
-    return _cache["v"]
+def options(voc, **opts):
+    return H.options(voc, {**H.DEFAULTS, "xcd": 0}, **opts)
 
 
 def test_glue_and_prenet_condition(golden_dir):
@@ -61,13 +56,13 @@ def test_mulaw_table_equals_the_reference_decode(golden_dir):
     dec = np.load(os.path.join(golden_dir, "preprocess.npz"))["mulaw_decode_256"].astype(np.float32)
     z = synth.randint("mt/z", (4, 8), 512).cuda()
     spk = synth.randint("mt/spk", (4,), 102).cuda()
-    for xcd in (0, 1):
-        voc.set_option("xcd", xcd)
-        wav, mu = voc.generate(z, spk, seed=21, utt_base=0, return_mulaw=True)
-        wav, mu = wav.cpu().numpy(), mu.cpu().numpy()
-        assert np.array_equal(wav, dec[mu])
-        assert len(np.unique(mu)) > 200                       # most of the 256 classes occur in 10 240 samples
-    voc.set_option("xcd", 0)
+    with options(voc) as set_option:
+        for xcd in (0, 1):
+            set_option("xcd", xcd)
+            wav, mu = voc.generate(z, spk, seed=21, utt_base=0, return_mulaw=True)
+            wav, mu = wav.cpu().numpy(), mu.cpu().numpy()
+            assert np.array_equal(wav, dec[mu])
+            assert len(np.unique(mu)) > 200                       # most of the 256 classes occur in 10 240 samples
 
 
 def test_teacher_forced_logits():
@@ -91,25 +86,15 @@ def _check_free_run(voc, sd, z, spk, n_codes, seed, utt_base, steps):
     wav, mu = voc.generate(z.cuda(), spk.cuda(), n_codes=n_codes, seed=seed, utt_base=utt_base, return_mulaw=True,
                            max_steps=steps)
     wav, mu = wav.cpu().numpy(), mu.cpu().numpy()
-    stats = []
-    for b in range(z.shape[0]):
-        nc = z.shape[1] if n_codes is None else n_codes[b]
-        n = min(steps, 320 * nc)
-        s_gpu = mu[b, :n]
-        inputs = np.concatenate([[128], s_gpu[:-1]])
-        r = oracle.vocoder_generate(sd, z[b, :nc].numpy(), int(spk[b]), seed=seed, utterance=utt_base + b, n_steps=n,
-                                    inputs=inputs, want_logits=True)
-        exact = int((r["samples"] == s_gpu).sum())
-        for t in np.nonzero(r["samples"] != s_gpu)[0]:
-            pick, sc = oracle.sample_from_logits(r["logits"][t], seed, utt_base + b, int(t))
-            assert sc[pick] - sc[int(s_gpu[t])] <= 2e-5, (b, int(t), float(sc[pick]), float(sc[int(s_gpu[t])]))
-        want_wav = np.array([oracle.mulaw_decode(int(s)) for s in s_gpu], np.float32)
-        assert np.array_equal(wav[b, :n], want_wav)
-        assert not wav[b, n:].any() and not mu[b, n:].any()
-        stats.append((n, exact))
+    B = z.shape[0]
+    stats = oracle.judge_draws(sd, z, spk, mu, seed=seed, utt_ids=range(utt_base, utt_base + B), rows=range(B), steps=steps,
+                               n_codes=n_codes, wav=wav)
+    for b, (n, exact) in enumerate(stats):
+        assert not mu[b, n:].any()
         if exact == n:      # same samples -> compare with the oracle's own free run as well
+            nc = z.shape[1] if n_codes is None else n_codes[b]
             free = oracle.vocoder_generate(sd, z[b, :nc].numpy(), int(spk[b]), seed=seed, utterance=utt_base + b, n_steps=n)
-            assert np.array_equal(free["samples"], s_gpu)
+            assert np.array_equal(free["samples"], mu[b, :n])
             assert float(np.mean((free["wav"] - wav[b, :n]) ** 2)) <= 1e-5
     return stats
 
@@ -139,18 +124,16 @@ def test_graph_replay_equals_eager_launches():
     voc, _ = vocoder()
     z = synth.randint("gr/z", (2, 2), 512).cuda()
     spk = synth.randint("gr/spk", (2,), 102).cuda()
-    voc.set_option("use_graph", 1)
-    voc.set_option("steps_per_graph", 64)
-    a = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)
-    voc.set_option("use_graph", 0)
-    b = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)
-    voc.set_option("use_graph", 1)
-    voc.set_option("steps_per_graph", 160)
-    c = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)
-    d = voc.generate(z, spk, seed=4, utt_base=0, return_mulaw=True, max_steps=300)
-    voc.set_option("steps_per_graph", 32)              # divides the 160-sample hop: several replays per conditioning
-    e = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)     # frame, Gcond row cached per replay
-    voc.set_option("steps_per_graph", 160)
+    with options(voc, use_graph=1, steps_per_graph=64) as set_option:
+        a = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)
+        set_option("use_graph", 0)
+        b = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)
+        set_option("use_graph", 1)
+        set_option("steps_per_graph", 160)
+        c = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)
+        d = voc.generate(z, spk, seed=4, utt_base=0, return_mulaw=True, max_steps=300)
+        set_option("steps_per_graph", 32)              # divides the 160-sample hop: several replays per conditioning
+        e = voc.generate(z, spk, seed=3, utt_base=0, return_mulaw=True, max_steps=300)     # frame, Gcond row cached per replay
     assert torch.equal(a[1], b[1]) and torch.equal(a[0], b[0]) and torch.equal(a[1], c[1]) and torch.equal(a[1], e[1])
     assert not torch.equal(a[1], d[1])
     assert a[0].shape == (2, 640) and a[0].abs().max() <= 1.0
@@ -178,11 +161,8 @@ def test_continuous_batching_equals_static_batches():
     ids = [11, 12, 13, 14, 15, 16, 17]
     ref_w, ref_m = voc.generate(z.cuda(), spk.cuda(), n_codes=n_codes, seed=21, utt_ids=ids, return_mulaw=True)
     for slots in (2, 3):
-        voc.set_option("slots", slots)
-        try:
+        with options(voc, slots=slots):
             w, m = voc.generate(z.cuda(), spk.cuda(), n_codes=n_codes, seed=21, utt_ids=ids, return_mulaw=True)
-        finally:
-            voc.set_option("slots", 0)
         assert torch.equal(m, ref_m) and torch.equal(w, ref_w), slots
     assert int((ref_m[1, 320:] != 0).sum()) == 0 and int((ref_m[0] != 0).sum()) > 1000
 
@@ -214,19 +194,12 @@ def test_tile_groups_and_large_batch_kernel_are_bit_identical():
     n_codes = [1 + (i % 3) for i in range(B)]
     ids = list(range(100, 100 + B))
     outs = {}
-    try:
-        for name, opts in (("one_group", {"two_groups": 0, "big_min_tiles": 0}),
-                           ("two_groups", {"two_groups": 1, "big_min_tiles": 0}),
-                           ("big_kernel", {"two_groups": 0, "big_min_tiles": 2}),
-                           ("two_groups_36_slots", {"two_groups": 1, "big_min_tiles": 0, "slots": 36})):
-            for k, val in opts.items():
-                voc.set_option(k, val)
+    for name, opts in (("one_group", {"two_groups": 0, "big_min_tiles": 0}),
+                       ("two_groups", {"two_groups": 1, "big_min_tiles": 0}),
+                       ("big_kernel", {"two_groups": 0, "big_min_tiles": 2}),
+                       ("two_groups_36_slots", {"two_groups": 1, "big_min_tiles": 0, "slots": 36})):
+        with options(voc, **opts):
             outs[name] = voc.generate(z, spk, n_codes=n_codes, seed=9, utt_ids=ids, return_mulaw=True)[1]
-            voc.set_option("slots", 0)
-    finally:
-        voc.set_option("two_groups", 1)
-        voc.set_option("big_min_tiles", 5)
-        voc.set_option("slots", 0)
     ref = outs["one_group"]
     assert int((ref != 0).sum()) > 10000
     for name, m in outs.items():
@@ -245,22 +218,13 @@ def test_large_batch_kernel_13_tiles_one_group_and_two_groups_bit_identical():
     n_codes = [1 + (i % 3) for i in range(B)]
     ids = list(range(5000, 5000 + B))
     outs = {}
-    try:
-        for name, opts in (("small_kernel", {"two_groups": 0, "big_min_tiles": 0}),
-                           ("big_one_group", {"two_groups": 0, "big_min_tiles": 5}),
-                           ("big_two_groups", {"two_groups": 1, "big_min_tiles": 5}),
-                           ("big_one_group_three_launches", {"two_groups": 0, "big_min_tiles": 5, "fuse_fc2": 0}),
-                           ("big_one_group_150_slots", {"two_groups": 0, "big_min_tiles": 5, "slots": 150})):
-            for k, val in opts.items():
-                voc.set_option(k, val)
+    for name, opts in (("small_kernel", {"two_groups": 0, "big_min_tiles": 0}),
+                       ("big_one_group", {"two_groups": 0, "big_min_tiles": 5}),
+                       ("big_two_groups", {"two_groups": 1, "big_min_tiles": 5}),
+                       ("big_one_group_three_launches", {"two_groups": 0, "big_min_tiles": 5, "fuse_fc2": 0}),
+                       ("big_one_group_150_slots", {"two_groups": 0, "big_min_tiles": 5, "slots": 150})):
+        with options(voc, **opts):
             outs[name] = voc.generate(z, spk, n_codes=n_codes, seed=17, utt_ids=ids, return_mulaw=True)[1]
-            voc.set_option("slots", 0)
-            voc.set_option("fuse_fc2", 1)
-    finally:
-        voc.set_option("two_groups", 1)
-        voc.set_option("big_min_tiles", 5)
-        voc.set_option("slots", 0)
-        voc.set_option("fuse_fc2", 1)
     ref = outs["small_kernel"]
     assert int((ref != 0).sum()) > 50000
     for name, m in outs.items():
@@ -296,17 +260,8 @@ def _check_rows_direct(voc, sd, B, rows, steps, seed, utt0, tag):
     wav, mu = voc.generate(z.cuda(), spk.cuda(), seed=seed, utt_base=utt0, return_mulaw=True, max_steps=steps)
     wav, mu = wav.cpu().numpy(), mu.cpu().numpy()
     assert np.isfinite(wav).all() and not mu[:, steps:].any()
-    n_exact = 0
-    for b in rows:
-        s_gpu = mu[b, :steps]
-        inputs = np.concatenate([[128], s_gpu[:-1]])
-        r = oracle.vocoder_generate(sd, z[b].numpy(), int(spk[b]), seed=seed, utterance=utt0 + b, n_steps=steps,
-                                    inputs=inputs, want_logits=True)
-        n_exact += int((r["samples"] == s_gpu).sum())
-        for t in np.nonzero(r["samples"] != s_gpu)[0]:
-            pick, sc = oracle.sample_from_logits(r["logits"][t], seed, utt0 + b, int(t))
-            assert sc[pick] - sc[int(s_gpu[t])] <= 2e-5, (tag, b, int(t))
-        assert np.array_equal(wav[b, :steps], np.array([oracle.mulaw_decode(int(s)) for s in s_gpu], np.float32))
+    stats = oracle.judge_draws(sd, z, spk, mu, seed=seed, utt_ids=range(utt0, utt0 + B), rows=rows, steps=steps, wav=wav)
+    n_exact = sum(e for _, e in stats)
     assert n_exact >= 0.999 * steps * len(rows)
     tv = torch_ref.TorchVocoder(sd)
     x_in = torch.from_numpy(np.concatenate([np.full((B, 1), 128), mu[:, : steps - 1]], axis=1))
@@ -365,14 +320,10 @@ def test_teacher_forced_scan_chunks_and_training_shape():
     spk = synth.randint("tf2/spk", (B,), 102)
     x = synth.randint("tf2/x", (B, Ts), 256)
     a = voc(x.cuda(), z.cuda(), spk.cuda())
-    try:
-        voc.set_option("tf_chunk_replays", 1)
+    with options(voc, tf_chunk_replays=1) as set_option:
         b = voc(x.cuda(), z.cuda(), spk.cuda())
-        voc.set_option("use_graph", 0)
+        set_option("use_graph", 0)
         c = voc(x.cuda(), z.cuda(), spk.cuda())
-    finally:
-        voc.set_option("use_graph", 1)
-        voc.set_option("tf_chunk_replays", 4)
     assert torch.equal(a, b) and torch.equal(a, c)
     r = oracle.vocoder_generate(sd, z[1].numpy(), int(spk[1]), seed=0, n_steps=Ts, inputs=x[1].numpy(), want_logits=True)
     worst = float(np.abs(a[1].cpu().numpy() - r["logits"]).max())
@@ -394,10 +345,10 @@ def test_single_utterance_default_path_equals_the_launch_path():
     voc, sd = vocoder()
     z = synth.randint("ps/z", (1, 4), 512)
     spk = torch.tensor([7])
-    try:
+    with options(voc) as set_option:
         w0, m0 = voc.generate(z.cuda(), spk.cuda(), seed=13, utt_base=3, return_mulaw=True)
         assert voc.last_path() == 0
-        voc.set_option("xcd", -1)
+        set_option("xcd", -1)
         w1, m1 = voc.generate(z.cuda(), spk.cuda(), seed=13, utt_base=3, return_mulaw=True)
         assert voc.last_path() == 2
         w2, m2 = voc.generate(z.cuda(), spk.cuda(), seed=13, utt_base=3, return_mulaw=True, max_steps=333)
@@ -408,8 +359,6 @@ def test_single_utterance_default_path_equals_the_launch_path():
         assert stats[0][1] >= 0.999 * stats[0][0]
         with pytest.raises(RuntimeError):
             voc.kernel_times(10)               # no launch-per-step state after a resident call
-    finally:
-        voc.set_option("xcd", 0)
 
 
 def test_fused_fc2_gru_launch_same_bits_and_direct_oracle():
@@ -425,14 +374,9 @@ def test_fused_fc2_gru_launch_same_bits_and_direct_oracle():
         n_codes = [1 + (i % 3) for i in range(B)]
         ids = list(range(500, 500 + B))
         outs = []
-        try:
-            for f2 in (1, 0):
-                voc.set_option("fuse_fc2", f2)
-                voc.set_option("slots", slots)
+        for f2 in (1, 0):
+            with options(voc, fuse_fc2=f2, slots=slots):
                 outs.append(voc.generate(z, spk, n_codes=n_codes, seed=77, utt_ids=ids, return_mulaw=True))
-        finally:
-            voc.set_option("fuse_fc2", 1)
-            voc.set_option("slots", 0)
         for o in outs[1:]:
             assert torch.equal(outs[0][1], o[1]) and torch.equal(outs[0][0], o[0]), (B, slots)
         assert int((outs[0][1] != 0).sum()) > 100 * B
@@ -451,9 +395,7 @@ def test_other_sizes_9_bit_mulaw_wider_fc_smaller_rnn():
     conf.rnnms.bits_mu_law = 9
     conf.rnnms.wave_ar.size_h_rnn = 512
     conf.rnnms.wave_ar.size_h_fc = 512
-    voc = V.Vocoder(conf)
-    voc.load_state_dict(sd)
-    voc = voc.to("cuda").eval()
+    voc, _ = vocoder(conf=conf, sd=sd)
     B, Tc, Ts = 3, 2, 300
     z = synth.randint("sz/z", (B, Tc), 512)
     spk = synth.randint("sz/spk", (B,), 102)
@@ -467,25 +409,14 @@ def test_other_sizes_9_bit_mulaw_wider_fc_smaller_rnn():
     print("9-bit / 512 / 512 teacher-forced logits, max |GPU - C oracle| = %.3g" % worst)
     assert worst <= 1e-5
     outs = []
-    for f2 in (1, 0):
-        voc.set_option("fuse_fc2", f2)
-        wav, mu = voc.generate(z.cuda(), spk.cuda(), seed=13, utt_base=40, return_mulaw=True, max_steps=Ts)
-        voc.check()
-        assert voc.last_path() == 0
-        outs.append((wav.cpu().numpy(), mu.cpu().numpy()))
-    voc.set_option("fuse_fc2", 1)
+    with H.options(voc) as set_option:
+        for f2 in (1, 0):
+            set_option("fuse_fc2", f2)
+            outs.append([t.numpy() for t in H.decode(voc, z.cuda(), spk.cuda(), path=0, seed=13, utt_base=40, max_steps=Ts)])
     assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][0], outs[1][0])
     wav, mu = outs[0]
     assert mu.max() > 255                                     # classes beyond 8 bits do occur
-    for b in range(B):
-        s_gpu = mu[b, :Ts]
-        inputs = np.concatenate([[256], s_gpu[:-1]])
-        r = oracle.vocoder_generate(sd, z[b].numpy(), int(spk[b]), seed=13, utterance=40 + b, n_steps=Ts, inputs=inputs,
-                                    want_logits=True, bits=9)
-        for t in np.nonzero(r["samples"] != s_gpu)[0]:
-            pick, sc = oracle.sample_from_logits(r["logits"][t], 13, 40 + b, int(t))
-            assert sc[pick] - sc[int(s_gpu[t])] <= 2e-5, (b, int(t))
-        assert np.array_equal(wav[b, :Ts], np.array([oracle.mulaw_decode(int(v), 9) for v in s_gpu], np.float32))
+    oracle.judge_draws(sd, z, spk, mu, seed=13, utt_ids=range(40, 40 + B), rows=range(B), steps=Ts, wav=wav, bits=9)
     # 100 utterances: the large-batch kernel; rows 0..2 are the utterances above
     z2 = torch.cat([z, synth.randint("sz/z2", (97, Tc), 512)])
     spk2 = torch.cat([spk, synth.randint("sz/s2", (97,), 102)])

@@ -7,127 +7,79 @@ test_gpu_vocoder.py, tolerance 2e-5 on the Gumbel-max score); (2) bit for bit ag
 BASELINE sizes (configs[2]: 1 x 32 000; configs[3]'s per-GPU shard: 32 x 32 000): an utterance alone equals itself in the
 batch, continuous batching through few slots equals one slot per utterance.
 """
-import numpy as np
 import pytest
 import torch
 
+import decode_harness as H
 import oracle
 import vectorquantizedcpc_amd as V
-from vectorquantizedcpc_amd import driver, synth
+from vectorquantizedcpc_amd import synth
 
 pytestmark = pytest.mark.gpu
-_cache = {}
-
-
-def vocoder(fresh=False):
-    if fresh or "v" not in _cache:
-        sd = synth.vocoder_state_dict()
-        v = V.Vocoder(V.ConfVocoder())
-        v.load_state_dict(sd)
-        v = v.to("cuda").eval()
-        if fresh:
-            return v, sd
-        _cache["v"] = (v, sd)
-    return _cache["v"]
+vocoder = H.Handles()
 
 
 def _both_paths(voc, z, spk, **kw):
-    out = {}
-    for mode in (1, 0):
-        voc.set_option("xcd", mode)
-        wav, mu = voc.generate(z, spk, return_mulaw=True, **kw)
-        voc.check()
-        out[mode] = (wav.cpu(), mu.cpu())
-    voc.set_option("xcd", -1)
-    return out
+    return H.path_pair(voc, z, spk, {"xcd": 1}, {"xcd": 0}, path=2, **kw)
 
 
 @pytest.mark.parametrize("B,Tc,ragged", [(1, 3, False), (2, 2, False), (3, 4, True), (4, 2, False), (9, 3, True), (17, 2, True),
                                          (32, 2, False)])
 def test_same_samples_as_the_launch_path(B, Tc, ragged):
     voc, _ = vocoder()
-    z = synth.randint(f"xcd/z{B}", (B, Tc), 512).cuda()
-    spk = synth.randint(f"xcd/s{B}", (B,), 102).cuda()
-    n_codes = [max(1, Tc - (b % Tc)) for b in range(B)] if ragged else None
-    out = _both_paths(voc, z, spk, n_codes=n_codes, seed=13, utt_base=3)
-    assert torch.equal(out[1][1], out[0][1]) and torch.equal(out[1][0], out[0][0])
-    assert int((out[1][1] != 0).sum()) > 0.9 * 320 * sum(n_codes or [Tc] * B)
+    z, spk = H.inputs(f"xcd/?{B}", B, Tc)
+    n_codes = H.ragged_countdown(B, Tc) if ragged else None
+    resident, launch = _both_paths(voc, z, spk, n_codes=n_codes, seed=13, utt_base=3)
+    H.assert_same_bits(resident, launch)
+    H.assert_live(resident[1], n_codes or [Tc] * B)
+
+
+def _draws_against_the_oracle(B, Tc, steps, tag, seed, utt_base, rows):
+    """(steps, exact draws) of ``rows`` of one call on the resident decoders, every draw and the waveform judged by the C oracle."""
+    voc, sd = vocoder()
+    z, spk = H.inputs(tag, B, Tc, device="cpu")
+    with H.options(voc, xcd=1):
+        wav, mu = H.decode(voc, z.cuda(), spk.cuda(), path=2, seed=seed, utt_base=utt_base, max_steps=steps)
+    return oracle.judge_draws(sd, z, spk, mu, seed=seed, utt_ids=range(utt_base, utt_base + B), rows=rows, steps=steps, wav=wav)
 
 
 @pytest.mark.parametrize("B", [5, 20])
 def test_draw_by_draw_against_the_oracle(B):
     """B = 5: one slot per XCD (fp32 vector chains); B = 20: up to three slots per XCD = the four-slot kernel, whose W_hh / fc1 chains run
     on the matrix pipe (v_mfma_f32_4x4x1_16B_f32, ar_chain.h) with one column idle."""
-    voc, sd = vocoder()
-    voc.set_option("xcd", 1)
-    try:
-        Tc, steps = 2, 480
-        z = synth.randint("xcd/oz", (B, Tc), 512)
-        spk = synth.randint("xcd/os", (B,), 102)
-        wav, mu = voc.generate(z.cuda(), spk.cuda(), seed=13, utt_base=11, return_mulaw=True, max_steps=steps)
-        voc.check()
-        wav, mu = wav.cpu().numpy(), mu.cpu().numpy()
-        exact = total = 0
-        for b in range(B):
-            s_gpu = mu[b, :steps]
-            inputs = np.concatenate([[128], s_gpu[:-1]])
-            r = oracle.vocoder_generate(sd, z[b].numpy(), int(spk[b]), seed=13, utterance=11 + b, n_steps=steps, inputs=inputs,
-                                        want_logits=True)
-            for t in np.nonzero(r["samples"] != s_gpu)[0]:
-                pick, sc = oracle.sample_from_logits(r["logits"][t], 13, 11 + b, int(t))
-                assert sc[pick] - sc[int(s_gpu[t])] <= 2e-5, (b, int(t))
-            exact += int((r["samples"] == s_gpu).sum())
-            total += steps
-            assert np.array_equal(wav[b, :steps], np.array([oracle.mulaw_decode(int(s)) for s in s_gpu], np.float32))
-            assert not wav[b, steps:].any()
-        assert exact >= 0.999 * total
-    finally:
-        voc.set_option("xcd", -1)
+    stats = _draws_against_the_oracle(B, 2, 480, "xcd/o?", seed=13, utt_base=11, rows=range(B))
+    assert sum(e for _, e in stats) >= 0.999 * sum(n for n, _ in stats)
 
 
 def test_more_utterances_than_slots_and_alone_equals_in_batch():
     """Continuous batching: 40 ragged utterances through 8 decode slots (one per XCD) and through all 32; every utterance
     equals the same utterance decoded alone (its sampling stream does not depend on the placement)."""
     voc, _ = vocoder()
-    n = 40
-    Tc = 3
-    z = synth.randint("xcd/cz", (n, Tc), 512).cuda()
-    spk = synth.randint("xcd/cs", (n,), 102).cuda()
-    n_codes = [1 + (7 * i) % Tc for i in range(n)]
+    n, Tc = 40, 3
+    z, spk = H.inputs("xcd/c?", n, Tc)
+    n_codes = H.ragged_sevens(n, Tc)
     ids = list(range(100, 100 + n))
-    voc.set_option("xcd", 1)
-    try:
+    with H.options(voc, xcd=1) as set_option:
         res = {}
         for slots in (8, 32):
-            voc.set_option("xcd_slots", slots)
-            wav, mu = voc.generate(z, spk, n_codes=n_codes, seed=5, utt_ids=ids, return_mulaw=True)
-            voc.check()
-            res[slots] = (wav.cpu(), mu.cpu())
-        assert torch.equal(res[8][1], res[32][1]) and torch.equal(res[8][0], res[32][0])
+            set_option("xcd_slots", slots)
+            res[slots] = H.decode(voc, z, spk, n_codes=n_codes, seed=5, utt_ids=ids)
+        H.assert_same_bits(res[8], res[32])
         for i in (0, 13, 39):
             w1, m1 = voc.generate(z[i:i + 1, :n_codes[i]], spk[i:i + 1], seed=5, utt_ids=[ids[i]], return_mulaw=True)
-            L = 320 * n_codes[i]
+            L = H.FRAME * n_codes[i]
             assert torch.equal(m1[0].cpu(), res[8][1][i, :L]) and torch.equal(w1[0].cpu(), res[8][0][i, :L])
             assert not res[8][1][i, L:].any()
-    finally:
-        voc.set_option("xcd_slots", 32)
-        voc.set_option("xcd", -1)
 
 
 def test_agent_scope_stores_same_bits():
     voc, _ = vocoder()
-    z = synth.randint("xcd/az", (6, 2), 512).cuda()
-    spk = synth.randint("xcd/as", (6,), 102).cuda()
-    voc.set_option("xcd", 1)
-    try:
+    z, spk = H.inputs("xcd/a?", 6, 2)
+    with H.options(voc, xcd=1) as set_option:
         a = voc.generate(z, spk, seed=2, utt_base=0, return_mulaw=True)
-        voc.set_option("xcd_agent_stores", 1)
-        b = voc.generate(z, spk, seed=2, utt_base=0, return_mulaw=True)
-        voc.check()
-        assert torch.equal(a[1], b[1]) and torch.equal(a[0], b[0])
-    finally:
-        voc.set_option("xcd_agent_stores", 0)
-        voc.set_option("xcd", -1)
+        set_option("xcd_agent_stores", 1)
+        b = H.decode(voc, z, spk, seed=2, utt_base=0)
+        H.assert_same_bits(a, b)
 
 
 def test_baseline_sizes_properties():
@@ -152,15 +104,6 @@ def test_baseline_sizes_properties():
 # ------------------------------------------------------------------ the error path of the in-kernel hand-offs
 
 
-def _reference_bits(z, spk, **kw):
-    ref, _ = vocoder(fresh=True)
-    ref.set_option("xcd", 0)
-    ref.set_option("fuse_fc2", 0)
-    wav, mu = ref.generate(z, spk, return_mulaw=True, **kw)
-    ref.check()
-    return wav.cpu(), mu.cpu()
-
-
 @pytest.mark.parametrize("B", [1, 12, 20])
 def test_xcd_handoff_timeout_is_reported_by_the_same_call_and_the_rerun_is_right(B):
     """One worker skips a candidate publish: every wait behind it gives up after the (shortened) deadline, check() raises
@@ -178,7 +121,7 @@ def test_xcd_handoff_timeout_is_reported_by_the_same_call_and_the_rerun_is_right
     voc.set_option("xcd_debug_drop_step", -1)
     wav2, mu2 = voc.generate(z, spk, seed=9, utt_base=0, return_mulaw=True)      # the handle has fallen back
     assert voc.last_path() == 0
-    want = _reference_bits(z, spk, seed=9, utt_base=0)
+    want = H.reference_bits(z, spk, seed=9, utt_base=0)
     assert torch.equal(mu2.cpu(), want[1]) and torch.equal(wav2.cpu(), want[0])
     # Vocoder.generate itself (the reference's call, convert.py:77) checks and repeats once: the drop-in caller gets the right bits
     voc3, _ = vocoder(fresh=True)
@@ -208,7 +151,7 @@ def test_fused_launch_handoff_timeout_is_reported_and_the_rerun_is_right():
     voc.set_option("handoff_debug_drop_step", -1)
     wav2, mu2 = voc.generate(z, spk, seed=9, utt_base=0, return_mulaw=True)
     voc.check()
-    want = _reference_bits(z, spk, seed=9, utt_base=0)
+    want = H.reference_bits(z, spk, seed=9, utt_base=0)
     assert torch.equal(mu2.cpu(), want[1]) and torch.equal(wav2.cpu(), want[0])
 
 
@@ -253,7 +196,7 @@ def test_placement_miss_writes_nothing_is_reported_and_is_not_latched(B):
     assert not bool(mu.any()) and not bool(wav.any())                 # nothing was written
     wav2, mu2 = voc.generate(z, spk, seed=9, utt_base=0, return_mulaw=True)     # the misplacement was one shot; nothing latched
     assert voc.last_path() == want_path
-    want = _reference_bits(z, spk, seed=9, utt_base=0)
+    want = H.reference_bits(z, spk, seed=9, utt_base=0)
     assert torch.equal(mu2.cpu(), want[1]) and torch.equal(wav2.cpu(), want[0])
     # the default call repeats on its own
     voc.set_option("xcd_debug_misplace", 1)
@@ -322,32 +265,14 @@ def test_32_x_32000_bit_equal_to_the_launch_path():
     voc, _ = vocoder()
     z = synth.randint("xcd/fz32", (32, 100), 512).cuda()
     spk = (torch.arange(32, device="cuda") % 102)
-    out = _both_paths(voc, z, spk, seed=13, utt_base=0)
-    assert out[1][1].shape == (32, 32000)
-    assert torch.equal(out[1][1], out[0][1]) and torch.equal(out[1][0], out[0][0])
+    resident, launch = _both_paths(voc, z, spk, seed=13, utt_base=0)
+    assert resident[1].shape == (32, 32000)
+    H.assert_same_bits(resident, launch)
 
 
 def test_2400_consecutive_steps_draw_by_draw_against_the_oracle():
     """A late-step divergence (tag wrap, conditioning-frame index, slot hand-over) cannot hide behind 400-step windows: 2 400
     consecutive steps (15 conditioning frames) of two utterances inside a batch of 9 on the per-XCD decoders, every draw
     checked against the C oracle on the same history."""
-    voc, sd = vocoder()
-    voc.set_option("xcd", 1)
-    try:
-        B, Tc, steps = 9, 8, 2400
-        z = synth.randint("xcd/lz", (B, Tc), 512)
-        spk = synth.randint("xcd/ls", (B,), 102)
-        wav, mu = voc.generate(z.cuda(), spk.cuda(), seed=21, utt_base=5, return_mulaw=True, max_steps=steps)
-        assert voc.last_path() == 2
-        mu = mu.cpu().numpy()
-        for b in (0, 8):
-            inputs = np.concatenate([[128], mu[b, :steps - 1]])
-            r = oracle.vocoder_generate(sd, z[b].numpy(), int(spk[b]), seed=21, utterance=5 + b, n_steps=steps, inputs=inputs,
-                                        want_logits=True)
-            diff = np.nonzero(r["samples"] != mu[b, :steps])[0]
-            assert len(diff) <= 0.001 * steps, (b, len(diff))
-            for t in diff:
-                pick, sc = oracle.sample_from_logits(r["logits"][t], 21, 5 + b, int(t))
-                assert sc[pick] - sc[int(mu[b, t])] <= 2e-5, (b, int(t))
-    finally:
-        voc.set_option("xcd", -1)
+    for b, (n, exact) in zip((0, 8), _draws_against_the_oracle(9, 8, 2400, "xcd/l?", seed=21, utt_base=5, rows=(0, 8))):
+        assert n - exact <= 0.001 * n, (b, n - exact)

@@ -11,119 +11,36 @@ import numpy as np
 import pytest
 import torch
 
-import vectorquantizedcpc_amd as V
-from vectorquantizedcpc_amd import _lib, synth
+import decode_harness as H
+from vectorquantizedcpc_amd import _lib
 
 pytestmark = pytest.mark.gpu
 TC, STEPS, SEED, UTT_BASE = 2, 320, 31, 5
-_cache = {}
-
-
-def _vocoder():
-    if "v" not in _cache:
-        v = V.Vocoder(V.ConfVocoder())
-        v.load_state_dict(synth.vocoder_state_dict())
-        _cache["v"] = v.to("cuda").eval()
-    return _cache["v"]
-
-
-def _inputs(B, ragged):
-    z = synth.randint(f"ah/z{B}", (B, TC), 512).cuda()
-    spk = synth.randint(f"ah/s{B}", (B,), 102).cuda()
-    n_codes = [1 + ((b * 5 + b // 8) % 3 != 0) for b in range(B)] if ragged else None
-    return z, spk, n_codes
-
-
-def _launch_path(B, ragged):
-    """The launch-per-step kernels' bits of a case, computed once."""
-    key = ("ref", B, ragged)
-    if key not in _cache:
-        voc = _vocoder()
-        z, spk, n_codes = _inputs(B, ragged)
-        voc.set_option("xcd", 0)
-        try:
-            wav, mu = voc.generate(z, spk, n_codes=n_codes, seed=SEED, utt_base=UTT_BASE, return_mulaw=True, max_steps=0 if ragged else STEPS)
-            voc.check()
-            assert voc.last_path() != 2
-        finally:
-            voc.set_option("xcd", -1)
-        _cache[key] = (wav.cpu(), mu.cpu())
-    return _cache[key]
-
-
-def _resident(B, ragged, **opts):
-    voc = _vocoder()
-    z, spk, n_codes = _inputs(B, ragged)
-    voc.set_option("xcd", 1)
-    for k, v in opts.items():
-        voc.set_option(k, v)
-    try:
-        wav, mu = voc.generate(z, spk, n_codes=n_codes, seed=SEED, utt_base=UTT_BASE, return_mulaw=True, max_steps=0 if ragged else STEPS,
-                               async_=True)
-        voc.check()                                        # no hand-off timed out
-        assert voc.last_path() == 2
-    finally:
-        voc.set_option("xcd", -1)
-    return wav.cpu(), mu.cpu(), n_codes
-
-
-def _assert_equal(got, want, B, n_codes):
-    assert torch.equal(got[1], want[1]) and torch.equal(got[0], want[0])
-    assert int((got[1] != 0).sum()) > 0.9 * 320 * sum(n_codes or [1] * B)
+CASES = H.CutCases(H.Handles(), "ah/?{B}", TC, STEPS, SEED, UTT_BASE)
 
 
 @pytest.mark.parametrize("B,ragged", [(1, False), (8, False), (9, False), (16, True), (17, False), (25, False), (31, False), (32, False)])
 def test_every_form_of_the_draw(B, ragged):
     """One slot per XCD (1, 8), two slots (9, 16 ragged), four slots with XCDs that run two or three of them (17, 25, 31), and all of
     them (32): a draw on one, two or four chain waves of a workgroup, fc1's joint stores with one to four live slots."""
-    wav, mu, n_codes = _resident(B, ragged)
-    _assert_equal((wav, mu), _launch_path(B, ragged), B, n_codes)
+    CASES.assert_equal(CASES.resident(B, ragged), B, ragged)
 
 
 def test_32_ragged():
-    wav, mu, n_codes = _resident(32, True)
-    _assert_equal((wav, mu), _launch_path(32, True), 32, n_codes)
-    for b, n in enumerate(n_codes):
-        assert not mu[b, 320 * n:].any()
+    CASES.assert_equal(CASES.resident(32, True), 32, True)
 
 
 def test_40_utterances_through_32_slots():
-    voc = _vocoder()
-    try:
-        wav, mu, n_codes = _resident(40, True, xcd_slots=32)
-    finally:
-        voc.set_option("xcd_slots", 32)
-    _assert_equal((wav, mu), _launch_path(40, True), 40, n_codes)
+    CASES.assert_equal(CASES.resident(40, True, xcd_slots=32), 40, True)
 
 
 def test_stream_of_two_chunks_equals_one_shot():
     """The resume kernels share fc1's epilogue and fc2_and_draw: one code frame in two chunks of 160 samples equals the one-shot call."""
-    voc = _vocoder()
-    z, spk, _ = _inputs(32, False)
-    z = z[:, :1].contiguous()
-    voc.set_option("xcd", 0)
-    want = [t.cpu() for t in voc.generate(z, spk, seed=SEED, utt_base=UTT_BASE, return_mulaw=True)]
-    voc.set_option("xcd", 1)
-    try:
-        chunks = []
-        for w, m in voc.generate_stream(z, spk, chunk_samples=160, seed=SEED, utt_base=UTT_BASE, return_mulaw=True):
-            assert voc.last_path() == 2
-            chunks.append((w.cpu(), m.cpu()))
-        voc.check()
-    finally:
-        voc.set_option("xcd", -1)
-    assert [c[0].shape[1] for c in chunks] == [160, 160]
-    assert want[1].shape[1] == 320 and int((want[1] != 0).sum()) > 0.9 * 320 * 32
-    assert torch.equal(torch.cat([c[1] for c in chunks], 1), want[1]) and torch.equal(torch.cat([c[0] for c in chunks], 1), want[0])
+    CASES.assert_stream_equals_one_shot(32, chunk=160)
 
 
 def test_agent_scope_stores_same_bits():
-    voc = _vocoder()
-    try:
-        wav, mu, n_codes = _resident(32, False, xcd_agent_stores=1)
-    finally:
-        voc.set_option("xcd_agent_stores", 0)
-    _assert_equal((wav, mu), _launch_path(32, False), 32, n_codes)
+    CASES.assert_equal(CASES.resident(32, False, xcd_agent_stores=1), 32, False)
 
 
 # ---- the draw helper alone

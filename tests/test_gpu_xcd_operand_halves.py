@@ -10,69 +10,32 @@ wave; ragged lengths end slots while their neighbours run on; 40 utterances thro
 that was live; the streamed case runs the resume kernel's priming step at every chunk.
 """
 import pytest
-import torch
 
-import vectorquantizedcpc_amd as V
-from vectorquantizedcpc_amd import synth
+import decode_harness as H
 
 pytestmark = pytest.mark.gpu
-FRAME = 320                     # samples per code frame
-_cache = {}
-
-
-def vocoder():
-    if "v" not in _cache:
-        v = V.Vocoder(V.ConfVocoder())
-        v.load_state_dict(synth.vocoder_state_dict())
-        _cache["v"] = v.to("cuda").eval()
-    return _cache["v"]
-
-
-def inputs(B, Tc, ragged):
-    z = synth.randint(f"halves/z{B}", (B, Tc), 512).cuda()
-    spk = synth.randint(f"halves/s{B}", (B,), 102).cuda()
-    n_codes = [1 + (7 * b) % Tc for b in range(B)] if ragged else None
-    return z, spk, n_codes
+vocoder = H.Handles()
 
 
 @pytest.mark.parametrize("ragged", [False, True])
 @pytest.mark.parametrize("B", [17, 25, 32, 40])
 def test_same_bits_as_the_launch_path(B, ragged):
-    voc = vocoder()
+    voc, _ = vocoder()
     Tc = 3
-    z, spk, n_codes = inputs(B, Tc, ragged)
-    out = {}
-    try:
-        voc.set_option("xcd_slots", 32)
-        for mode in (1, 0):
-            voc.set_option("xcd", mode)
-            wav, mu = voc.generate(z, spk, n_codes=n_codes, return_mulaw=True, seed=13, utt_base=3)
-            voc.check()
-            assert voc.last_path() == (2 if mode else 0)
-            if mode:
-                assert voc.last_slots() == min(B, 32)          # 17..32 slots: four per XCD, ar_xcd_kernel<4>
-            out[mode] = (wav.cpu(), mu.cpu())
-    finally:
-        voc.set_option("xcd_slots", 32)                  # the default (the option takes 1..32)
-        voc.set_option("xcd", -1)
-    assert torch.equal(out[1][1], out[0][1]) and torch.equal(out[1][0], out[0][0])
-    assert int((out[1][1] != 0).sum()) > 0.9 * FRAME * sum(n_codes or [Tc] * B)
+    z, spk = H.inputs(f"halves/?{B}", B, Tc)
+    n_codes = H.ragged_sevens(B, Tc) if ragged else None
+    # 17..32 slots: four per XCD, ar_xcd_kernel<4>
+    resident, launch = H.path_pair(voc, z, spk, {"xcd_slots": 32, "xcd": 1}, {"xcd": 0}, path=2, slots=min(B, 32), n_codes=n_codes,
+                                   seed=13, utt_base=3)
+    H.assert_same_bits(resident, launch)
+    H.assert_live(resident[1], n_codes or [Tc] * B)
 
 
 def test_streamed_in_chunks_of_one_frame_same_bits_as_one_call():
-    voc = vocoder()
+    voc, _ = vocoder()
     B, Tc = 20, 4
-    z, spk, _ = inputs(B, Tc, False)
-    want_w, want_m = voc.generate(z, spk, return_mulaw=True, seed=17, utt_base=5)
-    voc.check()
-    assert voc.last_path() == 2
-    ws, ms = [], []
-    for w, m in voc.generate_stream(z, spk, chunk_samples=FRAME, return_mulaw=True, seed=17, utt_base=5):
-        assert voc.last_path() == 2 and 17 <= voc.last_slots() <= 32      # ar_xcd_resume_kernel<4>
-        ws.append(w)
-        ms.append(m)
-    assert len(ws) == Tc
-    got_w, got_m = torch.cat(ws, 1), torch.cat(ms, 1)
-    assert got_w.shape == want_w.shape
-    assert torch.equal(got_m, want_m) and torch.equal(got_w, want_w)
-    assert int((got_m != 0).sum()) > 0.9 * FRAME * Tc * B
+    z, spk = H.inputs(f"halves/?{B}", B, Tc)
+    want = H.decode(voc, z, spk, path=2, seed=17, utt_base=5)
+    got = H.streamed(voc, z, spk, H.FRAME, path=2, slots=(17, 32), chunks=Tc, seed=17, utt_base=5)      # ar_xcd_resume_kernel<4>
+    H.assert_same_bits(got, want)
+    H.assert_live(got[1], [Tc] * B)

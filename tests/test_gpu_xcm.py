@@ -7,83 +7,45 @@ test_gpu_vocoder.py checks against the oracles on their own; (2) draw by draw ag
 single-GPU form (256 x 32 000 through 128 slots): an utterance alone equals itself in the batch, fewer slots give the same
 samples; (4) the abort path of its in-kernel hand-offs.
 """
-import numpy as np
 import pytest
 import torch
 
+import decode_harness as H
 import oracle
-import vectorquantizedcpc_amd as V
-from vectorquantizedcpc_amd import driver, synth
+from vectorquantizedcpc_amd import synth
 
 pytestmark = pytest.mark.gpu
-_cache = {}
-
-
-def vocoder(fresh=False):
-    if fresh or "v" not in _cache:
-        sd = synth.vocoder_state_dict()
-        v = V.Vocoder(V.ConfVocoder())
-        v.load_state_dict(sd)
-        v = v.to("cuda").eval()
-        if fresh:
-            return v, sd
-        _cache["v"] = (v, sd)
-    return _cache["v"]
+vocoder = H.Handles()
 
 
 def _both_paths(voc, z, spk, **kw):
-    out = {}
-    for name, (xcd, xcm) in (("xcm", (-1, 1)), ("launch", (0, 0))):
-        voc.set_option("xcd", xcd)
-        voc.set_option("xcm", xcm)
-        wav, mu = voc.generate(z, spk, return_mulaw=True, **kw)
-        voc.check()
-        assert voc.last_path() == (3 if name == "xcm" else voc.last_path())
-        out[name] = (wav.cpu(), mu.cpu())
-    voc.set_option("xcd", -1)
-    voc.set_option("xcm", -1)
-    return out
+    return H.path_pair(voc, z, spk, {"xcd": -1, "xcm": 1}, {"xcd": 0, "xcm": 0}, path=3, **kw)
 
 
 @pytest.mark.parametrize("B,Tc,ragged", [(1, 2, False), (7, 3, True), (16, 2, False), (17, 3, True), (40, 2, True), (128, 2, False),
                                          (150, 3, True)])
 def test_same_samples_as_the_launch_path(B, Tc, ragged):
     voc, _ = vocoder()
-    z = synth.randint(f"xcm/z{B}", (B, Tc), 512).cuda()
-    spk = synth.randint(f"xcm/s{B}", (B,), 102).cuda()
-    n_codes = [max(1, Tc - (b % Tc)) for b in range(B)] if ragged else None
-    out = _both_paths(voc, z, spk, n_codes=n_codes, seed=13, utt_base=3)
-    assert torch.equal(out["xcm"][1], out["launch"][1]) and torch.equal(out["xcm"][0], out["launch"][0])
-    assert int((out["xcm"][1] != 0).sum()) > 0.9 * 320 * sum(n_codes or [Tc] * B)
+    z, spk = H.inputs(f"xcm/?{B}", B, Tc)
+    n_codes = H.ragged_countdown(B, Tc) if ragged else None
+    xcm, launch = _both_paths(voc, z, spk, n_codes=n_codes, seed=13, utt_base=3)
+    H.assert_same_bits(xcm, launch)
+    H.assert_live(xcm[1], n_codes or [Tc] * B)
+
+
+def _draws_against_the_oracle(B, Tc, steps, tag, seed, utt_base, rows):
+    """(steps, exact draws) of ``rows`` of one call on the matrix-core decoders, every draw and the waveform judged by the C oracle."""
+    voc, sd = vocoder()
+    z, spk = H.inputs(tag, B, Tc, device="cpu")
+    with H.options(voc, xcm=1):
+        wav, mu = H.decode(voc, z.cuda(), spk.cuda(), path=3, seed=seed, utt_base=utt_base, max_steps=steps)
+    return oracle.judge_draws(sd, z, spk, mu, seed=seed, utt_ids=range(utt_base, utt_base + B), rows=rows, steps=steps, wav=wav)
 
 
 def test_draw_by_draw_against_the_oracle():
-    voc, sd = vocoder()
-    voc.set_option("xcm", 1)
-    try:
-        B, Tc, steps = 19, 2, 400
-        z = synth.randint("xcm/oz", (B, Tc), 512)
-        spk = synth.randint("xcm/os", (B,), 102)
-        wav, mu = voc.generate(z.cuda(), spk.cuda(), seed=13, utt_base=11, return_mulaw=True, max_steps=steps)
-        voc.check()
-        assert voc.last_path() == 3
-        wav, mu = wav.cpu().numpy(), mu.cpu().numpy()
-        exact = total = 0
-        for b in (0, 7, 16, 18):            # slots on XCDs 0, 7, 0 (second local slot), 2
-            s_gpu = mu[b, :steps]
-            inputs = np.concatenate([[128], s_gpu[:-1]])
-            r = oracle.vocoder_generate(sd, z[b].numpy(), int(spk[b]), seed=13, utterance=11 + b, n_steps=steps, inputs=inputs,
-                                        want_logits=True)
-            for t in np.nonzero(r["samples"] != s_gpu)[0]:
-                pick, sc = oracle.sample_from_logits(r["logits"][t], 13, 11 + b, int(t))
-                assert sc[pick] - sc[int(s_gpu[t])] <= 2e-5, (b, int(t))
-            exact += int((r["samples"] == s_gpu).sum())
-            total += steps
-            assert np.array_equal(wav[b, :steps], np.array([oracle.mulaw_decode(int(s)) for s in s_gpu], np.float32))
-            assert not wav[b, steps:].any()
-        assert exact >= 0.999 * total
-    finally:
-        voc.set_option("xcm", -1)
+    # rows: slots on XCDs 0, 7, 0 (second local slot), 2
+    stats = _draws_against_the_oracle(19, 2, 400, "xcm/o?", seed=13, utt_base=11, rows=(0, 7, 16, 18))
+    assert sum(e for _, e in stats) >= 0.999 * sum(n for n, _ in stats)
 
 
 def test_more_utterances_than_slots_and_alone_equals_in_batch():
@@ -91,29 +53,21 @@ def test_more_utterances_than_slots_and_alone_equals_in_batch():
     equals the same utterance decoded alone (its sampling stream does not depend on the placement)."""
     voc, _ = vocoder()
     n, Tc = 200, 3
-    z = synth.randint("xcm/cz", (n, Tc), 512).cuda()
-    spk = synth.randint("xcm/cs", (n,), 102).cuda()
-    n_codes = [1 + (7 * i) % Tc for i in range(n)]
+    z, spk = H.inputs("xcm/c?", n, Tc)
+    n_codes = H.ragged_sevens(n, Tc)
     ids = list(range(100, 100 + n))
-    voc.set_option("xcm", 1)
-    try:
+    with H.options(voc, xcm=1) as set_option:
         res = {}
         for slots in (128, 24):
-            voc.set_option("xcm_slots", slots)
-            wav, mu = voc.generate(z, spk, n_codes=n_codes, seed=5, utt_ids=ids, return_mulaw=True)
-            voc.check()
-            assert voc.last_path() == 3
-            res[slots] = (wav.cpu(), mu.cpu())
-        assert torch.equal(res[128][1], res[24][1]) and torch.equal(res[128][0], res[24][0])
-        voc.set_option("xcm", 0)
+            set_option("xcm_slots", slots)
+            res[slots] = H.decode(voc, z, spk, path=3, n_codes=n_codes, seed=5, utt_ids=ids)
+        H.assert_same_bits(res[128], res[24])
+        set_option("xcm", 0)
         for i in (0, 77, 199):
             w1, m1 = voc.generate(z[i:i + 1, :n_codes[i]], spk[i:i + 1], seed=5, utt_ids=[ids[i]], return_mulaw=True)
-            L = 320 * n_codes[i]
+            L = H.FRAME * n_codes[i]
             assert torch.equal(m1[0].cpu(), res[128][1][i, :L]) and torch.equal(w1[0].cpu(), res[128][0][i, :L])
             assert not res[128][1][i, L:].any()
-    finally:
-        voc.set_option("xcm_slots", 128)
-        voc.set_option("xcm", -1)
 
 
 def test_path_by_utterances_in_flight():
@@ -125,14 +79,11 @@ def test_path_by_utterances_in_flight():
         voc.generate(z, spk, seed=1, max_steps=8)
         voc.check()
         assert voc.last_path() == want, (B, voc.last_path())
-    voc.set_option("slots", 100)                 # 600 utterances through 100 decode slots: 100 in flight
-    try:
+    with H.options(voc, slots=100):              # 600 utterances through 100 decode slots: 100 in flight
         z = synth.randint("xcm/pz600", (600, 1), 512).cuda()
         voc.generate(z, torch.zeros(600, dtype=torch.long, device="cuda"), seed=1, max_steps=8)
         voc.check()
         assert voc.last_path() == 3
-    finally:
-        voc.set_option("slots", 0)
 
 
 def test_configs3_single_gpu_form_properties():
@@ -155,15 +106,6 @@ def test_configs3_single_gpu_form_properties():
         assert torch.equal(m1[0], mu[i]) and torch.equal(w1[0], wav[i])
 
 
-def _reference_bits(z, spk, **kw):
-    ref, _ = vocoder(fresh=True)
-    ref.set_option("xcd", 0)
-    ref.set_option("fuse_fc2", 0)
-    wav, mu = ref.generate(z, spk, return_mulaw=True, **kw)
-    ref.check()
-    return wav.cpu(), mu.cpu()
-
-
 def test_handoff_timeout_is_reported_by_the_same_call_and_the_rerun_is_right():
     """One worker skips a candidate publish: every wait behind it gives up after the (shortened) deadline, check() raises for
     THAT call, the handle falls back to launches, and the repeated call gives the samples of the undisturbed paths."""
@@ -182,7 +124,7 @@ def test_handoff_timeout_is_reported_by_the_same_call_and_the_rerun_is_right():
     wav2, mu2 = voc.generate(z, spk, seed=9, utt_base=0, return_mulaw=True)      # the handle has fallen back
     voc.check()
     assert voc.last_path() == 0
-    want = _reference_bits(z, spk, seed=9, utt_base=0)
+    want = H.reference_bits(z, spk, seed=9, utt_base=0)
     assert torch.equal(mu2.cpu(), want[1]) and torch.equal(wav2.cpu(), want[0])
     voc3, _ = vocoder(fresh=True)
     voc3.set_option("xcm", 1)
@@ -199,38 +141,12 @@ def test_128_x_32000_bit_equal_to_the_launch_path():
     voc, _ = vocoder()
     z = synth.randint("xcm/fz128", (128, 100), 512).cuda()
     spk = (torch.arange(128, device="cuda") % 102)
-    out = {}
-    for name, (xcd, xcm) in {"xcm": (-1, 1), "launch": (0, 0)}.items():
-        voc.set_option("xcd", xcd)
-        voc.set_option("xcm", xcm)
-        wav, mu = voc.generate(z, spk, seed=13, utt_base=0, return_mulaw=True)
-        assert voc.last_path() == (3 if name == "xcm" else 0)
-        out[name] = (wav.cpu(), mu.cpu())
-    voc.set_option("xcd", -1)
-    voc.set_option("xcm", -1)
-    assert torch.equal(out["xcm"][1], out["launch"][1]) and torch.equal(out["xcm"][0], out["launch"][0])
+    xcm, launch = _both_paths(voc, z, spk, seed=13, utt_base=0)
+    H.assert_same_bits(xcm, launch)
 
 
 def test_2400_consecutive_steps_draw_by_draw_against_the_oracle():
     """2 400 consecutive steps of two utterances inside a batch of 80 on the matrix-core decoders, every draw checked against
     the C oracle on the same history (a late-step divergence cannot hide behind 400-step windows)."""
-    voc, sd = vocoder()
-    voc.set_option("xcm", 1)
-    try:
-        B, Tc, steps = 80, 8, 2400
-        z = synth.randint("xcm/lz", (B, Tc), 512)
-        spk = synth.randint("xcm/ls", (B,), 102)
-        wav, mu = voc.generate(z.cuda(), spk.cuda(), seed=21, utt_base=5, return_mulaw=True, max_steps=steps)
-        assert voc.last_path() == 3
-        mu = mu.cpu().numpy()
-        for b in (0, 79):
-            inputs = np.concatenate([[128], mu[b, :steps - 1]])
-            r = oracle.vocoder_generate(sd, z[b].numpy(), int(spk[b]), seed=21, utterance=5 + b, n_steps=steps, inputs=inputs,
-                                        want_logits=True)
-            diff = np.nonzero(r["samples"] != mu[b, :steps])[0]
-            assert len(diff) <= 0.001 * steps, (b, len(diff))
-            for t in diff:
-                pick, sc = oracle.sample_from_logits(r["logits"][t], 21, 5 + b, int(t))
-                assert sc[pick] - sc[int(mu[b, t])] <= 2e-5, (b, int(t))
-    finally:
-        voc.set_option("xcm", -1)
+    for b, (n, exact) in zip((0, 79), _draws_against_the_oracle(80, 8, 2400, "xcm/l?", seed=21, utt_base=5, rows=(0, 79))):
+        assert n - exact <= 0.001 * n, (b, n - exact)
