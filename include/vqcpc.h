@@ -164,7 +164,8 @@ int vqcpc_encoder_vq_adapt(vqcpc_encoder *enc, const float *x, int n_rows, doubl
                            float *z_st, int64_t *idx, float *loss, float *perplexity, void *stream);
 
 /* Device memory the handle's grow-only work buffers hold at the moment (front-end activations, statistics, the work space
- * of vqcpc_encoder_vq_adapt and of vqcpc_encoder_context_fwd / _bwd: the peak of the calls so far; the weights are not counted). */
+ * of vqcpc_encoder_vq_adapt, of vqcpc_encoder_context_fwd / _bwd and of the front-end gradients of vqcpc_grad.h: the peak of the
+ * calls so far; the weights are not counted). */
 int vqcpc_encoder_workspace_bytes(vqcpc_encoder *enc, uint64_t *bytes);
 
 /* After the caller has synchronised the stream that carried vqcpc_encoder_encode / _context: did the resident context

@@ -1,0 +1,170 @@
+"""CPU side of the front-end gradients: the pins hold the float64 reference, two fp32 numpy restatements (the kernels' documented
+orders, and other orders) pass the judge of tests/front_grad_ref.py, five seeded faults do not, the second header is plain C99 and
+its symbols are exported and bound, and ``fit_encoder`` / ``cli fit-encoder`` check their arguments before any GPU is needed."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import front_grad_ref as R
+from vectorquantizedcpc_amd import _lib, cli, driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SMALL = [n for n in R.SMALL_CASES if not n.endswith(("_m1", "_m2"))]
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES + [R.CHAIN])
+def test_pins_hold_the_float64_reference(name):
+    ref, p = R.grads64(name), R.pins()
+    for k, G in ref.items():
+        if k == "differ":
+            assert int(p[f"{name}_differ"]) == G
+            continue
+        want = p[f"{name}_{k}_samples"]
+        got = G.reshape(-1)[R.sample_positions(name, k, G.size)]
+        scale = max(float(p[f"{name}_{k}_max"]), 1e-300)
+        assert np.abs(got - want).max() <= 1e-12 * scale, (name, k)
+        sums = np.array([G.sum(), (G ** 2).sum()])
+        assert np.abs(sums - p[f"{name}_{k}_sums"]).max() <= 1e-12 * max(1.0, np.abs(p[f"{name}_{k}_sums"]).max()) * G.size ** 0.5, (name, k)
+        assert abs(np.abs(G).max() - float(p[f"{name}_{k}_max"])) <= 1e-12 * scale
+
+
+def test_masks_of_the_small_cases_are_the_float64_run_s_own():
+    # where they are, forcing the masks changes nothing: the reference is plain autograd on the reference's modules
+    for name in ("partial_tile", "one_tile"):
+        print(name, int(R.pins()[f"{name}_differ"]))
+        assert int(R.pins()[f"{name}_differ"]) == 0
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_kernel_order_restatement_passes_the_judge(name):
+    R.judge(name, R.kernel_order32(name), "kernel order")
+
+
+@pytest.mark.parametrize("name", SMALL + ["slab_plus_one"])
+def test_reordered_restatement_passes_the_judge(name):
+    R.judge(name, R.reordered32(name), "other orders")
+
+
+@pytest.mark.parametrize("fault,name", [("mask_from_pre", "partial_tile"), ("drop_means", "partial_tile"),
+                                        ("pad_rows_counted", "partial_tile"), ("conv_edge", "partial_tile"),
+                                        ("skip_short_slab", "slab_plus_one")])
+def test_the_judge_notices_a_seeded_fault(fault, name):
+    assert fault in R.FAULTS
+    with pytest.raises(AssertionError):
+        R.judge(name, R.reordered32(name, fault), fault)
+
+
+def test_dead_units_have_exactly_zero_affine_gradients():
+    ref = R.grads64("dead_units")
+    dead = ~R.masks("dead_units")[R.DEAD_LN].any(axis=0)
+    assert dead.sum() > 0                                            # columns no row ever activates
+    for k in (f"ln_g{R.DEAD_LN}", f"ln_b{R.DEAD_LN}"):
+        assert not ref[k][dead].any()
+        for got in (R.kernel_order32("dead_units"), R.reordered32("dead_units")):
+            assert not got[k][dead].view(np.uint32).any(), k         # +0
+
+
+def test_vq_bwd_formula_is_the_autograd_of_the_reference_lines():
+    x = torch.from_numpy(np.random.default_rng(0).standard_normal((7, 64))).requires_grad_(True)
+    q = torch.from_numpy(np.random.default_rng(1).standard_normal((7, 64)))
+    gs = torch.from_numpy(np.random.default_rng(2).standard_normal((7, 64)))
+    loss = 0.25 * torch.nn.functional.mse_loss(x, q.detach())        # model.py:147-148
+    z_st = x + (q - x).detach()                                      # model.py:150
+    ((z_st * gs).sum() + 3.0 * loss).backward()
+    want = R.vq_bwd64(x.detach().numpy(), q.numpy(), gs.numpy(), 3.0)
+    assert np.abs(x.grad.numpy() - want).max() <= 1e-14
+
+
+# ------------------------------------------------------------------ the header
+def declared():
+    text = open(os.path.join(ROOT, "include", "vqcpc_grad.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(vqcpc_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_every_declared_symbol_is_exported_and_bound():
+    """``_lib.SYMBOLS`` is pinned to include/vqcpc.h by tests/test_abi_cpu.py; the second header's list is ``_lib.GRAD_SYMBOLS``."""
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    names = declared()
+    assert len(names) == 4
+    for n in names:
+        assert hasattr(lib, n), f"{n} declared in include/vqcpc_grad.h but not exported"
+        assert getattr(_lib.load(), n).argtypes is not None, n
+    assert sorted(_lib.GRAD_SYMBOLS) == names
+    assert not set(_lib.GRAD_SYMBOLS) & set(_lib.SYMBOLS)
+
+
+def test_header_is_plain_c(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('''#include "vqcpc_grad.h"
+#include <stddef.h>
+int use(vqcpc_encoder *enc, float *p, void *saved, void *s) {
+    vqcpc_encoder_front_weights w;
+    vqcpc_encoder_front_grads g;
+    uint64_t n = 0;
+    int rc = vqcpc_encoder_front_saved_bytes(enc, 1, 32, &n);
+    w.conv_weight = p; g.conv_weight = p; w.ln_weight[4] = p; g.ln_bias[0] = NULL;
+    rc |= vqcpc_encoder_front_fwd(enc, p, 1, 32, VQCPC_CONV_AUTO, &w, p, saved, s);
+    rc |= vqcpc_encoder_front_fwd(enc, p, 1, 32, VQCPC_CONV_AUTO, NULL, p, saved, s);
+    rc |= vqcpc_encoder_front_bwd(enc, p, 1, 32, VQCPC_CONV_AUTO, &w, saved, p, &g, s);
+    rc |= vqcpc_encoder_vq_bwd(enc, p, p, 16, p, NULL, p, s);
+    return rc;
+}
+''')
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only",
+                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_front_tensors_struct_mirrors_the_header():
+    fields = [n for n, _ in _lib.EncoderFrontTensors._fields_]
+    assert fields == ["conv_weight", "ln_weight", "ln_bias", "fc_weight", "out_weight", "out_bias"]
+    assert ctypes.sizeof(_lib.EncoderFrontTensors) == 17 * ctypes.sizeof(ctypes.c_void_p)
+
+
+# ------------------------------------------------------------------ argument checks that need no GPU
+def test_fit_encoder_checks_train_before_anything_else():
+    for bad in ((), ("front", "front"), ("front", "codebook"), ("all",)):
+        with pytest.raises(ValueError, match="fit_encoder: train"):
+            driver.fit_encoder(None, None, {}, train=bad)
+    assert driver.FIT_ENCODER_PARTS == ("front", "rnn", "predictors")
+
+
+def test_cli_fit_encoder_parses(capsys):
+    with pytest.raises(SystemExit) as e:
+        cli.main(["fit-encoder", "--help"])
+    assert e.value.code == 0
+    text = capsys.readouterr().out
+    assert "--train" in text and "--freeze-codebook" in text and "--out-checkpoint" in text
+    for bad in ("front,foo", "", "rnn,rnn"):
+        with pytest.raises(SystemExit) as e:
+            cli.main(["fit-encoder", "--dataset", "x", "--random-init", "--out-checkpoint", "y", "--train", bad])
+        assert e.value.code == 2
+    assert "fit-encoder --train" in capsys.readouterr().err
+    with pytest.raises(SystemExit) as e:                             # a checkpoint or --random-init, as every command
+        cli.main(["fit-encoder", "--dataset", "x", "--out-checkpoint", "y"])
+    assert e.value.code == 2
+
+
+def test_front_end_has_no_cpu_fallback():
+    import vectorquantizedcpc_amd as V
+    enc = V.Encoder(V.ConfEncoder(80, 512, 512, 64, 256))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        enc.front_end(torch.zeros(1, 80, 32), differentiable=True)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        enc.quantize(torch.zeros(1, 16, 64))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        enc.forward_differentiable(torch.zeros(1, 80, 32))
+
+
+def test_the_fit_s_reference_falls_and_both_precisions_pick_the_same_codes():
+    losses, idx64, _, m64 = R.chain_sgd(torch.float64, R.FIT_STEPS, R.FIT_LR)
+    _, idx32, _, m32 = R.chain_sgd(torch.float32, R.FIT_STEPS, R.FIT_LR)
+    assert all(a > b for a, b in zip(losses, losses[1:])), losses
+    assert all(np.array_equal(a, b) for a, b in zip(idx64, idx32))
+    assert abs(min(m64, m32) - float(R.pins()["chain_fit_vq_margin"])) <= 1e-6

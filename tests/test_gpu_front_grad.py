@@ -1,0 +1,458 @@
+"""-m gpu: the front end's gradients (``csrc/front_grad.hip``, ``include/vqcpc_grad.h``) -- the forward's bits against
+``vqcpc_encoder_stage``, the 17 gradients against float64 on the cases of tests/front_grad_ref.py, their repeatability on a dirty
+work space, partial requests, ``vqcpc_encoder_vq_bwd``, the autograd surface of ``Encoder.front_end`` / ``quantize``, the whole
+training step with ``CPCLoss``, the ABI's errors and ``cli fit-encoder``.
+
+Cases, reference and judge: tests/front_grad_ref.py (``judge`` prints every figure, then asserts); tests/test_front_grad_cpu.py holds
+two fp32 restatements to the same judge on the CPU.  Nothing here is measured on the code under test.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import front_grad_ref as R
+import vectorquantizedcpc_amd as V
+from vectorquantizedcpc_amd import _lib, synth
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def release_what_this_file_holds():
+    """The cases, the float64 references and the device buffers of this file are released when it is done, so that the files that
+    run after it find the process -- its heap and torch's caching allocator -- as they would without it."""
+    yield
+    import gc
+    R._cases.clear()
+    R._fwd.clear()
+    R._refs.clear()
+    _state.clear()
+    gc.collect()
+    torch.cuda.empty_cache()
+
+_state = {}
+TOP_TWO = ("fc3", "ln_g4", "ln_b4", "out_w", "out_b")            # the top two Linear layers and the LayerNorm between them
+
+
+def bits(t):
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+def encoder(C=80, w=None):
+    """A fresh Encoder with in_channels = C on the GPU (seeded weights), its front end set to ``w`` (dict by ``R.KEYS``) if given."""
+    if C not in _state:
+        _state[C] = synth.encoder_state_dict(in_channels=C, ln_affine="random", codebook="data")
+    enc = V.Encoder(V.ConfEncoder(C, 512, 512, 64, 256))
+    sd = dict(_state[C])
+    if w is not None:
+        sd.update(dict(zip(R.SD_NAMES, (w[k] for k in R.KEYS))))
+    enc.load_state_dict(sd)
+    return enc.cuda().eval()
+
+
+def on_gpu(g):
+    return g["mel"].cuda(), [g["w"][k].cuda().contiguous() for k in R.KEYS]
+
+
+def run(enc, g, mel, ws, G, want=None):
+    """fwd + bwd with the caller's weights -> dict by ``R.KEYS`` (device tensors or None) and ``z_pre``."""
+    want = tuple(want is None or k in want for k in R.KEYS)
+    z_pre, saved = enc._front_fwd(mel, ws, g["mode"])
+    grads = enc._front_bwd(mel, saved, G, ws, want, g["mode"])
+    return dict(zip(R.KEYS, grads), z_pre=z_pre)
+
+
+def numpy_of(r):
+    return {k: (None if v is None else v.cpu().numpy()) for k, v in r.items() if k != "z_pre"}
+
+
+# ------------------------------------------------------------------ 1. the forward is vqcpc_encoder_stage's
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_forward_bits_equal_the_stage_entry(name):
+    g = R.load(name)
+    enc = encoder(g["C"], g["w"])
+    mel, ws = on_gpu(g)
+    forced = R.masks(name)
+    for l, s in enumerate((1, 3, 5, 7, 9)):                          # first: a mask mismatch is reported as what it is
+        got = (enc.stage(mel, s, g["mode"]) > 0).cpu().numpy().reshape(g["R"], 512)
+        assert np.array_equal(got, forced[l]), f"{name}: ReLU mask {l} differs from the oracle's in {(got != forced[l]).sum()} elements"
+    want = enc.stage(mel, 10, g["mode"])
+    mine, saved = enc._front_fwd(mel, ws, g["mode"])                 # the caller's pointers
+    own, saved_own = enc._front_fwd(mel, None, g["mode"])            # NULL: the handle's copies
+    assert torch.equal(bits(mine), bits(want)) and torch.equal(bits(own), bits(want))
+    assert torch.equal(bits(saved), bits(saved_own))
+    n = g["R"] * 512
+    for l, s in enumerate((0, 2, 4, 6, 8)):                          # saved: the rows entering each LayerNorm and leaving each ReLU
+        assert torch.equal(bits(saved[l * n:(l + 1) * n]), bits(enc.stage(mel, s, g["mode"]))), l
+        assert torch.equal(bits(saved[(5 + l) * n:(6 + l) * n]), bits(enc.stage(mel, s + 1, g["mode"]))), l
+
+
+# ------------------------------------------------------------------ 2. against float64
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_gradients_against_float64(name):
+    g = R.load(name)
+    enc = encoder(g["C"])
+    mel, ws = on_gpu(g)
+    R.judge(name, numpy_of(run(enc, g, mel, ws, g["G"].cuda())), "GPU")
+
+
+# ------------------------------------------------------------------ 3. equal inputs, equal bits, on a work space that is dirty
+def test_repeatable_on_a_dirty_work_space():
+    small, large = R.load("partial_tile"), R.load("slab_plus_one")
+    mel, ws = on_gpu(small)
+    mel_l, ws_l = on_gpu(large)
+    G, Gl = small["G"].cuda(), large["G"].cuda()
+    first = run(encoder(), small, mel, ws, G)                        # a fresh handle
+    enc = encoder()
+    run(enc, small, mel, ws, G)
+    before = enc.workspace_bytes()
+    run(enc, large, mel_l, ws_l, Gl)                                 # a larger call: the work space grows and is left full of it
+    assert enc.workspace_bytes() > before
+    second = run(enc, small, mel, ws, G)
+    run(enc, large, mel_l, ws_l, Gl * float("nan"))                  # NaN through every gradient buffer and partial
+    third = run(enc, small, mel, ws, G)
+    for k in R.KEYS + ["z_pre"]:
+        assert torch.equal(bits(first[k]), bits(second[k])) and torch.equal(bits(first[k]), bits(third[k])), k
+        assert torch.isfinite(third[k]).all(), k
+
+
+# ------------------------------------------------------------------ 4. partial requests
+def test_partial_requests_and_exact_zeros():
+    g = R.load("partial_tile")
+    mel, ws = on_gpu(g)
+    G = g["G"].cuda()
+    full = run(encoder(), g, mel, ws, G)
+    enc = encoder()
+    top = run(enc, g, mel, ws, G, TOP_TWO)
+    assert all(top[k] is None for k in R.KEYS if k not in TOP_TWO)
+    for k in TOP_TWO:
+        assert torch.equal(bits(top[k]), bits(full[k])), k
+    # the chain stops at the lowest wanted tensor: out_w and out_b alone need no (R, 512) gradient buffer at all
+    enc_top = encoder()
+    only = run(enc_top, g, mel, ws, G, ("out_w", "out_b"))
+    assert torch.equal(bits(only["out_w"]), bits(full["out_w"])) and torch.equal(bits(only["out_b"]), bits(full["out_b"]))
+    assert enc_top.workspace_bytes() + 2 * g["R"] * 512 * 4 <= enc.workspace_bytes()
+    for k in ("conv", "ln_g0", "fc1", "ln_b3"):                      # one tensor alone, from every depth
+        alone = run(encoder(), g, mel, ws, G, (k,))
+        assert torch.equal(bits(alone[k]), bits(full[k])), k
+
+    # unrequested outputs are untouched: all 17 canary-filled, only TOP_TWO handed over
+    z_pre, saved = enc._front_fwd(mel, ws)
+    outs = [torch.full_like(w, -7.0) for w in ws]
+    asked = [o if k in TOP_TWO else None for k, o in zip(R.KEYS, outs)]
+    h = enc._sizes_handle(mel.device)
+    _lib.check(_lib.load().vqcpc_encoder_front_bwd(h, mel.data_ptr(), g["B"], g["T"], 0, ctypes.byref(enc._front_struct(ws)), saved.data_ptr(),
+                                                   G.data_ptr(), ctypes.byref(enc._front_struct(asked)), _lib.current_stream()))
+    for k, o in zip(R.KEYS, outs):
+        if k in TOP_TWO:
+            assert torch.equal(bits(o), bits(full[k])), k
+        else:
+            assert bool((o == -7.0).all()), k
+
+    zero = R.load("zero_upstream")
+    mel0, ws0 = on_gpu(zero)
+    r = run(encoder(), zero, mel0, ws0, zero["G"].cuda())
+    for k in R.KEYS:
+        assert bits(r[k]).eq(0).all(), k                             # +0, not -0
+
+
+# ------------------------------------------------------------------ 5. vq_bwd
+def vq_bwd(enc, z_pre, z_q, gs, gl):
+    out = torch.full_like(z_pre, float("nan"))
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(_lib.load().vqcpc_encoder_vq_bwd(enc._native(), z_pre.data_ptr(), z_q.data_ptr(), z_pre.numel() // 64, ptr(gs), ptr(gl),
+                                                out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+@pytest.mark.parametrize("rows", [1, 63, 1025])
+def test_vq_bwd_against_its_float64_formula(rows):
+    enc = encoder()
+    z_pre, z_q, gs = (R._u(f"vq_bwd/{rows}/{n}", (rows, 64), 1.5) for n in ("z_pre", "z_q", "gs"))
+    gl = R._u(f"vq_bwd/{rows}/gl", (1,), 2.0)
+    # the reference's own fp32: autograd through model.py:147-150 in torch fp32 on the CPU
+    x = z_pre.clone().requires_grad_(True)
+    ((x + (z_q - x).detach()) * gs).sum().backward(retain_graph=False)
+    (0.25 * torch.nn.functional.mse_loss(x, z_q)).backward(gl[0])
+    both64 = R.vq_bwd64(z_pre.numpy(), z_q.numpy(), gs.numpy(), gl[0].item())
+    e_ref = float(np.abs(x.grad.numpy().astype(np.float64) - both64).max())
+    dev = [t.cuda() for t in (z_pre, z_q, gs, gl)]
+    for what, a, b, want in (("both", dev[2], dev[3], both64), ("loss only", None, dev[3], R.vq_bwd64(z_pre.numpy(), z_q.numpy(), None, gl[0].item()))):
+        got = vq_bwd(enc, dev[0], dev[1], a, b).cpu().numpy().astype(np.float64)
+        err, allowed = float(np.abs(got - want).max()), 4.0 * max(e_ref, R.U32 * float(np.abs(want).max()))
+        print(f"vq_bwd {rows} rows, {what}: max|G - G64| = {err:.3g}, e_ref = {e_ref:.3g}, err / bound {err / allowed:.3f}")
+        assert err <= allowed
+    assert torch.equal(bits(vq_bwd(enc, dev[0], dev[1], dev[2], None)), bits(dev[2]))      # grad_loss NULL: the bits of grad_z_st
+
+
+# ------------------------------------------------------------------ 6. the autograd surface
+def front_params(enc):
+    return enc._front_params(torch.device("cuda", torch.cuda.current_device()))
+
+
+def test_autograd_surface():
+    g = R.load("partial_tile")
+    mel, ws = on_gpu(g)
+    G = g["G"].cuda()
+    direct = run(encoder(), g, mel, ws, G)
+    enc = encoder(80, g["w"])
+    plain = enc.front_end(mel)
+    with torch.no_grad():
+        quiet = enc.front_end(mel, differentiable=True)
+    assert plain.grad_fn is None and not plain.requires_grad and quiet.grad_fn is None and not quiet.requires_grad
+    z = enc.front_end(mel, differentiable=True)
+    assert z.requires_grad and z.grad_fn is not None
+    assert torch.equal(bits(plain), bits(z.detach())) and torch.equal(bits(quiet), bits(z.detach()))
+    (z * G).sum().backward()
+    for k, p in zip(R.KEYS, front_params(enc)):
+        assert torch.equal(bits(p.grad), bits(direct[k])), k
+    (enc.front_end(mel, differentiable=True) * G).sum().backward()  # .grad accumulates
+    for k, p in zip(R.KEYS, front_params(enc)):
+        assert torch.equal(bits(p.grad), bits(direct[k] * 2.0)), k
+    assert all(p.grad is None for p in enc.rnn.parameters())
+
+    # only what requires grad is asked for; nothing to differentiate: detached
+    enc = encoder(80, g["w"])
+    for k, p in zip(R.KEYS, front_params(enc)):
+        p.requires_grad_(k in TOP_TWO)
+    (enc.front_end(mel, differentiable=True) * G).sum().backward()
+    for k, p in zip(R.KEYS, front_params(enc)):
+        assert (p.grad is not None) == (k in TOP_TWO) and (p.grad is None or torch.equal(bits(p.grad), bits(direct[k]))), k
+    for p in front_params(enc):
+        p.requires_grad_(False)
+    assert enc.front_end(mel, differentiable=True).grad_fn is None
+
+    # quantize: a grad_fn only when z_pre requires grad; values of the default call; the straight-through gradient
+    enc = encoder(80, g["w"])
+    zp = plain.clone().requires_grad_(True)
+    d_st, d_loss, d_ppl, d_idx = enc.quantize(plain)
+    assert d_st.grad_fn is None and d_loss.grad_fn is None
+    z_st, vq_loss, ppl, idx = enc.quantize(zp, differentiable=True)
+    assert z_st.grad_fn is not None and vq_loss.grad_fn is not None and not ppl.requires_grad and not idx.requires_grad
+    assert torch.equal(bits(z_st.detach()), bits(d_st)) and torch.equal(bits(vq_loss.detach()), bits(d_loss)) and torch.equal(idx, d_idx)
+    assert torch.equal(bits(ppl), bits(d_ppl))
+    ref_st, ref_loss, ref_ppl = enc.codebook(plain)                  # VQEmbeddingEMA.forward, as it always was
+    assert torch.equal(bits(ref_st), bits(d_st)) and torch.equal(bits(ref_loss), bits(d_loss)) and torch.equal(bits(ref_ppl), bits(d_ppl))
+    (z_st * G).sum().backward()
+    assert torch.equal(bits(zp.grad), bits(G))                       # straight through, the loss term dropped
+    with torch.no_grad():
+        assert enc.quantize(zp, differentiable=True)[0].grad_fn is None
+
+    # five optimizer steps: no new handle, and every step reads the moved weights
+    enc = encoder(80, g["w"])
+    enc.front_end(mel)
+    opt = torch.optim.SGD(front_params(enc), lr=1e-5)
+    handles, values = set(), []
+    for _ in range(5):
+        opt.zero_grad(set_to_none=True)
+        z = enc.front_end(mel, differentiable=True)
+        z_st, vq_loss, _, _ = enc.quantize(z, differentiable=True)
+        loss = (z_st ** 2).sum() / g["R"] + vq_loss
+        loss.backward()
+        opt.step()
+        handles.add(enc._handle.value)
+        values.append(loss.detach())
+    values = [float(v) for v in values]
+    assert len(handles) == 1 and all(a > b for a, b in zip(values, values[1:])), values
+    fresh = enc.front_end(mel)                                       # through _native(): rebuilt once, reads the stepped weights
+    again, _ = enc._front_fwd(mel, [p.detach() for p in front_params(enc)])
+    assert torch.equal(bits(fresh), bits(again))
+
+
+# ------------------------------------------------------------------ 7. the whole step
+RNN = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def chain_modules():
+    g = R.chain_case()
+    enc = V.Encoder(V.ConfEncoder(80, 512, 512, 64, g["c_dim"]))
+    enc.load_state_dict(g["sd"])
+    cpc = V.CPCLoss(V.ConfCPC(g["n_pred"], g["Spk"], g["Utt"], g["Neg"], 64, g["c_dim"]))
+    cpc.load_state_dict(g["cpc_sd"])
+    return g, enc.cuda().train(), cpc.cuda()
+
+
+def chain_step(g, enc, cpc, adapt):
+    z, c, vq_loss, ppl = enc.forward_differentiable(g["mel"].cuda(), adapt_codebook=adapt)
+    loss, _ = cpc(z, c, negatives=(g["utt"], g["seq"]), differentiable=True)
+    (loss + vq_loss).backward()
+    K = g["K"]
+    got = {k: p.grad for k, p in zip(R.KEYS, front_params(enc))}
+    got.update({k: getattr(enc.rnn, n).grad for k, n in zip(("w_ih", "w_hh", "b_ih", "b_hh"), RNN)})
+    got["W"] = torch.stack([m.weight.grad for m in cpc.predictors[:K]])
+    got["b"] = torch.stack([m.bias.grad for m in cpc.predictors[:K]])
+    assert all(m.weight.grad is None for m in cpc.predictors[K:])
+    return got, (loss.detach(), vq_loss.detach(), ppl)
+
+
+def test_the_whole_step_against_float64():
+    g, enc, cpc = chain_modules()
+    mel = g["mel"].cuda()
+    forced, idx, margin = R.chain_forced(g["w"], g["E"], g["mel"])
+    for l, s in enumerate((1, 3, 5, 7, 9)):                          # first: the decisions are the oracle's
+        assert np.array_equal((enc.stage(mel, s) > 0).cpu().numpy().reshape(-1, 512), forced[l]), l
+    assert np.array_equal(enc.encode_indices(mel).cpu().numpy().reshape(-1), idx)
+    print(f"\nchain: smallest VQ margin {margin:.3g}")
+    got, values = chain_step(g, enc, cpc, adapt=False)
+    R.judge(R.CHAIN, {k: v.cpu().numpy() for k, v in got.items()}, "GPU", keys=R.CHAIN_KEYS)
+    with pytest.raises(NotImplementedError):                         # Encoder.forward in .train() stays what it was
+        enc(mel)
+
+    # adapt_codebook=True: the same gradients bit for bit, and the buffers of vqcpc_encoder_vq_adapt
+    g, enc2, cpc2 = chain_modules()
+    got2, values2 = chain_step(g, enc2, cpc2, adapt=True)
+    for k in R.CHAIN_KEYS:
+        assert torch.equal(bits(got2[k]), bits(got[k])), k
+    assert all(torch.equal(bits(a), bits(b)) for a, b in zip(values, values2))
+    _, enc3, _ = chain_modules()
+    enc3.adapt_codebook(mel)
+    for name in ("embedding", "ema_count", "ema_weight"):
+        assert torch.equal(bits(getattr(enc2.codebook, name)), bits(getattr(enc3.codebook, name))), name
+        assert not torch.equal(bits(getattr(enc2.codebook, name)), bits(getattr(enc.codebook, name))), name
+
+
+# ------------------------------------------------------------------ 8. a fit
+def test_fit_on_one_fixed_batch_follows_float64():
+    """``R.FIT_STEPS`` steps of SGD on one fixed batch with the codebook frozen, all 23 tensors stepping.  The pins tool asserted
+    that the float64 run and the fp32 CPU run pick the same codes at every step (smallest margin: ``chain_fit_vq_margin``)."""
+    ref_losses, idx64, p64, _ = R.chain_sgd(torch.float64, R.FIT_STEPS, R.FIT_LR)
+    assert all(a > b for a, b in zip(ref_losses, ref_losses[1:])), ref_losses
+    _, idx32, p32, _ = R.chain_sgd(torch.float32, R.FIT_STEPS, R.FIT_LR)         # the reference's own fp32, on the CPU
+    assert all(np.array_equal(a, b) for a, b in zip(idx64, idx32))
+
+    g, enc, cpc = chain_modules()
+    K = g["K"]
+    mel, neg = g["mel"].cuda(), (g["utt"], g["seq"])
+    params = front_params(enc) + list(enc.rnn.parameters()) + [p for m in cpc.predictors[:K] for p in m.parameters()]
+    opt = torch.optim.SGD(params, lr=R.FIT_LR)
+    losses, handles = [], set()
+    for step in range(R.FIT_STEPS):
+        opt.zero_grad(set_to_none=True)
+        z, c, vq_loss, _ = enc.forward_differentiable(mel, adapt_codebook=False)
+        loss, _ = cpc(z, c, negatives=neg, differentiable=True)
+        (loss + vq_loss).backward()
+        opt.step()
+        losses.append((loss + vq_loss).detach())
+        if step:
+            handles.add(enc._handle.value)
+    losses = [float(l) for l in losses]
+    print(f"\nfit: GPU loss {losses[0]:.6f} -> {losses[-1]:.6f}, float64 {ref_losses[0]:.6f} -> {ref_losses[-1]:.6f}")
+    assert losses[-1] < losses[0] and len(handles) == 1
+    got = {k: p.detach().cpu().double().numpy() for k, p in zip(R.KEYS, front_params(enc))}
+    got.update({k: getattr(enc.rnn, n).detach().cpu().double().numpy() for k, n in zip(("w_ih", "w_hh", "b_ih", "b_hh"), RNN)})
+    got["W"] = torch.stack([p.weight.detach() for p in cpc.predictors[:K]]).cpu().double().numpy()
+    got["b"] = torch.stack([p.bias.detach() for p in cpc.predictors[:K]]).cpu().double().numpy()
+    bad = []
+    for k in R.CHAIN_KEYS:
+        drift, own = float(np.abs(got[k] - p64[k]).max()), float(np.abs(p32[k] - p64[k]).max())
+        allowed = 4.0 * max(own, R.U32 * float(np.abs(p64[k]).max()))
+        print(f"fit: max|{k}_gpu - {k}_64| = {drift:.3g}, torch fp32 on the CPU drifts {own:.3g}, allowed {allowed:.3g} (ratio {drift / allowed:.3f})")
+        if not drift <= allowed:
+            bad.append((k, drift, allowed))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------ 9. ABI errors
+def test_abi_errors_enqueue_nothing():
+    g = R.load("partial_tile")
+    enc = encoder()
+    mel, ws = on_gpu(g)
+    G = g["G"].cuda()
+    B, T = g["B"], g["T"]
+    lib, h, s = _lib.load(), enc._native(), _lib.current_stream()
+    n = ctypes.c_uint64()
+    assert lib.vqcpc_encoder_front_saved_bytes(h, B, T, ctypes.byref(n)) == 0 and n.value == g["R"] * (10 * 512 + 10) * 4
+    z_pre = torch.full((B, g["To"], 64), -7.0, device="cuda")
+    saved = torch.full((n.value // 4,), -7.0, device="cuda")
+    outs = [torch.full_like(w, -7.0) for w in ws]
+    W, Gs = enc._front_struct(ws), enc._front_struct(outs)
+
+    def fwd(mel=mel.data_ptr(), B=B, T=T, mode=0, w=W, z=z_pre.data_ptr(), saved=saved.data_ptr()):
+        return lib.vqcpc_encoder_front_fwd(h, mel, B, T, mode, ctypes.byref(w) if w is not None else None, z, saved, s)
+
+    def bwd(mel=mel.data_ptr(), B=B, T=T, mode=0, w=W, saved=saved.data_ptr(), G=G.data_ptr(), grads=Gs):
+        return lib.vqcpc_encoder_front_bwd(h, mel, B, T, mode, ctypes.byref(w) if w is not None else None, saved, G,
+                                           ctypes.byref(grads) if grads is not None else None, s)
+
+    INVALID = -1
+    assert lib.vqcpc_encoder_front_saved_bytes(h, 0, T, ctypes.byref(n)) == INVALID
+    assert lib.vqcpc_encoder_front_saved_bytes(h, B, 1, ctypes.byref(n)) == INVALID
+    assert lib.vqcpc_encoder_front_saved_bytes(h, B, T, None) == INVALID
+    for call in (fwd, bwd):
+        assert call(mel=None) == INVALID and call(saved=None) == INVALID and b"null argument" in lib.vqcpc_last_error()
+        assert call(B=0) == INVALID and call(T=1) == INVALID and b"B >= 1" in lib.vqcpc_last_error()
+        assert call(mode=3) == INVALID
+        assert call(mel=mel.data_ptr() + 4) == INVALID and b"16-byte aligned" in lib.vqcpc_last_error()
+        assert call(saved=saved.data_ptr() + 4) == INVALID and b"16-byte aligned" in lib.vqcpc_last_error()
+        hole = enc._front_struct(ws[:12] + [None] + ws[13:])
+        assert call(w=hole) == INVALID and b"every front-end tensor" in lib.vqcpc_last_error()
+        off = enc._front_struct(ws)
+        off.out_bias = ws[16].data_ptr() + 4
+        assert call(w=off) == INVALID
+    assert fwd(z=None) == INVALID and fwd(z=z_pre.data_ptr() + 4) == INVALID
+    assert bwd(G=None) == INVALID and bwd(grads=None) == INVALID
+    assert bwd(grads=enc._front_struct([None] * 17)) == INVALID and b"no gradient" in lib.vqcpc_last_error()
+    off = enc._front_struct(outs)
+    off.conv_weight = outs[0].data_ptr() + 4
+    assert bwd(grads=off) == INVALID
+    vq = lambda a=z_pre.data_ptr(), q=z_pre.data_ptr(), rows=8, gs=G.data_ptr(), gl=None, out=z_pre.data_ptr(): \
+        lib.vqcpc_encoder_vq_bwd(h, a, q, rows, gs, gl, out, s)
+    assert vq(a=None) == INVALID and vq(q=None) == INVALID and vq(out=None) == INVALID and vq(rows=0) == INVALID
+    assert vq(gs=None, gl=None) == INVALID and vq(gs=G.data_ptr() + 4) == INVALID
+    if torch.cuda.device_count() > 1:
+        with torch.cuda.device(1):
+            assert fwd() == INVALID and b"belongs to device" in lib.vqcpc_last_error()
+            assert bwd() == INVALID and vq() == INVALID
+    torch.cuda.synchronize()
+    assert bool((z_pre == -7.0).all()) and bool((saved == -7.0).all()) and all(bool((o == -7.0).all()) for o in outs)
+    assert fwd() == 0 and bwd() == 0
+    torch.cuda.synchronize()
+    assert bool((z_pre != -7.0).all()) and all(bool((o != -7.0).all()) for o in outs)
+    assert fwd(w=None) == 0 and bwd(w=None) == 0
+    torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------ 10. the command line: score, fit, score, checkpoint
+def test_cli_fit_encoder_end_to_end(tmp_path, capsys):
+    import json
+    from vectorquantizedcpc_amd import cli, io
+    ds = tmp_path / "datasets" / "eng"
+    (ds / "test").mkdir(parents=True)
+    names = [f"S{s}_{u}" for s in (1, 2) for u in "ab"]
+    for n in names:
+        np.save(ds / "test" / f"{n}.mel.npy", synth.mel("fit/" + n, 1, 44)[0].numpy())
+    (ds / "test.json").write_text(json.dumps([["x", 0, 1, f"eng/test/{n}"] for n in names]))
+    common = ["--dataset", str(ds), "--prediction-steps", "4", "--speakers", "2", "--utterances", "2", "--negatives", "3",
+              "--sample-frames", "16"]
+    src, out = tmp_path / "in.pt", tmp_path / "fit.pt"
+    init = synth.cpc_state_dict(n_prediction_steps=4)
+    esd = synth.encoder_state_dict(ln_affine="random", codebook="data")
+    # a codebook that has been trained: every code has been seen (ema_count = 0 with data-scale codes is the state of no checkpoint:
+    # the first EMA update divides a code's 0.999 ema_weight by its 0.001 n rows)
+    esd["codebook.ema_count"] = torch.full_like(esd["codebook.ema_count"], 50.0)
+    esd["codebook.ema_weight"] = esd["codebook.embedding"] * 50.0
+    torch.save({"encoder": esd, "cpc": init, "epoch": 7}, src)
+    adapted = tmp_path / "adapted.pt"
+    assert cli.main(["adapt-codebook", "--dataset", str(ds), "--cpc-checkpoint", str(src), "--out-checkpoint", str(adapted)]) == 0
+    capsys.readouterr()
+    src = adapted                                                    # adapt -> fit encoder -> score
+    assert cli.main(["fit-encoder", *common, "--cpc-checkpoint", str(src), "--out-checkpoint", str(out), "--steps", "10", "--lr", "1e-4"]) == 0
+    text = capsys.readouterr().out
+    assert text.count("cpc loss:") == 2 and "before the fit" in text and "after the fit" in text
+    line = [l for l in text.splitlines() if l.startswith("fitted")][0]
+    lo, hi = (float(v) for v in line.split(": loss ")[1].split(" = ")[0].split(" -> "))     # the step's loss, cpc + vq (train_cpc.py:116)
+    print(line)
+    assert hi < lo, line
+    old, ck = (torch.load(f, map_location="cpu", weights_only=True) for f in (src, out))
+    assert set(ck) == {"encoder", "cpc", "epoch"} and ck["epoch"] == 7 and list(ck["cpc"]) == list(init)
+    assert list(ck["encoder"]) == list(old["encoder"])
+    for k, v in old["encoder"].items():
+        assert not torch.equal(ck["encoder"][k], v), k               # the front end, the LSTM and the codebook's buffers all moved
+    for k in range(4):
+        for p in ("weight", "bias"):
+            assert torch.equal(ck["cpc"][f"predictors.{k}.{p}"], init[f"predictors.{k}.{p}"]) != (k < 2), (k, p)
+    assert io.load_cpc_checkpoint(out).keys() == init.keys()
+    assert cli.main(["score", *common, "--cpc-checkpoint", str(out)]) == 0                 # score reads the fitted checkpoint
+    assert "cpc loss:" in capsys.readouterr().out

@@ -1,0 +1,67 @@
+"""Writes tests/golden/front_grad_pins.npz, the pins of tests/front_grad_ref.py's float64 reference of the front-end gradients: per
+case and tensor 64 sampled elements, the sum and the sum of squares, the largest magnitude -- and ``e_ref = max |G_ref32 - G_ref64|``,
+the error of the same torch modules (and, for ``chain``, of the same composition with the VQ step, the LSTM and the CPC loss) run in
+fp32 on the CPU under the same forced ReLU masks (and code indices).  Per case it records ``differ``: the number of mask elements in
+which the float64 run's own ReLUs differ from the fp32 program's; for ``chain`` also the smallest VQ margin of the fp32 forward, and
+-- after asserting that the float64 and the fp32 CPU run of the tests' fit pick the same codes at every step -- of that fit.
+The judges of the tests are built from these alone.  Data only; written with fixed archive dates: the same bytes at every run.
+
+    python tools/gen_front_grad_golden.py
+"""
+import os
+import sys
+import zipfile
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import front_grad_ref as R  # noqa: E402
+
+
+def pins_of(names):
+    out = {}
+    for name in names:
+        ref = R.grads64(name)
+        low = R.chain_grads(torch.float32) if name == R.CHAIN else R.torch_grads(name, torch.float32)
+        for k, G in ref.items():
+            if k == "differ":
+                out[f"{name}_differ"] = np.int64(G)
+                print(f"{name}: {G} mask elements differ between the fp32 program and the float64 run")
+                continue
+            out[f"{name}_{k}_samples"] = G.reshape(-1)[R.sample_positions(name, k, G.size)]
+            out[f"{name}_{k}_sums"] = np.array([G.sum(), (G ** 2).sum()])
+            out[f"{name}_{k}_max"] = np.float64(np.abs(G).max())
+            out[f"{name}_{k}_e_ref"] = np.float64(np.abs(low[k] - G).max())
+            print(f"{name} {k}: max {out[f'{name}_{k}_max']:.3g}, e_ref {out[f'{name}_{k}_e_ref']:.3g}")
+    return out
+
+
+def write_npz(path, arrays):
+    """An uncompressed .npz as ``np.load`` reads it, with the archive's dates fixed (``np.savez`` stamps the time of writing)."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as zf:
+        for key, value in arrays.items():
+            with zf.open(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(value), allow_pickle=False)
+    print(f"wrote {path} ({os.path.getsize(path)} bytes)")
+
+
+def main():
+    torch.set_num_threads(1)                                        # one summation order for the recorded fp32 error
+    out = pins_of(R.ALL_CASES + [R.CHAIN])
+    g = R.chain_case()
+    out["chain_vq_margin"] = np.float64(R.chain_forced(g["w"], g["E"], g["mel"])[2])
+    print(f"chain: smallest VQ margin of the fp32 forward {out['chain_vq_margin']:.3g}")
+    # the fit of the tests: over all its steps the float64 run and the fp32 CPU run must pick the same codes
+    _, idx64, _, m64 = R.chain_sgd(torch.float64, R.FIT_STEPS, R.FIT_LR)
+    _, idx32, _, m32 = R.chain_sgd(torch.float32, R.FIT_STEPS, R.FIT_LR)
+    assert all(np.array_equal(a, b) for a, b in zip(idx64, idx32)), "the fit's batch: float64 and fp32 pick different codes"
+    out["chain_fit_vq_margin"] = np.float64(min(m64, m32))
+    print(f"chain fit ({R.FIT_STEPS} steps, lr {R.FIT_LR}): the same codes at every step, smallest VQ margin {out['chain_fit_vq_margin']:.3g}")
+    write_npz(R.PINS, out)
+
+
+if __name__ == "__main__":
+    main()

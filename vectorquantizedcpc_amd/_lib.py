@@ -7,6 +7,7 @@ import contextlib
 import ctypes as C
 import os
 import warnings
+import weakref
 
 import numpy as np
 import torch
@@ -34,6 +35,9 @@ SYMBOLS = [
     "vqcpc_resampler_create", "vqcpc_resampler_destroy", "vqcpc_resampler_out_len", "vqcpc_resampler_run",
 ]
 
+# every symbol include/vqcpc_grad.h declares, exported by the same library (SYMBOLS stays the list of include/vqcpc.h alone)
+GRAD_SYMBOLS = ["vqcpc_encoder_front_saved_bytes", "vqcpc_encoder_front_fwd", "vqcpc_encoder_front_bwd", "vqcpc_encoder_vq_bwd"]
+
 
 class EncoderWeights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p), ("ln_weight", C.c_void_p * 5), ("ln_bias", C.c_void_p * 5),
@@ -42,6 +46,12 @@ class EncoderWeights(C.Structure):
                 ("rnn_b_ih", C.c_void_p), ("rnn_b_hh", C.c_void_p),
                 ("in_channels", C.c_int), ("channels", C.c_int), ("n_embeddings", C.c_int),
                 ("z_dim", C.c_int), ("c_dim", C.c_int)]
+
+
+class EncoderFrontTensors(C.Structure):
+    """``vqcpc_encoder_front_weights`` and ``vqcpc_encoder_front_grads`` (``include/vqcpc_grad.h``): the same members, read or written."""
+    _fields_ = [("conv_weight", C.c_void_p), ("ln_weight", C.c_void_p * 5), ("ln_bias", C.c_void_p * 5),
+                ("fc_weight", C.c_void_p * 4), ("out_weight", C.c_void_p), ("out_bias", C.c_void_p)]
 
 
 class CPCWeights(C.Structure):
@@ -88,6 +98,10 @@ def load():
     lib.vqcpc_encoder_context_saved_bytes.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
     lib.vqcpc_encoder_context_fwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_encoder_context_bwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vqcpc_encoder_front_saved_bytes.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
+    lib.vqcpc_encoder_front_fwd.argtypes = [vp, vp, i32, i32, i32, C.POINTER(EncoderFrontTensors), vp, vp, vp]
+    lib.vqcpc_encoder_front_bwd.argtypes = [vp, vp, i32, i32, i32, C.POINTER(EncoderFrontTensors), vp, vp, C.POINTER(EncoderFrontTensors), vp]
+    lib.vqcpc_encoder_vq_bwd.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     lib.vqcpc_encoder_stage.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     lib.vqcpc_encoder_vq_encode.argtypes = [vp, vp, i32, vp, i64p, vp]
     lib.vqcpc_encoder_vq_adapt.argtypes = [vp, vp, i32, C.c_double, C.c_double, vp, vp, vp, vp, i64p, vp, vp, vp]
@@ -170,8 +184,13 @@ class WeightSlots:
 
     def __init__(self, module, names):
         self.names = list(names)
-        self.module = module
-        self._resolve()
+        self._module = weakref.ref(module)       # the module keeps its slots in its __dict__: a strong reference back would make
+        self._resolve()                          # every module garbage that only the cycle collector frees -- its native handle
+                                                 # (hipFree synchronises the device) would then go whenever a collection happens to run
+
+    @property
+    def module(self):
+        return self._module()
 
     def _resolve(self):
         self.slots, self.owners = [], []

@@ -27,6 +27,15 @@
                                                  --out-checkpoint out.pt [--steps 200 --lr 4e-4] [--freeze-predictors]
                                                  [the options of score]
 
+    python -m vectorquantizedcpc_amd.cli fit-encoder --dataset datasets/2019/english --cpc-checkpoint in.pt | --random-init
+                                                 --out-checkpoint out.pt [--steps 200 --lr 4e-4] [--train front,rnn,predictors]
+                                                 [--freeze-codebook] [the options of score]
+
+``fit-encoder`` runs the reference's whole training step (``train_cpc.py:116-124``, ``driver.fit_encoder``): the front end, the
+context LSTM and the K predictors under one Adam, ``loss = cpc_loss + vq_loss``, the codebook following by its EMA update unless
+``--freeze-codebook`` -- every gradient from the loss down to ``conv.weight`` is a HIP call (``vqcpc_cpc_grad``,
+``vqcpc_encoder_context_bwd``, ``vqcpc_encoder_vq_bwd``, ``vqcpc_encoder_front_bwd``).  It prints the ``score`` lines before and
+after and writes a checkpoint with ``"encoder"`` and ``"cpc"`` replaced.
 ``fit-context`` refits the context LSTM ``encoder.rnn`` together with the K predictors (``driver.fit_context``: back-propagation
 through time is ``vqcpc_encoder_context_bwd``'s, the optimizer torch's Adam over both, as ``train_cpc.py:53-55`` has them) on the
 frozen front end and codebook -- the step after ``adapt-codebook``.  It prints the ``score`` lines before and after and writes a
@@ -178,6 +187,27 @@ def fit_context_dataset(args) -> int:
     return rc
 
 
+def fit_encoder_dataset(args) -> int:
+    train = tuple(t for t in args.train.split(",") if t)
+    enc, cpc, by_speaker = _score_setup(args)
+    print("before the fit:")
+    if _print_score(args, enc, cpc, by_speaker):
+        return 1
+    r = driver.fit_encoder(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed,
+                           adapt_codebook=not args.freeze_codebook, train=train)
+    print(f"fitted {', '.join(train)} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches, codebook "
+          f"{'frozen' if args.freeze_codebook else 'following'}: loss {r['losses'][0] + r['vq_losses'][0]:.6f} -> "
+          f"{r['losses'][-1] + r['vq_losses'][-1]:.6f} = cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f} + "
+          f"vq loss {r['vq_losses'][0]:.2E} -> {r['vq_losses'][-1]:.2E}")
+    print("after the fit:")
+    rc = _print_score(args, enc, cpc, by_speaker)
+    io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
+                              encoder_state=enc.state_dict() if args.random_init else None,
+                              encoder_update=None if args.random_init else enc.state_dict())
+    print(f"wrote {args.out_checkpoint}: \"encoder\" replaced ({len(enc.state_dict())} keys), \"cpc\" replaced ({len(cpc.state_dict())} keys)")
+    return rc
+
+
 def score_vocoder_dataset(args) -> int:
     import json
     from . import preprocess
@@ -306,7 +336,7 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook", "fit-predictors", "fit-context"):
+    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook", "fit-predictors", "fit-context", "fit-encoder"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
         if name in ("encode", "convert"):
@@ -315,7 +345,7 @@ def main(argv=None) -> int:
         p.add_argument("--random-init", action="store_true", help="seeded random-init weights (no checkpoint ships with the reference)")
         p.add_argument("--device", default="cuda")
         p.add_argument("--max-batch", type=int, default=64)
-        if name in ("score", "fit-predictors", "fit-context"):               # config.py:42-47, :202
+        if name in ("score", "fit-predictors", "fit-context", "fit-encoder"):               # config.py:42-47, :202
             p.add_argument("--prediction-steps", type=int, default=12)
             p.add_argument("--speakers", type=int, default=8)
             p.add_argument("--utterances", type=int, default=8)
@@ -328,6 +358,9 @@ def main(argv=None) -> int:
                 p.add_argument("--lr", type=float, default=4e-4, help="Adam's learning rate (config.py's CPC training rate)")
             if name == "fit-context":
                 p.add_argument("--freeze-predictors", action="store_true", help="step the LSTM alone")
+            if name == "fit-encoder":
+                p.add_argument("--train", default=",".join(driver.FIT_ENCODER_PARTS), help="comma-separated parts that step")
+                p.add_argument("--freeze-codebook", action="store_true", help="no EMA update of the codebook")
         elif name == "encode":
             p.add_argument("--save-auxiliary", action="store_true")
         elif name == "adapt-codebook":
@@ -368,11 +401,16 @@ def main(argv=None) -> int:
         return abx_dataset(args)
     if not args.random_init and not args.cpc_checkpoint:
         ap.error("give --cpc-checkpoint (and --vocoder-checkpoint for convert) or --random-init")
+    if args.cmd == "fit-encoder":
+        parts = [t for t in args.train.split(",") if t]
+        if not parts or len(set(parts)) != len(parts) or any(t not in driver.FIT_ENCODER_PARTS for t in parts):
+            ap.error(f"fit-encoder --train: name each of {','.join(driver.FIT_ENCODER_PARTS)} at most once, and at least one")
     if args.cmd == "score-vocoder" and not args.random_init and not args.vocoder_checkpoint:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,
             "score-vocoder": score_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset,
-            "fit-predictors": fit_predictors_dataset, "fit-context": fit_context_dataset}[args.cmd](args)
+            "fit-predictors": fit_predictors_dataset, "fit-context": fit_context_dataset,
+            "fit-encoder": fit_encoder_dataset}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -63,7 +63,7 @@ __device__ __forceinline__ float2 ln512_moments(const float *x, const LnConst &k
 
 __global__ __launch_bounds__(256) void ln512_kernel(const float *__restrict__ X, const float *__restrict__ g,
                                                     const float *__restrict__ b, float *__restrict__ Y, int M,
-                                                    float eps, int relu, LnConst k) {
+                                                    float eps, int relu, LnConst k, float *__restrict__ stat) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int half = lane >> 5, ll = lane & 31;
     const int row = (blockIdx.x * 4 + wave) * 2 + half;
@@ -72,6 +72,7 @@ __global__ __launch_bounds__(256) void ln512_kernel(const float *__restrict__ X,
     const float2 mr = ln512_moments(x, k, eps);
     const float mean = mr.x, rstd = mr.y;
     if (row < M) {
+        if (stat && ll == 0) { stat[2 * (size_t)row] = mean; stat[2 * (size_t)row + 1] = rstd; }   // kept for the backward (front_grad.hip)
         float *y = Y + (size_t)row * 512;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -762,8 +763,9 @@ __global__ void conv_weight_permute_kernel(const float *__restrict__ w, float *_
 // ------------------------------------------------------------------------------------------
 // launches (encoder_internal.h)
 // ------------------------------------------------------------------------------------------
-void launch_ln512(const float *X, const float *g, const float *b, float *Y, int M, float eps, int relu, const LnConst &k, hipStream_t s) {
-    hipLaunchKernelGGL(ln512_kernel, dim3((M + 7) / 8), dim3(256), 0, s, X, g, b, Y, M, eps, relu, k);
+void launch_ln512(const float *X, const float *g, const float *b, float *Y, int M, float eps, int relu, const LnConst &k, hipStream_t s,
+                  float *stat) {
+    hipLaunchKernelGGL(ln512_kernel, dim3((M + 7) / 8), dim3(256), 0, s, X, g, b, Y, M, eps, relu, k, stat);
 }
 void launch_vq_encode(const float *X, int N, const float4 *Ef, const float *E, const float *e2, int n_emb, int64_t *idx, float *zq, hipStream_t s) {
     hipLaunchKernelGGL(vq_encode_kernel, dim3((N + 15) / 16), dim3(256), 0, s, X, N, Ef, E, e2, n_emb, idx, zq);
@@ -785,8 +787,8 @@ void launch_vq_stats(const float *x, const float *q, const int64_t *idx, int n_r
     hipLaunchKernelGGL(vq_stats_partial_kernel, dim3(nparts), dim3(256), 0, s, x, q, idx, n_rows, zst, part, hist);
     hipLaunchKernelGGL(vq_stats_final_kernel, dim3(1), dim3(256), 0, s, part, nparts, hist, n_emb, n_rows, loss, ppl);
 }
-void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C) {
-    hipLaunchKernelGGL(conv_weight_permute_kernel, dim3((unsigned)(((size_t)O * C * 4 + 255) / 256)), dim3(256), 0, 0, w, w1, w2, O, C);
+void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C, hipStream_t s) {
+    hipLaunchKernelGGL(conv_weight_permute_kernel, dim3((unsigned)(((size_t)O * C * 4 + 255) / 256)), dim3(256), 0, s, w, w1, w2, O, C);
 }
 void launch_rowsumsq64(const float *X, float *out, int n, hipStream_t s) {
     hipLaunchKernelGGL(rowsumsq64_kernel, dim3((n + 63) / 64), dim3(64), 0, s, X, out, n);

@@ -1,6 +1,7 @@
 // encoder_host.hip -- the encoder handle (struct vqcpc_encoder), the choice among the three schedules of its front end
 // (layered kernels, one fused launch, six column-split launches: encoder.hip) and every vqcpc_encoder_* entry point.
 #include "encoder_internal.h"
+#include "../../include/vqcpc_grad.h"
 #include <string.h>
 
 struct vqcpc_encoder {
@@ -18,6 +19,8 @@ struct vqcpc_encoder {
     DevPtr<char> stats;
     DevPtr<char> adapt;                  // work space of vqcpc_encoder_vq_adapt, grown on demand: q, idx, 16-bit idx, counts
     CtxGradWork ctx;                     // work space of vqcpc_encoder_context_fwd / _bwd (context_grad.hip)
+    FrontGradWork front;                 // work space of vqcpc_encoder_front_fwd / _bwd (front_grad.hip)
+    DevPtr<float> conv_w;                // conv.weight as given (the layout of its gradient)
     int device = 0;                      // the device the handle was created on
     // fused and column-split schedules: weights in 16x16x4 fragment order (only when 4 * in_channels <= 512, the width of
     // their activation tile), and the model's half of their kernel argument
@@ -50,6 +53,7 @@ static int encoder_create_impl(const vqcpc_encoder_weights *w, vqcpc_encoder *e)
     TRY(e->conv_w1.reserve(nconv * sizeof(float)));
     TRY(e->conv_w2.reserve(nconv * sizeof(float)));
     launch_conv_weight_permute(w->conv_weight, e->conv_w1, e->conv_w2, CH, C);
+    TRY(dev_copy(e->conv_w, w->conv_weight, nconv * sizeof(float), hipMemcpyDeviceToDevice));
     HIP_TRY(hipGetLastError());
     const hipMemcpyKind D2D = hipMemcpyDeviceToDevice;
     for (int i = 0; i < 5; ++i) {
@@ -307,6 +311,94 @@ extern "C" int vqcpc_encoder_context_bwd(vqcpc_encoder *e, const float *z, int B
     return vq_ctx_bwd(e->ctx, w, z, B, Tz, c, (const float *)saved, grad_c, grad_z, grad_w_ih, grad_w_hh, grad_bias, (hipStream_t)stream);
 }
 
+// ---- include/vqcpc_grad.h: the front end of a training step, its backward and the VQ step's backward (front_grad.hip)
+// The checks vqcpc_encoder_front_fwd / _bwd share; nothing is enqueued before they pass.
+static int front_grad_begin(vqcpc_encoder *e, const char *what, const float *mel, int B, int T, int conv_mode,
+                            const vqcpc_encoder_front_weights *w, FrontW &fw) {
+    VQ_REQUIRE(e && mel, "%s: null argument", what);
+    VQ_REQUIRE(B >= 1 && T >= 2, "%s: need B >= 1 and T >= 2 (got B=%d T=%d)", what, B, T);
+    VQ_REQUIRE(conv_mode >= 0 && conv_mode <= 2, "%s: conv_mode must be 0, 1 or 2", what);
+    VQ_REQUIRE((long long)B * frames_of(T) <= (1ll << 22), "%s: B * (T / 2) = %lld rows, more than 2^22", what, (long long)B * frames_of(T));
+    VQ_REQUIRE((long long)B * e->in_channels * T < (1ll << 31), "%s: mel of %lld elements, 2^31 or more", what, (long long)B * e->in_channels * T);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    VQ_REQUIRE(dev == e->device, "%s: handle belongs to device %d, current device is %d", what, e->device, dev);
+    bool ok = aligned16(mel);
+    if (w) {
+        fw.conv = w->conv_weight; fw.conv_w1 = fw.conv_w2 = nullptr;
+        fw.out_w = w->out_weight; fw.out_b = w->out_bias;
+        bool all = w->conv_weight && w->out_weight && w->out_bias;
+        ok = ok && aligned16(w->conv_weight) && aligned16(w->out_weight) && aligned16(w->out_bias);
+        for (int i = 0; i < 5; ++i) {
+            fw.ln_g[i] = w->ln_weight[i]; fw.ln_b[i] = w->ln_bias[i];
+            all = all && w->ln_weight[i] && w->ln_bias[i];
+            ok = ok && aligned16(w->ln_weight[i]) && aligned16(w->ln_bias[i]);
+        }
+        for (int i = 0; i < 4; ++i) { fw.fc_w[i] = w->fc_weight[i]; all = all && w->fc_weight[i]; ok = ok && aligned16(w->fc_weight[i]); }
+        VQ_REQUIRE(all, "%s: a weights struct must give every front-end tensor (NULL struct = the handle's copies)", what);
+    } else {
+        fw.conv = e->conv_w; fw.conv_w1 = e->conv_w1; fw.conv_w2 = e->conv_w2;
+        for (int i = 0; i < 5; ++i) { fw.ln_g[i] = e->ln_g[i]; fw.ln_b[i] = e->ln_b[i]; }
+        for (int i = 0; i < 4; ++i) fw.fc_w[i] = e->fc_w[i];
+        fw.out_w = e->out_w; fw.out_b = e->out_b;
+    }
+    VQ_REQUIRE(ok, "%s: mel and the weights must be 16-byte aligned", what);
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_front_saved_bytes(vqcpc_encoder *e, int B, int T, uint64_t *bytes) {
+    VQ_REQUIRE(e && bytes, "vqcpc_encoder_front_saved_bytes: null argument");
+    VQ_REQUIRE(B >= 1 && T >= 2, "vqcpc_encoder_front_saved_bytes: need B >= 1 and T >= 2 (got B=%d T=%d)", B, T);
+    *bytes = (uint64_t)vq_front_saved_bytes(B, frames_of(T));
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_encoder_front_fwd(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode,
+                                       const vqcpc_encoder_front_weights *w, float *z_pre, void *saved, void *stream) {
+    VQ_REQUIRE(z_pre && saved, "vqcpc_encoder_front_fwd: null argument");
+    FrontW fw;
+    TRY(front_grad_begin(e, "vqcpc_encoder_front_fwd", mel, B, T, conv_mode, w, fw));
+    VQ_REQUIRE(aligned16(z_pre) && aligned16(saved), "vqcpc_encoder_front_fwd: z_pre and saved must be 16-byte aligned");
+    return vq_front_fwd(e->front, fw, e->lnc, mel, B, e->in_channels, T, resolve_conv_mode(e, conv_mode, B, T), z_pre, (float *)saved,
+                        (hipStream_t)stream);
+}
+
+extern "C" int vqcpc_encoder_front_bwd(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode,
+                                       const vqcpc_encoder_front_weights *w, const void *saved, const float *grad_z_pre,
+                                       const vqcpc_encoder_front_grads *grads, void *stream) {
+    VQ_REQUIRE(saved && grad_z_pre && grads, "vqcpc_encoder_front_bwd: null argument");
+    FrontW fw;
+    TRY(front_grad_begin(e, "vqcpc_encoder_front_bwd", mel, B, T, conv_mode, w, fw));
+    FrontG g;
+    g.conv = grads->conv_weight; g.out_w = grads->out_weight; g.out_b = grads->out_bias;
+    bool any = g.conv || g.out_w || g.out_b, ok = aligned16(saved) && aligned16(grad_z_pre) && aligned16(g.conv) && aligned16(g.out_w) && aligned16(g.out_b);
+    for (int i = 0; i < 5; ++i) {
+        g.ln_g[i] = grads->ln_weight[i]; g.ln_b[i] = grads->ln_bias[i];
+        any = any || g.ln_g[i] || g.ln_b[i];
+        ok = ok && aligned16(g.ln_g[i]) && aligned16(g.ln_b[i]);
+    }
+    for (int i = 0; i < 4; ++i) { g.fc_w[i] = grads->fc_weight[i]; any = any || g.fc_w[i]; ok = ok && aligned16(g.fc_w[i]); }
+    VQ_REQUIRE(any, "vqcpc_encoder_front_bwd: no gradient asked for");
+    VQ_REQUIRE(ok, "vqcpc_encoder_front_bwd: saved, grad_z_pre and the gradients must be 16-byte aligned");
+    return vq_front_bwd(e->front, fw, mel, B, e->in_channels, T, (const float *)saved, grad_z_pre, g, (hipStream_t)stream);
+}
+
+extern "C" int vqcpc_encoder_vq_bwd(vqcpc_encoder *e, const float *z_pre, const float *z_q, int n_rows, const float *grad_z_st,
+                                    const float *grad_loss, float *grad_z_pre, void *stream) {
+    VQ_REQUIRE(e && z_pre && z_q && grad_z_pre, "vqcpc_encoder_vq_bwd: null argument");
+    VQ_REQUIRE(grad_z_st || grad_loss, "vqcpc_encoder_vq_bwd: give grad_z_st, grad_loss or both");
+    VQ_REQUIRE(n_rows >= 1, "vqcpc_encoder_vq_bwd: n_rows must be at least 1 (got %d)", n_rows);
+    VQ_REQUIRE(aligned16(z_pre) && aligned16(z_q) && aligned16(grad_z_pre) && aligned16(grad_z_st),
+               "vqcpc_encoder_vq_bwd: the rows must be 16-byte aligned");
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    VQ_REQUIRE(dev == e->device, "vqcpc_encoder_vq_bwd: handle belongs to device %d, current device is %d", e->device, dev);
+    const float scale = (float)(0.5 / ((double)n_rows * (double)e->z_dim));
+    launch_vq_bwd(z_pre, z_q, (size_t)n_rows * e->z_dim, scale, grad_z_st, grad_loss, grad_z_pre, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
 extern "C" int vqcpc_encoder_forward_stats(vqcpc_encoder *e, const float *z_pre, const float *z_q,
                                            const int64_t *idx, int n_rows, float *z_st, float *loss,
                                            float *perplexity, void *stream) {
@@ -371,6 +463,6 @@ extern "C" int vqcpc_encoder_vq_adapt(vqcpc_encoder *e, const float *x, int n_ro
 
 extern "C" int vqcpc_encoder_workspace_bytes(vqcpc_encoder *e, uint64_t *bytes) {
     VQ_REQUIRE(e && bytes, "vqcpc_encoder_workspace_bytes: null argument");
-    *bytes = (uint64_t)(e->bufA.cap + e->bufB.cap + e->zpre.cap + e->stats.cap + e->adapt.cap + e->ctx.bytes());
+    *bytes = (uint64_t)(e->bufA.cap + e->bufB.cap + e->zpre.cap + e->stats.cap + e->adapt.cap + e->ctx.bytes() + e->front.bytes());
     return VQCPC_OK;
 }

@@ -43,8 +43,9 @@ struct FusedP {
     float eps; LnConst lnc;
 };
 
-// Y = LayerNorm(512)(X) (+ ReLU), M rows.
-void launch_ln512(const float *X, const float *g, const float *b, float *Y, int M, float eps, int relu, const LnConst &k, hipStream_t s);
+// Y = LayerNorm(512)(X) (+ ReLU), M rows.  stat (M, 2), if given, receives every row's (mean, rstd) as the kernel computed them.
+void launch_ln512(const float *X, const float *g, const float *b, float *Y, int M, float eps, int relu, const LnConst &k, hipStream_t s,
+                  float *stat = nullptr);
 // VQEmbeddingEMA.encode of N rows of 64: Ef codebook fragments (launch_vq_build_frag), e2 = |E|^2 (launch_rowsumsq64).
 void launch_vq_encode(const float *X, int N, const float4 *Ef, const float *E, const float *e2, int n_emb, int64_t *idx, float *zq, hipStream_t s);
 // The whole front end + VQ in one launch (p.stage < 0), or up to p.stage with that stage's rows in p.stage_out.
@@ -55,7 +56,7 @@ void launch_enc_split(const FusedP &p, float *a, float *b, hipStream_t s);
 void launch_vq_stats(const float *x, const float *q, const int64_t *idx, int n_rows, float *zst, double *part, int nparts, unsigned *hist,
                      int n_emb, float *loss, float *ppl, hipStream_t s);
 // Weight arrangement at create (default stream).
-void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C);   // conv.weight (O, C, 4) -> (O, 4 C) in the k order of mode 1, 2
+void launch_conv_weight_permute(const float *w, float *w1, float *w2, int O, int C, hipStream_t s = 0);   // conv.weight (O, C, 4) -> (O, 4 C) in the k order of mode 1, 2; also per call for a caller's weights, on its stream
 void launch_rowsumsq64(const float *X, float *out, int n, hipStream_t s = 0);          // also after a codebook update, on its stream
 void launch_vq_build_frag(const float *E, float4 *Ef, int n_emb, hipStream_t s = 0);
 void launch_frag16_build(const float *W, int N, int K, float4 *Wf);                     // N % 16 == 0, K % 64 == 0: (N / 16) (K / 16) 64 float4
@@ -74,3 +75,34 @@ struct EmaP {
     float *codebook;                                          // the handle's copy of embedding
 };
 void launch_ema_update(const EmaP &p, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// front_grad.hip: the front end of a training step and its backward (include/vqcpc_grad.h)
+// ------------------------------------------------------------------------------------------
+// The front end's weights as the kernels read them: the handle's copies, or a caller's tensors.
+struct FrontW {
+    const float *conv;                  // conv.weight (512, C, 4), the reference's layout
+    const float *conv_w1, *conv_w2;     // the same as a GEMM operand in the k order of conv mode 1, 2; null = build per call from `conv`
+    const float *ln_g[5], *ln_b[5];
+    const float *fc_w[4];
+    const float *out_w, *out_b;
+};
+struct FrontG {                         // gradients wanted (null = not)
+    float *conv, *ln_g[5], *ln_b[5], *fc_w[4], *out_w, *out_b;
+};
+// The work space of both calls, grow-only, a member of the encoder handle.
+struct FrontGradWork {
+    DevBuf convw;                       // forward, caller's weights: conv.weight in the two k orders
+    DevBuf wT;                          // backward: one layer's weight, transposed
+    DevBuf d0, d1;                      // backward: two (R, 512) gradient buffers
+    DevBuf part, colpart;               // backward: slab partials of a weight gradient; tile partials of dgamma, dbeta
+    size_t bytes() const { return convw.cap + wT.cap + d0.cap + d1.cap + part.cap + colpart.cap; }
+};
+size_t vq_front_saved_bytes(int B, int To);
+// C = in_channels, conv_mode 1 or 2 (resolved).  z_pre (R, 64) and `saved` as vqcpc_grad.h says.
+int vq_front_fwd(FrontGradWork &k, FrontW w, const LnConst &lnc, const float *mel, int B, int C, int T, int conv_mode, float *z_pre,
+                 float *saved, hipStream_t s);
+int vq_front_bwd(FrontGradWork &k, const FrontW &w, const float *mel, int B, int C, int T, const float *saved, const float *grad_z_pre,
+                 const FrontG &g, hipStream_t s);
+void launch_vq_bwd(const float *z_pre, const float *z_q, size_t n, float scale, const float *grad_z_st, const float *grad_loss,
+                   float *grad_z_pre, hipStream_t s);

@@ -374,6 +374,69 @@ def fit_context(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 20
                 lambda z, c: encoder.context(z, differentiable=True))
 
 
+FIT_ENCODER_PARTS = ("front", "rnn", "predictors")
+
+
+def fit_encoder(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 200, lr: float = 4e-4, optimizer=torch.optim.Adam,
+                sample_frames: int = 128, seed: int = 13, device=None, adapt_codebook: bool = True, train=FIT_ENCODER_PARTS):
+    """Refit the whole encoder -- the training step of ``train_cpc.py:116-124`` -- after the codebook moved
+    (``adapt_codebook`` -> ``fit_encoder`` -> ``score_batches``): the Conv1d / LayerNorm / Linear front end that produces the units
+    follows the codebook, which ``fit_context`` and ``fit_predictors`` cannot make it do.
+
+    ``train``: which parts step, any of ``"front"`` (``encoder.conv`` and ``encoder.encoder``), ``"rnn"`` (``encoder.rnn``) and
+    ``"predictors"`` (``cpc.predictors[:K]``), under ONE ``optimizer(params, lr=lr)`` as ``train_cpc.py:53-55`` has them -- torch's,
+    as glue; the parameters of a part that is not named are left alone and receive no gradient.  ``adapt_codebook``: run the EMA
+    update of ``model.py:136-145`` in every step, as the reference's training branch does; False keeps the codebook frozen.
+
+    The batches, the cuts and ``stream_id`` = batch number are those of ``score_batches``; step i takes batch ``i mod batches``.
+    Nothing is encoded ahead, because the front end moves.  Every step is ``encoder.forward_differentiable(mels)`` ->
+    ``cpc(z, c, seed=seed, stream_id=batch, differentiable=True)`` -> ``loss = cpc_loss + vq_loss`` -> ``backward()``: one
+    ``vqcpc_cpc_grad``, one ``vqcpc_encoder_context_bwd``, one ``vqcpc_encoder_vq_bwd`` and one ``vqcpc_encoder_front_bwd`` call,
+    each asking only for what is needed -- then ``opt.step()``.  The native handles are not rebuilt between steps.
+
+    Returns what ``fit_context`` returns (``losses`` = the CPC loss per step), plus per-step ``vq_losses`` and ``perplexities``."""
+    train = tuple(train)
+    unknown = [t for t in train if t not in FIT_ENCODER_PARTS]
+    if unknown or not train or len(set(train)) != len(train):
+        raise ValueError(f"fit_encoder: train must name each of {FIT_ENCODER_PARTS} at most once and at least one of them, got {train!r}")
+    K = cpc.n_prediction_steps
+    parts = {"front": list(encoder.conv.parameters()) + list(encoder.encoder.parameters()), "rnn": list(encoder.rnn.parameters()),
+             "predictors": [p for m in cpc.predictors[:K] for p in m.parameters()]}
+    params = [p for name in FIT_ENCODER_PARTS if name in train for p in parts[name]]
+    frozen = [p for name in FIT_ENCODER_PARTS if name not in train for p in parts[name] if p.requires_grad]
+    S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
+    dev = device if device is not None else next(encoder.parameters()).device
+    n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
+    res = {"losses": [], "vq_losses": [], "perplexities": [], "accuracies": [], "steps": 0, "batches": n_batches,
+           "utterances": n_batches * S * U, "speakers_skipped": skipped, "speakers_left_over": left}
+    if n_batches == 0 or steps <= 0:
+        return res
+    opt = optimizer(params, lr=lr)
+    for p in frozen:                                     # a part that does not step costs no backward either
+        p.requires_grad_(False)
+    try:
+        for step in range(steps):
+            b = step % n_batches
+            mels = batch_mels(b)
+            opt.zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                z, c, vq_loss, perplexity = encoder.forward_differentiable(mels, adapt_codebook=adapt_codebook)
+                cpc_loss, acc = cpc(z, c, seed=seed, stream_id=b, differentiable=True)
+                (cpc_loss + vq_loss).backward()
+            if hasattr(encoder, "check"):
+                encoder.check()
+            opt.step()
+            res["losses"].append(float(cpc_loss.detach()))
+            res["vq_losses"].append(float(vq_loss.detach()))
+            res["perplexities"].append(float(perplexity))
+            res["accuracies"].append(list(acc))
+            res["steps"] = step + 1
+    finally:
+        for p in frozen:
+            p.requires_grad_(True)
+    return res
+
+
 # ---------------------------------------------------------------------------------------- vocoder scoring
 def mulaw_classes(wave, bits: int = 8):
     """Mu-law classes of a 16 kHz waveform as the reference makes its vocoder targets (``preprocess.py:20-27, :90-91``): peak

@@ -36,7 +36,7 @@ class VQEmbeddingEMA(nn.Module):
     wrappers over the owning ``Encoder``'s native handle (the same VQ kernel ``Encoder.encode`` runs).  In training mode
     ``forward`` also runs the EMA update of ``model.py:136-145`` (``vqcpc_encoder_vq_adapt``): no gradient is involved, the three
     buffers are updated IN PLACE (the reference rebinds them) and the native handle follows without being rebuilt.  The
-    straight-through gradient of ``model.py:150`` is not provided.
+    straight-through gradient of ``model.py:150`` is not provided here: ``Encoder.quantize(z_pre, differentiable=True)`` has it.
     """
 
     def __init__(self, n_embeddings, embedding_dim, commitment_cost=0.25, decay=0.999, epsilon=1e-5):
@@ -155,8 +155,8 @@ class Encoder(_lib.NativeModule):
 
     def workspace_bytes(self) -> int:
         """Device bytes of the native handle's grow-only work buffers (``vqcpc_encoder_workspace_bytes``): front-end activations,
-        statistics and the work spaces of the codebook update and of the context gradients -- the peak of the calls so far, weights
-        not counted."""
+        statistics and the work spaces of the codebook update, of the context gradients and of the front-end gradients -- the peak of
+        the calls so far, weights not counted."""
         import ctypes
         n = ctypes.c_uint64()
         _lib.check(_lib.load().vqcpc_encoder_workspace_bytes(self._native(), ctypes.byref(n)))
@@ -224,7 +224,7 @@ class Encoder(_lib.NativeModule):
                                                        out.data_ptr(), _lib.current_stream()))
         return out
 
-    def _adapt_rows(self, xf: Tensor, z_st: Optional[Tensor] = None, idx: Optional[Tensor] = None) -> Tensor:
+    def _adapt_rows(self, xf: Tensor, z_st: Optional[Tensor] = None, idx: Optional[Tensor] = None, handle=None) -> Tensor:
         """One codebook update (``vqcpc_encoder_vq_adapt``) over the rows xf (N, z_dim) fp32, contiguous, on the module's device
         -> a 2-element device tensor (loss, perplexity) from the codebook as it was (and, into ``z_st`` (N, z_dim) / ``idx`` (N) int64
         if given, the straight-through rows and the code indices of that codebook).  The three buffers are written through
@@ -237,7 +237,7 @@ class Encoder(_lib.NativeModule):
                                    f"(got {t.dtype}, contiguous={t.is_contiguous()}, {t.device})")
         if xf.size(0) < 1:
             raise RuntimeError("codebook update: no rows")
-        h = self._native()
+        h = handle if handle is not None else self._native()
         stats = torch.empty(2, device=xf.device)
         with _lib.device_guard(xf.device):
             _lib.check(_lib.load().vqcpc_encoder_vq_adapt(
@@ -345,6 +345,152 @@ class Encoder(_lib.NativeModule):
             _lib.check(_lib.load().vqcpc_encoder_context(self._native(), zf.data_ptr(), B, T, c.data_ptr(), _lib.current_stream()))
         return c
 
+    # ------------------------------------------------------------------ the front end, the VQ step and their gradients
+    _FRONT_NAMES = (["conv.weight"] + [f"encoder.{n}.weight" for n in (0, 3, 6, 9, 12)] + [f"encoder.{n}.bias" for n in (0, 3, 6, 9, 12)] +
+                    [f"encoder.{n}.weight" for n in (2, 5, 8, 11)] + ["encoder.14.weight", "encoder.14.bias"])
+
+    def _front_params(self, dev):
+        """The front end's 17 parameters in the member order of ``vqcpc_encoder_front_weights``."""
+        sub = lambda name: self.get_parameter(name)
+        ws = [sub(n) for n in self._FRONT_NAMES]
+        for n, t in zip(self._FRONT_NAMES, ws):
+            if t.dtype != torch.float32 or t.device != dev:
+                raise RuntimeError(f"{n} must be a float32 tensor on {dev} (got {t.dtype}, {t.device})")
+        return ws
+
+    @staticmethod
+    def _front_struct(tensors):
+        """17 tensors (or None) in ``_FRONT_NAMES`` order -> ``_lib.EncoderFrontTensors``."""
+        ptr = [t.data_ptr() if t is not None else None for t in tensors]
+        s = _lib.EncoderFrontTensors()
+        s.conv_weight = ptr[0]
+        for i in range(5):
+            s.ln_weight[i], s.ln_bias[i] = ptr[1 + i], ptr[6 + i]
+        for i in range(4):
+            s.fc_weight[i] = ptr[11 + i]
+        s.out_weight, s.out_bias = ptr[15], ptr[16]
+        return s
+
+    def _check_mels(self, mels: Tensor) -> Tensor:
+        _lib.require_cuda(mels, "mel")
+        if mels.dim() != 3 or mels.size(1) != self.conf.in_channels:
+            raise RuntimeError(f"expected mel of shape (B, {self.conf.in_channels}, T), got {tuple(mels.shape)}")
+        if mels.size(0) < 1 or mels.size(2) < 2:
+            raise RuntimeError("Conv1d(k=4, s=2, p=1) needs at least one utterance of at least 2 mel frames")
+        _lib.require_same_device(mels, self.conv.weight, "mel")
+        return mels.detach().to(torch.float32).contiguous()
+
+    def _front_fwd(self, mel: Tensor, weights=None, conv_mode: int = 0):
+        """One ``vqcpc_encoder_front_fwd`` call on a contiguous fp32 device mel -> (z_pre, saved).  ``weights``: the 17 front-end
+        tensors (contiguous, ``_FRONT_NAMES`` order), or None = the handle's copies."""
+        import ctypes
+        B, _, T = mel.shape
+        dev = mel.device
+        h = self._sizes_handle(dev) if weights is not None else self._native()
+        lib = _lib.load()
+        n = ctypes.c_uint64()
+        _lib.check(lib.vqcpc_encoder_front_saved_bytes(h, B, T, ctypes.byref(n)))
+        z_pre = torch.empty(B, (T - 2) // 2 + 1, self.conf.z_dim, device=dev)
+        saved = torch.empty(int(n.value) // 4, device=dev)
+        w = ctypes.byref(self._front_struct(weights)) if weights is not None else None
+        with _lib.device_guard(dev):
+            _lib.check(lib.vqcpc_encoder_front_fwd(h, mel.data_ptr(), B, T, conv_mode, w, z_pre.data_ptr(), saved.data_ptr(),
+                                                   _lib.current_stream()))
+        return z_pre, saved
+
+    def _front_bwd(self, mel: Tensor, saved: Tensor, grad_z_pre: Tensor, weights=None, want=(True,) * 17, conv_mode: int = 0):
+        """One ``vqcpc_encoder_front_bwd`` call.  want: 17 booleans in ``_FRONT_NAMES`` order -> the 17 gradients or None."""
+        import ctypes
+        B, _, T = mel.shape
+        dev = mel.device
+        h = self._sizes_handle(dev) if weights is not None else self._native()
+        shapes = [self.get_parameter(n).shape for n in self._FRONT_NAMES]
+        grads = [torch.empty(sh, device=dev) if w else None for sh, w in zip(shapes, want)]
+        w = ctypes.byref(self._front_struct(weights)) if weights is not None else None
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().vqcpc_encoder_front_bwd(h, mel.data_ptr(), B, T, conv_mode, w, saved.data_ptr(), grad_z_pre.data_ptr(),
+                                                           ctypes.byref(self._front_struct(grads)), _lib.current_stream()))
+        return grads
+
+    def front_end(self, mels: Tensor, *, differentiable: bool = False, conv_mode: int = 0) -> Tensor:
+        """``self.encoder(self.conv(mels).transpose(1, 2))`` (``model.py:65-67`` / ``:78-80``): mels (B, in_channels, T) ->
+        z_pre (B, T // 2, z_dim), the rows before the VQ.
+
+        differentiable=False (the default): ``stage(mels, 10)``, detached.  differentiable=True, grad mode on and a front-end
+        parameter requiring grad: ``z_pre`` carries a ``grad_fn``.  Its forward is one ``vqcpc_encoder_front_fwd`` on the parameters
+        as they are (an optimizer step costs no new handle) and keeps the rows the backward reads again; its backward is one
+        ``vqcpc_encoder_front_bwd`` call (``csrc/front_grad.hip``: every sum in a fixed order) asking only for the gradients autograd
+        needs.  The mel receives no gradient.  The value has the bits of the default call.  Under ``torch.no_grad()`` the flag
+        changes nothing."""
+        mel = self._check_mels(mels)
+        if differentiable and torch.is_grad_enabled():
+            ws = self._front_params(mel.device)
+            if any(p.requires_grad for p in ws):
+                return _FrontGrad.apply(self, mel, conv_mode, *ws)
+        return self.stage(mel, 10, conv_mode)
+
+    def _codebook_handle(self, dev):
+        """The handle for a call that reads only the CODEBOOK from the handle's copies (``quantize``): a live handle on ``dev`` whose
+        codebook is current serves, also one whose other copies an optimizer step has made stale -- a fit of the front end costs no
+        new handle per step.  (``vqcpc_encoder_vq_adapt`` keeps the handle's codebook and the buffer in step.)"""
+        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
+            i = 2 + self._WEIGHT_NAMES.index("codebook.embedding")
+            e = self.codebook.embedding
+            if self._handle_key[i] == (e.data_ptr(), e._version):
+                return self._handle
+        return self._native()
+
+    def _quantize_rows(self, xf: Tensor, adapt: bool, want_q: bool):
+        """The VQ step over rows xf (N, z_dim) fp32 contiguous -> (z_st, stats = [loss, perplexity], idx, q or None): the codebook
+        as it is on entry decides all four; with ``adapt`` the EMA update follows (``vqcpc_encoder_vq_adapt``)."""
+        N, dev = xf.size(0), xf.device
+        z_st = torch.empty_like(xf)
+        idx = torch.empty(N, dtype=torch.int64, device=dev)
+        q = None
+        lib, h = _lib.load(), self._codebook_handle(dev)
+        if want_q or not adapt:
+            q = torch.empty_like(xf)
+            with _lib.device_guard(dev):
+                _lib.check(lib.vqcpc_encoder_vq_encode(h, xf.data_ptr(), N, q.data_ptr(), idx.data_ptr(), _lib.current_stream()))
+        if adapt:
+            stats = self._adapt_rows(xf, z_st, idx, handle=h)
+        else:
+            stats = torch.empty(2, device=dev)
+            with _lib.device_guard(dev):
+                _lib.check(lib.vqcpc_encoder_forward_stats(h, xf.data_ptr(), q.data_ptr(), idx.data_ptr(), N, z_st.data_ptr(),
+                                                           stats[0:].data_ptr(), stats[1:].data_ptr(), _lib.current_stream()))
+        return z_st, stats, idx, q
+
+    def quantize(self, z_pre: Tensor, *, differentiable: bool = False, adapt: bool = False):
+        """``self.codebook(z_pre)`` (``model.py:117-155``): z_pre (B, T, z_dim) -> (z_st, vq_loss, perplexity, indices (B, T)),
+        all four from the codebook as it is on entry.
+
+        adapt=False: the eval branch (``vqcpc_encoder_vq_encode`` + ``vqcpc_encoder_forward_stats``).  adapt=True: the reference's
+        training branch, ``vqcpc_encoder_vq_adapt`` -- the EMA update of ``model.py:136-145`` follows, in place.
+        differentiable=True, grad mode on and ``z_pre`` requiring grad: ``z_st`` and ``vq_loss`` carry a ``grad_fn`` whose backward is
+        one ``vqcpc_encoder_vq_bwd`` call, the straight-through estimator plus the commitment loss of ``model.py:147-150``; the
+        values are those of the default call.  ``VQEmbeddingEMA.forward`` stays as it is."""
+        _lib.require_cuda(z_pre, "z_pre")
+        _lib.require_same_device(z_pre, self.codebook.embedding, "z_pre")
+        D = self.conf.z_dim
+        if z_pre.dim() != 3 or z_pre.size(2) != D or z_pre.numel() == 0:
+            raise RuntimeError(f"expected z_pre of shape (B, T, {D}), got {tuple(z_pre.shape)}")
+        if differentiable and torch.is_grad_enabled() and z_pre.requires_grad:
+            return _VQGrad.apply(self, z_pre.to(torch.float32), bool(adapt))
+        with torch.no_grad():
+            z_st, stats, idx, _ = self._quantize_rows(z_pre.detach().to(torch.float32).reshape(-1, D).contiguous(), bool(adapt), False)
+        return z_st.view_as(z_pre), stats[0], stats[1], idx.view(z_pre.shape[:2])
+
+    def forward_differentiable(self, mels: Tensor, *, adapt_codebook: bool = True):
+        """``model.py:72-86`` in training mode: (z, c, vq_loss, perplexity) with a ``grad_fn`` wherever a parameter requires grad --
+        ``front_end``, ``quantize`` and ``context``, each ``differentiable=True``.  ``adapt_codebook``: run the EMA update as the
+        reference's training branch does (the gradients are the same either way: they come from the codebook as it was).  Works in
+        either mode; ``forward`` itself stays the inference path."""
+        z_pre = self.front_end(mels, differentiable=True)
+        z, vq_loss, perplexity, _ = self.quantize(z_pre, differentiable=True, adapt=adapt_codebook)
+        c = self.context(z, differentiable=True)
+        return z, c, vq_loss, perplexity
+
     def forward(self, mels: Tensor):
         """``model.py:72-86`` in eval mode: (z, c, vq_loss, perplexity)."""
         if self.training:
@@ -383,8 +529,9 @@ class CPCLoss(_lib.NativeModule):
     grad mode returns a loss that ``backward()`` can be called on: ``vqcpc_cpc_grad`` (``csrc/cpc_grad.hip``) computes the loss
     and the gradients with respect to ``z``, ``c`` and the first K predictors in one call, every sum in a fixed order, so equal
     inputs give equal bits.  That is what ``driver.fit_predictors`` refits the predictors with on a frozen encoder, and what
-    ``driver.fit_context`` hands to ``Encoder.context(z, differentiable=True)`` to refit the context LSTM with them; the encoder's
-    front end and the VQ straight-through estimator have no backward here, and the optimizer is torch's.
+    ``driver.fit_context`` hands to ``Encoder.context(z, differentiable=True)`` to refit the context LSTM with them; in
+    ``driver.fit_encoder`` ``dz`` goes on through ``Encoder.quantize`` and ``Encoder.front_end`` down to ``conv.weight``.  The
+    optimizer is torch's.
 
     All ``n_prediction_steps`` predictors are held (the reference's 24 ``state_dict()`` keys, so
     ``load_state_dict(checkpoint["cpc"])`` works unchanged); like the reference only the first half is ever used
@@ -569,6 +716,56 @@ class _ContextGrad(torch.autograd.Function):
                                                  (w_ih.detach().contiguous(), w_hh.detach().contiguous()), ctx.want)
         need = ctx.needs_input_grad
         return None, gz, gi, gh, gb if need[4] else None, gb if need[5] else None
+
+
+class _FrontGrad(torch.autograd.Function):
+    """``Encoder.front_end(mels, differentiable=True)``: ``forward`` is ``vqcpc_encoder_front_fwd`` and keeps ``saved``;
+    ``backward`` is one ``vqcpc_encoder_front_bwd`` call asking for the gradients ``needs_input_grad`` names."""
+
+    @staticmethod
+    def forward(ctx, module, mel, conv_mode, *ws):
+        z_pre, saved = module._front_fwd(mel, [w.detach().contiguous() for w in ws], conv_mode)
+        ctx.module, ctx.kept, ctx.conv_mode = module, (mel, saved), conv_mode
+        ctx.save_for_backward(*ws)                       # torch refuses the backward if an in-place step has moved them since
+        return z_pre
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_z_pre):
+        mel, saved = ctx.kept
+        grads = ctx.module._front_bwd(mel, saved, grad_z_pre.to(torch.float32).contiguous(),
+                                      [w.detach().contiguous() for w in ctx.saved_tensors], ctx.needs_input_grad[3:], ctx.conv_mode)
+        return (None, None, None) + tuple(grads)
+
+
+class _VQGrad(torch.autograd.Function):
+    """``Encoder.quantize(z_pre, differentiable=True)``: ``forward`` is the VQ step and keeps the rows and their codes' rows;
+    ``backward`` is one ``vqcpc_encoder_vq_bwd`` call; a term whose upstream gradient is absent is dropped."""
+
+    @staticmethod
+    def forward(ctx, module, z_pre, adapt):
+        xf = z_pre.detach().reshape(-1, z_pre.size(2)).contiguous()
+        z_st, stats, idx, q = module._quantize_rows(xf, adapt, True)
+        ctx.module, ctx.kept, ctx.shape = module, (xf, q), z_pre.shape
+        ctx.set_materialize_grads(False)
+        loss, ppl, idx = stats[0], stats[1], idx.view(z_pre.shape[:2])
+        ctx.mark_non_differentiable(ppl, idx)
+        return z_st.view_as(z_pre), loss, ppl, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_z_st, grad_loss, _grad_ppl, _grad_idx):
+        if grad_z_st is None and grad_loss is None:
+            return None, None, None
+        xf, q = ctx.kept
+        gs = grad_z_st.to(torch.float32).contiguous() if grad_z_st is not None else None
+        gl = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None
+        out = torch.empty_like(xf)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with _lib.device_guard(xf.device):
+            _lib.check(_lib.load().vqcpc_encoder_vq_bwd(ctx.module._sizes_handle(xf.device), xf.data_ptr(), q.data_ptr(), xf.size(0),
+                                                        ptr(gs), ptr(gl), out.data_ptr(), _lib.current_stream()))
+        return None, out.view(ctx.shape), None
 
 
 class _CPCGrad(torch.autograd.Function):
