@@ -161,6 +161,7 @@ def load():
     lib.vqcpc_resampler_run.argtypes = [vp, vp, C.POINTER(C.c_int), i32, i32, vp, i32, vp]
     lib.vqcpc_probe_gates.argtypes = [vp, i32, vp, vp]          # test surface of csrc/gate_probe.hip, not in include/vqcpc.h
     lib.vqcpc_probe_draw.argtypes = [vp, i32, vp, vp, vp]       # likewise
+    lib.vqcpc_probe_words.argtypes = [vp, i32, i32, vp, vp]     # likewise
     lib.vqcpc_debug_live_bytes.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]    # likewise (csrc/runtime.hip)
     _lib = lib
     return lib

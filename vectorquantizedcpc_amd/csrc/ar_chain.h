@@ -17,14 +17,36 @@ constexpr int THREADS = 768;
 constexpr int NT_H = HR / 8;           // terms of a chain over h: 112
 constexpr int NT_A = HF / 8;           // terms of a chain over a: 32
 
-// exchange area of one XCD, in granules
-__host__ __device__ constexpr int xg_h(int bxt) { return NW * bxt * 32; }         // [rank][slot][32] (28 used: two whole lines)
-__host__ __device__ constexpr int xg_a(int bxt) { return bxt * NW * FPB; }        // [slot][rank][8]: the 256 granules of a slot are one run of 2 KB
+// Which instantiations exchange h_t / a_t as 4-byte words (ar_shared.h: xd_word_h / xd_word_a) instead of 8-byte {tag, value} granules:
+// bit BXT of the two masks (the exchanges are independent: either can be built alone).  h_t: four slots per XCD do; one and two
+// slots keep the granules until they have been measured under the same rule.  a_t: none -- at four slots it measured 0.1 us per
+// step slower than the granules (profiles/r15_ab_exchange_words.txt); the code stays for the next look at it.
+// -DXD_WORDS_H=7 -DXD_WORDS_A=7 builds all three on words, 0 none.  Candidates are granules either way.
+#ifndef XD_WORDS_H
+#define XD_WORDS_H 4
+#endif
+#ifndef XD_WORDS_A
+#define XD_WORDS_A 0
+#endif
+__host__ __device__ constexpr bool xd_words_h(int bxt) { return (XD_WORDS_H & bxt) != 0; }
+__host__ __device__ constexpr bool xd_words_a(int bxt) { return (XD_WORDS_A & bxt) != 0; }
+// exchange area of one XCD, in 8-byte units (a granule, or two words)
+__host__ __device__ constexpr int xg_h(int bxt) { return NW * bxt * (xd_words_h(bxt) ? 16 : 32); }   // [rank][slot][32] (28 used): granules two whole lines, words one
+__host__ __device__ constexpr int xg_a(int bxt) { return bxt * NW * FPB / (xd_words_a(bxt) ? 2 : 1); }   // [slot][rank][8]: a slot's 256 are one run of 2 KB (granules) or 1 KB (words)
 __host__ __device__ constexpr int xg_c() { return NW * 16; }                      // [slot < 16][rank]: a slot's 32 candidates are contiguous
 __host__ __device__ constexpr int xg_region(int bxt) { return xg_h(bxt) + xg_a(bxt) + xg_c(); }
 constexpr int CTL_WORDS = 64;          // u32: arrivals per XCC [0..7], total [8]
 // byte offset of a_t row `row` (0..7) of worker `rank`, slot `slot`, in the a_t region
 __device__ __forceinline__ unsigned xg_a_off(unsigned rank, unsigned row, unsigned slot) { return (((slot * NW + rank) << 3) + row) * 8u; }
+// the same for words; and the byte offset of h_t chunk q (units 4 q .. 4 q + 3, q < 7) of (rank, slot) in the h_t region of words
+__device__ __forceinline__ unsigned xg_a_off_w(unsigned rank, unsigned row, unsigned slot) { return (((slot * NW + rank) << 3) + row) * 4u; }
+__device__ __forceinline__ unsigned xg_h_off_w(unsigned rank, unsigned slot, unsigned bxt, unsigned unit) { return (((rank * bxt + slot) << 5) + unit) * 4u; }
+// one fc1 row of step `tag` - 1 goes out, as a word or as a granule
+template <bool WORDS>
+__device__ __forceinline__ void xd_put_a(u64 *ga, unsigned rank, unsigned row, unsigned slot, float v, unsigned tag, int agent) {
+    if constexpr (WORDS) xd_put_word(ga, xg_a_off_w(rank, row, slot), xd_word_a(v, tag & 1u), agent);
+    else xd_put(ga, xg_a_off(rank, row, slot), ((u64)tag << 32) | __float_as_uint(v), agent);
+}
 
 // Placement, run by ONE thread per workgroup: which XCD am I on (xid), which of its workers am I (rank, a ticket)?  Waits, bounded, until
 // the whole grid has taken its tickets; false unless every XCD was dealt exactly `nw` workgroups (STATUS_MISPLACED is then set).  The
@@ -73,10 +95,27 @@ __device__ __forceinline__ void gran_load4(u64 (&v)[4], const u64 *base, unsigne
 }
 // Two 16-byte chunks 1 KB apart, each TWO neighbouring granules, each granule validated by its own tag as ever (its publisher wrote it
 // with one 8-byte store): from L2 an 8-byte sc1 access moves 0.54..0.70 of what a 16-byte one does.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef xd_u32x4 u32x4;
 __device__ __forceinline__ void gran_chunks2(u32x4 (&v)[2], const u64 *base, unsigned off) {
     asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %3 sc1\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024 sc1\n\ts_waitcnt vmcnt(0)"
                  : "=&v"(v[0]), "=&v"(v[1]) : "v"(off), "s"(base) : "memory");
+}
+// 16-byte chunks of four WORDS (ar_shared.h), one global_load_dwordx4 each: one chunk, or two in flight together.  A lane whose
+// offset is XD_NO_CHUNK (its chunk belongs to a slot this XCD does not run, or it has none) does not load and keeps what `v` held: the
+// statement narrows exec to the other lanes around the load and puts it back.
+constexpr unsigned XD_NO_CHUNK = 0xFFFFFFFFu;
+__device__ __forceinline__ void gran_load(u32x4 &v, const u64 *base, unsigned off) {
+    u64 ex;
+    asm volatile("s_nop 4\n\tv_cmp_ne_u32 vcc, -1, %2\n\ts_and_saveexec_b64 %1, vcc\n\tglobal_load_dwordx4 %0, %2, %3 sc1\n\t"
+                 "s_mov_b64 exec, %1\n\ts_waitcnt vmcnt(0)"
+                 : "+v"(v), "=&s"(ex) : "v"(off), "s"(base) : "memory", "vcc");
+}
+__device__ __forceinline__ void gran_load_pair(u32x4 &a, u32x4 &b, const u64 *base, unsigned off, unsigned off2) {
+    u64 ex;
+    asm volatile("s_nop 4\n\tv_cmp_ne_u32 vcc, -1, %3\n\ts_and_saveexec_b64 %2, vcc\n\tglobal_load_dwordx4 %0, %3, %5 sc1\n\t"
+                 "s_mov_b64 exec, %2\n\tv_cmp_ne_u32 vcc, -1, %4\n\ts_and_saveexec_b64 %2, vcc\n\tglobal_load_dwordx4 %1, %4, %5 sc1\n\t"
+                 "s_mov_b64 exec, %2\n\ts_waitcnt vmcnt(0)"
+                 : "+v"(a), "+v"(b), "=&s"(ex) : "v"(off), "v"(off2), "s"(base) : "memory", "vcc");
 }
 // 2 N granules: N at `off` + i STEP and N at `off2` + i STEP, all in flight together
 template <int N, int STEP>
@@ -116,18 +155,34 @@ __device__ __forceinline__ void gran_load(u64 (&v)[N], const u64 *base, unsigned
         : "+v"(acc)                                                                                                      \
         : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]), "v"(h[4]), "v"(h[5]), "v"(h[6]), "v"(h[7]),                       \
           "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]))
+// the same on |h|: a_t exchange words carry the step's parity in their sign bit (ar_shared.h), and a_t = max(0, .) has none of its own
+#define XD_FMAC8A(J)                                                                                                     \
+    asm("v_fmac_f32_dpp %0, |%1|, %9 " XD_QP(J) "\n\tv_fmac_f32_dpp %0, |%2|, %10 " XD_QP(J) "\n\t"                    \
+        "v_fmac_f32_dpp %0, |%3|, %11 " XD_QP(J) "\n\tv_fmac_f32_dpp %0, |%4|, %12 " XD_QP(J) "\n\t"                   \
+        "v_fmac_f32_dpp %0, |%5|, %13 " XD_QP(J) "\n\tv_fmac_f32_dpp %0, |%6|, %14 " XD_QP(J) "\n\t"                   \
+        "v_fmac_f32_dpp %0, |%7|, %15 " XD_QP(J) "\n\tv_fmac_f32_dpp %0, |%8|, %16 " XD_QP(J)                          \
+        : "+v"(acc)                                                                                                      \
+        : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]), "v"(h[4]), "v"(h[5]), "v"(h[6]), "v"(h[7]),                       \
+          "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]))
 #define XD_FMAC4(J)                                                                                                      \
     asm("v_fmac_f32_dpp %0, %1, %5 " XD_QP(J) "\n\tv_fmac_f32_dpp %0, %2, %6 " XD_QP(J) "\n\t"                         \
         "v_fmac_f32_dpp %0, %3, %7 " XD_QP(J) "\n\tv_fmac_f32_dpp %0, %4, %8 " XD_QP(J)                                \
         : "+v"(acc)                                                                                                      \
         : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]), "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]))
 // terms 8 J .. 8 J + 7 of a 32-term phase: operands h[0..7] as held by quad lane J, weights w[0..7]
-template <int J>
+template <int J, bool ABS = false>
 __device__ __forceinline__ void fmac8(float &acc, const float *h, const float *w) {
-    if constexpr (J == 0) XD_FMAC8(0);
-    if constexpr (J == 1) XD_FMAC8(1);
-    if constexpr (J == 2) XD_FMAC8(2);
-    if constexpr (J == 3) XD_FMAC8(3);
+    if constexpr (ABS) {
+        if constexpr (J == 0) XD_FMAC8A(0);
+        if constexpr (J == 1) XD_FMAC8A(1);
+        if constexpr (J == 2) XD_FMAC8A(2);
+        if constexpr (J == 3) XD_FMAC8A(3);
+    } else {
+        if constexpr (J == 0) XD_FMAC8(0);
+        if constexpr (J == 1) XD_FMAC8(1);
+        if constexpr (J == 2) XD_FMAC8(2);
+        if constexpr (J == 3) XD_FMAC8(3);
+    }
 }
 template <int J>
 __device__ __forceinline__ void fmac4(float &acc, const float *h, const float *w) {

@@ -16,6 +16,7 @@ typedef unsigned long long u64;
 constexpr unsigned STATUS_TIMEOUT = 1u;      // an in-kernel exchange timed out
 constexpr unsigned STATUS_MISPLACED = 2u;    // the resident decoders' workgroups were not dealt 32 per XCD (nothing written)
 constexpr unsigned STATUS_BAD_INDEX = 4u;    // a code index or speaker id outside its embedding table
+constexpr unsigned STATUS_RANGE = 8u;        // a hidden value that a 4-byte exchange word cannot carry (non-finite or |h| >= 2: xd_word_h)
 
 // ---- launch-per-step recurrences (vocoder.hip's sample loop, scan.hip's sequence scans): weights in fragment order
 // (scan.hip, build_wfrag_kernel), one 16-row x 16-utterance MFMA tile per workgroup, K split over 4 waves.
@@ -230,6 +231,56 @@ __device__ __forceinline__ void xd_put4(u64 *base, unsigned byte_off, u64 v0, u6
     else asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %5 sc0\n\tglobal_store_dwordx2 %0, %2, %5 offset:%6 sc0\n\t"
                       "global_store_dwordx2 %0, %3, %5 offset:%7 sc0\n\tglobal_store_dwordx2 %0, %4, %5 offset:%8 sc0"
                       :: "v"(byte_off), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(base), "i"(STEP), "i"(2 * STEP), "i"(3 * STEP) : "memory");
+}
+
+// ---- 4-byte exchange WORDS (ar_xcd.hip, the instantiations xd_words() names in ar_chain.h): the value's own bits with ONE spare bit
+// replaced by the parity of the step, (t + 1) & 1 -- the low bit of what the 8-byte granules carry as their tag.  Half the bytes of a
+// granule, and four values per 16-byte load.  The spare bits: h_t is a convex combination of values in [-1, 1], so |h| < 2 and bit 30 of
+// its fp32 image (the exponent's top bit) is 0; a_t = max(0, .) is neither negative nor NaN, so bit 31 is 0 (-0 never gets there:
+// max(0, -0) and `v > 0 ? v : 0` give +0 -- and if it did, the cleared bit would make it +0, which no fmaf into an accumulator that
+// started at +0 can tell from -0).
+// Why one bit is enough.  A worker publishes h_t only after it has picked x_{t-1}; that pick needs every worker's candidate of step
+// t - 1; a worker publishes its candidate only after its own gathers of h_{t-1} and a_{t-1} are complete.  So when ANY word of step t
+// is written, every reader has finished with step t - 1, and a reader looking for step t has already seen step t - 1 at that address:
+// the location holds step t - 1 (the other parity) or step t, nothing older -- the sc1 loads are served by L2, where a location does
+// not go backwards.  The same chain holds for a_t (published behind the gather of h_t, which is behind x_{t-1}).  The launcher zeroes
+// the area, so an untouched word reads parity 0 and the first step (t = 0) publishes parity 1; a call that aborts leaves the kernel,
+// and the next launch zeroes the area again.
+// A hidden value with bit 30 set -- NaN, +-inf or |h| >= 2, from non-finite weights or conditioning or a resumed h_in -- does not fit:
+// xd_word_h_fits says so, and the publisher ends the call (STATUS_RANGE) as a timeout would.
+constexpr unsigned XD_HBIT = 1u << 30, XD_ABIT = 1u << 31;
+__device__ __forceinline__ unsigned xd_word_h(float v, unsigned parity) { return (__float_as_uint(v) & ~XD_HBIT) | (parity << 30); }
+__device__ __forceinline__ bool xd_word_h_fits(float v) { return (__float_as_uint(v) & XD_HBIT) == 0u; }
+__device__ __forceinline__ bool xd_word_h_ok(unsigned w, unsigned parity) { return ((w >> 30) & 1u) == parity; }
+__device__ __forceinline__ float xd_word_h_value(unsigned w) { return __uint_as_float(w & ~XD_HBIT); }
+__device__ __forceinline__ unsigned xd_word_a(float v, unsigned parity) { return (__float_as_uint(v) & ~XD_ABIT) | (parity << 31); }
+__device__ __forceinline__ bool xd_word_a_fits(float v) { return (__float_as_uint(v) & XD_ABIT) == 0u; }
+__device__ __forceinline__ bool xd_word_a_ok(unsigned w, unsigned parity) { return (w >> 31) == parity; }
+__device__ __forceinline__ float xd_word_a_value(unsigned w) { return __uint_as_float(w & ~XD_ABIT); }
+// The four words of a 16-byte chunk, each validated by its own bit, with as few vector instructions as it takes: the sweeps run on
+// SIMDs whose issue ports the other waves' matrix chains keep busy, where every vector instruction costs 10..20 ns
+// (profiles/r15_ab_exchange_words.txt: 13 per chunk instead of 8 gave the format's whole gain back).
+// h_t: x = word ^ (parity << 30) IS xd_word_h_value(word) if xd_word_h_ok(word, parity) -- the bit is cleared -- and has bit 30 set
+// if the word is of the other parity: four xors open the chunk, xd_chunk_h_ok tests the four bits at once.
+typedef unsigned xd_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ xd_u32x4 xd_chunk_h_open(const xd_u32x4 &w, unsigned parity) {
+    const unsigned pb = parity << 30;
+    return xd_u32x4{w[0] ^ pb, w[1] ^ pb, w[2] ^ pb, w[3] ^ pb};
+}
+__device__ __forceinline__ bool xd_chunk_h_ok(const xd_u32x4 &x) { return ((x[0] | x[1] | x[2] | x[3]) & XD_HBIT) == 0u; }
+// a_t: the bit is the sign, and the reader's products take |word| (fmac8a, ar_chain.h), so the words are used as they are; the four
+// xd_word_a_ok at once: parity 1 <=> the AND of the four is negative, parity 0 <=> their OR is not (`parity` is wave-uniform)
+__device__ __forceinline__ bool xd_chunk_a_ok(const xd_u32x4 &w, unsigned parity) {
+    return parity ? (int)(w[0] & w[1] & w[2] & w[3]) < 0 : (int)(w[0] | w[1] | w[2] | w[3]) >= 0;
+}
+// one word / one chunk of four published with one store, addressed and scoped as xd_put
+__device__ __forceinline__ void xd_put_word(u64 *base, unsigned byte_off, unsigned w, int agent) {
+    if (agent) asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2 sc1" :: "v"(byte_off), "v"(w), "s"(base) : "memory");
+    else asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2 sc0" :: "v"(byte_off), "v"(w), "s"(base) : "memory");
+}
+__device__ __forceinline__ void xd_put_chunk(u64 *base, unsigned byte_off, xd_u32x4 w, int agent) {
+    if (agent) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1" :: "v"(byte_off), "v"(w), "s"(base) : "memory");
+    else asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc0" :: "v"(byte_off), "v"(w), "s"(base) : "memory");
 }
 
 struct Waiter {                      // bounded spinning shared by all sweeps of the kernel

@@ -35,11 +35,17 @@
 //                -> publish a_t; W_hh rows 80..83 for the OTHER wave's slots (one chain pass: a half wave per slot); the
 //                next step's Gumbel noise (Philox + two logs per class); x_t from the slot's 32 candidates, picked up
 //                before barrier B
-//   all waves    sweep h_t into LDS (four slots: the chain waves, which publish nothing, nap first -- XD_HNAP -- so that their first round
-//                is not issued before the data can exist)
+//   all waves    sweep h_t into LDS (four slots: the chain waves only, which publish nothing and nap first -- XD_HNAP -- so that their
+//                first round is not issued before the data can exist)
 // Exchange regions of an XCD (ar_chain.h): h_t [rank][slot][32 units], swept with 8-byte loads; a_t [slot][rank][8] -- a slot's 256
 // granules in one run, which a lane of the slot's fc2 wave takes as two 16-byte loads of two granules each; candidates [slot][rank].
 // Every granule is published by one 8-byte store and validated by its own tag, whatever the width of the load that fetched it.
+// Four slots per XCD: h_t travels as 4-byte WORDS instead -- the value's bits with bit 30, which |h| < 2 leaves free, replaced by the
+// step's parity (ar_shared.h: xd_word_h, and why one bit is enough).  A (rank, slot) pair is one 128-byte line, a publisher's half wave
+// still writes one contiguous run (112 bytes), and a sweeping lane takes a 16-byte chunk of four units with ONE global_load_dwordx4,
+// each word validated by its own bit: 14.3 KB per CU and step instead of 28.7, one load instruction per chain wave instead of four.
+// The chain waves take all of it (XD_SVC_SWEEP below).  A hidden value the word cannot carry ends the call (STATUS_RANGE).  a_t can
+// be built the same way (XD_WORDS_A, ar_chain.h) and is not: it measured slower.
 // Four slots per XCD, what differs: every wave runs ONE dependent chain of 112 matrix instructions per step (waves 2..11 rows
 // 0..79 with pinned weights, wave 0 fc1 for all four slots -- its four accumulators combined, biased, rectified and stored together
 // (fc1_finish4, xd_put4) -- and wave 1 W_hh rows 80..83, both with weights streamed from LDS);
@@ -137,6 +143,19 @@ extern "C" int vqcpc_debug_xd_polls(unsigned *out) {
 #ifndef XD_HNAP
 #define XD_HNAP 10
 #endif
+// four slots per XCD, words: who sweeps h_t.  XD_SVC_SWEEP 0: the service waves do not -- between their h_t store and barrier A they are the
+// last of the workgroup (they publish, post the next step's state and only then would load), so every chunk they take, with its
+// validation and its LDS stores, is on the step's critical path; the ten chain waves, which wait behind their nap anyway, take all
+// 896 chunks: one per thread, and the threads of waves XD_HX .. XD_HX + 3 a second one.  1: every thread takes one chunk and the
+// threads of waves XD_HX, XD_HX + 1 a second (XD_HX 0: the granules' shape).  At 32 utterances, us per step: granules 3.21;
+// words with the service waves' two chunks each 3.18; their second chunk on waves 10 / 11 instead 3.12; no sweep on the service
+// waves and the second chunks on waves 2..5 / 4..7 / 6..9 / 8..11: 3.05 / 3.15 / 3.14 / 3.12 (profiles/r15_ab_exchange_words.txt).
+#ifndef XD_SVC_SWEEP
+#define XD_SVC_SWEEP 0
+#endif
+#ifndef XD_HX
+#define XD_HX 2
+#endif
 
 namespace {
 
@@ -165,6 +184,7 @@ template <int BXT, bool RESUME>
 __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &rp) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using L = Lds<BXT>;
+    constexpr bool W = xd_words_h(BXT), WA = xd_words_a(BXT);      // h_t / a_t travel as 4-byte words (ar_shared.h), not as 8-byte granules
     float *gemb = smem + L::gemb, *fc1w = smem + L::fc1w, *fc2w = smem + L::fc2w, *whx = smem + L::whx, *hc = smem + L::hc,
           *ac = smem + L::ac, *gsum = smem + L::gsum;
     float *noise = smem + L::noise, *mtab = smem + L::mtab, *c_bq = smem + L::bq;
@@ -237,24 +257,74 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
     const unsigned hdst1 = BXT == 4 ? chain_pos_plain<HR / 64>(hk1, NT_H) : chain_pos<HR / 64>(hk1, NT_H),
                    hdst2 = BXT == 4 ? chain_pos_plain<HR / 64>(hk2, NT_H) : chain_pos<HR / 64>(hk2, NT_H);
     const bool two = tid < HR - THREADS;
+    // words: the sweep deals 16-byte chunks, each four consecutive units of one (rank, slot): chunk c = (rank * BXT + slot) * 7 + q holds
+    // units 4 q .. 4 q + 3, so a wave's 64 chunks are consecutive in memory (but for the unused eighth chunk of a line).  Thread tid takes
+    // chunk tid, threads 0..127 of four slots also chunk 768 + tid: the shape above, with chunks in place of columns.  A chunk of a slot
+    // this XCD does not run is not loaded.  In hc a chunk's units 1 and 3 are the next chain's (NT_H further), unit 2 sits at wd*b.
+    constexpr unsigned NCH = NW * BXT * 7;
+    unsigned woff1 = XD_NO_CHUNK, woff2 = XD_NO_CHUNK, wd1 = 0, wd1b = 0, wd2 = 0, wd2b = 0;
+    constexpr bool SVC = !(W && BXT == 4 && XD_SVC_SWEEP == 0);      // the service waves take part in the sweep
+    constexpr unsigned NT1 = SVC ? THREADS : THREADS - 128u;        // threads with a first chunk; the next NCH - NT1 chunks are second chunks
+    const unsigned ct = SVC ? tid : tid - 128u;
+    const bool hx2 = NCH > NT1 && wave >= XD_HX && wave < XD_HX + (int)((NCH - NT1) / 64u);      // this wave's threads take a second chunk
+    if constexpr (W) {
+        auto chunk = [&](unsigned c, unsigned &off, unsigned &d0, unsigned &d2) {
+            const unsigned rs = c / 7u, q = c - 7u * rs, r = rs / BXT, b = rs - r * BXT, k0 = UPB * r + 4u * q;
+            if (c < NCH && (int)b < bx) off = xg_h_off_w(r, b, BXT, 4u * q);
+            d0 = b * L::HS + (BXT == 4 ? chain_pos_plain<HR / 64>(k0, NT_H) : chain_pos<HR / 64>(k0, NT_H));
+            d2 = BXT == 4 ? d0 + 4u : b * L::HS + chain_pos<HR / 64>(k0 + 2, NT_H);
+        };
+        if (SVC || wave >= 2) chunk(ct, woff1, wd1, wd1b);
+        if (hx2) chunk(NT1 + tid - 64u * XD_HX, woff2, wd2, wd2b);
+    }
+    static_assert(!(W && (XD_ABLATE & 8)), "XD_ABLATE bit 3 is a proxy on the granule format");
+    // XD_ABLATE bit 3 (granules, four slots; timing only): the sweep loads and checks slots 0 and 1, the other two columns of hc keep
+    // what they held -- half the sweep's bytes and instructions, an upper bound on what the words can return (profiles/r15_ab_exchange_words.txt)
+    constexpr int NL = (BXT == 4 && (XD_ABLATE & 8)) ? 2 : BXT;
 #define XD_SWEEP_H()                                                                                              \
     do {                                                                                                          \
-        u64 v1[BXT], v2[BXT];                                                                                     \
         if (BXT == 4 && XD_HNAP > 0 && wave >= 2) __builtin_amdgcn_s_sleep(XD_HNAP);                              \
         wt.start();                                                                                               \
-        for (unsigned spins = 0;; ++spins) {                                                                      \
-            bool ok = true;                                                                                       \
-            if (wave < 2) {                                                                                       \
-                gran_load_pair<BXT, 256>(v1, v2, gh, hoff1, hoff2);                                               \
-                _Pragma("unroll") for (int b = 0; b < BXT; ++b) ok &= b >= bx || (unsigned)(v2[b] >> 32) == tag;  \
-            } else gran_load<BXT, 256>(v1, gh, hoff1);                                                            \
-            _Pragma("unroll") for (int b = 0; b < BXT; ++b) ok &= b >= bx || (unsigned)(v1[b] >> 32) == tag;      \
-            if ((XD_ABLATE & 4) || __all(ok)) { XD_POLLS(0, spins); break; }                                      \
-            if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }                                                 \
-            __builtin_amdgcn_s_sleep(1);                                                                          \
-        }                                                                                                         \
-        _Pragma("unroll") for (int b = 0; b < BXT; ++b) {                                                         \
-            if (b < bx) { hc[b * L::HS + hdst1] = __uint_as_float((unsigned)v1[b]); if (two) hc[b * L::HS + hdst2] = __uint_as_float((unsigned)v2[b]); } \
+        if constexpr (W) {                                                                                        \
+            const unsigned par = tag & 1u;                                                                        \
+            u32x4 c1 = {0u, 0u, 0u, 0u}, c2 = {0u, 0u, 0u, 0u};                                                   \
+            for (unsigned spins = 0;; ++spins) {                                                                  \
+                bool ok = true;                                                                                   \
+                if (hx2) {                                                                                        \
+                    gran_load_pair(c1, c2, gh, woff1, woff2);                                                     \
+                    c2 = xd_chunk_h_open(c2, par);                                                                \
+                    ok = (woff2 == XD_NO_CHUNK) | xd_chunk_h_ok(c2);                                              \
+                } else gran_load(c1, gh, woff1);                                                                  \
+                c1 = xd_chunk_h_open(c1, par);                                                                    \
+                ok &= (woff1 == XD_NO_CHUNK) | xd_chunk_h_ok(c1);                                                 \
+                if ((XD_ABLATE & 4) || __all(ok)) { XD_POLLS(0, spins); break; }                                  \
+                if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }                                \
+                __builtin_amdgcn_s_sleep(1);                                                                      \
+            }                                                                                                     \
+            if (woff1 != XD_NO_CHUNK) {                                                                           \
+                hc[wd1] = __uint_as_float(c1[0]); hc[wd1 + NT_H] = __uint_as_float(c1[1]);                        \
+                hc[wd1b] = __uint_as_float(c1[2]); hc[wd1b + NT_H] = __uint_as_float(c1[3]);                      \
+            }                                                                                                     \
+            if (hx2 && woff2 != XD_NO_CHUNK) {                                                                    \
+                hc[wd2] = __uint_as_float(c2[0]); hc[wd2 + NT_H] = __uint_as_float(c2[1]);                        \
+                hc[wd2b] = __uint_as_float(c2[2]); hc[wd2b + NT_H] = __uint_as_float(c2[3]);                      \
+            }                                                                                                     \
+        } else {                                                                                                  \
+            u64 v1[NL], v2[NL];                                                                                   \
+            for (unsigned spins = 0;; ++spins) {                                                                  \
+                bool ok = true;                                                                                   \
+                if (wave < 2) {                                                                                   \
+                    gran_load_pair<NL, 256>(v1, v2, gh, hoff1, hoff2);                                            \
+                    _Pragma("unroll") for (int b = 0; b < NL; ++b) ok &= b >= bx || (unsigned)(v2[b] >> 32) == tag; \
+                } else gran_load<NL, 256>(v1, gh, hoff1);                                                         \
+                _Pragma("unroll") for (int b = 0; b < NL; ++b) ok &= b >= bx || (unsigned)(v1[b] >> 32) == tag;   \
+                if ((XD_ABLATE & 4) || __all(ok)) { XD_POLLS(0, spins); break; }                                  \
+                if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }                                \
+                __builtin_amdgcn_s_sleep(1);                                                                      \
+            }                                                                                                     \
+            _Pragma("unroll") for (int b = 0; b < NL; ++b) {                                                      \
+                if (b < bx) { hc[b * L::HS + hdst1] = __uint_as_float((unsigned)v1[b]); if (two) hc[b * L::HS + hdst2] = __uint_as_float((unsigned)v2[b]); } \
+            }                                                                                                     \
         }                                                                                                         \
     } while (0)
 
@@ -283,7 +353,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 float v = chain_combine(chain_regs<NT_H>(w1, opnd));
                 v += b1;
                 v = v > 0.f ? v : 0.f;
-                if (sum_lane) xd_put(ga, xg_a_off((unsigned)rank, r8, 0u), ((u64)tag << 32) | __float_as_uint(v), agent);
+                if (sum_lane) xd_put_a<WA>(ga, (unsigned)rank, r8, 0u, v, tag, agent);
                 XD_STAMP(1, 10);
                 XD_BARRIVE();
                 ps_barrier();                                            // B
@@ -329,8 +399,24 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 asm volatile("" : "+v"(lno));      // opaque, and rebuilt: the hoisted address of this read -- then r8, then the lane id
                 const unsigned r8o = ((lno >> 5) << 2) | (lno & 3u);      // itself -- was spilled to scratch and reloaded at every step
                 const float nz = noise[(t & 1) * (BXT * 8) + fs * 8 + r8o];
-                u32x4 va[2];
                 wt.start();
+                if constexpr (WA) {
+                    // words: the slot's run is 1 KB, the lane's chunk a_t[4 lane .. 4 lane + 3] -- one load; a_t[k + 1] is the chain next
+                    // door (48 further), a_t[k + 2] the second operand word of the same phase (16 further).  The words go into LDS as they are: fc2 takes |word|
+                    const unsigned aoffw = xg_a_off_w(0u, 0u, (unsigned)fs) + lane * 16u;
+                    const unsigned adw = (unsigned)chain_pos<HF / 64>(4 * (int)lane, 48);
+                    u32x4 vw = {0u, 0u, 0u, 0u};
+                    for (unsigned spins = 0;; ++spins) {
+                        gran_load(vw, ga, aoffw);
+                        if ((XD_ABLATE & 2) || __all(xd_chunk_a_ok(vw, tag & 1u))) { XD_POLLS(1, spins); break; }
+                        if (wt.expired(spins, lane, s_abort + 1)) { *s_abort = 1; break; }
+                    }
+                    ac[fs * (8 * 48) + adw] = __uint_as_float(vw[0]);
+                    ac[fs * (8 * 48) + 48 + adw] = __uint_as_float(vw[1]);
+                    ac[fs * (8 * 48) + 16 + adw] = __uint_as_float(vw[2]);
+                    ac[fs * (8 * 48) + 64 + adw] = __uint_as_float(vw[3]);
+                } else {
+                u32x4 va[2];
                 for (unsigned spins = 0;; ++spins) {
                     gran_chunks2(va, ga, aoff);
                     const bool ok = va[0][1] == tag && va[0][3] == tag && va[1][1] == tag && va[1][3] == tag;
@@ -342,6 +428,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     ac[fs * (8 * 48) + 192 * i + adst] = __uint_as_float(va[i][0]);
                     ac[fs * (8 * 48) + 192 * i + 48 + adst] = __uint_as_float(va[i][2]);
                 }
+                }
                 XD_STAMP(2, 8);
                 const float4 a0 = *(const float4 *)opnd2, a1 = *(const float4 *)(opnd2 + 16);
                 const float hv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -351,10 +438,10 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     float4 na = wa, nb2 = wb;
                     if (J < 3) { na = wp2[64 * (2 * J + 2)]; nb2 = wp2[64 * (2 * J + 3)]; }
                     const float w8[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
-                    if (J == 0) fmac8<0>(acc2, hv, w8);
-                    if (J == 1) fmac8<1>(acc2, hv, w8);
-                    if (J == 2) fmac8<2>(acc2, hv, w8);
-                    if (J == 3) fmac8<3>(acc2, hv, w8);
+                    if (J == 0) fmac8<0, WA>(acc2, hv, w8);                // words: |a_t| -- the sign bit is the parity
+                    if (J == 1) fmac8<1, WA>(acc2, hv, w8);
+                    if (J == 2) fmac8<2, WA>(acc2, hv, w8);
+                    if (J == 3) fmac8<3, WA>(acc2, hv, w8);
                     wa = na; wb = nb2;
                 }
                 float v2 = chain_combine(acc2);
@@ -521,6 +608,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
         ps_barrier();                                                    // state and noise of step 0 posted
 
         int x = NC / 2;
+        float hsent = 0.f;                                               // words: the h_t this lane published at step t
         for (int t = 0; t < n_steps; ++t) {
             const unsigned tag = (unsigned)t + 1u;
             __builtin_amdgcn_s_setprio(3);
@@ -547,7 +635,10 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     if (st_prime && cu < UPB) { hn = st_hin; hprev = hn; }
                     if (st_last && rp.h_out && cu < UPB) rp.h_out[(size_t)st_row * HR + UPB * rank + cu] = hn;
                 }
-                if (cu < UPB) xd_put(gh, (((unsigned)(rank * BXT + cb) << 5) + cu) * 8u, ((u64)tag << 32) | __float_as_uint(hn), agent);
+                if constexpr (W) {
+                    if (cu < UPB) xd_put_word(gh, xg_h_off_w((unsigned)rank, (unsigned)cb, BXT, cu), xd_word_h(hn, tag & 1u), agent);
+                    hsent = hn;                                          // tested for its range where this wave has slack (below)
+                } else if (cu < UPB) xd_put(gh, (((unsigned)(rank * BXT + cb) << 5) + cu) * 8u, ((u64)tag << 32) | __float_as_uint(hn), agent);
             }
             XD_STAMP(0, 2); if (wave == 0) XD_WSTAMP(0);
             // ---- in the shadow of the h_t exchange: the sample x_{t-1} goes out (network_vocoder.py:78 output), the slot's state
@@ -560,7 +651,7 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
             float4 w1p[BXT == 4 ? 2 * XD_DEPTH : 8];                      // the first weights of what follows barrier A, requested in front of it
 #pragma unroll
             for (int i = 0; i < (BXT == 4 ? 2 * XD_DEPTH : 8); ++i) w1p[i] = (BXT == 4 && sv == 1) ? wpx[32 * i] : wp1[64 * i];      // four slots: wave 1 runs W_hh rows 80..83
-            XD_SWEEP_H();
+            if constexpr (SVC) XD_SWEEP_H();
             XD_STAMP(0, 3);
             XD_BARRIVE();
             ps_barrier();                                                // A: h_t in LDS
@@ -582,7 +673,11 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                     // statement of four stores 8 bytes apart (profiles/r13_ab_at_handoff.txt)
                     float v[4];
                     fc1_finish4(a4, b1q, v);
-                    if (sum_lane && (int)j < bx)
+                    if constexpr (WA) {              // the four rows are one 16-byte chunk of the slot's run: one store
+                        const unsigned par = tag & 1u;
+                        if (sum_lane && (int)j < bx)
+                            xd_put_chunk(ga, xg_a_off_w((unsigned)rank, 4u * rq, j), u32x4{xd_word_a(v[0], par), xd_word_a(v[1], par), xd_word_a(v[2], par), xd_word_a(v[3], par)}, agent);
+                    } else if (sum_lane && (int)j < bx)
                         xd_put4<8>(ga, xg_a_off((unsigned)rank, 4u * rq, j), ((u64)tag << 32) | __float_as_uint(v[0]), ((u64)tag << 32) | __float_as_uint(v[1]),
                                    ((u64)tag << 32) | __float_as_uint(v[2]), ((u64)tag << 32) | __float_as_uint(v[3]), agent);
 #if XD_HOLD
@@ -602,17 +697,26 @@ __device__ __forceinline__ void xcd_decoder(const XdParams &p, const XdResume &r
                 float v = chain_combine(accA);
                 v += b1;
                 v = v > 0.f ? v : 0.f;
-                if (sum_lane) xd_put(ga, xg_a_off((unsigned)rank, r8, (unsigned)sv), ((u64)tag << 32) | __float_as_uint(v), agent);
+                if (sum_lane) xd_put_a<WA>(ga, (unsigned)rank, r8, (unsigned)sv, v, tag, agent);
                 if (n_own > 1) {
                     float v2 = chain_combine(accB);
                     v2 += b1;
                     v2 = v2 > 0.f ? v2 : 0.f;
-                    if (sum_lane) xd_put(ga, xg_a_off((unsigned)rank, r8, (unsigned)sv + 2u), ((u64)tag << 32) | __float_as_uint(v2), agent);
+                    if (sum_lane) xd_put_a<WA>(ga, (unsigned)rank, r8, (unsigned)sv + 2u, v2, tag, agent);
                 }
             }
             XD_STAMP(0, 5); if (wave == 0) XD_WSTAMP(2);
             XD_STAMP(1, 10);
             __builtin_amdgcn_s_setprio(1);
+            // ---- words: was the h_t published above one the word can carry?  Tested HERE, where both service waves wait for the candidates --
+            // between the store and barrier A every vector instruction is on the step's critical path (0.03 us there).  If not, the call ends
+            // as on a timeout: this workgroup leaves at barrier B, the others when their next wait looks at the status word.
+            if constexpr (W) {
+                if (__any(cell_on && cu < UPB && !xd_word_h_fits(hsent))) {
+                    if (lane == 0) __hip_atomic_store(p.status, (unsigned)s_abort[1] | STATUS_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    *s_abort = 1;
+                }
+            }
             // ---- W_hh rows 80..83 of the OTHER wave's slots, behind the a_t exchange and the chain waves' fc2: one chain pass,
             // the lower half wave on slot 1 - sv, the upper half on slot 3 - sv
             if (BXT != 4 && xb0 < bx) {

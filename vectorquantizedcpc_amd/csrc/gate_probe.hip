@@ -44,3 +44,31 @@ extern "C" int vqcpc_probe_draw(const float *sc, int n, int *cls, unsigned *bits
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }
+
+// The resident decoders' 4-byte exchange words (xd_word_h / xd_word_a and their readers, ar_shared.h), element-wise over fp32 bit
+// patterns: for each pattern and each parity the word, whether the value fits, the parity bit as the reader sees it, and the value the
+// reader takes out.
+__global__ void __launch_bounds__(256) probe_words_kernel(const unsigned *__restrict__ bits, int n, int is_a, unsigned *__restrict__ out) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float v = __uint_as_float(bits[i]);
+        for (unsigned par = 0; par < 2; ++par) {
+            const unsigned w = is_a ? xd_word_a(v, par) : xd_word_h(v, par);
+            unsigned *o = out + ((size_t)par * 4) * n + i;
+            o[0] = w;
+            o[(size_t)n] = (is_a ? xd_word_a_fits(v) : xd_word_h_fits(v)) ? 1u : 0u;
+            // which parity the reader accepts: 0, 1, or 2 if it accepts both or none
+            const bool k0 = is_a ? xd_word_a_ok(w, 0u) : xd_word_h_ok(w, 0u), k1 = is_a ? xd_word_a_ok(w, 1u) : xd_word_h_ok(w, 1u);
+            o[2 * (size_t)n] = k0 == k1 ? 2u : (k1 ? 1u : 0u);
+            o[3 * (size_t)n] = __float_as_uint(is_a ? xd_word_a_value(w) : xd_word_h_value(w));
+        }
+    }
+}
+
+// bits (n) device uint32 -> out (2 parities, 4, n) uint32: rows word, fits, parity read back, value bits; enqueued on `stream`.
+extern "C" int vqcpc_probe_words(const unsigned *bits, int n, int is_a, unsigned *out, void *stream) {
+    VQ_REQUIRE(bits && out && n > 0, "vqcpc_probe_words: bad argument");
+    const int blocks = n / 256 + 1 < 4096 ? n / 256 + 1 : 4096;
+    hipLaunchKernelGGL(probe_words_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, bits, n, is_a, out);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}

@@ -264,6 +264,13 @@ static int status_check(vqcpc_vocoder *v, bool synced) {
         return VQCPC_ERR_HIP;
     }
     fall_back(v);
+    if (code & STATUS_RANGE) {         // as a timeout, but the launch path's own hand-offs are not in doubt: the fused fc2 launch stays
+        vq_set_error("decode aborted (%s): a non-finite or out-of-range hidden state (NaN, inf or |h| >= 2 -- from the weights, the conditioning "
+                     "or a resumed state) cannot travel in the resident decoders' exchange words (outputs of that call are incomplete); this handle "
+                     "now uses one launch per kernel and step, and re-arms after %d clean calls or set_option xcd -- repeat the call",
+                     which, REARM_CLEAN);
+        return VQCPC_ERR_HIP;
+    }
     if (v->fuse_fc2) { v->fuse_fc2 = 0; clear_graphs(v); }
     vq_set_error("decode aborted (%s): an in-kernel exchange timed out (outputs of that call are incomplete); this handle now uses one launch "
                  "per kernel and step, and re-arms after %d clean calls or set_option xcd / fuse_fc2 -- repeat the call", which, REARM_CLEAN);
