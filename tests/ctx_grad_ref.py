@@ -3,16 +3,13 @@ fp32 numpy restatements that show on the CPU that the judge rests on nothing the
 
 Reference: ``torch.nn.LSTM(D, H, batch_first=True).double()`` on the CPU -- what ``model.py:57`` constructs -- with the loss
 ``sum(c * G)`` for a seeded upstream ``G`` and gradients by autograd.  tests/golden/ctx_grad_pins.npz
-(``tools/gen_ctx_grad_golden.py``) pins it: 64 sampled elements, the sum and the sum of squares per tensor, within 1e-12 relative,
-and holds ``e_ref = max |G_ref32 - G_ref64|``, the same module's own fp32 CPU error, per tensor.
+(``tools/gen_ctx_grad_golden.py``) pins it and holds ``e_ref``, the same module's own fp32 CPU error, per tensor.
 
-Judge, per tensor (c, z, W_ih, W_hh, b), the same for every case: ``max |G - G64| <= 4 max(e_ref, 2^-24 max |G64|)`` (DESIGN 2.6,
-the rule of tests/cpc_grad_ref.py); where ``G64`` is identically zero the result must be exact ``+0``.  Nothing in it is measured
-on the code under test.
+Pins and judge, per tensor (c, z, W_ih, W_hh, b): tests/grad_judge.py.
 
 ``WIDE_CASES`` (tests/golden/ctx_grad_wide_pins.npz, the same tool): twelve more cases at D = 64 -- nine utterance tiles, row counts
 on and one past a slab edge, three tiles at H = 512, thirteen slabs at H = 64, 3 000 steps, the forward suite's ``stressed`` weight
-set, and upstream gradients that are zero but for late steps, as ``CPCLoss`` hands them over.  They are judged by the rule above and
+set, and upstream gradients that are zero but for late steps, as ``CPCLoss`` hands them over.  They are judged by that rule and
 by ``judge_steps``: the same rule per time step for ``c`` and ``dz``, ``max_{b,d} |G[:, t] - G64[:, t]| <= 4 max(e_ref[t], 2^-24
 max |G64[:, t]|)`` with ``e_ref[t]`` the fp32 CPU error of that step, so that a step whose values are orders of magnitude below the
 tensor's largest is held to its own size; a step whose float64 values are all zero must come back zero.  ``FAULTS``: mistakes
@@ -27,15 +24,15 @@ import numpy as np
 import torch
 
 import cpc_grad_ref
-from vectorquantizedcpc_amd import synth
+import grad_judge
+from grad_judge import U32
 
-U32 = 2.0 ** -24
 f32, f64 = np.float32, np.float64
 TENSORS = ("c", "z", "W_ih", "W_hh", "b")
 GRADS = TENSORS[1:]
-N_SAMPLES = 64
-PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ctx_grad_pins.npz")
-WIDE_PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ctx_grad_wide_pins.npz")
+PINS = os.path.join(grad_judge.GOLD, "ctx_grad_pins.npz")
+WIDE_PINS = os.path.join(grad_judge.GOLD, "ctx_grad_wide_pins.npz")
+POSITIONS = "ctx_grad/{name}/{tensor}/pins"    # the seed of a tensor's pinned samples
 STEP_TENSORS = ("c", "z")                      # (B, T, .): judged per time step as well, on the wide cases
 
 # name -> B, T, D, H, weight scale
@@ -70,12 +67,11 @@ WIDE_CASES = {
 ALL_WIDE = list(WIDE_CASES)
 CHAIN = "chain"                                # the composition with CPCLoss on small_odd
 
-_cases, _refs, _pins = {}, {}, None
+_cases, _refs = {}, {}
 
 
 def _u(name, shape, bound):
-    n = int(np.prod(shape))
-    return torch.from_numpy(((synth.uniform01("ctx_grad/" + name, n) * 2.0 - 1.0) * bound).astype(f32).reshape(shape))
+    return grad_judge.uniform("ctx_grad/" + name, shape, bound)
 
 
 def lstm_weights(name, D, H, scale=1):
@@ -142,45 +138,17 @@ def grads64(name):
     return _refs[name]
 
 
-def sample_positions(name, tensor, numel):
-    return synth.randint(f"ctx_grad/{name}/{tensor}/pins", (N_SAMPLES,), numel).numpy()
-
-
 def pins():
-    global _pins
-    if _pins is None:
-        _pins = {**np.load(PINS), **np.load(WIDE_PINS)}            # keys start with the case's name: the two files share none
-    return _pins
+    return grad_judge.load_pins(PINS, WIDE_PINS)
 
 
 def bound(name, tensor):
-    """The judge's right-hand side for one tensor of one case."""
-    p = pins()
-    return 4.0 * max(float(p[f"{name}_{tensor}_e_ref"]), U32 * float(p[f"{name}_{tensor}_max"]))
+    return grad_judge.bound(pins(), name, tensor)
 
 
 def judge(name, got, what):
-    """Every tensor of ``got`` (dict of arrays; missing or None = not asked for) against float64: prints each figure, then asserts."""
-    ref, p = grads64(name), pins()
-    bad = []
-    for k in ref:
-        if got.get(k) is None:
-            continue
-        a = np.asarray(got[k])
-        assert a.shape == ref[k].shape, (k, a.shape, ref[k].shape)
-        if not ref[k].any():                                         # identically zero: exact +0, bit for bit
-            ok = a.dtype == f32 and not a.view(np.uint32).any()
-            print(f"{what} {name} d{k}: reference identically zero, result all +0: {ok}")
-            if not ok:
-                bad.append((k, "not +0"))
-            continue
-        a = a.astype(f64)
-        err, e_ref = float(np.abs(a - ref[k]).max()), float(p[f"{name}_{k}_e_ref"])
-        print(f"{what} {name} {k}: max|G - G64| = {err:.3g}, e_ref = {e_ref:.3g}, ratio {err / e_ref if e_ref else float('inf'):.3f}, "
-              f"bound {bound(name, k):.3g}, max|G64| = {np.abs(ref[k]).max():.3g}")
-        if not (np.isfinite(a).all() and err <= bound(name, k)):
-            bad.append((k, err, bound(name, k)))
-    assert not bad, bad
+    ref = grads64(name)
+    grad_judge.judge(ref, pins(), name, got, what, list(ref))
 
 
 def step_max(a):

@@ -6,12 +6,10 @@ of LayerNorm / ReLU / Linear -- on the CPU in float64, with the loss ``sum(z_pre
 autograd.  ReLU makes the gradient piecewise, so the reference differentiates the branch the fp32 program took: the five ReLU masks
 come from the project's CPU oracle's fp32 forward (``oracle.conv1d_k4s2`` / ``layernorm`` / ``linear``, the bits of the GPU's
 stages) and are applied module by module in place of ``nn.ReLU``.  tests/golden/front_grad_pins.npz
-(``tools/gen_front_grad_golden.py``) pins it: 64 sampled elements, the sum and the sum of squares per tensor, within 1e-12 relative;
-it holds ``max |G64|`` and ``e_ref = max |G_ref32 - G_ref64|``, the same modules' own fp32 CPU error under the same masks, per tensor,
-and per case the number of mask elements in which the float64 run's own ReLUs differ from the forced ones.
+(``tools/gen_front_grad_golden.py``) pins it and holds ``e_ref``, the same modules' own fp32 CPU error under the same masks, per
+tensor, and per case the number of mask elements in which the float64 run's own ReLUs differ from the forced ones.
 
-Judge, per tensor, the same for every case: ``max |G - G64| <= 4 max(e_ref, 2^-24 max |G64|)``; where ``G64`` is
-identically zero the result must be exact ``+0``.  Nothing in it is measured on the code under test.
+Pins and judge, per tensor: tests/grad_judge.py.
 
 ``chain``: the whole training step on a small batch -- the modules above, the VQ step with the code indices of the fp32 forward
 forced (``model.py:147-150``), ``nn.LSTM`` and ``cpc_grad_ref.loss_torch`` with given negatives, ``loss = cpc + vq`` -- judged by
@@ -26,18 +24,19 @@ import torch
 
 import cpc_grad_ref
 import ctx_grad_ref
+import grad_judge
 import oracle
+from grad_judge import U32  # noqa: F401  (the GPU tests' own bounds read it from here)
 from vectorquantizedcpc_amd import synth
 
-U32 = 2.0 ** -24
 f32, f64 = np.float32, np.float64
 LN_IDS, FC_IDS = (0, 3, 6, 9, 12), (2, 5, 8, 11)
 # the 17 front-end tensors in the member order of vqcpc_encoder_front_weights, and their state_dict() names
 KEYS = ["conv"] + [f"ln_g{i}" for i in range(5)] + [f"ln_b{i}" for i in range(5)] + [f"fc{i}" for i in range(4)] + ["out_w", "out_b"]
 SD_NAMES = (["conv.weight"] + [f"encoder.{n}.weight" for n in LN_IDS] + [f"encoder.{n}.bias" for n in LN_IDS] +
             [f"encoder.{n}.weight" for n in FC_IDS] + ["encoder.14.weight", "encoder.14.bias"])
-N_SAMPLES = 64
-PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "front_grad_pins.npz")
+PINS = os.path.join(grad_judge.GOLD, "front_grad_pins.npz")
+POSITIONS = "front_grad/{name}/{tensor}/pins"          # the seed of a tensor's pinned samples
 
 # name -> B, T, in_channels, conv_mode, variant
 CASES = {
@@ -62,12 +61,11 @@ SMALL_CASES = [n for n in ALL_CASES if CASES[n][0] * (CASES[n][1] // 2) <= 64]  
 DEAD_LN = 2                                            # dead_units: encoder.6.bias
 CHAIN = "chain"
 
-_cases, _fwd, _refs, _pins = {}, {}, {}, None
+_cases, _fwd, _refs = {}, {}, {}
 
 
 def _u(name, shape, bound):
-    n = int(np.prod(shape))
-    return torch.from_numpy(((synth.uniform01("front_grad/" + name, n) * 2.0 - 1.0) * bound).astype(f32).reshape(shape))
+    return grad_judge.uniform("front_grad/" + name, shape, bound)
 
 
 def _base(name):
@@ -172,45 +170,21 @@ def grads64(name):
     return _refs[name]
 
 
-def sample_positions(name, tensor, numel):
-    return synth.randint(f"front_grad/{name}/{tensor}/pins", (N_SAMPLES,), numel).numpy()
-
-
 def pins():
-    global _pins
-    if _pins is None:
-        _pins = dict(np.load(PINS))
-    return _pins
+    return grad_judge.load_pins(PINS)
 
 
 def bound(name, tensor):
-    """The judge's right-hand side for one tensor of one case."""
-    p = pins()
-    return 4.0 * max(float(p[f"{name}_{tensor}_e_ref"]), U32 * float(p[f"{name}_{tensor}_max"]))
+    return grad_judge.bound(pins(), name, tensor)
+
+
+def tensors(name):
+    """The keys of a case's reference that are tensors (``differ`` is a count)."""
+    return [k for k in grads64(name) if k != "differ"]
 
 
 def judge(name, got, what, keys=None):
-    """Every tensor of ``got`` (dict of arrays; missing or None = not asked for) against float64: prints each figure, then asserts."""
-    ref, p = grads64(name), pins()
-    bad = []
-    for k in (keys or [k for k in ref if k != "differ"]):
-        if got.get(k) is None:
-            continue
-        a = np.asarray(got[k])
-        assert a.shape == ref[k].shape, (k, a.shape, ref[k].shape)
-        if not ref[k].any():                                         # identically zero: exact +0, bit for bit
-            ok = a.dtype == f32 and not a.view(np.uint32).any()
-            print(f"{what} {name} d{k}: reference identically zero, result all +0: {ok}")
-            if not ok:
-                bad.append((k, "not +0"))
-            continue
-        a = a.astype(f64)
-        err, e_ref = float(np.abs(a - ref[k]).max()), float(p[f"{name}_{k}_e_ref"])
-        print(f"{what} {name} d{k}: max|G - G64| = {err:.3g}, e_ref = {e_ref:.3g}, err / bound {err / bound(name, k):.3f}, "
-              f"bound {bound(name, k):.3g}, max|G64| = {np.abs(ref[k]).max():.3g}")
-        if not (np.isfinite(a).all() and err <= bound(name, k)):
-            bad.append((k, err, bound(name, k)))
-    assert not bad, bad
+    grad_judge.judge(grads64(name), pins(), name, got, what, keys or tensors(name))
 
 
 # ------------------------------------------------------------------ vq_bwd: the float64 formula

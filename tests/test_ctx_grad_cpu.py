@@ -16,6 +16,7 @@ import torch
 
 import cpc_grad_ref
 import ctx_grad_ref as R
+import grad_judge
 import vectorquantizedcpc_amd as V
 from vectorquantizedcpc_amd import _lib, cli, driver
 
@@ -26,14 +27,8 @@ ENTRIES = ("vqcpc_encoder_context_saved_bytes", "vqcpc_encoder_context_fwd", "vq
 # ------------------------------------------------------------------ reference
 @pytest.mark.parametrize("name", R.ALL_CASES + [R.CHAIN])
 def test_pins_reproduce_from_the_float64_reference(name):
-    ref, p = R.grads64(name), R.pins()
-    for k, G in ref.items():
-        top = float(p[f"{name}_{k}_max"])
-        assert abs(np.abs(G).max() - top) <= 1e-12 * top
-        samples = G.reshape(-1)[R.sample_positions(name, k, G.size)]
-        assert np.abs(samples - p[f"{name}_{k}_samples"]).max() <= 1e-12 * top, k
-        s, ss = p[f"{name}_{k}_sums"]
-        assert abs(G.sum() - s) <= 1e-12 * np.abs(G).sum() and abs((G ** 2).sum() - ss) <= 1e-12 * ss, k
+    ref = R.grads64(name)
+    grad_judge.check_pins(ref, R.pins(), name, list(ref), R.POSITIONS)
 
 
 @pytest.mark.parametrize("name", R.ALL_CASES)
@@ -66,18 +61,12 @@ def test_structure_of_the_reference():
 def test_wide_pins_reproduce_from_the_float64_reference(name):
     ref, p = R.grads64(name), R.pins()
     T = R.load(name)["T"]
-    for k, G in ref.items():
-        top = float(p[f"{name}_{k}_max"])
-        assert abs(np.abs(G).max() - top) <= 1e-12 * top
-        samples = G.reshape(-1)[R.sample_positions(name, k, G.size)]
-        assert np.abs(samples - p[f"{name}_{k}_samples"]).max() <= 1e-12 * top, k
-        s, ss = p[f"{name}_{k}_sums"]
-        assert abs(G.sum() - s) <= 1e-12 * np.abs(G).sum() and abs((G ** 2).sum() - ss) <= 1e-12 * ss, k
-        if k in R.STEP_TENSORS:
-            steps, e_ref = p[f"{name}_{k}_step_max"], p[f"{name}_{k}_step_e_ref"]
-            assert steps.shape == e_ref.shape == (T,)
-            assert (np.abs(R.step_max(G) - steps) <= 1e-12 * steps).all(), k       # step by step: a zero step is pinned as zero
-            assert steps.max() == top and e_ref.max() == float(p[f"{name}_{k}_e_ref"]), k
+    grad_judge.check_pins(ref, p, name, list(ref), R.POSITIONS)
+    for k in R.STEP_TENSORS:
+        steps, e_ref = p[f"{name}_{k}_step_max"], p[f"{name}_{k}_step_e_ref"]
+        assert steps.shape == e_ref.shape == (T,)
+        assert (np.abs(R.step_max(ref[k]) - steps) <= 1e-12 * steps).all(), k      # step by step: a zero step is pinned as zero
+        assert steps.max() == float(p[f"{name}_{k}_max"]) and e_ref.max() == float(p[f"{name}_{k}_e_ref"]), k
 
 
 def test_structure_of_the_wide_cases():

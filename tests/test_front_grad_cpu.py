@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import front_grad_ref as R
+import grad_judge
 from vectorquantizedcpc_amd import _lib, cli, driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,17 +21,9 @@ SMALL = [n for n in R.SMALL_CASES if not n.endswith(("_m1", "_m2"))]
 @pytest.mark.parametrize("name", R.ALL_CASES + [R.CHAIN])
 def test_pins_hold_the_float64_reference(name):
     ref, p = R.grads64(name), R.pins()
-    for k, G in ref.items():
-        if k == "differ":
-            assert int(p[f"{name}_differ"]) == G
-            continue
-        want = p[f"{name}_{k}_samples"]
-        got = G.reshape(-1)[R.sample_positions(name, k, G.size)]
-        scale = max(float(p[f"{name}_{k}_max"]), 1e-300)
-        assert np.abs(got - want).max() <= 1e-12 * scale, (name, k)
-        sums = np.array([G.sum(), (G ** 2).sum()])
-        assert np.abs(sums - p[f"{name}_{k}_sums"]).max() <= 1e-12 * max(1.0, np.abs(p[f"{name}_{k}_sums"]).max()) * G.size ** 0.5, (name, k)
-        assert abs(np.abs(G).max() - float(p[f"{name}_{k}_max"])) <= 1e-12 * scale
+    grad_judge.check_pins(ref, p, name, R.tensors(name), R.POSITIONS)
+    if "differ" in ref:
+        assert int(p[f"{name}_differ"]) == ref["differ"]
 
 
 def test_masks_of_the_small_cases_are_the_float64_run_s_own():

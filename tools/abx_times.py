@@ -24,6 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import _lib, abx, synth  # noqa: E402
 
 SPEAKERS, CONTEXTS, PHONES, PER_CELL = 8, 5, 10, 5          # 8 x 5 x 10 x 5 = 2 000 tokens
@@ -51,32 +52,6 @@ def workload():
     tok = abx.tokens_of(items, {f: feats[f].shape[0] for f in files})
     tokens = [(int(first[files.index(it.file)]) + lo, n) for it, (lo, n) in zip(items, tok)]
     return items, np.concatenate([feats[f] for f in files]), tokens, book.astype(np.float32), np.concatenate([idx[f] for f in files])
-
-
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def measure(variants, windows, target_ms):
-    reps = {}
-    for name, fn in variants.items():
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        one = window_ms(fn, 2)
-        reps[name] = max(1, int(target_ms / max(one, 1e-4)))
-        window_ms(fn, reps[name])
-    times = {name: [] for name in variants}
-    for _ in range(windows):
-        for name, fn in variants.items():
-            times[name].append(window_ms(fn, reps[name]))
-    return {n: (statistics.median(v), min(v), max(v), reps[n]) for n, v in times.items()}
 
 
 def fused_call(frames, tokens, blocks, dev):
@@ -243,7 +218,7 @@ def main():
         ttw = torch.cat([o.reshape(-1) for o in tout]).cpu().numpy()
         flop = sum(lens[a] * lens[x] for b in pl.blocks for a in b.a for x in b.x) * D * 8
         r = measure({FUSED: fused, INDEX: icall, EDIT: ecall, TABLE: build, "torch on the GPU (bmm + DP as torch ops)": lambda: tcall()},
-                    args.windows, args.window_ms)
+                    args.windows, args.window_ms, probe=2, min_reps=1)
         lines.append(f"\n{mode}: {len(pl.blocks)} blocks, {pl.n_pairs} pairs, {int(abx.aggregate(pl, got)['n_triples'])} triples, "
                      f"{flop / 1e9:.2f} GFLOP of frame distances")
         for name, (med, lo, hi, reps) in r.items():

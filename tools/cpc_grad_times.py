@@ -7,7 +7,7 @@ sum) against the eager composition's peak allocation.
 
     python tools/cpc_grad_times.py [--out profiles/cpc_grad_times.txt] [--windows 20] [--window-ms 40]
 
-Windows, alternation and the table are those of ``tools/cpc_times.py`` (median [min .. max] over the windows).
+Windows and alternation are those of ``tools/timing.py``, the table that of ``tools/cpc_times.py`` (median [min .. max] over the windows).
 """
 import argparse
 import os
@@ -19,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import vectorquantizedcpc_amd as V  # noqa: E402
-from cpc_times import SHAPES, eager_cpc, measure  # noqa: E402
+from cpc_times import SHAPES, eager_cpc  # noqa: E402
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import _lib, synth  # noqa: E402
 
 

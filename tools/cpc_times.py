@@ -13,7 +13,6 @@ import argparse
 import math
 import os
 import re
-import statistics
 import subprocess
 import sys
 
@@ -22,6 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import vectorquantizedcpc_amd as V  # noqa: E402
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import _lib, synth  # noqa: E402
 
 SHAPES = {"train_shape 8x8": (8, 8, 17, 70, 12), "8x larger 32x16": (32, 16, 17, 70, 12)}
@@ -47,33 +47,6 @@ def eager_cpc(weights, biases, z, c, Spk, Utt, Neg, K):
         losses.append(torch.nn.functional.cross_entropy(f, labels))
         accs.append((f.argmax(dim=1) == labels).float().mean())
     return torch.stack(losses).mean(), torch.stack(accs)
-
-
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def measure(variants, windows, target_ms):
-    """variants: name -> callable.  -> name -> (median, min, max) ms per call, reps per window."""
-    reps = {}
-    for name, fn in variants.items():
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        one = window_ms(fn, 10)
-        reps[name] = max(10, int(target_ms / max(one, 1e-4)))
-        window_ms(fn, reps[name])
-    times = {name: [] for name in variants}
-    for _ in range(windows):
-        for name, fn in variants.items():                    # the variants take turns
-            times[name].append(window_ms(fn, reps[name]))
-    return {n: (statistics.median(v), min(v), max(v), reps[n]) for n, v in times.items()}
 
 
 def main():

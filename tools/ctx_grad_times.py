@@ -7,7 +7,7 @@
 
     python tools/ctx_grad_times.py [--out profiles/ctx_grad_times.txt] [--windows 20] [--window-ms 40]
 
-Windows, alternation and the table are those of ``tools/cpc_times.py`` (median [min .. max] over the windows).
+Windows and alternation are those of ``tools/timing.py``, the table that of ``tools/cpc_times.py`` (median [min .. max] over the windows).
 """
 import argparse
 import os
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import vectorquantizedcpc_amd as V  # noqa: E402
-from cpc_times import measure  # noqa: E402
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import synth  # noqa: E402
 
 SHAPES = {"train_shape 64 x 70": (64, 70), "8x larger 512 x 70": (512, 70)}       # (B, T), z_dim 64 -> c_dim 256

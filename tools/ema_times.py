@@ -14,7 +14,6 @@ and the peak device memory the PyTorch composition allocates beside the work spa
 """
 import argparse
 import os
-import statistics
 import sys
 
 import torch
@@ -25,34 +24,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ema_ref  # noqa: E402
 import vectorquantizedcpc_amd as V  # noqa: E402
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import synth  # noqa: E402
 
 SHAPES = [(4096, 512), (33280, 1024)]
-
-
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def measure(variants, windows, target_ms):
-    reps = {}
-    for name, fn in variants.items():
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        reps[name] = max(1, int(target_ms / max(window_ms(fn, 3), 1e-4)))
-        window_ms(fn, reps[name])
-    times = {name: [] for name in variants}
-    for _ in range(windows):
-        for name, fn in variants.items():
-            times[name].append(window_ms(fn, reps[name]))
-    return {n: (statistics.median(v), min(v), max(v), reps[n]) for n, v in times.items()}
 
 
 class TorchEMA:
@@ -138,7 +113,7 @@ def main():
             "torch model.py:131-145 (distances given)", "torch model.py:123-155 (whole forward)"
         with torch.no_grad():
             r = measure({HIP: lambda: enc.codebook(x), EVAL: lambda: ev.codebook(x), T_UPD: lambda: ref_u.update(x, x_flat, dist),
-                         T_FWD: lambda: ref.forward(x)}, args.windows, args.window_ms)
+                         T_FWD: lambda: ref.forward(x)}, args.windows, args.window_ms, probe=3, min_reps=1)
         lines.append(f"\n{n_rows} rows x {n_emb} codes (skewed use: {len(set(case['code'].tolist()))} codes in use, the largest owns "
                      f"{int(max(torch.bincount(torch.from_numpy(case['code'])).tolist()))} rows)")
         for name, (med, lo, hi, reps) in r.items():

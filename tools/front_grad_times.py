@@ -8,7 +8,7 @@ forward + ``backward()`` in PyTorch eager fp32 on the same GPU, what a user woul
 
     python tools/front_grad_times.py [--out profiles/front_grad_times.txt] [--windows 20] [--window-ms 40]
 
-Windows, alternation and the table are those of ``tools/cpc_times.py`` (median [min .. max] over the windows).
+Windows and alternation are those of ``tools/timing.py``, the table that of ``tools/cpc_times.py`` (median [min .. max] over the windows).
 """
 import argparse
 import os
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import vectorquantizedcpc_amd as V  # noqa: E402
-from cpc_times import measure  # noqa: E402
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import synth  # noqa: E402
 
 SHAPES = {"train_shape 64 x 128 frames": (8, 8, 128), "8x larger 512 x 128 frames": (64, 8, 128)}     # speakers, utterances, mel frames

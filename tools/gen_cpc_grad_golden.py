@@ -9,7 +9,7 @@ predictors' gradients stacked, the other K stay ``None``) the file holds DATA on
     <case>_<tensor>_e_ref     max |G_ref32 - G_ref64|: the reference's own fp32 error, the yardstick of the judge
     <case>_<tensor>_max       max |G_ref64|
     <case>_<tensor>_sums      [sum G_ref64, sum G_ref64^2]
-    <case>_<tensor>_samples   G_ref64 at the 64 positions ``cpc_grad_ref.sample_positions`` draws with ``synth.randint``
+    <case>_<tensor>_samples   G_ref64 at the 64 positions ``grad_judge.sample_positions`` draws from ``cpc_grad_ref.POSITIONS``
     <case>_loss64             the float64 loss
 
 Usage:  python tools/gen_cpc_grad_golden.py
@@ -52,6 +52,7 @@ def reference_grads(model, g, double):
 
 def main():
     import cpc_grad_ref as R
+    import grad_judge
     torch.set_num_threads(1)
     model = import_reference()
     print("reference imported from", model.__file__, "| torch", torch.__version__)
@@ -61,13 +62,11 @@ def main():
         r32, r64 = reference_grads(model, g, False), reference_grads(model, g, True)
         mine = R.grads64(name)
         out[f"{name}_loss64"] = np.array(r64["loss"])
+        out.update(grad_judge.pin_entries(name, r64, r32, R.POSITIONS, R.TENSORS))
         line = [f"{name}: loss64 {r64['loss']:.9f}"]
         for k in R.TENSORS:
             assert r32[k].dtype == np.float32 and r64[k].dtype == np.float64
-            e_ref, top = float(np.abs(r32[k].astype(np.float64) - r64[k]).max()), float(np.abs(r64[k]).max())
-            out[f"{name}_{k}_e_ref"], out[f"{name}_{k}_max"] = np.array(e_ref), np.array(top)
-            out[f"{name}_{k}_sums"] = np.array([r64[k].sum(), (r64[k] ** 2).sum()])
-            out[f"{name}_{k}_samples"] = r64[k].reshape(-1)[R.sample_positions(name, k, r64[k].size)]
+            e_ref, top = float(out[f"{name}_{k}_e_ref"]), float(out[f"{name}_{k}_max"])
             line.append(f"d{k}: e_ref {e_ref:.3g} ({e_ref / top:.3g} of max|G| = {top:.3g}), restatement differs by "
                         f"{np.abs(mine[k] - r64[k]).max():.3g}")
         print("  ".join(line))

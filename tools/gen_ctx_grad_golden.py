@@ -11,7 +11,6 @@ tests/golden/ctx_grad_pins.npz: the nine cases and ``chain``; left as it is unle
 """
 import os
 import sys
-import zipfile
 
 import numpy as np
 import torch
@@ -20,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import ctx_grad_ref as R  # noqa: E402
+import grad_judge  # noqa: E402
 
 
 def pins_of(names, per_step):
@@ -27,11 +27,8 @@ def pins_of(names, per_step):
     for name in names:
         ref = R.grads64(name)
         low = R.chain_grads(torch.float32) if name == R.CHAIN else R.torch_grads(name, torch.float32)
-        for k, G in ref.items():
-            out[f"{name}_{k}_samples"] = G.reshape(-1)[R.sample_positions(name, k, G.size)]
-            out[f"{name}_{k}_sums"] = np.array([G.sum(), (G ** 2).sum()])
-            out[f"{name}_{k}_max"] = np.float64(np.abs(G).max())
-            out[f"{name}_{k}_e_ref"] = np.float64(np.abs(low[k] - G).max())
+        for k, G in ref.items():                                    # tensor by tensor: the archive keeps this order
+            out.update(grad_judge.pin_entries(name, ref, low, R.POSITIONS, [k]))
             print(f"{name} {k}: max {out[f'{name}_{k}_max']:.3g}, e_ref {out[f'{name}_{k}_e_ref']:.3g}")
             if per_step and k in R.STEP_TENSORS:
                 top, err = R.step_max(G), R.step_max(low[k] - G)
@@ -40,22 +37,13 @@ def pins_of(names, per_step):
     return out
 
 
-def write_npz(path, arrays):
-    """An uncompressed .npz as ``np.load`` reads it, with the archive's dates fixed (``np.savez`` stamps the time of writing)."""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as zf:
-        for key, value in arrays.items():
-            with zf.open(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
-                np.lib.format.write_array(f, np.asanyarray(value), allow_pickle=False)
-    print(f"wrote {path} ({os.path.getsize(path)} bytes)")
-
-
 def main():
     torch.set_num_threads(1)                                        # one summation order for the recorded fp32 error
     if "--nine" in sys.argv[1:]:
         out = pins_of(R.ALL_CASES + [R.CHAIN], per_step=False)
         np.savez(R.PINS, **out)
         print(f"wrote {R.PINS} ({os.path.getsize(R.PINS)} bytes)")
-    write_npz(R.WIDE_PINS, pins_of(R.ALL_WIDE, per_step=True))
+    grad_judge.write_npz(R.WIDE_PINS, pins_of(R.ALL_WIDE, per_step=True))
 
 
 if __name__ == "__main__":

@@ -10,7 +10,6 @@ The judges of the tests are built from these alone.  Data only; written with fix
 """
 import os
 import sys
-import zipfile
 
 import numpy as np
 import torch
@@ -19,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import front_grad_ref as R  # noqa: E402
+import grad_judge  # noqa: E402
 
 
 def pins_of(names):
@@ -26,26 +26,13 @@ def pins_of(names):
     for name in names:
         ref = R.grads64(name)
         low = R.chain_grads(torch.float32) if name == R.CHAIN else R.torch_grads(name, torch.float32)
-        for k, G in ref.items():
-            if k == "differ":
-                out[f"{name}_differ"] = np.int64(G)
-                print(f"{name}: {G} mask elements differ between the fp32 program and the float64 run")
-                continue
-            out[f"{name}_{k}_samples"] = G.reshape(-1)[R.sample_positions(name, k, G.size)]
-            out[f"{name}_{k}_sums"] = np.array([G.sum(), (G ** 2).sum()])
-            out[f"{name}_{k}_max"] = np.float64(np.abs(G).max())
-            out[f"{name}_{k}_e_ref"] = np.float64(np.abs(low[k] - G).max())
+        out.update(grad_judge.pin_entries(name, ref, low, R.POSITIONS, R.tensors(name)))
+        for k in R.tensors(name):
             print(f"{name} {k}: max {out[f'{name}_{k}_max']:.3g}, e_ref {out[f'{name}_{k}_e_ref']:.3g}")
+        if "differ" in ref:
+            out[f"{name}_differ"] = np.int64(ref["differ"])
+            print(f"{name}: {ref['differ']} mask elements differ between the fp32 program and the float64 run")
     return out
-
-
-def write_npz(path, arrays):
-    """An uncompressed .npz as ``np.load`` reads it, with the archive's dates fixed (``np.savez`` stamps the time of writing)."""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as zf:
-        for key, value in arrays.items():
-            with zf.open(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
-                np.lib.format.write_array(f, np.asanyarray(value), allow_pickle=False)
-    print(f"wrote {path} ({os.path.getsize(path)} bytes)")
 
 
 def main():
@@ -60,7 +47,7 @@ def main():
     assert all(np.array_equal(a, b) for a, b in zip(idx64, idx32)), "the fit's batch: float64 and fp32 pick different codes"
     out["chain_fit_vq_margin"] = np.float64(min(m64, m32))
     print(f"chain fit ({R.FIT_STEPS} steps, lr {R.FIT_LR}): the same codes at every step, smallest VQ margin {out['chain_fit_vq_margin']:.3g}")
-    write_npz(R.PINS, out)
+    grad_judge.write_npz(R.PINS, out)
 
 
 if __name__ == "__main__":

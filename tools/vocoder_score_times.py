@@ -14,7 +14,6 @@ csrc/nll.hip (compiles the file).
 """
 import argparse
 import os
-import statistics
 import subprocess
 import sys
 
@@ -24,34 +23,11 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import vectorquantizedcpc_amd as V  # noqa: E402
+from timing import measure  # noqa: E402
 from vectorquantizedcpc_amd import synth  # noqa: E402
 
 SHAPES = {"training shape (32, 5119)": (32, 5120, 16), "32 whole utterances of 32 000 samples": (32, 32000, 100)}
 FLOP_PER_SAMPLE = 2 * (896 * 256 + 256 * 256)
-
-
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def measure(variants, windows, target_ms):
-    reps = {}
-    for name, fn in variants.items():
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        reps[name] = max(1, int(target_ms / max(window_ms(fn, 1), 1e-3)))
-    times = {name: [] for name in variants}
-    for _ in range(windows):
-        for name, fn in variants.items():                    # the variants take turns
-            times[name].append(window_ms(fn, reps[name]))
-    return {n: (statistics.median(v), min(v), max(v), reps[n]) for n, v in times.items()}
 
 
 def fresh_vocoder(dev):
@@ -98,7 +74,7 @@ def main():
         la, lb = float(fused(voc)), float(composed(voc))
         assert abs(la - lb) < 1e-4, (la, lb)
         r = measure({"(a) Vocoder.nll": lambda: fused(voc), "(b) forward + F.cross_entropy": lambda: composed(voc)},
-                    args.windows, args.window_ms)
+                    args.windows, args.window_ms, probe=1, min_reps=1)
         flop = B * (L - 1) * FLOP_PER_SAMPLE
         lines.append(f"\n{label}: B {B}, L {L}, Tc {Tc}; head {flop / 1e9:.1f} GFLOP; loss (a) {la:.6f} (b) {lb:.6f}")
         for name, (med, lo, hi, reps) in r.items():

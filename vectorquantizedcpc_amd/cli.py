@@ -67,6 +67,7 @@ input carries no reference loudness and its output is written as generated.  Utt
 length-bucketed drivers; every output equals the batch-1 result.
 """
 import argparse
+import functools
 import sys
 from pathlib import Path
 
@@ -151,61 +152,53 @@ def score_dataset(args) -> int:
     return _print_score(args, *_score_setup(args))
 
 
-def fit_predictors_dataset(args) -> int:
+def _fit_dataset(args, fit, what, losses, encoder_update, wrote) -> int:
+    """The body of the three fit commands: score, ``fit(enc, cpc, by_speaker, ...)``, a summary line -- ``what(cpc)`` was fitted,
+    ``losses(r)`` closes it --, score again, and save with ``encoder_update(enc)`` (None: ``"encoder"`` stays as it was), which
+    ``wrote(enc, update)`` describes."""
     enc, cpc, by_speaker = _score_setup(args)
     print("before the fit:")
     if _print_score(args, enc, cpc, by_speaker):
         return 1
-    r = driver.fit_predictors(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed)
-    print(f"fitted {cpc.n_prediction_steps} predictors in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches: "
-          f"cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}")
+    r = fit(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed)
+    print(f"fitted {what(cpc)} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches{losses(r)}")
     print("after the fit:")
     rc = _print_score(args, enc, cpc, by_speaker)
+    update = encoder_update(enc)
     io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
-                              encoder_state=enc.state_dict() if args.random_init else None)
-    print(f"wrote {args.out_checkpoint}: \"encoder\" as it was, \"cpc\" replaced ({len(cpc.state_dict())} keys)")
+                              encoder_state=enc.state_dict() if args.random_init else None,
+                              encoder_update=None if args.random_init else update)
+    print(f"wrote {args.out_checkpoint}: {wrote(enc, update)}, \"cpc\" replaced ({len(cpc.state_dict())} keys)")
     return rc
+
+
+def _cpc_losses(r) -> str:
+    return f": cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}"
+
+
+def fit_predictors_dataset(args) -> int:
+    return _fit_dataset(args, driver.fit_predictors, lambda cpc: f"{cpc.n_prediction_steps} predictors", _cpc_losses,
+                        lambda enc: None, lambda enc, update: "\"encoder\" as it was")
 
 
 def fit_context_dataset(args) -> int:
-    enc, cpc, by_speaker = _score_setup(args)
-    print("before the fit:")
-    if _print_score(args, enc, cpc, by_speaker):
-        return 1
-    r = driver.fit_context(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed,
-                           train_predictors=not args.freeze_predictors)
-    what = "the context LSTM" + ("" if args.freeze_predictors else f" and {cpc.n_prediction_steps} predictors")
-    print(f"fitted {what} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches: "
-          f"cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}")
-    print("after the fit:")
-    rc = _print_score(args, enc, cpc, by_speaker)
-    rnn = {f"rnn.{k}": v for k, v in enc.rnn.state_dict().items()}
-    io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
-                              encoder_state=enc.state_dict() if args.random_init else None,
-                              encoder_update=None if args.random_init else rnn)
-    print(f"wrote {args.out_checkpoint}: \"encoder\" with rnn.* replaced ({len(rnn)} keys), \"cpc\" replaced ({len(cpc.state_dict())} keys)")
-    return rc
+    return _fit_dataset(args, functools.partial(driver.fit_context, train_predictors=not args.freeze_predictors),
+                        lambda cpc: "the context LSTM" + ("" if args.freeze_predictors else f" and {cpc.n_prediction_steps} predictors"),
+                        _cpc_losses, lambda enc: {f"rnn.{k}": v for k, v in enc.rnn.state_dict().items()},
+                        lambda enc, update: f"\"encoder\" with rnn.* replaced ({len(update)} keys)")
 
 
 def fit_encoder_dataset(args) -> int:
     train = tuple(t for t in args.train.split(",") if t)
-    enc, cpc, by_speaker = _score_setup(args)
-    print("before the fit:")
-    if _print_score(args, enc, cpc, by_speaker):
-        return 1
-    r = driver.fit_encoder(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed,
-                           adapt_codebook=not args.freeze_codebook, train=train)
-    print(f"fitted {', '.join(train)} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches, codebook "
-          f"{'frozen' if args.freeze_codebook else 'following'}: loss {r['losses'][0] + r['vq_losses'][0]:.6f} -> "
-          f"{r['losses'][-1] + r['vq_losses'][-1]:.6f} = cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f} + "
-          f"vq loss {r['vq_losses'][0]:.2E} -> {r['vq_losses'][-1]:.2E}")
-    print("after the fit:")
-    rc = _print_score(args, enc, cpc, by_speaker)
-    io.save_fitted_checkpoint(args.out_checkpoint, cpc.state_dict(), None if args.random_init else args.cpc_checkpoint,
-                              encoder_state=enc.state_dict() if args.random_init else None,
-                              encoder_update=None if args.random_init else enc.state_dict())
-    print(f"wrote {args.out_checkpoint}: \"encoder\" replaced ({len(enc.state_dict())} keys), \"cpc\" replaced ({len(cpc.state_dict())} keys)")
-    return rc
+
+    def losses(r):
+        return (f", codebook {'frozen' if args.freeze_codebook else 'following'}: loss {r['losses'][0] + r['vq_losses'][0]:.6f} -> "
+                f"{r['losses'][-1] + r['vq_losses'][-1]:.6f} = cpc loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f} + "
+                f"vq loss {r['vq_losses'][0]:.2E} -> {r['vq_losses'][-1]:.2E}")
+
+    return _fit_dataset(args, functools.partial(driver.fit_encoder, adapt_codebook=not args.freeze_codebook, train=train),
+                        lambda cpc: ", ".join(train), losses, lambda enc: enc.state_dict(),
+                        lambda enc, update: f"\"encoder\" replaced ({len(update)} keys)")
 
 
 def score_vocoder_dataset(args) -> int:

@@ -315,41 +315,71 @@ def fit_predictors(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int =
 
     Returns ``losses`` and ``accuracies`` (per step; reading them synchronises once per step), ``steps``, ``batches``,
     ``utterances`` and the speakers ``score_batches`` would name: ``speakers_skipped``, ``speakers_left_over``."""
-    K = cpc.n_prediction_steps
-    return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device,
-                [p for m in cpc.predictors[:K] for p in m.parameters()], lambda z, c: c)
+    return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, _predictor_params(cpc),
+                _encoded_step(cpc, seed, lambda z, c: c))
 
 
-def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params, context):
-    """The loop ``fit_predictors`` and ``fit_context`` share: the batches of ``_score_plan``, step i on batch ``i mod batches``,
-    every batch encoded once under ``no_grad`` and kept on the device, then per step ``context(z, c)`` -> the contexts the loss
-    reads, ``cpc(..., differentiable=True)``, ``backward()`` and one step of ``optimizer(params, lr=lr)``."""
+def _predictor_params(cpc):
+    """The parameters of the K predictors the loss reads."""
+    return [p for m in cpc.predictors[:cpc.n_prediction_steps] for p in m.parameters()]
+
+
+def _encoded_step(cpc, seed, context):
+    """The step of a fit on a frozen front end, for ``_fit``: ``context(z, c)`` -> the contexts the loss reads."""
+    def step(b, batch):
+        z, c = batch
+        loss, acc = cpc(z, context(z, c), seed=seed, stream_id=b, differentiable=True)
+        return loss, loss, acc, {}
+    return step
+
+
+def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params, step_of, frozen=(),
+         encode_once=True, extras=()):
+    """The loop the three fits share: the batches of ``_score_plan``, step i on batch ``i mod batches``; per step
+    ``step_of(b, batch)`` -> (the loss to back-propagate, the CPC loss, the accuracies, dict of the ``extras``), ``backward()`` and
+    one step of ``optimizer(params, lr=lr)``.  ``encode_once``: ``batch`` is ``(z, c)`` of ``encoder(mels)``, computed under
+    ``no_grad`` at the batch's first turn, checked and kept on the device; otherwise it is the mels, nothing is encoded ahead and
+    ``encoder.check()`` follows ``backward()``.  ``frozen``: parameters that require no gradient while the loop runs.  ``extras``:
+    the names of further per-step lists in the result."""
     S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
     dev = device if device is not None else next(encoder.parameters()).device
     n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
-    res = {"losses": [], "accuracies": [], "steps": 0, "batches": n_batches, "utterances": n_batches * S * U,
-           "speakers_skipped": skipped, "speakers_left_over": left}
+    res = {"losses": [], **{k: [] for k in extras}, "accuracies": [], "steps": 0, "batches": n_batches,
+           "utterances": n_batches * S * U, "speakers_skipped": skipped, "speakers_left_over": left}
     if n_batches == 0 or steps <= 0:
         return res
     opt = optimizer(params, lr=lr)
+    for p in frozen:                                     # a part that does not step costs no backward either
+        p.requires_grad_(False)
     encoded = {}
-    for step in range(steps):
-        b = step % n_batches
-        if b not in encoded:
-            with torch.no_grad():
-                z, c, _, _ = encoder(batch_mels(b))
-                if hasattr(encoder, "check"):
-                    encoder.check()
-            encoded[b] = (z.detach(), c.detach())
-        z, c = encoded[b]
-        opt.zero_grad(set_to_none=True)
-        with torch.enable_grad():
-            loss, acc = cpc(z, context(z, c), seed=seed, stream_id=b, differentiable=True)
-            loss.backward()
-        opt.step()
-        res["losses"].append(float(loss.detach()))
-        res["accuracies"].append(list(acc))
-        res["steps"] = step + 1
+    try:
+        for step in range(steps):
+            b = step % n_batches
+            if not encode_once:
+                batch = batch_mels(b)
+            elif b in encoded:
+                batch = encoded[b]
+            else:
+                with torch.no_grad():
+                    z, c, _, _ = encoder(batch_mels(b))
+                    if hasattr(encoder, "check"):
+                        encoder.check()
+                batch = encoded[b] = (z.detach(), c.detach())
+            opt.zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                loss, cpc_loss, acc, extra = step_of(b, batch)
+                loss.backward()
+            if not encode_once and hasattr(encoder, "check"):
+                encoder.check()
+            opt.step()
+            res["losses"].append(float(cpc_loss.detach()))
+            for k in extras:
+                res[k].append(float(extra[k]))
+            res["accuracies"].append(list(acc))
+            res["steps"] = step + 1
+    finally:
+        for p in frozen:
+            p.requires_grad_(True)
     return res
 
 
@@ -368,10 +398,9 @@ def fit_context(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 20
     encoder's once.
 
     Returns what ``fit_predictors`` returns."""
-    K = cpc.n_prediction_steps
-    params = list(encoder.rnn.parameters()) + ([p for m in cpc.predictors[:K] for p in m.parameters()] if train_predictors else [])
+    params = list(encoder.rnn.parameters()) + (_predictor_params(cpc) if train_predictors else [])
     return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params,
-                lambda z, c: encoder.context(z, differentiable=True))
+                _encoded_step(cpc, seed, lambda z, c: encoder.context(z, differentiable=True)))
 
 
 FIT_ENCODER_PARTS = ("front", "rnn", "predictors")
@@ -399,42 +428,18 @@ def fit_encoder(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 20
     unknown = [t for t in train if t not in FIT_ENCODER_PARTS]
     if unknown or not train or len(set(train)) != len(train):
         raise ValueError(f"fit_encoder: train must name each of {FIT_ENCODER_PARTS} at most once and at least one of them, got {train!r}")
-    K = cpc.n_prediction_steps
     parts = {"front": list(encoder.conv.parameters()) + list(encoder.encoder.parameters()), "rnn": list(encoder.rnn.parameters()),
-             "predictors": [p for m in cpc.predictors[:K] for p in m.parameters()]}
+             "predictors": _predictor_params(cpc)}
     params = [p for name in FIT_ENCODER_PARTS if name in train for p in parts[name]]
     frozen = [p for name in FIT_ENCODER_PARTS if name not in train for p in parts[name] if p.requires_grad]
-    S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
-    dev = device if device is not None else next(encoder.parameters()).device
-    n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
-    res = {"losses": [], "vq_losses": [], "perplexities": [], "accuracies": [], "steps": 0, "batches": n_batches,
-           "utterances": n_batches * S * U, "speakers_skipped": skipped, "speakers_left_over": left}
-    if n_batches == 0 or steps <= 0:
-        return res
-    opt = optimizer(params, lr=lr)
-    for p in frozen:                                     # a part that does not step costs no backward either
-        p.requires_grad_(False)
-    try:
-        for step in range(steps):
-            b = step % n_batches
-            mels = batch_mels(b)
-            opt.zero_grad(set_to_none=True)
-            with torch.enable_grad():
-                z, c, vq_loss, perplexity = encoder.forward_differentiable(mels, adapt_codebook=adapt_codebook)
-                cpc_loss, acc = cpc(z, c, seed=seed, stream_id=b, differentiable=True)
-                (cpc_loss + vq_loss).backward()
-            if hasattr(encoder, "check"):
-                encoder.check()
-            opt.step()
-            res["losses"].append(float(cpc_loss.detach()))
-            res["vq_losses"].append(float(vq_loss.detach()))
-            res["perplexities"].append(float(perplexity))
-            res["accuracies"].append(list(acc))
-            res["steps"] = step + 1
-    finally:
-        for p in frozen:
-            p.requires_grad_(True)
-    return res
+
+    def step(b, mels):
+        z, c, vq_loss, perplexity = encoder.forward_differentiable(mels, adapt_codebook=adapt_codebook)
+        cpc_loss, acc = cpc(z, c, seed=seed, stream_id=b, differentiable=True)
+        return cpc_loss + vq_loss, cpc_loss, acc, {"vq_losses": vq_loss.detach(), "perplexities": perplexity}
+
+    return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params, step, frozen=frozen,
+                encode_once=False, extras=("vq_losses", "perplexities"))
 
 
 # ---------------------------------------------------------------------------------------- vocoder scoring
