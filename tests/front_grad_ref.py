@@ -15,6 +15,11 @@ Pins and judge, per tensor: tests/grad_judge.py.
 forced (``model.py:147-150``), ``nn.LSTM`` and ``cpc_grad_ref.loss_torch`` with given negatives, ``loss = cpc + vq`` -- judged by
 the same rule with ``e_ref`` from the same composition in torch fp32 on the CPU.
 
+``WIDE_CASES`` (tests/golden/front_grad_wide_pins.npz, the same tool): fourteen more cases at the shapes where the kernels branch
+-- a ragged last slab behind two whole ones, an odd slab count, one long utterance on the direct conv order, utterances of one output
+frame, the smallest calls, ``in_channels`` 16 / 128 / 144 / 256 across slabs, a silent utterance, a loud batch and an upstream gradient
+that is zero but for a few rows -- judged by the same rule (tests/test_gpu_front_grad_wide.py).
+
 ``FAULTS``: mistakes seeded into the restatements by a switch, which tests/test_front_grad_cpu.py shows the judge to notice.
 """
 import os
@@ -36,6 +41,7 @@ KEYS = ["conv"] + [f"ln_g{i}" for i in range(5)] + [f"ln_b{i}" for i in range(5)
 SD_NAMES = (["conv.weight"] + [f"encoder.{n}.weight" for n in LN_IDS] + [f"encoder.{n}.bias" for n in LN_IDS] +
             [f"encoder.{n}.weight" for n in FC_IDS] + ["encoder.14.weight", "encoder.14.bias"])
 PINS = os.path.join(grad_judge.GOLD, "front_grad_pins.npz")
+WIDE_PINS = os.path.join(grad_judge.GOLD, "front_grad_wide_pins.npz")
 POSITIONS = "front_grad/{name}/{tensor}/pins"          # the seed of a tensor's pinned samples
 
 # name -> B, T, in_channels, conv_mode, variant
@@ -59,6 +65,27 @@ CASES = {
 ALL_CASES = list(CASES)
 SMALL_CASES = [n for n in ALL_CASES if CASES[n][0] * (CASES[n][1] // 2) <= 64]      # what the numpy restatements run
 DEAD_LN = 2                                            # dead_units: encoder.6.bias
+
+# the same row format; GRAD_SLAB = 1024 rows, tiles of 16 rows, VQCPC_CONV_AUTO takes the direct order where C * T > 20480
+WIDE_CASES = {
+    "tail37": (5, 834, 80, 0, None),                   # 2085 rows: three slabs, the last of two whole tiles and one of 5 rows
+    "one_long": (1, 4100, 80, 0, None),                # 2050 rows: B = 1 on the direct order by AUTO, slab edges inside one utterance, last slab 2 rows
+    "T2": (130, 2, 80, 0, None),                       # To = 1: 130 rows, nine tiles, taps 0 and 3 read only padding
+    "T2_m1": (130, 2, 80, 1, None),                    # the same data, the im2col order by name at B > 1
+    "T3_m2": (67, 3, 80, 2, None),                     # To = 1 with a third frame: tap 3 live
+    "r1": (1, 2, 80, 0, None),                         # one row: the smallest call
+    "r17": (1, 34, 80, 0, None),                       # 17 rows: a second tile of one row
+    "c16_slabs": (9, 230, 16, 0, None),                # 1035 rows: 4C = 64 across two slabs
+    "c128_m1": (3, 42, 128, 1, None),                  # 4C = 512, the last width of the fused schedule
+    "c144_slabs": (9, 230, 144, 0, None),              # 4C = 576 > 512, two slabs
+    "c256_slabs_m2": (9, 230, 256, 2, None),           # the widest conv, two slabs, the direct order by name
+    "silent": (4, 42, 80, 0, "silent"),                # mel[1] = 0: rows whose x_0 is 0, variance 0, rstd = 1 / sqrt(eps)
+    "loud": (3, 42, 80, 0, "loud"),                    # mel x 50
+    "sparse_G": (9, 230, 80, 0, "sparse"),             # G zero but for rows 0 and 1030 .. 1034, as a loss over a few frames hands it over
+}
+ALL_WIDE = list(WIDE_CASES)
+WIDE_SMALL = [n for n in ALL_WIDE if WIDE_CASES[n][0] * ((WIDE_CASES[n][1] - 2) // 2 + 1) <= 130]   # what kernel_order32 runs of them
+SPARSE_ROWS = (0, 1030, 1031, 1032, 1033, 1034)
 CHAIN = "chain"
 
 _cases, _fwd, _refs = {}, {}, {}
@@ -77,7 +104,7 @@ def load(name):
     """A case as a dict: sizes, ``mel`` (B, C, T) and upstream ``G`` (B, To, 64) as fp32 torch tensors, ``w`` = the 17 front-end
     tensors by ``KEYS``.  Computed once and shared (treat as read-only)."""
     if name not in _cases:
-        B, T, C, mode, variant = CASES[name]
+        B, T, C, mode, variant = CASES[name] if name in CASES else WIDE_CASES[name]
         base = _base(name)
         To = (T - 2) // 2 + 1
         sd = synth.encoder_state_dict(in_channels=C, ln_affine="random")
@@ -89,8 +116,16 @@ def load(name):
         G = _u(base + "/G", (B, To, 64), 1.0)
         if variant == "zero_upstream":
             G = torch.zeros_like(G)
-        _cases[name] = dict(name=name, B=B, T=T, C=C, To=To, R=B * To, mode=mode, mel=synth.mel("front_grad/" + base, B, T, n_mels=C),
-                            G=G, w=w)
+        if variant == "sparse":
+            keep = torch.zeros(B * To, 1)
+            keep[list(SPARSE_ROWS)] = 1.0
+            G = (G.reshape(B * To, 64) * keep).reshape(B, To, 64)
+        mel = synth.mel("front_grad/" + base, B, T, n_mels=C)
+        if variant == "silent":
+            mel[1] = 0.0
+        if variant == "loud":
+            mel = mel * 50.0
+        _cases[name] = dict(name=name, B=B, T=T, C=C, To=To, R=B * To, mode=mode, mel=mel, G=G, w=w)
     return _cases[name]
 
 
@@ -171,7 +206,7 @@ def grads64(name):
 
 
 def pins():
-    return grad_judge.load_pins(PINS)
+    return grad_judge.load_pins(PINS, WIDE_PINS)
 
 
 def bound(name, tensor):
@@ -283,13 +318,15 @@ def chain_grads(dtype=torch.float64):
 
 
 # ------------------------------------------------------------------ fp32 restatements
-FAULTS = ("mask_from_pre", "drop_means", "pad_rows_counted", "conv_edge", "skip_short_slab")   # seeded into reordered32 only
+FAULTS = ("mask_from_pre", "drop_means", "pad_rows_counted", "conv_edge", "skip_short_slab",     # seeded into reordered32 only
+          "slab_tail_tiles", "ahead_group_dropped", "conv_tail")
 fma = ctx_grad_ref.fma
 
 
 def im2col(mel, To, fault=None):
     """(R, 4 C), column 4 c + tap: zero in the padding and for the frame an odd T leaves over.  ``fault`` "conv_edge": the tap
-    before an utterance's first frame reads the last frame of the utterance before it."""
+    before an utterance's first frame reads the last frame of the utterance before it; "conv_tail": a tap past an utterance's end
+    reads the first frames of the utterance after it."""
     B, C, T = mel.shape
     cols = np.zeros((B, To, C, 4), f32)
     flat = mel.transpose(1, 0, 2).reshape(C, B * T)
@@ -300,6 +337,8 @@ def im2col(mel, To, fault=None):
                 cols[:, tt, :, tap] = mel[:, :, ti]
             elif fault == "conv_edge" and ti < 0:
                 cols[1:, tt, :, tap] = flat[:, np.arange(1, B) * T - 1].T
+            elif fault == "conv_tail" and ti >= T:
+                cols[:-1, tt, :, tap] = mel[1:, :, ti - T]
     return cols.reshape(B * To, 4 * C)
 
 
@@ -379,6 +418,10 @@ def ln_bwd_reordered(da, x, a, gamma, fault=None):
     if fault == "pad_rows_counted":                                  # the last tile's padding carries row 0
         extra = [0] * (-R % 16)
         cb, cg = np.concatenate([cb, cb[extra]]), np.concatenate([cg, cg[extra]])
+    if fault == "slab_tail_tiles":                                   # the last slab's tiles past its last whole group of four are left out
+        r0 = (R - 1) // 1024 * 1024
+        kept = r0 + ((R - r0 + 15) // 16) // 4 * 64
+        cb, cg = cb[:kept], cg[:kept]
     tree = ctx_grad_ref._tree
     dbeta = np.zeros(512, f32) + tree([cb[r:r + 64].sum(axis=0) for r in range(0, cb.shape[0], 64)])
     dgamma = np.zeros(512, f32) + tree([cg[r:r + 64].sum(axis=0) for r in range(0, cg.shape[0], 64)])
@@ -392,6 +435,8 @@ def backward32(name, ln_bwd, wdot, colsum, dot, fault=None):
     G = g["G"].numpy().reshape(g["R"], 64)
     R = g["R"]
     summed = R - R % 1024 if fault == "skip_short_slab" and R % 1024 < 16 else R
+    if fault == "ahead_group_dropped":
+        summed = R - R % 64
     out = {"out_w": wdot(G[:summed], fw["a"][4][:summed]), "out_b": colsum(G[:summed])}
     d = dot(G, w["out_w"])
     for l in range(4, -1, -1):

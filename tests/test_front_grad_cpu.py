@@ -1,5 +1,6 @@
 """CPU side of the front-end gradients: the pins hold the float64 reference, two fp32 numpy restatements (the kernels' documented
-orders, and other orders) pass the judge of tests/front_grad_ref.py, five seeded faults do not, the second header is plain C99 and
+orders, and other orders) pass the judge of tests/front_grad_ref.py -- the fifteen cases and the fourteen ``WIDE_CASES`` -- eight
+seeded faults do not, the second header is plain C99 and
 its symbols are exported and bound, and ``fit_encoder`` / ``cli fit-encoder`` check their arguments before any GPU is needed."""
 import ctypes
 import os
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [n for n in R.SMALL_CASES if not n.endswith(("_m1", "_m2"))]
 
 
-@pytest.mark.parametrize("name", R.ALL_CASES + [R.CHAIN])
+@pytest.mark.parametrize("name", R.ALL_CASES + [R.CHAIN] + R.ALL_WIDE)
 def test_pins_hold_the_float64_reference(name):
     ref, p = R.grads64(name), R.pins()
     grad_judge.check_pins(ref, p, name, R.tensors(name), R.POSITIONS)
@@ -33,23 +34,60 @@ def test_masks_of_the_small_cases_are_the_float64_run_s_own():
         assert int(R.pins()[f"{name}_differ"]) == 0
 
 
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", SMALL + R.WIDE_SMALL)
 def test_kernel_order_restatement_passes_the_judge(name):
     R.judge(name, R.kernel_order32(name), "kernel order")
 
 
-@pytest.mark.parametrize("name", SMALL + ["slab_plus_one"])
+@pytest.mark.parametrize("name", SMALL + ["slab_plus_one"] + R.ALL_WIDE)
 def test_reordered_restatement_passes_the_judge(name):
     R.judge(name, R.reordered32(name), "other orders")
 
 
 @pytest.mark.parametrize("fault,name", [("mask_from_pre", "partial_tile"), ("drop_means", "partial_tile"),
                                         ("pad_rows_counted", "partial_tile"), ("conv_edge", "partial_tile"),
-                                        ("skip_short_slab", "slab_plus_one")])
+                                        ("skip_short_slab", "slab_plus_one"), ("slab_tail_tiles", "tail37"),
+                                        ("ahead_group_dropped", "tail37"), ("conv_tail", "T2")])
 def test_the_judge_notices_a_seeded_fault(fault, name):
     assert fault in R.FAULTS
     with pytest.raises(AssertionError):
         R.judge(name, R.reordered32(name, fault), fault)
+
+
+def test_every_fault_has_a_case():
+    marks = [m for m in test_the_judge_notices_a_seeded_fault.pytestmark if m.name == "parametrize"]
+    assert sorted(f for f, _ in marks[0].args[1]) == sorted(R.FAULTS)
+
+
+def test_wide_cases_are_the_shapes_they_are_named_for():
+    rows = {n: R.WIDE_CASES[n][0] * ((R.WIDE_CASES[n][1] - 2) // 2 + 1) for n in R.ALL_WIDE}
+    assert rows == dict(tail37=2085, one_long=2050, T2=130, T2_m1=130, T3_m2=67, r1=1, r17=17, c16_slabs=1035, c128_m1=63,
+                        c144_slabs=1035, c256_slabs_m2=1035, silent=84, loud=63, sparse_G=1035)
+    assert sorted(R.WIDE_SMALL) == sorted(["T2", "T2_m1", "T3_m2", "r1", "r17", "c128_m1", "silent", "loud"])
+    assert not set(R.ALL_WIDE) & set(R.ALL_CASES)
+    assert R.WIDE_CASES["one_long"][2] * R.WIDE_CASES["one_long"][1] > 20480        # VQCPC_CONV_AUTO: the direct order at B = 1
+    assert torch.equal(R.load("T2")["mel"], R.load("T2_m1")["mel"]) and torch.equal(R.load("T2")["G"], R.load("T2_m1")["G"])
+    silent = R.load("silent")
+    assert not silent["mel"][1].any() and silent["mel"][0].any() and silent["mel"][2].any()
+    x0 = R.forward32("silent")["x"][0].reshape(4, 21, 512)
+    assert not x0[1].view(np.uint32).any() and x0[0].any(axis=1).all()               # zero-variance rows: rstd = 1 / sqrt(eps)
+    assert float(R.load("loud")["mel"].max()) > 45.0
+    G = R.load("sparse_G")["G"].reshape(-1, 64).numpy()
+    assert sorted(np.flatnonzero(G.any(axis=1))) == list(R.SPARSE_ROWS)
+
+
+def test_the_taps_that_read_only_padding_are_exactly_zero():
+    """To = 1: at T = 2 taps 0 and 3 of the conv read padding in every row, at T = 3 tap 0 does.  The float64 reference is
+    identically zero there, both restatements return +0, and ``conv_tail`` is the fault that fills T2's tap 3."""
+    for name, taps in (("T2", (0, 3)), ("T2_m1", (0, 3)), ("T3_m2", (0,))):
+        ref = R.grads64(name)["conv"]
+        for tap in range(4):
+            assert ref[:, :, tap].any() == (tap not in taps), (name, tap)
+        for got in (R.kernel_order32(name), R.reordered32(name)):
+            for tap in taps:
+                assert got["conv"].dtype == np.float32 and not np.ascontiguousarray(got["conv"][:, :, tap]).view(np.uint32).any(), (name, tap)
+    assert R.reordered32("T2", "conv_tail")["conv"][:, :, 3].any()
+    assert not R.reordered32("T2", "conv_tail")["conv"][:, :, 0].any()
 
 
 def test_dead_units_have_exactly_zero_affine_gradients():

@@ -1,5 +1,5 @@
-"""Writes tests/golden/front_grad_pins.npz, the pins of tests/front_grad_ref.py's float64 reference of the front-end gradients: per
-case and tensor 64 sampled elements, the sum and the sum of squares, the largest magnitude -- and ``e_ref = max |G_ref32 - G_ref64|``,
+"""Writes tests/golden/front_grad_pins.npz (the fifteen cases and ``chain``) and tests/golden/front_grad_wide_pins.npz (the fourteen
+``WIDE_CASES``), the pins of tests/front_grad_ref.py's float64 reference of the front-end gradients: per case and tensor 64 sampled elements, the sum and the sum of squares, the largest magnitude -- and ``e_ref = max |G_ref32 - G_ref64|``,
 the error of the same torch modules (and, for ``chain``, of the same composition with the VQ step, the LSTM and the CPC loss) run in
 fp32 on the CPU under the same forced ReLU masks (and code indices).  Per case it records ``differ``: the number of mask elements in
 which the float64 run's own ReLUs differ from the fp32 program's; for ``chain`` also the smallest VQ margin of the fp32 forward, and
@@ -48,6 +48,11 @@ def main():
     out["chain_fit_vq_margin"] = np.float64(min(m64, m32))
     print(f"chain fit ({R.FIT_STEPS} steps, lr {R.FIT_LR}): the same codes at every step, smallest VQ margin {out['chain_fit_vq_margin']:.3g}")
     grad_judge.write_npz(R.PINS, out)
+    wide = pins_of(R.ALL_WIDE)
+    for name in R.ALL_WIDE:                                         # what the wide cases are there for
+        ref = R.grads64(name)
+        assert all(np.isfinite(ref[k]).all() for k in R.tensors(name)), name
+    grad_judge.write_npz(R.WIDE_PINS, wide)
 
 
 if __name__ == "__main__":
