@@ -54,6 +54,14 @@ class EncoderFrontTensors(C.Structure):
                 ("fc_weight", C.c_void_p * 4), ("out_weight", C.c_void_p), ("out_bias", C.c_void_p)]
 
 
+def fill_front(s, values):
+    """Set the seventeen members ``EncoderWeights`` and ``EncoderFrontTensors`` share from ``values`` (device pointers or None) in
+    the order of ``Encoder._FRONT_NAMES``: conv, 5 LayerNorm weights, 5 LayerNorm biases, 4 fc, out weight, out bias.  -> ``s``."""
+    v = list(values)
+    s.conv_weight, s.ln_weight[:], s.ln_bias[:], s.fc_weight[:], s.out_weight, s.out_bias = v[0], v[1:6], v[6:11], v[11:15], v[15], v[16]
+    return s
+
+
 class CPCWeights(C.Structure):
     _fields_ = [("weight", C.c_void_p * 16), ("bias", C.c_void_p * 16),
                 ("n_steps", C.c_int), ("n_speakers", C.c_int), ("n_utterances", C.c_int), ("n_negatives", C.c_int),
@@ -351,6 +359,20 @@ class NativeModule(nn.Module):
         for name, value in self.__dict__.get("_options", {}).items():     # options survive a rebuild of the handle
             check(getattr(lib, self._SET_OPTION)(h, name.encode(), value))
         return h
+
+    def _live_handle(self, dev):
+        """The handle if one is live on ``dev`` -- also one whose copies an optimizer step has made stale -- else None."""
+        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
+            return self._handle
+        return None
+
+    def _sizes_handle(self, dev):
+        """The handle for a call that reads the weights from the CALLER's pointers (the ``*_fwd`` / ``*_bwd`` / ``*_grad`` entries):
+        it gives sizes and work space only, so any live handle on ``dev`` serves.  ``_native()`` would answer the moved
+        ``WeightSlots.key`` with destroy, create and a synchronisation per optimizer step; calls that read the handle's copies still
+        go through ``_native()``, which rebuilds once when it sees the moved ``_version``, and so never read stale ones."""
+        h = self._live_handle(dev)
+        return h if h is not None else self._native()
 
     def _release(self):
         if getattr(self, "_handle", None) is not None:

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/vqcpc.h"
 
 // runtime.hip: the per-thread error string behind vqcpc_last_error, and the check every create call starts with
@@ -29,6 +30,27 @@ int vq_require_gfx950();             // VQCPC_OK, or VQCPC_ERR_NO_DEVICE with th
 
 // propagate a VQCPC_* status
 #define TRY(x) do { int rc_ = (x); if (rc_ != VQCPC_OK) return rc_; } while (0)
+
+// A call on a handle (`what`: the entry's name) must run on the device the handle was created on.
+inline int vq_require_device(int handle_device, const char *what) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    VQ_REQUIRE(dev == handle_device, "%s: handle belongs to device %d, current device is %d", what, handle_device, dev);
+    return VQCPC_OK;
+}
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+template <class... P> inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15) == 0; }    // all of them; null counts
+// H / 64 in {1, 2, 4, 8} (hidden sizes 64, 128, 256, 512) as a compile-time constant: f(std::integral_constant<int, H / 64>());
+// false, and f not called, for any other value.
+template <class F> inline bool vq_with_sw(int sw, F &&f) {
+    switch (sw) {
+        case 1: f(std::integral_constant<int, 1>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        case 4: f(std::integral_constant<int, 4>()); return true;
+        case 8: f(std::integral_constant<int, 8>()); return true;
+        default: return false;
+    }
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -132,18 +154,28 @@ struct LstmWeights {
     int D, H;
 };
 LstmWeights vq_lstm_plan_weights(const LstmPlan *p);
+// The launch-per-step scan of that LSTM, x (B, T, D) -> out (B, T, H) from zero state, in two halves over a grow-only scratch that
+// the caller owns: vq_lstm_project reserves the scratch and enqueues the hoisted projection gi = x W_ih^T + bias; vq_lstm_steps
+// zeroes the h and cell tiles and enqueues the T step launches (seq_step.h), which also fill *save if it is given.
+struct LstmScratch {
+    DevBuf gi, hbuf, cbuf;         // hoisted projection (B T, 4H), two h tiles, one cell tile
+    size_t bytes() const { return gi.cap + hbuf.cap + cbuf.cap; }
+};
+struct SeqSave;                    // seq_step.h
+int vq_lstm_project(LstmScratch &k, const LstmWeights &w, const float *x, int B, int T, hipStream_t s);
+int vq_lstm_steps(LstmScratch &k, const LstmWeights &w, int B, int T, float *out, const SeqSave *save, hipStream_t s);
 
 // ---- gradients of the context LSTM (context_grad.hip): a forward that keeps state, and back-propagation through time.
 // The work space of both, grow-only, a member of the encoder handle.
 struct CtxGradWork {
-    DevBuf gi, hbuf, cbuf;         // forward: hoisted projection, h and cell tiles (as vq_lstm_run's)
+    LstmScratch fwd;               // forward: its own scratch of the launch-per-step scan (vq_lstm_run has the plan's)
     DevBuf bias, Wf;               // forward, caller's weights: b_ih + b_hh and the W_hh fragments
     DevBuf WfT;                    // backward: W_hh^T fragments
     DevBuf dA, carry, part;        // backward: pre-activation gradients (B T, 4H), the cell carry (B, H), slab partials
-    size_t bytes() const { return gi.cap + hbuf.cap + cbuf.cap + bias.cap + Wf.cap + WfT.cap + dA.cap + carry.cap + part.cap; }
+    size_t bytes() const { return fwd.bytes() + bias.cap + Wf.cap + WfT.cap + dA.cap + carry.cap + part.cap; }
 };
 size_t vq_ctx_saved_bytes(int B, int T, int H);
-// c (B, T, H) with the bits of vq_lstm_run's launch-per-step path; `saved` receives what vq_ctx_bwd reads again.
+// c (B, T, H) from vq_lstm_run's own launch-per-step scan (vq_lstm_project, vq_lstm_steps); `saved` receives what vq_ctx_bwd reads again.
 // own_weights: w.bias and w.Wf are not given -- they are built from b_ih, b_hh, w.w_hh into the work space, in stream order.
 int vq_ctx_fwd(CtxGradWork &k, LstmWeights w, bool own_weights, const float *b_ih, const float *b_hh, const float *z, int B, int T,
                float *c, float *saved, hipStream_t s);

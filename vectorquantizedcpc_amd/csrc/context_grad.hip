@@ -5,9 +5,10 @@
 // memory, no wait on another workgroup; launch boundaries order the steps and the passes.  Equal inputs give equal bits.
 // Every operation below is one separately rounded fp32 operation (-ffp-contract=off); "chain" = fp32 fmas from 0.
 //
-// Forward (vq_ctx_fwd): vq_gemm_chain for the input projection and T launches of seq_step_body<4, SW, true> (seq_step.h), the
-//   statements of vq_lstm_run's launch-per-step path -> the same bits of c at every B (the resident single-utterance scan is not
-//   used).  `saved` = gates (R, 4H) i | f | g | o after their non-linearities, cell state (R, H), tanh(cell) (R, H).
+// Forward (vq_ctx_fwd): vq_lstm_project and vq_lstm_steps of scan.hip, the two functions that ARE vq_lstm_run's launch-per-step
+//   path, over this work space's own scratch and with a SeqSave (seq_step_save_kernel) -> the same bits of c at every B (the
+//   resident single-utterance scan is not used).  `saved` = gates (R, 4H) i | f | g | o after their non-linearities, cell state
+//   (R, H), tanh(cell) (R, H).
 //
 // Backward scan: ctx_bwd_step_kernel<NS>, grid (H / 16, ceil(B / 16)), one launch per step t = T-1 .. 0.  Workgroup (rg, bt) owns
 //   hidden units 16 rg .. + 15 of utterances 16 bt .. + 15.
@@ -44,11 +45,6 @@
 #include "grad_slab.h"
 
 namespace {
-
-template <int SW>
-__global__ __launch_bounds__(256) void seq_step_save_kernel(SeqP p, int step, SeqSave sv) {
-    seq_step_body<4, SW, true>(p, step, sv);
-}
 
 // W_hh^T in fragment order: WfT[((rg * 4 + w) * NS + s) * 64 + lane] (float4) = W_hh[16 S + 4 (lane >> 4) + 0 .. 3][16 rg + (lane & 15)],
 // S = w NS + s, NS = H / 16 (K = 4H over four waves).
@@ -180,8 +176,6 @@ __global__ __launch_bounds__(256) void ctx_grad_z_kernel(const float *dA, const 
     if (r < R) dz[(size_t)r * D + c0 + (tid & 15)] = v;
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 size_t vq_ctx_saved_bytes(int B, int T, int H) { return (size_t)B * T * 6 * H * sizeof(float); }
@@ -194,35 +188,16 @@ static SeqSave saved_view(const float *saved, int B, int T, int H) {
 
 int vq_ctx_fwd(CtxGradWork &k, LstmWeights w, bool own_weights, const float *b_ih, const float *b_hh, const float *z, int B, int T,
                float *c, float *saved, hipStream_t s) {
-    const int H = w.H, D = w.D, nbt = (B + 15) / 16;
-    const size_t hsz = (size_t)nbt * H * 16 * sizeof(float);
-    TRY(k.gi.reserve((size_t)B * T * 4 * H * sizeof(float)));
-    TRY(k.hbuf.reserve(2 * hsz));
-    TRY(k.cbuf.reserve(hsz));
+    const int H = w.H;
     if (own_weights) {                                   // what vq_lstm_plan_create builds, from the caller's tensors, in stream order
         TRY(k.bias.reserve((size_t)4 * H * sizeof(float)));
         vq_add_vec(b_ih, b_hh, k.bias.as<float>(), 4 * H, s);
         TRY(vq_build_wfrag(w.w_hh, H, H / 4, H, 4, 4, H, k.Wf, s));
         w.bias = k.bias.as<float>(); w.Wf = k.Wf.as<float>();
     }
-    TRY(vq_gemm_chain(z, D, w.w_ih, w.bias, k.gi.as<float>(), 4 * H, B * T, 4 * H, D, D, s));
-    HIP_TRY(hipMemsetAsync(k.hbuf.p, 0, 2 * hsz, s));
-    HIP_TRY(hipMemsetAsync(k.cbuf.p, 0, hsz, s));
-    SeqP q{};
-    q.Wf = w.Wf; q.Gi = k.gi.as<float>(); q.hbuf = k.hbuf.as<float>(); q.cbuf = k.cbuf.as<float>();
-    q.out = c; q.len = nullptr; q.H = H; q.nbt = nbt; q.B = B; q.T = T; q.ndir = 1;
+    TRY(vq_lstm_project(k.fwd, w, z, B, T, s));
     const SeqSave sv = saved_view(saved, B, T, H);
-    const dim3 grid(H / 4, 1, nbt), blk(256);
-    for (int t = 0; t < T; ++t) {
-        switch (H / 64) {
-#define CASE(n) case n: hipLaunchKernelGGL((seq_step_save_kernel<n>), grid, blk, 0, s, q, t, sv); break;
-            CASE(1) CASE(2) CASE(4) CASE(8)
-#undef CASE
-            default: vq_set_error("context forward: hidden size %d unsupported", H); return VQCPC_ERR_INVALID;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
+    return vq_lstm_steps(k.fwd, w, B, T, c, &sv, s);
 }
 
 int vq_ctx_bwd(CtxGradWork &k, LstmWeights w, const float *z, int B, int T, const float *c, const float *saved, const float *grad_c,
@@ -243,12 +218,10 @@ int vq_ctx_bwd(CtxGradWork &k, LstmWeights w, const float *z, int B, int T, cons
     p.dA = k.dA.as<float>(); p.carry = k.carry.as<float>(); p.H = H; p.B = B; p.T = T;
     const dim3 blk(256), grid(H / 16, nbt);
     for (int t = T - 1; t >= 0; --t) {
-        switch (H / 64) {
-#define CASE(n) case n: hipLaunchKernelGGL((ctx_bwd_step_kernel<4 * n>), grid, blk, 0, s, p, t); break;
-            CASE(1) CASE(2) CASE(4) CASE(8)
-#undef CASE
-            default: vq_set_error("context backward: hidden size %d unsupported", H); return VQCPC_ERR_INVALID;
-        }
+        const bool built = vq_with_sw(H / 64, [&](auto sw) {
+            hipLaunchKernelGGL((ctx_bwd_step_kernel<4 * decltype(sw)::value>), grid, blk, 0, s, p, t);
+        });
+        if (!built) { vq_set_error("context backward: hidden size %d unsupported", H); return VQCPC_ERR_INVALID; }
     }
     const float *dA = k.dA.as<float>();
     if (want_w) {
@@ -264,12 +237,9 @@ int vq_ctx_bwd(CtxGradWork &k, LstmWeights w, const float *z, int B, int T, cons
     }
     if (grad_z) {
         const dim3 gz((unsigned)((R + 15) / 16), D / 16);
-        switch (H / 64) {
-#define CASE(n) case n: hipLaunchKernelGGL((ctx_grad_z_kernel<4 * n>), gz, blk, 0, s, dA, w.w_ih, grad_z, (int)R, D, H); break;
-            CASE(1) CASE(2) CASE(4) CASE(8)
-#undef CASE
-            default: break;
-        }
+        vq_with_sw(H / 64, [&](auto sw) {
+            hipLaunchKernelGGL((ctx_grad_z_kernel<4 * decltype(sw)::value>), gz, blk, 0, s, dA, w.w_ih, grad_z, (int)R, D, H);
+        });
     }
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;

@@ -221,8 +221,6 @@ __global__ __launch_bounds__(256) void cpc_grad_z_sum_kernel(const float *dzk, f
     dz[e] = sum;
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int vqcpc_cpc_grad(vqcpc_cpc *cpc, const float *z, const float *c, int T, const float *W, const float *bias,

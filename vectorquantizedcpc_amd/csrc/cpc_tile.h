@@ -176,9 +176,7 @@ static int cpc_begin(vqcpc_cpc *cpc, const char *what, const float *z, const flo
     const int L = T - K, N = cpc->Spk * cpc->Utt;
     VQ_REQUIRE((long long)N * cpc->Neg * L < (1ll << 31), "%s: Spk * Utt * Neg * L = %lld does not fit the draw counter", what,
                (long long)N * cpc->Neg * L);
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    VQ_REQUIRE(dev == cpc->device, "%s: handle belongs to device %d, current device is %d", what, cpc->device, dev);
+    TRY(vq_require_device(cpc->device, what));
     const int tiles = (L + CPC_TT - 1) / CPC_TT;
     P = (size_t)N * tiles;
     TRY(cpc->part_loss.reserve(P * K * sizeof(double)));

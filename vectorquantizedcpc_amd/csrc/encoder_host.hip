@@ -1,7 +1,6 @@
 // encoder_host.hip -- the encoder handle (struct vqcpc_encoder), the choice among the three schedules of its front end
 // (layered kernels, one fused launch, six column-split launches: encoder.hip) and every vqcpc_encoder_* entry point.
 #include "encoder_internal.h"
-#include "../../include/vqcpc_grad.h"
 #include <string.h>
 
 struct vqcpc_encoder {
@@ -21,6 +20,7 @@ struct vqcpc_encoder {
     CtxGradWork ctx;                     // work space of vqcpc_encoder_context_fwd / _bwd (context_grad.hip)
     FrontGradWork front;                 // work space of vqcpc_encoder_front_fwd / _bwd (front_grad.hip)
     DevPtr<float> conv_w;                // conv.weight as given (the layout of its gradient)
+    FrontW fw{};                         // the front-end weights above as the layered schedule and the gradients read them
     int device = 0;                      // the device the handle was created on
     // fused and column-split schedules: weights in 16x16x4 fragment order (only when 4 * in_channels <= 512, the width of
     // their activation tile), and the model's half of their kernel argument
@@ -78,6 +78,11 @@ static int encoder_create_impl(const vqcpc_encoder_weights *w, vqcpc_encoder *e)
         for (int i = 0; i < 4; ++i) TRY(build_frag16(e->fc_w[i], CH, CH, e->fc_f[i]));
         TRY(build_frag16(e->out_w, w->z_dim, CH, e->out_f));
     }
+    FrontW &f = e->fw;
+    f.t.conv_weight = e->conv_w; f.conv_w1 = e->conv_w1; f.conv_w2 = e->conv_w2;
+    for (int i = 0; i < 5; ++i) { f.t.ln_weight[i] = e->ln_g[i]; f.t.ln_bias[i] = e->ln_b[i]; }
+    for (int i = 0; i < 4; ++i) f.t.fc_weight[i] = e->fc_w[i];
+    f.t.out_weight = e->out_w; f.t.out_bias = e->out_b;
     FusedP &p = e->fp;
     p.C = C;
     for (int i = 0; i < 5; ++i) { p.ln_g[i] = e->ln_g[i]; p.ln_b[i] = e->ln_b[i]; }
@@ -116,39 +121,45 @@ static int resolve_conv_mode(const vqcpc_encoder *e, int conv_mode, int B, int T
     return (B > 1 || (long)B * e->in_channels * T > 20480) ? VQCPC_CONV_DIRECT : VQCPC_CONV_IM2COL;
 }
 
-// conv + seg-FC stack up to `stop_stage` (0 conv, 1 LN0+ReLU, 2+2l FC_l, 3+2l LN_l+ReLU, 10 z_pre).
-// Returns the device buffer holding that stage's rows in *stage_out.
-static int encoder_front(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, int stop_stage,
-                         float *zp, const float **stage_out, hipStream_t s) {
-    const int C = e->in_channels, CH = e->channels, To = frames_of(T), N = B * To;
-    conv_mode = resolve_conv_mode(e, conv_mode, B, T);
-    TRY(e->bufA.reserve((size_t)N * CH * sizeof(float)));
-    TRY(e->bufB.reserve((size_t)N * CH * sizeof(float)));
-    float *a = e->bufA, *b = e->bufB;
-    e->last_schedule = 0;
-
+// The layered schedule (encoder_internal.h): conv + seg-FC stack up to `stop_stage`.  The one place that spells the sequence; the
+// inference path below and the state-keeping forward of front_grad.hip differ only in `d`.
+int vq_front_chain(const FrontW &w, const LnConst &lnc, const float *mel, int B, int C, int T, int conv_mode, int stop_stage,
+                   const FrontDst &d, const float **stage_out, hipStream_t s) {
+    const int CH = 512, To = frames_of(T), N = B * To;
     // conv (model.py:65) as an im2col GEMM in the reference back-end's summation order
     const bool one_chain = conv_mode == VQCPC_CONV_IM2COL;
-    TRY(vq_gemm_chain_im2col(mel, C, T, To, one_chain ? e->conv_w1 : e->conv_w2, a, N, CH, one_chain ? 4 * C : 64, conv_mode, s));
-    *stage_out = a;
-    if (stop_stage == 0) return VQCPC_OK;
-
-    // seg-FC stack (model.py:46-55, :67)
-    launch_ln512(a, e->ln_g[0], e->ln_b[0], b, N, 1e-5f, 1, e->lnc, s);
-    *stage_out = b;
-    if (stop_stage == 1) return VQCPC_OK;
-    for (int l = 0; l < 4; ++l) {
-        TRY(vq_gemm_chain(b, CH, e->fc_w[l], nullptr, a, CH, N, CH, CH, 256, s));
-        *stage_out = a;
-        if (stop_stage == 2 + 2 * l) return VQCPC_OK;
-        launch_ln512(a, e->ln_g[l + 1], e->ln_b[l + 1], b, N, 1e-5f, 1, e->lnc, s);
-        *stage_out = b;
-        if (stop_stage == 3 + 2 * l) return VQCPC_OK;
+    TRY(vq_gemm_chain_im2col(mel, C, T, To, one_chain ? w.conv_w1 : w.conv_w2, d.x[0], N, CH, one_chain ? 4 * C : 64, conv_mode, s));
+    *stage_out = d.x[0];
+    // seg-FC stack (model.py:46-55, :67): stage 1 + 2l = LN_l + ReLU, 2 + 2l = FC_l, 10 = the out layer
+    for (int st = 1; st <= stop_stage; ++st) {
+        const int l = (st - 1) / 2;
+        if (st & 1) {
+            launch_ln512(d.x[l], w.t.ln_weight[l], w.t.ln_bias[l], d.a[l], N, 1e-5f, 1, lnc, s, d.stat[l]);
+            *stage_out = d.a[l];
+        } else if (st < 10) {
+            TRY(vq_gemm_chain(d.a[l], CH, w.t.fc_weight[l], nullptr, d.x[l + 1], CH, N, CH, CH, 256, s));
+            *stage_out = d.x[l + 1];
+        } else {
+            TRY(vq_gemm_chain(d.a[4], CH, w.t.out_weight, w.t.out_bias, d.z_pre, 64, N, 64, CH, 256, s));
+            *stage_out = d.z_pre;
+            HIP_TRY(hipGetLastError());
+        }
     }
-    TRY(vq_gemm_chain(b, CH, e->out_w, e->out_b, zp, 64, N, 64, CH, 256, s));
-    *stage_out = zp;
-    HIP_TRY(hipGetLastError());
     return VQCPC_OK;
+}
+
+// Inference: the chain over the handle's copies and its two ping-pong buffers, no statistics kept.
+// Returns the device buffer holding the stop stage's rows in *stage_out.
+static int encoder_front(vqcpc_encoder *e, const float *mel, int B, int T, int conv_mode, int stop_stage,
+                         float *zp, const float **stage_out, hipStream_t s) {
+    const size_t bytes = (size_t)B * frames_of(T) * e->channels * sizeof(float);
+    TRY(e->bufA.reserve(bytes));
+    TRY(e->bufB.reserve(bytes));
+    e->last_schedule = 0;
+    FrontDst d{};
+    for (int l = 0; l < 5; ++l) { d.x[l] = e->bufA; d.a[l] = e->bufB; }
+    d.z_pre = zp;
+    return vq_front_chain(e->fw, e->lnc, mel, B, e->in_channels, T, resolve_conv_mode(e, conv_mode, B, T), stop_stage, d, stage_out, s);
 }
 
 static bool use_fused(const vqcpc_encoder *e) { return e->fused != 0 && e->conv_f[0] != nullptr; }
@@ -210,7 +221,7 @@ extern "C" int vqcpc_encoder_encode(vqcpc_encoder *e, const float *mel, int B, i
     const int To = frames_of(T), N = B * To;
     float *zp = z_pre;
     if (!zp && !use_fused(e)) { TRY(e->zpre.reserve((size_t)N * 64 * sizeof(float))); zp = e->zpre; }
-    VQ_REQUIRE(((uintptr_t)zp & 15) == 0 && ((uintptr_t)z_q & 15) == 0, "encoder.encode: outputs must be 16-byte aligned");
+    VQ_REQUIRE(aligned16(zp, z_q), "encoder.encode: outputs must be 16-byte aligned");
     if (use_fused(e)) {
         TRY(encoder_fused(e, mel, B, T, conv_mode, z_pre, z_q, idx, -1, nullptr, s));     // z_pre only if asked for
     } else {
@@ -231,7 +242,7 @@ extern "C" int vqcpc_encoder_check(vqcpc_encoder *e) {
 extern "C" int vqcpc_encoder_vq_encode(vqcpc_encoder *e, const float *x, int n_rows, float *z_q, int64_t *idx,
                                        void *stream) {
     VQ_REQUIRE(e && x && z_q && idx && n_rows > 0, "vqcpc_encoder_vq_encode: bad argument");
-    VQ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)z_q & 15) == 0, "vqcpc_encoder_vq_encode: rows must be 16-byte aligned");
+    VQ_REQUIRE(aligned16(x, z_q), "vqcpc_encoder_vq_encode: rows must be 16-byte aligned");
     launch_vq_encode(x, n_rows, e->cbfrag, e->codebook, e->e2, e->n_emb, idx, z_q, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
@@ -248,7 +259,7 @@ extern "C" int vqcpc_encoder_stage(vqcpc_encoder *e, const float *mel, int B, in
     const float *src = nullptr;
     float *zp = nullptr;
     if (stage == 10) {
-        VQ_REQUIRE(((uintptr_t)out & 15) == 0, "vqcpc_encoder_stage: out must be 16-byte aligned");
+        VQ_REQUIRE(aligned16(out), "vqcpc_encoder_stage: out must be 16-byte aligned");
         zp = out;
     }
     TRY(encoder_front(e, mel, B, T, conv_mode, stage, zp, &src, s));
@@ -271,14 +282,11 @@ static int context_grad_begin(vqcpc_encoder *e, const char *what, int B, int Tz,
     VQ_REQUIRE(given == 0 || given == (need_bias ? 4 : 2), "%s: give all of the LSTM's weight tensors, or none of them (the handle's copies)", what);
     VQ_REQUIRE((long long)B * Tz <= 65535ll * 1024 && B <= 65535 * 16, "%s: B * Tz = %lld rows, more than 65535 slabs of 1024", what,
                (long long)B * Tz);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    VQ_REQUIRE(dev == e->device, "%s: handle belongs to device %d, current device is %d", what, e->device, dev);
+    TRY(vq_require_device(e->device, what));
     w = vq_lstm_plan_weights(e->lstm);
     if (own) { w.w_ih = w_ih; w.w_hh = w_hh; w.bias = nullptr; w.Wf = nullptr; }
     return VQCPC_OK;
 }
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int vqcpc_encoder_context_saved_bytes(vqcpc_encoder *e, int B, int Tz, uint64_t *bytes) {
     VQ_REQUIRE(e && bytes, "vqcpc_encoder_context_saved_bytes: null argument");
@@ -293,7 +301,7 @@ extern "C" int vqcpc_encoder_context_fwd(vqcpc_encoder *e, const float *z, int B
     LstmWeights w;
     bool own = false;
     TRY(context_grad_begin(e, "vqcpc_encoder_context_fwd", B, Tz, w_ih, w_hh, b_ih, b_hh, true, w, own));
-    VQ_REQUIRE(aligned16(z) && aligned16(c) && aligned16(saved) && aligned16(w.w_ih) && aligned16(w.w_hh),
+    VQ_REQUIRE(aligned16(z, c, saved, w.w_ih, w.w_hh),
                "vqcpc_encoder_context_fwd: z, c, saved and the weights must be 16-byte aligned");
     return vq_ctx_fwd(e->ctx, w, own, b_ih, b_hh, z, B, Tz, c, (float *)saved, (hipStream_t)stream);
 }
@@ -305,8 +313,7 @@ extern "C" int vqcpc_encoder_context_bwd(vqcpc_encoder *e, const float *z, int B
     LstmWeights w;
     bool own = false;
     TRY(context_grad_begin(e, "vqcpc_encoder_context_bwd", B, Tz, w_ih, w_hh, nullptr, nullptr, false, w, own));
-    VQ_REQUIRE(aligned16(z) && aligned16(c) && aligned16(saved) && aligned16(grad_c) && aligned16(w.w_ih) && aligned16(w.w_hh) &&
-               aligned16(grad_z) && aligned16(grad_w_ih) && aligned16(grad_w_hh) && aligned16(grad_bias),
+    VQ_REQUIRE(aligned16(z, c, saved, grad_c, w.w_ih, w.w_hh, grad_z, grad_w_ih, grad_w_hh, grad_bias),
                "vqcpc_encoder_context_bwd: z, c, saved, the weights and the gradients must be 16-byte aligned");
     return vq_ctx_bwd(e->ctx, w, z, B, Tz, c, (const float *)saved, grad_c, grad_z, grad_w_ih, grad_w_hh, grad_bias, (hipStream_t)stream);
 }
@@ -320,27 +327,15 @@ static int front_grad_begin(vqcpc_encoder *e, const char *what, const float *mel
     VQ_REQUIRE(conv_mode >= 0 && conv_mode <= 2, "%s: conv_mode must be 0, 1 or 2", what);
     VQ_REQUIRE((long long)B * frames_of(T) <= (1ll << 22), "%s: B * (T / 2) = %lld rows, more than 2^22", what, (long long)B * frames_of(T));
     VQ_REQUIRE((long long)B * e->in_channels * T < (1ll << 31), "%s: mel of %lld elements, 2^31 or more", what, (long long)B * e->in_channels * T);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    VQ_REQUIRE(dev == e->device, "%s: handle belongs to device %d, current device is %d", what, e->device, dev);
+    TRY(vq_require_device(e->device, what));
     bool ok = aligned16(mel);
     if (w) {
-        fw.conv = w->conv_weight; fw.conv_w1 = fw.conv_w2 = nullptr;
-        fw.out_w = w->out_weight; fw.out_b = w->out_bias;
-        bool all = w->conv_weight && w->out_weight && w->out_bias;
-        ok = ok && aligned16(w->conv_weight) && aligned16(w->out_weight) && aligned16(w->out_bias);
-        for (int i = 0; i < 5; ++i) {
-            fw.ln_g[i] = w->ln_weight[i]; fw.ln_b[i] = w->ln_bias[i];
-            all = all && w->ln_weight[i] && w->ln_bias[i];
-            ok = ok && aligned16(w->ln_weight[i]) && aligned16(w->ln_bias[i]);
-        }
-        for (int i = 0; i < 4; ++i) { fw.fc_w[i] = w->fc_weight[i]; all = all && w->fc_weight[i]; ok = ok && aligned16(w->fc_weight[i]); }
+        fw = FrontW{*w, nullptr, nullptr};
+        bool all = true;
+        for (const float *p : front_slots(*w)) { all = all && p; ok = ok && aligned16(p); }
         VQ_REQUIRE(all, "%s: a weights struct must give every front-end tensor (NULL struct = the handle's copies)", what);
     } else {
-        fw.conv = e->conv_w; fw.conv_w1 = e->conv_w1; fw.conv_w2 = e->conv_w2;
-        for (int i = 0; i < 5; ++i) { fw.ln_g[i] = e->ln_g[i]; fw.ln_b[i] = e->ln_b[i]; }
-        for (int i = 0; i < 4; ++i) fw.fc_w[i] = e->fc_w[i];
-        fw.out_w = e->out_w; fw.out_b = e->out_b;
+        fw = e->fw;
     }
     VQ_REQUIRE(ok, "%s: mel and the weights must be 16-byte aligned", what);
     return VQCPC_OK;
@@ -358,7 +353,7 @@ extern "C" int vqcpc_encoder_front_fwd(vqcpc_encoder *e, const float *mel, int B
     VQ_REQUIRE(z_pre && saved, "vqcpc_encoder_front_fwd: null argument");
     FrontW fw;
     TRY(front_grad_begin(e, "vqcpc_encoder_front_fwd", mel, B, T, conv_mode, w, fw));
-    VQ_REQUIRE(aligned16(z_pre) && aligned16(saved), "vqcpc_encoder_front_fwd: z_pre and saved must be 16-byte aligned");
+    VQ_REQUIRE(aligned16(z_pre, saved), "vqcpc_encoder_front_fwd: z_pre and saved must be 16-byte aligned");
     return vq_front_fwd(e->front, fw, e->lnc, mel, B, e->in_channels, T, resolve_conv_mode(e, conv_mode, B, T), z_pre, (float *)saved,
                         (hipStream_t)stream);
 }
@@ -369,18 +364,11 @@ extern "C" int vqcpc_encoder_front_bwd(vqcpc_encoder *e, const float *mel, int B
     VQ_REQUIRE(saved && grad_z_pre && grads, "vqcpc_encoder_front_bwd: null argument");
     FrontW fw;
     TRY(front_grad_begin(e, "vqcpc_encoder_front_bwd", mel, B, T, conv_mode, w, fw));
-    FrontG g;
-    g.conv = grads->conv_weight; g.out_w = grads->out_weight; g.out_b = grads->out_bias;
-    bool any = g.conv || g.out_w || g.out_b, ok = aligned16(saved) && aligned16(grad_z_pre) && aligned16(g.conv) && aligned16(g.out_w) && aligned16(g.out_b);
-    for (int i = 0; i < 5; ++i) {
-        g.ln_g[i] = grads->ln_weight[i]; g.ln_b[i] = grads->ln_bias[i];
-        any = any || g.ln_g[i] || g.ln_b[i];
-        ok = ok && aligned16(g.ln_g[i]) && aligned16(g.ln_b[i]);
-    }
-    for (int i = 0; i < 4; ++i) { g.fc_w[i] = grads->fc_weight[i]; any = any || g.fc_w[i]; ok = ok && aligned16(g.fc_w[i]); }
+    bool any = false, ok = aligned16(saved, grad_z_pre);
+    for (float *p : front_slots(*grads)) { any = any || p; ok = ok && aligned16(p); }
     VQ_REQUIRE(any, "vqcpc_encoder_front_bwd: no gradient asked for");
     VQ_REQUIRE(ok, "vqcpc_encoder_front_bwd: saved, grad_z_pre and the gradients must be 16-byte aligned");
-    return vq_front_bwd(e->front, fw, mel, B, e->in_channels, T, (const float *)saved, grad_z_pre, g, (hipStream_t)stream);
+    return vq_front_bwd(e->front, fw, mel, B, e->in_channels, T, (const float *)saved, grad_z_pre, *grads, (hipStream_t)stream);
 }
 
 extern "C" int vqcpc_encoder_vq_bwd(vqcpc_encoder *e, const float *z_pre, const float *z_q, int n_rows, const float *grad_z_st,
@@ -388,11 +376,9 @@ extern "C" int vqcpc_encoder_vq_bwd(vqcpc_encoder *e, const float *z_pre, const 
     VQ_REQUIRE(e && z_pre && z_q && grad_z_pre, "vqcpc_encoder_vq_bwd: null argument");
     VQ_REQUIRE(grad_z_st || grad_loss, "vqcpc_encoder_vq_bwd: give grad_z_st, grad_loss or both");
     VQ_REQUIRE(n_rows >= 1, "vqcpc_encoder_vq_bwd: n_rows must be at least 1 (got %d)", n_rows);
-    VQ_REQUIRE(aligned16(z_pre) && aligned16(z_q) && aligned16(grad_z_pre) && aligned16(grad_z_st),
+    VQ_REQUIRE(aligned16(z_pre, z_q, grad_z_pre, grad_z_st),
                "vqcpc_encoder_vq_bwd: the rows must be 16-byte aligned");
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    VQ_REQUIRE(dev == e->device, "vqcpc_encoder_vq_bwd: handle belongs to device %d, current device is %d", e->device, dev);
+    TRY(vq_require_device(e->device, "vqcpc_encoder_vq_bwd"));
     const float scale = (float)(0.5 / ((double)n_rows * (double)e->z_dim));
     launch_vq_bwd(z_pre, z_q, (size_t)n_rows * e->z_dim, scale, grad_z_st, grad_loss, grad_z_pre, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -432,7 +418,7 @@ extern "C" int vqcpc_encoder_vq_adapt(vqcpc_encoder *e, const float *x, int n_ro
     VQ_REQUIRE(n_rows >= 1 && n_rows <= (1 << 24), "vqcpc_encoder_vq_adapt: n_rows must be in [1, 2^24] (got %d)", n_rows);
     VQ_REQUIRE(decay > 0.0 && decay < 1.0, "vqcpc_encoder_vq_adapt: decay must be in (0, 1) (got %g)", decay);
     VQ_REQUIRE(epsilon > 0.0, "vqcpc_encoder_vq_adapt: epsilon must be > 0 (got %g)", epsilon);
-    VQ_REQUIRE(((uintptr_t)x & 15) == 0, "vqcpc_encoder_vq_adapt: rows must be 16-byte aligned");
+    VQ_REQUIRE(aligned16(x), "vqcpc_encoder_vq_adapt: rows must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     size_t off[4];
     TRY(e->adapt.reserve(adapt_offsets(n_rows, e->n_emb, off)));

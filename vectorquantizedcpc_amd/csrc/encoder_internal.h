@@ -1,6 +1,7 @@
 // What the encoder's kernels (encoder.hip), its handle (encoder_host.hip) and the exact-chain GEMM (gemm_chain.hip) share.
 #pragma once
 #include "common.h"
+#include "../../include/vqcpc_grad.h"
 
 // ------------------------------------------------------------------------------------------
 // im2col of Conv1d(k = 4, stride 2, padding 1) over mel (B, C, T) (model.py:43, :65): GEMM row m = b * To + tt, column kidx.
@@ -79,17 +80,31 @@ void launch_ema_update(const EmaP &p, hipStream_t s);
 // ------------------------------------------------------------------------------------------
 // front_grad.hip: the front end of a training step and its backward (include/vqcpc_grad.h)
 // ------------------------------------------------------------------------------------------
-// The front end's weights as the kernels read them: the handle's copies, or a caller's tensors.
+// The front end's weights as the kernels read them: the handle's copies (built once at create), or a caller's tensors.
 struct FrontW {
-    const float *conv;                  // conv.weight (512, C, 4), the reference's layout
-    const float *conv_w1, *conv_w2;     // the same as a GEMM operand in the k order of conv mode 1, 2; null = build per call from `conv`
-    const float *ln_g[5], *ln_b[5];
-    const float *fc_w[4];
-    const float *out_w, *out_b;
+    vqcpc_encoder_front_weights t;      // the seventeen tensors in the reference's layouts (t.conv_weight: also the layout of its gradient)
+    const float *conv_w1, *conv_w2;     // conv.weight as a GEMM operand in the k order of conv mode 1, 2; null = build per call from t
 };
-struct FrontG {                         // gradients wanted (null = not)
-    float *conv, *ln_g[5], *ln_b[5], *fc_w[4], *out_w, *out_b;
-};
+using FrontG = vqcpc_encoder_front_grads;              // gradients wanted (null = not)
+// The seventeen slots of either struct as one array in member order: conv, 5 LayerNorm weights, 5 LayerNorm biases, 4 fc, out
+// weight, out bias -- the one way to walk them all.
+constexpr int FRONT_SLOTS = 17;
+static_assert(sizeof(vqcpc_encoder_front_weights) == FRONT_SLOTS * sizeof(void *) && sizeof(FrontG) == FRONT_SLOTS * sizeof(void *),
+              "the front-end structs are seventeen pointers and nothing else");
+inline const float *const (&front_slots(const vqcpc_encoder_front_weights &w))[FRONT_SLOTS] {
+    return reinterpret_cast<const float *const (&)[FRONT_SLOTS]>(w);
+}
+inline float *const (&front_slots(const FrontG &g))[FRONT_SLOTS] { return reinterpret_cast<float *const (&)[FRONT_SLOTS]>(g); }
+
+// Where a call of the layered schedule leaves its rows, per layer l = 0 .. 4: x[l] (N, 512) the rows entering LayerNorm l (the conv's
+// or an FC's output), a[l] (N, 512) the rows leaving its ReLU, stat[l] (N, 2) that LayerNorm's (mean, rstd) or null = not kept;
+// z_pre (N, 64), needed for stage 10 only.  Layers may share buffers wherever a row is dead before it is overwritten.
+struct FrontDst { float *x[5], *a[5], *stat[5], *z_pre; };
+// THE layered schedule (encoder_host.hip): conv as an im2col GEMM, then LayerNorm + ReLU and FC in turn, up to `stop_stage`
+// (0 conv, 1 + 2l LN_l + ReLU, 2 + 2l FC_l, 10 z_pre), every GEMM an exact chain with fixed K blocks.  C = in_channels, conv_mode
+// 1 or 2 (resolved), w.conv_w1 / conv_w2 given.  *stage_out = the buffer of `d` that holds the stop stage's rows.
+int vq_front_chain(const FrontW &w, const LnConst &lnc, const float *mel, int B, int C, int T, int conv_mode, int stop_stage,
+                   const FrontDst &d, const float **stage_out, hipStream_t s);
 // The work space of both calls, grow-only, a member of the encoder handle.
 struct FrontGradWork {
     DevBuf convw;                       // forward, caller's weights: conv.weight in the two k orders

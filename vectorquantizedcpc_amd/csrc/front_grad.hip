@@ -7,9 +7,10 @@
 // memory, no wait on another workgroup; launch boundaries order the passes.  Equal inputs give equal bits.  Every operation below
 // is one separately rounded fp32 operation (-ffp-contract=off); every accumulator starts from +0.
 //
-// Forward (vq_front_fwd): the layered schedule of encoder_host.hip -- vq_gemm_chain_im2col, launch_ln512, vq_gemm_chain with the
-//   same K blocks -- writing straight into `saved`, so z_pre has the bits of vqcpc_encoder_stage(10).  saved = x_0 .. x_4 (R, 512
-//   each), a_0 .. a_4 (R, 512 each), then (mean, rstd) of every row of LN_0 .. LN_4 (R, 2 each) as ln512_kernel computed them.
+// Forward (vq_front_fwd): vq_front_chain of encoder_host.hip, the function that IS the layered schedule of vqcpc_encoder_stage,
+//   called with the views of `saved` as its destinations, so z_pre has the bits of vqcpc_encoder_stage(10).  saved = x_0 .. x_4
+//   (R, 512 each), a_0 .. a_4 (R, 512 each), then (mean, rstd) of every row of LN_0 .. LN_4 (R, 2 each) as ln512_kernel computed
+//   them.  A caller's conv.weight is first brought into the two k orders (launch_conv_weight_permute), in stream order.
 //
 // Backward (vq_front_bwd), from the top; G = dLoss / dz_pre (R, 64); a pass whose products nobody asked for is not launched:
 //   dW_out = G^T a_4, dW_l = dy_{l+1}^T a_l, dW_conv = dy_0^T im2col(mel): front_grad_w_kernel, grid (column pairs of tiles of 16,
@@ -188,13 +189,12 @@ __global__ __launch_bounds__(256) void vq_bwd_kernel(const float *__restrict__ z
     out[e] = grad_z_st ? grad_z_st[e] + t : t;
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct SavedView { float *x[5], *a[5], *stat[5]; };
-SavedView saved_view(const float *saved, size_t R) {
+// `saved` as the layered schedule's destinations: every layer's rows and statistics in a place of their own.
+FrontDst saved_view(const float *saved, size_t R, float *z_pre = nullptr) {
     float *s = const_cast<float *>(saved);
-    SavedView v;
+    FrontDst v;
     for (int l = 0; l < 5; ++l) { v.x[l] = s + l * R * CH; v.a[l] = s + (5 + l) * R * CH; v.stat[l] = s + 10 * R * CH + l * 2 * R; }
+    v.z_pre = z_pre;
     return v;
 }
 
@@ -209,41 +209,32 @@ void launch_vq_bwd(const float *z_pre, const float *z_q, size_t n, float scale, 
 
 int vq_front_fwd(FrontGradWork &k, FrontW w, const LnConst &lnc, const float *mel, int B, int C, int T, int conv_mode, float *z_pre,
                  float *saved, hipStream_t s) {
-    const int To = (T - 2) / 2 + 1, N = B * To;
     if (!w.conv_w1) {                                    // a caller's conv.weight: the two k orders, in stream order
         const size_t nconv = (size_t)CH * C * 4;
         TRY(k.convw.reserve(2 * nconv * sizeof(float)));
         float *w1 = k.convw.as<float>(), *w2 = w1 + nconv;
-        launch_conv_weight_permute(w.conv, w1, w2, CH, C, s);
+        launch_conv_weight_permute(w.t.conv_weight, w1, w2, CH, C, s);
         w.conv_w1 = w1; w.conv_w2 = w2;
     }
-    const SavedView v = saved_view(saved, (size_t)N);
-    const bool one_chain = conv_mode == VQCPC_CONV_IM2COL;
-    TRY(vq_gemm_chain_im2col(mel, C, T, To, one_chain ? w.conv_w1 : w.conv_w2, v.x[0], N, CH, one_chain ? 4 * C : 64, conv_mode, s));
-    for (int l = 0; l < 5; ++l) {
-        launch_ln512(v.x[l], w.ln_g[l], w.ln_b[l], v.a[l], N, 1e-5f, 1, lnc, s, v.stat[l]);
-        if (l < 4) TRY(vq_gemm_chain(v.a[l], CH, w.fc_w[l], nullptr, v.x[l + 1], CH, N, CH, CH, 256, s));
-    }
-    TRY(vq_gemm_chain(v.a[4], CH, w.out_w, w.out_b, z_pre, ZD, N, ZD, CH, 256, s));
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
+    const float *unused = nullptr;
+    return vq_front_chain(w, lnc, mel, B, C, T, conv_mode, 10, saved_view(saved, (size_t)B * ((T - 2) / 2 + 1), z_pre), &unused, s);
 }
 
 int vq_front_bwd(FrontGradWork &k, const FrontW &w, const float *mel, int B, int C, int T, const float *saved, const float *grad_z_pre,
                  const FrontG &g, hipStream_t s) {
     const int To = (T - 2) / 2 + 1, R = B * To;
     const int slabs = (R + GRAD_SLAB - 1) / GRAD_SLAB, tiles = (R + LN_TILE - 1) / LN_TILE;
-    const SavedView v = saved_view(saved, (size_t)R);
+    const FrontDst v = saved_view(saved, (size_t)R);
     // how far down the chain goes: da_l is needed for LN_l's own gradients and for dy_l; dy_l for the weight below it and for da_{l-1}
     bool need_da[5], need_dy[5];
     for (int l = 0; l < 5; ++l) {
-        need_dy[l] = l == 0 ? g.conv != nullptr : (g.fc_w[l - 1] != nullptr || need_da[l - 1]);
-        need_da[l] = g.ln_g[l] || g.ln_b[l] || need_dy[l];
+        need_dy[l] = l == 0 ? g.conv_weight != nullptr : (g.fc_weight[l - 1] != nullptr || need_da[l - 1]);
+        need_da[l] = g.ln_weight[l] || g.ln_bias[l] || need_dy[l];
     }
-    bool any_w = g.conv || g.out_w || g.out_b, any_ln = false;
-    for (int l = 0; l < 4; ++l) any_w = any_w || g.fc_w[l];
-    for (int l = 0; l < 5; ++l) any_ln = any_ln || g.ln_g[l] || g.ln_b[l];
-    const int kmax = g.conv && 4 * C > CH ? 4 * C : CH;
+    bool any_w = g.conv_weight || g.out_weight || g.out_bias, any_ln = false;
+    for (int l = 0; l < 4; ++l) any_w = any_w || g.fc_weight[l];
+    for (int l = 0; l < 5; ++l) any_ln = any_ln || g.ln_weight[l] || g.ln_bias[l];
+    const int kmax = g.conv_weight && 4 * C > CH ? 4 * C : CH;
     if (any_w) TRY(k.part.reserve(up256((size_t)slabs * CH * kmax * sizeof(float))));
     if (any_ln) TRY(k.colpart.reserve(up256((size_t)(tiles + slabs) * 2 * CH * sizeof(float))));      // tile partials, then slab sums
     if (need_da[4]) {
@@ -261,46 +252,46 @@ int vq_front_bwd(FrontGradWork &k, const FrontW &w, const float *mel, int B, int
     };
 
     // the out layer (model.py:55)
-    if (g.out_w) {
+    if (g.out_weight) {
         hipLaunchKernelGGL((front_grad_w_kernel<false, 1>), dim3(CH / 32, ZD / 64, slabs), blk, 0, s, grad_z_pre, ZD, (const float *)v.a[4], CH,
                            nullptr, 0, 0, 0, part, R);
-        finish(g.out_w, (size_t)ZD * CH);
+        finish(g.out_weight, (size_t)ZD * CH);
     }
-    if (g.out_b) {
+    if (g.out_bias) {
         hipLaunchKernelGGL(front_grad_bias_kernel, dim3(slabs), blk, 0, s, grad_z_pre, part, R);
-        finish(g.out_b, ZD);
+        finish(g.out_bias, ZD);
     }
     float *d = k.d0.as<float>(), *dn = k.d1.as<float>();
     if (need_da[4]) {
-        transpose(w.out_w, ZD, CH);                                           // (512, 64): da_4 = G W_out
+        transpose(w.t.out_weight, ZD, CH);                                    // (512, 64): da_4 = G W_out
         TRY(vq_gemm_chain(grad_z_pre, ZD, wT, nullptr, d, CH, R, CH, ZD, 64, s));
     }
     for (int l = 4; l >= 0 && need_da[l]; --l) {
-        const bool ln = g.ln_g[l] || g.ln_b[l];
+        const bool ln = g.ln_weight[l] || g.ln_bias[l];
         hipLaunchKernelGGL(front_ln_bwd_kernel, dim3(tiles), blk, 0, s, d, (const float *)v.x[l], (const float *)v.a[l],
-                           (const float *)v.stat[l], w.ln_g[l], ln ? k.colpart.as<float>() : nullptr, R);
+                           (const float *)v.stat[l], w.t.ln_weight[l], ln ? k.colpart.as<float>() : nullptr, R);
         if (ln) {                                                             // the tile partials by slab, then the slabs in order
             const float *slabpart = k.colpart.as<float>() + (size_t)tiles * 2 * CH;
             hipLaunchKernelGGL(front_ln_slab_kernel, dim3(slabs, 2 * CH / 64), blk, 0, s, (const float *)k.colpart.as<float>(),
                                k.colpart.as<float>() + (size_t)tiles * 2 * CH, tiles);
-            if (g.ln_b[l]) hipLaunchKernelGGL(front_sum_parts_kernel, dim3(CH / 256), blk, 0, s, slabpart, g.ln_b[l], slabs, (size_t)CH, (size_t)2 * CH);
-            if (g.ln_g[l]) hipLaunchKernelGGL(front_sum_parts_kernel, dim3(CH / 256), blk, 0, s, slabpart + CH, g.ln_g[l], slabs, (size_t)CH, (size_t)2 * CH);
+            if (g.ln_bias[l]) hipLaunchKernelGGL(front_sum_parts_kernel, dim3(CH / 256), blk, 0, s, slabpart, g.ln_bias[l], slabs, (size_t)CH, (size_t)2 * CH);
+            if (g.ln_weight[l]) hipLaunchKernelGGL(front_sum_parts_kernel, dim3(CH / 256), blk, 0, s, slabpart + CH, g.ln_weight[l], slabs, (size_t)CH, (size_t)2 * CH);
         }
         if (l == 0) {
-            if (g.conv) {                                                     // dW_conv in the layout of conv.weight: k = 4 c + tap
+            if (g.conv_weight) {                                              // dW_conv in the layout of conv.weight: k = 4 c + tap
                 hipLaunchKernelGGL((front_grad_w_kernel<true, 2>), dim3(4 * C / 32, CH / 128, slabs), blk, 0, s, (const float *)d, CH, nullptr,
                                    4 * C, mel, C, T, To, part, R);
-                finish(g.conv, (size_t)CH * 4 * C);
+                finish(g.conv_weight, (size_t)CH * 4 * C);
             }
             break;
         }
-        if (g.fc_w[l - 1]) {
+        if (g.fc_weight[l - 1]) {
             hipLaunchKernelGGL((front_grad_w_kernel<false, 2>), dim3(CH / 32, CH / 128, slabs), blk, 0, s, (const float *)d, CH,
                                (const float *)v.a[l - 1], CH, nullptr, 0, 0, 0, part, R);
-            finish(g.fc_w[l - 1], (size_t)CH * CH);
+            finish(g.fc_weight[l - 1], (size_t)CH * CH);
         }
         if (need_da[l - 1]) {
-            transpose(w.fc_w[l - 1], CH, CH);
+            transpose(w.t.fc_weight[l - 1], CH, CH);
             TRY(vq_gemm_chain(d, CH, wT, nullptr, dn, CH, R, CH, CH, 64, s));
             float *t = d; d = dn; dn = t;
         }

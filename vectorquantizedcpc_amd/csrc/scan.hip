@@ -55,16 +55,23 @@ __global__ __launch_bounds__(256) void seq_step_kernel(SeqP p, int step) {
     seq_step_body<G, SW, false>(p, step, SeqSave{});
 }
 
-template <int G>
-static int launch_seq(const SeqP &p, int step, hipStream_t s) {
-    const int SW = p.H / 64;
+// The LSTM step that also stores what back-propagation through time reads again (context_grad.hip).
+template <int SW>
+__global__ __launch_bounds__(256) void seq_step_save_kernel(SeqP p, int step, SeqSave sv) {
+    seq_step_body<4, SW, true>(p, step, sv);
+}
+
+template <int G, bool SAVE = false>
+static int launch_seq(const SeqP &p, int step, hipStream_t s, const SeqSave &sv = SeqSave{}) {
+    static_assert(!SAVE || G == 4, "only the LSTM step saves");
     dim3 grid(p.H / 4, p.ndir, p.nbt), blk(256);
-    switch (SW) {
-#define CASE(n) case n: hipLaunchKernelGGL((seq_step_kernel<G, n>), grid, blk, 0, s, p, step); break;
-        CASE(1) CASE(2) CASE(4) CASE(8)         // hidden sizes 64, 128 (the reference's prenet), 256 (its context LSTM), 512
-#undef CASE
-        default: vq_set_error("recurrent step: hidden size %d unsupported (64, 128, 256 and 512 are built)", p.H); return VQCPC_ERR_INVALID;
-    }
+    // hidden sizes 64, 128 (the reference's prenet), 256 (its context LSTM), 512
+    const bool built = vq_with_sw(p.H / 64, [&](auto sw) {
+        constexpr int SW = decltype(sw)::value;
+        if constexpr (SAVE) hipLaunchKernelGGL((seq_step_save_kernel<SW>), grid, blk, 0, s, p, step, sv);
+        else hipLaunchKernelGGL((seq_step_kernel<G, SW>), grid, blk, 0, s, p, step);
+    });
+    if (!built) { vq_set_error("recurrent step: hidden size %d unsupported (64, 128, 256 and 512 are built)", p.H); return VQCPC_ERR_INVALID; }
     return VQCPC_OK;
 }
 
@@ -89,7 +96,8 @@ struct LstmPlan {
     int D, H;
     DevPtr<float> w_ih, bias, Wf;
     DevPtr<float> w_hh;                  // plain [4H][H] copy for the persistent single-utterance scan
-    DevBuf gi, hbuf, cbuf, px;
+    LstmScratch k;
+    DevBuf px;
     PinnedWord abort;                    // a timed-out exchange of the persistent scan is reported by the next call
     int persistent = -1;                 // -1 auto (one utterance, H = 256), 0 off, 2 = auto with agent-scope stores forced (tests)
     bool pending = false;                // a persistent scan may have raised the flag
@@ -133,25 +141,33 @@ int vq_lstm_check(LstmPlan *p) {
     }
     return VQCPC_OK;
 }
+static size_t lstm_tile_bytes(int B, int H) { return (size_t)((B + 15) / 16) * H * 16 * sizeof(float); }
+int vq_lstm_project(LstmScratch &k, const LstmWeights &w, const float *x, int B, int T, hipStream_t s) {
+    const int H = w.H;
+    TRY(k.gi.reserve((size_t)B * T * 4 * H * sizeof(float)));
+    TRY(k.hbuf.reserve(2 * lstm_tile_bytes(B, H)));
+    TRY(k.cbuf.reserve(lstm_tile_bytes(B, H)));
+    return vq_gemm_chain(x, w.D, w.w_ih, w.bias, k.gi.as<float>(), 4 * H, B * T, 4 * H, w.D, w.D, s);
+}
+int vq_lstm_steps(LstmScratch &k, const LstmWeights &w, int B, int T, float *out, const SeqSave *save, hipStream_t s) {
+    const size_t hsz = lstm_tile_bytes(B, w.H);
+    HIP_TRY(hipMemsetAsync(k.hbuf.p, 0, 2 * hsz, s));
+    HIP_TRY(hipMemsetAsync(k.cbuf.p, 0, hsz, s));
+    SeqP q{};
+    q.Wf = w.Wf; q.Gi = k.gi.as<float>(); q.hbuf = k.hbuf.as<float>(); q.cbuf = k.cbuf.as<float>();
+    q.out = out; q.len = nullptr; q.H = w.H; q.nbt = (B + 15) / 16; q.B = B; q.T = T; q.ndir = 1;
+    for (int t = 0; t < T; ++t) TRY((save ? launch_seq<4, true>(q, t, s, *save) : launch_seq<4>(q, t, s)));
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
 int vq_lstm_run(LstmPlan *p, const float *x, int B, int T, float *out, hipStream_t s) {
-    const int H = p->H, nbt = (B + 15) / 16;
-    TRY(p->gi.reserve((size_t)B * T * 4 * H * sizeof(float)));
-    const size_t hsz = (size_t)nbt * H * 16 * sizeof(float);
-    TRY(p->hbuf.reserve(2 * hsz));
-    TRY(p->cbuf.reserve(hsz));
-    TRY(vq_gemm_chain(x, p->D, p->w_ih, p->bias, p->gi.as<float>(), 4 * H, B * T, 4 * H, p->D, p->D, s));
+    const LstmWeights w = vq_lstm_plan_weights(p);
+    TRY(vq_lstm_project(p->k, w, x, B, T, s));
     TRY(vq_lstm_check(p));               // did an earlier persistent scan report a timeout?  (no HIP call: host-mapped word)
     // encode.py:42-46 calls encode() on ONE utterance at a time: that scan is a chain of T dependent 256-value exchanges,
     // 3.6 us each as launches, < 1 us each inside one resident kernel
-    if (p->persistent != 0 && B == 1 && H == 256 && T >= 1) return lstm_persist_launch(p, T, out, s);
-    HIP_TRY(hipMemsetAsync(p->hbuf.p, 0, 2 * hsz, s));
-    HIP_TRY(hipMemsetAsync(p->cbuf.p, 0, hsz, s));
-    SeqP q{};
-    q.Wf = p->Wf; q.Gi = p->gi.as<float>(); q.hbuf = p->hbuf.as<float>(); q.cbuf = p->cbuf.as<float>();
-    q.out = out; q.len = nullptr; q.H = H; q.nbt = nbt; q.B = B; q.T = T; q.ndir = 1;
-    for (int t = 0; t < T; ++t) TRY(launch_seq<4>(q, t, s));
-    HIP_TRY(hipGetLastError());
-    return VQCPC_OK;
+    if (p->persistent != 0 && B == 1 && p->H == 256 && T >= 1) return lstm_persist_launch(p, T, out, s);
+    return vq_lstm_steps(p->k, w, B, T, out, nullptr, s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -329,7 +345,7 @@ static int lstm_persist_launch(LstmPlan *p, int T, float *out, hipStream_t s) {
     TRY(p->px.reserve(bytes));
     HIP_TRY(hipMemsetAsync(p->px.p, 0, bytes, s));
     LstmPersistP q{};
-    q.w_hh = p->w_hh; q.Gi = p->gi.as<float>(); q.out = out; q.g = p->px.as<u64>(); q.T = T;
+    q.w_hh = p->w_hh; q.Gi = p->k.gi.as<float>(); q.out = out; q.g = p->px.as<u64>(); q.T = T;
     q.force_agent = p->persistent == 2;
     q.dbg_drop_step = p->dbg_drop_step;
     q.timeout_ticks = (unsigned)p->timeout_ms * 100000u;

@@ -1,5 +1,5 @@
 // One time step of a recurrence whose input projection is hoisted (prenet bi-GRU, encoder LSTM): the statements shared by
-// seq_step_kernel of scan.hip and the state-keeping forward of context_grad.hip, so that both give the same bits.
+// seq_step_kernel and seq_step_save_kernel of scan.hip (the latter serves context_grad.hip), so that both give the same bits.
 // Weights in fragment order (scan.hip, build_wfrag_kernel), one 16-row x 16-utterance MFMA tile per workgroup, K over 4 waves.
 #pragma once
 #include "common.h"

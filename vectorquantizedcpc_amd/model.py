@@ -31,6 +31,25 @@ class ConfEncoder:
     c_dim: int = MISSING
 
 
+def _vq_eval(h, xf: Tensor, q: Optional[Tensor] = None, idx: Optional[Tensor] = None, stats: bool = True):
+    """The eval VQ step (``model.py:103-134``, ``:147-153``) on the native handle ``h`` over rows xf (N, z_dim) fp32, contiguous:
+    ``vqcpc_encoder_vq_encode`` -- unless the caller has ``q`` and ``idx`` of these rows already (``vqcpc_encoder_encode`` gives
+    them) -- then, with ``stats``, ``vqcpc_encoder_forward_stats``.  -> (q, idx, z_st, [loss, perplexity]), the last two None
+    without ``stats``.  The caller chooses the handle, and with it the moment a stale one is rebuilt."""
+    lib, dev, N = _lib.load(), xf.device, xf.size(0)
+    z_st = st = None
+    with _lib.device_guard(dev):
+        if q is None:
+            q = torch.empty_like(xf)
+            idx = torch.empty(N, dtype=torch.int64, device=dev)
+            _lib.check(lib.vqcpc_encoder_vq_encode(h, xf.data_ptr(), N, q.data_ptr(), idx.data_ptr(), _lib.current_stream()))
+        if stats:
+            z_st, st = torch.empty_like(xf), torch.empty(2, device=dev)
+            _lib.check(lib.vqcpc_encoder_forward_stats(h, xf.data_ptr(), q.data_ptr(), idx.data_ptr(), N, z_st.data_ptr(),
+                                                       st[0:].data_ptr(), st[1:].data_ptr(), _lib.current_stream()))
+    return q, idx, z_st, st
+
+
 class VQEmbeddingEMA(nn.Module):
     """Codebook buffers (``model.py:89-101``) + the reference's public ``encode`` / ``forward`` (``model.py:103-155``) as thin
     wrappers over the owning ``Encoder``'s native handle (the same VQ kernel ``Encoder.encode`` runs).  In training mode
@@ -67,20 +86,11 @@ class VQEmbeddingEMA(nn.Module):
             raise RuntimeError(f"expected x of shape (Batch, Time, {D}), got {tuple(x.shape)}")
         return owner, x.detach().to(torch.float32).reshape(-1, D).contiguous()
 
-    def _rows(self, x: Tensor):
-        owner, xf = self._flat(x)
-        q = torch.empty_like(xf)
-        idx = torch.empty(xf.size(0), dtype=torch.int64, device=x.device)
-        h = owner._native()
-        with _lib.device_guard(x.device):
-            _lib.check(_lib.load().vqcpc_encoder_vq_encode(h, xf.data_ptr(), xf.size(0), q.data_ptr(), idx.data_ptr(),
-                                                           _lib.current_stream()))
-        return owner, h, xf, q, idx
-
     @torch.no_grad()
     def encode(self, x: Tensor):
         """``model.py:103-115``: (quantized, indices (Batch, Time))."""
-        _, _, _, q, idx = self._rows(x)
+        owner, xf = self._flat(x)
+        q, idx, _, _ = _vq_eval(owner._native(), xf, stats=False)
         return q.view_as(x), idx.view(x.size(0), x.size(1))
 
     def forward(self, x: Tensor):
@@ -97,13 +107,8 @@ class VQEmbeddingEMA(nn.Module):
                 stats = owner._adapt_rows(xf, z_st)
             return z_st.view_as(x), stats[0], stats[1]
         with torch.no_grad():
-            _, h, xf, q, idx = self._rows(x)
-            z_st = torch.empty_like(xf)
-            stats = torch.empty(2, device=x.device)
-            with _lib.device_guard(x.device):
-                _lib.check(_lib.load().vqcpc_encoder_forward_stats(h, xf.data_ptr(), q.data_ptr(), idx.data_ptr(), xf.size(0),
-                                                                   z_st.data_ptr(), stats[0:].data_ptr(), stats[1:].data_ptr(),
-                                                                   _lib.current_stream()))
+            owner, xf = self._flat(x)
+            _, _, z_st, stats = _vq_eval(owner._native(), xf)
         return z_st.view_as(x), stats[0], stats[1]
 
 
@@ -129,13 +134,7 @@ class Encoder(_lib.NativeModule):
                       "codebook.embedding", "rnn.weight_ih_l0", "rnn.weight_hh_l0", "rnn.bias_ih_l0", "rnn.bias_hh_l0"])
 
     def _weights(self, p):
-        w = _lib.EncoderWeights()
-        w.conv_weight = p("conv.weight")
-        for i, n in enumerate((0, 3, 6, 9, 12)):
-            w.ln_weight[i], w.ln_bias[i] = p(f"encoder.{n}.weight"), p(f"encoder.{n}.bias")
-        for i, n in enumerate((2, 5, 8, 11)):
-            w.fc_weight[i] = p(f"encoder.{n}.weight")
-        w.out_weight, w.out_bias = p("encoder.14.weight"), p("encoder.14.bias")
+        w = _lib.fill_front(_lib.EncoderWeights(), [p(n) for n in self._FRONT_NAMES])
         w.codebook = p("codebook.embedding")
         w.rnn_w_ih, w.rnn_w_hh = p("rnn.weight_ih_l0"), p("rnn.weight_hh_l0")
         w.rnn_b_ih, w.rnn_b_hh = p("rnn.bias_ih_l0"), p("rnn.bias_hh_l0")
@@ -274,15 +273,6 @@ class Encoder(_lib.NativeModule):
     # ------------------------------------------------------------------ the context LSTM and its gradient
     _RNN_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
 
-    def _sizes_handle(self, dev):
-        """The handle for a call that reads the LSTM's weights from the CALLER's pointers (``vqcpc_encoder_context_fwd`` /
-        ``_bwd``): it gives sizes and work space only, so any live handle on ``dev`` serves -- also one whose copies an optimizer
-        step has made stale (``CPCLoss._sizes_handle`` is the same rule).  ``encode`` / ``forward`` still go through ``_native()``,
-        which rebuilds once when it sees the moved ``_version``."""
-        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
-            return self._handle
-        return self._native()
-
     def _rnn_weights(self, dev):
         ws = [getattr(self.rnn, n) for n in self._RNN_NAMES]
         for n, t in zip(self._RNN_NAMES, ws):
@@ -361,15 +351,7 @@ class Encoder(_lib.NativeModule):
     @staticmethod
     def _front_struct(tensors):
         """17 tensors (or None) in ``_FRONT_NAMES`` order -> ``_lib.EncoderFrontTensors``."""
-        ptr = [t.data_ptr() if t is not None else None for t in tensors]
-        s = _lib.EncoderFrontTensors()
-        s.conv_weight = ptr[0]
-        for i in range(5):
-            s.ln_weight[i], s.ln_bias[i] = ptr[1 + i], ptr[6 + i]
-        for i in range(4):
-            s.fc_weight[i] = ptr[11 + i]
-        s.out_weight, s.out_bias = ptr[15], ptr[16]
-        return s
+        return _lib.fill_front(_lib.EncoderFrontTensors(), [t.data_ptr() if t is not None else None for t in tensors])
 
     def _check_mels(self, mels: Tensor) -> Tensor:
         _lib.require_cuda(mels, "mel")
@@ -433,32 +415,24 @@ class Encoder(_lib.NativeModule):
         """The handle for a call that reads only the CODEBOOK from the handle's copies (``quantize``): a live handle on ``dev`` whose
         codebook is current serves, also one whose other copies an optimizer step has made stale -- a fit of the front end costs no
         new handle per step.  (``vqcpc_encoder_vq_adapt`` keeps the handle's codebook and the buffer in step.)"""
-        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
-            i = 2 + self._WEIGHT_NAMES.index("codebook.embedding")
-            e = self.codebook.embedding
-            if self._handle_key[i] == (e.data_ptr(), e._version):
-                return self._handle
+        h = self._live_handle(dev)
+        e = self.codebook.embedding
+        if h is not None and self._handle_key[2 + self._WEIGHT_NAMES.index("codebook.embedding")] == (e.data_ptr(), e._version):
+            return h
         return self._native()
 
     def _quantize_rows(self, xf: Tensor, adapt: bool, want_q: bool):
         """The VQ step over rows xf (N, z_dim) fp32 contiguous -> (z_st, stats = [loss, perplexity], idx, q or None): the codebook
         as it is on entry decides all four; with ``adapt`` the EMA update follows (``vqcpc_encoder_vq_adapt``)."""
-        N, dev = xf.size(0), xf.device
-        z_st = torch.empty_like(xf)
-        idx = torch.empty(N, dtype=torch.int64, device=dev)
-        q = None
-        lib, h = _lib.load(), self._codebook_handle(dev)
+        h = self._codebook_handle(xf.device)
+        q = idx = z_st = stats = None
         if want_q or not adapt:
-            q = torch.empty_like(xf)
-            with _lib.device_guard(dev):
-                _lib.check(lib.vqcpc_encoder_vq_encode(h, xf.data_ptr(), N, q.data_ptr(), idx.data_ptr(), _lib.current_stream()))
+            q, idx, z_st, stats = _vq_eval(h, xf, stats=not adapt)
         if adapt:
+            z_st = torch.empty_like(xf)
+            if idx is None:
+                idx = torch.empty(xf.size(0), dtype=torch.int64, device=xf.device)
             stats = self._adapt_rows(xf, z_st, idx, handle=h)
-        else:
-            stats = torch.empty(2, device=dev)
-            with _lib.device_guard(dev):
-                _lib.check(lib.vqcpc_encoder_forward_stats(h, xf.data_ptr(), q.data_ptr(), idx.data_ptr(), N, z_st.data_ptr(),
-                                                           stats[0:].data_ptr(), stats[1:].data_ptr(), _lib.current_stream()))
         return z_st, stats, idx, q
 
     def quantize(self, z_pre: Tensor, *, differentiable: bool = False, adapt: bool = False):
@@ -499,15 +473,12 @@ class Encoder(_lib.NativeModule):
         with torch.no_grad():
             zq, _, idx, z_pre = self._encode_native(mels, want_c=False, want_pre=True)
             B, Tz, D = zq.shape
-            z_st = torch.empty_like(zq)
-            stats = torch.empty(2, device=zq.device)
+            h = self._native()
+            _, _, z_st, stats = _vq_eval(h, z_pre.view(-1, D), zq.view(-1, D), idx.view(-1))
             c = torch.empty(B, Tz, self.conf.c_dim, device=zq.device)
-            lib, h, s = _lib.load(), self._native(), _lib.current_stream()
             with _lib.device_guard(zq.device):
-                _lib.check(lib.vqcpc_encoder_forward_stats(h, z_pre.data_ptr(), zq.data_ptr(), idx.data_ptr(), B * Tz,
-                                                           z_st.data_ptr(), stats[0:].data_ptr(), stats[1:].data_ptr(), s))
-                _lib.check(lib.vqcpc_encoder_context(h, z_st.data_ptr(), B, Tz, c.data_ptr(), s))
-        return z_st, c, stats[0], stats[1]
+                _lib.check(_lib.load().vqcpc_encoder_context(h, z_st.data_ptr(), B, Tz, c.data_ptr(), _lib.current_stream()))
+        return z_st.view_as(zq), c, stats[0], stats[1]
 
 
 @dataclass
@@ -625,15 +596,6 @@ class CPCLoss(_lib.NativeModule):
                 correct.data_ptr() if correct is not None else None, scores.data_ptr() if scores is not None else None,
                 _lib.current_stream()))
         return {"loss": out[0], "step_loss": out[1:1 + K], "accuracy": out[1 + K:], "correct": correct, "scores": scores}
-
-    def _sizes_handle(self, dev):
-        """The handle for a call that reads the predictors from the CALLER's pointers (``vqcpc_cpc_grad``): it gives sizes and
-        work space only, so any live handle on ``dev`` serves -- also one whose copies an optimizer step has made stale.
-        ``_native()`` would answer the moved ``WeightSlots.key`` with destroy, create and a synchronisation per step; scoring
-        (``forward_detailed``) still goes through ``_native()`` and so never reads stale copies."""
-        if self._handle is not None and self._handle_key[:2] == (dev.type, dev.index):
-            return self._handle
-        return self._native()
 
     def _grad_call(self, z, c, W, b, utt, seq, seed, stream_id, want):
         """One ``vqcpc_cpc_grad`` call on contiguous fp32 device tensors.  want = (z, c, W, b) booleans.
