@@ -1,0 +1,109 @@
+"""-m gpu: the entries of ``include/vqcpc_vocoder_grad.h`` on a caller's stream -- the stream contract of ``include/vqcpc.h`` (*all
+work is enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly as tests/test_gpu_stream_contract.py
+and tests/test_gpu_front_grad_stream.py hold the entries of the first two headers.  This file keeps the table of the third header:
+
+  ==================================  ===  ====================================================================================
+  entry                               how  held by
+  ==================================  ===  ====================================================================================
+  vqcpc_vocoder_ar_fwd                N    test_ar_fwd_then_bwd_weights_in_stream_order
+  vqcpc_vocoder_ar_bwd                N    test_ar_bwd_alone
+  ==================================  ===  ====================================================================================
+
+N: does not synchronise (``busy`` is asserted).  A backward behind a forward of the same handle may wait for the staging arena of
+the forward's uploads, so the pair is probed after its first call and the backward is held on its own as well.
+``test_every_stream_entry_is_listed`` reads the header with the regular expression of tests/test_gpu_stream_contract.py and fails
+when an entry with a ``stream`` argument is missing above.
+"""
+import os
+import re
+
+import pytest
+import torch
+
+import stream_harness as H
+import voc_grad_ref as R
+import vectorquantizedcpc_amd as V
+from vectorquantizedcpc_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = {"vqcpc_vocoder_ar_fwd": "N", "vqcpc_vocoder_ar_bwd": "N"}
+CASE = "ragged"
+
+
+@pytest.fixture(scope="module", autouse=True)
+def release_what_this_file_holds():
+    """The cases, the references and the device buffers of this file are released when it is done, and the stream harness's
+    session-wide delay chain and report are left as they were found (tests/test_gpu_front_grad_stream.py says why)."""
+    found, reported = H._delay, len(H.REPORT)
+    yield
+    import gc
+    H._delay = found
+    del H.REPORT[reported:]
+    R._cases.clear()
+    R._refs.clear()
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def test_every_stream_entry_is_listed():
+    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_grad.h")).read()
+    found = set(re.findall(r"\bint\s+(vqcpc_\w+)\s*\([^;{]*?void\s*\*\s*stream\b[^;{]*?\)\s*;", text))
+    assert found == set(ENTRIES), (sorted(found - set(ENTRIES)), sorted(set(ENTRIES) - found))
+    for name, how in ENTRIES.items():
+        assert re.search(r"^  %s\s+%s\W" % (name, how), __doc__, re.M), name
+
+
+def setup():
+    """The vocoder of the case, and its true and decoy inputs: audio, z, speaker, the nine tensors of rnnms.ar, grad_loss."""
+    c = R.load(CASE)
+    voc = V.Vocoder(V.ConfVocoder(rnnms=V.ConfRNNMSVocoder(dim_voc_latent=c["C"], upsampling_t=c["up"],
+                                                           wave_ar=V.ConfWaveAR(size_i_embed_ar=c["de"], size_h_rnn=c["Hr"]))))
+    voc.load_state_dict(c["sd"])
+    voc = voc.cuda().eval()
+    B, Tc, L = c["B"], c["Tc"], c["L"]
+    true = [c["audio"].cuda(), c["z"].cuda(), c["spk"].cuda()] + [p.detach().clone() for p in voc._ar_params()] + \
+           [torch.tensor(1.5, device="cuda")]
+    other = synth.vocoder_state_dict(seed=99, dim_voc_latent=c["C"], size_i_embed_ar=c["de"], size_h_rnn=c["Hr"])
+    decoy = [synth.randint("voc_grad/sc_decoy/a", (B, L), 256).cuda(), synth.randint("voc_grad/sc_decoy/z", (B, Tc), 512).cuda(),
+             synth.randint("voc_grad/sc_decoy/s", (B,), 102).cuda()] + [other["rnnms.ar." + n].cuda() for n in R.SD_NAMES] + \
+            [torch.tensor(-0.5, device="cuda")]
+    return c, voc, true, decoy
+
+
+def test_ar_fwd_then_bwd_weights_in_stream_order():
+    """fwd then bwd back to back on ``s``; the audio, the codes, the speakers, the nine tensors and the upstream gradient are all
+    written on ``s`` behind the delay: the class table, the frame table, the unit quads and the W_hh fragments must be made from what
+    the stream holds when the call's turn comes."""
+    c, voc, true, decoy = setup()
+
+    def entry(audio, z, spk, *rest):
+        ws, gl = list(rest[:9]), rest[9]
+        call = voc._nll_call(audio, z, spk, c["lengths"], c["n_codes"])
+        nll_sum, n_scored, n_correct, cond, saved = voc._ar_fwd(call, ws, want_cond=True)
+        busy = H.probe()
+        grads, gc = voc._ar_bwd(call, saved, ws, gl, cond_grad=True)
+        return H.Early([nll_sum, n_scored, n_correct, cond] + grads + [gc], busy)
+
+    H.hold(entry, true, decoy, label="ar_fwd + ar_bwd " + CASE)
+
+
+def test_ar_bwd_alone():
+    """The backward as the first call on ``s``, with ``saved`` among the buffers written behind the delay."""
+    c, voc, true, decoy = setup()
+
+    def saved_of(inputs):
+        call = voc._nll_call(*inputs[:3], c["lengths"], c["n_codes"])
+        return torch.nan_to_num(voc._ar_fwd(call, list(inputs[3:12]))[4])     # rows no scored step wrote are never read: any finite value
+
+    true, decoy = true + [saved_of(true)], decoy + [saved_of(decoy)]
+    torch.cuda.synchronize()
+
+    def entry(audio, z, spk, *rest):
+        ws, gl, saved = list(rest[:9]), rest[9], rest[10]
+        call = voc._nll_call(audio, z, spk, c["lengths"], c["n_codes"])
+        grads, gc = voc._ar_bwd(call, saved, ws, gl, cond_grad=True)
+        return grads + [gc]
+
+    H.hold(entry, true, decoy, label="ar_bwd " + CASE)

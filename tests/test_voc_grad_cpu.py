@@ -1,0 +1,160 @@
+"""The vocoder gradients without a GPU: the float64 reference of tests/voc_grad_ref.py reproduces its pins and equals torch's own
+modules, the third header is exported, bound and plain C, the cases meet the conditions the GPU tests rely on, and the recorded
+float64 fit is a trend, not noise."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import grad_judge
+import voc_fit_ref
+import voc_grad_ref as R
+from vectorquantizedcpc_amd import _lib, cli, driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_reference_reproduces_its_pins(name):
+    grad_judge.check_pins(R.grads64(name), R.pins(), name, R.TENSORS, R.POSITIONS)
+
+
+@pytest.mark.parametrize("name", R.MODULE_CASES)
+def test_reference_equals_torch_modules(name):
+    """``nn.Embedding`` + ``nn.GRU`` + ``nn.Linear`` + ``F.cross_entropy`` autograd from the same state dict, within 1e-12 relative."""
+    ref, mod = R.grads64(name), R.module_grads(name)
+    assert len(set(R.load(name)["lengths"])) == 1
+    for k in R.TENSORS + ("loss",):
+        top = float(np.abs(mod[k]).max())
+        assert top > 0 and float(np.abs(ref[k] - mod[k]).max()) <= 1e-12 * top, (k, float(np.abs(ref[k] - mod[k]).max()), top)
+
+
+def test_cases_meet_their_conditions():
+    cs = {n: R.load(n) for n in R.ALL_CASES}
+    for n, c in cs.items():
+        assert len(c["lengths"]) == len(c["n_codes"]) == c["B"] and c["L"] >= max(c["lengths"])
+        for s, nc in zip(c["slen"], c["n_codes"]):
+            assert 0 <= nc <= c["Tc"] and s <= 2 * c["up"] * nc, n
+        assert max(c["slen"]) <= 1300 and sum(c["slen"]) > 0
+    c = cs["ref_sizes"]
+    assert (c["Hr"], c["de"], c["C"], c["up"], c["B"], c["Tc"], c["L"]) == (896, 256, 256, 160, 2, 1, 321) and max(c["slen"]) == 5 * 64
+    c = cs["ragged"]
+    s, up = c["slen"], c["up"]
+    assert c["B"] == 5 and s[0] == 0 and s[1] == 2 * up * c["n_codes"][1] and s[2] % up and s[2] < 2 * up * c["n_codes"][2]
+    assert s[4] > 64 and s[4] % 64 and s[3] % 64 and len(set(c["n_codes"])) == 5
+    c = cs["chunks"]
+    ch = c["options"]["tf_chunk_replays"] * 160                      # steps_per_graph at its default
+    s = sorted(c["slen"])
+    assert -(-s[-1] // ch) == 3 and s[-1] % ch and any(ch < v < 2 * ch for v in s)
+    assert cs["b1"]["B"] == 1 and cs["b17"]["B"] == 17 and cs["b32_big"]["B"] == 32 and cs["b32_big"]["options"] == {"big_min_tiles": 2}
+    assert (cs["h512"]["Hr"], cs["h1024"]["Hr"]) == (512, 1024) and all(cs[n]["de"] == 32 and cs[n]["C"] == 128 for n in ("h512", "h1024"))
+    assert cs["stressed"]["weights"] == "stressed" and cs["upstream"]["grad_loss"] not in (None, 1.0)
+    a = cs["const_audio"]["audio"]
+    assert int(a.min()) == int(a.max()) == 77
+    emb = R.grads64("const_audio")["embedding"]
+    assert not emb[np.arange(256) != 77].any() and emb[77].any()     # the float64 reference: rows of classes never fed are zero
+    gc = R.grads64("ragged")["grad_cond"]
+    for b, n in enumerate(cs["ragged"]["slen"]):
+        assert not gc[b, -(-n // 8):].any()                          # frames no scored step reads
+    assert -(-max(cs["long"]["slen"]) // 640) == 3                   # three chunks at the default chunk of 640
+
+
+def test_b_ih_and_b_hh_differ_in_the_n_third_only():
+    g = R.grads64("b1")
+    Hr = R.load("b1")["Hr"]
+    assert np.abs(g["b_ih"][:2 * Hr] - g["b_hh"][:2 * Hr]).max() <= 1e-15 and np.abs(g["b_ih"][2 * Hr:] - g["b_hh"][2 * Hr:]).max() > 1e-6
+
+
+def test_recorded_fit_is_a_trend():
+    losses = R.pins()["fit_ref_losses"]
+    assert losses.shape == (voc_fit_ref.STEPS,)
+    dec, spread = voc_fit_ref.decrease(losses), float(losses[-5:].max() - losses[-5:].min())
+    print(f"float64 fit: loss {losses[0]:.6f} -> mean of the last five {losses[-5:].mean():.6f}: decrease {dec:.4f}, spread of the last five {spread:.4f}")
+    assert dec > 0 and dec >= 3.0 * spread
+
+
+# ------------------------------------------------------------------ the header
+def declared():
+    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_grad.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(vqcpc_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_every_declared_symbol_is_exported_and_bound():
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    names = declared()
+    assert len(names) == 3
+    for n in names:
+        assert hasattr(lib, n), f"{n} declared in include/vqcpc_vocoder_grad.h but not exported"
+        assert getattr(_lib.load(), n).argtypes is not None, n
+    assert sorted(_lib.VOC_GRAD_SYMBOLS) == names
+    assert not set(_lib.VOC_GRAD_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.GRAD_SYMBOLS))
+    assert _lib.load().vqcpc_abi_version() == 1
+
+
+def test_header_is_plain_c(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('''#include "vqcpc_vocoder_grad.h"
+#include <stddef.h>
+int use(vqcpc_vocoder *voc, int64_t *i, float *p, double *d, void *saved, void *s) {
+    vqcpc_vocoder_ar_weights w;
+    vqcpc_vocoder_ar_grads g;
+    uint64_t n = 0;
+    int rc = vqcpc_vocoder_ar_saved_bytes(voc, 2, 321, &n);
+    w.embedding = p; w.w_ih = p; w.w_hh = p; w.b_ih = p; w.b_hh = p; w.fc1_weight = p; w.fc1_bias = p; w.fc2_weight = p; w.fc2_bias = p;
+    g = (vqcpc_vocoder_ar_grads){NULL, p, NULL, NULL, NULL, NULL, NULL, NULL, p};
+    rc |= vqcpc_vocoder_ar_fwd(voc, i, i, i, 2, 1, 321, NULL, NULL, &w, d, i, i, p, saved, s);
+    rc |= vqcpc_vocoder_ar_fwd(voc, i, i, i, 2, 1, 321, NULL, NULL, NULL, d, i, i, NULL, saved, s);
+    rc |= vqcpc_vocoder_ar_bwd(voc, i, i, i, 2, 1, 321, NULL, NULL, &w, saved, p, &g, p, s);
+    rc |= vqcpc_vocoder_ar_bwd(voc, i, i, i, 2, 1, 321, NULL, NULL, NULL, saved, NULL, NULL, p, s);
+    return rc;
+}
+''')
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only",
+                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_ar_tensors_struct_mirrors_the_header():
+    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_grad.h")).read()
+    for kind in ("const float", "float"):
+        body = re.search(r"typedef struct \{([^}]*)\} vqcpc_vocoder_ar_%s;" % ("weights" if kind == "const float" else "grads"), text).group(1)
+        assert re.findall(r"\b%s \*(\w+);" % kind, body) == [n for n, _ in _lib.VocoderArTensors._fields_]
+    assert ctypes.sizeof(_lib.VocoderArTensors) == 9 * ctypes.sizeof(ctypes.c_void_p)
+    import vectorquantizedcpc_amd as V
+    assert tuple(n for n, _ in _lib.VocoderArTensors._fields_) == V.Vocoder.AR_KEYS == R.KEYS
+    voc = V.Vocoder(V.ConfVocoder())
+    assert [tuple(p.shape) for p in voc._ar_params()] == [tuple(voc.state_dict()["rnnms.ar." + n].shape) for n in R.SD_NAMES]
+
+
+# ------------------------------------------------------------------ argument checks that need no GPU
+def test_training_cuts_are_seeded_and_cover_their_samples():
+    import torch
+    idx = [torch.arange(n) for n in (30, 2, 10, 1)]
+    audio = [torch.arange(320 * n + 7) for n in (30, 2, 10, 1)]
+    n_codes = [30, 2, 10, 1]
+    keep = [driver.scored_samples(a.numel(), n) for a, n in zip(audio, n_codes)]
+    a = driver.training_cuts(idx, audio, n_codes, keep, 160, 2, 13)
+    b = driver.training_cuts(idx, audio, n_codes, keep, 160, 2, 13)
+    assert all(torch.equal(x, y) for x, y in zip(a[0] + a[1], b[0] + b[1])) and a[2:] == b[2:]
+    assert a[2] == [2, 2, 2, 1] and a[3] == [641, 641, 641, 321]
+    for i, au in zip(a[0], a[1]):
+        assert int(au[0]) == 320 * int(i[0])                          # the samples under the cut's first code
+    whole = driver.training_cuts(idx, audio, n_codes, keep, 160, None, 13)
+    assert whole[2] == n_codes and whole[3] == keep and n_codes == [30, 2, 10, 1]
+    with pytest.raises(ValueError, match="clip_codes"):
+        driver.training_cuts(idx, audio, n_codes, keep, 160, 0, 13)
+
+
+def test_cli_fit_vocoder_parses(capsys):
+    with pytest.raises(SystemExit) as e:
+        cli.main(["fit-vocoder", "--help"])
+    assert e.value.code == 0
+    text = capsys.readouterr().out
+    assert all(o in text for o in ("--steps", "--lr", "--clip-codes", "--out", "--in-dir", "--vocoder-checkpoint"))
+    assert "fit-vocoder" in cli.__doc__
+    with pytest.raises(SystemExit):
+        cli.main(["fit-vocoder", "--dataset", "d", "--in-dir", "w", "--out", "o.pt"])      # neither checkpoints nor --random-init

@@ -19,6 +19,7 @@
                                                                            -> <round>_xcd_timeline.txt, <round>_xcm_timeline.txt
   probe        tools/xcd_decoder_probe.py, tools/xcm_probe.py              -> <round>_xcd_probe.csv, <round>_xcm_probe.csv
   by_batch     tools/bench_by_batch.py                                     -> <round>_bench_by_batch.csv
+  voc_grad     tools/voc_grad_times.py                                     -> voc_grad_times.txt (no round prefix: one file)
   summary      rewrites the numbers quoted in profiles/<round>_summary.md from the files above
 
 Every step is a fresh child process; the parent never touches the GPU (rocprofv3 must have the program itself after `--`).
@@ -63,7 +64,7 @@ def main():
     args = ap.parse_args()
     skip = set(s for s in args.skip.split(",") if s)
     if args.only:
-        every = {"bench", "trace", "pmc", "pmc_big", "pmc_xcm", "pmc_sq", "manifest", "encoder", "timeline", "probe", "by_batch", "summary"}
+        every = {"bench", "trace", "pmc", "pmc_big", "pmc_xcm", "pmc_sq", "manifest", "encoder", "timeline", "probe", "by_batch", "voc_grad", "summary"}
         skip = every - set(s for s in args.only.split(",") if s)
     R = args.round
     # on the GPU box only gpurun_out/ travels back: the artifacts go to gpurun_out/profiles_<round>/ (copy them into profiles/
@@ -130,6 +131,9 @@ def main():
     if "by_batch" not in skip:
         ok["by_batch"] = run([PY, "tools/bench_by_batch.py", "1", "8", "16", "32", "64", "96", "128", "256", "384", "512"],
                              out=os.path.join(P, f"{R}_bench_by_batch.csv"))
+    if "voc_grad" not in skip:
+        ok["voc_grad"] = run([PY, "tools/voc_grad_times.py", "--out", os.path.join(P, "voc_grad_times.txt")], out=os.path.join(S, "voc_grad.log"),
+                             timeout=900)
     if "summary" not in skip:
         summary(P, R)
     print("[refresh]", json.dumps(ok), flush=True)

@@ -38,6 +38,9 @@ SYMBOLS = [
 # every symbol include/vqcpc_grad.h declares, exported by the same library (SYMBOLS stays the list of include/vqcpc.h alone)
 GRAD_SYMBOLS = ["vqcpc_encoder_front_saved_bytes", "vqcpc_encoder_front_fwd", "vqcpc_encoder_front_bwd", "vqcpc_encoder_vq_bwd"]
 
+# every symbol include/vqcpc_vocoder_grad.h declares, likewise
+VOC_GRAD_SYMBOLS = ["vqcpc_vocoder_ar_saved_bytes", "vqcpc_vocoder_ar_fwd", "vqcpc_vocoder_ar_bwd"]
+
 
 class EncoderWeights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p), ("ln_weight", C.c_void_p * 5), ("ln_bias", C.c_void_p * 5),
@@ -60,6 +63,12 @@ def fill_front(s, values):
     v = list(values)
     s.conv_weight, s.ln_weight[:], s.ln_bias[:], s.fc_weight[:], s.out_weight, s.out_bias = v[0], v[1:6], v[6:11], v[11:15], v[15], v[16]
     return s
+
+
+class VocoderArTensors(C.Structure):
+    """``vqcpc_vocoder_ar_weights`` and ``vqcpc_vocoder_ar_grads`` (``include/vqcpc_vocoder_grad.h``): the same nine members of
+    ``rnnms.ar``, read or written."""
+    _fields_ = [(n, C.c_void_p) for n in ("embedding", "w_ih", "w_hh", "b_ih", "b_hh", "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")]
 
 
 class CPCWeights(C.Structure):
@@ -139,6 +148,11 @@ def load():
                                            C.POINTER(C.c_uint32), vp, i64p, i32, vp]
     lib.vqcpc_vocoder_logits.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, vp, vp]
     lib.vqcpc_vocoder_nll.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, i64p, i64p, vp, vp]
+    lib.vqcpc_vocoder_ar_saved_bytes.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
+    lib.vqcpc_vocoder_ar_fwd.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(VocoderArTensors),
+                                         vp, i64p, i64p, vp, vp, vp]
+    lib.vqcpc_vocoder_ar_bwd.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(VocoderArTensors),
+                                         vp, vp, C.POINTER(VocoderArTensors), vp, vp]
     lib.vqcpc_vocoder_condition.argtypes = [vp, i64p, i64p, i32, i32, vp, vp]
     lib.vqcpc_vocoder_glue.argtypes = [vp, i64p, i64p, i32, i32, vp, vp]
     lib.vqcpc_vocoder_set_option.argtypes = [vp, C.c_char_p, i32]
@@ -366,12 +380,22 @@ class NativeModule(nn.Module):
             return self._handle
         return None
 
-    def _sizes_handle(self, dev):
-        """The handle for a call that reads the weights from the CALLER's pointers (the ``*_fwd`` / ``*_bwd`` / ``*_grad`` entries):
-        it gives sizes and work space only, so any live handle on ``dev`` serves.  ``_native()`` would answer the moved
-        ``WeightSlots.key`` with destroy, create and a synchronisation per optimizer step; calls that read the handle's copies still
-        go through ``_native()``, which rebuilds once when it sees the moved ``_version``, and so never read stale ones."""
+    def _sizes_handle(self, dev, read_from_handle=()):
+        """The handle for a call that reads weights from the CALLER's pointers (the ``*_fwd`` / ``*_bwd`` / ``*_grad`` entries).
+        For those tensors the handle gives sizes and work space only, so a live handle on ``dev`` whose copies of them an optimizer
+        step has made stale still serves: ``_native()`` would answer the moved ``WeightSlots.key`` with destroy, create and a
+        synchronisation per step.  ``read_from_handle``: the ``state_dict()`` names such an entry nevertheless reads from the
+        handle's COPIES (the vocoder's frozen conditioning path); the live handle is reused only while the key of every one of them
+        is the one it was built from, and rebuilt through ``_native()`` otherwise -- ``load_state_dict`` or an in-place write to
+        one of them is never missed.  Calls that read the handle's copies throughout go through ``_native()``, which rebuilds once
+        when it sees a moved ``_version``."""
         h = self._live_handle(dev)
+        if h is not None and read_from_handle:
+            slots = self.__dict__["_slots"]                  # a live handle was built from them
+            for i, (name, t) in enumerate(zip(slots.names, slots.tensors())):
+                if name in read_from_handle and (t.data_ptr(), t._version) != self._handle_key[2 + i]:
+                    h = None
+                    break
         return h if h is not None else self._native()
 
     def _release(self):

@@ -11,6 +11,9 @@
 
     python -m vectorquantizedcpc_amd.cli score-vocoder --dataset datasets/2019/english --in-dir wavs/
                                                  [--cpc-checkpoint .. --vocoder-checkpoint .. | --random-init] [--per-utterance]
+    python -m vectorquantizedcpc_amd.cli fit-vocoder   --dataset datasets/2019/english --in-dir wavs/ --out vocoder.pt
+                                                 [--cpc-checkpoint .. --vocoder-checkpoint .. | --random-init]
+                                                 [--steps 200 --lr 4e-4 --clip-codes 16 --seed 13]
 
     python -m vectorquantizedcpc_amd.cli abx     --items FILE --mode within|across [--frame-shift 0.02 --frame-offset 0.01]
                                                  --features DIR | --dataset datasets/2019/english
@@ -52,6 +55,11 @@ error rate of the units on an items file (``file onset offset phone prev next sp
 ``encode`` wrote (``--features``) or straight from the mels of ``test.json`` (``--dataset``, ``driver.score_abx``);
 ``--feature indices`` scores the units as codebook indices (the numbers of ``z`` from a distance table, or ``--metric edit``:
 the edit distance between index runs).
+``fit-vocoder`` refits the vocoder's sample-rate network ``rnnms.ar`` (embedding, GRU, fc1, fc2) on the same utterances, conditioned
+on the units of the (frozen) encoder -- the step after ``adapt-codebook`` / ``fit-encoder``, or for a new speaker
+(``driver.fit_vocoder``: forward and back-propagation through time are ``vqcpc_vocoder_ar_fwd`` / ``_bwd``, the optimizer torch's
+Adam; the prenet and the two embedding tables stay frozen).  It prints the ``score-vocoder`` line before and after and writes
+``{"vocoder": state_dict}``.
 ``score-vocoder`` is the validation number the reference's vocoder training never computes (``vocoder.py:68-94``): the
 teacher-forced cross-entropy of ``vocoder.py:62-63`` on ``<in_dir>/<utterance>.wav`` of every entry of ``test.json``, speaker id
 from ``speakers.json`` by the file name's prefix: loss in nats per sample, bits per sample and top-1 accuracy
@@ -201,7 +209,9 @@ def fit_encoder_dataset(args) -> int:
                         lambda enc, update: f"\"encoder\" replaced ({len(update)} keys)")
 
 
-def score_vocoder_dataset(args) -> int:
+def _vocoder_setup(args):
+    """Encoder, Vocoder and the waveforms (at 16 kHz) and speaker ids of ``test.json``, for ``score-vocoder`` and ``fit-vocoder``;
+    None after a message when a file's speaker is not in ``speakers.json``."""
     import json
     from . import preprocess
     paths = io.read_test_metadata(args.dataset)
@@ -214,20 +224,56 @@ def score_vocoder_dataset(args) -> int:
         prefix = p.stem.split("_")[0]
         if prefix not in names:
             print(f"{p.stem}: speaker {prefix!r} is not in speakers.json")
-            return 1
+            return None
         rate, a = io.read_wav_file(Path(args.in_dir) / p.stem)
         if rate != 16000:                                      # the resampling of librosa.load(sr=16000), convert.py:54-56
             a = preprocess.resample(torch.as_tensor(a, dtype=torch.float32, device=dev)[None], rate, 16000)[0].cpu().numpy()
         waves.append(a)
         speakers.append(names.index(prefix))
+    return enc, voc, paths, waves, speakers
+
+
+def _vocoder_line(tot) -> str:
+    return (f"vocoder loss:{tot['loss']:.4f} nats/sample, {tot['bits_per_sample']:.4f} bits/sample, top-1 accuracy:{tot['accuracy']:.4f} "
+            f"over {tot['n_scored']} samples of {tot['n_utterances']} utterances ({tot['n_cut']} samples past the codes cut)")
+
+
+def score_vocoder_dataset(args) -> int:
+    setup = _vocoder_setup(args)
+    if setup is None:
+        return 1
+    enc, voc, paths, waves, speakers = setup
     records, tot = driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)
     if args.per_utterance:
         for p, r in zip(paths, records):
             loss = r["nll_sum"] / r["n_scored"] if r["n_scored"] else float("nan")
             print(f"{p.stem}: loss:{loss:.4f} nats/sample over {r['n_scored']} samples, correct {r['n_correct']}, "
                   f"codes {r['n_codes']}, samples cut {r['n_cut']}")
-    print(f"vocoder loss:{tot['loss']:.4f} nats/sample, {tot['bits_per_sample']:.4f} bits/sample, top-1 accuracy:{tot['accuracy']:.4f} "
-          f"over {tot['n_scored']} samples of {tot['n_utterances']} utterances ({tot['n_cut']} samples past the codes cut)")
+    print(_vocoder_line(tot))
+    return 0
+
+
+def fit_vocoder_dataset(args) -> int:
+    """score, ``driver.fit_vocoder``, score again on the same utterances, and the vocoder checkpoint (``{"vocoder": state_dict}``,
+    as ``convert`` and ``score-vocoder`` read it)."""
+    setup = _vocoder_setup(args)
+    if setup is None:
+        return 1
+    enc, voc, paths, waves, speakers = setup
+    print("before the fit:")
+    print(_vocoder_line(driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)[1]))
+    r = driver.fit_vocoder(enc, voc, waves, None, speakers, steps=args.steps, lr=args.lr, max_batch=min(args.max_batch, 32),
+                           clip_codes=args.clip_codes if args.clip_codes > 0 else None, seed=args.seed)
+    if r["steps"] == 0:
+        print("no utterance with two samples to score: nothing fitted")
+        return 1
+    print(f"fitted rnnms.ar (embedding, GRU, fc1, fc2) in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches of "
+          f"{r['utterances']} utterances: loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}")
+    print("after the fit:")
+    print(_vocoder_line(driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)[1]))
+    sd = {k: v.detach().cpu().clone() for k, v in voc.state_dict().items()}
+    torch.save({"vocoder": sd}, args.out)
+    print(f"wrote {args.out}: \"vocoder\" ({len(sd)} keys; rnnms.ar.* refitted, the rest as it was)")
     return 0
 
 
@@ -329,7 +375,7 @@ def convert_dataset(args) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vectorquantizedcpc_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("encode", "convert", "score", "score-vocoder", "adapt-codebook", "fit-predictors", "fit-context", "fit-encoder"):
+    for name in ("encode", "convert", "score", "score-vocoder", "fit-vocoder", "adapt-codebook", "fit-predictors", "fit-context", "fit-encoder"):
         p = sub.add_parser(name)
         p.add_argument("--dataset", required=True, help="datasets/<name> directory (test.json, speakers.json)")
         if name in ("encode", "convert"):
@@ -359,10 +405,17 @@ def main(argv=None) -> int:
         elif name == "adapt-codebook":
             p.add_argument("--out-checkpoint", required=True)
             p.add_argument("--epochs", type=int, default=1)
-        elif name == "score-vocoder":
+        elif name in ("score-vocoder", "fit-vocoder"):
             p.add_argument("--vocoder-checkpoint")
             p.add_argument("--in-dir", required=True, help="directory of <utterance>.wav files")
-            p.add_argument("--per-utterance", action="store_true", help="also print one line per file")
+            if name == "score-vocoder":
+                p.add_argument("--per-utterance", action="store_true", help="also print one line per file")
+            else:
+                p.add_argument("--steps", type=int, default=200)
+                p.add_argument("--lr", type=float, default=4e-4, help="Adam's learning rate")
+                p.add_argument("--clip-codes", type=int, default=16, help="codes per training cut (16: the reference's 5120 samples); 0: whole utterances")
+                p.add_argument("--seed", type=int, default=synth.SEED)
+                p.add_argument("--out", required=True, help="the vocoder checkpoint to write")
         else:
             p.add_argument("--vocoder-checkpoint")
             p.add_argument("--synthesis-list", required=True)
@@ -398,10 +451,10 @@ def main(argv=None) -> int:
         parts = [t for t in args.train.split(",") if t]
         if not parts or len(set(parts)) != len(parts) or any(t not in driver.FIT_ENCODER_PARTS for t in parts):
             ap.error(f"fit-encoder --train: name each of {','.join(driver.FIT_ENCODER_PARTS)} at most once, and at least one")
-    if args.cmd == "score-vocoder" and not args.random_init and not args.vocoder_checkpoint:
+    if args.cmd in ("score-vocoder", "fit-vocoder") and not args.random_init and not args.vocoder_checkpoint:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,
-            "score-vocoder": score_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset,
+            "score-vocoder": score_vocoder_dataset, "fit-vocoder": fit_vocoder_dataset, "adapt-codebook": adapt_codebook_dataset,
             "fit-predictors": fit_predictors_dataset, "fit-context": fit_context_dataset,
             "fit-encoder": fit_encoder_dataset}[args.cmd](args)
 

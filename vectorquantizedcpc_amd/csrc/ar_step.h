@@ -89,7 +89,7 @@ struct ArModel {               // constant per handle (baked into the captured g
 // dynamic-LDS attribute has been set (launch_ar_steps sets it once).
 struct ArStep { int Hr, Hf, n_cls, big_min_tiles; bool *big_attr_set; };
 
-int build_wfrag12(const float *W, int ldw, int n_rg, int K, int H, DevBuf &out);     // reserves `out`
+int build_wfrag12(const float *W, int ldw, int n_rg, int K, int H, DevBuf &out, hipStream_t s = 0);     // reserves `out`
 bool use_big(const ArStep &a, int nbt);
 // One GRU-step launch for local step `tl`; nf = fc2 blocks of the previous step in front (fused launch, 0 = none).
 int launch_gru_step(const ArStep &a, const ArModel &m, const ArCall *call, int tl, int nbt, int nf, hipStream_t s);

@@ -38,11 +38,11 @@ __global__ void build_wfrag12_kernel(const float *__restrict__ W, int ldw, float
     const int row = (i >> 2) * H + 4 * rg + (i & 3);
     ((float4 *)Wp)[id] = *(const float4 *)(W + (size_t)row * ldw + 16 * (w * SW + s) + 4 * kq);
 }
-int build_wfrag12(const float *W, int ldw, int n_rg, int K, int H, DevBuf &out) {
+int build_wfrag12(const float *W, int ldw, int n_rg, int K, int H, DevBuf &out, hipStream_t s) {
     VQ_REQUIRE(K % 64 == 0 && ldw % 4 == 0, "build_wfrag12: K=%d not a multiple of 64", K);
     const size_t n4 = (size_t)n_rg * (K / 16) * 48;
     TRY(out.reserve(n4 * sizeof(float4)));
-    hipLaunchKernelGGL(build_wfrag12_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, W, ldw, out.as<float>(), n_rg, K, H);
+    hipLaunchKernelGGL(build_wfrag12_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, W, ldw, out.as<float>(), n_rg, K, H);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }

@@ -1,0 +1,518 @@
+// Gradients of the vocoder objective (vocoder.py:62-63: F.cross_entropy of the teacher-forced energies of audio[:, :-1] against
+// audio[:, 1:]) through the sample-rate network rnnms.ar.* -- embedding, GRU, fc1, fc2 -- and with respect to the conditioning
+// series: vqcpc_vocoder_ar_fwd / _bwd of include/vqcpc_vocoder_grad.h.  The prenet and the two tables in front of it are frozen.
+// B utterances, Hr = size_h_rnn, Hf = n_cls = 256, de = size_i_embed_ar, C = dim_voc_latent, up = upsampling_t.  Utterance b scores
+// the steps t < slen[b] = max(n_audio[b] - 1, 0): step t is fed x = audio[b, t], reads conditioning frame t / up and is scored against
+// audio[b, t + 1].  Gate order r, z, n; h_t = n + z (h_{t-1} - n) (oracle/f64_ref.py:64-69).  loss = sum_b nll_sum[b] / N.
+// Every sum has ONE order, fixed by the code and independent of the grid's timing: no floating-point read-modify-write that two
+// workgroups share, no wait on another workgroup; launch boundaries order the steps and the passes.  Equal inputs give equal bits.
+// Every operation below is one separately rounded fp32 operation (-ffp-contract=off); "chain" = fp32 fmas from 0.
+//
+// Forward (vqcpc_vocoder_ar_fwd): vq_tf_score of vocoder_host.hip, the function that IS vqcpc_vocoder_nll -- the same launch-per-step
+//   scan and the same fused head -- with the caller's weights re-laid into the work space first (vq_vocoder_relayout) and h_t of every
+//   scored step copied out of the chunk buffer after each chunk (tf_save_h_kernel): saved = (B, L - 1, Hr).
+//
+// Backward (vqcpc_vocoder_ar_bwd).  s = grad_loss * fl(1 / N).  The conditioning (frozen) runs again: cond and the frame table
+//   Gc = cond W_ih[:, de:]^T + b_ih; Gemb = emb W_ih[:, :de]^T is the class table.  Every wanted output and the two table gradients
+//   dGemb (n_cls, 3Hr), dGc (frames, 3Hr) are zero-filled, then the chunks of CH = tf_chunk_replays * steps_per_graph steps run in
+//   REVERSE time order, each adding its sums to them: total' = total + (chunk's sum).  Rows of a chunk: r = b CH + (t - t0); a row is
+//   live where t < slen[b]; a row that is not live enters every sum as exact zeros and nothing is read for it.
+//   Per chunk:
+//   1. voc_gather_h_kernel: H = h_t, Hp = h_{t-1} (zero at t = 0) of the chunk's rows from `saved`.
+//   2. Gates again: gh = Hp W_hh^T + b_hh (vq_gemm_chain: bias + chain over k ascending); voc_gates_kernel: gi = Gemb[x] + Gc[frame],
+//      r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n) (libm expf / tanhf).
+//   3. Head: a = relu(H W1^T + b1), e = a W2^T + b2 (vq_gemm_chain); voc_softmax_kernel, one wave per row: m = max e (butterfly over
+//      the lanes), q_k = expf(e_k - m), S = sum q (four per lane in k order, then the butterfly xor 32, 16, .., 1),
+//      dlogit_k = (q_k / S - [k == target]) * s.  da = (dlogit W2) * [a > 0], dh_head = da W1: voc_rows_w_kernel, one 16 x 16 tile per
+//      workgroup, k over the four waves: wave w takes k in [w K / 4, (w + 1) K / 4) in super-steps S of 16; MFMA c (c = 0 .. 3) takes
+//      k = 16 S + 4 q + c, q = 0 .. 3 summed in that order inside the instruction; c even goes to accumulator 0, c odd to
+//      accumulator 1, S ascending; the wave's sum is a0 + a1 and the four waves are combined ((w0 + w1) + w2) + w3.
+//   4. The serial part, voc_bwd_step_kernel, grid (Hr / 16, ceil(B / 16)), ONE launch per step, t descending.  Workgroup (rg, bt)
+//      owns hidden units 16 rg .. + 15 of utterances 16 bt .. + 15:
+//        dh_rec[b, u] = sum_k W_hh[k, u] dgh[t + 1][b, k], k < 3Hr, on v_mfma_f32_16x16x4_f32 in the order of 3 (K = 3Hr);
+//          +0 without an MFMA at the last step of the call, and a column whose utterance has no step t + 1 enters as zeros.
+//        dh = (dh_head + dh_rec) + carry        (carry = z_{t+1} dh_{t+1}; 0 at the utterance's last scored step)
+//        dn = dh (1 - z)    dz = dh (h_{t-1} - n)
+//        dgi_n = dn (1 - n n)    dgi_z = dz (z (1 - z))    dgi_r = (dgi_n gh_n) (r (1 - r))
+//        dgh = (dgi_r, dgi_z, dgi_n r)          carry' = dh z
+//      dgi (3Hr) and the n third of dgh (Hr) are stored for the chunk, with one more row per utterance that keeps step t0 + CH of
+//      the chunk done before.
+//   5. Weight sums of the chunk, voc_atb_kernel (A^T B over the chunk's rows, one 16 x 16 tile per wave, grid (Nb / 16, Na / 64)):
+//      slabs of GRAD_SLAB = 1024 consecutive rows; inside a slab MFMA (s, c) takes rows r0 + 16 s + 4 q + c, q = 0 .. 3 summed inside
+//      the instruction, c even to accumulator 0, c odd to accumulator 1, s ascending, the two added at the end (slab_mfma_tile of
+//      grad_slab.h); the slabs are added in slab order from 0, and that sum is added to the total.
+//        dW2 += dlogit^T a     dW1 += da^T H     dW_hh += dgh^T Hp     dGemb += onehot(x)^T dgi (the one-hot rows made on the fly)
+//      Column sums, voc_colsum_kernel (64 columns per workgroup): thread (column, row group g = 0 .. 3) adds rows g + 4 i, i ascending,
+//      into four accumulators (i mod 4) combined (a0 + a1) + (a2 + a3); the four row groups are combined the same way; added to the
+//      total:  db2 += sum dlogit    db1 += sum da    db_hh += sum dgh.
+//      Frame sums, voc_frame_sum_kernel: dGc[frame] += (sum of dgi over the frame's live steps inside the chunk, t ascending from 0).
+//   After the last chunk, from the two tables (the same two kernels, rows = classes or frames):
+//      dW_ih[:, :de] = dGemb^T emb    dW_ih[:, de:] = dGc^T cond    db_ih = column sums of dGc
+//      d emb = dGemb W_ih[:, :de]     grad_cond = dGc W_ih[:, de:]   (voc_rows_w_kernel, K = 3Hr)
+//   Classes never fed and frames no scored step reads keep their zero rows: their products are sums of (+-0) from +0, i.e. +0.
+//
+// Work space (VocGradWork, beside what the forward scan uses), floats, M = B CH:
+//   M (11 Hr + 2 Hf + n_cls) + 4 B Hr + B Hr + (n_cls + frames) 3Hr, plus for a caller's weights the scan's layouts of them.
+//
+// Padding and dirt: the utterance columns b >= B of the last tile are masked (their lanes load nothing and store nothing), rows that
+// are not live likewise; the scan reads dgh[t + 1] and the carry only where step t + 1 of the same call wrote them.  Whatever an
+// earlier call left in the work space never reaches a result.
+#include "vocoder_internal.h"
+#include "grad_slab.h"
+#include "../../include/vqcpc_vocoder_grad.h"
+
+namespace {
+
+struct VocRows {                         // the chunk in flight
+    const int *slen;                     // [B] scored steps
+    const int64_t *audio;                // (B, L)
+    int B, L, CH, t0, Hr;
+};
+__device__ __forceinline__ bool row_live(const VocRows &q, int r, int &b, int &t) {
+    b = r / q.CH;
+    t = q.t0 + r % q.CH;
+    return b < q.B && t < q.slen[b];
+}
+__device__ __forceinline__ int clamp_class(long long x) { return x < 0 ? 0 : (x >= NLL_CLS ? NLL_CLS - 1 : (int)x); }
+
+// grid (ceil(CH Hr / 4 / 256), B); Hp null: only the head's sums are wanted
+__global__ void voc_gather_h_kernel(const float4 *__restrict__ saved, float4 *__restrict__ H, float4 *__restrict__ Hp,
+                                    const int *__restrict__ slen, int CH, int t0, int H4, int Tsv) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= CH * H4) return;
+    const int tt = i / H4, u = i % H4, t = t0 + tt;
+    const bool live = t < slen[b];
+    const size_t o = ((size_t)b * CH + tt) * H4 + u;
+    const float4 *src = saved + ((size_t)b * Tsv + t) * H4 + u;
+    float4 h = make_float4(0.f, 0.f, 0.f, 0.f), hp = h;
+    if (live) h = src[0];
+    if (live && t > 0) hp = src[-H4];
+    H[o] = h;
+    if (Hp) Hp[o] = hp;
+}
+
+// gh (M, 3Hr): in gh_r | gh_z | gh_n, out r | z | gh_n; nn (M, Hr) = n.  grid (ceil(CH Hr / 256), B)
+__global__ void voc_gates_kernel(float *__restrict__ gh, float *__restrict__ nn, const float *__restrict__ Gemb, const float *__restrict__ Gc,
+                                 const int *__restrict__ gbase, VocRows q, int up) {
+    const int Hr = q.Hr, i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= q.CH * Hr) return;
+    const int tt = i / Hr, u = i % Hr, t = q.t0 + tt;
+    if (t >= q.slen[b]) return;
+    const float *e = Gemb + (size_t)clamp_class(q.audio[(size_t)b * q.L + t]) * 3 * Hr + u;
+    const float *c = Gc + ((size_t)gbase[b] + t / up) * 3 * Hr + u;
+    float *g = gh + ((size_t)b * q.CH + tt) * 3 * Hr + u;
+    const float r = sigmoidf_((e[0] + c[0]) + g[0]);
+    const float z = sigmoidf_((e[Hr] + c[Hr]) + g[Hr]);
+    const float n = tanhf((e[2 * Hr] + c[2 * Hr]) + r * g[2 * Hr]);
+    g[0] = r; g[Hr] = z;
+    nn[((size_t)b * q.CH + tt) * Hr + u] = n;
+}
+
+// e (M, 256) -> dlogit in place; one wave per row, 4 rows per workgroup.  grid (ceil(M / 4))
+__global__ __launch_bounds__(256) void voc_softmax_kernel(float *__restrict__ e, VocRows q, const float *__restrict__ grad_loss, float inv_n) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= q.B * q.CH) return;
+    int b, t;
+    float4 *row = (float4 *)(e + (size_t)r * NLL_CLS) + lane;
+    if (!row_live(q, r, b, t)) { *row = make_float4(0.f, 0.f, 0.f, 0.f); return; }
+    const float s = grad_loss ? grad_loss[0] * inv_n : inv_n;
+    const float4 v = *row;
+    float m = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+    float4 p = make_float4(expf(v.x - m), expf(v.y - m), expf(v.z - m), expf(v.w - m));
+    float S = ((p.x + p.y) + p.z) + p.w;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) S = S + __shfl_xor(S, d);
+    const int k = clamp_class(q.audio[(size_t)b * q.L + t + 1]) - 4 * lane;
+    p.x = (p.x / S - (k == 0 ? 1.f : 0.f)) * s;
+    p.y = (p.y / S - (k == 1 ? 1.f : 0.f)) * s;
+    p.z = (p.z / S - (k == 2 ? 1.f : 0.f)) * s;
+    p.w = (p.w / S - (k == 3 ? 1.f : 0.f)) * s;
+    *row = p;
+}
+
+// out (R, N) = A (R, K) W (K rows of ldw, columns [0, N)), one 16 x 16 tile per workgroup; K % 64 == 0, N % 16 == 0.
+// mask (R, N) or null: out = mask > 0 ? product : 0.  frames / gbase: out row (b, f) of (B, T2) reads A's row gbase[b] + f where
+// f < frames[b] and is left alone elsewhere (the caller zero-filled it).  grid (ceil(R / 16), N / 16)
+__global__ __launch_bounds__(256) void voc_rows_w_kernel(const float *__restrict__ A, const float *__restrict__ W, int ldw, float *__restrict__ out,
+                                                         const float *__restrict__ mask, int R, int K, int N, const int *__restrict__ frames,
+                                                         const int *__restrict__ gbase, int T2) {
+    __shared__ float red[4][16][17];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4;
+    const int r0 = blockIdx.x * 16, c0 = blockIdx.y * 16, NS = K / 64;
+    long long src = -1;                                                // A's row of this lane's output row, -1: masked
+    if (r0 + i < R) {
+        src = r0 + i;
+        if (frames) { const int b = (r0 + i) / T2, f = (r0 + i) % T2; src = f < frames[b] ? (long long)gbase[b] + f : -1; }
+    }
+    const float4 *ap = (const float4 *)(A + (size_t)(src < 0 ? 0 : src) * K) + (size_t)wave * NS * 4 + kq;
+    const float *wp = W + ((size_t)wave * NS * 16 + 4 * kq) * ldw + c0 + i;
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < NS; ++s) {
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (src >= 0) av = ap[4 * s];
+        const float *w = wp + (size_t)16 * s * ldw;
+        mfma_k4(a0, a1, av, make_float4(w[0], w[ldw], w[2 * (size_t)ldw], w[3 * (size_t)ldw]));
+    }
+    float v = reduce4(red, a0 + a1, wave, lane, tid);                  // row r0 + (tid >> 4), column c0 + (tid & 15)
+    const int r = r0 + (tid >> 4), c = c0 + (tid & 15);
+    if (r >= R) return;
+    if (frames && r % T2 >= frames[r / T2]) return;
+    if (mask && !(mask[(size_t)r * N + c] > 0.f)) v = 0.f;
+    out[(size_t)r * N + c] = v;
+}
+
+struct VocStepP {
+    const float *w_hh;                   // (3Hr, Hr)
+    const float *gh, *nn, *hp, *dhh;     // (M, 3Hr) r | z | gh_n; (M, Hr) n; h_{t-1}; dh_head
+    float *dgi, *dghn;                   // (B (CH + 1), 3Hr), (B (CH + 1), Hr)
+    float *carry;                        // (B, Hr)
+    VocRows q;
+    int longest;
+};
+
+template <int NS>                        // 3Hr / 64
+__global__ __launch_bounds__(256) void voc_bwd_step_kernel(VocStepP p, int t) {
+    __shared__ float red[4][16][17];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rg = blockIdx.x, bt = blockIdx.y, Hr = p.q.Hr, CH = p.q.CH, tt = t - p.q.t0;
+    const int bl = tid >> 4, ul = tid & 15, bg = bt * 16 + bl, unit = 16 * rg + ul;
+    const bool act = bg < p.q.B && t < p.q.slen[bg];
+    const size_t row = (size_t)bg * CH + tt, drow = (size_t)bg * (CH + 1) + tt;
+    float r = 0.f, z = 0.f, hn = 0.f, n = 0.f, hp = 0.f, dhh = 0.f, carry = 0.f;
+    if (act) {                                       // requested first: they do not depend on the product
+        const float *g = p.gh + row * (3 * Hr) + unit;
+        r = g[0]; z = g[Hr]; hn = g[2 * Hr];
+        n = p.nn[row * Hr + unit];
+        hp = p.hp[row * Hr + unit];
+        dhh = p.dhh[row * Hr + unit];
+        if (t + 1 < p.q.slen[bg]) carry = p.carry[(size_t)bg * Hr + unit];
+    }
+    float dh_rec = 0.f;
+    if (t + 1 < p.longest) {                         // uniform over the grid
+        const int bcol = bt * 16 + (lane & 15);
+        const bool live = bcol < p.q.B && t + 1 < p.q.slen[bcol];         // a masked column loads nothing
+        const size_t nrow = (size_t)(live ? bcol : 0) * (CH + 1) + tt + 1;
+        const int kq = lane >> 4;
+        const float *wp = p.w_hh + ((size_t)wave * NS * 16 + 4 * kq) * Hr + unit - ul + (lane & 15);
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int s = 0; s < NS; ++s) {
+            const int k = 16 * (wave * NS + s) + 4 * kq;                  // 2Hr is a multiple of 16: four k never straddle the two buffers
+            float4 d4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) d4 = k < 2 * Hr ? *(const float4 *)(p.dgi + nrow * (3 * Hr) + k) : *(const float4 *)(p.dghn + nrow * Hr + (k - 2 * Hr));
+            const float *w = wp + (size_t)16 * s * Hr;
+            mfma_k4(a0, a1, make_float4(w[0], w[Hr], w[2 * (size_t)Hr], w[3 * (size_t)Hr]), d4);
+        }
+        const f32x4 acc = a0 + a1;                   // row = unit 4 (lane >> 4) + r, column = utterance lane & 15
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wave][(lane >> 4) * 4 + e][lane & 15] = acc[e];
+        __syncthreads();
+        dh_rec = sum4(red[0][ul][bl], red[1][ul][bl], red[2][ul][bl], red[3][ul][bl]);
+    }
+    if (act) {
+        const float dh = (dhh + dh_rec) + carry;
+        const float dn = dh * (1.0f - z), dz = dh * (hp - n);
+        const float gn = dn * (1.0f - n * n), gz = dz * (z * (1.0f - z)), gr = (gn * hn) * (r * (1.0f - r));
+        float *d = p.dgi + drow * (3 * Hr) + unit;
+        d[0] = gr; d[Hr] = gz; d[2 * Hr] = gn;
+        p.dghn[drow * Hr + unit] = gn * r;
+        p.carry[(size_t)bg * Hr + unit] = dh * z;
+    }
+}
+
+// Row t0 of every utterance -> its extra row CH, for the chunk in front.  grid (ceil(4 Hr / 256), B)
+__global__ void voc_keep_first_kernel(float *__restrict__ dgi, float *__restrict__ dghn, int CH, int Hr) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= 4 * Hr) return;
+    const size_t r0 = (size_t)b * (CH + 1), r1 = r0 + CH;
+    if (i < 3 * Hr) dgi[r1 * 3 * Hr + i] = dgi[r0 * 3 * Hr + i];
+    else dghn[r1 * Hr + i - 3 * Hr] = dghn[r0 * Hr + i - 3 * Hr];
+}
+
+// The operands of the sums over rows.  PLAIN: A (R, lda), Bm (R, ldb) as they stand.  WHH: A = dgh of the chunk's live rows (dgi's r
+// and z thirds, dghn), Bm = Hp.  GEMB: A = onehot(x) of the live rows, Bm = dgi.
+enum { ATB_PLAIN = 0, ATB_WHH = 1, ATB_GEMB = 2 };
+struct VocAtbP {
+    const float *A; int lda;
+    const float *A2;                     // WHH: dghn
+    const float *Bm; int ldb;
+    VocRows q;
+    float *out; int ldo;                 // out[m * ldo + c] += sum
+    int R;
+};
+template <int MODE>
+__device__ __forceinline__ float atb_a(const VocAtbP &p, int r, int m) {
+    if (MODE == ATB_PLAIN) return p.A[(size_t)r * p.lda + m];
+    int b, t;
+    if (!row_live(p.q, r, b, t)) return 0.f;
+    if (MODE == ATB_GEMB) return clamp_class(p.q.audio[(size_t)b * p.q.L + t]) == m ? 1.f : 0.f;
+    const size_t dr = (size_t)b * (p.q.CH + 1) + (t - p.q.t0);
+    return m < 2 * p.q.Hr ? p.A[dr * (3 * p.q.Hr) + m] : p.A2[dr * p.q.Hr + m - 2 * p.q.Hr];
+}
+template <int MODE>
+__device__ __forceinline__ float atb_b(const VocAtbP &p, int r, int c) {
+    if (MODE != ATB_GEMB) return p.Bm[(size_t)r * p.ldb + c];
+    int b, t;
+    if (!row_live(p.q, r, b, t)) return 0.f;
+    return p.Bm[((size_t)b * (p.q.CH + 1) + (t - p.q.t0)) * p.ldb + c];
+}
+
+// grid (Nb / 16, Na / 64): wave w of workgroup (x, y) owns the tile rows 64 y + 16 w .. + 15 of A's columns, columns 16 x .. + 15 of Bm's.
+template <int MODE>
+__global__ __launch_bounds__(256) void voc_atb_kernel(VocAtbP p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, ks = lane >> 4;
+    const int m = blockIdx.y * 64 + wave * 16 + i, c = blockIdx.x * 16 + i;
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < p.R; r0 += GRAD_SLAB)
+        sum = sum + slab_mfma_tile(p.R, r0, ks, [&](int r) { return atb_a<MODE>(p, r, m); }, [&](int r) { return atb_b<MODE>(p, r, c); });
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {                    // row = 64 y + 16 w + 4 ks + e of the output, column = 16 x + i
+        float *o = p.out + (size_t)(blockIdx.y * 64 + wave * 16 + ks * 4 + e) * p.ldo + c;
+        *o = *o + sum[e];
+    }
+}
+
+// Column sums over the rows: out[m] += sum_r a(r, m).  grid (Na / 64)
+template <int MODE>
+__global__ __launch_bounds__(256) void voc_colsum_kernel(VocAtbP p) {
+    __shared__ float red[4][64];
+    const int d = threadIdx.x & 63, rg = threadIdx.x >> 6, m = blockIdx.x * 64 + d;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; rg + 4 * i < p.R; i += 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = rg + 4 * (i + e);
+            a[e] += r < p.R ? atb_a<MODE>(p, r, m) : 0.f;
+        }
+    }
+    red[rg][d] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    if (rg == 0) p.out[m] = p.out[m] + ((red[0][d] + red[1][d]) + (red[2][d] + red[3][d]));
+}
+
+// dGc[gbase[b] + f] += sum of dgi over the live steps of frame f inside the chunk.  grid (B T2, ceil(3Hr / 256))
+__global__ void voc_frame_sum_kernel(const float *__restrict__ dgi, float *__restrict__ dGc, const int *__restrict__ frames,
+                                     const int *__restrict__ gbase, VocRows q, int T2, int up) {
+    const int b = blockIdx.x / T2, f = blockIdx.x % T2, col = blockIdx.y * blockDim.x + threadIdx.x;
+    if (col >= 3 * q.Hr || f >= frames[b]) return;
+    const long long lo64 = (long long)f * up, hi64 = lo64 + up;
+    int lo = lo64 < q.t0 ? q.t0 : (int)(lo64 < q.slen[b] ? lo64 : q.slen[b]);
+    int hi = (int)(hi64 < q.slen[b] ? hi64 : q.slen[b]);
+    hi = hi < q.t0 + q.CH ? hi : q.t0 + q.CH;
+    if (lo >= hi) return;
+    float sum = 0.f;
+    for (int t = lo; t < hi; ++t) sum += dgi[((size_t)b * (q.CH + 1) + (t - q.t0)) * (3 * q.Hr) + col];
+    float *o = dGc + ((size_t)gbase[b] + f) * (3 * q.Hr) + col;
+    *o = *o + sum;
+}
+
+// cond (rows of the utterances' own frames) -> (B, T2, C), +0 past an utterance's frames.  grid (B T2, ceil(C / 256))
+__global__ void voc_cond_out_kernel(const float *__restrict__ cond, float *__restrict__ out, const int *__restrict__ frames,
+                                    const int *__restrict__ gbase, int T2, int C) {
+    const int c = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x / T2, f = blockIdx.x % T2;
+    if (c >= C) return;
+    out[(size_t)blockIdx.x * C + c] = f < frames[b] ? cond[((size_t)gbase[b] + f) * C + c] : 0.f;
+}
+
+template <int MODE> void launch_atb(const VocAtbP &p, int Na, int Nb, hipStream_t s) {
+    hipLaunchKernelGGL((voc_atb_kernel<MODE>), dim3(Nb / 16, Na / 64), dim3(256), 0, s, p);
+}
+template <int MODE> void launch_colsum(const VocAtbP &p, int Na, hipStream_t s) {
+    hipLaunchKernelGGL((voc_colsum_kernel<MODE>), dim3(Na / 64), dim3(256), 0, s, p);
+}
+void launch_rows_w(const float *A, const float *W, int ldw, float *out, const float *mask, long long R, int K, int N, const int *frames,
+                   const int *gbase, int T2, hipStream_t s) {
+    hipLaunchKernelGGL(voc_rows_w_kernel, dim3((unsigned)((R + 15) / 16), N / 16), dim3(256), 0, s, A, W, ldw, out, mask, (int)R, K, N, frames, gbase, T2);
+}
+
+const float *const *members(const vqcpc_vocoder_ar_weights *w) { return &w->embedding; }     // nine pointers in a row
+float *const *members(const vqcpc_vocoder_ar_grads *g) { return &g->embedding; }
+
+// What both entries check before anything is enqueued.
+int check_call(vqcpc_vocoder *v, const char *what, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+               const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const void *saved, std::vector<int> &slen, int *longest) {
+    VQ_REQUIRE(v && audio && idx && speaker && saved, "%s: null argument", what);
+    TRY(vq_require_device(v->device, what));
+    TRY(vq_tf_check(v, B, Tc, L, n_codes, n_audio, slen, longest));
+    VQ_REQUIRE((long long)B * (L > 1 ? L - 1 : 1) < (1ll << 31) / 4, "%s: B * (L - 1) = %lld rows do not fit the row index (< 2^29)", what,
+               (long long)B * (L - 1));
+    VQ_REQUIRE(B <= 65535, "%s: B = %d, at most 65535 utterances per call", what, B);
+    VQ_REQUIRE(aligned16(saved), "%s: saved must be 16-byte aligned", what);
+    if (w)
+        for (int i = 0; i < 9; ++i) {
+            VQ_REQUIRE(members(w)[i], "%s: all nine tensors of rnnms.ar are required in *w", what);
+            VQ_REQUIRE(aligned16(members(w)[i]), "%s: the tensors of *w must be 16-byte aligned", what);
+        }
+    return VQCPC_OK;
+}
+
+int view_of(vqcpc_vocoder *v, const vqcpc_vocoder_ar_weights *w, bool scan, ArView *view, hipStream_t s) {
+    if (!w) { *view = vq_vocoder_view(v); return VQCPC_OK; }
+    return vq_vocoder_relayout(v, w->embedding, w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->fc1_weight, w->fc1_bias, w->fc2_weight, w->fc2_bias, scan, view, s);
+}
+
+}  // namespace
+
+extern "C" int vqcpc_vocoder_ar_saved_bytes(vqcpc_vocoder *v, int B, int L, uint64_t *bytes) {
+    VQ_REQUIRE(v && bytes, "vqcpc_vocoder_ar_saved_bytes: null argument");
+    VQ_REQUIRE(B >= 1 && L >= 1, "vqcpc_vocoder_ar_saved_bytes: need B >= 1 and L >= 1 (got %d, %d)", B, L);
+    VQ_REQUIRE(v->d.Hf == NLL_HF && v->d.n_cls == NLL_CLS, "vqcpc_vocoder_ar_saved_bytes: the scoring head is built for size_h_fc %d and %d "
+               "classes, this model has %d and %d", NLL_HF, NLL_CLS, v->d.Hf, v->d.n_cls);
+    *bytes = up256((uint64_t)B * (L > 1 ? L - 1 : 1) * v->d.Hr * sizeof(float));
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_vocoder_ar_fwd(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+                                    const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, double *nll_sum,
+                                    int64_t *n_scored, int64_t *n_correct, float *cond, void *saved, void *stream) {
+    const char *what = "vqcpc_vocoder_ar_fwd";
+    VQ_REQUIRE(nll_sum && n_scored && n_correct, "%s: null argument", what);
+    std::vector<int> slen;
+    int longest = 0;
+    TRY(check_call(v, what, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, saved, slen, &longest));
+    VQ_REQUIRE(aligned16(cond), "%s: cond must be 16-byte aligned", what);
+    hipStream_t s = (hipStream_t)stream;
+    ArView view;
+    TRY(view_of(v, w, true, &view, s));
+    const int T2 = 2 * Tc, C = 2 * v->d.Hp;
+    if (longest == 0 && cond) {                      // nothing to score: the scan's conditioning does not run, so it runs here
+        UttLayout u;
+        TRY(vq_tf_condition(v, idx, speaker, B, Tc, n_codes, slen, &view, u, s));
+    }
+    TRY(vq_tf_score(v, audio, idx, speaker, B, Tc, L, n_codes, slen, longest, &view, nll_sum, n_scored, n_correct, nullptr, (float *)saved, s));
+    if (cond)
+        hipLaunchKernelGGL(voc_cond_out_kernel, dim3(B * T2, (C + 255) / 256), dim3(256), 0, s, v->cond.as<float>(), cond, v->len.as<int>(),
+                           v->gbase.as<int>(), T2, C);
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}
+
+extern "C" int vqcpc_vocoder_ar_bwd(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+                                    const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const void *saved,
+                                    const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream) {
+    const char *what = "vqcpc_vocoder_ar_bwd";
+    std::vector<int> slen;
+    int longest = 0;
+    TRY(check_call(v, what, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, saved, slen, &longest));
+    const vqcpc_vocoder_ar_grads none{};
+    const vqcpc_vocoder_ar_grads &g = grads ? *grads : none;
+    bool any = grad_cond != nullptr;
+    for (int i = 0; i < 9; ++i) {
+        any = any || members(&g)[i];
+        VQ_REQUIRE(aligned16(members(&g)[i]), "%s: the tensors of *grads must be 16-byte aligned", what);
+    }
+    VQ_REQUIRE(any, "%s: no wanted output (every member of *grads and grad_cond are NULL)", what);
+    VQ_REQUIRE(aligned16(grad_cond) && ((uintptr_t)grad_loss & 3) == 0, "%s: grad_cond must be 16-byte aligned, grad_loss 4-byte", what);
+    long long N = 0;
+    for (int b = 0; b < B; ++b) N += slen[b];
+    VQ_REQUIRE(N > 0, "%s: N = 0, no utterance has two samples: the mean over the scored samples does not exist", what);
+    const float inv_n = (float)(1.0 / (double)N);
+
+    hipStream_t s = (hipStream_t)stream;
+    const auto &d = v->d;
+    const int Hr = d.Hr, Hf = d.Hf, n_cls = d.n_cls, de = d.de, C = 2 * d.Hp, T2 = 2 * Tc, up = d.upsample_t, Tsv = L - 1;
+    const int CH = v->tf_chunk_replays * v->steps_per_graph, nbt = (B + 15) / 16;
+    const size_t M = (size_t)B * CH, F = sizeof(float);
+    VQ_REQUIRE(M < ((size_t)1 << 26), "%s: B * chunk = %zu rows of one chunk do not fit the row index (< 2^26); lower tf_chunk_replays", what, M);
+    const bool need_fc1 = g.fc1_weight || g.fc1_bias;
+    const bool need_tabs = g.embedding || g.w_ih || g.b_ih || grad_cond, need_rnn = need_tabs || g.w_hh || g.b_hh;
+    VocGradWork &k = v->gw;
+    TRY(k.hcur.reserve(M * Hr * F));
+    TRY(k.a1.reserve(M * Hf * F));
+    TRY(k.dl.reserve(M * n_cls * F));
+    if (need_fc1 || need_rnn) TRY(k.da.reserve(M * Hf * F));
+    if (need_rnn) {
+        TRY(k.hprev.reserve(M * Hr * F));
+        TRY(k.gh.reserve(M * 3 * Hr * F));
+        TRY(k.nn.reserve(M * Hr * F));
+        TRY(k.dhh.reserve(M * Hr * F));
+        TRY(k.dgi.reserve((size_t)B * (CH + 1) * 3 * Hr * F));
+        TRY(k.dghn.reserve((size_t)B * (CH + 1) * Hr * F));
+        TRY(k.carry.reserve(up256((size_t)B * Hr * F)));
+    }
+    ArView view;
+    TRY(view_of(v, w, false, &view, s));
+    UttLayout u;
+    TRY(vq_tf_condition(v, idx, speaker, B, Tc, n_codes, slen, &view, u, s));
+    const size_t grows = (size_t)u.grows;            // > 0: some utterance scores a step, so it has a code
+    if (need_tabs) {
+        TRY(k.dGemb.reserve((size_t)n_cls * 3 * Hr * F));
+        TRY(k.dGc.reserve(grows * 3 * Hr * F));
+        HIP_TRY(hipMemsetAsync(k.dGemb.p, 0, (size_t)n_cls * 3 * Hr * F, s));
+        HIP_TRY(hipMemsetAsync(k.dGc.p, 0, grows * 3 * Hr * F, s));
+    }
+    const size_t out_elems[9] = {(size_t)n_cls * de, (size_t)3 * Hr * (de + C), (size_t)3 * Hr * Hr, (size_t)3 * Hr, (size_t)3 * Hr,
+                                 (size_t)Hf * Hr, (size_t)Hf, (size_t)n_cls * Hf, (size_t)n_cls};
+    for (int i = 0; i < 9; ++i)
+        if (members(&g)[i]) HIP_TRY(hipMemsetAsync(members(&g)[i], 0, out_elems[i] * F, s));
+    if (grad_cond) HIP_TRY(hipMemsetAsync(grad_cond, 0, (size_t)B * T2 * C * F, s));
+
+    // the plain tensors the products read: the caller's, or the handle's copies
+    const float *w_hh = w ? w->w_hh : v->w_hh.as<float>(), *b_hh = w ? w->b_hh : v->b_hh.as<float>();
+    const float *emb = w ? w->embedding : v->ar_emb.as<float>();
+    const float *w_emb = w ? w->w_ih : v->w_emb.as<float>(), *w_cond = w ? w->w_ih + de : v->w_cond.as<float>();
+    const int ld_emb = w ? de + C : de, ld_cond = w ? de + C : C;
+    const int *slen_dev = v->nll_len.as<int>(), *frames = v->len.as<int>(), *gbase = v->gbase.as<int>();
+    float *Hc = k.hcur.as<float>(), *Hp = k.hprev.as<float>(), *gh = k.gh.as<float>(), *nn = k.nn.as<float>(), *a1 = k.a1.as<float>();
+    float *dl = k.dl.as<float>(), *da = k.da.as<float>(), *dhh = k.dhh.as<float>(), *dgi = k.dgi.as<float>(), *dghn = k.dghn.as<float>();
+
+    const int nch = (longest + CH - 1) / CH;
+    for (int ch = nch - 1; ch >= 0; --ch) {
+        const int t0 = ch * CH, n = longest - t0 < CH ? longest - t0 : CH;
+        const VocRows q{slen_dev, audio, B, L, CH, t0, Hr};
+        const dim3 gh4((unsigned)((CH * (Hr / 4) + 255) / 256), B), ghr((unsigned)((CH * Hr + 255) / 256), B);
+        hipLaunchKernelGGL(voc_gather_h_kernel, gh4, dim3(256), 0, s, (const float4 *)saved, (float4 *)Hc, (float4 *)(need_rnn ? Hp : nullptr),
+                           slen_dev, CH, t0, Hr / 4, Tsv);
+        // head
+        TRY(vq_gemm_chain_ex(Hc, Hr, view.w_fc1, view.b_fc1, a1, Hf, (int)M, Hf, Hr, Hr, 1, 0, 0, 0, 0, s));
+        TRY(vq_gemm_chain(a1, Hf, view.w_fc2, view.b_fc2, dl, n_cls, (int)M, n_cls, Hf, Hf, s));
+        hipLaunchKernelGGL(voc_softmax_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, dl, q, grad_loss, inv_n);
+        VocAtbP p{};
+        p.q = q; p.R = (int)M;
+        if (g.fc2_weight) { p.A = dl; p.lda = n_cls; p.Bm = a1; p.ldb = Hf; p.out = g.fc2_weight; p.ldo = Hf; launch_atb<ATB_PLAIN>(p, n_cls, Hf, s); }
+        if (g.fc2_bias) { p.A = dl; p.lda = n_cls; p.out = g.fc2_bias; launch_colsum<ATB_PLAIN>(p, n_cls, s); }
+        if (need_fc1 || need_rnn) launch_rows_w(dl, view.w_fc2, Hf, da, a1, (long long)M, n_cls, Hf, nullptr, nullptr, 1, s);
+        if (g.fc1_weight) { p.A = da; p.lda = Hf; p.Bm = Hc; p.ldb = Hr; p.out = g.fc1_weight; p.ldo = Hr; launch_atb<ATB_PLAIN>(p, Hf, Hr, s); }
+        if (g.fc1_bias) { p.A = da; p.lda = Hf; p.out = g.fc1_bias; launch_colsum<ATB_PLAIN>(p, Hf, s); }
+        if (!need_rnn) continue;
+        launch_rows_w(da, view.w_fc1, Hr, dhh, nullptr, (long long)M, Hf, Hr, nullptr, nullptr, 1, s);
+        // gates again
+        TRY(vq_gemm_chain(Hp, Hr, w_hh, b_hh, gh, 3 * Hr, (int)M, 3 * Hr, Hr, Hr, s));
+        hipLaunchKernelGGL(voc_gates_kernel, ghr, dim3(256), 0, s, gh, nn, view.Gemb, v->gcond.as<float>(), gbase, q, up);
+        // the serial part
+        VocStepP sp{w_hh, gh, nn, Hp, dhh, dgi, dghn, k.carry.as<float>(), q, longest};
+        const dim3 grid(Hr / 16, nbt);
+        for (int t = t0 + n - 1; t >= t0; --t) {
+            if (Hr == 512) hipLaunchKernelGGL((voc_bwd_step_kernel<24>), grid, dim3(256), 0, s, sp, t);
+            else if (Hr == 896) hipLaunchKernelGGL((voc_bwd_step_kernel<42>), grid, dim3(256), 0, s, sp, t);
+            else hipLaunchKernelGGL((voc_bwd_step_kernel<48>), grid, dim3(256), 0, s, sp, t);
+        }
+        // the chunk's sums
+        p.A = dgi; p.A2 = dghn; p.Bm = Hp; p.ldb = Hr;
+        if (g.w_hh) { p.out = g.w_hh; p.ldo = Hr; launch_atb<ATB_WHH>(p, 3 * Hr, Hr, s); }
+        if (g.b_hh) { p.out = g.b_hh; launch_colsum<ATB_WHH>(p, 3 * Hr, s); }
+        if (need_tabs) {
+            p.Bm = dgi; p.ldb = 3 * Hr; p.out = k.dGemb.as<float>(); p.ldo = 3 * Hr;
+            launch_atb<ATB_GEMB>(p, n_cls, 3 * Hr, s);
+            hipLaunchKernelGGL(voc_frame_sum_kernel, dim3(B * T2, (3 * Hr + 255) / 256), dim3(256), 0, s, dgi, k.dGc.as<float>(), frames, gbase, q, T2, up);
+        }
+        if (ch > 0) hipLaunchKernelGGL(voc_keep_first_kernel, dim3((4 * Hr + 255) / 256, B), dim3(256), 0, s, dgi, dghn, CH, Hr);
+    }
+    if (need_tabs) {
+        float *dGemb = k.dGemb.as<float>(), *dGc = k.dGc.as<float>();
+        VocAtbP p{};
+        if (g.w_ih) {
+            p.A = dGemb; p.lda = 3 * Hr; p.Bm = emb; p.ldb = de; p.out = g.w_ih; p.ldo = de + C; p.R = n_cls;
+            launch_atb<ATB_PLAIN>(p, 3 * Hr, de, s);
+            p.A = dGc; p.Bm = v->cond.as<float>(); p.ldb = C; p.out = g.w_ih + de; p.R = (int)grows;
+            launch_atb<ATB_PLAIN>(p, 3 * Hr, C, s);
+        }
+        if (g.b_ih) { p.A = dGc; p.lda = 3 * Hr; p.out = g.b_ih; p.R = (int)grows; launch_colsum<ATB_PLAIN>(p, 3 * Hr, s); }
+        if (g.embedding) launch_rows_w(dGemb, w_emb, ld_emb, g.embedding, nullptr, n_cls, 3 * Hr, de, nullptr, nullptr, 1, s);
+        if (grad_cond) launch_rows_w(dGc, w_cond, ld_cond, grad_cond, nullptr, (long long)B * T2, 3 * Hr, C, frames, gbase, T2, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return VQCPC_OK;
+}

@@ -70,6 +70,7 @@ static std::vector<const DevBuf *> work_buffers(const vqcpc_vocoder *v) {
     std::vector<const DevBuf *> b = {&v->series, &v->gi, &v->out0, &v->cond, &v->gcond, &v->gbase, &v->hseq, &v->len, &v->hall, &v->a1c, &v->nll_part,
                                      &v->nll_len, &v->xd_x, &v->xd_segs};
     for (auto &G : v->grp) b.insert(b.end(), {&G.har, &G.a1, &G.cand_s, &G.cand_k, &G.slot_tab, &G.cur, &G.gcur, &G.candg});
+    for (const DevBuf *g : v->gw.all()) b.push_back(g);
     return b;
 }
 
@@ -85,9 +86,10 @@ extern "C" void vqcpc_vocoder_destroy(vqcpc_vocoder *v) { delete v; }
 
 static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v) {
     v->d = *w;
+    HIP_TRY(hipGetDevice(&v->device));
     const int F = w->dz + w->ds, Hp = w->Hp, dl = 2 * Hp, Hr = w->Hr, de = w->de;
     const hipMemcpyKind D2D = hipMemcpyDeviceToDevice;
-    DevBuf w_emb, emb;                   // temporaries of the Gemb table
+    DevPtr<float> &w_emb = v->w_emb, &emb = v->ar_emb;     // the Gemb table's two factors (kept: its gradients need them)
     TRY(dev_copy(v->code_emb, w->code_embedding, (size_t)w->n_codes * w->dz * sizeof(float), D2D));
     TRY(dev_copy(v->spk_emb, w->speaker_embedding, (size_t)w->n_speakers * w->ds * sizeof(float), D2D));
     for (int l = 0; l < 2; ++l) {
@@ -357,15 +359,38 @@ struct NllCall {
     std::vector<int> slen;               // scored steps per utterance: n_audio[b] - 1, at least 0
     float *nll;                          // DEVICE (B, L - 1) or null
     double *nll_sum; int64_t *n_scored, *n_correct;   // DEVICE (B)
+    ArView w;                            // the weights the scan and the head read
+    float *hsave;                        // DEVICE (B, L - 1, Hr) or null: h_t of every scored step (the gradients' forward)
 };
+
+ArView vq_vocoder_view(const vqcpc_vocoder *v) {
+    return ArView{v->w_cond, v->b_ih, v->Gemb, v->Gemb4, v->bh4, v->Wf_hh12, v->Wf_hh16, v->w_fc1, v->b_fc1, v->w_fc2, v->b_fc2, 0};
+}
+
+// h_t of the chunk's scored steps, from hall [B][CH][Hr] to the caller's (B, Tsv, Hr): grid (ceil(CH Hr / 4 / 256), B).  Rows at or
+// past an utterance's scored length are left alone: the backward does not read them.
+__global__ void tf_save_h_kernel(const float4 *__restrict__ hall, float4 *__restrict__ saved, const int *__restrict__ slen, int CH,
+                                 int t0, int Tsv, int H4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= CH * H4) return;
+    const int tt = i / H4, u = i % H4, t = t0 + tt;
+    if (t >= slen[b] || t >= Tsv) return;
+    saved[((size_t)b * Tsv + t) * H4 + u] = hall[((size_t)b * CH + tt) * H4 + u];
+}
 
 static int tf_chunk_nll(vqcpc_vocoder *v, int B, int CH, int chunk, const NllCall &nc, hipStream_t s) {
     NllHead h{};
-    h.hall = v->hall.as<float>(); h.w1 = v->w_fc1; h.b1 = v->b_fc1; h.w2 = v->w_fc2; h.b2 = v->b_fc2;
+    h.hall = v->hall.as<float>(); h.w1 = nc.w.w_fc1; h.b1 = nc.w.b_fc1; h.w2 = nc.w.w_fc2; h.b2 = nc.w.b_fc2;
     h.audio = nc.audio; h.slen = v->nll_len.as<int>(); h.nll = nc.nll; h.part = v->nll_part.as<NllPart>();
     h.status = v->status.dev; h.status_tag = v->epoch << 8;
     h.B = B; h.L = nc.L; h.CH = CH; h.t0 = chunk * CH; h.Hr = v->d.Hr;
-    return vq_tf_nll_chunk(h, nc.nll_sum, nc.n_scored, nc.n_correct, s);
+    TRY(vq_tf_nll_chunk(h, nc.nll_sum, nc.n_scored, nc.n_correct, s));
+    if (nc.hsave) {
+        const int H4 = v->d.Hr / 4;
+        hipLaunchKernelGGL(tf_save_h_kernel, dim3((unsigned)((CH * H4 + 255) / 256), B), dim3(256), 0, s, (const float4 *)v->hall.as<float>(),
+                           (float4 *)nc.hsave, v->nll_len.as<int>(), CH, chunk * CH, nc.L - 1, H4);
+    }
+    return VQCPC_OK;
 }
 // One resident, weight-stationary decoder per XCD (ar_xcd.hip, or its matrix-core form ar_xcm.hip): slot q runs the utterances
 // of cp.dp.lists[q] back to back (no replay boundaries here).
@@ -411,14 +436,15 @@ int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long lon
 
 // The cached graph of one replay of group g (captured on first use).  A graph bakes its ArModel's buffer pointers: when a
 // workspace of the group moved, the group's cached graphs are dropped first.
-static int group_graph(vqcpc_vocoder *v, int g, const ArModel &m, int nbt, bool tf, hipGraphExec_t *out) {
+static int group_graph(vqcpc_vocoder *v, int g, const ArModel &m, int nbt, bool tf, int alt, hipGraphExec_t *out) {
     auto &G = v->grp[g];
     const void *now[8] = {G.har.p, G.a1.p, G.cand_s.p, G.cand_k.p, G.cur.p, G.gcur.p, G.candg.p, nullptr};
     if (memcmp(G.baked, now, sizeof now) != 0) {
         clear_graphs(G);
         memcpy(G.baked, now, sizeof now);
     }
-    const int gkey = (((nbt * 17 + m.live_last) * 2 + m.lead6) * 2 + (tf ? 1 : 0)) * 3 + m.fused;   // what the capture bakes
+    // what the capture bakes; alt: the model reads a caller's weights from the gradient work space (fixed addresses of their own)
+    const int gkey = ((((nbt * 17 + m.live_last) * 2 + m.lead6) * 2 + (tf ? 1 : 0)) * 3 + m.fused) * 2 + alt;
     auto it = G.graphs.find(gkey);
     if (it == G.graphs.end()) {
         hipGraph_t gr = nullptr;
@@ -497,6 +523,9 @@ int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs,
         ArModel &m = models[g];
         m = ArModel{};
         m.Wf_hh12 = v->Wf_hh12; m.Wf_hh16 = v->Wf_hh16; m.bh4 = v->bh4; m.Gemb4 = v->Gemb4; m.Gemb = v->Gemb; m.Wf_fc1 = v->Wf_fc1; m.Wf_fc1h = v->Wf_fc1h; m.b_fc1 = v->b_fc1;
+        if (nc) {                                     // a scoring call's GRU steps read the call's view (the handle's, or a caller's weights)
+            m.Wf_hh12 = nc->w.Wf_hh12; m.Wf_hh16 = nc->w.Wf_hh16; m.bh4 = nc->w.bh4; m.Gemb4 = nc->w.Gemb4; m.Gemb = nc->w.Gemb;
+        }
         m.Wf_fc2 = v->Wf_fc2; m.b_fc2 = v->b_fc2; m.mulaw_tab = v->mulaw_tab;
         m.hbuf = G.har.as<float>(); m.a1 = G.a1.as<float>(); m.cand_s = G.cand_s.as<float>(); m.cand_k = G.cand_k.as<int>(); m.cur = G.cur.as<XdSeg>(); m.gcur4 = G.gcur.as<float4>();
         m.gc_replay = d.upsample_t % S == 0;
@@ -517,7 +546,7 @@ int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs,
     HIP_TRY(hipEventRecord(v->ev0, s));
     if (v->use_graph) {
         hipGraphExec_t exec[2] = {nullptr, nullptr};
-        for (int g = 0; g < cp.n_grp; ++g) TRY(group_graph(v, g, models[g], cp.tiles[g], tf, &exec[g]));
+        for (int g = 0; g < cp.n_grp; ++g) TRY(group_graph(v, g, models[g], cp.tiles[g], tf, nc ? nc->w.alt : 0, &exec[g]));
         if (cp.n_grp == 2) {              // group 1 runs on the side stream.  (Round 1 started it a fixed 12 000 cycles late "to
             HIP_TRY(hipEventRecord(v->ev_fork, s));                     // de-phase the groups": measured with and without, and with
             HIP_TRY(hipStreamWaitEvent(v->side_stream, v->ev_fork, 0));  // 40 000 -- the same 23.4 / 40.6 us per step at 256 / 512
@@ -575,7 +604,7 @@ int begin_call(vqcpc_vocoder *v, const CallPlan &cp, int B) {
 }
 
 int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, const int64_t *spk, int B, int Tc,
-                     DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s) {
+                     DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s, const float *w_cond, const float *b_ih) {
     const int Hr = v->d.Hr, dl = 2 * v->d.Hp;
     TRY(v->len.reserve(u.lens.size() * sizeof(int)));
     TRY(v->stage.upload(v->len.p, u.lens.data(), u.lens.size() * sizeof(int), s));
@@ -586,7 +615,34 @@ int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, c
     TRY(run_condition(v, idx, spk, B, Tc, v->len.as<int>(), gbase.as<int>(), (size_t)u.grows, cond.as<float>(), s));
     TRY(gcond.reserve(crows * 3 * Hr * sizeof(float)));
     if (u.grows > 0)
-        TRY(vq_gemm_chain(cond.as<float>(), dl, v->w_cond, v->b_ih, gcond.as<float>(), 3 * Hr, (int)u.grows, 3 * Hr, dl, dl, s));
+        TRY(vq_gemm_chain(cond.as<float>(), dl, w_cond ? w_cond : v->w_cond.as<float>(), b_ih ? b_ih : v->b_ih.as<float>(), gcond.as<float>(),
+                          3 * Hr, (int)u.grows, 3 * Hr, dl, dl, s));
+    return VQCPC_OK;
+}
+
+int vq_vocoder_relayout(vqcpc_vocoder *v, const float *embedding, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                        const float *fc1_weight, const float *fc1_bias, const float *fc2_weight, const float *fc2_bias, bool scan, ArView *out, hipStream_t s) {
+    // what vocoder_create_impl builds for the scan, from the caller's tensors, in stream order
+    const auto &d = v->d;
+    const int Hr = d.Hr, de = d.de, dl = 2 * d.Hp;
+    VocGradWork &g = v->gw;
+    TRY(g.w_emb.reserve((size_t)3 * Hr * de * sizeof(float)));
+    TRY(g.w_cond.reserve((size_t)3 * Hr * dl * sizeof(float)));
+    TRY(g.Gemb.reserve((size_t)d.n_cls * 3 * Hr * sizeof(float)));
+    hipLaunchKernelGGL(copy_submatrix_kernel, dim3((unsigned)(((size_t)3 * Hr * de + 255) / 256)), dim3(256), 0, s, w_ih, de + dl, 0, g.w_emb.as<float>(), 3 * Hr, de);
+    hipLaunchKernelGGL(copy_submatrix_kernel, dim3((unsigned)(((size_t)3 * Hr * dl + 255) / 256)), dim3(256), 0, s, w_ih, de + dl, de, g.w_cond.as<float>(), 3 * Hr, dl);
+    TRY(vq_gemm_chain(embedding, de, g.w_emb.as<float>(), nullptr, g.Gemb.as<float>(), 3 * Hr, d.n_cls, 3 * Hr, de, de, s));
+    if (scan) {
+        TRY(g.Gemb4.reserve((size_t)d.n_cls * Hr * sizeof(float4)));
+        TRY(g.bh4.reserve((size_t)Hr * sizeof(float4)));
+        hipLaunchKernelGGL(quads_build_kernel, dim3((unsigned)(((size_t)d.n_cls * Hr + 255) / 256)), dim3(256), 0, s, g.Gemb.as<float>(), g.Gemb4.as<float4>(), d.n_cls, Hr);
+        hipLaunchKernelGGL(quads_build_kernel, dim3((unsigned)((Hr + 255) / 256)), dim3(256), 0, s, b_hh, g.bh4.as<float4>(), 1, Hr);
+        TRY(build_wfrag12(w_hh, Hr, Hr / 4, Hr, Hr, g.Wf12, s));
+        if (Hr % 16 == 0) TRY(vq_build_wfrag(w_hh, Hr, 3 * (Hr / 16), Hr, 4, 16, Hr, g.Wf16, s));
+    }
+    HIP_TRY(hipGetLastError());
+    *out = ArView{g.w_cond.as<float>(), b_ih, g.Gemb.as<float>(), g.Gemb4.as<float4>(), g.bh4.as<float4>(), g.Wf12.as<float>(), g.Wf16.as<float>(),
+                  fc1_weight, fc1_bias, fc2_weight, fc2_bias, 1};
     return VQCPC_OK;
 }
 
@@ -600,7 +656,7 @@ static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int 
     CallPlan cp;
     TRY(plan_call(plan_opts(v), B, Tc, n_codes_host, inputs != nullptr, Ts, max_steps, utt_base, utt_ids_host, cp, nc ? nc->slen.data() : nullptr));
     TRY(begin_call(v, cp, B));
-    TRY(run_conditioning(v, cp, idx, spk, B, Tc, v->cond, v->gcond, v->gbase, s));
+    TRY(run_conditioning(v, cp, idx, spk, B, Tc, v->cond, v->gcond, v->gbase, s, nc ? nc->w.w_cond : nullptr, nc ? nc->w.b_ih : nullptr));
     if (wav) HIP_TRY(hipMemsetAsync(wav, 0, (size_t)B * Lout * sizeof(float), s));
     if (mulaw) HIP_TRY(hipMemsetAsync(mulaw, 0, (size_t)B * Lout * sizeof(int64_t), s));
     if (v->last_path != 0) v->last_path = 1;      // a call that fails from here on ran no decode loop
@@ -635,28 +691,54 @@ extern "C" int vqcpc_vocoder_nll(vqcpc_vocoder *v, const int64_t *audio, const i
                                  int L, const int *n_codes, const int *n_audio, double *nll_sum, int64_t *n_scored,
                                  int64_t *n_correct, float *nll, void *stream) {
     VQ_REQUIRE(v && audio && idx && speaker && nll_sum && n_scored && n_correct, "vqcpc_vocoder_nll: null argument");
+    std::vector<int> slen;
+    int longest = 0;
+    TRY(vq_tf_check(v, B, Tc, L, n_codes, n_audio, slen, &longest));
+    return vq_tf_score(v, audio, idx, speaker, B, Tc, L, n_codes, slen, longest, nullptr, nll_sum, n_scored, n_correct, nll, nullptr,
+                       (hipStream_t)stream);
+}
+
+int vq_tf_check(const vqcpc_vocoder *v, int B, int Tc, int L, const int *n_codes, const int *n_audio, std::vector<int> &slen, int *longest) {
     VQ_REQUIRE(B > 0 && Tc > 0 && L > 0, "vocoder.nll: need B > 0, Tc > 0 and L > 0 (got %d, %d, %d)", B, Tc, L);
     const auto &d = v->d;
     VQ_REQUIRE(d.Hf == NLL_HF && d.n_cls == NLL_CLS, "vocoder.nll: the scoring head is built for size_h_fc %d and %d classes "
                "(config.py:69,77), this model has %d and %d", NLL_HF, NLL_CLS, d.Hf, d.n_cls);
-    hipStream_t s = (hipStream_t)stream;
-    NllCall nc{audio, L, std::vector<int>(B, 0), nll, nll_sum, n_scored, n_correct};
-    int longest = 0;
+    slen.assign(B, 0);
+    *longest = 0;
     for (int b = 0; b < B; ++b) {
         const int na = n_audio ? n_audio[b] : L, ncd = n_codes ? n_codes[b] : Tc;
         VQ_REQUIRE(na >= 0 && na <= L, "vocoder.nll: n_audio[%d] = %d outside [0, %d]", b, na, L);
         VQ_REQUIRE(ncd >= 0 && ncd <= Tc, "vocoder: n_codes[%d] = %d outside [0, %d]", b, ncd, Tc);
         VQ_REQUIRE((long)na - 1 <= (long)2 * d.upsample_t * ncd, "vocoder.nll: utterance %d has %d samples to score but its %d codes "
                    "cover %ld (n_audio - 1 <= 2 * upsample_t * n_codes)", b, na - 1, ncd, (long)2 * d.upsample_t * ncd);
-        nc.slen[b] = na >= 2 ? na - 1 : 0;
-        longest = nc.slen[b] > longest ? nc.slen[b] : longest;
+        slen[b] = na >= 2 ? na - 1 : 0;
+        *longest = slen[b] > *longest ? slen[b] : *longest;
     }
+    return VQCPC_OK;
+}
+
+int vq_tf_score(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L, const int *n_codes,
+                const std::vector<int> &slen, int longest, const ArView *w, double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *nll,
+                float *hsave, hipStream_t s) {
+    NllCall nc{audio, L, slen, nll, nll_sum, n_scored, n_correct, w ? *w : vq_vocoder_view(v), hsave};
     HIP_TRY(hipMemsetAsync(nll_sum, 0, (size_t)B * sizeof(double), s));
     HIP_TRY(hipMemsetAsync(n_scored, 0, (size_t)B * sizeof(int64_t), s));
     HIP_TRY(hipMemsetAsync(n_correct, 0, (size_t)B * sizeof(int64_t), s));
     if (nll && L > 1) HIP_TRY(hipMemsetAsync(nll, 0, (size_t)B * (L - 1) * sizeof(float), s));
     if (longest == 0) return VQCPC_OK;         // no row has two samples: nothing to score
     return run_ar(v, idx, speaker, B, Tc, n_codes, audio, longest, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, s, &nc);
+}
+
+int vq_tf_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes, const std::vector<int> &slen,
+                    const ArView *w, UttLayout &u, hipStream_t s) {
+    CallPlan cp;                               // no decode loop: the layout alone sizes the staging arena
+    TRY(utt_layout(B, Tc, n_codes, v->d.upsample_t, 0, nullptr, cp));
+    TRY(begin_call(v, cp, B));
+    TRY(run_conditioning(v, cp, idx, speaker, B, Tc, v->cond, v->gcond, v->gbase, s, w ? w->w_cond : nullptr, w ? w->b_ih : nullptr));
+    TRY(v->nll_len.reserve((size_t)B * sizeof(int)));
+    TRY(v->stage.upload(v->nll_len.p, slen.data(), (size_t)B * sizeof(int), s));
+    u = cp;
+    return VQCPC_OK;
 }
 
 // Average wall time of `reps` back-to-back launches of each per-sample kernel (HIP events on

@@ -52,12 +52,36 @@ struct HostStage {
 // Defaults of the decode-loop options: the handle starts with them, and vqcpc_vocoder_plan takes them for -1 / 0.
 constexpr int XCM_MIN_DEFAULT = 68, XCM_MAX_DEFAULT = 512, XCD_SLOTS_DEFAULT = 8 * XD_MAX_BX, XCM_SLOTS_DEFAULT = 8 * XM_BX;
 
+// The sample-rate network's weights as the teacher-forced scan, its head and the conditioning's last product read them: the
+// handle's copies (alt 0), or the layouts a gradient entry made from a caller's tensors for one call (alt 1; the captured step
+// graphs bake these pointers, so the two sets have graphs of their own).
+struct ArView {
+    const float *w_cond, *b_ih;          // W_ih[:, de:] as a contiguous (3Hr, C); (3Hr)
+    const float *Gemb;                   // [n_cls][3Hr]
+    const float4 *Gemb4, *bh4;
+    const float *Wf_hh12, *Wf_hh16;
+    const float *w_fc1, *b_fc1, *w_fc2, *b_fc2;      // plain
+    int alt;
+};
+
+// Work space of the vocoder gradients (vocoder_grad.hip), grow-only, counted by vqcpc_vocoder_workspace_bytes.
+struct VocGradWork {
+    DevBuf w_emb, w_cond, Gemb, Gemb4, bh4, Wf12, Wf16;       // a caller's weights, re-laid per call
+    DevBuf hcur, hprev, gh, nn, a1, dl, da, dhh, dgi, dghn, carry, dGemb, dGc;     // backward: one chunk's rows, the carry, the two table gradients
+    std::vector<const DevBuf *> all() const {
+        return {&w_emb, &w_cond, &Gemb, &Gemb4, &bh4, &Wf12, &Wf16, &hcur, &hprev, &gh, &nn, &a1, &dl, &da, &dhh, &dgi, &dghn, &carry, &dGemb, &dGc};
+    }
+};
+
 struct vqcpc_vocoder {
     ~vqcpc_vocoder();                    // what is not memory: graphs, the arena's pending uploads, streams, events (vocoder_host.hip)
     vqcpc_vocoder_weights d;             // dims only (the weights below are owned copies)
+    int device = 0;                      // the device the handle was created on
     DevPtr<float> code_emb, spk_emb;
     DevPtr<float> p_wih[2], p_bih[2], p_bhh[2], p_wf[2];   // per layer, both directions stacked
     DevPtr<float> w_cond, b_ih, Gemb;
+    DevPtr<float> ar_emb, w_emb;         // plain copies of the sample embedding and of W_ih[:, :de] (the gradients of the Gemb table)
+    VocGradWork gw;
     DevPtr<float4> Gemb4, bh4;
     DevPtr<float> Wf_hh12, Wf_hh16, b_hh, Wf_fc1, Wf_fc1h, b_fc1, Wf_fc2, b_fc2;
     DevPtr<float> w_fc1, w_fc2;          // plain (rows, K) copies for the teacher-forced scan's batched GEMMs
@@ -177,6 +201,28 @@ PlanOpts plan_opts(const vqcpc_vocoder *v);
 // Start of every call that uploads: an earlier call's report, the next epoch, the staging arena sized for this plan.
 int begin_call(vqcpc_vocoder *v, const CallPlan &cp, int B);
 // Upload the layout's frame counts and row bases, run the prenet over every utterance's own frames and make the Gcond rows.
-int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, const int64_t *spk, int B, int Tc, DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s);
+// w_cond, b_ih: the last product's operands (an ArView's), null = the handle's copies.
+int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, const int64_t *spk, int B, int Tc, DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s,
+                     const float *w_cond = nullptr, const float *b_ih = nullptr);
+
+// ------------------------------------------------------------------------------------------
+// what the gradient entries (vocoder_grad.hip) call in vocoder_host.hip
+// ------------------------------------------------------------------------------------------
+ArView vq_vocoder_view(const vqcpc_vocoder *v);
+// The layouts of ArView from a caller's tensors, enqueued on s into v->gw.  scan: also what only the step kernels read (unit quads,
+// W_hh fragments); without it the view serves the conditioning's last product and the Gemb table alone.
+int vq_vocoder_relayout(vqcpc_vocoder *v, const float *embedding, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                        const float *fc1_weight, const float *fc1_bias, const float *fc2_weight, const float *fc2_bias, bool scan, ArView *out, hipStream_t s);
+// The host-visible conditions of a scoring call (vqcpc_vocoder_nll's), and its scored steps per utterance.
+int vq_tf_check(const vqcpc_vocoder *v, int B, int Tc, int L, const int *n_codes, const int *n_audio, std::vector<int> &slen, int *longest);
+// The scoring call itself: vqcpc_vocoder_nll's scan and head with the weights of `w` (null = the handle's); hsave (B, L - 1, Hr) or
+// null receives h_t of every scored step.
+int vq_tf_score(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L, const int *n_codes,
+                const std::vector<int> &slen, int longest, const ArView *w, double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *nll,
+                float *hsave, hipStream_t s);
+// Conditioning of a backward call: a call's start (begin_call), then cond (ragged rows), Gcond, the frame counts (v->len) and row
+// bases (v->gbase) on the device, and the scored steps in v->nll_len.
+int vq_tf_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes, const std::vector<int> &slen,
+                    const ArView *w, UttLayout &u, hipStream_t s);
 int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long long seed, float *wav, int64_t *mulaw, hipStream_t s, const Resume *rs = nullptr);
 int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs, int T2, int Ts, unsigned long long seed, float *wav, int64_t *mulaw, float *logits, hipStream_t s, const Resume *rs = nullptr, const NllCall *nc = nullptr);

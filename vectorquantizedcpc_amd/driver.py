@@ -460,31 +460,21 @@ def scored_samples(n_audio: int, n_codes: int, upsample: int = 160) -> int:
 
 
 @torch.no_grad()
-def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speakers: Sequence[int], max_batch: int = 64,
-                  max_pad_frac: float = 0.25, conf=None):
-    """Teacher-forced score of a vocoder checkpoint on held-out utterances -- the validation number the reference does not
-    compute (its ``validation_step`` returns 0 because whole utterances do not batch there, ``vocoder.py:68-94``).
-
-    ``waves_or_mels``: per utterance a 1-D waveform at the front end's rate (16 kHz: after any resampling, before pre-emphasis)
-    or a (n_mels, T) log-mel.  ``audio``: per utterance the int mu-law classes to score, or None with waveforms: then they are
-    ``mulaw_classes`` of the same waveform.  mel -> ``Encoder.encode`` -> code indices -> length buckets -> ``Vocoder.nll`` with
-    ``n_codes`` / ``lengths`` per bucket.  Returns ``(records, totals)``: one dict per utterance (``nll_sum``, ``n_scored``,
-    ``n_correct``, ``n_codes``, ``indices`` = the code indices it was conditioned on, ``n_cut`` = samples of the utterance that
-    the codes do not cover and that were cut) and the
-    corpus totals (``loss`` in nats per sample, ``bits_per_sample``, ``accuracy``, ``n_scored``, ``n_correct``, ``nll_sum``,
-    ``n_cut``, ``n_utterances``)."""
-    import math
+def _vocoder_utterances(encoder, vocoder, waves_or_mels, audio, speakers, max_batch, max_pad_frac, conf, who):
+    """What ``score_vocoder`` and ``fit_vocoder`` make of their utterances before the vocoder runs: waveforms -> mels (batched HIP
+    front end), mels -> ``encode_utterances`` -> code indices, the mu-law classes (``mulaw_classes`` of the waveforms where
+    ``audio`` is None) and the samples of each that a scoring call takes.  -> ``(codes, n_codes, audio, keep)``."""
     from . import preprocess
     dev = next(encoder.parameters()).device
     up = vocoder.conf.rnnms.upsampling_t
     n = len(waves_or_mels)
     if len(speakers) != n or (audio is not None and len(audio) != n):
-        raise ValueError("score_vocoder: one speaker (and one audio array) per utterance")
+        raise ValueError(f"{who}: one speaker (and one audio array) per utterance")
     mels = list(waves_or_mels)
     is_wave = [torch.as_tensor(m).dim() == 1 for m in mels]
     if audio is None:
         if not all(is_wave):
-            raise ValueError("score_vocoder: audio=None needs waveforms (the classes are made from them)")
+            raise ValueError(f"{who}: audio=None needs waveforms (the classes are made from them)")
         audio = [mulaw_classes(w, vocoder.conf.rnnms.bits_mu_law) for w in mels]
     wave_ids = [i for i in range(n) if is_wave[i]]
     if wave_ids:
@@ -499,6 +489,28 @@ def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, spea
     n_codes = [int(c["indices"].numel()) for c in codes]
     audio = [torch.as_tensor(a).to(torch.int64).reshape(-1) for a in audio]
     keep = [scored_samples(a.numel(), nc, up) for a, nc in zip(audio, n_codes)]
+    return codes, n_codes, audio, keep
+
+
+@torch.no_grad()
+def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speakers: Sequence[int], max_batch: int = 64,
+                  max_pad_frac: float = 0.25, conf=None):
+    """Teacher-forced score of a vocoder checkpoint on held-out utterances -- the validation number the reference does not
+    compute (its ``validation_step`` returns 0 because whole utterances do not batch there, ``vocoder.py:68-94``).
+
+    ``waves_or_mels``: per utterance a 1-D waveform at the front end's rate (16 kHz: after any resampling, before pre-emphasis)
+    or a (n_mels, T) log-mel.  ``audio``: per utterance the int mu-law classes to score, or None with waveforms: then they are
+    ``mulaw_classes`` of the same waveform.  mel -> ``Encoder.encode`` -> code indices -> length buckets -> ``Vocoder.nll`` with
+    ``n_codes`` / ``lengths`` per bucket.  Returns ``(records, totals)``: one dict per utterance (``nll_sum``, ``n_scored``,
+    ``n_correct``, ``n_codes``, ``indices`` = the code indices it was conditioned on, ``n_cut`` = samples of the utterance that
+    the codes do not cover and that were cut) and the
+    corpus totals (``loss`` in nats per sample, ``bits_per_sample``, ``accuracy``, ``n_scored``, ``n_correct``, ``nll_sum``,
+    ``n_cut``, ``n_utterances``)."""
+    import math
+    dev = next(encoder.parameters()).device
+    n = len(waves_or_mels)
+    codes, n_codes, audio, keep = _vocoder_utterances(encoder, vocoder, waves_or_mels, audio, speakers, max_batch, max_pad_frac, conf,
+                                                      "score_vocoder")
     records: List[Optional[dict]] = [None] * n
     for ids in make_buckets(keep, [0] * n, max_batch, max_pad_frac):
         z = _pad_batch([codes[i]["indices"] for i in ids], dev, torch.int64, min_len=1)
@@ -515,6 +527,78 @@ def score_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, spea
     tot["bits_per_sample"] = tot["loss"] / math.log(2.0)
     tot["accuracy"] = tot["n_correct"] / tot["n_scored"] if tot["n_scored"] else float("nan")
     return records, tot
+
+
+def training_cuts(indices, audio, n_codes, keep, upsample: int, clip_codes: Optional[int], seed: int):
+    """The cuts ``fit_vocoder`` trains on: per utterance its code indices and the ``keep`` classes they cover; with ``clip_codes``,
+    an utterance with more codes keeps a cut of that many from a start drawn from ``torch.Generator().manual_seed(seed)`` (one draw
+    per such utterance, in order) and the ``2 * upsample * clip_codes + 1`` samples under it.  -> ``(indices, audio, n_codes, keep)``
+    as new lists.  Pure host code: the float64 reference of the tests cuts with it as well."""
+    indices, audio = list(indices), [a[:k] for a, k in zip(audio, keep)]
+    n_codes, keep = list(n_codes), list(keep)
+    if clip_codes is not None:
+        if clip_codes < 1:
+            raise ValueError(f"fit_vocoder: clip_codes must be at least 1 or None, got {clip_codes}")
+        gen = torch.Generator().manual_seed(int(seed))
+        for i, nc in enumerate(n_codes):
+            if nc > clip_codes:
+                start = int(torch.randint(0, nc - clip_codes + 1, (1,), generator=gen))
+                indices[i] = indices[i][start:start + clip_codes]
+                audio[i] = audio[i][2 * upsample * start: 2 * upsample * (start + clip_codes) + 1]
+                n_codes[i], keep[i] = clip_codes, int(audio[i].numel())
+    return indices, audio, n_codes, keep
+
+
+def fit_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speakers: Sequence[int], steps: int = 200, lr: float = 4e-4,
+                optimizer=torch.optim.Adam, max_batch: int = 32, max_pad_frac: float = 0.25, clip_codes: Optional[int] = 16, seed: int = 13,
+                conf=None):
+    """Refit the vocoder's sample-rate network ``vocoder.rnnms.ar`` (embedding, GRU, fc1, fc2) on the units a frozen encoder
+    produces -- the vocoder objective of ``vocoder.py:62-63`` -- after ``adapt_codebook`` or ``fit_encoder`` moved those units, or for
+    new speakers and recording conditions (``score_vocoder`` -> ``fit_vocoder`` -> ``score_vocoder``).  ``code_embedding``,
+    ``speaker_embedding`` and ``rnnms.prenet`` stay frozen (their backward is not built yet).
+
+    The utterances, their codes and classes are prepared exactly as ``score_vocoder`` prepares them (the same function), once,
+    under ``no_grad``.  ``clip_codes``: every utterance with more codes keeps a seeded cut of that many codes and the
+    ``2 * upsampling_t * clip_codes + 1`` samples they cover -- 16 gives the reference's (., 5120) training shape; None: whole
+    utterances.  The reference clips the MEL before it encodes; this cuts the CODES after the whole utterance was encoded, so the
+    units at the edges of a cut have seen their context.  The buckets are ``score_vocoder``'s (``make_buckets``); step i takes bucket
+    ``i mod n``.  Every step is ``vocoder.nll(..., differentiable=True).loss.backward()`` -- one ``vqcpc_vocoder_ar_fwd`` and one
+    ``vqcpc_vocoder_ar_bwd`` call -- then one step of ``optimizer(vocoder.rnnms.ar.parameters(), lr=lr)`` (torch's, as glue).  The
+    native handle is not rebuilt between steps; it is refreshed once at the end, so that ``generate`` and ``nll`` see the new
+    weights.
+
+    Returns ``losses`` (per step, before that step's update), ``steps``, ``batches`` and ``utterances`` (those with at least one
+    sample to score)."""
+    dev = next(encoder.parameters()).device
+    up = vocoder.conf.rnnms.upsampling_t
+    codes, n_codes, audio, keep = _vocoder_utterances(encoder, vocoder, waves_or_mels, audio, speakers, max_batch, max_pad_frac, conf,
+                                                      "fit_vocoder")
+    idx, audio, n_codes, keep = training_cuts([c["indices"] for c in codes], audio, n_codes, keep, up, clip_codes, seed)
+    live = [i for i in range(len(idx)) if keep[i] >= 2]
+    batches = []
+    for ids in make_buckets([keep[i] for i in live], [0] * len(live), max_batch, max_pad_frac):
+        ids = [live[k] for k in ids]
+        batches.append((_pad_batch([audio[i] for i in ids], "cpu", torch.int64, min_len=1).to(dev),
+                        _pad_batch([idx[i] for i in ids], dev, torch.int64, min_len=1),
+                        torch.tensor([int(speakers[i]) for i in ids], device=dev), [keep[i] for i in ids], [n_codes[i] for i in ids]))
+    res = {"losses": [], "steps": 0, "batches": len(batches), "utterances": len(live)}
+    if not batches or steps <= 0:
+        return res
+    params = list(vocoder.rnnms.ar.parameters())
+    if not any(p.requires_grad for p in params):
+        raise ValueError("fit_vocoder: no parameter of vocoder.rnnms.ar requires a gradient")
+    opt = optimizer(params, lr=lr)
+    for step in range(steps):
+        a, z, spk, lengths, ncs = batches[step % len(batches)]
+        opt.zero_grad(set_to_none=True)
+        with torch.enable_grad():
+            loss = vocoder.nll(a, z, spk, lengths=lengths, n_codes=ncs, differentiable=True).loss
+            loss.backward()
+        opt.step()
+        res["losses"].append(float(loss.detach()))
+        res["steps"] = step + 1
+    vocoder.refresh()
+    return res
 
 
 # ---------------------------------------------------------------------------------------- ABX scoring

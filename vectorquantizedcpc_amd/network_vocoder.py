@@ -97,6 +97,9 @@ class Vocoder(_lib.NativeModule):
                      ["rnnms.ar.embedding.weight"] + [f"rnnms.ar.rnn.{k}_l0" for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] +
                      [f"rnnms.ar.{fc}.{k}" for fc in ("fc1", "fc2") for k in ("weight", "bias")])
 
+    # what the gradient entries read from the handle's copies although the nine tensors of rnnms.ar are the caller's
+    _FROZEN_NAMES = frozenset(n for n in _WEIGHT_NAMES if not n.startswith("rnnms.ar."))
+
     def _weights(self, p):
         w = _lib.VocoderWeights()
         w.code_embedding, w.speaker_embedding = p("code_embedding.weight"), p("speaker_embedding.weight")
@@ -271,16 +274,18 @@ class Vocoder(_lib.NativeModule):
             self.check()              # a bad z / speaker raises here, like nn.Embedding, and is not left latched for generate()
         return logits
 
-    @torch.no_grad()
-    def nll(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, per_sample: bool = False) -> "VocoderNLL":
-        """Teacher-forced negative log-likelihood per utterance: the vocoder's training objective (``vocoder.py:62-63``: the
-        energies of ``audio[:, :-1]`` against the targets ``audio[:, 1:]``) as a number for held-out data, without the
-        ``(B, T_s, 2**bits)`` energies ever existing (``vqcpc_vocoder_nll``).
+    # ------------------------------------------------------------------ scoring and its gradients
+    AR_KEYS = ("embedding", "w_ih", "w_hh", "b_ih", "b_hh", "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")   # vqcpc_vocoder_ar_weights
 
-        ``audio`` (B, L) integer mu-law classes; ``lengths`` valid samples per row of a padded batch (default L): row b scores
-        the positions ``0 .. lengths[b] - 2`` and nothing behind them is read; ``n_codes`` valid codes per row (default T'),
-        with ``lengths[b] - 1 <= 2 * upsampling_t * n_codes[b]``.  ``per_sample=True`` also returns the (B, L - 1) fp32 values.
-        A class outside ``[0, 2**bits)`` in a scored position raises ``IndexError``.  Synchronises its stream (``check()``)."""
+    def _ar_params(self):
+        """The nine parameters of ``rnnms.ar`` in the order of ``AR_KEYS``."""
+        ar = self.rnnms.ar
+        return [ar.embedding.weight, ar.rnn.weight_ih_l0, ar.rnn.weight_hh_l0, ar.rnn.bias_ih_l0, ar.rnn.bias_hh_l0,
+                ar.fc1.weight, ar.fc1.bias, ar.fc2.weight, ar.fc2.bias]
+
+    def _nll_call(self, audio: Tensor, z: Tensor, speaker: Tensor, lengths, n_codes):
+        """What every scoring entry takes, checked: ``(audio, z, speaker, B, Tc, L, n_audio, n_codes)`` with the tensors int64,
+        contiguous and on the module's device and the two per-utterance lists as ``c_int`` arrays (or None)."""
         z, speaker = self._prep(z, speaker)
         _lib.require_cuda(audio, "audio")
         _lib.require_same_device(audio, self.code_embedding.weight, "audio")
@@ -290,8 +295,120 @@ class Vocoder(_lib.NativeModule):
         if audio.is_floating_point() or audio.dtype == torch.bool:
             raise RuntimeError("audio must be an integer tensor of mu-law classes (the targets of F.cross_entropy, vocoder.py:63)")
         audio = audio.detach().to(torch.int64).contiguous()
-        L = audio.size(1)
-        na, nc = _lib.int_array(lengths, B, "lengths"), _lib.int_array(n_codes, B, "n_codes")
+        return (audio, z, speaker, B, Tc, audio.size(1), _lib.int_array(lengths, B, "lengths"), _lib.int_array(n_codes, B, "n_codes"))
+
+    def _ar_struct(self, tensors):
+        """``VocoderArTensors`` of nine tensors (None = NULL member), or None for ``tensors`` None."""
+        if tensors is None:
+            return None
+        s = _lib.VocoderArTensors()
+        for k, t in zip(self.AR_KEYS, tensors):
+            setattr(s, k, None if t is None else t.data_ptr())
+        return s
+
+    def _ar_weights(self, weights, dev):
+        """The nine tensors a gradient call reads: None (the handle's copies) or nine fp32 tensors on ``dev``, made contiguous."""
+        if weights is None:
+            return None
+        ws = [w.detach().contiguous() for w in weights]
+        for k, w, p in zip(self.AR_KEYS, ws, self._ar_params()):
+            if w.dtype != torch.float32 or w.device != dev or w.shape != p.shape:
+                raise RuntimeError(f"rnnms.ar {k} must be a float32 tensor of shape {tuple(p.shape)} on {dev} "
+                                   f"(got {w.dtype}, {tuple(w.shape)}, {w.device})")
+        return ws
+
+    def _ar_fwd(self, call, weights=None, want_cond: bool = False):
+        """One ``vqcpc_vocoder_ar_fwd`` call -> (nll_sum, n_scored, n_correct, cond or None, saved).  ``call``: ``_nll_call``'s
+        tuple; ``weights``: ``_ar_weights``'s list."""
+        audio, z, speaker, B, Tc, L, na, nc = call
+        dev = z.device
+        h = self._sizes_handle(dev, self._FROZEN_NAMES) if weights is not None else self._native()
+        lib = _lib.load()
+        n = C.c_uint64()
+        _lib.check(lib.vqcpc_vocoder_ar_saved_bytes(h, B, L, C.byref(n)))
+        nll_sum = torch.empty(B, dtype=torch.float64, device=dev)
+        n_scored = torch.empty(B, dtype=torch.int64, device=dev)
+        n_correct = torch.empty(B, dtype=torch.int64, device=dev)
+        cond = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=dev) if want_cond else None
+        saved = torch.empty(int(n.value) // 4, device=dev)
+        with _lib.device_guard(dev):
+            _lib.check(lib.vqcpc_vocoder_ar_fwd(h, audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, self._ar_struct(weights),
+                                                nll_sum.data_ptr(), n_scored.data_ptr(), n_correct.data_ptr(),
+                                                cond.data_ptr() if want_cond else None, saved.data_ptr(), _lib.current_stream()))
+        return nll_sum, n_scored, n_correct, cond, saved
+
+    def _ar_bwd(self, call, saved, weights=None, grad_loss=None, want=(True,) * 9, cond_grad: bool = False):
+        """One ``vqcpc_vocoder_ar_bwd`` call -> (nine gradients or None in the order of ``AR_KEYS``, grad_cond or None).
+        ``grad_loss``: fp32 device scalar or None = 1."""
+        audio, z, speaker, B, Tc, L, na, nc = call
+        dev = z.device
+        h = self._sizes_handle(dev, self._FROZEN_NAMES) if weights is not None else self._native()
+        grads = [torch.empty_like(p, memory_format=torch.contiguous_format) if w else None for p, w in zip(self._ar_params(), want)]
+        gc = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=dev) if cond_grad else None
+        with _lib.device_guard(dev):
+            _lib.check(_lib.load().vqcpc_vocoder_ar_bwd(h, audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, self._ar_struct(weights),
+                                                        saved.data_ptr(), None if grad_loss is None else grad_loss.data_ptr(),
+                                                        self._ar_struct(grads), gc.data_ptr() if cond_grad else None, _lib.current_stream()))
+        return grads, gc
+
+    @torch.no_grad()
+    def ar_gradients(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, want=AR_KEYS, cond_grad: bool = False,
+                     weights=None, grad_loss=None) -> dict:
+        """The gradients of ``nll(...).loss`` (the mean NLL over every scored sample of the batch) with respect to the tensors of
+        ``rnnms.ar`` that ``want`` names (keys of ``AR_KEYS``), and with ``cond_grad=True`` with respect to the conditioning series:
+        one ``vqcpc_vocoder_ar_fwd`` and one ``vqcpc_vocoder_ar_bwd`` call (``csrc/vocoder_grad.hip``).  -> dict of device tensors:
+        the wanted keys, ``cond`` and ``grad_cond`` (B, 2T', dim_voc_latent) with ``cond_grad``, ``loss`` (float64 scalar),
+        ``nll_sum``, ``n_scored``, ``n_correct``.  ``weights``: nine tensors in the order of ``AR_KEYS`` read in place of the
+        module's parameters' copies in the native handle (default: the parameters themselves, as they are now); ``grad_loss``: the
+        upstream gradient, a number (default 1).  ``code_embedding``, ``speaker_embedding`` and ``rnnms.prenet`` are frozen: they
+        receive no gradient.  Synchronises its stream (``check()``)."""
+        unknown = [k for k in want if k not in self.AR_KEYS]
+        if unknown:
+            raise ValueError(f"ar_gradients: unknown tensors {unknown}; known: {self.AR_KEYS}")
+        call = self._nll_call(audio, z, speaker, lengths, n_codes)
+        dev = call[1].device
+        ws = self._ar_weights(self._ar_params() if weights is None else weights, dev)
+        nll_sum, n_scored, n_correct, cond, saved = self._ar_fwd(call, ws, cond_grad)
+        gl = None if grad_loss is None else torch.tensor(float(grad_loss), dtype=torch.float32, device=dev)
+        grads, gc = self._ar_bwd(call, saved, ws, gl, tuple(k in want for k in self.AR_KEYS), cond_grad)
+        with _lib.device_guard(dev):
+            self.check()
+        out = {k: g for k, g in zip(self.AR_KEYS, grads) if g is not None}
+        out.update(loss=nll_sum.sum() / n_scored.sum(), nll_sum=nll_sum, n_scored=n_scored, n_correct=n_correct)
+        if cond_grad:
+            out.update(cond=cond, grad_cond=gc)
+        return out
+
+    def nll(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, per_sample: bool = False,
+            differentiable: bool = False) -> "VocoderNLL":
+        """Teacher-forced negative log-likelihood per utterance: the vocoder's training objective (``vocoder.py:62-63``: the
+        energies of ``audio[:, :-1]`` against the targets ``audio[:, 1:]``) as a number for held-out data, without the
+        ``(B, T_s, 2**bits)`` energies ever existing (``vqcpc_vocoder_nll``).
+
+        ``audio`` (B, L) integer mu-law classes; ``lengths`` valid samples per row of a padded batch (default L): row b scores
+        the positions ``0 .. lengths[b] - 2`` and nothing behind them is read; ``n_codes`` valid codes per row (default T'),
+        with ``lengths[b] - 1 <= 2 * upsampling_t * n_codes[b]``.  ``per_sample=True`` also returns the (B, L - 1) fp32 values.
+        A class outside ``[0, 2**bits)`` in a scored position raises ``IndexError``.  Synchronises its stream (``check()``).
+
+        ``differentiable=True`` (grad mode on, a parameter of ``rnnms.ar`` requiring grad): the returned ``.loss`` carries a
+        ``grad_fn``.  Its forward is ``vqcpc_vocoder_ar_fwd`` on the parameters as they are (an optimizer step costs no new
+        handle) and keeps ``h_t`` of every scored step; ``loss.backward()`` is one ``vqcpc_vocoder_ar_bwd`` call that asks only
+        for the gradients of those of the nine ``rnnms.ar`` parameters that require one.  ``code_embedding``,
+        ``speaker_embedding`` and ``rnnms.prenet`` are frozen in this path and receive NO gradient.  ``per_sample`` is not
+        available with it."""
+        if differentiable and torch.is_grad_enabled() and any(p.requires_grad for p in self._ar_params()):
+            if per_sample:
+                raise ValueError("Vocoder.nll: per_sample is not available with differentiable=True")
+            call = self._nll_call(audio, z, speaker, lengths, n_codes)
+            loss, nll_sum, n_scored, n_correct = _ArGrad.apply(self, call, *self._ar_params())
+            with _lib.device_guard(call[1].device):
+                self.check()
+            return VocoderNLL(nll_sum, n_scored, n_correct, None, loss)
+        with torch.no_grad():
+            return self._nll_scored(audio, z, speaker, lengths, n_codes, per_sample)
+
+    def _nll_scored(self, audio, z, speaker, lengths, n_codes, per_sample):
+        audio, z, speaker, B, Tc, L, na, nc = self._nll_call(audio, z, speaker, lengths, n_codes)
         dev = z.device
         nll_sum = torch.empty(B, dtype=torch.float64, device=dev)
         n_scored = torch.empty(B, dtype=torch.int64, device=dev)
@@ -339,11 +456,35 @@ class VocoderNLL:
     n_scored: Tensor
     n_correct: Tensor
     nll: object = None
+    attached: object = None       # ``Vocoder.nll(..., differentiable=True)``: the same mean, carrying its ``grad_fn``
 
     @property
     def loss(self) -> Tensor:
         """Mean over every scored sample; with equal lengths exactly the reference's ``F.cross_entropy`` mean (``vocoder.py:63``)."""
-        return self.nll_sum.sum() / self.n_scored.sum()
+        return self.attached if self.attached is not None else self.nll_sum.sum() / self.n_scored.sum()
+
+
+class _ArGrad(torch.autograd.Function):
+    """``Vocoder.nll(..., differentiable=True)``: ``forward`` is ``vqcpc_vocoder_ar_fwd`` and keeps ``saved``; ``backward`` is one
+    ``vqcpc_vocoder_ar_bwd`` call asking for the gradients ``needs_input_grad`` names."""
+
+    @staticmethod
+    def forward(ctx, module, call, *ws):
+        weights = module._ar_weights(ws, call[1].device)
+        nll_sum, n_scored, n_correct, _, saved = module._ar_fwd(call, weights)
+        ctx.module, ctx.kept = module, (call, saved)
+        ctx.save_for_backward(*ws)                       # torch refuses the backward if an in-place step has moved them since
+        ctx.mark_non_differentiable(nll_sum, n_scored, n_correct)
+        return nll_sum.sum() / n_scored.sum(), nll_sum, n_scored, n_correct
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, *_):
+        call, saved = ctx.kept
+        module = ctx.module
+        grads, _ = module._ar_bwd(call, saved, module._ar_weights(ctx.saved_tensors, call[1].device),
+                                  grad_loss.to(torch.float32).contiguous(), ctx.needs_input_grad[2:])
+        return (None, None) + tuple(grads)
 
 
 class VocoderStream:
