@@ -2,7 +2,7 @@
  * vqcpc_vocoder_grad.h -- C ABI of libvqcpc_hip.so, third header: the gradients of the vocoder objective (vocoder.py:62-63,
  * F.cross_entropy of the teacher-forced energies of audio[:, :-1] against audio[:, 1:]) through the sample-rate network
  * rnnms.ar.* -- embedding, GRU, fc1, fc2 -- and with respect to the conditioning series that feeds it.  The prenet and the two
- * embedding tables in front of it are frozen here: grad_cond is where a later backward of theirs starts.
+ * embedding tables in front of it are frozen here: grad_cond is where their backward (vqcpc_vocoder_cond_grad.h) starts.
  *
  * Why a header of its own: tests/test_gpu_stream_contract.py and tests/test_gpu_front_grad_stream.py each require the set of
  * stream-taking entries of ONE header (vqcpc.h, vqcpc_grad.h) to equal their own table.  The entries below take a stream; they

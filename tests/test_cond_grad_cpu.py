@@ -1,0 +1,182 @@
+"""No GPU: the float64 reference of the conditioning path's gradients (tests/cond_grad_ref.py) -- its forward against
+``oracle.f64_ref.F64Vocoder.condition``, its pins against a fresh run, the recorded fits -- and what of the fourth header and its
+Python surface needs no device."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import cond_grad_ref as R
+import grad_judge
+import voc_fit_ref
+import voc_grad_ref as VR
+import vectorquantizedcpc_amd as V
+from oracle import f64_ref
+from vectorquantizedcpc_amd import _lib, cli, driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FAST = [n for n in R.ALL_CASES if n != "long"]
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_forward_equals_the_float64_oracle(name):
+    c = R.load(name)
+    want = f64_ref.F64Vocoder(c["sd"]).condition(c["z"], c["spk"], c["n_codes"])
+    got = R.grads64(name)["cond"]
+    for b, w in enumerate(want):
+        n = w.shape[0]
+        assert n == 2 * c["n_codes"][b] and not got[b, n:].any()
+        if n:
+            assert np.abs(got[b, :n] - w.numpy()).max() <= 1e-12 * np.abs(w.numpy()).max(), b
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_pins_equal_a_fresh_run(name):
+    grad_judge.check_pins(R.grads64(name), R.pins(), name, R.KEYS + ("cond",), R.POSITIONS)
+
+
+@pytest.mark.parametrize("name", ["h512"])
+def test_chain_pins_equal_a_fresh_run(name):
+    ref = R.chain64(name)
+    grad_judge.check_pins(ref, R.pins(), "chain_" + name, R.ALL27, R.POSITIONS)
+    assert abs(float(ref["loss"]) - float(R.pins()[f"chain_{name}_loss"])) <= 1e-12
+    # fed by the frozen conditioning it is the loss of tests/voc_grad_ref.py, and the nine gradients of rnnms.ar are its
+    ar = VR.grads64(name)
+    assert abs(float(ref["loss"]) - float(ar["loss"])) <= 1e-12
+    for k, n in zip(VR.KEYS, R.AR_NAMES):
+        assert np.abs(ref[n] - ar[k]).max() <= 1e-12 * np.abs(ar[k]).max(), k
+
+
+def test_cases_cover_what_they_name():
+    cs = {n: R.load(n) for n in FAST}
+    assert cs["ragged"]["n_codes"] == [2, 5, 3, 4, 6, 0] and cs["b17"]["B"] == 17 and cs["b1"]["B"] == 1
+    assert cs["hp64"]["C"] == 128 and cs["hp256"]["C"] == 512 and (cs["dz_ne_ds"]["dz"], cs["dz_ne_ds"]["ds"]) == (96, 32)
+    long = R.CASES["long"]
+    rows = 2 * sum(long["n_codes"])
+    assert rows == 2300 and -(-rows // 1024) == 3 and rows % 1024 and 2 * max(long["n_codes"]) == 1400
+    # one_code: every other row of both table gradients is zero, and the shared speaker's row sums both of its utterances
+    g, c = R.grads64("one_code"), cs["one_code"]
+    assert not g["code_embedding.weight"][np.arange(R.N_CODES) != 77].any() and g["code_embedding.weight"][77].any()
+    spk = g["speaker_embedding.weight"]
+    assert not spk[[i for i in range(R.N_SPK) if i not in (7, 30)]].any() and spk[7].any() and spk[30].any()
+    alone = []
+    for b in (0, 2):                                                 # the two utterances of speaker 7, each alone
+        m = R.Conditioning(c["sd"])
+        x = m(c["z"][b:b + 1], c["spk"][b:b + 1], c["n_codes"][b:b + 1])[0]
+        (x * c["G"][b, :x.shape[0]].double()).sum().backward()
+        alone.append(m.grads()["speaker_embedding.weight"][7].numpy())
+    assert np.abs(spk[7] - (alone[0] + alone[1])).max() <= 1e-12 * np.abs(spk[7]).max()
+    # sparse_upstream: only utterance 1 contributes
+    g, c = R.grads64("sparse_upstream"), cs["sparse_upstream"]
+    named = set(c["z"][1, :c["n_codes"][1]].tolist())
+    assert not g["code_embedding.weight"][[k for k in range(R.N_CODES) if k not in named]].any()
+    assert not g["speaker_embedding.weight"][np.arange(R.N_SPK) != int(c["spk"][1])].any()
+    # the stressed set saturates gates of the prenet: some reset or update gate within 1e-3 of 0 or 1
+    assert float(cs["stressed"]["sd"]["rnnms.prenet.weight_ih_l0"].abs().max()) > 3.9 * float(cs["b1"]["sd"]["rnnms.prenet.weight_ih_l0"].abs().max())
+
+
+def test_b_ih_and_b_hh_differ_in_the_n_third_only():
+    g = R.grads64("b1")
+    Hp = R.load("b1")["C"] // 2
+    a, b = g["rnnms.prenet.bias_ih_l1_reverse"], g["rnnms.prenet.bias_hh_l1_reverse"]
+    assert np.abs(a[:2 * Hp] - b[:2 * Hp]).max() <= 1e-15 and np.abs(a[2 * Hp:] - b[2 * Hp:]).max() > 1e-6
+
+
+def test_recorded_fits_are_trends():
+    for run, (train, steps, lr) in R.FIT_RUNS.items():
+        losses = R.pins()[f"fit_{run}_losses"]
+        assert losses.shape == (steps,)
+        dec, spread = voc_fit_ref.decrease(losses), float(losses[-5:].max() - losses[-5:].min())
+        print(f"float64 fit {run} {train}: loss {losses[0]:.6f} -> mean of the last five {losses[-5:].mean():.6f}: decrease {dec:.4f}, "
+              f"spread of the last five {spread:.4f}")
+        assert dec > 0 and dec >= 4.0 * spread
+
+
+# ------------------------------------------------------------------ the header
+def declared():
+    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_cond_grad.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(vqcpc_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_every_declared_symbol_is_exported_and_bound():
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    names = declared()
+    assert len(names) == 5
+    for n in names:
+        assert hasattr(lib, n), f"{n} declared in include/vqcpc_vocoder_cond_grad.h but not exported"
+        assert getattr(_lib.load(), n).argtypes is not None, n
+    assert sorted(_lib.COND_GRAD_SYMBOLS) == names
+    assert not set(_lib.COND_GRAD_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.GRAD_SYMBOLS) | set(_lib.VOC_GRAD_SYMBOLS))
+    assert _lib.load().vqcpc_abi_version() == 1
+
+
+def test_header_is_plain_c(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('''#include "vqcpc_vocoder_cond_grad.h"
+#include <stddef.h>
+int use(vqcpc_vocoder *voc, int64_t *i, float *p, double *d, void *saved, void *s) {
+    vqcpc_vocoder_cond_weights w;
+    vqcpc_vocoder_cond_grads g = {0};
+    uint64_t n = 0;
+    int l, k, rc = vqcpc_vocoder_cond_saved_bytes(voc, 2, 16, &n);
+    w.code_embedding = p; w.speaker_embedding = p;
+    for (l = 0; l < 2; ++l)
+        for (k = 0; k < 2; ++k) { w.prenet_w_ih[l][k] = p; w.prenet_w_hh[l][k] = p; w.prenet_b_ih[l][k] = p; w.prenet_b_hh[l][k] = p; }
+    g.code_embedding = p; g.prenet_b_hh[1][1] = p;
+    rc |= vqcpc_vocoder_cond_fwd(voc, i, i, 2, 16, NULL, &w, p, saved, s);
+    rc |= vqcpc_vocoder_cond_bwd(voc, i, i, 2, 16, NULL, NULL, saved, p, &g, s);
+    rc |= vqcpc_vocoder_ar_fwd_cond(voc, i, i, i, 2, 1, 321, NULL, NULL, NULL, p, d, i, i, NULL, saved, s);
+    rc |= vqcpc_vocoder_ar_bwd_cond(voc, i, i, i, 2, 1, 321, NULL, NULL, NULL, p, saved, NULL, NULL, p, s);
+    return rc;
+}
+''')
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only",
+                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_cond_tensors_struct_mirrors_the_header():
+    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_cond_grad.h")).read()
+    for kind, what in (("const float", "weights"), ("float", "grads")):
+        body = re.search(r"typedef struct \{([^}]*)\} vqcpc_vocoder_cond_%s;" % what, text).group(1)
+        assert re.findall(r"\b%s \*(\w+)(?:\[2\]\[2\])?;" % kind, body) == [n for n, _ in _lib.VocoderCondTensors._fields_]
+    assert ctypes.sizeof(_lib.VocoderCondTensors) == 18 * ctypes.sizeof(ctypes.c_void_p)
+    assert V.Vocoder.COND_KEYS == R.KEYS and V.Vocoder.AR_NAMES == R.AR_NAMES
+    voc = V.Vocoder(V.ConfVocoder())
+    assert sorted(V.Vocoder.COND_KEYS + V.Vocoder.AR_NAMES) == sorted(voc.state_dict())
+    # the struct's members in the order of COND_KEYS
+    s = voc._cond_struct([None] * 18)
+    assert s.code_embedding is None and s.prenet_b_hh[1][1] is None
+    params = voc._cond_params()
+    s = voc._cond_struct(params)
+    assert s.prenet_w_ih[1][0] == voc.rnnms.prenet.weight_ih_l1.data_ptr() and s.prenet_b_hh[0][1] == voc.rnnms.prenet.bias_hh_l0_reverse.data_ptr()
+    assert s.prenet_w_hh[1][1] == voc.rnnms.prenet.weight_hh_l1_reverse.data_ptr() and s.speaker_embedding == voc.speaker_embedding.weight.data_ptr()
+
+
+# ------------------------------------------------------------------ argument checks that need no GPU
+def test_train_names_are_checked():
+    voc = V.Vocoder(V.ConfVocoder())
+    for bad in (("ar", "ar"), ("prenet", "mel"), (), ("embedding",)):
+        with pytest.raises(ValueError, match="train must name each of"):
+            voc.nll(None, None, None, differentiable=True, train=bad)
+        with pytest.raises(ValueError, match="train must name each of"):
+            driver.fit_vocoder(None, voc, [], None, [], train=bad)
+    assert [len(voc._part_params(p)) for p in voc.TRAIN_PARTS] == [9, 16, 2]
+    with pytest.raises(ValueError, match="unknown tensors"):
+        voc.cond_gradients(None, None, None, want=("rnnms.ar.fc1.bias",))
+
+
+def test_cli_fit_vocoder_train_parses(capsys):
+    with pytest.raises(SystemExit) as e:
+        cli.main(["fit-vocoder", "--help"])
+    assert e.value.code == 0
+    assert "--train" in capsys.readouterr().out
+    for bad in ("ar,ar", "prenet,mel", ","):
+        with pytest.raises(SystemExit) as e:
+            cli.main(["fit-vocoder", "--dataset", "x", "--in-dir", "y", "--random-init", "--out", "z", "--train", bad])
+        assert e.value.code == 2
+    assert "fit-vocoder --train" in capsys.readouterr().err

@@ -41,6 +41,10 @@ GRAD_SYMBOLS = ["vqcpc_encoder_front_saved_bytes", "vqcpc_encoder_front_fwd", "v
 # every symbol include/vqcpc_vocoder_grad.h declares, likewise
 VOC_GRAD_SYMBOLS = ["vqcpc_vocoder_ar_saved_bytes", "vqcpc_vocoder_ar_fwd", "vqcpc_vocoder_ar_bwd"]
 
+# every symbol include/vqcpc_vocoder_cond_grad.h declares, likewise
+COND_GRAD_SYMBOLS = ["vqcpc_vocoder_cond_saved_bytes", "vqcpc_vocoder_cond_fwd", "vqcpc_vocoder_cond_bwd", "vqcpc_vocoder_ar_fwd_cond",
+                     "vqcpc_vocoder_ar_bwd_cond"]
+
 
 class EncoderWeights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p), ("ln_weight", C.c_void_p * 5), ("ln_bias", C.c_void_p * 5),
@@ -69,6 +73,14 @@ class VocoderArTensors(C.Structure):
     """``vqcpc_vocoder_ar_weights`` and ``vqcpc_vocoder_ar_grads`` (``include/vqcpc_vocoder_grad.h``): the same nine members of
     ``rnnms.ar``, read or written."""
     _fields_ = [(n, C.c_void_p) for n in ("embedding", "w_ih", "w_hh", "b_ih", "b_hh", "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")]
+
+
+class VocoderCondTensors(C.Structure):
+    """``vqcpc_vocoder_cond_weights`` and ``vqcpc_vocoder_cond_grads`` (``include/vqcpc_vocoder_cond_grad.h``): the same eighteen
+    members of the conditioning path, read or written; the prenet's indexed ``[layer][direction]`` as in ``VocoderWeights``."""
+    _fields_ = [("code_embedding", C.c_void_p), ("speaker_embedding", C.c_void_p),
+                ("prenet_w_ih", (C.c_void_p * 2) * 2), ("prenet_w_hh", (C.c_void_p * 2) * 2),
+                ("prenet_b_ih", (C.c_void_p * 2) * 2), ("prenet_b_hh", (C.c_void_p * 2) * 2)]
 
 
 class CPCWeights(C.Structure):
@@ -153,6 +165,14 @@ def load():
                                          vp, i64p, i64p, vp, vp, vp]
     lib.vqcpc_vocoder_ar_bwd.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(VocoderArTensors),
                                          vp, vp, C.POINTER(VocoderArTensors), vp, vp]
+    lib.vqcpc_vocoder_cond_saved_bytes.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
+    lib.vqcpc_vocoder_cond_fwd.argtypes = [vp, i64p, i64p, i32, i32, C.POINTER(C.c_int), C.POINTER(VocoderCondTensors), vp, vp, vp]
+    lib.vqcpc_vocoder_cond_bwd.argtypes = [vp, i64p, i64p, i32, i32, C.POINTER(C.c_int), C.POINTER(VocoderCondTensors), vp, vp,
+                                           C.POINTER(VocoderCondTensors), vp]
+    lib.vqcpc_vocoder_ar_fwd_cond.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                              C.POINTER(VocoderArTensors), vp, vp, i64p, i64p, vp, vp, vp]
+    lib.vqcpc_vocoder_ar_bwd_cond.argtypes = [vp, i64p, i64p, i64p, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                              C.POINTER(VocoderArTensors), vp, vp, vp, C.POINTER(VocoderArTensors), vp, vp]
     lib.vqcpc_vocoder_condition.argtypes = [vp, i64p, i64p, i32, i32, vp, vp]
     lib.vqcpc_vocoder_glue.argtypes = [vp, i64p, i64p, i32, i32, vp, vp]
     lib.vqcpc_vocoder_set_option.argtypes = [vp, C.c_char_p, i32]

@@ -58,7 +58,9 @@ the edit distance between index runs).
 ``fit-vocoder`` refits the vocoder's sample-rate network ``rnnms.ar`` (embedding, GRU, fc1, fc2) on the same utterances, conditioned
 on the units of the (frozen) encoder -- the step after ``adapt-codebook`` / ``fit-encoder``, or for a new speaker
 (``driver.fit_vocoder``: forward and back-propagation through time are ``vqcpc_vocoder_ar_fwd`` / ``_bwd``, the optimizer torch's
-Adam; the prenet and the two embedding tables stay frozen).  It prints the ``score-vocoder`` line before and after and writes
+Adam).  ``--train ar,prenet,embeddings`` names the parts that step: by default the prenet and the two embedding tables stay
+frozen; with them named the whole ``loss.backward()`` runs in HIP down to ``code_embedding.weight`` (``vqcpc_vocoder_cond_fwd`` /
+``_bwd``) -- after the codebook moved, ``code_embedding`` is the table the moved indices index.  It prints the ``score-vocoder`` line before and after and writes
 ``{"vocoder": state_dict}``.
 ``score-vocoder`` is the validation number the reference's vocoder training never computes (``vocoder.py:68-94``): the
 teacher-forced cross-entropy of ``vocoder.py:62-63`` on ``<in_dir>/<utterance>.wav`` of every entry of ``test.json``, speaker id
@@ -253,6 +255,11 @@ def score_vocoder_dataset(args) -> int:
     return 0
 
 
+def _vocoder_parts(train: str):
+    """``--train ar,prenet,embeddings`` -> the tuple ``driver.fit_vocoder`` takes."""
+    return tuple(t for t in train.split(",") if t)
+
+
 def fit_vocoder_dataset(args) -> int:
     """score, ``driver.fit_vocoder``, score again on the same utterances, and the vocoder checkpoint (``{"vocoder": state_dict}``,
     as ``convert`` and ``score-vocoder`` read it)."""
@@ -263,17 +270,18 @@ def fit_vocoder_dataset(args) -> int:
     print("before the fit:")
     print(_vocoder_line(driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)[1]))
     r = driver.fit_vocoder(enc, voc, waves, None, speakers, steps=args.steps, lr=args.lr, max_batch=min(args.max_batch, 32),
-                           clip_codes=args.clip_codes if args.clip_codes > 0 else None, seed=args.seed)
+                           clip_codes=args.clip_codes if args.clip_codes > 0 else None, seed=args.seed, train=_vocoder_parts(args.train))
     if r["steps"] == 0:
         print("no utterance with two samples to score: nothing fitted")
         return 1
-    print(f"fitted rnnms.ar (embedding, GRU, fc1, fc2) in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches of "
+    fitted = {"ar": "rnnms.ar (embedding, GRU, fc1, fc2)", "prenet": "rnnms.prenet", "embeddings": "code_embedding and speaker_embedding"}
+    print(f"fitted {', '.join(fitted[t] for t in _vocoder_parts(args.train))} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches of "
           f"{r['utterances']} utterances: loss {r['losses'][0]:.6f} -> {r['losses'][-1]:.6f}")
     print("after the fit:")
     print(_vocoder_line(driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)[1]))
     sd = {k: v.detach().cpu().clone() for k, v in voc.state_dict().items()}
     torch.save({"vocoder": sd}, args.out)
-    print(f"wrote {args.out}: \"vocoder\" ({len(sd)} keys; rnnms.ar.* refitted, the rest as it was)")
+    print(f"wrote {args.out}: \"vocoder\" ({len(sd)} keys; {args.train} refitted, the rest as it was)")
     return 0
 
 
@@ -415,6 +423,8 @@ def main(argv=None) -> int:
                 p.add_argument("--lr", type=float, default=4e-4, help="Adam's learning rate")
                 p.add_argument("--clip-codes", type=int, default=16, help="codes per training cut (16: the reference's 5120 samples); 0: whole utterances")
                 p.add_argument("--seed", type=int, default=synth.SEED)
+                p.add_argument("--train", default="ar", help="comma-separated parts that step, of " + ",".join(Vocoder.TRAIN_PARTS) +
+                               ": rnnms.ar, rnnms.prenet, and the code and speaker embedding tables")
                 p.add_argument("--out", required=True, help="the vocoder checkpoint to write")
         else:
             p.add_argument("--vocoder-checkpoint")
@@ -451,6 +461,10 @@ def main(argv=None) -> int:
         parts = [t for t in args.train.split(",") if t]
         if not parts or len(set(parts)) != len(parts) or any(t not in driver.FIT_ENCODER_PARTS for t in parts):
             ap.error(f"fit-encoder --train: name each of {','.join(driver.FIT_ENCODER_PARTS)} at most once, and at least one")
+    if args.cmd == "fit-vocoder":
+        parts = _vocoder_parts(args.train)
+        if not parts or len(set(parts)) != len(parts) or any(t not in Vocoder.TRAIN_PARTS for t in parts):
+            ap.error(f"fit-vocoder --train: name each of {','.join(Vocoder.TRAIN_PARTS)} at most once, and at least one")
     if args.cmd in ("score-vocoder", "fit-vocoder") and not args.random_init and not args.vocoder_checkpoint:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,

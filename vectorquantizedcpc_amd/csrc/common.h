@@ -136,6 +136,9 @@ int vq_build_wfrag(const float *W, int ldw, int n_rg, int K, int ksplit, int row
 // len / row0: valid steps and first row of every utterance (ragged rows), or null = T steps from row b * T.
 int vq_bigru_scan(const float *Wf, const float *b_hh, const float *Gi, float *hbuf, float *out, const int *len, const int *row0,
                   int H, int B, int T, hipStream_t s);
+// W_hh^T of a recurrent layer (K gate rows, H columns) in the fragment order of the backward scans' MFMA (context_grad.hip,
+// build_wfrag_t_kernel): (H / 16) (K / 16) 64 float4 into WfT.  H % 16 == 0, K % 64 == 0.
+void vq_build_wfrag_t(const float *w_hh, float *WfT, int H, int K, hipStream_t s);
 struct LstmPlan;   // opaque, owns fragment-ordered weights
 int vq_lstm_plan_create(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
                         int D, int H, LstmPlan **out);

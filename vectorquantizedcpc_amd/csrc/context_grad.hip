@@ -47,13 +47,13 @@
 namespace {
 
 // W_hh^T in fragment order: WfT[((rg * 4 + w) * NS + s) * 64 + lane] (float4) = W_hh[16 S + 4 (lane >> 4) + 0 .. 3][16 rg + (lane & 15)],
-// S = w NS + s, NS = H / 16 (K = 4H over four waves).
-__global__ void build_wfrag_t_kernel(const float *__restrict__ w_hh, float4 *__restrict__ WfT, int H) {
-    const size_t total = (size_t)(H / 16) * (H / 4) * 64;
+// S = w NS + s, NS = K / 64 (the K gate rows of W_hh over four waves: K = 4H here, 3H for the prenet's GRU layers in prenet_grad.hip).
+__global__ void build_wfrag_t_kernel(const float *__restrict__ w_hh, float4 *__restrict__ WfT, int H, int K) {
+    const size_t total = (size_t)(H / 16) * (K / 16) * 64;
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= total) return;
     const int lane = (int)(id & 63);
-    const int S = (int)((id >> 6) % (size_t)(H / 4)), rg = (int)((id >> 6) / (size_t)(H / 4));
+    const int S = (int)((id >> 6) % (size_t)(K / 16)), rg = (int)((id >> 6) / (size_t)(K / 16));
     const float *src = w_hh + (size_t)(16 * S + 4 * (lane >> 4)) * H + 16 * rg + (lane & 15);
     WfT[id] = make_float4(src[0], src[H], src[2 * (size_t)H], src[3 * (size_t)H]);
 }
@@ -178,6 +178,11 @@ __global__ __launch_bounds__(256) void ctx_grad_z_kernel(const float *dA, const 
 
 }  // namespace
 
+void vq_build_wfrag_t(const float *w_hh, float *WfT, int H, int K, hipStream_t s) {
+    const size_t nfrag = (size_t)(H / 16) * (K / 16) * 64;
+    hipLaunchKernelGGL(build_wfrag_t_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, s, w_hh, (float4 *)WfT, H, K);
+}
+
 size_t vq_ctx_saved_bytes(int B, int T, int H) { return (size_t)B * T * 6 * H * sizeof(float); }
 
 static SeqSave saved_view(const float *saved, int B, int T, int H) {
@@ -210,8 +215,7 @@ int vq_ctx_bwd(CtxGradWork &k, LstmWeights w, const float *z, int B, int T, cons
     TRY(k.dA.reserve(up256((size_t)R * M * sizeof(float))));
     TRY(k.carry.reserve(up256((size_t)B * H * sizeof(float))));
     if (want_w) TRY(k.part.reserve(up256((size_t)slabs * M * ld * sizeof(float))));
-    const size_t nfrag = (size_t)(H / 16) * (H / 4) * 64;
-    hipLaunchKernelGGL(build_wfrag_t_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, s, w.w_hh, k.WfT.as<float4>(), H);
+    vq_build_wfrag_t(w.w_hh, k.WfT.as<float>(), H, M, s);
     const SeqSave sv = saved_view(saved, B, T, H);
     CtxBwdP p{};
     p.WfT = k.WfT.as<float4>(); p.gates = sv.gates; p.cell = sv.cell; p.tanhc = sv.tanhc; p.grad_c = grad_c;

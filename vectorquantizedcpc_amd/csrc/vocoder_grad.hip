@@ -1,6 +1,8 @@
 // Gradients of the vocoder objective (vocoder.py:62-63: F.cross_entropy of the teacher-forced energies of audio[:, :-1] against
 // audio[:, 1:]) through the sample-rate network rnnms.ar.* -- embedding, GRU, fc1, fc2 -- and with respect to the conditioning
-// series: vqcpc_vocoder_ar_fwd / _bwd of include/vqcpc_vocoder_grad.h.  The prenet and the two tables in front of it are frozen.
+// series: vqcpc_vocoder_ar_fwd / _bwd of include/vqcpc_vocoder_grad.h, and their *_cond forms of include/vqcpc_vocoder_cond_grad.h, which
+// take the conditioning series from the caller instead of running the prenet.  The prenet and the two tables in front of it are frozen
+// here; their backward is prenet_grad.hip, fed by grad_cond.
 // B utterances, Hr = size_h_rnn, Hf = n_cls = 256, de = size_i_embed_ar, C = dim_voc_latent, up = upsampling_t.  Utterance b scores
 // the steps t < slen[b] = max(n_audio[b] - 1, 0): step t is fed x = audio[b, t], reads conditioning frame t / up and is scored against
 // audio[b, t + 1].  Gate order r, z, n; h_t = n + z (h_{t-1} - n) (oracle/f64_ref.py:64-69).  loss = sum_b nll_sum[b] / N.
@@ -59,7 +61,7 @@
 // earlier call left in the work space never reaches a result.
 #include "vocoder_internal.h"
 #include "grad_slab.h"
-#include "../../include/vqcpc_vocoder_grad.h"
+#include "../../include/vqcpc_vocoder_cond_grad.h"
 
 namespace {
 
@@ -308,14 +310,6 @@ __global__ void voc_frame_sum_kernel(const float *__restrict__ dgi, float *__res
     *o = *o + sum;
 }
 
-// cond (rows of the utterances' own frames) -> (B, T2, C), +0 past an utterance's frames.  grid (B T2, ceil(C / 256))
-__global__ void voc_cond_out_kernel(const float *__restrict__ cond, float *__restrict__ out, const int *__restrict__ frames,
-                                    const int *__restrict__ gbase, int T2, int C) {
-    const int c = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x / T2, f = blockIdx.x % T2;
-    if (c >= C) return;
-    out[(size_t)blockIdx.x * C + c] = f < frames[b] ? cond[((size_t)gbase[b] + f) * C + c] : 0.f;
-}
-
 template <int MODE> void launch_atb(const VocAtbP &p, int Na, int Nb, hipStream_t s) {
     hipLaunchKernelGGL((voc_atb_kernel<MODE>), dim3(Nb / 16, Na / 64), dim3(256), 0, s, p);
 }
@@ -353,7 +347,29 @@ int view_of(vqcpc_vocoder *v, const vqcpc_vocoder_ar_weights *w, bool scan, ArVi
     return vq_vocoder_relayout(v, w->embedding, w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->fc1_weight, w->fc1_bias, w->fc2_weight, w->fc2_bias, scan, view, s);
 }
 
+// the forward and the backward behind both forms of their entries; cond_in: the conditioning series given, or null = the prenet runs
+int ar_fwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+           const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const float *cond_in, double *nll_sum,
+           int64_t *n_scored, int64_t *n_correct, float *cond, void *saved, void *stream);
+int ar_bwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+           const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const float *cond_in, const void *saved,
+           const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream);
+
 }  // namespace
+
+void vq_grad_atb(const float *A, int lda, const float *Bm, int ldb, float *out, int ldo, int R, int Na, int Nb, hipStream_t s) {
+    VocAtbP p{};
+    p.A = A; p.lda = lda; p.Bm = Bm; p.ldb = ldb; p.out = out; p.ldo = ldo; p.R = R;
+    launch_atb<ATB_PLAIN>(p, Na, Nb, s);
+}
+void vq_grad_colsum(const float *A, int lda, float *out, int R, int Na, hipStream_t s) {
+    VocAtbP p{};
+    p.A = A; p.lda = lda; p.out = out; p.R = R;
+    launch_colsum<ATB_PLAIN>(p, Na, s);
+}
+void vq_grad_rows_w(const float *A, const float *W, int ldw, float *out, int R, int K, int N, hipStream_t s) {
+    launch_rows_w(A, W, ldw, out, nullptr, R, K, N, nullptr, nullptr, 1, s);
+}
 
 extern "C" int vqcpc_vocoder_ar_saved_bytes(vqcpc_vocoder *v, int B, int L, uint64_t *bytes) {
     VQ_REQUIRE(v && bytes, "vqcpc_vocoder_ar_saved_bytes: null argument");
@@ -367,7 +383,32 @@ extern "C" int vqcpc_vocoder_ar_saved_bytes(vqcpc_vocoder *v, int B, int L, uint
 extern "C" int vqcpc_vocoder_ar_fwd(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
                                     const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, double *nll_sum,
                                     int64_t *n_scored, int64_t *n_correct, float *cond, void *saved, void *stream) {
-    const char *what = "vqcpc_vocoder_ar_fwd";
+    return ar_fwd("vqcpc_vocoder_ar_fwd", v, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, nullptr, nll_sum, n_scored, n_correct, cond, saved, stream);
+}
+extern "C" int vqcpc_vocoder_ar_fwd_cond(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+                                         const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const float *cond_in,
+                                         double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *cond, void *saved, void *stream) {
+    VQ_REQUIRE(cond_in && aligned16(cond_in), "vqcpc_vocoder_ar_fwd_cond: cond_in must be given and 16-byte aligned");
+    return ar_fwd("vqcpc_vocoder_ar_fwd_cond", v, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, cond_in, nll_sum, n_scored, n_correct, cond, saved, stream);
+}
+extern "C" int vqcpc_vocoder_ar_bwd(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+                                    const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const void *saved,
+                                    const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream) {
+    return ar_bwd("vqcpc_vocoder_ar_bwd", v, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, nullptr, saved, grad_loss, grads, grad_cond, stream);
+}
+extern "C" int vqcpc_vocoder_ar_bwd_cond(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+                                         const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const float *cond_in,
+                                         const void *saved, const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond,
+                                         void *stream) {
+    VQ_REQUIRE(cond_in && aligned16(cond_in), "vqcpc_vocoder_ar_bwd_cond: cond_in must be given and 16-byte aligned");
+    return ar_bwd("vqcpc_vocoder_ar_bwd_cond", v, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, cond_in, saved, grad_loss, grads, grad_cond, stream);
+}
+
+namespace {
+
+int ar_fwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+           const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const float *cond_in, double *nll_sum,
+           int64_t *n_scored, int64_t *n_correct, float *cond, void *saved, void *stream) {
     VQ_REQUIRE(nll_sum && n_scored && n_correct, "%s: null argument", what);
     std::vector<int> slen;
     int longest = 0;
@@ -379,20 +420,17 @@ extern "C" int vqcpc_vocoder_ar_fwd(vqcpc_vocoder *v, const int64_t *audio, cons
     const int T2 = 2 * Tc, C = 2 * v->d.Hp;
     if (longest == 0 && cond) {                      // nothing to score: the scan's conditioning does not run, so it runs here
         UttLayout u;
-        TRY(vq_tf_condition(v, idx, speaker, B, Tc, n_codes, slen, &view, u, s));
+        TRY(vq_tf_condition(v, idx, speaker, B, Tc, n_codes, slen, &view, u, s, cond_in));
     }
-    TRY(vq_tf_score(v, audio, idx, speaker, B, Tc, L, n_codes, slen, longest, &view, nll_sum, n_scored, n_correct, nullptr, (float *)saved, s));
-    if (cond)
-        hipLaunchKernelGGL(voc_cond_out_kernel, dim3(B * T2, (C + 255) / 256), dim3(256), 0, s, v->cond.as<float>(), cond, v->len.as<int>(),
-                           v->gbase.as<int>(), T2, C);
+    TRY(vq_tf_score(v, audio, idx, speaker, B, Tc, L, n_codes, slen, longest, &view, nll_sum, n_scored, n_correct, nullptr, (float *)saved, s, cond_in));
+    if (cond) vq_cond_rows(v->cond.as<float>(), cond, v->len.as<int>(), v->gbase.as<int>(), B, T2, C, true, s);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }
 
-extern "C" int vqcpc_vocoder_ar_bwd(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
-                                    const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const void *saved,
-                                    const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream) {
-    const char *what = "vqcpc_vocoder_ar_bwd";
+int ar_bwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L,
+           const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const float *cond_in, const void *saved,
+           const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream) {
     std::vector<int> slen;
     int longest = 0;
     TRY(check_call(v, what, audio, idx, speaker, B, Tc, L, n_codes, n_audio, w, saved, slen, &longest));
@@ -435,7 +473,7 @@ extern "C" int vqcpc_vocoder_ar_bwd(vqcpc_vocoder *v, const int64_t *audio, cons
     ArView view;
     TRY(view_of(v, w, false, &view, s));
     UttLayout u;
-    TRY(vq_tf_condition(v, idx, speaker, B, Tc, n_codes, slen, &view, u, s));
+    TRY(vq_tf_condition(v, idx, speaker, B, Tc, n_codes, slen, &view, u, s, cond_in));
     const size_t grows = (size_t)u.grows;            // > 0: some utterance scores a step, so it has a code
     if (need_tabs) {
         TRY(k.dGemb.reserve((size_t)n_cls * 3 * Hr * F));
@@ -516,3 +554,5 @@ extern "C" int vqcpc_vocoder_ar_bwd(vqcpc_vocoder *v, const int64_t *audio, cons
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }
+
+}  // namespace

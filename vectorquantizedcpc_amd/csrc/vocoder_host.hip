@@ -71,6 +71,7 @@ static std::vector<const DevBuf *> work_buffers(const vqcpc_vocoder *v) {
                                      &v->nll_len, &v->xd_x, &v->xd_segs};
     for (auto &G : v->grp) b.insert(b.end(), {&G.har, &G.a1, &G.cand_s, &G.cand_k, &G.slot_tab, &G.cur, &G.gcur, &G.candg});
     for (const DevBuf *g : v->gw.all()) b.push_back(g);
+    for (const DevBuf *g : v->cg.all()) b.push_back(g);
     return b;
 }
 
@@ -98,10 +99,12 @@ static int vocoder_create_impl(const vqcpc_vocoder_weights *w, vqcpc_vocoder *v)
         TRY(v->p_bih[l].reserve((size_t)6 * Hp * sizeof(float)));
         TRY(v->p_bhh[l].reserve((size_t)6 * Hp * sizeof(float)));
         TRY(v->p_wf[l].reserve((size_t)2 * (Hp / 4) * (Hp / 16) * 64 * sizeof(float4)));
+        TRY(v->p_whh[l].reserve((size_t)6 * Hp * Hp * sizeof(float)));
         for (int d = 0; d < 2; ++d) {
             HIP_TRY(hipMemcpy(v->p_wih[l] + (size_t)d * 3 * Hp * I, w->prenet_w_ih[l][d], (size_t)3 * Hp * I * sizeof(float), D2D));
             HIP_TRY(hipMemcpy(v->p_bih[l] + (size_t)d * 3 * Hp, w->prenet_b_ih[l][d], (size_t)3 * Hp * sizeof(float), D2D));
             HIP_TRY(hipMemcpy(v->p_bhh[l] + (size_t)d * 3 * Hp, w->prenet_b_hh[l][d], (size_t)3 * Hp * sizeof(float), D2D));
+            HIP_TRY(hipMemcpy(v->p_whh[l] + (size_t)d * 3 * Hp * Hp, w->prenet_w_hh[l][d], (size_t)3 * Hp * Hp * sizeof(float), D2D));
             DevBuf frag;                 // one direction's W_hh in fragment order
             TRY(vq_build_wfrag(w->prenet_w_hh[l][d], Hp, Hp / 4, Hp, 4, 3, Hp, frag));
             HIP_TRY(hipMemcpy((char *)v->p_wf[l].p + d * frag.cap, frag.p, frag.cap, D2D));
@@ -312,28 +315,30 @@ extern "C" int vqcpc_vocoder_last_timing(vqcpc_vocoder *v, float *loop_ms, int *
 // utterance 2 Tc frames.  Ragged: frames_dev[b] valid frames per utterance, row0_dev[b] its first row, n_rows = their sum -- every
 // buffer of the prenet (series, hoisted gate inputs, both layers' outputs) holds the utterances' OWN frames only, utterance b at
 // rows row0[b] ..: on a manifest of 1 - 10 s utterances (mean 3.4 s) two thirds of B x T_max would be padding.
-static int run_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int B, int Tc,
-                         const int *frames_dev, const int *row0_dev, size_t n_rows, float *cond_out, hipStream_t s) {
+// cv: the weights it reads; series_out, out0_out: where the glued series and layer 0's output go, null = the handle's work space.
+static int run_condition(vqcpc_vocoder *v, const CondView &cv, const int64_t *idx, const int64_t *spk, int B, int Tc,
+                         const int *frames_dev, const int *row0_dev, size_t n_rows, float *series_out, float *out0_out, float *cond_out,
+                         hipStream_t s) {
     const auto &d = v->d;
     const int F = d.dz + d.ds, Hp = d.Hp, dl = 2 * Hp, T2 = 2 * Tc, nbt = (B + 15) / 16;
     const size_t rows = row0_dev ? (n_rows ? n_rows : 1) : (size_t)B * T2;
-    TRY(v->series.reserve(rows * F * sizeof(float)));
+    if (!series_out) { TRY(v->series.reserve(rows * F * sizeof(float))); series_out = v->series.as<float>(); }
     TRY(v->gi.reserve(rows * 6 * Hp * sizeof(float)));
-    TRY(v->out0.reserve(rows * dl * sizeof(float)));
+    if (!out0_out) { TRY(v->out0.reserve(rows * dl * sizeof(float))); out0_out = v->out0.as<float>(); }
     const size_t hsz = (size_t)2 * nbt * Hp * 16 * sizeof(float);
     TRY(v->hseq.reserve(2 * hsz));
     const size_t ng = (size_t)B * T2 * F;
-    hipLaunchKernelGGL(glue_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, idx, spk, v->code_emb,
-                       v->spk_emb, v->series.as<float>(), B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status.dev, v->epoch << 8,
+    hipLaunchKernelGGL(glue_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, idx, spk, cv.code_emb,
+                       cv.spk_emb, series_out, B, Tc, d.dz, d.ds, d.n_codes, d.n_speakers, v->status.dev, v->epoch << 8,
                        frames_dev, row0_dev);
     v->status_pending = true;            // an index outside its table is reported through the status word
     for (int l = 0; l < 2; ++l) {
-        const float *xin = l == 0 ? v->series.as<float>() : v->out0.as<float>();
+        const float *xin = l == 0 ? series_out : out0_out;
         const int I = l == 0 ? F : dl;
-        float *xout = l == 0 ? v->out0.as<float>() : cond_out;
-        TRY(vq_gemm_chain(xin, I, v->p_wih[l], v->p_bih[l], v->gi.as<float>(), 6 * Hp, (int)rows, 6 * Hp, I, I, s));
+        float *xout = l == 0 ? out0_out : cond_out;
+        TRY(vq_gemm_chain(xin, I, cv.wih[l], cv.bih[l], v->gi.as<float>(), 6 * Hp, (int)rows, 6 * Hp, I, I, s));
         if (frames_dev && !row0_dev) HIP_TRY(hipMemsetAsync(xout, 0, rows * dl * sizeof(float), s));      // dense rows past an utterance's end
-        TRY(vq_bigru_scan(v->p_wf[l], v->p_bhh[l], v->gi.as<float>(), v->hseq.as<float>(), xout, frames_dev, row0_dev, Hp, B, T2, s));
+        TRY(vq_bigru_scan(cv.wf[l], cv.bhh[l], v->gi.as<float>(), v->hseq.as<float>(), xout, frames_dev, row0_dev, Hp, B, T2, s));
     }
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
@@ -361,7 +366,33 @@ struct NllCall {
     double *nll_sum; int64_t *n_scored, *n_correct;   // DEVICE (B)
     ArView w;                            // the weights the scan and the head read
     float *hsave;                        // DEVICE (B, L - 1, Hr) or null: h_t of every scored step (the gradients' forward)
+    const float *cond_in;                // DEVICE (B, 2Tc, 2Hp) or null: the conditioning series given (run_conditioning)
 };
+
+CondView vq_cond_view(const vqcpc_vocoder *v) {
+    CondView c{};
+    c.code_emb = v->code_emb; c.spk_emb = v->spk_emb;
+    const size_t whh = (size_t)3 * v->d.Hp * v->d.Hp;
+    for (int l = 0; l < 2; ++l) {
+        c.wih[l] = v->p_wih[l]; c.bih[l] = v->p_bih[l]; c.bhh[l] = v->p_bhh[l]; c.wf[l] = v->p_wf[l];
+        c.whh[l][0] = v->p_whh[l]; c.whh[l][1] = v->p_whh[l] + whh;
+    }
+    return c;
+}
+
+// grid (B T2, ceil(C / 256))
+__global__ void cond_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, const int *__restrict__ frames,
+                                 const int *__restrict__ gbase, int T2, int C, int to_dense) {
+    const int c = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x / T2, f = blockIdx.x % T2;
+    if (c >= C) return;
+    const bool own = f < frames[b];
+    const size_t dense = (size_t)blockIdx.x * C + c, ragged = ((size_t)gbase[b] + f) * C + c;
+    if (to_dense) dst[dense] = own ? src[ragged] : 0.f;
+    else if (own) dst[ragged] = src[dense];
+}
+void vq_cond_rows(const float *src, float *dst, const int *frames, const int *gbase, int B, int T2, int C, bool to_dense, hipStream_t s) {
+    hipLaunchKernelGGL(cond_rows_kernel, dim3(B * T2, (C + 255) / 256), dim3(256), 0, s, src, dst, frames, gbase, T2, C, to_dense ? 1 : 0);
+}
 
 ArView vq_vocoder_view(const vqcpc_vocoder *v) {
     return ArView{v->w_cond, v->b_ih, v->Gemb, v->Gemb4, v->bh4, v->Wf_hh12, v->Wf_hh16, v->w_fc1, v->b_fc1, v->w_fc2, v->b_fc2, 0};
@@ -603,16 +634,29 @@ int begin_call(vqcpc_vocoder *v, const CallPlan &cp, int B) {
     return v->stage.begin(stage_bytes(cp, B));
 }
 
-int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, const int64_t *spk, int B, int Tc,
-                     DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s, const float *w_cond, const float *b_ih) {
-    const int Hr = v->d.Hr, dl = 2 * v->d.Hp;
+int vq_upload_layout(vqcpc_vocoder *v, const UttLayout &u, DevBuf &gbase, hipStream_t s) {
     TRY(v->len.reserve(u.lens.size() * sizeof(int)));
     TRY(v->stage.upload(v->len.p, u.lens.data(), u.lens.size() * sizeof(int), s));
     TRY(gbase.reserve(u.gbase.size() * sizeof(int)));
-    TRY(v->stage.upload(gbase.p, u.gbase.data(), u.gbase.size() * sizeof(int), s));
+    return v->stage.upload(gbase.p, u.gbase.data(), u.gbase.size() * sizeof(int), s);
+}
+
+int vq_cond_run(vqcpc_vocoder *v, const UttLayout &u, const CondView &cv, const int64_t *idx, const int64_t *spk, int B, int Tc, DevBuf &gbase,
+                float *series, float *out0, float *cond, hipStream_t s) {
+    TRY(vq_upload_layout(v, u, gbase, s));
+    return run_condition(v, cv, idx, spk, B, Tc, v->len.as<int>(), gbase.as<int>(), (size_t)u.grows, series, out0, cond, s);
+}
+
+int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, const int64_t *spk, int B, int Tc,
+                     DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s, const float *w_cond, const float *b_ih, const float *cond_in) {
+    const int Hr = v->d.Hr, dl = 2 * v->d.Hp;
     const size_t crows = u.grows > 0 ? (size_t)u.grows : 1;
     TRY(cond.reserve(crows * dl * sizeof(float)));
-    TRY(run_condition(v, idx, spk, B, Tc, v->len.as<int>(), gbase.as<int>(), (size_t)u.grows, cond.as<float>(), s));
+    if (cond_in) {
+        TRY(vq_upload_layout(v, u, gbase, s));
+        vq_cond_rows(cond_in, cond.as<float>(), v->len.as<int>(), gbase.as<int>(), B, 2 * Tc, dl, false, s);
+        HIP_TRY(hipGetLastError());
+    } else TRY(vq_cond_run(v, u, vq_cond_view(v), idx, spk, B, Tc, gbase, nullptr, nullptr, cond.as<float>(), s));
     TRY(gcond.reserve(crows * 3 * Hr * sizeof(float)));
     if (u.grows > 0)
         TRY(vq_gemm_chain(cond.as<float>(), dl, w_cond ? w_cond : v->w_cond.as<float>(), b_ih ? b_ih : v->b_ih.as<float>(), gcond.as<float>(),
@@ -656,7 +700,8 @@ static int run_ar(vqcpc_vocoder *v, const int64_t *idx, const int64_t *spk, int 
     CallPlan cp;
     TRY(plan_call(plan_opts(v), B, Tc, n_codes_host, inputs != nullptr, Ts, max_steps, utt_base, utt_ids_host, cp, nc ? nc->slen.data() : nullptr));
     TRY(begin_call(v, cp, B));
-    TRY(run_conditioning(v, cp, idx, spk, B, Tc, v->cond, v->gcond, v->gbase, s, nc ? nc->w.w_cond : nullptr, nc ? nc->w.b_ih : nullptr));
+    TRY(run_conditioning(v, cp, idx, spk, B, Tc, v->cond, v->gcond, v->gbase, s, nc ? nc->w.w_cond : nullptr, nc ? nc->w.b_ih : nullptr,
+                         nc ? nc->cond_in : nullptr));
     if (wav) HIP_TRY(hipMemsetAsync(wav, 0, (size_t)B * Lout * sizeof(float), s));
     if (mulaw) HIP_TRY(hipMemsetAsync(mulaw, 0, (size_t)B * Lout * sizeof(int64_t), s));
     if (v->last_path != 0) v->last_path = 1;      // a call that fails from here on ran no decode loop
@@ -719,8 +764,8 @@ int vq_tf_check(const vqcpc_vocoder *v, int B, int Tc, int L, const int *n_codes
 
 int vq_tf_score(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L, const int *n_codes,
                 const std::vector<int> &slen, int longest, const ArView *w, double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *nll,
-                float *hsave, hipStream_t s) {
-    NllCall nc{audio, L, slen, nll, nll_sum, n_scored, n_correct, w ? *w : vq_vocoder_view(v), hsave};
+                float *hsave, hipStream_t s, const float *cond_in) {
+    NllCall nc{audio, L, slen, nll, nll_sum, n_scored, n_correct, w ? *w : vq_vocoder_view(v), hsave, cond_in};
     HIP_TRY(hipMemsetAsync(nll_sum, 0, (size_t)B * sizeof(double), s));
     HIP_TRY(hipMemsetAsync(n_scored, 0, (size_t)B * sizeof(int64_t), s));
     HIP_TRY(hipMemsetAsync(n_correct, 0, (size_t)B * sizeof(int64_t), s));
@@ -730,11 +775,11 @@ int vq_tf_score(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, cons
 }
 
 int vq_tf_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes, const std::vector<int> &slen,
-                    const ArView *w, UttLayout &u, hipStream_t s) {
+                    const ArView *w, UttLayout &u, hipStream_t s, const float *cond_in) {
     CallPlan cp;                               // no decode loop: the layout alone sizes the staging arena
     TRY(utt_layout(B, Tc, n_codes, v->d.upsample_t, 0, nullptr, cp));
     TRY(begin_call(v, cp, B));
-    TRY(run_conditioning(v, cp, idx, speaker, B, Tc, v->cond, v->gcond, v->gbase, s, w ? w->w_cond : nullptr, w ? w->b_ih : nullptr));
+    TRY(run_conditioning(v, cp, idx, speaker, B, Tc, v->cond, v->gcond, v->gbase, s, w ? w->w_cond : nullptr, w ? w->b_ih : nullptr, cond_in));
     TRY(v->nll_len.reserve((size_t)B * sizeof(int)));
     TRY(v->stage.upload(v->nll_len.p, slen.data(), (size_t)B * sizeof(int), s));
     u = cp;
@@ -800,5 +845,5 @@ extern "C" int vqcpc_vocoder_glue(vqcpc_vocoder *v, const int64_t *idx, const in
 extern "C" int vqcpc_vocoder_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc,
                                        float *cond, void *stream) {
     VQ_REQUIRE(v && idx && speaker && cond && B > 0 && Tc > 0, "vqcpc_vocoder_condition: bad argument");
-    return run_condition(v, idx, speaker, B, Tc, nullptr, nullptr, 0, cond, (hipStream_t)stream);
+    return run_condition(v, vq_cond_view(v), idx, speaker, B, Tc, nullptr, nullptr, 0, nullptr, nullptr, cond, (hipStream_t)stream);
 }

@@ -73,15 +73,37 @@ struct VocGradWork {
     }
 };
 
+// The conditioning path's weights as glue_kernel, the hoisted projections and the bi-GRU scan read them, per layer with both
+// directions stacked: the handle's copies, or the layouts a gradient entry made from a caller's tensors for one call.
+struct CondView {
+    const float *code_emb, *spk_emb;
+    const float *wih[2], *bih[2], *bhh[2];           // (2, 3Hp, I), (2, 3Hp), (2, 3Hp)
+    const float *wf[2];                  // W_hh fragments of both directions (vq_build_wfrag, rowmode 3), null where no scan runs
+    const float *whh[2][2];              // plain (3Hp, Hp) per layer and direction (the backward's products)
+};
+
+// Work space of the conditioning path's gradients (prenet_grad.hip), grow-only, counted by vqcpc_vocoder_workspace_bytes.
+struct CondGradWork {
+    DevBuf wih[2], bih[2], bhh[2], wf[2], frag;      // a caller's weights, re-laid per call (frag: one direction's fragments on their way)
+    DevBuf wft;                          // backward: one layer's W_hh^T fragments, both directions
+    DevBuf hprev, gh, nn, dout, dgi, dgh, carry, dx0, keys;  // backward: one layer's rows, the carry, dseries, the rows' table indices
+    std::vector<const DevBuf *> all() const {
+        return {&wih[0], &wih[1], &bih[0], &bih[1], &bhh[0], &bhh[1], &wf[0], &wf[1], &frag, &wft, &hprev, &gh, &nn, &dout, &dgi,
+                &dgh, &carry, &dx0, &keys};
+    }
+};
+
 struct vqcpc_vocoder {
     ~vqcpc_vocoder();                    // what is not memory: graphs, the arena's pending uploads, streams, events (vocoder_host.hip)
     vqcpc_vocoder_weights d;             // dims only (the weights below are owned copies)
     int device = 0;                      // the device the handle was created on
     DevPtr<float> code_emb, spk_emb;
     DevPtr<float> p_wih[2], p_bih[2], p_bhh[2], p_wf[2];   // per layer, both directions stacked
+    DevPtr<float> p_whh[2];              // plain (2, 3Hp, Hp) copies of the prenet's W_hh (the gradients of the conditioning path)
     DevPtr<float> w_cond, b_ih, Gemb;
     DevPtr<float> ar_emb, w_emb;         // plain copies of the sample embedding and of W_ih[:, :de] (the gradients of the Gemb table)
     VocGradWork gw;
+    CondGradWork cg;
     DevPtr<float4> Gemb4, bh4;
     DevPtr<float> Wf_hh12, Wf_hh16, b_hh, Wf_fc1, Wf_fc1h, b_fc1, Wf_fc2, b_fc2;
     DevPtr<float> w_fc1, w_fc2;          // plain (rows, K) copies for the teacher-forced scan's batched GEMMs
@@ -201,9 +223,25 @@ PlanOpts plan_opts(const vqcpc_vocoder *v);
 // Start of every call that uploads: an earlier call's report, the next epoch, the staging arena sized for this plan.
 int begin_call(vqcpc_vocoder *v, const CallPlan &cp, int B);
 // Upload the layout's frame counts and row bases, run the prenet over every utterance's own frames and make the Gcond rows.
-// w_cond, b_ih: the last product's operands (an ArView's), null = the handle's copies.
+// w_cond, b_ih: the last product's operands (an ArView's), null = the handle's copies.  cond_in (B, 2Tc, 2Hp) or null: the
+// conditioning series given -- its rows of the utterances' own frames are packed into `cond` and the prenet does not run.
 int run_conditioning(vqcpc_vocoder *v, const UttLayout &u, const int64_t *idx, const int64_t *spk, int B, int Tc, DevBuf &cond, DevBuf &gcond, DevBuf &gbase, hipStream_t s,
-                     const float *w_cond = nullptr, const float *b_ih = nullptr);
+                     const float *w_cond = nullptr, const float *b_ih = nullptr, const float *cond_in = nullptr);
+
+// ------------------------------------------------------------------------------------------
+// what the conditioning path's gradient entries (prenet_grad.hip) call in vocoder_host.hip
+// ------------------------------------------------------------------------------------------
+CondView vq_cond_view(const vqcpc_vocoder *v);
+// The layout's frame counts (-> v->len) and row bases (-> gbase) on the device, through the staging arena of the call begun.
+int vq_upload_layout(vqcpc_vocoder *v, const UttLayout &u, DevBuf &gbase, hipStream_t s);
+// run_conditioning's first half: upload the layout's frame counts (v->len) and row bases (gbase), then glue -> layer 0 -> layer 1
+// with the weights of `cv` over the utterances' own frames.  series, out0: where the glued series and layer 0's output go (null =
+// the handle's work space); cond: layer 1's output, rows of the layout.
+int vq_cond_run(vqcpc_vocoder *v, const UttLayout &u, const CondView &cv, const int64_t *idx, const int64_t *spk, int B, int Tc, DevBuf &gbase,
+                float *series, float *out0, float *cond, hipStream_t s);
+// Rows of the utterances' own frames (gbase[b] + f, f < frames[b]) <-> (B, T2, C).  to_dense: dst (B, T2, C), +0 past an utterance's
+// frames; else dst = the ragged rows, and the dense rows past an utterance's frames are not read.
+void vq_cond_rows(const float *src, float *dst, const int *frames, const int *gbase, int B, int T2, int C, bool to_dense, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // what the gradient entries (vocoder_grad.hip) call in vocoder_host.hip
@@ -219,10 +257,17 @@ int vq_tf_check(const vqcpc_vocoder *v, int B, int Tc, int L, const int *n_codes
 // null receives h_t of every scored step.
 int vq_tf_score(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc, int L, const int *n_codes,
                 const std::vector<int> &slen, int longest, const ArView *w, double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *nll,
-                float *hsave, hipStream_t s);
+                float *hsave, hipStream_t s, const float *cond_in = nullptr);
 // Conditioning of a backward call: a call's start (begin_call), then cond (ragged rows), Gcond, the frame counts (v->len) and row
-// bases (v->gbase) on the device, and the scored steps in v->nll_len.
+// bases (v->gbase) on the device, and the scored steps in v->nll_len.  cond_in: run_conditioning's.
 int vq_tf_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes, const std::vector<int> &slen,
-                    const ArView *w, UttLayout &u, hipStream_t s);
+                    const ArView *w, UttLayout &u, hipStream_t s, const float *cond_in = nullptr);
+// vocoder_grad.hip's fixed-order products over rows, which prenet_grad.hip runs on its own rows (the orders: vocoder_grad.hip's header).
+// out (Na, ldo)[:, :Nb] += A^T B for A (R, lda), B (R, ldb); Na % 64 == 0, Nb % 16 == 0.
+void vq_grad_atb(const float *A, int lda, const float *Bm, int ldb, float *out, int ldo, int R, int Na, int Nb, hipStream_t s);
+// out (Na) += column sums of A (R, lda); Na % 64 == 0.
+void vq_grad_colsum(const float *A, int lda, float *out, int R, int Na, hipStream_t s);
+// out (R, N) = A (R, K) W (K rows of ldw); K % 64 == 0, N % 16 == 0.
+void vq_grad_rows_w(const float *A, const float *W, int ldw, float *out, int R, int K, int N, hipStream_t s);
 int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long long seed, float *wav, int64_t *mulaw, hipStream_t s, const Resume *rs = nullptr);
 int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs, int T2, int Ts, unsigned long long seed, float *wav, int64_t *mulaw, float *logits, hipStream_t s, const Resume *rs = nullptr, const NllCall *nc = nullptr);

@@ -551,24 +551,31 @@ def training_cuts(indices, audio, n_codes, keep, upsample: int, clip_codes: Opti
 
 def fit_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speakers: Sequence[int], steps: int = 200, lr: float = 4e-4,
                 optimizer=torch.optim.Adam, max_batch: int = 32, max_pad_frac: float = 0.25, clip_codes: Optional[int] = 16, seed: int = 13,
-                conf=None):
-    """Refit the vocoder's sample-rate network ``vocoder.rnnms.ar`` (embedding, GRU, fc1, fc2) on the units a frozen encoder
-    produces -- the vocoder objective of ``vocoder.py:62-63`` -- after ``adapt_codebook`` or ``fit_encoder`` moved those units, or for
-    new speakers and recording conditions (``score_vocoder`` -> ``fit_vocoder`` -> ``score_vocoder``).  ``code_embedding``,
-    ``speaker_embedding`` and ``rnnms.prenet`` stay frozen (their backward is not built yet).
+                conf=None, train=("ar",)):
+    """Refit the vocoder on the units a frozen encoder produces -- the vocoder objective of ``vocoder.py:62-63`` -- after
+    ``adapt_codebook`` or ``fit_encoder`` moved those units, or for new speakers and recording conditions (``score_vocoder`` ->
+    ``fit_vocoder`` -> ``score_vocoder``).
+
+    ``train``: which parts step, any of ``"ar"`` (the sample-rate network ``vocoder.rnnms.ar``: embedding, GRU, fc1, fc2),
+    ``"prenet"`` (``vocoder.rnnms.prenet``) and ``"embeddings"`` (``code_embedding`` -- the table the moved code indices index --
+    and ``speaker_embedding``), under ONE ``optimizer(params, lr=lr)`` as the reference's trainer has them; the parameters of a part
+    that is not named are left alone and receive no gradient.  The default refits the sample-rate network around a frozen
+    conditioning path.
 
     The utterances, their codes and classes are prepared exactly as ``score_vocoder`` prepares them (the same function), once,
     under ``no_grad``.  ``clip_codes``: every utterance with more codes keeps a seeded cut of that many codes and the
     ``2 * upsampling_t * clip_codes + 1`` samples they cover -- 16 gives the reference's (., 5120) training shape; None: whole
     utterances.  The reference clips the MEL before it encodes; this cuts the CODES after the whole utterance was encoded, so the
     units at the edges of a cut have seen their context.  The buckets are ``score_vocoder``'s (``make_buckets``); step i takes bucket
-    ``i mod n``.  Every step is ``vocoder.nll(..., differentiable=True).loss.backward()`` -- one ``vqcpc_vocoder_ar_fwd`` and one
-    ``vqcpc_vocoder_ar_bwd`` call -- then one step of ``optimizer(vocoder.rnnms.ar.parameters(), lr=lr)`` (torch's, as glue).  The
-    native handle is not rebuilt between steps; it is refreshed once at the end, so that ``generate`` and ``nll`` see the new
-    weights.
+    ``i mod n``.  Every step is ``vocoder.nll(..., differentiable=True, train=train).loss.backward()`` -- one
+    ``vqcpc_vocoder_ar_fwd`` and one ``vqcpc_vocoder_ar_bwd`` call; with a conditioning part named, ``vqcpc_vocoder_cond_fwd``,
+    ``vqcpc_vocoder_ar_fwd_cond``, ``vqcpc_vocoder_ar_bwd_cond`` and ``vqcpc_vocoder_cond_bwd`` -- then one step of
+    ``optimizer(params, lr=lr)`` (torch's, as glue).  The native handle is not rebuilt between steps; it is refreshed once at the
+    end, so that ``generate`` and ``nll`` see the new weights.
 
     Returns ``losses`` (per step, before that step's update), ``steps``, ``batches`` and ``utterances`` (those with at least one
     sample to score)."""
+    train = vocoder._train_parts(train, "fit_vocoder")
     dev = next(encoder.parameters()).device
     up = vocoder.conf.rnnms.upsampling_t
     codes, n_codes, audio, keep = _vocoder_utterances(encoder, vocoder, waves_or_mels, audio, speakers, max_batch, max_pad_frac, conf,
@@ -584,15 +591,15 @@ def fit_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speake
     res = {"losses": [], "steps": 0, "batches": len(batches), "utterances": len(live)}
     if not batches or steps <= 0:
         return res
-    params = list(vocoder.rnnms.ar.parameters())
+    params = [p for part in vocoder.TRAIN_PARTS if part in train for p in vocoder._part_params(part)]
     if not any(p.requires_grad for p in params):
-        raise ValueError("fit_vocoder: no parameter of vocoder.rnnms.ar requires a gradient")
+        raise ValueError("fit_vocoder: no parameter of " + (" / ".join(train) if train != ("ar",) else "vocoder.rnnms.ar") + " requires a gradient")
     opt = optimizer(params, lr=lr)
     for step in range(steps):
         a, z, spk, lengths, ncs = batches[step % len(batches)]
         opt.zero_grad(set_to_none=True)
         with torch.enable_grad():
-            loss = vocoder.nll(a, z, spk, lengths=lengths, n_codes=ncs, differentiable=True).loss
+            loss = vocoder.nll(a, z, spk, lengths=lengths, n_codes=ncs, differentiable=True, train=train).loss
             loss.backward()
         opt.step()
         res["losses"].append(float(loss.detach()))

@@ -136,6 +136,14 @@ class Vocoder(_lib.NativeModule):
                 raise IndexError("index out of range in self")
             raise RuntimeError(f"libvqcpc_hip: {msg} (status {rc})")
 
+    def _check_rc(self, rc: int):
+        """``_lib.check`` for a call that may follow another on the same handle without a synchronisation between them: the later
+        call reports what the earlier one's kernels have already written to the status word, and a bad index is ``check()``'s
+        ``IndexError`` there as well (the word is cleared by the report)."""
+        if rc != 0 and "index out of range in self" in _lib.load().vqcpc_last_error().decode():
+            raise IndexError("index out of range in self")
+        _lib.check(rc)
+
     def last_timing(self):
         """(milliseconds, samples) of the last decode loop, from HIP events on its stream."""
         ms, n = C.c_float(), C.c_int()
@@ -317,12 +325,20 @@ class Vocoder(_lib.NativeModule):
                                    f"(got {w.dtype}, {tuple(w.shape)}, {w.device})")
         return ws
 
-    def _ar_fwd(self, call, weights=None, want_cond: bool = False):
+    def _ar_handle(self, dev, weights, cond_in):
+        """The handle of a gradient call on ``rnnms.ar``.  With the caller's nine tensors and the conditioning series given, nothing
+        is read from the handle's copies: a live handle serves whatever has moved since it was built."""
+        if weights is None:
+            return self._native()
+        return self._sizes_handle(dev, () if cond_in is not None else self._FROZEN_NAMES)
+
+    def _ar_fwd(self, call, weights=None, want_cond: bool = False, cond_in=None):
         """One ``vqcpc_vocoder_ar_fwd`` call -> (nll_sum, n_scored, n_correct, cond or None, saved).  ``call``: ``_nll_call``'s
-        tuple; ``weights``: ``_ar_weights``'s list."""
+        tuple; ``weights``: ``_ar_weights``'s list; ``cond_in`` (B, 2T', dim_voc_latent): the conditioning series given
+        (``vqcpc_vocoder_ar_fwd_cond``: the prenet does not run)."""
         audio, z, speaker, B, Tc, L, na, nc = call
         dev = z.device
-        h = self._sizes_handle(dev, self._FROZEN_NAMES) if weights is not None else self._native()
+        h = self._ar_handle(dev, weights, cond_in)
         lib = _lib.load()
         n = C.c_uint64()
         _lib.check(lib.vqcpc_vocoder_ar_saved_bytes(h, B, L, C.byref(n)))
@@ -331,25 +347,165 @@ class Vocoder(_lib.NativeModule):
         n_correct = torch.empty(B, dtype=torch.int64, device=dev)
         cond = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=dev) if want_cond else None
         saved = torch.empty(int(n.value) // 4, device=dev)
+        head = (h, audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, self._ar_struct(weights))
+        tail = (nll_sum.data_ptr(), n_scored.data_ptr(), n_correct.data_ptr(), cond.data_ptr() if want_cond else None, saved.data_ptr(),
+                _lib.current_stream())
         with _lib.device_guard(dev):
-            _lib.check(lib.vqcpc_vocoder_ar_fwd(h, audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, self._ar_struct(weights),
-                                                nll_sum.data_ptr(), n_scored.data_ptr(), n_correct.data_ptr(),
-                                                cond.data_ptr() if want_cond else None, saved.data_ptr(), _lib.current_stream()))
+            if cond_in is None:
+                _lib.check(lib.vqcpc_vocoder_ar_fwd(*head, *tail))
+            else:
+                self._check_rc(lib.vqcpc_vocoder_ar_fwd_cond(*head, cond_in.data_ptr(), *tail))
         return nll_sum, n_scored, n_correct, cond, saved
 
-    def _ar_bwd(self, call, saved, weights=None, grad_loss=None, want=(True,) * 9, cond_grad: bool = False):
+    def _ar_bwd(self, call, saved, weights=None, grad_loss=None, want=(True,) * 9, cond_grad: bool = False, cond_in=None):
         """One ``vqcpc_vocoder_ar_bwd`` call -> (nine gradients or None in the order of ``AR_KEYS``, grad_cond or None).
-        ``grad_loss``: fp32 device scalar or None = 1."""
+        ``grad_loss``: fp32 device scalar or None = 1; ``cond_in``: that of the forward (``vqcpc_vocoder_ar_bwd_cond``)."""
         audio, z, speaker, B, Tc, L, na, nc = call
         dev = z.device
-        h = self._sizes_handle(dev, self._FROZEN_NAMES) if weights is not None else self._native()
+        h = self._ar_handle(dev, weights, cond_in)
         grads = [torch.empty_like(p, memory_format=torch.contiguous_format) if w else None for p, w in zip(self._ar_params(), want)]
         gc = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=dev) if cond_grad else None
+        head = (h, audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, self._ar_struct(weights))
+        tail = (saved.data_ptr(), None if grad_loss is None else grad_loss.data_ptr(), self._ar_struct(grads),
+                gc.data_ptr() if cond_grad else None, _lib.current_stream())
         with _lib.device_guard(dev):
-            _lib.check(_lib.load().vqcpc_vocoder_ar_bwd(h, audio.data_ptr(), z.data_ptr(), speaker.data_ptr(), B, Tc, L, nc, na, self._ar_struct(weights),
-                                                        saved.data_ptr(), None if grad_loss is None else grad_loss.data_ptr(),
-                                                        self._ar_struct(grads), gc.data_ptr() if cond_grad else None, _lib.current_stream()))
+            if cond_in is None:
+                _lib.check(_lib.load().vqcpc_vocoder_ar_bwd(*head, *tail))
+            else:
+                self._check_rc(_lib.load().vqcpc_vocoder_ar_bwd_cond(*head, cond_in.data_ptr(), *tail))
         return grads, gc
+
+    # ------------------------------------------------------------------ the conditioning path's gradients
+    # vqcpc_vocoder_cond_weights, by state_dict() name: the two tables, then w_ih, w_hh, b_ih, b_hh, each [layer][direction]
+    COND_KEYS = ("code_embedding.weight", "speaker_embedding.weight") + tuple(
+        f"rnnms.prenet.{k}_l{layer}{suf}" for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for layer in range(2)
+        for suf in ("", "_reverse"))
+    AR_NAMES = tuple(n for n in _WEIGHT_NAMES if n.startswith("rnnms.ar."))      # the state_dict() names behind AR_KEYS, in its order
+    TRAIN_PARTS = ("ar", "prenet", "embeddings")
+
+    def _cond_params(self):
+        """The eighteen parameters of the conditioning path in the order of ``COND_KEYS``."""
+        return [self.get_parameter(n) for n in self.COND_KEYS]
+
+    def _part_params(self, part: str):
+        """The parameters of one of ``TRAIN_PARTS``."""
+        if part == "ar":
+            return self._ar_params()
+        cond = self._cond_params()
+        return cond[:2] if part == "embeddings" else cond[2:]
+
+    @classmethod
+    def _train_parts(cls, train, who: str):
+        train = tuple(train)
+        unknown = [t for t in train if t not in cls.TRAIN_PARTS]
+        if unknown or not train or len(set(train)) != len(train):
+            raise ValueError(f"{who}: train must name each of {cls.TRAIN_PARTS} at most once and at least one of them, got {train!r}")
+        return train
+
+    def _cond_struct(self, tensors):
+        """``VocoderCondTensors`` of eighteen tensors in the order of ``COND_KEYS`` (None = NULL member), or None for None."""
+        if tensors is None:
+            return None
+        s = _lib.VocoderCondTensors()
+        p = [None if t is None else t.data_ptr() for t in tensors]
+        s.code_embedding, s.speaker_embedding = p[0], p[1]
+        for i, field in enumerate((s.prenet_w_ih, s.prenet_w_hh, s.prenet_b_ih, s.prenet_b_hh)):
+            for layer in range(2):
+                for d in range(2):
+                    field[layer][d] = p[2 + 4 * i + 2 * layer + d]
+        return s
+
+    def _cond_weights(self, weights, dev):
+        """The eighteen tensors a gradient call reads: None (the handle's copies) or fp32 tensors on ``dev``, made contiguous."""
+        if weights is None:
+            return None
+        ws = [w.detach().contiguous() for w in weights]
+        if len(ws) != len(self.COND_KEYS):
+            raise RuntimeError(f"the conditioning path has {len(self.COND_KEYS)} tensors (Vocoder.COND_KEYS), got {len(ws)}")
+        for k, w, p in zip(self.COND_KEYS, ws, self._cond_params()):
+            if w.dtype != torch.float32 or w.device != dev or w.shape != p.shape:
+                raise RuntimeError(f"{k} must be a float32 tensor of shape {tuple(p.shape)} on {dev} "
+                                   f"(got {w.dtype}, {tuple(w.shape)}, {w.device})")
+        return ws
+
+    def _cond_fwd(self, z, speaker, nc, weights=None):
+        """One ``vqcpc_vocoder_cond_fwd`` call -> (cond (B, 2T', dim_voc_latent), saved).  ``z``, ``speaker``: ``_prep``'s;
+        ``nc``: ``c_int`` array or None; ``weights``: ``_cond_weights``'s list."""
+        B, Tc = z.shape
+        dev = z.device
+        h = self._sizes_handle(dev) if weights is not None else self._native()
+        lib = _lib.load()
+        n = C.c_uint64()
+        _lib.check(lib.vqcpc_vocoder_cond_saved_bytes(h, B, Tc, C.byref(n)))
+        cond = torch.empty(B, 2 * Tc, self.conf.rnnms.dim_voc_latent, device=dev)
+        saved = torch.empty(int(n.value) // 4, device=dev)
+        with _lib.device_guard(dev):
+            self._check_rc(lib.vqcpc_vocoder_cond_fwd(h, z.data_ptr(), speaker.data_ptr(), B, Tc, nc, self._cond_struct(weights), cond.data_ptr(),
+                                                      saved.data_ptr(), _lib.current_stream()))
+        return cond, saved
+
+    def _cond_bwd(self, z, speaker, nc, saved, grad_cond, weights=None, want=(True,) * 18):
+        """One ``vqcpc_vocoder_cond_bwd`` call -> eighteen gradients or None in the order of ``COND_KEYS``."""
+        B, Tc = z.shape
+        dev = z.device
+        h = self._sizes_handle(dev) if weights is not None else self._native()
+        grads = [torch.empty_like(p, memory_format=torch.contiguous_format) if w else None for p, w in zip(self._cond_params(), want)]
+        with _lib.device_guard(dev):
+            self._check_rc(_lib.load().vqcpc_vocoder_cond_bwd(h, z.data_ptr(), speaker.data_ptr(), B, Tc, nc, self._cond_struct(weights),
+                                                              saved.data_ptr(), grad_cond.data_ptr(), self._cond_struct(grads),
+                                                              _lib.current_stream()))
+        return grads
+
+    @torch.no_grad()
+    def cond_gradients(self, z: Tensor, speaker: Tensor, grad_cond: Tensor, *, n_codes=None, want=COND_KEYS, weights=None) -> dict:
+        """The gradients of ``sum(cond * grad_cond)`` -- ``cond`` the conditioning series (B, 2T', dim_voc_latent) of ``z`` and
+        ``speaker``, summed over every utterance's own ``2 * n_codes[b]`` frames -- with respect to the tensors of the conditioning
+        path that ``want`` names (``COND_KEYS``: the two embedding tables and the sixteen tensors of ``rnnms.prenet``, by
+        ``state_dict()`` name): one ``vqcpc_vocoder_cond_fwd`` and one ``vqcpc_vocoder_cond_bwd`` call (``csrc/prenet_grad.hip``).
+        -> dict of device tensors: the wanted names and ``cond``.  ``weights``: eighteen tensors in the order of ``COND_KEYS`` read
+        in place of the native handle's copies (default: the parameters themselves, as they are now).  Synchronises its stream
+        (``check()``): an index outside its table raises ``IndexError``."""
+        unknown = [k for k in want if k not in self.COND_KEYS]
+        if unknown:
+            raise ValueError(f"cond_gradients: unknown tensors {unknown}; known: {self.COND_KEYS}")
+        z, speaker = self._prep(z, speaker)
+        B, Tc = z.shape
+        dev = z.device
+        nc = _lib.int_array(n_codes, B, "n_codes")
+        want_shape = (B, 2 * Tc, self.conf.rnnms.dim_voc_latent)
+        if tuple(grad_cond.shape) != want_shape or grad_cond.dtype != torch.float32 or grad_cond.device != dev:
+            raise RuntimeError(f"grad_cond must be a float32 tensor of shape {want_shape} on {dev} "
+                               f"(got {grad_cond.dtype}, {tuple(grad_cond.shape)}, {grad_cond.device})")
+        ws = self._cond_weights(self._cond_params() if weights is None else weights, dev)
+        cond, saved = self._cond_fwd(z, speaker, nc, ws)
+        grads = self._cond_bwd(z, speaker, nc, saved, grad_cond.detach().contiguous(), ws, tuple(k in want for k in self.COND_KEYS))
+        with _lib.device_guard(dev):
+            self.check()
+        out = {k: g for k, g in zip(self.COND_KEYS, grads) if g is not None}
+        out["cond"] = cond
+        return out
+
+    @torch.no_grad()
+    def vocoder_gradients(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, grad_loss=None) -> dict:
+        """The gradients of ``nll(...).loss`` with respect to all 27 tensors of the vocoder, by ``state_dict()`` name: the direct
+        form of ``nll(..., differentiable=True, train=TRAIN_PARTS).loss.backward()`` -- ``vqcpc_vocoder_cond_fwd``,
+        ``vqcpc_vocoder_ar_fwd_cond``, ``vqcpc_vocoder_ar_bwd_cond`` asking for ``grad_cond``, ``vqcpc_vocoder_cond_bwd`` -- on the
+        parameters as they are now.  -> dict of device tensors: the 27 names, ``loss`` (float64 scalar), ``nll_sum``, ``n_scored``,
+        ``n_correct``.  Synchronises its stream (``check()``)."""
+        call = self._nll_call(audio, z, speaker, lengths, n_codes)
+        _, z, speaker, _, _, _, _, nc = call
+        dev = z.device
+        cw, aw = self._cond_weights(self._cond_params(), dev), self._ar_weights(self._ar_params(), dev)
+        cond, csaved = self._cond_fwd(z, speaker, nc, cw)
+        nll_sum, n_scored, n_correct, _, saved = self._ar_fwd(call, aw, cond_in=cond)
+        gl = None if grad_loss is None else torch.tensor(float(grad_loss), dtype=torch.float32, device=dev)
+        ar_grads, gc = self._ar_bwd(call, saved, aw, gl, cond_grad=True, cond_in=cond)
+        cond_grads = self._cond_bwd(z, speaker, nc, csaved, gc, cw)
+        with _lib.device_guard(dev):
+            self.check()
+        out = dict(zip(self.COND_KEYS + self.AR_NAMES, cond_grads + ar_grads))
+        out.update(loss=nll_sum.sum() / n_scored.sum(), nll_sum=nll_sum, n_scored=n_scored, n_correct=n_correct)
+        return out
 
     @torch.no_grad()
     def ar_gradients(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, want=AR_KEYS, cond_grad: bool = False,
@@ -360,8 +516,8 @@ class Vocoder(_lib.NativeModule):
         the wanted keys, ``cond`` and ``grad_cond`` (B, 2T', dim_voc_latent) with ``cond_grad``, ``loss`` (float64 scalar),
         ``nll_sum``, ``n_scored``, ``n_correct``.  ``weights``: nine tensors in the order of ``AR_KEYS`` read in place of the
         module's parameters' copies in the native handle (default: the parameters themselves, as they are now); ``grad_loss``: the
-        upstream gradient, a number (default 1).  ``code_embedding``, ``speaker_embedding`` and ``rnnms.prenet`` are frozen: they
-        receive no gradient.  Synchronises its stream (``check()``)."""
+        upstream gradient, a number (default 1).  ``code_embedding``, ``speaker_embedding`` and ``rnnms.prenet`` receive no gradient
+        here: ``cond_gradients`` takes ``grad_cond`` on to them, ``vocoder_gradients`` does both.  Synchronises its stream (``check()``)."""
         unknown = [k for k in want if k not in self.AR_KEYS]
         if unknown:
             raise ValueError(f"ar_gradients: unknown tensors {unknown}; known: {self.AR_KEYS}")
@@ -380,7 +536,7 @@ class Vocoder(_lib.NativeModule):
         return out
 
     def nll(self, audio: Tensor, z: Tensor, speaker: Tensor, *, lengths=None, n_codes=None, per_sample: bool = False,
-            differentiable: bool = False) -> "VocoderNLL":
+            differentiable: bool = False, train=("ar",)) -> "VocoderNLL":
         """Teacher-forced negative log-likelihood per utterance: the vocoder's training objective (``vocoder.py:62-63``: the
         energies of ``audio[:, :-1]`` against the targets ``audio[:, 1:]``) as a number for held-out data, without the
         ``(B, T_s, 2**bits)`` energies ever existing (``vqcpc_vocoder_nll``).
@@ -393,14 +549,23 @@ class Vocoder(_lib.NativeModule):
         ``differentiable=True`` (grad mode on, a parameter of ``rnnms.ar`` requiring grad): the returned ``.loss`` carries a
         ``grad_fn``.  Its forward is ``vqcpc_vocoder_ar_fwd`` on the parameters as they are (an optimizer step costs no new
         handle) and keeps ``h_t`` of every scored step; ``loss.backward()`` is one ``vqcpc_vocoder_ar_bwd`` call that asks only
-        for the gradients of those of the nine ``rnnms.ar`` parameters that require one.  ``code_embedding``,
-        ``speaker_embedding`` and ``rnnms.prenet`` are frozen in this path and receive NO gradient.  ``per_sample`` is not
-        available with it."""
-        if differentiable and torch.is_grad_enabled() and any(p.requires_grad for p in self._ar_params()):
+        for the gradients of those of the nine ``rnnms.ar`` parameters that require one.  ``per_sample`` is not available with it.
+
+        ``train``: the parts that receive a gradient, any of ``"ar"`` (``rnnms.ar``), ``"prenet"`` (``rnnms.prenet``) and
+        ``"embeddings"`` (``code_embedding``, ``speaker_embedding``); the parameters of a part that is not named receive NONE.
+        The default leaves the conditioning path frozen, as above.  With a conditioning part named the forward is
+        ``vqcpc_vocoder_cond_fwd`` then ``vqcpc_vocoder_ar_fwd_cond`` on the parameters as they are, and ``backward()`` is one
+        ``vqcpc_vocoder_ar_bwd_cond`` call asking for ``grad_cond`` then one ``vqcpc_vocoder_cond_bwd`` call, each asking only for
+        the tensors of named parts that require a gradient: an optimizer step on any of the 27 tensors costs no new handle."""
+        train = self._train_parts(train, "Vocoder.nll")
+        if differentiable and torch.is_grad_enabled() and any(p.requires_grad for part in train for p in self._part_params(part)):
             if per_sample:
                 raise ValueError("Vocoder.nll: per_sample is not available with differentiable=True")
             call = self._nll_call(audio, z, speaker, lengths, n_codes)
-            loss, nll_sum, n_scored, n_correct = _ArGrad.apply(self, call, *self._ar_params())
+            if train == ("ar",):
+                loss, nll_sum, n_scored, n_correct = _ArGrad.apply(self, call, *self._ar_params())
+            else:
+                loss, nll_sum, n_scored, n_correct = _VocGrad.apply(self, call, train, *self._cond_params(), *self._ar_params())
             with _lib.device_guard(call[1].device):
                 self.check()
             return VocoderNLL(nll_sum, n_scored, n_correct, None, loss)
@@ -485,6 +650,43 @@ class _ArGrad(torch.autograd.Function):
         grads, _ = module._ar_bwd(call, saved, module._ar_weights(ctx.saved_tensors, call[1].device),
                                   grad_loss.to(torch.float32).contiguous(), ctx.needs_input_grad[2:])
         return (None, None) + tuple(grads)
+
+
+class _VocGrad(torch.autograd.Function):
+    """``Vocoder.nll(..., differentiable=True, train=...)`` with a conditioning part named: ``forward`` is ``vqcpc_vocoder_cond_fwd``
+    then ``vqcpc_vocoder_ar_fwd_cond`` and keeps both ``saved`` buffers and the series; ``backward`` is one
+    ``vqcpc_vocoder_ar_bwd_cond`` call asking for ``grad_cond`` and one ``vqcpc_vocoder_cond_bwd`` call, each asking for the
+    gradients ``needs_input_grad`` names among the tensors of the parts in ``train``."""
+
+    @staticmethod
+    def forward(ctx, module, call, train, *ws):
+        _, z, speaker, _, _, _, _, nc = call
+        dev = z.device
+        cw, aw = module._cond_weights(ws[:18], dev), module._ar_weights(ws[18:], dev)
+        cond, csaved = module._cond_fwd(z, speaker, nc, cw)
+        nll_sum, n_scored, n_correct, _, saved = module._ar_fwd(call, aw, cond_in=cond)
+        ctx.module, ctx.kept, ctx.train = module, (call, cond, csaved, saved), train
+        ctx.save_for_backward(*ws)                       # torch refuses the backward if an in-place step has moved them since
+        ctx.mark_non_differentiable(nll_sum, n_scored, n_correct)
+        return nll_sum.sum() / n_scored.sum(), nll_sum, n_scored, n_correct
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, *_):
+        call, cond, csaved, saved = ctx.kept
+        module, train = ctx.module, ctx.train
+        _, z, speaker, _, _, _, _, nc = call
+        dev = z.device
+        need = ctx.needs_input_grad[3:]
+        want_cond = tuple(n and (("embeddings" if i < 2 else "prenet") in train) for i, n in enumerate(need[:18]))
+        want_ar = tuple(n and "ar" in train for n in need[18:])
+        ws = ctx.saved_tensors
+        ar_grads, gc = module._ar_bwd(call, saved, module._ar_weights(ws[18:], dev), grad_loss.to(torch.float32).contiguous(), want_ar,
+                                      cond_grad=any(want_cond), cond_in=cond)
+        cond_grads = [None] * 18
+        if any(want_cond):
+            cond_grads = module._cond_bwd(z, speaker, nc, csaved, gc, module._cond_weights(ws[:18], dev), want_cond)
+        return (None, None, None) + tuple(cond_grads) + tuple(ar_grads)
 
 
 class VocoderStream:
