@@ -65,7 +65,8 @@ int vqcpc_vocoder_cond_saved_bytes(vqcpc_vocoder *voc, int B, int Tc, uint64_t *
  * equal vqcpc_vocoder_condition's (n_codes NULL) and the cond output of vqcpc_vocoder_ar_fwd; with a struct the bits of a handle
  * created from those tensors.  saved (DEVICE, 16-byte aligned, vqcpc_vocoder_cond_saved_bytes) receives what the backward reads
  * again: the glued series and both layers' outputs, over the utterances' own frames.  An index outside its table is clamped for
- * the read and reported by vqcpc_vocoder_check.
+ * the read and reported by vqcpc_vocoder_check.  Of idx[b, :] the forward and the backward read the elements [0, n_codes[b]) and
+ * nothing behind them: an index there, inside its table or not, changes no bit of any output and is not reported.
  * VQCPC_ERR_INVALID before anything is enqueued: a NULL argument (cw excepted), a NULL member of *cw, a pointer that is not
  * 16-byte aligned, B < 1 or Tc < 1, n_codes[b] outside [0, Tc], a handle of another device. */
 int vqcpc_vocoder_cond_fwd(vqcpc_vocoder *voc, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes,

@@ -73,6 +73,10 @@ int vqcpc_vocoder_ar_saved_bytes(vqcpc_vocoder *voc, int B, int L, uint64_t *byt
  * cond (B, 2 Tc, C) DEVICE fp32 or NULL: receives the conditioning rows the scan used (the prenet's output; rows past an
  * utterance's 2 n_codes[b] frames are +0).  saved (DEVICE, 16-byte aligned, vqcpc_vocoder_ar_saved_bytes) receives h_t of every
  * scored step.
+ * Behind the valid data nothing is read, here and in the backward: of audio[b, :] the elements [0, n_audio[b]) where n_audio[b] >= 2
+ * and none otherwise (step t < n_audio[b] - 1 is fed audio[b, t] and scored against audio[b, t + 1]), of idx[b, :] the elements
+ * [0, n_codes[b]).  Whatever lies behind them -- a class or a code index outside its table included -- changes no bit of any output
+ * and is not reported by vqcpc_vocoder_check.
  * VQCPC_ERR_INVALID before anything is enqueued: the NULL and range conditions of vqcpc_vocoder_nll, a NULL saved, a NULL member
  * of *w, a pointer that is not 16-byte aligned, a handle of another device. */
 int vqcpc_vocoder_ar_fwd(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc,

@@ -13,6 +13,14 @@ Chain: the end-to-end loss is ``voc_grad_ref.loss_of`` -- the float64 sample loo
 differentiable conditioning, on three cases of tests/voc_grad_ref.py; all 27 tensors are leaves.
 
 Pins and judge, per tensor: tests/grad_judge.py.
+
+``WIDE_CASES``: ten more cases (tests/test_gpu_cond_grad_wide.py) on the paths the eleven leave out -- Hp = 512, row counts on and two
+past a slab edge, nine batch tiles, a tile without a frame, tables that are no multiple of a tile and widths that are no multiple
+of 16, and the two ends of an 80-frame BPTT chain with one code row per position -- and ``CHAIN_WIDE``, two wide cases of
+tests/voc_grad_ref.py for the chain; pinned in tests/golden/cond_grad_wide_pins.npz.  The two table gradients also have row pins for
+``grad_judge.judge_rows``: ``e_ref`` per row is the larger of two fp32 CPU yardsticks that sum in different orders, ``nn.GRU`` and
+``Conditioning(..., manual=True)``, a Python loop over the frames with ``f64_ref._gru_update`` that is held to ``nn.GRU`` within
+1e-12 in float64 and carries the seeded fault ``("cut", n)``.
 """
 import os
 
@@ -32,11 +40,11 @@ AR_NAMES = tuple("rnnms.ar." + n for n in VR.SD_NAMES)
 ALL27 = KEYS + AR_NAMES
 PINS = os.path.join(grad_judge.GOLD, "cond_grad_pins.npz")
 POSITIONS = "cond_grad/{name}/{tensor}/pins"
-N_CODES, N_SPK = 512, 102
+N_CODES, N_SPK = 512, 102                                           # the tables' rows unless a case says otherwise ("K", "n_spk")
 
 # name -> sizes (dz, ds, C = dim_voc_latent), batch (B, Tc), code counts (None = all), weight set, indices ("random" or one code for
 # every position), speakers (None = seeded), upstream ("dense", or (b, frame): non-zero in that frame of that utterance alone)
-_D = dict(dz=64, ds=64, C=256, n_codes=None, weights="default", idx="random", spk=None, upstream="dense")
+_D = dict(dz=64, ds=64, C=256, n_codes=None, weights="default", idx="random", spk=None, upstream="dense", K=N_CODES, n_spk=N_SPK, z_set=None)
 CASES = {
     "ref_sizes": dict(_D, B=2, Tc=16),
     # distinct code counts, and one utterance with no code at all: the smallest count the scoring entry accepts
@@ -55,11 +63,36 @@ CASES = {
 ALL_CASES = list(CASES)
 CHAIN_CASES = ("ragged", "chunks", "h512")                           # of tests/voc_grad_ref.py
 
+# Past the eleven.  R = 2 sum(n_codes) rows; GRAD_SLAB = 1024 rows; a batch tile is 16 utterances; a table tile is 64 rows by 16
+# columns.  K, n_spk: the tables' rows.  z_set: {(b, t): code} or "tail" -- z[1] = 100 + arange(40), one code row per position, and
+# every other utterance's codes outside 100 .. 139.
+_TAIL = dict(_D, B=3, Tc=40, n_codes=[40, 40, 17], z_set="tail")
+WIDE_CASES = {
+    "hp512": dict(_D, C=1024, B=17, Tc=4, n_codes=[1 + b % 4 for b in range(17)]),          # pre_bwd_step_kernel<24>, two tiles
+    "slab_exact": dict(_D, C=128, B=16, Tc=32),                                             # R = 1024
+    "slab_plus_two": dict(_D, C=128, B=19, Tc=27),                                          # R = 1026: the second slab holds two rows
+    # nine tiles, two live columns in the last; every fifth utterance has no frame, the first of the batch included
+    "b130": dict(_D, C=128, B=130, Tc=4, n_codes=[(3 * b) % 5 for b in range(130)]),
+    "dead_tile": dict(_D, C=128, B=40, Tc=3, n_codes=[0 if 16 <= b < 32 else 3 for b in range(40)]),
+    # F = 32; Nk = 100 and Nk = 1 against tiles of 64 rows; the last code row is named
+    "tables_small": dict(_D, dz=16, ds=16, C=128, K=100, n_spk=1, B=3, Tc=5, z_set={(0, 0): 99}),
+    # the code table's last column tile has 8 live columns; the speaker table starts at column 40
+    "dz40_ds24": dict(_D, dz=40, ds=24, K=1024, n_spk=7, B=3, Tc=5, z_set={(0, 0): 1023}),
+    "tail": dict(_TAIL, upstream=(1, 79)),                           # the forward directions' BPTT chain over 80 frames
+    "head": dict(_TAIL, upstream=(1, 0)),                            # the reverse directions' chain
+    "tail_stressed": dict(_TAIL, upstream=(1, 79), weights="stressed"),
+}
+ALL_WIDE = list(WIDE_CASES)
+CHAIN_WIDE = ("straddle", "slab_plus_two")                           # of tests/voc_grad_ref.py; the second runs Hp = 512 inside the chain
+WIDE_PINS = os.path.join(grad_judge.GOLD, "cond_grad_wide_pins.npz")
+ROW_TENSORS = KEYS[:2]                                               # the two tables: judged per row as well
+
 _cases, _refs, _chain = {}, {}, {}
 
 
 def state_dict(c):
-    sd = synth.vocoder_state_dict(dim_i_embedding=c["dz"], dim_speaker_embedding=c["ds"], dim_voc_latent=c["C"], size_h_rnn=512)
+    sd = synth.vocoder_state_dict(size_i_codebook=c["K"], n_speakers=c["n_spk"], dim_i_embedding=c["dz"], dim_speaker_embedding=c["ds"],
+                                  dim_voc_latent=c["C"], size_h_rnn=512)
     return f64_ref.stressed(sd) if c["weights"] == "stressed" else sd
 
 
@@ -67,12 +100,21 @@ def load(name):
     """A case as a dict: its sizes, ``sd`` (fp32 state dict), ``z`` (B, Tc), ``spk`` (B) int64, ``n_codes`` as a list, ``G``
     (B, 2 Tc, C) fp32 with zero rows past an utterance's frames.  Computed once and shared (treat as read-only)."""
     if name not in _cases:
-        c = dict(CASES[name], name=name)
+        c = dict(CASES[name] if name in CASES else WIDE_CASES[name], name=name)
         B, Tc = c["B"], c["Tc"]
         c["sd"] = state_dict(c)
-        c["z"] = (synth.randint(f"cond_grad/{name}/z", (B, Tc), N_CODES) if c["idx"] == "random"
+        c["z"] = (synth.randint(f"cond_grad/{name}/z", (B, Tc), c["K"]) if c["idx"] == "random"
                   else torch.full((B, Tc), int(c["idx"]), dtype=torch.int64))
-        c["spk"] = synth.randint(f"cond_grad/{name}/s", (B,), N_SPK) if c["spk"] is None else torch.tensor(c["spk"], dtype=torch.int64)
+        if c["z_set"] == "tail":
+            z = c["z"].clone()
+            z[(z >= 100) & (z < 100 + Tc)] += Tc                     # the other utterances name no code of 100 .. 100 + Tc - 1
+            z[1] = 100 + torch.arange(Tc)
+            c["z"] = z
+        elif c["z_set"]:
+            c["z"] = c["z"].clone()
+            for (b, t), k in c["z_set"].items():
+                c["z"][b, t] = k
+        c["spk"] = synth.randint(f"cond_grad/{name}/s", (B,), c["n_spk"]) if c["spk"] is None else torch.tensor(c["spk"], dtype=torch.int64)
         c["n_codes"] = [Tc] * B if c["n_codes"] is None else list(c["n_codes"])
         G = grad_judge.uniform(f"cond_grad/{name}/G", (B, 2 * Tc, c["C"]), 1.0)
         if c["upstream"] != "dense":
@@ -88,10 +130,18 @@ def load(name):
 
 
 class Conditioning(nn.Module):
-    """The conditioning path as torch's own modules, loaded from a vocoder state dict, in ``dtype``."""
+    """The conditioning path as torch's own modules, loaded from a vocoder state dict, in ``dtype``.
 
-    def __init__(self, sd, dtype=torch.float64):
+    ``manual=True``: a second statement of the bi-GRU on the same parameters -- per layer and direction ``gi = x W_ih^T + b_ih`` for
+    all frames, then a Python loop over the frames with ``f64_ref._gru_update(gi[t], W_hh h + b_hh, h)``, the reverse direction
+    from the last frame down.  In float64 it equals ``nn.GRU`` within 1e-12; in fp32 it sums in another order.  ``fault=("cut", n)``
+    (manual only) detaches ``h`` in both layers and both directions at every frame more than ``n`` frames from frame 79: the chain
+    of the back-propagation through time is dropped ``n`` frames from there, the forward keeps its value."""
+
+    def __init__(self, sd, dtype=torch.float64, manual=False, fault=None):
         super().__init__()
+        assert fault is None or (manual and fault[0] == "cut")
+        self.manual, self.fault = manual, fault
         n_codes, dz = sd["code_embedding.weight"].shape
         n_spk, ds = sd["speaker_embedding.weight"].shape
         Hp = sd["rnnms.prenet.weight_hh_l0"].shape[1]
@@ -110,8 +160,28 @@ class Conditioning(nn.Module):
                 continue
             ze = self.code_embedding(z[b, :n]).repeat_interleave(2, dim=0)
             x = torch.cat((ze, self.speaker_embedding(spk[b])[None, :].expand(2 * n, -1)), dim=1)
-            out.append(self.rnnms.prenet(x[None])[0][0])
+            out.append(self._bigru(x) if self.manual else self.rnnms.prenet(x[None])[0][0])
         return out
+
+    def _bigru(self, x):
+        """The two bidirectional layers over one utterance's frames ``x`` (T, I), frame by frame."""
+        g = self.rnnms.prenet
+        T = x.shape[0]
+        for layer in range(2):
+            halves = []
+            for suf in ("", "_reverse"):
+                w_ih, w_hh, b_ih, b_hh = (getattr(g, f"{k}_l{layer}{suf}") for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                gi = x @ w_ih.T + b_ih
+                h = torch.zeros(g.hidden_size, dtype=x.dtype)
+                hs = [None] * T
+                for t in (range(T) if suf == "" else range(T - 1, -1, -1)):
+                    h = f64_ref._gru_update(gi[t], w_hh @ h + b_hh, h)
+                    if self.fault is not None and abs(t - 79) > self.fault[1]:
+                        h = h.detach()
+                    hs[t] = h
+                halves.append(torch.stack(hs))
+            x = torch.cat(halves, dim=1)
+        return x
 
     def grads(self):
         p = dict(self.named_parameters())
@@ -122,15 +192,17 @@ def _np(d):
     return {k: v.detach().numpy().astype(np.float64) for k, v in d.items()}
 
 
-def grads(name, dtype=torch.float64):
-    """The reference in ``dtype`` on the CPU: dict over ``KEYS`` plus ``cond`` (B, 2 Tc, C), numpy float64."""
+def grads(name, dtype=torch.float64, manual=False, fault=None):
+    """The reference in ``dtype`` on the CPU: dict over ``KEYS`` plus ``cond`` (B, 2 Tc, C), numpy float64.  ``manual``, ``fault``:
+    ``Conditioning``'s."""
     c = load(name)
-    m = Conditioning(c["sd"], dtype)
-    cond = m(c["z"], c["spk"], c["n_codes"])
-    G = c["G"].to(dtype)
-    loss = sum((x * G[b, :x.shape[0]]).sum() for b, x in enumerate(cond))
-    if loss.requires_grad:
-        loss.backward()
+    m = Conditioning(c["sd"], dtype, manual, fault)
+    with grad_judge.one_thread():
+        cond = m(c["z"], c["spk"], c["n_codes"])
+        G = c["G"].to(dtype)
+        loss = sum((x * G[b, :x.shape[0]]).sum() for b, x in enumerate(cond))
+        if loss.requires_grad:
+            loss.backward()
     dense = torch.zeros(c["B"], 2 * c["Tc"], c["C"], dtype=dtype)
     for b, x in enumerate(cond):
         dense[b, :x.shape[0]] = x.detach()
@@ -149,8 +221,9 @@ def chain_grads(name, dtype=torch.float64):
     c = VR.load(name)
     m = Conditioning(c["sd"], dtype)
     p = {k: v.clone().requires_grad_(True) for k, v in VR.weights(c, dtype).items()}
-    loss = VR.loss_of(p, m(c["z"], c["spk"], c["n_codes"]), c["audio"], c["slen"], c["up"])
-    (loss * (1.0 if c["grad_loss"] is None else c["grad_loss"])).backward()
+    with grad_judge.one_thread():
+        loss = VR.loss_of(p, m(c["z"], c["spk"], c["n_codes"]), c["audio"], c["slen"], c["up"])
+        (loss * (1.0 if c["grad_loss"] is None else c["grad_loss"])).backward()
     out = m.grads()
     out.update({n: p[k].grad for k, n in zip(VR.KEYS, AR_NAMES)})
     out["loss"] = loss.detach()
@@ -164,11 +237,22 @@ def chain64(name):
 
 
 def pins():
-    return grad_judge.load_pins(PINS)
+    return grad_judge.load_pins(PINS, WIDE_PINS)
 
 
 def judge(name, got, what):
     grad_judge.judge(grads64(name), pins(), name, got, what, KEYS)
+
+
+def judge_rows(name, got, what):
+    """The two table gradients of a wide case per code and per speaker (``grad_judge.judge_rows``)."""
+    return grad_judge.judge_rows(grads64(name), pins(), name, got, what, ROW_TENSORS)
+
+
+def named_rows(c):
+    """(codes, speakers) whose rows of the table gradients are not zero: those the frames with a path to the upstream name."""
+    live = [c["upstream"][0]] if c["upstream"] != "dense" else [b for b, n in enumerate(c["n_codes"]) if n]
+    return (sorted({int(k) for b in live for k in c["z"][b, :c["n_codes"][b]]}), sorted({int(c["spk"][b]) for b in live}))
 
 
 def judge_chain(name, got, what):

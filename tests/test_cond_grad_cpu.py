@@ -1,6 +1,8 @@
 """No GPU: the float64 reference of the conditioning path's gradients (tests/cond_grad_ref.py) -- its forward against
 ``oracle.f64_ref.F64Vocoder.condition``, its pins against a fresh run, the recorded fits -- and what of the fourth header and its
-Python surface needs no device."""
+Python surface needs no device.  Past the eleven cases: the wide and chain-wide cases reproduce their pins, row pins included, and
+hold the arithmetic their table claims; the manual loop over the frames equals ``nn.GRU``; both fp32 yardsticks pass both judges;
+a chain cut far from the upstream passes the per-tensor judge and fails the per-row one."""
 import ctypes
 import os
 import re
@@ -76,6 +78,101 @@ def test_cases_cover_what_they_name():
     assert not g["speaker_embedding.weight"][np.arange(R.N_SPK) != int(c["spk"][1])].any()
     # the stressed set saturates gates of the prenet: some reset or update gate within 1e-3 of 0 or 1
     assert float(cs["stressed"]["sd"]["rnnms.prenet.weight_ih_l0"].abs().max()) > 3.9 * float(cs["b1"]["sd"]["rnnms.prenet.weight_ih_l0"].abs().max())
+
+
+# ------------------------------------------------------------------ past the eleven: WIDE_CASES, CHAIN_WIDE
+CUT = 56               # frames from the upstream at which the seeded fault drops the chain (see test_cut_chain_...)
+
+
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_wide_pins_equal_a_fresh_run(name):
+    grad_judge.check_pins(R.grads64(name), R.pins(), name, R.KEYS + ("cond",), R.POSITIONS)
+    grad_judge.check_row_pins(R.grads64(name), R.pins(), name, R.ROW_TENSORS)
+
+
+@pytest.mark.parametrize("name", R.CHAIN_WIDE)
+def test_wide_chain_pins_equal_a_fresh_run(name):
+    ref = R.chain64(name)
+    grad_judge.check_pins(ref, R.pins(), "chain_" + name, R.ALL27, R.POSITIONS)
+    assert abs(float(ref["loss"]) - float(R.pins()[f"chain_{name}_loss"])) <= 1e-12
+    ar = VR.grads64(name)                                            # fed by the frozen conditioning it is tests/voc_grad_ref.py's loss
+    assert abs(float(ref["loss"]) - float(ar["loss"])) <= 1e-12
+    for k, n in zip(VR.KEYS, R.AR_NAMES):
+        assert np.abs(ref[n] - ar[k]).max() <= 1e-12 * np.abs(ar[k]).max(), k
+
+
+@pytest.mark.parametrize("name", ["ragged", "tail"])
+def test_manual_loop_equals_nn_gru(name):
+    """The second statement of the bi-GRU, a Python loop over the frames, against ``nn.GRU`` in float64: 1e-12 relative."""
+    ref, loop = R.grads64(name), R.grads(name, manual=True)
+    for k in R.KEYS + ("cond",):
+        top = float(np.abs(ref[k]).max())
+        assert float(np.abs(loop[k] - ref[k]).max()) <= 1e-12 * top, (k, float(np.abs(loop[k] - ref[k]).max()), top)
+
+
+def test_wide_cases_cover_what_they_name():
+    cs = {n: R.load(n) for n in R.ALL_WIDE}
+    rows = {n: 2 * sum(c["n_codes"]) for n, c in cs.items()}
+    for n, c in cs.items():
+        assert len(c["n_codes"]) == c["B"] and all(0 <= k <= c["Tc"] for k in c["n_codes"]) and (c["dz"] + c["ds"]) % 32 == 0
+        assert int(c["z"].min()) >= 0 and int(c["z"].max()) < c["K"] and int(c["spk"].max()) < c["n_spk"], n
+    c = cs["hp512"]
+    assert c["C"] // 2 == 512 and c["B"] == 17 and c["n_codes"][:5] == [1, 2, 3, 4, 1]
+    assert rows["slab_exact"] == 1024 and rows["slab_plus_two"] == 1026
+    c = cs["b130"]
+    assert -(-c["B"] // 16) == 9 and c["B"] % 16 == 2 and c["n_codes"][0] == 0 and c["n_codes"].count(0) == 26
+    c = cs["dead_tile"]
+    assert not any(c["n_codes"][16:32]) and all(c["n_codes"][:16]) and all(c["n_codes"][32:]) and c["B"] == 40
+    c = cs["tables_small"]
+    assert (c["dz"], c["ds"], c["K"], c["n_spk"]) == (16, 16, 100, 1) and c["K"] % 64 and int(c["z"][0, 0]) == 99 == c["K"] - 1
+    c = cs["dz40_ds24"]
+    assert (c["dz"], c["ds"], c["K"], c["n_spk"]) == (40, 24, 1024, 7) and c["dz"] % 16 == 8 and int(c["z"][0, 0]) == 1023
+    for n, f in (("tail", 79), ("head", 0), ("tail_stressed", 79)):
+        c = cs[n]
+        assert c["upstream"] == (1, f) and c["z"][1].tolist() == list(range(100, 140)) and c["n_codes"] == [40, 40, 17]
+        assert not ((c["z"][[0, 2]] >= 100) & (c["z"][[0, 2]] < 140)).any()
+        assert c["G"][1, f].any() and not c["G"][0].any() and not c["G"][2].any() and int((c["G"][1] != 0).any(dim=1).sum()) == 1
+    # tail: one code row per position; the rows span the far end of the chain, and the tensor-wide bound hides many of them
+    G, p = R.grads64("tail")["code_embedding.weight"], R.pins()
+    top = np.abs(G).max(axis=1)
+    named = list(range(100, 140))
+    assert R.named_rows(cs["tail"])[0] == named and not G[[k for k in range(512) if k not in named]].any()
+    wide = grad_judge.bound(p, "tail", "code_embedding.weight")
+    below = int((top[named] < wide).sum())
+    print(f"tail d code_embedding: named rows {top[named].max():.3g} .. {top[named].min():.3g}, tensor-wide bound {wide:.3g}, {below} of "
+          f"{len(named)} rows wholly below it")
+    assert top[named].max() >= 1e6 * top[named].min() and below >= 10
+    assert top[100] == top[named].min() and top[139] == top[named].max()         # the row of position 0 is the far end
+    Gh = np.abs(R.grads64("head")["code_embedding.weight"]).max(axis=1)
+    assert Gh[100] == Gh[named].max() and Gh[named].max() >= 1e6 * Gh[named].min()
+
+
+def _fp32(name, **kw):
+    import torch
+    return {k: v.astype(np.float32) for k, v in R.grads(name, torch.float32, **kw).items()}      # on one thread: the generator's order
+
+
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_fp32_yardsticks_pass_both_judges(name):
+    for what, kw in (("fp32 nn.GRU", {}), ("fp32 loop", dict(manual=True))):
+        low = _fp32(name, **kw)
+        R.judge(name, low, what)
+        R.judge_rows(name, low, what)
+
+
+def test_cut_chain_passes_the_tensor_judge_and_fails_the_row_judge():
+    """What the per-row judge adds.  The fp32 loop on ``tail`` with the chain of the back-propagation through time dropped ``CUT`` =
+    56 frames from the upstream (frame 79): the rows of the codes at positions 0 .. 10 come back zero.  Every one of the eighteen
+    tensors passes the per-tensor judge -- worst err / bound 0.255 (speaker_embedding.weight), d code_embedding 0.250 -- because those
+    rows, at most 7.2e-9, lie below its bound of 3.2e-7; the per-row judge fails by 2.2e5 at the row of code 108 (position 8, 62 frames
+    away).  At 48 frames the per-tensor judge still fails (2.6, bias_ih_l0), from 52 on it passes."""
+    bad = _fp32("tail", manual=True, fault=("cut", CUT))
+    R.judge("tail", bad, f"cut {CUT}")
+    with pytest.raises(AssertionError, match="code_embedding.weight"):
+        R.judge_rows("tail", bad, f"cut {CUT}")
+    far = [100 + i for i in range(40) if 79 - (2 * i + 1) > CUT]
+    assert far == list(range(100, 111)) and not bad["code_embedding.weight"][far].any()
+    assert R.grads64("tail")["code_embedding.weight"][far].any(axis=1).all()
 
 
 def test_b_ih_and_b_hh_differ_in_the_n_third_only():

@@ -1,6 +1,7 @@
 """The vocoder gradients without a GPU: the float64 reference of tests/voc_grad_ref.py reproduces its pins and equals torch's own
 modules, the third header is exported, bound and plain C, the cases meet the conditions the GPU tests rely on, and the recorded
-float64 fit is a trend, not noise."""
+float64 fit is a trend, not noise.  Past the twelve cases: the wide cases reproduce their pins, row pins included, hold the
+arithmetic their table claims, their fp32 CPU run passes both judges, and two seeded faults fail them."""
 import ctypes
 import os
 import re
@@ -60,6 +61,96 @@ def test_cases_meet_their_conditions():
     for b, n in enumerate(cs["ragged"]["slen"]):
         assert not gc[b, -(-n // 8):].any()                          # frames no scored step reads
     assert -(-max(cs["long"]["slen"]) // 640) == 3                   # three chunks at the default chunk of 640
+
+
+# ------------------------------------------------------------------ past the twelve: WIDE_CASES
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_wide_reference_reproduces_its_pins(name):
+    grad_judge.check_pins(R.grads64(name), R.pins(), name, R.TENSORS, R.POSITIONS)
+    grad_judge.check_row_pins(R.grads64(name), R.pins(), name, R.ROW_TENSORS)
+
+
+def test_wide_cases_cover_what_they_name():
+    cs = {n: R.load(n) for n in R.ALL_WIDE}
+    for n, c in cs.items():
+        assert len(c["lengths"]) == len(c["n_codes"]) == c["B"] and c["L"] >= max(c["lengths"])
+        for na, nc in zip(c["lengths"], c["n_codes"]):
+            assert 0 <= nc <= c["Tc"] and na - 1 <= 2 * c["up"] * nc, n          # n_audio - 1 <= 2 up n_codes
+        ch = R.chunk_of(c)
+        assert ch % 2 == 0 and ch >= 2 and sum(c["slen"]) > 0
+    # straddle: seven chunks, the last with 12 steps; four of the six chunk edges cut a frame; two tiles; de = 96
+    c = cs["straddle"]
+    ch, up, longest = R.chunk_of(c), c["up"], max(c["slen"])
+    assert (ch, up, longest) == (16, 6, 108) and ch % up and -(-longest // ch) == 7 and longest % ch == 12 and c["B"] == 19 and c["de"] == 96
+    cut = [f for f in range(longest // up) if (f * up) // ch != (f * up + up - 1) // ch]
+    assert cut == [2, 5, 10, 13]                                     # the edges at 16, 32, 64 and 80; 48 and 96 fall between two frames
+    assert sorted(set(c["slen"])) == [108 - 5 * i for i in range(6, -1, -1)]
+    # frame_over_chunks: a frame spans two and a half chunks, and chunks lie wholly inside one frame
+    c = cs["frame_over_chunks"]
+    ch, up = R.chunk_of(c), c["up"]
+    assert up == 2.5 * ch and any(t0 // up == (t0 + ch - 1) // up and t0 % up for t0 in range(0, max(c["slen"]), ch))
+    # edge_ends: on, one past and one short of each chunk edge
+    c = cs["edge_ends"]
+    assert R.chunk_of(c) == 16 and c["slen"] == [16, 17, 15, 32, 33, 31, 48]
+    # the slab edge: M = B CH rows per chunk, GRAD_SLAB = 1024
+    c = cs["slab_exact"]
+    assert c["B"] * R.chunk_of(c) == 1024 and min(c["slen"]) == 2 * R.chunk_of(c) == 128
+    c = cs["slab_plus_two"]
+    ch = R.chunk_of(c)
+    assert c["B"] * ch == 1026 and (c["C"], c["de"]) == (1024, 32) and -(-max(c["slen"]) // ch) == 3
+    for r in (1024, 1025):                                           # rows 1024 and 1025 are live in the first two chunks
+        b, tt = divmod(r, ch)
+        assert b == 18 and [t0 + tt < c["slen"][b] for t0 in (0, ch, 2 * ch)] == [True, True, False]
+    # h1024_tiles: three tiles, the middle one scores nothing, one live column in the last
+    c = cs["h1024_tiles"]
+    assert (c["Hr"], c["C"], c["B"]) == (1024, 512, 33) and 3 * c["Hr"] // 64 == 48
+    assert not any(c["slen"][16:32]) and not any(c["n_codes"][16:32]) and c["lengths"][16:32] == [1] * 16
+    assert c["lengths"][5] == 0 and c["slen"][32] == 48 and sum(1 for s in c["slen"][:16] if s) == 15
+    c = cs["one_step"]
+    assert max(c["slen"]) == 1 and sum(c["slen"]) == 2 and c["slen"] == [1, 0, 0, 1]
+    c = cs["stressed_edges"]
+    assert c["weights"] == "stressed" and -(-max(c["slen"]) // R.chunk_of(c)) - 1 == 7
+    assert sorted({cs[n]["C"] for n in cs}) == [128, 256, 512, 1024]
+    # the float64 reference: frames no scored step reads are zero, one_step's dead utterances receive nothing
+    for n, c in cs.items():
+        gc = R.grads64(n)["grad_cond"]
+        for b, s in enumerate(c["slen"]):
+            assert not gc[b, -(-s // c["up"]):].any() and all(gc[b, f].any() for f in range(-(-s // c["up"]))), (n, b)
+
+
+def _as_fp32(g):
+    return {k: v.astype(np.float32) for k, v in g.items()}
+
+
+def _ratios(name, got):
+    """err / bound of the per-tensor judge, per tensor."""
+    ref, p = R.grads64(name), R.pins()
+    return {k: float(np.abs(got[k].astype(np.float64) - ref[k]).max()) / grad_judge.bound(p, name, k) for k in R.TENSORS}
+
+
+@pytest.mark.parametrize("name", R.ALL_WIDE)
+def test_fp32_yardstick_passes_both_judges(name):
+    import torch
+    low = _as_fp32(R.grads(name, torch.float32))                     # on one thread: the generator's summation order
+    R.judge(name, low, "fp32 CPU")
+    R.judge_rows(name, low, "fp32 CPU")
+
+
+@pytest.mark.parametrize("fault,touched", [("carry", ("embedding", "w_ih", "w_hh", "b_ih", "b_hh", "grad_cond")),
+                                           ("straddle", ("w_ih", "b_ih", "grad_cond"))])
+def test_seeded_faults_fail_both_judges(fault, touched):
+    """The fp32 run of ``straddle`` with a fault seeded by autograd alone: every tensor the fault touches misses the per-tensor bound
+    (by four to five orders of magnitude), the others keep theirs, and the per-row judge fails on ``grad_cond``."""
+    import torch
+    bad = _as_fp32(R.grads("straddle", torch.float32, fault=fault))
+    ratios = _ratios("straddle", bad)
+    print(fault, {k: f"{v:.3g}" for k, v in ratios.items()})
+    for k in R.TENSORS:
+        assert (ratios[k] > 100.0) == (k in touched), (k, ratios[k])
+    with pytest.raises(AssertionError):
+        R.judge("straddle", bad, fault)
+    with pytest.raises(AssertionError, match="grad_cond"):
+        R.judge_rows("straddle", bad, fault)
 
 
 def test_b_ih_and_b_hh_differ_in_the_n_third_only():

@@ -10,6 +10,12 @@ float64 and once in fp32 on the CPU; tests/golden/voc_grad_pins.npz (``tools/gen
 ``nn.GRU`` + ``nn.Linear`` + ``F.cross_entropy`` built from the same state dict.
 
 Pins and judge, per tensor (the nine gradients and ``grad_cond``): tests/grad_judge.py.
+
+``WIDE_CASES``: eight more cases (tests/test_gpu_voc_grad_wide.py) on the paths the twelve leave out -- frames cut by a chunk edge,
+row counts on and two past a slab edge, utterances ending on, one past and one short of each chunk edge, a batch tile that scores
+nothing, a call of one step, saturated gates across chunk edges; pinned in tests/golden/voc_grad_wide_pins.npz, where ``embedding``
+(per class) and ``grad_cond`` (per utterance and frame) also have row pins for ``grad_judge.judge_rows``.  ``loss_of(..., fault=)``
+seeds the two errors those paths invite, by autograd alone; tests/test_voc_grad_cpu.py shows that both judges catch them.
 """
 import os
 
@@ -52,6 +58,43 @@ CASES = {
 ALL_CASES = list(CASES)
 MODULE_CASES = ("ref_sizes", "b17")          # equal lengths: F.cross_entropy's own mean applies
 
+
+def _chunk(ch):
+    return {"steps_per_graph": ch, "tf_chunk_replays": 1}            # CH = their product: even, at least 2
+
+
+# Past the twelve.  CH: the chunk, in steps; M = B CH rows per chunk; GRAD_SLAB = 1024 rows; a batch tile is 16 utterances.
+WIDE_CASES = {
+    # seven chunks of 16 steps, the last with 12; frames of 6 steps: the edges at 16, 32, 64 and 80 cut frames 2, 5, 10 and 13 (48 and
+    # 96 fall between two frames); two batch tiles; de = 96
+    "straddle": dict(_D, up=6, B=19, Tc=9, L=109, lengths=[109 - 5 * (b % 7) for b in range(19)], de=96, C=128, options=_chunk(16)),
+    # a frame of 40 steps spans two and a half chunks; chunks wholly inside one frame
+    "frame_over_chunks": dict(_D, up=40, B=3, Tc=2, L=150, lengths=[150, 97, 41], options=_chunk(16)),
+    # utterances of 16, 17, 15, 32, 33, 31 and 48 steps: on, one past and one short of each chunk edge
+    "edge_ends": dict(_D, B=7, Tc=3, L=49, lengths=[17, 18, 16, 33, 34, 32, 49], n_codes=[1, 2, 1, 2, 3, 2, 3], options=_chunk(16)),
+    # M = 1024: one full slab, a full tile, every row live in both chunks
+    "slab_exact": dict(_D, B=16, Tc=8, L=129, options=_chunk(64)),
+    # M = 1026: rows 1024 and 1025 (utterance 18, steps 52 and 53 of a chunk) are live in the first two chunks; dim_voc_latent 1024
+    "slab_plus_two": dict(_D, B=19, Tc=11, L=163, lengths=[163 - 9 * (b % 5) for b in range(19)], de=32, C=1024, options=_chunk(54)),
+    # three tiles at NS = 48: the middle one scores nothing, the last has one live column; utterance 5 has no sample at all
+    "h1024_tiles": dict(_D, Hr=1024, B=33, Tc=3, L=49, de=32, C=512,
+                        lengths=[0 if b == 5 else 1 if 16 <= b < 32 else 49 for b in range(33)],
+                        n_codes=[0 if 16 <= b < 32 else 3 for b in range(33)]),
+    # longest = 1: the step kernel runs without its product; N = 2
+    "one_step": dict(_D, B=4, Tc=1, L=2, lengths=[2, 1, 0, 2], n_codes=[1, 0, 0, 1]),
+    # saturated gates across seven chunk edges
+    "stressed_edges": dict(_D, Hr=896, B=2, Tc=8, L=129, weights="stressed", options=_chunk(16)),
+}
+ALL_WIDE = list(WIDE_CASES)
+WIDE_PINS = os.path.join(grad_judge.GOLD, "voc_grad_wide_pins.npz")
+ROW_TENSORS = ("embedding", "grad_cond")     # judged per row as well: per class, per (utterance, frame)
+FAULTS = ("carry", "straddle")
+
+
+def chunk_of(c):
+    """The chunk of a case in steps, as the library forms it: ``tf_chunk_replays * steps_per_graph`` (defaults 4 and 160)."""
+    return c["options"].get("tf_chunk_replays", 4) * c["options"].get("steps_per_graph", 160)
+
 _cases, _refs = {}, {}
 
 
@@ -64,7 +107,7 @@ def load(name):
     """A case as a dict: its sizes, ``sd`` (fp32 state dict), ``audio`` (B, L), ``z`` (B, Tc), ``spk`` (B) int64, ``lengths``
     and ``n_codes`` as lists.  Computed once and shared (treat as read-only)."""
     if name not in _cases:
-        c = dict(CASES[name], name=name)
+        c = dict(CASES[name] if name in CASES else WIDE_CASES[name], name=name)
         B, Tc, L = c["B"], c["Tc"], c["L"]
         c["sd"] = state_dict(c)
         c["audio"] = (synth.randint(f"voc_grad/{name}/a", (B, L), 256) if c["audio"] == "random"
@@ -88,9 +131,15 @@ def condition(c, dtype=torch.float64):
     return f64_ref.F64Vocoder(c["sd"], upsample=c["up"], dtype=dtype).condition(c["z"], c["spk"], c["n_codes"])
 
 
-def loss_of(p, cond, audio, slen, up):
+def loss_of(p, cond, audio, slen, up, fault=None, ch=None):
     """The teacher-forced mean NLL from the nine tensors ``p`` (dict over ``KEYS``) and the conditioning rows ``cond`` (list): the
-    sample loop of ``F64Vocoder.logits``, differentiable, in the dtype of ``p``."""
+    sample loop of ``F64Vocoder.logits``, differentiable, in the dtype of ``p``.
+
+    ``fault`` (default None: the statements as they are) seeds an error of the backward over chunks of ``ch`` steps, by autograd alone;
+    the loss keeps its value.  ``"carry"``: ``h`` is detached at every ``t % ch == 0`` -- nothing is carried across a chunk edge.
+    ``"straddle"``: the conditioning term of the steps that lie behind a chunk edge inside their frame is detached -- a frame cut
+    by an edge receives the share of its first chunk only."""
+    assert fault is None or (fault in FAULTS and ch)
     emb, w_ih, w_hh, b_ih, b_hh = (p[k] for k in KEYS[:5])
     de, Hr = emb.shape[1], w_hh.shape[1]
     B, T = audio.shape[0], max(slen)
@@ -102,11 +151,17 @@ def loss_of(p, cond, audio, slen, up):
         t = torch.arange(slen[b])
         fidx[b, :slen[b]] = int(base[b]) + t // up
         assert slen[b] == 0 or int(fidx[b, :slen[b]].max()) < int(base[b + 1]), "history longer than the conditioning covers"
-    gi = emb_tab[audio[:, :T]] + ctab[fidx]                                      # (B, T, 3 Hr)
+    cterm = ctab[fidx]
+    if fault == "straddle":
+        t = torch.arange(T)
+        cterm = torch.where(((t // up) * up < (t // ch) * ch)[None, :, None], cterm.detach(), cterm)
+    gi = emb_tab[audio[:, :T]] + cterm                                           # (B, T, 3 Hr)
     w_hh_t = w_hh.T
     h = torch.zeros(B, Hr, dtype=emb.dtype)
     hs = []
     for t in range(T):
+        if fault == "carry" and t % ch == 0:
+            h = h.detach()
         h = f64_ref._gru_update(gi[:, t], torch.addmm(b_hh, h, w_hh_t), h)
         hs.append(h)
     hs = torch.stack(hs, dim=1)
@@ -117,14 +172,15 @@ def loss_of(p, cond, audio, slen, up):
     return torch.where(mask, nll, torch.zeros_like(nll)).sum() / float(sum(slen))
 
 
-def grads(name, dtype=torch.float64):
+def grads(name, dtype=torch.float64, fault=None):
     """The reference in ``dtype`` on the CPU: dict over ``TENSORS`` plus ``loss``, numpy float64.  ``grad_cond`` is (B, 2 Tc, C) with
-    zero rows past an utterance's frames."""
+    zero rows past an utterance's frames.  ``fault``: ``loss_of``'s, over the case's own chunk."""
     c = load(name)
-    p = {k: v.clone().requires_grad_(True) for k, v in weights(c, dtype).items()}
-    cond = [x.clone().requires_grad_(True) for x in condition(c, dtype)]
-    loss = loss_of(p, cond, c["audio"], c["slen"], c["up"])
-    (loss * (1.0 if c["grad_loss"] is None else c["grad_loss"])).backward()
+    with grad_judge.one_thread():
+        p = {k: v.clone().requires_grad_(True) for k, v in weights(c, dtype).items()}
+        cond = [x.clone().requires_grad_(True) for x in condition(c, dtype)]
+        loss = loss_of(p, cond, c["audio"], c["slen"], c["up"], fault, chunk_of(c) if fault else None)
+        (loss * (1.0 if c["grad_loss"] is None else c["grad_loss"])).backward()
     out = {k: p[k].grad for k in KEYS}
     gc = torch.zeros(c["B"], 2 * c["Tc"], c["C"], dtype=dtype)
     for b, x in enumerate(cond):
@@ -166,8 +222,13 @@ def module_grads(name):
 
 
 def pins():
-    return grad_judge.load_pins(PINS)
+    return grad_judge.load_pins(PINS, WIDE_PINS)
 
 
 def judge(name, got, what):
     grad_judge.judge(grads64(name), pins(), name, got, what, TENSORS)
+
+
+def judge_rows(name, got, what):
+    """``embedding`` per class and ``grad_cond`` per utterance and frame of a wide case (``grad_judge.judge_rows``)."""
+    return grad_judge.judge_rows(grads64(name), pins(), name, got, what, ROW_TENSORS)
