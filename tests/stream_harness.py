@@ -38,9 +38,13 @@ made of several library calls, of which only the first can be held to (d) (a lat
 ``Early(outputs, probe())`` with ``probe()`` taken right after its first call.
 """
 import math
+import os
+import re
 import time
 
 import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 DELAY_FLOOR_MS = 20.0
 HOST_FACTOR = 10.0
@@ -247,3 +251,32 @@ def run(entry, inputs, decoy, *, expect_busy=True, reset=None, label="entry"):
 def hold(entry, inputs, decoy, **kw):
     """``run`` and ``verify``."""
     return run(entry, inputs, decoy, **kw).verify()
+
+
+# ------------------------------------------------------------------- what every file that keeps a header's table does with it
+def check_entries_listed(header, entries, doc):
+    """The entries of ``include/<header>`` that take a ``stream`` are exactly ``entries`` (name -> how), and each has its row in the
+    table of ``doc``, the test file's docstring.  Returns the names found in the header."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    found = set(re.findall(r"\bint\s+(vqcpc_\w+)\s*\([^;{]*?void\s*\*\s*stream\b[^;{]*?\)\s*;", text))
+    assert found == set(entries), (sorted(found - set(entries)), sorted(set(entries) - found))
+    for name, how in entries.items():
+        assert re.search(r"^  %s\s+%s\W" % (name, how), doc, re.M), name
+    return found
+
+
+def release_after(*caches):
+    """The body of a gradient file's module-wide fixture (``yield from`` it): when the file is done, the session-wide delay chain and
+    report are left as they were found, ``caches`` (the dicts of cases and references the file filled) are cleared and the device
+    buffers go back, so that the files that run after it find the process -- its heap, torch's caching allocator and the harness --
+    as they would without it (tests/test_gpu_stream_contract.py then builds and times the delay chain itself, as it always did)."""
+    global _delay
+    found, reported = _delay, len(REPORT)
+    yield
+    import gc
+    _delay = found
+    del REPORT[reported:]
+    for c in caches:
+        c.clear()
+    gc.collect()
+    torch.cuda.empty_cache()

@@ -10,11 +10,9 @@ the entries of the first header.  That file's table is pinned to ``vqcpc.h``; th
   vqcpc_encoder_vq_bwd                N    test_vq_bwd
   ==================================  ===  ====================================================================================
 
-N: does not synchronise (``busy`` is asserted).  ``test_every_stream_entry_is_listed`` reads the header with the regular
-expression of tests/test_gpu_stream_contract.py and fails when an entry with a ``stream`` argument is missing above.
+N: does not synchronise (``busy`` is asserted).  ``test_every_stream_entry_is_listed`` reads the header with
+``stream_harness.check_entries_listed`` and fails when an entry with a ``stream`` argument is missing above.
 """
-import os
-import re
 
 import pytest
 import torch
@@ -30,31 +28,15 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module", autouse=True)
 def release_what_this_file_holds():
     """The cases, the float64 references and the device buffers of this file are released when it is done, and the stream harness's
-    session-wide delay chain and report are left as they were found, so that the files that run after it find the process -- its
-    heap, torch's caching allocator and the harness -- as they would without it (tests/test_gpu_stream_contract.py then builds and
-    times the delay chain itself, as it always did)."""
-    found, reported = H._delay, len(H.REPORT)
-    yield
-    import gc
-    H._delay = found
-    del H.REPORT[reported:]
-    R._cases.clear()
-    R._fwd.clear()
-    R._refs.clear()
-    gc.collect()
-    torch.cuda.empty_cache()
+    session-wide delay chain and report are left as they were found (``stream_harness.release_after`` says why)."""
+    yield from H.release_after(R._cases, R._fwd, R._refs)
 
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"vqcpc_encoder_front_fwd": "N", "vqcpc_encoder_front_bwd": "N", "vqcpc_encoder_vq_bwd": "N"}
 
 
 def test_every_stream_entry_is_listed():
-    text = open(os.path.join(ROOT, "include", "vqcpc_grad.h")).read()
-    found = set(re.findall(r"\bint\s+(vqcpc_\w+)\s*\([^;{]*?void\s*\*\s*stream\b[^;{]*?\)\s*;", text))
-    assert found == set(ENTRIES), (sorted(found - set(ENTRIES)), sorted(set(ENTRIES) - found))
-    for name, how in ENTRIES.items():
-        assert re.search(r"^  %s\s+%s\W" % (name, how), __doc__, re.M), name
+    H.check_entries_listed("vqcpc_grad.h", ENTRIES, __doc__)
 
 
 def encoder():

@@ -101,8 +101,6 @@ Would the file notice?  Five host-side faults (wrong values at worst, never an a
 """
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -119,7 +117,6 @@ from test_gpu_abx import blocks_of, geometry_case
 from vectorquantizedcpc_amd import _lib, abx, loudness, preprocess, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # every entry of include/vqcpc.h with a `stream` argument -> how it is held (the table of the docstring)
 ENTRIES = {
@@ -143,13 +140,7 @@ def ptr(t):
 
 # ---------------------------------------------------------------------------------------------------- the harness itself
 def test_every_stream_entry_is_listed():
-    text = open(os.path.join(ROOT, "include", "vqcpc.h")).read()
-    found = set(re.findall(r"\bint\s+(vqcpc_\w+)\s*\([^;{]*?void\s*\*\s*stream\b[^;{]*?\)\s*;", text))
-    assert len(found) >= 20
-    assert found == set(ENTRIES), (sorted(found - set(ENTRIES)), sorted(set(ENTRIES) - found))
-    doc = __doc__
-    for name, how in ENTRIES.items():
-        assert re.search(r"^  %s\s+%s\W" % (name, how), doc, re.M), name
+    assert len(H.check_entries_listed("vqcpc.h", ENTRIES, __doc__)) >= 20
 
 
 def test_harness_rejects_faulty_entries():

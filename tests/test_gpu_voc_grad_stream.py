@@ -11,12 +11,9 @@ and tests/test_gpu_front_grad_stream.py hold the entries of the first two header
 
 N: does not synchronise (``busy`` is asserted).  A backward behind a forward of the same handle may wait for the staging arena of
 the forward's uploads, so the pair is probed after its first call and the backward is held on its own as well.
-``test_every_stream_entry_is_listed`` reads the header with the regular expression of tests/test_gpu_stream_contract.py and fails
-when an entry with a ``stream`` argument is missing above.
+``test_every_stream_entry_is_listed`` reads the header with ``stream_harness.check_entries_listed`` and fails when an entry with a
+``stream`` argument is missing above.
 """
-import os
-import re
-
 import pytest
 import torch
 
@@ -27,7 +24,6 @@ from vectorquantizedcpc_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"vqcpc_vocoder_ar_fwd": "N", "vqcpc_vocoder_ar_bwd": "N"}
 CASE = "ragged"
 
@@ -35,24 +31,12 @@ CASE = "ragged"
 @pytest.fixture(scope="module", autouse=True)
 def release_what_this_file_holds():
     """The cases, the references and the device buffers of this file are released when it is done, and the stream harness's
-    session-wide delay chain and report are left as they were found (tests/test_gpu_front_grad_stream.py says why)."""
-    found, reported = H._delay, len(H.REPORT)
-    yield
-    import gc
-    H._delay = found
-    del H.REPORT[reported:]
-    R._cases.clear()
-    R._refs.clear()
-    gc.collect()
-    torch.cuda.empty_cache()
+    session-wide delay chain and report are left as they were found (``stream_harness.release_after`` says why)."""
+    yield from H.release_after(R._cases, R._refs)
 
 
 def test_every_stream_entry_is_listed():
-    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_grad.h")).read()
-    found = set(re.findall(r"\bint\s+(vqcpc_\w+)\s*\([^;{]*?void\s*\*\s*stream\b[^;{]*?\)\s*;", text))
-    assert found == set(ENTRIES), (sorted(found - set(ENTRIES)), sorted(set(ENTRIES) - found))
-    for name, how in ENTRIES.items():
-        assert re.search(r"^  %s\s+%s\W" % (name, how), __doc__, re.M), name
+    H.check_entries_listed("vqcpc_vocoder_grad.h", ENTRIES, __doc__)
 
 
 def setup():

@@ -5,7 +5,7 @@
 #   SOURCE  the file to compile in its place (default csrc/UNIT.hip), e.g. a copy with one line changed, to show that a test
 #           file notices the fault; such copies and libraries live under build/ and are never committed
 # then: python tools/ab_libs.py build/exp/A/libvqcpc_hip.so build/exp/B/libvqcpc_hip.so
-# Build the library first (make -C vectorquantizedcpc_amd/csrc): the other units are linked from its objects.
+# Build the library first (make -C vectorquantizedcpc_amd/csrc): the other units are linked from its objects (the Makefile's OBJS).
 set -e
 cd "$(dirname "$0")/.."
 C=vectorquantizedcpc_amd/csrc
@@ -14,7 +14,7 @@ SRC=${4:-$C/$U.hip}
 mkdir -p build/exp/$1
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I$C $2 -c $SRC -o build/exp/$1/$U.o
 OBJS=
-for o in runtime gemm_chain encoder encoder_host codebook vocoder vocoder_host vocoder_plan vocoder_stream nll scan ar_xcd ar_xcm melfront loudness resample cpc cpc_grad context_grad front_grad vocoder_grad abx gate_probe; do
+for o in $(sed -n 's/^OBJS *= *//p' $C/Makefile | sed 's/\.o//g'); do
     if [ $o = $U ]; then OBJS="$OBJS build/exp/$1/$U.o"; else OBJS="$OBJS $C/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/exp/$1/libvqcpc_hip.so $OBJS

@@ -168,6 +168,14 @@ struct SeqSave;                    // seq_step.h
 int vq_lstm_project(LstmScratch &k, const LstmWeights &w, const float *x, int B, int T, hipStream_t s);
 int vq_lstm_steps(LstmScratch &k, const LstmWeights &w, int B, int T, float *out, const SeqSave *save, hipStream_t s);
 
+// ---- fixed-order sums over rows (grad_rows.hip; the orders: grad_slab.h), enqueued on s.  R < 2^31 rows.
+// out (Na, ldo)[:, :Nb] += A^T B for A (R, lda), B (R, ldb); Na % 64 == 0, Nb % 16 == 0.
+void vq_grad_atb(const float *A, int lda, const float *Bm, int ldb, float *out, int ldo, int R, int Na, int Nb, hipStream_t s);
+// out (Na) += column sums of A (R, lda); Na % 64 == 0.
+void vq_grad_colsum(const float *A, int lda, float *out, int R, int Na, hipStream_t s);
+// out (R, N) = A (R, K) W (K rows of ldw); K % 64 == 0, N % 16 == 0.
+void vq_grad_rows_w(const float *A, const float *W, int ldw, float *out, int R, int K, int N, hipStream_t s);
+
 // ---- gradients of the context LSTM (context_grad.hip): a forward that keeps state, and back-propagation through time.
 // The work space of both, grow-only, a member of the encoder handle.
 struct CtxGradWork {

@@ -12,11 +12,8 @@
 //
 // Backward scan: ctx_bwd_step_kernel<NS>, grid (H / 16, ceil(B / 16)), one launch per step t = T-1 .. 0.  Workgroup (rg, bt) owns
 //   hidden units 16 rg .. + 15 of utterances 16 bt .. + 15.
-//   dh_rec[b, u] = sum_k W_hh[k, u] dA[t+1][b, k], k < 4H, on v_mfma_f32_16x16x4_f32 with W_hh^T in fragment order
-//     (build_wfrag_t_kernel): wave w takes k in [w H, (w + 1) H), NS = H / 16 super-steps s of 16 k; inside a super-step MFMA c
-//     (c = 0 .. 3) takes k = 16 (w NS + s) + 4 q + c, q = 0 .. 3 summed in that order inside the instruction; c even goes to
-//     accumulator 0, c odd to accumulator 1, s ascending; the wave's sum is a0 + a1 and the four waves are combined
-//     ((w0 + w1) + w2) + w3.  At t = T-1 there is no MFMA: dh_rec = +0.
+//   dh_rec[b, u] = sum_k W_hh[k, u] dA[t+1][b, k], k < 4H: bptt_step_product of bptt_step.h (the order: there), NS = H / 16, with
+//     W_hh^T in fragment order (build_wfrag_t_kernel).  At t = T-1 there is no MFMA: dh_rec = +0.
 //   then per (b, u), with i f g o, tc = tanh(c_t), cp = c_{t-1} (0 at t = 0), gc = grad_c[b, t, u], carry (0 at t = T-1):
 //     dh  = gc + dh_rec                     do_ = dh * tc
 //     dct = (dh * o) * (1 - tc * tc) + carry
@@ -34,14 +31,14 @@
 //     group rg) adds rows r0 + rg + 4 i, i ascending, into four accumulators (i mod 4) combined (a0 + a1) + (a2 + a3); the four row
 //     groups are combined the same way (slab_column_sum of grad_slab.h); the slab partials go through the finish kernel as a column
 //     of their own.
-//   dz = dA W_ih: ctx_grad_z_kernel, grid (ceil(R / 16), D / 16), one 16 x 16 tile per workgroup, k < 4H over the four waves in
-//     the order of dh_rec (k = 16 (w NS + s) + 4 q + c), combined ((w0 + w1) + w2) + w3.
+//   dz = dA W_ih: vq_grad_rows_w (grad_rows.hip), one 16 x 16 tile per workgroup, k < 4H over the four waves in the order of dh_rec.
 //
 // Padding and dirt: the utterance columns b >= B of the last tile are MASKED -- their lanes load nothing (exact zeros enter the
 // MFMA, an output column depends on its own input column only) and store nothing; rows r >= R likewise.  The scan reads dA[t+1] and
 // the carry only after step t+1 of the same call wrote them for every b < B, and the slab partials of a column tile are read only
 // where this call wrote them: whatever an earlier call left in the work space never reaches a result.  Nothing is zero-filled.
 #include "seq_step.h"
+#include "bptt_step.h"
 #include "grad_slab.h"
 
 namespace {
@@ -69,12 +66,11 @@ struct CtxBwdP {
 
 template <int NS>
 __global__ __launch_bounds__(256) void ctx_bwd_step_kernel(CtxBwdP p, int t) {
-    __shared__ float red[4][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rg = blockIdx.x, bt = blockIdx.y, H = p.H, T = p.T;
     const bool last = t + 1 >= T;
     // the element-wise operands of thread (utterance tid >> 4, unit tid & 15) are requested first: they do not depend on the product
-    const int bl = tid >> 4, ul = tid & 15, bg = bt * 16 + bl, unit = 16 * rg + ul;
+    const int bg = bt * 16 + (tid >> 4), unit = 16 * rg + (tid & 15);
     const bool act = bg < p.B;
     const size_t row = (size_t)bg * T + t;
     float gc = 0.f, ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, tc = 0.f, cp = 0.f, carry = 0.f;
@@ -92,18 +88,8 @@ __global__ __launch_bounds__(256) void ctx_bwd_step_kernel(CtxBwdP p, int t) {
         const bool live = bcol < p.B;                // a masked column loads nothing
         const float4 *dp = (const float4 *)(p.dA + ((size_t)(live ? bcol : 0) * T + t + 1) * (4 * H)) + (size_t)wave * NS * 4 + (lane >> 4);
         const float4 *wp = p.WfT + ((size_t)(rg * 4 + wave) * NS) * 64 + lane;
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int s = 0; s < NS; ++s) {
-            float4 d4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (live) d4 = dp[4 * s];
-            mfma_k4(a0, a1, wp[s * 64], d4);
-        }
-        const f32x4 acc = a0 + a1;                   // row = unit 4 (lane >> 4) + r, column = utterance lane & 15
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[wave][(lane >> 4) * 4 + r][lane & 15] = acc[r];
-        __syncthreads();
-        dh_rec = sum4(red[0][ul][bl], red[1][ul][bl], red[2][ul][bl], red[3][ul][bl]);
+        dh_rec = bptt_step_product<NS, 4>([&](int s) { return wp[s * 64]; },
+                                          [&](int s) { return live ? dp[4 * s] : make_float4(0.f, 0.f, 0.f, 0.f); });
     }
     if (act) {
         const float dh = gc + dh_rec;
@@ -153,27 +139,6 @@ __global__ __launch_bounds__(256) void ctx_grad_w_finish_kernel(const float *par
     float sum = 0.f;
     for (int s = 0; s < S; ++s) sum += part[((size_t)s * M + m) * ld + col];
     *dst = sum;
-}
-
-template <int NS>
-__global__ __launch_bounds__(256) void ctx_grad_z_kernel(const float *dA, const float *w_ih, float *dz, int R, int D, int H) {
-    __shared__ float red[4][16][17];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4;
-    const int r0 = blockIdx.x * 16, c0 = blockIdx.y * 16;
-    const bool live = r0 + i < R;                                      // a masked row loads nothing
-    const float4 *ap = (const float4 *)(dA + (size_t)(live ? r0 + i : 0) * (4 * H)) + (size_t)wave * NS * 4 + kq;
-    const float *wp = w_ih + ((size_t)wave * NS * 16 + 4 * kq) * D + c0 + i;
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int s = 0; s < NS; ++s) {
-        float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (live) av = ap[4 * s];
-        const float *w = wp + (size_t)16 * s * D;
-        mfma_k4(a0, a1, av, make_float4(w[0], w[D], w[2 * (size_t)D], w[3 * (size_t)D]));
-    }
-    const float v = reduce4(red, a0 + a1, wave, lane, tid);            // row r0 + (tid >> 4), column c0 + (tid & 15)
-    const int r = r0 + (tid >> 4);
-    if (r < R) dz[(size_t)r * D + c0 + (tid & 15)] = v;
 }
 
 }  // namespace
@@ -239,12 +204,7 @@ int vq_ctx_bwd(CtxGradWork &k, LstmWeights w, const float *z, int B, int T, cons
         hipLaunchKernelGGL(ctx_grad_w_finish_kernel, dim3((unsigned)((outs + 255) / 256)), blk, 0, s, part, grad_w_ih, grad_w_hh, grad_bias,
                            slabs, D, H);
     }
-    if (grad_z) {
-        const dim3 gz((unsigned)((R + 15) / 16), D / 16);
-        vq_with_sw(H / 64, [&](auto sw) {
-            hipLaunchKernelGGL((ctx_grad_z_kernel<4 * decltype(sw)::value>), gz, blk, 0, s, dA, w.w_ih, grad_z, (int)R, D, H);
-        });
-    }
+    if (grad_z) vq_grad_rows_w(dA, w.w_ih, D, grad_z, (int)R, M, D, s);
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;
 }

@@ -1,5 +1,6 @@
-// Fixed-order sums over slabs of rows: the split-K weight gradients of cpc_grad.hip (dW, db) and context_grad.hip (dW_ih, dW_hh,
-// db) run these statements, each with its own row maps; a finish kernel then adds the slab partials in slab order.
+// Fixed-order sums over rows.  Slabs: the split-K weight gradients of cpc_grad.hip (dW, db) and context_grad.hip (dW_ih, dW_hh, db)
+// run slab_mfma_tile / slab_column_sum, each with its own row maps; a finish kernel then adds the slab partials in slab order.  Whole
+// sums in one workgroup: the kernel bodies behind grad_rows.hip, vocoder_grad.hip and prenet_grad.hip.
 #pragma once
 #include "ar_shared.h"
 
@@ -53,6 +54,70 @@ __device__ __forceinline__ f32x4 slab_mfma_tile(int R, int r0, int ks, FA a, FB 
     f32x4 out[1][1];
     slab_mfma_block<1, 1>(R, r0, ks, [&](int r, int) { return a(r); }, [&](int r, int) { return b(r); }, out);
     return out[0][0];
+}
+
+// ---- The sums over ALL rows below p.R as kernels.  P is a struct of the operands with their row maps: grad_rows.hip has the plain
+// ones (vq_grad_atb, vq_grad_colsum, vq_grad_rows_w), vocoder_grad.hip and prenet_grad.hip instantiate the same bodies with theirs.
+
+// A^T B, one 16 x 16 tile per wave: every slab in slab order from 0 (slab_mfma_tile), the slabs' sums added in that order from +0.
+// grid (column tiles of B, ceil(columns of A / 64)): wave w of workgroup (x, y) owns the output rows 64 y + 16 w .. + 15, columns
+// 16 x .. + 15.  P: R, a(r, m), b(r, c), put(m, c, sum).
+template <class P>
+__global__ __launch_bounds__(256) void grad_atb_kernel(P p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, ks = lane >> 4;
+    const int m0 = blockIdx.y * 64 + wave * 16, c = blockIdx.x * 16 + i;
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < p.R; r0 += GRAD_SLAB)
+        sum = sum + slab_mfma_tile(p.R, r0, ks, [&](int r) { return p.a(r, m0 + i); }, [&](int r) { return p.b(r, c); });
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p.put(m0 + ks * 4 + e, c, sum[e]);     // row 4 ks + e of the tile, column i
+}
+
+// Column sums, out[m] += sum_r a(r, m), 64 columns per workgroup: thread (column, row group g = 0 .. 3) adds rows g + 4 i, i
+// ascending, into four accumulators (i mod 4) combined (a0 + a1) + (a2 + a3); the four row groups are combined the same way.
+// grid (columns / 64).  P: R, a(r, m), out.
+template <class P>
+__global__ __launch_bounds__(256) void grad_colsum_kernel(P p) {
+    __shared__ float red[4][64];
+    const int d = threadIdx.x & 63, rg = threadIdx.x >> 6, m = blockIdx.x * 64 + d;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; rg + 4 * i < p.R; i += 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = rg + 4 * (i + e);
+            a[e] += r < p.R ? p.a(r, m) : 0.f;
+        }
+    }
+    red[rg][d] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    if (rg == 0) p.out[m] = p.out[m] + ((red[0][d] + red[1][d]) + (red[2][d] + red[3][d]));
+}
+
+// out (R, N) = A W for A (rows of K) and W (K rows of ldw, columns [0, N)), one 16 x 16 tile per workgroup; K % 64 == 0, N % 16 == 0.
+// Wave w takes k in [w K / 4, (w + 1) K / 4) in super-steps S of 16; MFMA c (c = 0 .. 3) takes k = 16 S + 4 q + c, q = 0 .. 3 summed
+// in that order inside the instruction; c even goes to accumulator 0, c odd to accumulator 1, S ascending (mfma_k4); the wave's sum
+// is a0 + a1 and the four waves are combined ((w0 + w1) + w2) + w3 (reduce4).  grid (ceil(R / 16), N / 16).
+// P: src(r) = A's row that output row r reads, or -1: the row is masked -- exact zeros enter, nothing is read and nothing stored;
+// value(r, c, v) = what is stored for the product v.
+template <class P>
+__global__ __launch_bounds__(256) void grad_rows_w_kernel(const float *__restrict__ A, const float *__restrict__ W, int ldw,
+                                                          float *__restrict__ out, int R, int K, int N, P p) {
+    __shared__ float red[4][16][17];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4;
+    const int r0 = blockIdx.x * 16, c0 = blockIdx.y * 16, NS = K / 64;
+    const long long src = r0 + i < R ? p.src(r0 + i) : -1;
+    const float4 *ap = (const float4 *)(A + (size_t)(src < 0 ? 0 : src) * K) + (size_t)wave * NS * 4 + kq;
+    const float *wp = W + ((size_t)wave * NS * 16 + 4 * kq) * ldw + c0 + i;
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < NS; ++s) {
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (src >= 0) av = ap[4 * s];
+        const float *w = wp + (size_t)16 * s * ldw;
+        mfma_k4(a0, a1, av, make_float4(w[0], w[ldw], w[2 * (size_t)ldw], w[3 * (size_t)ldw]));
+    }
+    const float v = reduce4(red, a0 + a1, wave, lane, tid);            // row r0 + (tid >> 4), column c0 + (tid & 15)
+    const int r = r0 + (tid >> 4), c = c0 + (tid & 15);
+    if (r < R && p.src(r) >= 0) out[(size_t)r * N + c] = p.value(r, c, v);
 }
 
 // Column sums of the same slab on the vector ALU, 256 threads = (column d = tid & 63, row group rg = tid >> 6): the thread adds

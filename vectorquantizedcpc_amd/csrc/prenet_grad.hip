@@ -26,32 +26,22 @@
 //   3. The serial part, pre_bwd_step_kernel, grid (Hp / 16, 2 directions, ceil(B / 16)), ONE launch per step s = longest - 1 .. 0.
 //      Workgroup (rg, d, bt) owns hidden units 16 rg .. + 15 of direction d of utterances 16 bt .. + 15.  Utterance b is live where
 //      s < len[b], at frame f(s) = s (d = 0) or len[b] - 1 - s (d = 1).
-//        dh_rec[b, u] = sum_k W_hh[d][k, u] dgh[f(s + 1)][b, d, k], k < 3Hp, on v_mfma_f32_16x16x4_f32 with W_hh^T in fragment order
-//          (vq_build_wfrag_t): wave w takes k in [w 3Hp / 4, (w + 1) 3Hp / 4), NS = 3Hp / 64 super-steps of 16 k; inside a super-step
-//          MFMA c (c = 0 .. 3) takes k = 16 (w NS + s') + 4 q + c, q = 0 .. 3 summed in that order inside the instruction; c even goes
-//          to accumulator 0, c odd to accumulator 1, s' ascending; the wave's sum is a0 + a1 and the four waves are combined
-//          ((w0 + w1) + w2) + w3 (context_grad.hip's order).  No MFMA at s = longest - 1.  Where s + 1 >= len[b] -- the utterance's
-//          first step of the backward -- dh_rec and the carry are exactly 0 by that mask, whatever the work space holds.
+//        dh_rec[b, u] = sum_k W_hh[d][k, u] dgh[f(s + 1)][b, d, k], k < 3Hp: bptt_step_product of bptt_step.h (the order: there),
+//          NS = 3Hp / 64, with W_hh^T in fragment order (vq_build_wfrag_t).  No MFMA at s = longest - 1.  Where s + 1 >= len[b] -- the
+//          utterance's first step of the backward -- dh_rec and the carry are exactly 0 by that mask, whatever the work space holds.
 //        dh = (dOut + dh_rec) + carry
-//        dn = dh (1 - z)    dz = dh (h_prev - n)
+//        gru_cell_bwd of bptt_step.h: dn = dh (1 - z)    dz = dh (h_prev - n)
 //        da_n = dn (1 - n n)    da_z = dz (z (1 - z))    da_r = (da_n gh_n) (r (1 - r))
 //        dgi = (da_r, da_z, da_n)    dgh = (da_r, da_z, da_n r)    carry' = dh z
 //      dgi and dgh go to rows (R, 6Hp) = [d][3Hp] of the work space, carry' to (2, B, Hp).
-//   4. The layer's sums over all R rows, per direction d, by vocoder_grad.hip's voc_atb_kernel and voc_colsum_kernel (vq_grad_atb,
-//      vq_grad_colsum): slabs of GRAD_SLAB = 1024 consecutive rows; inside a slab MFMA (s, c) takes rows r0 + 16 s + 4 q + c, q = 0 .. 3
-//      summed inside the instruction, c even to accumulator 0, c odd to accumulator 1, s ascending, the two added at the end
-//      (slab_mfma_tile of grad_slab.h); the slabs are added in slab order from 0, and that sum is added to the zero-filled output.
-//        dW_ih[d] = dgi[d]^T X    dW_hh[d] = dgh[d]^T Hprev[d]
-//      Column sums: thread (column, row group g = 0 .. 3) adds rows g + 4 i, i ascending, into four accumulators (i mod 4) combined
-//      (a0 + a1) + (a2 + a3); the four row groups are combined the same way:  db_ih[d] = sum dgi[d]    db_hh[d] = sum dgh[d].
-//   5. dX = dgi W_ih over BOTH directions in one order (voc_rows_w_kernel through vq_grad_rows_w, K = 6Hp: wave w takes k in
-//      [w 6Hp / 4, (w + 1) 6Hp / 4) in super-steps of 16, MFMA c takes k = 16 S + 4 q + c, c even / odd to two accumulators, the four
-//      waves combined ((w0 + w1) + w2) + w3).  Launched only if something in front of it is wanted: it is layer 0's dOut, and at
-//      layer 0 it is dseries (R, F).
-//   The tables, from dseries: pre_keys_kernel writes every row's (clamped) code index and speaker id; pre_table_kernel, one 16 x 16
-//   tile per wave, grid (ceil(columns / 16), ceil(table rows / 64)): out[k, c] = sum over the rows r with key[r] = k of dseries[r, c],
-//   as onehot(key)^T dseries in the slab order of 4 (slab_mfma_tile), slabs added in slab order from 0 -- K15's dGemb form.  A row
-//   of codes or speakers the batch never names is a sum of (+-0) from +0, i.e. +0.
+//   4. The layer's sums over all R rows, per direction d, by vq_grad_atb and vq_grad_colsum (grad_rows.hip; the orders:
+//      grad_slab.h), each added to the zero-filled output:
+//        dW_ih[d] = dgi[d]^T X    dW_hh[d] = dgh[d]^T Hprev[d]    db_ih[d] = sum dgi[d]    db_hh[d] = sum dgh[d].
+//   5. dX = dgi W_ih over BOTH directions in one order (vq_grad_rows_w, K = 6Hp).  Launched only if something in front of it is
+//      wanted: it is layer 0's dOut, and at layer 0 it is dseries (R, F).
+//   The tables, from dseries: pre_keys_kernel writes every row's (clamped) code index and speaker id; grad_atb_kernel with PreTable's
+//   operands, one 16 x 16 tile per wave: out[k, c] = sum over the rows r with key[r] = k of dseries[r, c], as onehot(key)^T dseries
+//   in the slab order of 4 -- K15's dGemb form.  A row of codes or speakers the batch never names is a sum of (+-0) from +0, i.e. +0.
 //
 // Work space (CondGradWork, beside what the forward uses), floats: R (2Hp + 6Hp + 2Hp + 2Hp + 6Hp + 6Hp + 6Hp + F) + 2 B Hp + one
 //   layer's W_hh^T fragments 6 Hp Hp + 2 R ints, plus for a caller's weights the stacked copies and fragments.
@@ -60,6 +50,7 @@
 // past an utterance's frames likewise; the scan reads dgh and the carry only where step s + 1 of the same call wrote them.  Whatever
 // an earlier call left in the work space never reaches a result.
 #include "vocoder_internal.h"
+#include "bptt_step.h"
 #include "grad_slab.h"
 #include "../../include/vqcpc_vocoder_cond_grad.h"
 
@@ -103,11 +94,10 @@ struct PreStepP {
 
 template <int NS>                        // 3Hp / 64
 __global__ __launch_bounds__(256) void pre_bwd_step_kernel(PreStepP p, int s) {
-    __shared__ float red[4][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rg = blockIdx.x, d = blockIdx.y, bt = blockIdx.z, Hp = p.Hp;
     // the element-wise operands of thread (utterance tid >> 4, unit tid & 15) are requested first: they do not depend on the product
-    const int bl = tid >> 4, ul = tid & 15, bg = bt * 16 + bl, unit = 16 * rg + ul;
+    const int bg = bt * 16 + (tid >> 4), unit = 16 * rg + (tid & 15);
     const int L = bg < p.B ? p.len[bg] : 0;
     const bool act = s < L, rec = s + 1 < L;         // rec: step s + 1 of this utterance ran -- else its BPTT starts here, from 0
     const size_t row = act ? (size_t)p.row0[bg] + (d == 0 ? s : L - 1 - s) : 0;
@@ -128,28 +118,16 @@ __global__ __launch_bounds__(256) void pre_bwd_step_kernel(PreStepP p, int s) {
         const size_t nrow = live ? (size_t)p.row0[bcol] + (d == 0 ? s + 1 : Lc - 2 - s) : 0;
         const float4 *dp = (const float4 *)(p.dgh + nrow * (6 * Hp) + (size_t)d * 3 * Hp) + (size_t)wave * NS * 4 + (lane >> 4);
         const float4 *wp = p.WfT + ((size_t)d * (Hp / 16) * 4 + (size_t)(rg * 4 + wave)) * NS * 64 + lane;
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 3
-        for (int q = 0; q < NS; ++q) {
-            float4 d4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (live) d4 = dp[4 * q];
-            mfma_k4(a0, a1, wp[q * 64], d4);
-        }
-        const f32x4 acc = a0 + a1;                   // row = unit 4 (lane >> 4) + e, column = utterance lane & 15
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[wave][(lane >> 4) * 4 + e][lane & 15] = acc[e];
-        __syncthreads();
-        dh_rec = sum4(red[0][ul][bl], red[1][ul][bl], red[2][ul][bl], red[3][ul][bl]);
+        dh_rec = bptt_step_product<NS, 3>([&](int q) { return wp[q * 64]; },
+                                          [&](int q) { return live ? dp[4 * q] : make_float4(0.f, 0.f, 0.f, 0.f); });
     }
     if (act) {
         if (!rec) dh_rec = 0.f;
-        const float dh = (dout + dh_rec) + carry;
-        const float dn = dh * (1.0f - z), dz = dh * (hp - n);
-        const float gn = dn * (1.0f - n * n), gz = dz * (z * (1.0f - z)), gr = (gn * hn) * (r * (1.0f - r));
+        const GruCellGrad c = gru_cell_bwd(r, z, hn, n, hp, (dout + dh_rec) + carry);
         const size_t o = row * (6 * Hp) + (size_t)d * 3 * Hp + unit;
-        p.dgi[o] = gr; p.dgi[o + Hp] = gz; p.dgi[o + 2 * Hp] = gn;
-        p.dgh[o] = gr; p.dgh[o + Hp] = gz; p.dgh[o + 2 * Hp] = gn * r;
-        p.carry[((size_t)d * p.B + bg) * Hp + unit] = dh * z;
+        p.dgi[o] = c.gr; p.dgi[o + Hp] = c.gz; p.dgi[o + 2 * Hp] = c.gn;
+        p.dgh[o] = c.gr; p.dgh[o + Hp] = c.gz; p.dgh[o + 2 * Hp] = c.gn_r;
+        p.carry[((size_t)d * p.B + bg) * Hp + unit] = c.carry;
     }
 }
 
@@ -166,22 +144,15 @@ __global__ void pre_keys_kernel(const int64_t *__restrict__ idx, const int64_t *
     keys[R + row] = (int)sp;
 }
 
-// out (Nk, ncol): out[k, c] = sum over the rows with key[r] == k of D[r, c0 + c].  grid (ceil(ncol / 16), ceil(Nk / 64)): wave w of
-// workgroup (x, y) owns table rows 64 y + 16 w .. + 15, columns 16 x .. + 15.
-__global__ __launch_bounds__(256) void pre_table_kernel(const int *__restrict__ key, const float *__restrict__ D, int ld, int c0, int ncol,
-                                                        float *__restrict__ out, int Nk, int R) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, ks = lane >> 4;
-    const int m = blockIdx.y * 64 + wave * 16 + i, c = blockIdx.x * 16 + i;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int r0 = 0; r0 < R; r0 += GRAD_SLAB)
-        sum = sum + slab_mfma_tile(R, r0, ks, [&](int r) { return key[r] == m ? 1.f : 0.f; },
-                                   [&](int r) { return c < ncol ? D[(size_t)r * ld + c0 + c] : 0.f; });
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {                    // row = 64 y + 16 w + 4 ks + e of the table, column = 16 x + i
-        const int k = blockIdx.y * 64 + wave * 16 + ks * 4 + e;
-        if (k < Nk && c < ncol) out[(size_t)k * ncol + c] = sum[e];
-    }
-}
+// out (Nk, ncol): out[k, c] = sum over the rows with key[r] == k of D[r, c0 + c], as onehot(key)^T D by grad_atb_kernel (grad_slab.h),
+// grid (ceil(ncol / 16), ceil(Nk / 64)).
+struct PreTable {
+    const int *key; const float *D; int ld, c0, ncol;
+    float *out; int Nk, R;
+    __device__ float a(int r, int m) const { return key[r] == m ? 1.f : 0.f; }
+    __device__ float b(int r, int c) const { return c < ncol ? D[(size_t)r * ld + c0 + c] : 0.f; }
+    __device__ void put(int k, int c, float v) const { if (k < Nk && c < ncol) out[(size_t)k * ncol + c] = v; }
+};
 
 const float *const *members(const vqcpc_vocoder_cond_weights *w) { return &w->code_embedding; }     // eighteen pointers in a row
 float *const *members(const vqcpc_vocoder_cond_grads *g) { return &g->code_embedding; }
@@ -373,11 +344,11 @@ extern "C" int vqcpc_vocoder_cond_bwd(vqcpc_vocoder *v, const int64_t *idx, cons
         const float *dx0 = k.dx0.as<float>();
         hipLaunchKernelGGL(pre_keys_kernel, dim3(B * T2), dim3(64), 0, s, idx, speaker, keys, len, row0, T2, Tc, d.n_codes, d.n_speakers, R);
         if (g.code_embedding)
-            hipLaunchKernelGGL(pre_table_kernel, dim3((dz + 15) / 16, (d.n_codes + 63) / 64), dim3(256), 0, s, keys, dx0, F, 0, dz, g.code_embedding,
-                               d.n_codes, (int)R);
+            hipLaunchKernelGGL(grad_atb_kernel<PreTable>, dim3((dz + 15) / 16, (d.n_codes + 63) / 64), dim3(256), 0, s,
+                               PreTable{keys, dx0, F, 0, dz, g.code_embedding, d.n_codes, (int)R});
         if (g.speaker_embedding)
-            hipLaunchKernelGGL(pre_table_kernel, dim3((ds + 15) / 16, (d.n_speakers + 63) / 64), dim3(256), 0, s, keys + R, dx0, F, dz, ds,
-                               g.speaker_embedding, d.n_speakers, (int)R);
+            hipLaunchKernelGGL(grad_atb_kernel<PreTable>, dim3((ds + 15) / 16, (d.n_speakers + 63) / 64), dim3(256), 0, s,
+                               PreTable{keys + R, dx0, F, dz, ds, g.speaker_embedding, d.n_speakers, (int)R});
     }
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;

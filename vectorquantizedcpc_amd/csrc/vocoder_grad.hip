@@ -25,32 +25,27 @@
 //      r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n) (libm expf / tanhf).
 //   3. Head: a = relu(H W1^T + b1), e = a W2^T + b2 (vq_gemm_chain); voc_softmax_kernel, one wave per row: m = max e (butterfly over
 //      the lanes), q_k = expf(e_k - m), S = sum q (four per lane in k order, then the butterfly xor 32, 16, .., 1),
-//      dlogit_k = (q_k / S - [k == target]) * s.  da = (dlogit W2) * [a > 0], dh_head = da W1: voc_rows_w_kernel, one 16 x 16 tile per
-//      workgroup, k over the four waves: wave w takes k in [w K / 4, (w + 1) K / 4) in super-steps S of 16; MFMA c (c = 0 .. 3) takes
-//      k = 16 S + 4 q + c, q = 0 .. 3 summed in that order inside the instruction; c even goes to accumulator 0, c odd to
-//      accumulator 1, S ascending; the wave's sum is a0 + a1 and the four waves are combined ((w0 + w1) + w2) + w3.
+//      dlogit_k = (q_k / S - [k == target]) * s.  da = (dlogit W2) * [a > 0], dh_head = da W1: grad_rows_w_kernel of grad_slab.h (the
+//      order: there), one 16 x 16 tile per workgroup, k over the four waves.
 //   4. The serial part, voc_bwd_step_kernel, grid (Hr / 16, ceil(B / 16)), ONE launch per step, t descending.  Workgroup (rg, bt)
 //      owns hidden units 16 rg .. + 15 of utterances 16 bt .. + 15:
-//        dh_rec[b, u] = sum_k W_hh[k, u] dgh[t + 1][b, k], k < 3Hr, on v_mfma_f32_16x16x4_f32 in the order of 3 (K = 3Hr);
-//          +0 without an MFMA at the last step of the call, and a column whose utterance has no step t + 1 enters as zeros.
+//        dh_rec[b, u] = sum_k W_hh[k, u] dgh[t + 1][b, k], k < 3Hr: bptt_step_product of bptt_step.h (the order: there), NS = 3Hr / 64,
+//          W_hh read in place; +0 without an MFMA at the last step of the call, and a column whose utterance has no step t + 1
+//          enters as zeros.
 //        dh = (dh_head + dh_rec) + carry        (carry = z_{t+1} dh_{t+1}; 0 at the utterance's last scored step)
-//        dn = dh (1 - z)    dz = dh (h_{t-1} - n)
+//        gru_cell_bwd of bptt_step.h: dn = dh (1 - z)    dz = dh (h_{t-1} - n)
 //        dgi_n = dn (1 - n n)    dgi_z = dz (z (1 - z))    dgi_r = (dgi_n gh_n) (r (1 - r))
 //        dgh = (dgi_r, dgi_z, dgi_n r)          carry' = dh z
 //      dgi (3Hr) and the n third of dgh (Hr) are stored for the chunk, with one more row per utterance that keeps step t0 + CH of
 //      the chunk done before.
-//   5. Weight sums of the chunk, voc_atb_kernel (A^T B over the chunk's rows, one 16 x 16 tile per wave, grid (Nb / 16, Na / 64)):
-//      slabs of GRAD_SLAB = 1024 consecutive rows; inside a slab MFMA (s, c) takes rows r0 + 16 s + 4 q + c, q = 0 .. 3 summed inside
-//      the instruction, c even to accumulator 0, c odd to accumulator 1, s ascending, the two added at the end (slab_mfma_tile of
-//      grad_slab.h); the slabs are added in slab order from 0, and that sum is added to the total.
+//   5. Weight sums of the chunk, grad_atb_kernel of grad_slab.h (A^T B over the chunk's rows in slabs of GRAD_SLAB rows, the slabs
+//      added in slab order from 0; the order: there), and that sum is added to the total.
 //        dW2 += dlogit^T a     dW1 += da^T H     dW_hh += dgh^T Hp     dGemb += onehot(x)^T dgi (the one-hot rows made on the fly)
-//      Column sums, voc_colsum_kernel (64 columns per workgroup): thread (column, row group g = 0 .. 3) adds rows g + 4 i, i ascending,
-//      into four accumulators (i mod 4) combined (a0 + a1) + (a2 + a3); the four row groups are combined the same way; added to the
-//      total:  db2 += sum dlogit    db1 += sum da    db_hh += sum dgh.
+//      Column sums, grad_colsum_kernel of grad_slab.h, added to the total:  db2 += sum dlogit    db1 += sum da    db_hh += sum dgh.
 //      Frame sums, voc_frame_sum_kernel: dGc[frame] += (sum of dgi over the frame's live steps inside the chunk, t ascending from 0).
 //   After the last chunk, from the two tables (the same two kernels, rows = classes or frames):
 //      dW_ih[:, :de] = dGemb^T emb    dW_ih[:, de:] = dGc^T cond    db_ih = column sums of dGc
-//      d emb = dGemb W_ih[:, :de]     grad_cond = dGc W_ih[:, de:]   (voc_rows_w_kernel, K = 3Hr)
+//      d emb = dGemb W_ih[:, :de]     grad_cond = dGc W_ih[:, de:]   (grad_rows_w_kernel, K = 3Hr)
 //   Classes never fed and frames no scored step reads keep their zero rows: their products are sums of (+-0) from +0, i.e. +0.
 //
 // Work space (VocGradWork, beside what the forward scan uses), floats, M = B CH:
@@ -60,6 +55,7 @@
 // are not live likewise; the scan reads dgh[t + 1] and the carry only where step t + 1 of the same call wrote them.  Whatever an
 // earlier call left in the work space never reaches a result.
 #include "vocoder_internal.h"
+#include "bptt_step.h"
 #include "grad_slab.h"
 #include "../../include/vqcpc_vocoder_cond_grad.h"
 
@@ -134,36 +130,19 @@ __global__ __launch_bounds__(256) void voc_softmax_kernel(float *__restrict__ e,
     *row = p;
 }
 
-// out (R, N) = A (R, K) W (K rows of ldw, columns [0, N)), one 16 x 16 tile per workgroup; K % 64 == 0, N % 16 == 0.
-// mask (R, N) or null: out = mask > 0 ? product : 0.  frames / gbase: out row (b, f) of (B, T2) reads A's row gbase[b] + f where
-// f < frames[b] and is left alone elsewhere (the caller zero-filled it).  grid (ceil(R / 16), N / 16)
-__global__ __launch_bounds__(256) void voc_rows_w_kernel(const float *__restrict__ A, const float *__restrict__ W, int ldw, float *__restrict__ out,
-                                                         const float *__restrict__ mask, int R, int K, int N, const int *__restrict__ frames,
-                                                         const int *__restrict__ gbase, int T2) {
-    __shared__ float red[4][16][17];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4;
-    const int r0 = blockIdx.x * 16, c0 = blockIdx.y * 16, NS = K / 64;
-    long long src = -1;                                                // A's row of this lane's output row, -1: masked
-    if (r0 + i < R) {
-        src = r0 + i;
-        if (frames) { const int b = (r0 + i) / T2, f = (r0 + i) % T2; src = f < frames[b] ? (long long)gbase[b] + f : -1; }
+// The row maps of grad_rows_w_kernel (grad_slab.h) that are not plain.  mask (R, N) or null: out = mask > 0 ? product : 0.  frames /
+// gbase or null: out row (b, f) of (B, T2) reads A's row gbase[b] + f where f < frames[b] and is left alone elsewhere (the caller
+// zero-filled it).
+struct VocRowMap {
+    const float *mask; int N;
+    const int *frames, *gbase; int T2;
+    __device__ long long src(int r) const {
+        if (!frames) return r;
+        const int b = r / T2, f = r % T2;
+        return f < frames[b] ? (long long)gbase[b] + f : -1;
     }
-    const float4 *ap = (const float4 *)(A + (size_t)(src < 0 ? 0 : src) * K) + (size_t)wave * NS * 4 + kq;
-    const float *wp = W + ((size_t)wave * NS * 16 + 4 * kq) * ldw + c0 + i;
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < NS; ++s) {
-        float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (src >= 0) av = ap[4 * s];
-        const float *w = wp + (size_t)16 * s * ldw;
-        mfma_k4(a0, a1, av, make_float4(w[0], w[ldw], w[2 * (size_t)ldw], w[3 * (size_t)ldw]));
-    }
-    float v = reduce4(red, a0 + a1, wave, lane, tid);                  // row r0 + (tid >> 4), column c0 + (tid & 15)
-    const int r = r0 + (tid >> 4), c = c0 + (tid & 15);
-    if (r >= R) return;
-    if (frames && r % T2 >= frames[r / T2]) return;
-    if (mask && !(mask[(size_t)r * N + c] > 0.f)) v = 0.f;
-    out[(size_t)r * N + c] = v;
-}
+    __device__ float value(int r, int c, float v) const { return mask && !(mask[(size_t)r * N + c] > 0.f) ? 0.f : v; }
+};
 
 struct VocStepP {
     const float *w_hh;                   // (3Hr, Hr)
@@ -176,10 +155,9 @@ struct VocStepP {
 
 template <int NS>                        // 3Hr / 64
 __global__ __launch_bounds__(256) void voc_bwd_step_kernel(VocStepP p, int t) {
-    __shared__ float red[4][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rg = blockIdx.x, bt = blockIdx.y, Hr = p.q.Hr, CH = p.q.CH, tt = t - p.q.t0;
-    const int bl = tid >> 4, ul = tid & 15, bg = bt * 16 + bl, unit = 16 * rg + ul;
+    const int bg = bt * 16 + (tid >> 4), unit = 16 * rg + (tid & 15);
     const bool act = bg < p.q.B && t < p.q.slen[bg];
     const size_t row = (size_t)bg * CH + tt, drow = (size_t)bg * (CH + 1) + tt;
     float r = 0.f, z = 0.f, hn = 0.f, n = 0.f, hp = 0.f, dhh = 0.f, carry = 0.f;
@@ -197,30 +175,24 @@ __global__ __launch_bounds__(256) void voc_bwd_step_kernel(VocStepP p, int t) {
         const bool live = bcol < p.q.B && t + 1 < p.q.slen[bcol];         // a masked column loads nothing
         const size_t nrow = (size_t)(live ? bcol : 0) * (CH + 1) + tt + 1;
         const int kq = lane >> 4;
-        const float *wp = p.w_hh + ((size_t)wave * NS * 16 + 4 * kq) * Hr + unit - ul + (lane & 15);
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int s = 0; s < NS; ++s) {
-            const int k = 16 * (wave * NS + s) + 4 * kq;                  // 2Hr is a multiple of 16: four k never straddle the two buffers
-            float4 d4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (live) d4 = k < 2 * Hr ? *(const float4 *)(p.dgi + nrow * (3 * Hr) + k) : *(const float4 *)(p.dghn + nrow * Hr + (k - 2 * Hr));
-            const float *w = wp + (size_t)16 * s * Hr;
-            mfma_k4(a0, a1, make_float4(w[0], w[Hr], w[2 * (size_t)Hr], w[3 * (size_t)Hr]), d4);
-        }
-        const f32x4 acc = a0 + a1;                   // row = unit 4 (lane >> 4) + r, column = utterance lane & 15
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[wave][(lane >> 4) * 4 + e][lane & 15] = acc[e];
-        __syncthreads();
-        dh_rec = sum4(red[0][ul][bl], red[1][ul][bl], red[2][ul][bl], red[3][ul][bl]);
+        const float *wp = p.w_hh + ((size_t)wave * NS * 16 + 4 * kq) * Hr + unit - (tid & 15) + (lane & 15);    // W_hh in place; 16 * rg spelled so: profiles/ab_bptt_shared.txt, section 3
+        dh_rec = bptt_step_product<NS, 2>(
+            [&](int s) {
+                const float *w = wp + (size_t)16 * s * Hr;
+                return make_float4(w[0], w[Hr], w[2 * (size_t)Hr], w[3 * (size_t)Hr]);
+            },
+            [&](int s) {
+                const int k = 16 * (wave * NS + s) + 4 * kq;                  // 2Hr is a multiple of 16: four k never straddle the two buffers
+                if (!live) return make_float4(0.f, 0.f, 0.f, 0.f);
+                return k < 2 * Hr ? *(const float4 *)(p.dgi + nrow * (3 * Hr) + k) : *(const float4 *)(p.dghn + nrow * Hr + (k - 2 * Hr));
+            });
     }
     if (act) {
-        const float dh = (dhh + dh_rec) + carry;
-        const float dn = dh * (1.0f - z), dz = dh * (hp - n);
-        const float gn = dn * (1.0f - n * n), gz = dz * (z * (1.0f - z)), gr = (gn * hn) * (r * (1.0f - r));
+        const GruCellGrad c = gru_cell_bwd(r, z, hn, n, hp, (dhh + dh_rec) + carry);
         float *d = p.dgi + drow * (3 * Hr) + unit;
-        d[0] = gr; d[Hr] = gz; d[2 * Hr] = gn;
-        p.dghn[drow * Hr + unit] = gn * r;
-        p.carry[(size_t)bg * Hr + unit] = dh * z;
+        d[0] = c.gr; d[Hr] = c.gz; d[2 * Hr] = c.gn;
+        p.dghn[drow * Hr + unit] = c.gn_r;
+        p.carry[(size_t)bg * Hr + unit] = c.carry;
     }
 }
 
@@ -233,66 +205,29 @@ __global__ void voc_keep_first_kernel(float *__restrict__ dgi, float *__restrict
     else dghn[r1 * Hr + i - 3 * Hr] = dghn[r0 * Hr + i - 3 * Hr];
 }
 
-// The operands of the sums over rows.  PLAIN: A (R, lda), Bm (R, ldb) as they stand.  WHH: A = dgh of the chunk's live rows (dgi's r
-// and z thirds, dghn), Bm = Hp.  GEMB: A = onehot(x) of the live rows, Bm = dgi.
-enum { ATB_PLAIN = 0, ATB_WHH = 1, ATB_GEMB = 2 };
-struct VocAtbP {
-    const float *A; int lda;
-    const float *A2;                     // WHH: dghn
-    const float *Bm; int ldb;
+// The operands of the chunk's sums over rows that are not plain (grad_atb_kernel, grad_colsum_kernel of grad_slab.h); a row that is not
+// live enters as zeros.  WHH: a = dgh of the chunk's rows (dgi's r and z thirds, dghn), b = Hp.  GEMB: a = onehot(x), b = dgi.
+enum { ATB_WHH, ATB_GEMB };
+template <int MODE> struct VocAtb {
+    const float *dgi, *dghn, *hp;
     VocRows q;
     float *out; int ldo;                 // out[m * ldo + c] += sum
     int R;
+    __device__ float a(int r, int m) const {
+        int b, t;
+        if (!row_live(q, r, b, t)) return 0.f;
+        if (MODE == ATB_GEMB) return clamp_class(q.audio[(size_t)b * q.L + t]) == m ? 1.f : 0.f;
+        const size_t dr = (size_t)b * (q.CH + 1) + (t - q.t0);
+        return m < 2 * q.Hr ? dgi[dr * (3 * q.Hr) + m] : dghn[dr * q.Hr + m - 2 * q.Hr];
+    }
+    __device__ float b(int r, int c) const {
+        if (MODE == ATB_WHH) return hp[(size_t)r * q.Hr + c];
+        int b, t;
+        if (!row_live(q, r, b, t)) return 0.f;
+        return dgi[((size_t)b * (q.CH + 1) + (t - q.t0)) * (3 * q.Hr) + c];
+    }
+    __device__ void put(int m, int c, float v) const { float *o = out + (size_t)m * ldo + c; *o = *o + v; }
 };
-template <int MODE>
-__device__ __forceinline__ float atb_a(const VocAtbP &p, int r, int m) {
-    if (MODE == ATB_PLAIN) return p.A[(size_t)r * p.lda + m];
-    int b, t;
-    if (!row_live(p.q, r, b, t)) return 0.f;
-    if (MODE == ATB_GEMB) return clamp_class(p.q.audio[(size_t)b * p.q.L + t]) == m ? 1.f : 0.f;
-    const size_t dr = (size_t)b * (p.q.CH + 1) + (t - p.q.t0);
-    return m < 2 * p.q.Hr ? p.A[dr * (3 * p.q.Hr) + m] : p.A2[dr * p.q.Hr + m - 2 * p.q.Hr];
-}
-template <int MODE>
-__device__ __forceinline__ float atb_b(const VocAtbP &p, int r, int c) {
-    if (MODE != ATB_GEMB) return p.Bm[(size_t)r * p.ldb + c];
-    int b, t;
-    if (!row_live(p.q, r, b, t)) return 0.f;
-    return p.Bm[((size_t)b * (p.q.CH + 1) + (t - p.q.t0)) * p.ldb + c];
-}
-
-// grid (Nb / 16, Na / 64): wave w of workgroup (x, y) owns the tile rows 64 y + 16 w .. + 15 of A's columns, columns 16 x .. + 15 of Bm's.
-template <int MODE>
-__global__ __launch_bounds__(256) void voc_atb_kernel(VocAtbP p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, ks = lane >> 4;
-    const int m = blockIdx.y * 64 + wave * 16 + i, c = blockIdx.x * 16 + i;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int r0 = 0; r0 < p.R; r0 += GRAD_SLAB)
-        sum = sum + slab_mfma_tile(p.R, r0, ks, [&](int r) { return atb_a<MODE>(p, r, m); }, [&](int r) { return atb_b<MODE>(p, r, c); });
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {                    // row = 64 y + 16 w + 4 ks + e of the output, column = 16 x + i
-        float *o = p.out + (size_t)(blockIdx.y * 64 + wave * 16 + ks * 4 + e) * p.ldo + c;
-        *o = *o + sum[e];
-    }
-}
-
-// Column sums over the rows: out[m] += sum_r a(r, m).  grid (Na / 64)
-template <int MODE>
-__global__ __launch_bounds__(256) void voc_colsum_kernel(VocAtbP p) {
-    __shared__ float red[4][64];
-    const int d = threadIdx.x & 63, rg = threadIdx.x >> 6, m = blockIdx.x * 64 + d;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; rg + 4 * i < p.R; i += 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = rg + 4 * (i + e);
-            a[e] += r < p.R ? atb_a<MODE>(p, r, m) : 0.f;
-        }
-    }
-    red[rg][d] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (rg == 0) p.out[m] = p.out[m] + ((red[0][d] + red[1][d]) + (red[2][d] + red[3][d]));
-}
 
 // dGc[gbase[b] + f] += sum of dgi over the live steps of frame f inside the chunk.  grid (B T2, ceil(3Hr / 256))
 __global__ void voc_frame_sum_kernel(const float *__restrict__ dgi, float *__restrict__ dGc, const int *__restrict__ frames,
@@ -310,15 +245,8 @@ __global__ void voc_frame_sum_kernel(const float *__restrict__ dgi, float *__res
     *o = *o + sum;
 }
 
-template <int MODE> void launch_atb(const VocAtbP &p, int Na, int Nb, hipStream_t s) {
-    hipLaunchKernelGGL((voc_atb_kernel<MODE>), dim3(Nb / 16, Na / 64), dim3(256), 0, s, p);
-}
-template <int MODE> void launch_colsum(const VocAtbP &p, int Na, hipStream_t s) {
-    hipLaunchKernelGGL((voc_colsum_kernel<MODE>), dim3(Na / 64), dim3(256), 0, s, p);
-}
-void launch_rows_w(const float *A, const float *W, int ldw, float *out, const float *mask, long long R, int K, int N, const int *frames,
-                   const int *gbase, int T2, hipStream_t s) {
-    hipLaunchKernelGGL(voc_rows_w_kernel, dim3((unsigned)((R + 15) / 16), N / 16), dim3(256), 0, s, A, W, ldw, out, mask, (int)R, K, N, frames, gbase, T2);
+void launch_rows_w(const float *A, const float *W, int ldw, float *out, const VocRowMap &map, long long R, int K, hipStream_t s) {
+    hipLaunchKernelGGL(grad_rows_w_kernel<VocRowMap>, dim3((unsigned)((R + 15) / 16), map.N / 16), dim3(256), 0, s, A, W, ldw, out, (int)R, K, map.N, map);
 }
 
 const float *const *members(const vqcpc_vocoder_ar_weights *w) { return &w->embedding; }     // nine pointers in a row
@@ -356,20 +284,6 @@ int ar_bwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64
            const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream);
 
 }  // namespace
-
-void vq_grad_atb(const float *A, int lda, const float *Bm, int ldb, float *out, int ldo, int R, int Na, int Nb, hipStream_t s) {
-    VocAtbP p{};
-    p.A = A; p.lda = lda; p.Bm = Bm; p.ldb = ldb; p.out = out; p.ldo = ldo; p.R = R;
-    launch_atb<ATB_PLAIN>(p, Na, Nb, s);
-}
-void vq_grad_colsum(const float *A, int lda, float *out, int R, int Na, hipStream_t s) {
-    VocAtbP p{};
-    p.A = A; p.lda = lda; p.out = out; p.R = R;
-    launch_colsum<ATB_PLAIN>(p, Na, s);
-}
-void vq_grad_rows_w(const float *A, const float *W, int ldw, float *out, int R, int K, int N, hipStream_t s) {
-    launch_rows_w(A, W, ldw, out, nullptr, R, K, N, nullptr, nullptr, 1, s);
-}
 
 extern "C" int vqcpc_vocoder_ar_saved_bytes(vqcpc_vocoder *v, int B, int L, uint64_t *bytes) {
     VQ_REQUIRE(v && bytes, "vqcpc_vocoder_ar_saved_bytes: null argument");
@@ -507,15 +421,14 @@ int ar_bwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64
         TRY(vq_gemm_chain_ex(Hc, Hr, view.w_fc1, view.b_fc1, a1, Hf, (int)M, Hf, Hr, Hr, 1, 0, 0, 0, 0, s));
         TRY(vq_gemm_chain(a1, Hf, view.w_fc2, view.b_fc2, dl, n_cls, (int)M, n_cls, Hf, Hf, s));
         hipLaunchKernelGGL(voc_softmax_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, dl, q, grad_loss, inv_n);
-        VocAtbP p{};
-        p.q = q; p.R = (int)M;
-        if (g.fc2_weight) { p.A = dl; p.lda = n_cls; p.Bm = a1; p.ldb = Hf; p.out = g.fc2_weight; p.ldo = Hf; launch_atb<ATB_PLAIN>(p, n_cls, Hf, s); }
-        if (g.fc2_bias) { p.A = dl; p.lda = n_cls; p.out = g.fc2_bias; launch_colsum<ATB_PLAIN>(p, n_cls, s); }
-        if (need_fc1 || need_rnn) launch_rows_w(dl, view.w_fc2, Hf, da, a1, (long long)M, n_cls, Hf, nullptr, nullptr, 1, s);
-        if (g.fc1_weight) { p.A = da; p.lda = Hf; p.Bm = Hc; p.ldb = Hr; p.out = g.fc1_weight; p.ldo = Hr; launch_atb<ATB_PLAIN>(p, Hf, Hr, s); }
-        if (g.fc1_bias) { p.A = da; p.lda = Hf; p.out = g.fc1_bias; launch_colsum<ATB_PLAIN>(p, Hf, s); }
+        const int R = (int)M;
+        if (g.fc2_weight) vq_grad_atb(dl, n_cls, a1, Hf, g.fc2_weight, Hf, R, n_cls, Hf, s);
+        if (g.fc2_bias) vq_grad_colsum(dl, n_cls, g.fc2_bias, R, n_cls, s);
+        if (need_fc1 || need_rnn) launch_rows_w(dl, view.w_fc2, Hf, da, VocRowMap{a1, Hf, nullptr, nullptr, 1}, R, n_cls, s);
+        if (g.fc1_weight) vq_grad_atb(da, Hf, Hc, Hr, g.fc1_weight, Hr, R, Hf, Hr, s);
+        if (g.fc1_bias) vq_grad_colsum(da, Hf, g.fc1_bias, R, Hf, s);
         if (!need_rnn) continue;
-        launch_rows_w(da, view.w_fc1, Hr, dhh, nullptr, (long long)M, Hf, Hr, nullptr, nullptr, 1, s);
+        vq_grad_rows_w(da, view.w_fc1, Hr, dhh, R, Hf, Hr, s);
         // gates again
         TRY(vq_gemm_chain(Hp, Hr, w_hh, b_hh, gh, 3 * Hr, (int)M, 3 * Hr, Hr, Hr, s));
         hipLaunchKernelGGL(voc_gates_kernel, ghr, dim3(256), 0, s, gh, nn, view.Gemb, v->gcond.as<float>(), gbase, q, up);
@@ -528,28 +441,25 @@ int ar_bwd(const char *what, vqcpc_vocoder *v, const int64_t *audio, const int64
             else hipLaunchKernelGGL((voc_bwd_step_kernel<48>), grid, dim3(256), 0, s, sp, t);
         }
         // the chunk's sums
-        p.A = dgi; p.A2 = dghn; p.Bm = Hp; p.ldb = Hr;
-        if (g.w_hh) { p.out = g.w_hh; p.ldo = Hr; launch_atb<ATB_WHH>(p, 3 * Hr, Hr, s); }
-        if (g.b_hh) { p.out = g.b_hh; launch_colsum<ATB_WHH>(p, 3 * Hr, s); }
+        const dim3 blk(256);
+        if (g.w_hh) hipLaunchKernelGGL(grad_atb_kernel<VocAtb<ATB_WHH>>, dim3(Hr / 16, 3 * Hr / 64), blk, 0, s, VocAtb<ATB_WHH>{dgi, dghn, Hp, q, g.w_hh, Hr, R});
+        if (g.b_hh) hipLaunchKernelGGL(grad_colsum_kernel<VocAtb<ATB_WHH>>, dim3(3 * Hr / 64), blk, 0, s, VocAtb<ATB_WHH>{dgi, dghn, Hp, q, g.b_hh, 0, R});
         if (need_tabs) {
-            p.Bm = dgi; p.ldb = 3 * Hr; p.out = k.dGemb.as<float>(); p.ldo = 3 * Hr;
-            launch_atb<ATB_GEMB>(p, n_cls, 3 * Hr, s);
+            hipLaunchKernelGGL(grad_atb_kernel<VocAtb<ATB_GEMB>>, dim3(3 * Hr / 16, n_cls / 64), blk, 0, s,
+                               VocAtb<ATB_GEMB>{dgi, dghn, Hp, q, k.dGemb.as<float>(), 3 * Hr, R});
             hipLaunchKernelGGL(voc_frame_sum_kernel, dim3(B * T2, (3 * Hr + 255) / 256), dim3(256), 0, s, dgi, k.dGc.as<float>(), frames, gbase, q, T2, up);
         }
         if (ch > 0) hipLaunchKernelGGL(voc_keep_first_kernel, dim3((4 * Hr + 255) / 256, B), dim3(256), 0, s, dgi, dghn, CH, Hr);
     }
     if (need_tabs) {
         float *dGemb = k.dGemb.as<float>(), *dGc = k.dGc.as<float>();
-        VocAtbP p{};
         if (g.w_ih) {
-            p.A = dGemb; p.lda = 3 * Hr; p.Bm = emb; p.ldb = de; p.out = g.w_ih; p.ldo = de + C; p.R = n_cls;
-            launch_atb<ATB_PLAIN>(p, 3 * Hr, de, s);
-            p.A = dGc; p.Bm = v->cond.as<float>(); p.ldb = C; p.out = g.w_ih + de; p.R = (int)grows;
-            launch_atb<ATB_PLAIN>(p, 3 * Hr, C, s);
+            vq_grad_atb(dGemb, 3 * Hr, emb, de, g.w_ih, de + C, n_cls, 3 * Hr, de, s);
+            vq_grad_atb(dGc, 3 * Hr, v->cond.as<float>(), C, g.w_ih + de, de + C, (int)grows, 3 * Hr, C, s);
         }
-        if (g.b_ih) { p.A = dGc; p.lda = 3 * Hr; p.out = g.b_ih; p.R = (int)grows; launch_colsum<ATB_PLAIN>(p, 3 * Hr, s); }
-        if (g.embedding) launch_rows_w(dGemb, w_emb, ld_emb, g.embedding, nullptr, n_cls, 3 * Hr, de, nullptr, nullptr, 1, s);
-        if (grad_cond) launch_rows_w(dGc, w_cond, ld_cond, grad_cond, nullptr, (long long)B * T2, 3 * Hr, C, frames, gbase, T2, s);
+        if (g.b_ih) vq_grad_colsum(dGc, 3 * Hr, g.b_ih, (int)grows, 3 * Hr, s);
+        if (g.embedding) vq_grad_rows_w(dGemb, w_emb, ld_emb, g.embedding, n_cls, 3 * Hr, de, s);
+        if (grad_cond) launch_rows_w(dGc, w_cond, ld_cond, grad_cond, VocRowMap{nullptr, C, frames, gbase, T2}, (long long)B * T2, 3 * Hr, s);
     }
     HIP_TRY(hipGetLastError());
     return VQCPC_OK;

@@ -262,12 +262,5 @@ int vq_tf_score(vqcpc_vocoder *v, const int64_t *audio, const int64_t *idx, cons
 // bases (v->gbase) on the device, and the scored steps in v->nll_len.  cond_in: run_conditioning's.
 int vq_tf_condition(vqcpc_vocoder *v, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes, const std::vector<int> &slen,
                     const ArView *w, UttLayout &u, hipStream_t s, const float *cond_in = nullptr);
-// vocoder_grad.hip's fixed-order products over rows, which prenet_grad.hip runs on its own rows (the orders: vocoder_grad.hip's header).
-// out (Na, ldo)[:, :Nb] += A^T B for A (R, lda), B (R, ldb); Na % 64 == 0, Nb % 16 == 0.
-void vq_grad_atb(const float *A, int lda, const float *Bm, int ldb, float *out, int ldo, int R, int Na, int Nb, hipStream_t s);
-// out (Na) += column sums of A (R, lda); Na % 64 == 0.
-void vq_grad_colsum(const float *A, int lda, float *out, int R, int Na, hipStream_t s);
-// out (R, N) = A (R, K) W (K rows of ldw); K % 64 == 0, N % 16 == 0.
-void vq_grad_rows_w(const float *A, const float *W, int ldw, float *out, int R, int K, int N, hipStream_t s);
 int run_resident(vqcpc_vocoder *v, const CallPlan &cp, int T2, unsigned long long seed, float *wav, int64_t *mulaw, hipStream_t s, const Resume *rs = nullptr);
 int run_launch_path(vqcpc_vocoder *v, const CallPlan &cp, const int64_t *inputs, int T2, int Ts, unsigned long long seed, float *wav, int64_t *mulaw, float *logits, hipStream_t s, const Resume *rs = nullptr, const NllCall *nc = nullptr);
