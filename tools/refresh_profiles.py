@@ -20,6 +20,7 @@
   probe        tools/xcd_decoder_probe.py, tools/xcm_probe.py              -> <round>_xcd_probe.csv, <round>_xcm_probe.csv
   by_batch     tools/bench_by_batch.py                                     -> <round>_bench_by_batch.csv
   voc_grad     tools/voc_grad_times.py                                     -> voc_grad_times.txt (no round prefix: one file)
+  adam         tools/adam_times.py                                         -> adam_times.txt (likewise)
   summary      rewrites the numbers quoted in profiles/<round>_summary.md from the files above
 
 Every step is a fresh child process; the parent never touches the GPU (rocprofv3 must have the program itself after `--`).
@@ -64,7 +65,7 @@ def main():
     args = ap.parse_args()
     skip = set(s for s in args.skip.split(",") if s)
     if args.only:
-        every = {"bench", "trace", "pmc", "pmc_big", "pmc_xcm", "pmc_sq", "manifest", "encoder", "timeline", "probe", "by_batch", "voc_grad", "summary"}
+        every = {"bench", "trace", "pmc", "pmc_big", "pmc_xcm", "pmc_sq", "manifest", "encoder", "timeline", "probe", "by_batch", "voc_grad", "adam", "summary"}
         skip = every - set(s for s in args.only.split(",") if s)
     R = args.round
     # on the GPU box only gpurun_out/ travels back: the artifacts go to gpurun_out/profiles_<round>/ (copy them into profiles/
@@ -134,6 +135,8 @@ def main():
     if "voc_grad" not in skip:
         ok["voc_grad"] = run([PY, "tools/voc_grad_times.py", "--out", os.path.join(P, "voc_grad_times.txt")], out=os.path.join(S, "voc_grad.log"),
                              timeout=900)
+    if "adam" not in skip:
+        ok["adam"] = run([PY, "tools/adam_times.py", "--out", os.path.join(P, "adam_times.txt")], out=os.path.join(S, "adam.log"), timeout=900)
     if "summary" not in skip:
         summary(P, R)
     print("[refresh]", json.dumps(ok), flush=True)

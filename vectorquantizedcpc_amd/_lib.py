@@ -45,6 +45,9 @@ VOC_GRAD_SYMBOLS = ["vqcpc_vocoder_ar_saved_bytes", "vqcpc_vocoder_ar_fwd", "vqc
 COND_GRAD_SYMBOLS = ["vqcpc_vocoder_cond_saved_bytes", "vqcpc_vocoder_cond_fwd", "vqcpc_vocoder_cond_bwd", "vqcpc_vocoder_ar_fwd_cond",
                      "vqcpc_vocoder_ar_bwd_cond"]
 
+# every symbol include/vqcpc_optim.h declares, likewise
+OPTIM_SYMBOLS = ["vqcpc_adam_step"]
+
 
 class EncoderWeights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p), ("ln_weight", C.c_void_p * 5), ("ln_bias", C.c_void_p * 5),
@@ -81,6 +84,16 @@ class VocoderCondTensors(C.Structure):
     _fields_ = [("code_embedding", C.c_void_p), ("speaker_embedding", C.c_void_p),
                 ("prenet_w_ih", (C.c_void_p * 2) * 2), ("prenet_w_hh", (C.c_void_p * 2) * 2),
                 ("prenet_b_ih", (C.c_void_p * 2) * 2), ("prenet_b_hh", (C.c_void_p * 2) * 2)]
+
+
+class AdamTensor(C.Structure):
+    """``vqcpc_adam_tensor`` (``include/vqcpc_optim.h``)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_uint64)]
+
+
+class AdamHyper(C.Structure):
+    """``vqcpc_adam_hyper`` (``include/vqcpc_optim.h``)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("step", C.c_int64)]
 
 
 class CPCWeights(C.Structure):
@@ -143,6 +156,7 @@ def load():
     lib.vqcpc_cpc_destroy.restype = None
     lib.vqcpc_cpc_score.argtypes = [vp, vp, vp, i32, i64p, i64p, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_cpc_grad.argtypes = [vp, vp, vp, i32, vp, vp, i64p, i64p, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vqcpc_adam_step.argtypes = [C.POINTER(AdamTensor), i32, C.POINTER(AdamHyper), vp]
     lib.vqcpc_abx_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
     lib.vqcpc_abx_score.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp]
     lib.vqcpc_abx_index_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
@@ -320,6 +334,13 @@ def cached_handle(cache: dict, device, create: str, *args):
             check(getattr(load(), create)(*args, C.byref(h)))
         cache[key] = h
     return h
+
+
+def adam_step(table, n: int, hyper, device):
+    """One ``vqcpc_adam_step`` call: the first ``n`` rows of ``table`` (an ``AdamTensor`` array) with ``hyper`` (an ``AdamHyper``), on
+    the current stream of ``device``."""
+    with device_guard(device):
+        check(load().vqcpc_adam_step(table, n, C.byref(hyper), current_stream()))
 
 
 def run_checked(run, check, message: str):

@@ -62,6 +62,12 @@ Adam).  ``--train ar,prenet,embeddings`` names the parts that step: by default t
 frozen; with them named the whole ``loss.backward()`` runs in HIP down to ``code_embedding.weight`` (``vqcpc_vocoder_cond_fwd`` /
 ``_bwd``) -- after the codebook moved, ``code_embedding`` is the table the moved indices index.  It prints the ``score-vocoder`` line before and after and writes
 ``{"vocoder": state_dict}``.
+The four ``fit-*`` commands share the optimizer options: ``--optimizer hip`` makes the update ``vqcpc_adam_step`` (``optim.Adam``;
+the default stays torch's Adam), ``--warmup E --initial-lr A --milestones M1,M2 --gamma G`` schedules the learning rate as the
+reference's ``scheduler.py`` does, from ``A`` to ``--lr`` over ``E`` epochs and times ``G`` at every milestone (``--milestones``
+alone: torch's ``MultiStepLR``; an epoch is one pass over the batches, for ``fit-vocoder`` one step, ``vocoder.py:102-105``), and
+``--optimizer-state PATH`` reads ``{"optimizer", "scheduler", "steps_done"}`` from the file if it exists and writes it at the end,
+so that a later run goes on where this one stopped.
 ``score-vocoder`` is the validation number the reference's vocoder training never computes (``vocoder.py:68-94``): the
 teacher-forced cross-entropy of ``vocoder.py:62-63`` on ``<in_dir>/<utterance>.wav`` of every entry of ``test.json``, speaker id
 from ``speakers.json`` by the file name's prefix: loss in nats per sample, bits per sample and top-1 accuracy
@@ -162,6 +168,33 @@ def score_dataset(args) -> int:
     return _print_score(args, *_score_setup(args))
 
 
+def _optimizer_kwargs(args) -> dict:
+    """``--optimizer``, the schedule options and ``--optimizer-state`` of a fit command -> the ``optimizer=``, ``scheduler=`` and
+    ``opt_state=`` its driver takes.  ``--warmup`` (with ``--milestones``) is ``optim.WarmupScheduler`` from ``--initial-lr`` to
+    ``--lr``; ``--milestones`` alone is torch's ``MultiStepLR``; neither: a constant ``--lr``, as before.  ``opt_state`` is what
+    ``--optimizer-state`` holds if the file exists, else an empty dict to be filled; None without the option."""
+    from . import optim
+    kw = {"optimizer": optim.Adam if args.optimizer == "hip" else torch.optim.Adam}
+    milestones = [int(m) for m in args.milestones.split(",") if m] if args.milestones else None
+    gamma = 0.1 if args.gamma is None else args.gamma
+    if args.warmup is not None:
+        initial = args.lr if args.initial_lr is None else args.initial_lr
+        kw["scheduler"] = lambda opt: optim.WarmupScheduler(opt, args.warmup, initial, args.lr, milestones, gamma)
+    elif milestones:
+        kw["scheduler"] = lambda opt: torch.optim.lr_scheduler.MultiStepLR(opt, milestones, gamma)
+    if args.optimizer_state:
+        path = Path(args.optimizer_state)
+        kw["opt_state"] = torch.load(path, map_location=args.device, weights_only=True) if path.exists() else {}
+    return kw
+
+
+def _save_optimizer_state(args, kw) -> None:
+    if args.optimizer_state:
+        state = kw["opt_state"]
+        torch.save({k: state.get(k) for k in ("optimizer", "scheduler", "steps_done")}, args.optimizer_state)
+        print(f"wrote {args.optimizer_state}: optimizer and scheduler state after {state.get('steps_done', 0)} steps")
+
+
 def _fit_dataset(args, fit, what, losses, encoder_update, wrote) -> int:
     """The body of the three fit commands: score, ``fit(enc, cpc, by_speaker, ...)``, a summary line -- ``what(cpc)`` was fitted,
     ``losses(r)`` closes it --, score again, and save with ``encoder_update(enc)`` (None: ``"encoder"`` stays as it was), which
@@ -170,7 +203,9 @@ def _fit_dataset(args, fit, what, losses, encoder_update, wrote) -> int:
     print("before the fit:")
     if _print_score(args, enc, cpc, by_speaker):
         return 1
-    r = fit(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed)
+    okw = _optimizer_kwargs(args)
+    r = fit(enc, cpc, by_speaker, steps=args.steps, lr=args.lr, sample_frames=args.sample_frames, seed=args.seed, **okw)
+    _save_optimizer_state(args, okw)
     print(f"fitted {what(cpc)} in {r['steps']} steps of Adam (lr {args.lr:g}) over {r['batches']} batches{losses(r)}")
     print("after the fit:")
     rc = _print_score(args, enc, cpc, by_speaker)
@@ -269,8 +304,10 @@ def fit_vocoder_dataset(args) -> int:
     enc, voc, paths, waves, speakers = setup
     print("before the fit:")
     print(_vocoder_line(driver.score_vocoder(enc, voc, waves, None, speakers, max_batch=args.max_batch)[1]))
+    okw = _optimizer_kwargs(args)
     r = driver.fit_vocoder(enc, voc, waves, None, speakers, steps=args.steps, lr=args.lr, max_batch=min(args.max_batch, 32),
-                           clip_codes=args.clip_codes if args.clip_codes > 0 else None, seed=args.seed, train=_vocoder_parts(args.train))
+                           clip_codes=args.clip_codes if args.clip_codes > 0 else None, seed=args.seed, train=_vocoder_parts(args.train), **okw)
+    _save_optimizer_state(args, okw)
     if r["steps"] == 0:
         print("no utterance with two samples to score: nothing fitted")
         return 1
@@ -392,6 +429,13 @@ def main(argv=None) -> int:
         p.add_argument("--random-init", action="store_true", help="seeded random-init weights (no checkpoint ships with the reference)")
         p.add_argument("--device", default="cuda")
         p.add_argument("--max-batch", type=int, default=64)
+        if name.startswith("fit-"):
+            p.add_argument("--optimizer", choices=("torch", "hip"), default="torch", help="hip: the update is vqcpc_adam_step (optim.Adam)")
+            p.add_argument("--warmup", type=int, help="epochs (fit-vocoder: steps) of linear warm-up from --initial-lr to --lr; needs --milestones")
+            p.add_argument("--initial-lr", type=float, help="the learning rate the warm-up starts from")
+            p.add_argument("--milestones", help="comma-separated epochs (fit-vocoder: steps) at which the rate is multiplied by --gamma, e.g. 300,400")
+            p.add_argument("--gamma", type=float, help="the factor at a milestone (default 0.1)")
+            p.add_argument("--optimizer-state", help="file of {optimizer, scheduler, steps_done}: read if it exists, written at the end")
         if name in ("score", "fit-predictors", "fit-context", "fit-encoder"):               # config.py:42-47, :202
             p.add_argument("--prediction-steps", type=int, default=12)
             p.add_argument("--speakers", type=int, default=8)
@@ -465,6 +509,11 @@ def main(argv=None) -> int:
         parts = _vocoder_parts(args.train)
         if not parts or len(set(parts)) != len(parts) or any(t not in Vocoder.TRAIN_PARTS for t in parts):
             ap.error(f"fit-vocoder --train: name each of {','.join(Vocoder.TRAIN_PARTS)} at most once, and at least one")
+    if args.cmd.startswith("fit-"):
+        if args.warmup is not None and not args.milestones:
+            ap.error(f"{args.cmd} --warmup needs --milestones (the warm-up ends before the first)")
+        if (args.initial_lr is not None and args.warmup is None) or (args.gamma is not None and not args.milestones):
+            ap.error(f"{args.cmd}: --initial-lr goes with --warmup, --gamma with --milestones")
     if args.cmd in ("score-vocoder", "fit-vocoder") and not args.random_init and not args.vocoder_checkpoint:
         ap.error("give --cpc-checkpoint and --vocoder-checkpoint, or --random-init")
     return {"encode": encode_dataset, "convert": convert_dataset, "score": score_dataset,

@@ -302,7 +302,7 @@ def score_batches(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, sample_frames
 
 
 def fit_predictors(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 200, lr: float = 4e-4, optimizer=torch.optim.Adam,
-                   sample_frames: int = 128, seed: int = 13, device=None):
+                   sample_frames: int = 128, seed: int = 13, device=None, scheduler=None, opt_state: Optional[dict] = None):
     """Refit the K linear predictors of ``cpc`` on a FROZEN ``encoder`` -- what an adapted codebook needs before its CPC
     score means anything again (``adapt_codebook`` -> ``fit_predictors`` -> ``score_batches``).  Log-sum-exp of affine functions
     is convex in ``(W_k, b_k)``, so this is a convex fit.
@@ -311,12 +311,20 @@ def fit_predictors(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int =
     The encoder runs under ``no_grad``, once per batch (it does not change; the encoded ``z``, ``c`` are kept on the device);
     ``cpc(z, c, seed=seed, stream_id=batch, differentiable=True)`` and ``backward()`` are one ``vqcpc_cpc_grad`` call asking
     for dW and db only; ``optimizer(params, lr=lr)`` -- torch's, as glue -- is given ``cpc.predictors[:K]`` alone, the K
-    predictors the loss never reads stay as they are.
+    predictors the loss never reads stay as they are.  ``optimizer=optim.Adam`` (``vectorquantizedcpc_amd.optim``) makes the update
+    one ``vqcpc_adam_step`` call as well.
+
+    ``scheduler``: None (a constant ``lr``) or a factory called with the optimizer, e.g.
+    ``lambda opt: optim.WarmupScheduler(opt, 150, 1e-5, 4e-4, [300, 400], 0.25)``; it is stepped when the batch index wraps (one
+    epoch = one pass over the batches, ``train_cpc.py:136``).  ``opt_state``: None or a dict.  Its ``"optimizer"`` (and
+    ``"scheduler"``) entries, where it has them, are loaded before step 0 -- the learning rate among them, which then wins over
+    ``lr`` --, the step-to-batch map continues from ``opt_state.get("steps_done", 0)``, and after the last step the dict holds both
+    state dicts and the new ``"steps_done"``: a fit of 2n steps equals two fits of n steps joined by one ``opt_state``, bit for bit.
 
     Returns ``losses`` and ``accuracies`` (per step; reading them synchronises once per step), ``steps``, ``batches``,
     ``utterances`` and the speakers ``score_batches`` would name: ``speakers_skipped``, ``speakers_left_over``."""
     return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, _predictor_params(cpc),
-                _encoded_step(cpc, seed, lambda z, c: c))
+                _encoded_step(cpc, seed, lambda z, c: c), scheduler=scheduler, opt_state=opt_state)
 
 
 def _predictor_params(cpc):
@@ -334,13 +342,13 @@ def _encoded_step(cpc, seed, context):
 
 
 def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params, step_of, frozen=(),
-         encode_once=True, extras=()):
+         encode_once=True, extras=(), scheduler=None, opt_state=None):
     """The loop the three fits share: the batches of ``_score_plan``, step i on batch ``i mod batches``; per step
     ``step_of(b, batch)`` -> (the loss to back-propagate, the CPC loss, the accuracies, dict of the ``extras``), ``backward()`` and
     one step of ``optimizer(params, lr=lr)``.  ``encode_once``: ``batch`` is ``(z, c)`` of ``encoder(mels)``, computed under
     ``no_grad`` at the batch's first turn, checked and kept on the device; otherwise it is the mels, nothing is encoded ahead and
     ``encoder.check()`` follows ``backward()``.  ``frozen``: parameters that require no gradient while the loop runs.  ``extras``:
-    the names of further per-step lists in the result."""
+    the names of further per-step lists in the result.  ``scheduler``, ``opt_state``: ``fit_predictors`` describes them."""
     S, U = cpc.n_speakers_per_batch, cpc.n_utterances_per_speaker
     dev = device if device is not None else next(encoder.parameters()).device
     n_batches, skipped, left, batch_mels = _score_plan(cpc, mels_by_speaker, sample_frames, seed, dev)
@@ -349,12 +357,13 @@ def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, see
     if n_batches == 0 or steps <= 0:
         return res
     opt = optimizer(params, lr=lr)
+    sched, done = _resume(opt, scheduler, opt_state)
     for p in frozen:                                     # a part that does not step costs no backward either
         p.requires_grad_(False)
     encoded = {}
     try:
         for step in range(steps):
-            b = step % n_batches
+            b = (done + step) % n_batches
             if not encode_once:
                 batch = batch_mels(b)
             elif b in encoded:
@@ -372,6 +381,10 @@ def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, see
             if not encode_once and hasattr(encoder, "check"):
                 encoder.check()
             opt.step()
+            if sched is not None and b == n_batches - 1:         # the batch index wraps: an epoch is over
+                sched.step()
+            if opt_state is not None:
+                opt_state["steps_done"] = done + step + 1
             res["losses"].append(float(cpc_loss.detach()))
             for k in extras:
                 res[k].append(float(extra[k]))
@@ -380,11 +393,33 @@ def _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, see
     finally:
         for p in frozen:
             p.requires_grad_(True)
+    _keep(opt, sched, opt_state)
     return res
 
 
+def _resume(opt, scheduler, opt_state):
+    """What a fit does with its optimizer before step 0: ``scheduler(opt)`` (None stays None), then the ``"optimizer"`` and
+    ``"scheduler"`` entries of ``opt_state`` loaded where it has them.  -> (the scheduler, the steps done before this fit)."""
+    sched = scheduler(opt) if scheduler is not None else None
+    if not opt_state:
+        return sched, 0
+    if opt_state.get("optimizer") is not None:
+        opt.load_state_dict(opt_state["optimizer"])
+    if sched is not None and opt_state.get("scheduler") is not None:
+        sched.load_state_dict(opt_state["scheduler"])
+    return sched, int(opt_state.get("steps_done", 0))
+
+
+def _keep(opt, sched, opt_state):
+    """After the last step: both state dicts into ``opt_state``, in place (``"steps_done"`` is the loop's)."""
+    if opt_state is not None:
+        opt_state["optimizer"] = opt.state_dict()
+        opt_state["scheduler"] = sched.state_dict() if sched is not None else None
+
+
 def fit_context(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 200, lr: float = 4e-4, optimizer=torch.optim.Adam,
-                sample_frames: int = 128, seed: int = 13, device=None, train_predictors: bool = True):
+                sample_frames: int = 128, seed: int = 13, device=None, train_predictors: bool = True, scheduler=None,
+                opt_state: Optional[dict] = None):
     """Refit the context LSTM ``encoder.rnn`` -- and, with ``train_predictors``, the K predictors of ``cpc`` with it, under one
     optimizer as ``train_cpc.py:53-55`` has them -- on a frozen front end and codebook: after the codebook moves the LSTM sees units
     it was never trained on (``adapt_codebook`` -> ``fit_context`` -> ``score_batches``).
@@ -397,17 +432,18 @@ def fit_context(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 20
     ``cpc.predictors[:K]``).  The native handles are not rebuilt between steps; the next ``encode`` / ``forward`` rebuilds the
     encoder's once.
 
-    Returns what ``fit_predictors`` returns."""
+    ``scheduler``, ``opt_state``: as for ``fit_predictors``.  Returns what ``fit_predictors`` returns."""
     params = list(encoder.rnn.parameters()) + (_predictor_params(cpc) if train_predictors else [])
     return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params,
-                _encoded_step(cpc, seed, lambda z, c: encoder.context(z, differentiable=True)))
+                _encoded_step(cpc, seed, lambda z, c: encoder.context(z, differentiable=True)), scheduler=scheduler, opt_state=opt_state)
 
 
 FIT_ENCODER_PARTS = ("front", "rnn", "predictors")
 
 
 def fit_encoder(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 200, lr: float = 4e-4, optimizer=torch.optim.Adam,
-                sample_frames: int = 128, seed: int = 13, device=None, adapt_codebook: bool = True, train=FIT_ENCODER_PARTS):
+                sample_frames: int = 128, seed: int = 13, device=None, adapt_codebook: bool = True, train=FIT_ENCODER_PARTS,
+                scheduler=None, opt_state: Optional[dict] = None):
     """Refit the whole encoder -- the training step of ``train_cpc.py:116-124`` -- after the codebook moved
     (``adapt_codebook`` -> ``fit_encoder`` -> ``score_batches``): the Conv1d / LayerNorm / Linear front end that produces the units
     follows the codebook, which ``fit_context`` and ``fit_predictors`` cannot make it do.
@@ -423,7 +459,7 @@ def fit_encoder(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 20
     ``vqcpc_cpc_grad``, one ``vqcpc_encoder_context_bwd``, one ``vqcpc_encoder_vq_bwd`` and one ``vqcpc_encoder_front_bwd`` call,
     each asking only for what is needed -- then ``opt.step()``.  The native handles are not rebuilt between steps.
 
-    Returns what ``fit_context`` returns (``losses`` = the CPC loss per step), plus per-step ``vq_losses`` and ``perplexities``."""
+    ``scheduler``, ``opt_state``: as for ``fit_predictors``.  Returns what ``fit_context`` returns (``losses`` = the CPC loss per step), plus per-step ``vq_losses`` and ``perplexities``."""
     train = tuple(train)
     unknown = [t for t in train if t not in FIT_ENCODER_PARTS]
     if unknown or not train or len(set(train)) != len(train):
@@ -439,7 +475,7 @@ def fit_encoder(encoder: Encoder, cpc: CPCLoss, mels_by_speaker, steps: int = 20
         return cpc_loss + vq_loss, cpc_loss, acc, {"vq_losses": vq_loss.detach(), "perplexities": perplexity}
 
     return _fit(encoder, cpc, mels_by_speaker, steps, lr, optimizer, sample_frames, seed, device, params, step, frozen=frozen,
-                encode_once=False, extras=("vq_losses", "perplexities"))
+                encode_once=False, extras=("vq_losses", "perplexities"), scheduler=scheduler, opt_state=opt_state)
 
 
 # ---------------------------------------------------------------------------------------- vocoder scoring
@@ -551,7 +587,7 @@ def training_cuts(indices, audio, n_codes, keep, upsample: int, clip_codes: Opti
 
 def fit_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speakers: Sequence[int], steps: int = 200, lr: float = 4e-4,
                 optimizer=torch.optim.Adam, max_batch: int = 32, max_pad_frac: float = 0.25, clip_codes: Optional[int] = 16, seed: int = 13,
-                conf=None, train=("ar",)):
+                conf=None, train=("ar",), scheduler=None, opt_state: Optional[dict] = None):
     """Refit the vocoder on the units a frozen encoder produces -- the vocoder objective of ``vocoder.py:62-63`` -- after
     ``adapt_codebook`` or ``fit_encoder`` moved those units, or for new speakers and recording conditions (``score_vocoder`` ->
     ``fit_vocoder`` -> ``score_vocoder``).
@@ -572,6 +608,10 @@ def fit_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speake
     ``vqcpc_vocoder_ar_fwd_cond``, ``vqcpc_vocoder_ar_bwd_cond`` and ``vqcpc_vocoder_cond_bwd`` -- then one step of
     ``optimizer(params, lr=lr)`` (torch's, as glue).  The native handle is not rebuilt between steps; it is refreshed once at the
     end, so that ``generate`` and ``nll`` see the new weights.
+
+    ``scheduler``: None or a factory called with the optimizer; it is stepped after EVERY step, as the reference's trainer steps its
+    ``MultiStepLR`` (``vocoder.py:102-105``).  ``opt_state``: as for ``fit_predictors`` (step i takes bucket
+    ``(steps_done + i) mod n``).
 
     Returns ``losses`` (per step, before that step's update), ``steps``, ``batches`` and ``utterances`` (those with at least one
     sample to score)."""
@@ -595,15 +635,21 @@ def fit_vocoder(encoder: Encoder, vocoder: Vocoder, waves_or_mels, audio, speake
     if not any(p.requires_grad for p in params):
         raise ValueError("fit_vocoder: no parameter of " + (" / ".join(train) if train != ("ar",) else "vocoder.rnnms.ar") + " requires a gradient")
     opt = optimizer(params, lr=lr)
+    sched, done = _resume(opt, scheduler, opt_state)
     for step in range(steps):
-        a, z, spk, lengths, ncs = batches[step % len(batches)]
+        a, z, spk, lengths, ncs = batches[(done + step) % len(batches)]
         opt.zero_grad(set_to_none=True)
         with torch.enable_grad():
             loss = vocoder.nll(a, z, spk, lengths=lengths, n_codes=ncs, differentiable=True, train=train).loss
             loss.backward()
         opt.step()
+        if sched is not None:
+            sched.step()
+        if opt_state is not None:
+            opt_state["steps_done"] = done + step + 1
         res["losses"].append(float(loss.detach()))
         res["steps"] = step + 1
+    _keep(opt, sched, opt_state)
     vocoder.refresh()
     return res
 

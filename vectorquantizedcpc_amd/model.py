@@ -502,7 +502,7 @@ class CPCLoss(_lib.NativeModule):
     inputs give equal bits.  That is what ``driver.fit_predictors`` refits the predictors with on a frozen encoder, and what
     ``driver.fit_context`` hands to ``Encoder.context(z, differentiable=True)`` to refit the context LSTM with them; in
     ``driver.fit_encoder`` ``dz`` goes on through ``Encoder.quantize`` and ``Encoder.front_end`` down to ``conv.weight``.  The
-    optimizer is torch's.
+    optimizer is torch's by default; ``optim.Adam`` makes the update one ``vqcpc_adam_step`` call.
 
     All ``n_prediction_steps`` predictors are held (the reference's 24 ``state_dict()`` keys, so
     ``load_state_dict(checkpoint["cpc"])`` works unchanged); like the reference only the first half is ever used
