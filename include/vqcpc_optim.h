@@ -29,6 +29,9 @@
  *
  * (beta^t is the C library's pow(beta, (double)t).)  Equal inputs give equal bits, whatever the list's split into launches.
  * Denormal g * g or v are outside the contract: keep |g| >= 1e-15 or exactly 0.
+ * An element whose g * g overflows (|g| above about 1.8e19), or whose g is infinite or NaN, follows IEEE arithmetic in the stated
+ * order: an overflow freezes that element's p -- v' = inf, so d = inf and m' / d = 0 -- for as long as its exp_avg_sq stays
+ * infinite; an infinite or NaN g makes its p NaN.  No other element of the call is affected.  Nothing is detected or reported.
  */
 #ifndef VQCPC_OPTIM_H
 #define VQCPC_OPTIM_H

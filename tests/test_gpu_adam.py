@@ -14,13 +14,10 @@ import pytest
 import torch
 
 import adam_ref as R
+from adam_ref import arena_case, bits, hyper                       # the arena of canaries: shared with tests/test_gpu_adam_wide.py
 from vectorquantizedcpc_amd import _lib, optim
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).reshape(-1).view(np.uint32)
 
 
 # ------------------------------------------------------------------ 1. the kernel's bits are the restatement's; 2. the judge
@@ -82,63 +79,6 @@ def test_all_zero_gradient_on_a_cold_state_changes_no_bit():
 
 
 # ------------------------------------------------------------------ 4. canaries; 5. refused calls
-CANARY = 64
-PATTERN = 0x7FA5C3E1          # a NaN payload: arithmetic on it would not give it back
-
-
-class Arena:
-    """One device allocation; ``take(a)`` carves a copy of the fp32 array ``a`` at the next 16-byte offset, with ``CANARY`` floats
-    of ``PATTERN`` before and after it."""
-
-    def __init__(self, arrays):
-        words = sum(2 * CANARY + (a.size + 3) // 4 * 4 for a in arrays)
-        self.host = np.full(words, PATTERN, np.uint32)
-        self.spans, at = [], 0
-        for a in arrays:
-            at += CANARY
-            self.host[at:at + a.size] = a.view(np.uint32)
-            self.spans.append((at, a.size))
-            at += (a.size + 3) // 4 * 4 + CANARY
-        assert at == words
-        self.dev = torch.from_numpy(self.host.view(np.int32)).cuda()
-        assert self.dev.data_ptr() % 16 == 0
-
-    def ptr(self, i):
-        assert (self.spans[i][0] * 4) % 16 == 0
-        return self.dev.data_ptr() + 4 * self.spans[i][0]
-
-    def read(self):
-        return self.dev.cpu().numpy().view(np.uint32)
-
-    def array(self, words, i):
-        at, n = self.spans[i]
-        return words[at:at + n].view(np.float32)
-
-    def canaries_intact(self, words):
-        mask = np.ones(words.size, bool)
-        for at, n in self.spans:
-            mask[at:at + n] = False
-        return bool((words[mask] == PATTERN).all()) and int(mask.sum()) >= 2 * CANARY * len(self.spans)
-
-
-def arena_case(name, k=1):
-    """The buffers of update ``k`` of a case -- p, g, m, v of every tensor with elements -- in one arena, and the call's table."""
-    ps, (ms, vs), gs = R.params(name), R.start_state(name), R.grads(name, k)
-    arrays = [a for quad in zip(ps, gs, ms, vs) for a in quad if a.size]
-    arena = Arena(arrays)
-    n = len(arrays) // 4
-    table = (_lib.AdamTensor * n)(*[_lib.AdamTensor(arena.ptr(4 * i), arena.ptr(4 * i + 1), arena.ptr(4 * i + 2), arena.ptr(4 * i + 3),
-                                                    arrays[4 * i].size) for i in range(n)])
-    return arena, table, n, arrays
-
-
-def hyper(name, k=1, **kw):
-    c = R.CASES[name]
-    h = dict(lr=c["lr"], beta1=c["betas"][0], beta2=c["betas"][1], eps=c["eps"], step=c["first"] + k - 1)
-    h.update(kw)
-    return _lib.AdamHyper(**h)
-
-
 @pytest.mark.parametrize("name", ["vector_and_tail", "around_a_chunk", "second_launch", "loaded_at_10000"])
 def test_canaries_around_every_buffer_keep_their_bits(name):
     arena, table, n, arrays = arena_case(name)

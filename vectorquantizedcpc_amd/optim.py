@@ -45,7 +45,17 @@ class Adam(torch.optim.Adam):
     whose parameters step together -- every fit of this project -- is one call.  The counts are mirrored on the host and read from
     ``state[p]["step"]`` again only when that tensor has been replaced (``load_state_dict``); the tensors themselves are 0-dim views
     into one buffer per group (values, dtype and device as torch's), so a group that steps together counts with one add.  ``step()`` bumps the parameters'
-    ``_version`` as an in-place torch operator would, so the native handles see the new weights."""
+    ``_version`` as an in-place torch operator would, so the native handles see the new weights.
+
+    What ``step()`` caches per parameter (its checks, its pointers, its count, its row of the group's table) is thrown away, for the
+    whole group, when any of this has changed since the last step for a parameter that has a gradient: the parameter object at
+    its position in ``group["params"]`` (a reorder, a replacement); the length of the group (``add_param_group`` aside, an append);
+    the identity of ``state[p]["step"]``, ``["exp_avg"]`` or ``["exp_avg_sq"]`` (``load_state_dict``, also into an optimizer that
+    has stepped; a state entry assigned by hand); ``data_ptr()`` of the parameter or of either moment (``p.data = ...``,
+    ``.set_()``, ``.to()``).  The group then gets a NEW buffer of counts and every parameter's count is read from its
+    ``state[p]["step"]`` before that tensor is rebound, so parameters that stand at different counts keep them through a reorder.
+    Not looked at between steps: a value written into ``state[p]["step"]`` in place.  A parameter or moment that is not 16-byte
+    aligned (a view that starts inside an allocation) is a ``ValueError`` naming it, before anything is written."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
                  capturable=False, differentiable=False, **kw):
@@ -66,7 +76,7 @@ class Adam(torch.optim.Adam):
 
     def _check(self, group, i, t, what, like=None):
         """``TypeError`` / ``ValueError`` / ``RuntimeError`` naming the tensor if ``t`` (parameter ``i`` of ``group``, its gradient or
-        a moment: ``what``) is not a dense, contiguous float32 tensor on the GPU (of ``like``'s shape and device)."""
+        a moment: ``what``) is not a dense, contiguous, 16-byte aligned float32 tensor on the GPU (of ``like``'s shape and device)."""
         who = what + _name(group, i)
         if t.layout is not torch.strided:
             raise TypeError(f"optim.Adam: {who} is {t.layout}, need a dense tensor")
@@ -76,6 +86,9 @@ class Adam(torch.optim.Adam):
             raise RuntimeError(f"optim.Adam: {who} is on {t.device}: vectorquantizedcpc_amd runs on MI355X only; there is no CPU fallback")
         if not t.is_contiguous():
             raise ValueError(f"optim.Adam: {who} is not contiguous (strides {t.stride()} for shape {tuple(t.shape)})")
+        if t.data_ptr() % 16:
+            raise ValueError(f"optim.Adam: {who} is not 16-byte aligned (data_ptr() % 16 = {t.data_ptr() % 16}): vqcpc_adam_step reads "
+                             "and writes 16-byte vectors, so a view that starts inside an allocation needs a copy of its own")
         if like is not None and (t.shape != like.shape or t.device != like.device):
             raise ValueError(f"optim.Adam: {who} has shape {tuple(t.shape)} on {t.device}, the parameter {tuple(like.shape)} on {like.device}")
 
@@ -83,7 +96,10 @@ class Adam(torch.optim.Adam):
         """The cached row of parameter ``i`` of ``group``: the parameter and its state checked, the state made at its first update as
         torch makes it, the update count read from ``state[p]["step"]``, and row ``i`` of the group's table filled (all but the
         gradient).  ``state[p]["step"]`` becomes element ``i`` of the group's one buffer of counts (a 0-dim view, the value kept), so
-        that a group that steps together counts with one add.  -> [p, step, count, exp_avg, exp_avg_sq, p's pointer, device, slots, i]."""
+        that a group that steps together counts with one add.  ``slots`` must be a buffer no live ``state[q]["step"]`` views yet
+        (``step()`` makes a new one before it rebuilds a row): writing element ``i`` of a buffer in use would overwrite the count of
+        the parameter that stood at ``i`` before.
+        -> [p, step, count, exp_avg, exp_avg_sq, p's pointer, device, slots, i, exp_avg's pointer, exp_avg_sq's pointer]."""
         self._check(group, i, p, "")
         if len(st) == 0:
             st["step"] = torch.tensor(0.0, dtype=_get_scalar_dtype())
@@ -96,9 +112,39 @@ class Adam(torch.optim.Adam):
         count = float(st["step"])
         st["step"] = counts[i]
         st["step"].fill_(count)
-        t = table[i]
-        t.param, t.exp_avg, t.exp_avg_sq, t.numel = p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-        return [p, st["step"], int(round(count)), m, v, p.data_ptr(), p.device, slots, i]
+        t, at = table[i], (p.data_ptr(), m.data_ptr(), v.data_ptr())
+        t.param, t.exp_avg, t.exp_avg_sq, t.numel = *at, p.numel()
+        return [p, st["step"], int(round(count)), m, v, at[0], p.device, slots, i, at[1], at[2]]
+
+    def _rows(self, group, slots, cache, fresh):
+        """The rows of the parameters of ``group`` that have a gradient, by the number of the update they take, in group order, with
+        the gradients' pointers written into the group's table.  A row is rebuilt (``_row``) when anything it cached has moved: the
+        parameter object, its slot, the group's ``slots``, the identity of one of the three state tensors, or the storage
+        (``data_ptr()``) of the parameter or of a moment.  Rows are rebuilt only into ``fresh`` slots; otherwise the first stale row
+        ends the scan -> None, and ``step()`` scans again with new slots, which makes every row of the group stale."""
+        params, state, table = group["params"], self.state, slots[1]
+        f32, strided = torch.float32, torch.strided
+        by_count = {}
+        for i, p in enumerate(params):
+            g = p.grad
+            if g is None:
+                continue
+            st, row = state[p], cache.get(id(p))
+            if (row is None or row[0] is not p or row[7] is not slots or row[8] != i or row[1] is not st.get("step")
+                    or row[3] is not st.get("exp_avg") or row[4] is not st.get("exp_avg_sq") or row[5] != p.data_ptr()
+                    or row[9] != row[3].data_ptr() or row[10] != row[4].data_ptr()):
+                if not fresh:
+                    return None
+                row = cache[id(p)] = self._row(group, i, p, st, slots)
+            if g.dtype is not f32 or g.layout is not strided or g.device != row[6] or not g.is_contiguous() or g.shape != p.shape:
+                self._check(group, i, g, "the gradient of ", p)
+            table[i].grad = g.data_ptr()
+            count = row[2] + 1
+            if count in by_count:
+                by_count[count].append(row)
+            else:
+                by_count[count] = [row]
+        return by_count
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -108,31 +154,17 @@ class Adam(torch.optim.Adam):
                 loss = closure()
         cache = self.__dict__.setdefault("_hip_rows", {})        # id(p) -> _row: checked once, again when the parameter or its state moved
         groups = self.__dict__.setdefault("_hip_groups", {})     # group index -> (its buffer of counts, its table)
-        state, f32, strided = self.state, torch.float32, torch.strided
         for gi, group in enumerate(self.param_groups):
             self._reject(group)
             params = group["params"]
             slots = groups.get(gi)
-            if slots is None or len(slots[1]) != len(params):
+            by_count = None
+            if slots is not None and len(slots[1]) == len(params):
+                by_count = self._rows(group, slots, cache, False)
+            if by_count is None:                                 # the first step, another group length, or a stale row: new slots
                 slots = groups[gi] = (torch.zeros(len(params), dtype=_get_scalar_dtype()), (_lib.AdamTensor * max(len(params), 1))())
+                by_count = self._rows(group, slots, cache, True)
             table = slots[1]
-            by_count = {}                                        # the update's number -> rows, in group order
-            for i, p in enumerate(params):
-                g = p.grad
-                if g is None:
-                    continue
-                st, row = state[p], cache.get(id(p))
-                if (row is None or row[0] is not p or row[7] is not slots or row[8] != i or row[1] is not st.get("step")
-                        or row[3] is not st.get("exp_avg") or row[4] is not st.get("exp_avg_sq") or row[5] != p.data_ptr()):
-                    row = cache[id(p)] = self._row(group, i, p, st, slots)
-                if g.dtype is not f32 or g.layout is not strided or g.device != row[6] or not g.is_contiguous() or g.shape != p.shape:
-                    self._check(group, i, g, "the gradient of ", p)
-                table[i].grad = g.data_ptr()
-                count = row[2] + 1
-                if count in by_count:
-                    by_count[count].append(row)
-                else:
-                    by_count[count] = [row]
             beta1, beta2 = group["betas"]
             for count, rows in by_count.items():
                 n = len(rows)
