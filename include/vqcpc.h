@@ -164,8 +164,8 @@ int vqcpc_encoder_vq_adapt(vqcpc_encoder *enc, const float *x, int n_rows, doubl
                            float *z_st, int64_t *idx, float *loss, float *perplexity, void *stream);
 
 /* Device memory the handle's grow-only work buffers hold at the moment (front-end activations, statistics, the work space
- * of vqcpc_encoder_vq_adapt, of vqcpc_encoder_context_fwd / _bwd and of the front-end gradients of vqcpc_grad.h: the peak of the
- * calls so far; the weights are not counted). */
+ * of vqcpc_encoder_vq_adapt, of vqcpc_encoder_context_fwd / _bwd and of the front-end gradients (vqcpc_encoder_front_fwd / _bwd):
+ * the peak of the calls so far; the weights are not counted). */
 int vqcpc_encoder_workspace_bytes(vqcpc_encoder *enc, uint64_t *bytes);
 
 /* After the caller has synchronised the stream that carried vqcpc_encoder_encode / _context: did the resident context
@@ -213,6 +213,78 @@ int vqcpc_encoder_context_fwd(vqcpc_encoder *enc, const float *z, int B, int Tz,
 int vqcpc_encoder_context_bwd(vqcpc_encoder *enc, const float *z, int B, int Tz, const float *w_ih, const float *w_hh,
                               const float *c, const void *saved, const float *grad_c, float *grad_z, float *grad_w_ih,
                               float *grad_w_hh, float *grad_bias, void *stream);
+
+/* ------------------------------------------------------------------ Encoder: front-end and VQ gradients ---- */
+
+/* The gradients of the encoder's front end (Conv1d / LayerNorm / Linear, model.py:43-55, :65-67) and of the VQ step's
+ * straight-through estimator (model.py:147-150).  Together with vqcpc_cpc_grad and vqcpc_encoder_context_bwd they are
+ * loss.backward() of the reference's training step (train_cpc.py:116-124), from the loss down to conv.weight.
+ *
+ * Every sum of these entries runs in one fixed order (vectorquantizedcpc_amd/csrc/front_grad.hip states each), without
+ * floating-point atomics: equal inputs give equal bits, whatever an earlier call left in the handle's work space.  That work
+ * space is grow-only and counted by vqcpc_encoder_workspace_bytes. */
+
+/* The front-end part of vqcpc_encoder_weights: DEVICE pointers to the caller's tensors in the reference's shapes, 16-byte
+ * aligned.  conv_weight (channels, in_channels, 4); ln_weight[i], ln_bias[i] (channels) for encoder.{0,3,6,9,12}; fc_weight[i]
+ * (channels, channels) for encoder.{2,5,8,11}; out_weight (z_dim, channels), out_bias (z_dim).  Every member is required.
+ * Where an entry takes `const vqcpc_encoder_front_weights *w`, NULL means the handle's copies; with a struct the handle gives
+ * sizes and work space only, and whatever re-layout a kernel needs (the conv weight's k order, transposes) is made per call,
+ * in stream order -- an optimizer step costs no new handle. */
+typedef struct {
+    const float *conv_weight;
+    const float *ln_weight[5];
+    const float *ln_bias[5];
+    const float *fc_weight[4];
+    const float *out_weight;
+    const float *out_bias;
+} vqcpc_encoder_front_weights;
+
+/* The gradients vqcpc_encoder_front_bwd writes: the members of the weights struct as DEVICE output pointers, same shapes,
+ * 16-byte aligned.  A NULL member is not wanted: its launches are skipped, and the chain of input-gradient products runs only
+ * as far down as the lowest wanted tensor.  Every element of a wanted tensor is written. */
+typedef struct {
+    float *conv_weight;
+    float *ln_weight[5];
+    float *ln_bias[5];
+    float *fc_weight[4];
+    float *out_weight;
+    float *out_bias;
+} vqcpc_encoder_front_grads;
+
+/* Bytes of the `saved` buffer that vqcpc_encoder_front_fwd fills for B utterances of T mel frames (its layout is private).
+ * VQCPC_ERR_INVALID for NULL, B < 1 or T < 2. */
+int vqcpc_encoder_front_saved_bytes(vqcpc_encoder *enc, int B, int T, uint64_t *bytes);
+
+/* The front end of a training step: mel (B, in_channels, T) DEVICE -> z_pre (B, T / 2, z_dim) DEVICE, the rows before the VQ
+ * (model.py:65-67).  z_pre has the bits of vqcpc_encoder_stage(..., stage 10, ...) for the same weights, shape and conv_mode
+ * (the layered schedule: exact-chain GEMMs and ATen's LayerNorm moments).  `saved` (DEVICE, 16-byte aligned,
+ * vqcpc_encoder_front_saved_bytes) receives what the backward reads again: the rows entering each of the five LayerNorms, the
+ * rows leaving each ReLU, and mean and rstd of every row of every LayerNorm exactly as this forward computed them.
+ * w: the caller's weights, or NULL = the handle's copies.
+ * VQCPC_ERR_INVALID before anything is enqueued: a NULL enc, mel, z_pre or saved, B < 1, T < 2, conv_mode outside 0 .. 2, a
+ * NULL member of *w, a pointer that is not 16-byte aligned, more than 2^22 rows, a handle of another device. */
+int vqcpc_encoder_front_fwd(vqcpc_encoder *enc, const float *mel, int B, int T, int conv_mode,
+                            const vqcpc_encoder_front_weights *w, float *z_pre, void *saved, void *stream);
+
+/* The backward of vqcpc_encoder_front_fwd: grad_z_pre (B, T / 2, z_dim) DEVICE = dLoss / dz_pre -> the wanted members of
+ * *grads.  mel, B, T, conv_mode, w, saved: those of the forward call (w's tensors unchanged since).  The ReLU mask is "the
+ * saved post-ReLU value > 0".  There is no gradient with respect to mel.
+ * VQCPC_ERR_INVALID before anything is enqueued: as the forward, a NULL grad_z_pre or grads, or no wanted member. */
+int vqcpc_encoder_front_bwd(vqcpc_encoder *enc, const float *mel, int B, int T, int conv_mode,
+                            const vqcpc_encoder_front_weights *w, const void *saved, const float *grad_z_pre,
+                            const vqcpc_encoder_front_grads *grads, void *stream);
+
+/* The backward of model.py:147-150, loss = 0.25 * mse_loss(z_pre, z_q.detach()) and z_st = z_pre + (z_q - z_pre).detach():
+ *   grad_z_pre = grad_z_st + grad_loss * (0.5 / (n_rows * z_dim)) * (z_pre - z_q)
+ * as separately rounded fp32 operations in this order, per element:
+ *   d = z_pre - z_q;   s = grad_loss * k, k = 0.5 / (n_rows * z_dim) formed in double and rounded to fp32 once;
+ *   t = s * d;         grad_z_pre = grad_z_st + t.
+ * z_pre, z_q, grad_z_st, grad_z_pre (n_rows, z_dim) DEVICE, 16-byte aligned; grad_loss a DEVICE scalar.  grad_loss NULL drops
+ * the loss term: grad_z_pre has the bits of grad_z_st.  grad_z_st NULL drops the straight-through term: grad_z_pre = t.
+ * VQCPC_ERR_INVALID before anything is enqueued: a NULL enc, z_pre, z_q or grad_z_pre, both gradients NULL, n_rows < 1, a
+ * pointer that is not 16-byte aligned, a handle of another device. */
+int vqcpc_encoder_vq_bwd(vqcpc_encoder *enc, const float *z_pre, const float *z_q, int n_rows, const float *grad_z_st,
+                         const float *grad_loss, float *grad_z_pre, void *stream);
 
 /* ------------------------------------------------------------------ CPC scoring ------ */
 
@@ -460,6 +532,176 @@ int vqcpc_vocoder_nll(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *i
                       int B, int Tc, int L, const int *n_codes, const int *n_audio,
                       double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *nll, void *stream);
 
+/* ---- Vocoder gradients: the sample-rate network ---- */
+
+/* The gradients of the vocoder objective (vocoder.py:62-63, F.cross_entropy of the teacher-forced energies of audio[:, :-1]
+ * against audio[:, 1:]) through the sample-rate network rnnms.ar.* -- embedding, GRU, fc1, fc2 -- and with respect to the
+ * conditioning series that feeds it.  The prenet and the two embedding tables in front of it are frozen here: grad_cond is where
+ * their backward (vqcpc_vocoder_cond_bwd) starts.
+ *
+ * Every sum of these entries runs in one fixed order (vectorquantizedcpc_amd/csrc/vocoder_grad.hip states each), without
+ * floating-point atomics: equal inputs give equal bits, whatever an earlier call left in the handle's work space.  That work
+ * space is grow-only and counted by vqcpc_vocoder_workspace_bytes.
+ *
+ * Sizes: those vqcpc_vocoder_nll accepts -- size_h_fc 256, 256 classes, size_h_rnn 512, 896 or 1024, any size_i_embed_ar,
+ * dim_voc_latent and upsampling_t vqcpc_vocoder_create accepts.  Below: n_cls = 256, Hf = 256, Hr = size_h_rnn,
+ * de = size_i_embed_ar, C = dim_voc_latent. */
+
+/* DEVICE pointers to the caller's nine tensors of rnnms.ar in the reference's shapes, fp32, 16-byte aligned: embedding (n_cls, de);
+ * w_ih (3 Hr, de + C), w_hh (3 Hr, Hr), b_ih, b_hh (3 Hr), gate order r, z, n; fc1_weight (Hf, Hr), fc1_bias (Hf); fc2_weight
+ * (n_cls, Hf), fc2_bias (n_cls).  Every member is required.  Where an entry takes `const vqcpc_vocoder_ar_weights *w`, NULL means
+ * the handle's copies; with a struct the handle gives sizes, the frozen conditioning path (code and speaker embedding, prenet) and
+ * work space only, and whatever re-layout the scan kernels need (the per-class and per-frame tables of the gates' input half, the
+ * W_hh fragments) is made per call, in stream order, into work space the handle owns -- an optimizer step costs no new handle. */
+typedef struct {
+    const float *embedding;
+    const float *w_ih;
+    const float *w_hh;
+    const float *b_ih;
+    const float *b_hh;
+    const float *fc1_weight;
+    const float *fc1_bias;
+    const float *fc2_weight;
+    const float *fc2_bias;
+} vqcpc_vocoder_ar_weights;
+
+/* The gradients vqcpc_vocoder_ar_bwd writes: the members of the weights struct as DEVICE output pointers, same shapes, 16-byte
+ * aligned.  A NULL member is not wanted and its launches are skipped.  Every element of a wanted tensor is written.  b_ih and b_hh
+ * are both outputs: their gradients differ in the n third, where r multiplies the hidden half only. */
+typedef struct {
+    float *embedding;
+    float *w_ih;
+    float *w_hh;
+    float *b_ih;
+    float *b_hh;
+    float *fc1_weight;
+    float *fc1_bias;
+    float *fc2_weight;
+    float *fc2_bias;
+} vqcpc_vocoder_ar_grads;
+
+/* Bytes of the `saved` buffer that vqcpc_vocoder_ar_fwd fills for B utterances of L samples (its layout is private).
+ * VQCPC_ERR_INVALID for NULL, B < 1 or L < 1, or a model the scoring head is not built for. */
+int vqcpc_vocoder_ar_saved_bytes(vqcpc_vocoder *voc, int B, int L, uint64_t *bytes);
+
+/* The forward of a training step.  audio, idx, speaker, B, Tc, L, n_codes, n_audio, nll_sum, n_scored, n_correct: those of
+ * vqcpc_vocoder_nll, with its meaning and its conditions.  It is the same scan and the same head: with w == NULL the three
+ * outputs have the bits of vqcpc_vocoder_nll for the same inputs, with a struct the bits of a handle created from those weights.
+ * cond (B, 2 Tc, C) DEVICE fp32 or NULL: receives the conditioning rows the scan used (the prenet's output; rows past an
+ * utterance's 2 n_codes[b] frames are +0).  saved (DEVICE, 16-byte aligned, vqcpc_vocoder_ar_saved_bytes) receives h_t of every
+ * scored step.
+ * Behind the valid data nothing is read, here and in the backward: of audio[b, :] the elements [0, n_audio[b]) where n_audio[b] >= 2
+ * and none otherwise (step t < n_audio[b] - 1 is fed audio[b, t] and scored against audio[b, t + 1]), of idx[b, :] the elements
+ * [0, n_codes[b]).  Whatever lies behind them -- a class or a code index outside its table included -- changes no bit of any output
+ * and is not reported by vqcpc_vocoder_check.
+ * VQCPC_ERR_INVALID before anything is enqueued: the NULL and range conditions of vqcpc_vocoder_nll, a NULL saved, a NULL member
+ * of *w, a pointer that is not 16-byte aligned, a handle of another device. */
+int vqcpc_vocoder_ar_fwd(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                         int L, const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, double *nll_sum,
+                         int64_t *n_scored, int64_t *n_correct, float *cond, void *saved, void *stream);
+
+/* The backward of vqcpc_vocoder_ar_fwd for the scalar loss = sum_b nll_sum[b] / N, N = sum_b max(n_audio[b] - 1, 0): the mean
+ * over every scored sample of the batch (with equal lengths exactly F.cross_entropy's mean).  audio .. n_audio, w, saved: those
+ * of the forward call (w's tensors unchanged since).  grad_loss: DEVICE fp32 scalar dL / dloss, NULL = 1.  1 / N is formed in
+ * double on the host and rounded to fp32 once; the per-sample factor is s = grad_loss * (float)(1 / N).
+ * grads: the wanted members receive dL / d(weight).  grad_cond (B, 2 Tc, C) DEVICE or NULL: dL / dcond; rows of frames that no
+ * scored step of their utterance reads are +0.  Rows of grads->embedding for classes never fed are +0.
+ * An utterance with n_audio[b] <= 1 contributes nothing.  The back-propagation through time of utterance b starts at its own last
+ * scored step with dh = 0: a ragged batch equals its utterances run one at a time, in value.
+ * VQCPC_ERR_INVALID before anything is enqueued: as the forward; N == 0; grads == NULL or without a wanted member while grad_cond
+ * is NULL too. */
+int vqcpc_vocoder_ar_bwd(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                         int L, const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w, const void *saved,
+                         const float *grad_loss, const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream);
+
+/* vqcpc_vocoder_ar_fwd and vqcpc_vocoder_ar_bwd with the conditioning series given: cond_in (B, T2, C) DEVICE, rows past an
+ * utterance's frames not read.  The scan and the backward take their conditioning rows from it and do not run the prenet (idx and
+ * speaker are not read); everything else is the statements of the two entries.  Given cond_in from
+ * vqcpc_vocoder_cond_fwd with cw == NULL, every output -- the nine gradients and grad_cond among them -- has the bits of
+ * vqcpc_vocoder_ar_fwd / _bwd.  VQCPC_ERR_INVALID: as those entries; a NULL or misaligned cond_in. */
+int vqcpc_vocoder_ar_fwd_cond(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                              int L, const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w,
+                              const float *cond_in, double *nll_sum, int64_t *n_scored, int64_t *n_correct, float *cond,
+                              void *saved, void *stream);
+int vqcpc_vocoder_ar_bwd_cond(vqcpc_vocoder *voc, const int64_t *audio, const int64_t *idx, const int64_t *speaker, int B, int Tc,
+                              int L, const int *n_codes, const int *n_audio, const vqcpc_vocoder_ar_weights *w,
+                              const float *cond_in, const void *saved, const float *grad_loss,
+                              const vqcpc_vocoder_ar_grads *grads, float *grad_cond, void *stream);
+
+/* ---- Vocoder gradients: the conditioning path ---- */
+
+/* The gradients of the vocoder's conditioning path (network_vocoder.py:73-77 and rnnms.prenet: code_embedding,
+ * speaker_embedding, the repeat of every code over two frames, the two bidirectional GRU layers) with respect to its eighteen
+ * tensors, from any upstream gradient of the conditioning series -- vqcpc_vocoder_ar_bwd's grad_cond is one.  With the *_cond
+ * forms of the scoring entries above, a step of the reference's vocoder trainer (vocoder.py:62-63) is vqcpc_vocoder_* calls from
+ * the loss down to code_embedding.weight.
+ *
+ * Every DEVICE pointer of these entries is fp32 and 16-byte aligned, and VQCPC_ERR_INVALID is returned before anything is
+ * enqueued.
+ *
+ * Every sum of these entries runs in one fixed order (vectorquantizedcpc_amd/csrc/prenet_grad.hip states each), without
+ * floating-point atomics: equal inputs give equal bits, whatever an earlier call left in the handle's work space.  That work
+ * space is grow-only and counted by vqcpc_vocoder_workspace_bytes.
+ *
+ * Below (and in the *_cond entries above): dz, ds = the two embedding widths, F = dz + ds, Hp = dim_voc_latent / 2, C = 2 Hp,
+ * T2 = 2 Tc frames. */
+
+/* DEVICE pointers to the caller's eighteen tensors of the conditioning path in the reference's shapes: code_embedding
+ * (n_codes, dz), speaker_embedding (n_speakers, ds); of layer l and direction d (0 forward, 1 reverse) prenet_w_ih[l][d]
+ * (3 Hp, F for l = 0, C for l = 1), prenet_w_hh[l][d] (3 Hp, Hp), prenet_b_ih[l][d], prenet_b_hh[l][d] (3 Hp), gate order
+ * r, z, n.  Every member is required.  Where an entry takes `const vqcpc_vocoder_cond_weights *cw`, NULL means the handle's
+ * copies; with a struct the handle gives sizes and work space only, and the stacked w_ih / b_ih / b_hh and the W_hh fragments
+ * the scan reads are made per call, in stream order, into work space the handle owns -- an optimizer step costs no new handle. */
+typedef struct {
+    const float *code_embedding;
+    const float *speaker_embedding;
+    const float *prenet_w_ih[2][2];
+    const float *prenet_w_hh[2][2];
+    const float *prenet_b_ih[2][2];
+    const float *prenet_b_hh[2][2];
+} vqcpc_vocoder_cond_weights;
+
+/* The gradients vqcpc_vocoder_cond_bwd writes: the same members as DEVICE output pointers, same shapes.  A NULL member is not
+ * wanted and its launches are skipped.  Every element of a wanted tensor is written; rows of the two tables that the batch
+ * never names are +0. */
+typedef struct {
+    float *code_embedding;
+    float *speaker_embedding;
+    float *prenet_w_ih[2][2];
+    float *prenet_w_hh[2][2];
+    float *prenet_b_ih[2][2];
+    float *prenet_b_hh[2][2];
+} vqcpc_vocoder_cond_grads;
+
+/* Bytes of the `saved` buffer that vqcpc_vocoder_cond_fwd fills for B utterances of Tc codes (its layout is private).
+ * VQCPC_ERR_INVALID for NULL, B < 1 or Tc < 1. */
+int vqcpc_vocoder_cond_saved_bytes(vqcpc_vocoder *voc, int B, int Tc, uint64_t *bytes);
+
+/* The conditioning series of a training step: glue, prenet layer 0, prenet layer 1 -- the statements of
+ * vqcpc_vocoder_condition.  idx (B, Tc) and speaker (B) DEVICE int64; n_codes: HOST, valid codes per utterance in [0, Tc], NULL =
+ * Tc.  cond (B, T2, C) DEVICE receives the series; rows past an utterance's 2 n_codes[b] frames are +0.  With cw == NULL its bits
+ * equal vqcpc_vocoder_condition's (n_codes NULL) and the cond output of vqcpc_vocoder_ar_fwd; with a struct the bits of a handle
+ * created from those tensors.  saved (DEVICE, 16-byte aligned, vqcpc_vocoder_cond_saved_bytes) receives what the backward reads
+ * again: the glued series and both layers' outputs, over the utterances' own frames.  An index outside its table is clamped for
+ * the read and reported by vqcpc_vocoder_check.  Of idx[b, :] the forward and the backward read the elements [0, n_codes[b]) and
+ * nothing behind them: an index there, inside its table or not, changes no bit of any output and is not reported.
+ * VQCPC_ERR_INVALID before anything is enqueued: a NULL argument (cw excepted), a NULL member of *cw, a pointer that is not
+ * 16-byte aligned, B < 1 or Tc < 1, n_codes[b] outside [0, Tc], a handle of another device. */
+int vqcpc_vocoder_cond_fwd(vqcpc_vocoder *voc, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes,
+                           const vqcpc_vocoder_cond_weights *cw, float *cond, void *saved, void *stream);
+
+/* The backward of vqcpc_vocoder_cond_fwd for L = sum(cond * grad_cond) over the utterances' own frames.  idx .. cw, saved: those
+ * of the forward call (cw's tensors unchanged since).  grad_cond (B, T2, C) DEVICE: any upstream gradient; rows past an
+ * utterance's frames are not read.  The wanted members of *grads receive dL / d(tensor).  The back-propagation through time of
+ * utterance b runs over its own 2 n_codes[b] frames, each direction from its own last step with dh = 0: a ragged batch equals
+ * its utterances run one at a time, in value.
+ * VQCPC_ERR_INVALID before anything is enqueued: as the forward; grads NULL or without a wanted member. */
+int vqcpc_vocoder_cond_bwd(vqcpc_vocoder *voc, const int64_t *idx, const int64_t *speaker, int B, int Tc, const int *n_codes,
+                           const vqcpc_vocoder_cond_weights *cw, const void *saved, const float *grad_cond,
+                           const vqcpc_vocoder_cond_grads *grads, void *stream);
+
+/* ---- Vocoder: stage outputs, options, status ---- */
+
 /* The wrapper's own glue alone (network_vocoder.py:73-77 / :56-66): series DEVICE (B, 2*Tc, dz + ds) = what the reference's
  * Vocoder.generate / Vocoder.forward hand to rnnms -- [:, :, :dz] the code embedding of code t/2, [:, :, dz:] the speaker
  * embedding.  The same kernel vqcpc_vocoder_generate / _logits / _condition run first; exposed so that it can be checked
@@ -613,6 +855,58 @@ int vqcpc_loudness_normalize(vqcpc_loudness *m, float *wav, const int *lens, int
  * fc2 as a launch of its own, for reference}.
  * Each time includes this chip's ~1.5 us dependent-launch boundary. */
 int vqcpc_vocoder_kernel_times(vqcpc_vocoder *voc, int reps, float *out_us, void *stream);
+
+/* ------------------------------------------------------------------ Optimizer step ---- */
+
+/* The parameter update.  With the gradient entries above, a training step of either reference trainer (train_cpc.py:116-124,
+ * vocoder.py:62-63) is vqcpc_* calls from the loss to the new parameters: the gradients come from the *_bwd / *_grad entries,
+ * vqcpc_adam_step applies them.
+ *
+ * DEVICE pointers are fp32 and 16-byte aligned, and VQCPC_ERR_INVALID is returned before anything is enqueued.  There is no
+ * handle: the entry allocates nothing, keeps nothing and copies nothing to the device -- the table of tensors travels in the
+ * kernel arguments.
+ *
+ * The update is Adam as torch.optim.Adam runs it with its defaults (no weight decay, no amsgrad, no maximize), in ONE stated
+ * order of fp32 operations.  Per element, with g the gradient, m = exp_avg, v = exp_avg_sq, p the parameter:
+ *
+ *     m' = m + (g - m) * w1
+ *     v' = v * c2 + (g * g) * w2
+ *     d  = sqrt(v') / rb + e
+ *     p' = p - ss * (m' / d)
+ *
+ * Every operation is one IEEE fp32 operation rounded to nearest even, once; nothing is contracted into a fused multiply-add; the
+ * square root and the two divisions are the correctly rounded ones.  The six scalars are formed in double on the host from the
+ * hyper-parameters of update number t = step and rounded to fp32 once each:
+ *
+ *     w1 = 1 - beta1      c2 = beta2      w2 = 1 - beta2      rb = sqrt(1 - beta2^t)      e = eps      ss = lr / (1 - beta1^t)
+ *
+ * (beta^t is the C library's pow(beta, (double)t).)  Equal inputs give equal bits, whatever the list's split into launches.
+ * Denormal g * g or v are outside the contract: keep |g| >= 1e-15 or exactly 0.
+ * An element whose g * g overflows (|g| above about 1.8e19), or whose g is infinite or NaN, follows IEEE arithmetic in the stated
+ * order: an overflow freezes that element's p -- v' = inf, so d = inf and m' / d = 0 -- for as long as its exp_avg_sq stays
+ * infinite; an infinite or NaN g makes its p NaN.  No other element of the call is affected.  Nothing is detected or reported. */
+
+/* One tensor of the update: four DEVICE buffers of numel fp32 elements each.  param, exp_avg and exp_avg_sq are read and
+ * written, grad is read.  With numel == 0 the tensor is skipped and its pointers are not looked at.  The buffers of one call
+ * must not overlap, neither within a tensor nor between tensors: every element is read and written by exactly one thread of one
+ * launch, and nothing orders two tensors of a call. */
+typedef struct { float *param; const float *grad; float *exp_avg; float *exp_avg_sq; uint64_t numel; } vqcpc_adam_tensor;
+
+/* The hyper-parameters of one update.  step: the number of THIS update, >= 1 (the first update of a fresh state is 1). */
+typedef struct { double lr, beta1, beta2, eps; int64_t step; } vqcpc_adam_hyper;
+
+/* Tensors one launch covers (the four pointers, numel and a chunk prefix per tensor, by value, within the 4 KiB of kernel
+ * arguments), and the elements one workgroup covers.  A list of n tensors takes ceil(n / VQCPC_ADAM_TABLE) launches, in list
+ * order; a workgroup finds its tensor by searching the chunk prefix. */
+#define VQCPC_ADAM_TABLE 72
+#define VQCPC_ADAM_CHUNK 4096
+
+/* One Adam update of n_tensors tensors with the hyper-parameters *h, as stated at the head of this section.  tensors and h are
+ * HOST memory, read before the call returns.  Enqueues ceil(n_tensors / VQCPC_ADAM_TABLE) launches on `stream` and nothing else.
+ * VQCPC_ERR_INVALID before anything is enqueued: tensors or h NULL; n_tensors < 1; a NULL or not 16-byte aligned member of a
+ * tensor with numel > 0; step < 1; lr or eps not finite or negative; a beta outside [0, 1); memory of the first tensor with
+ * numel > 0 that does not belong to the current device.  VQCPC_ERR_NO_DEVICE: the current device is not a gfx950. */
+int vqcpc_adam_step(const vqcpc_adam_tensor *tensors, int n_tensors, const vqcpc_adam_hyper *h, void *stream);
 
 #ifdef __cplusplus
 }

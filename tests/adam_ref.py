@@ -1,5 +1,5 @@
 """Shared by tests/test_adam_cpu.py, test_adam_wide_cpu.py, test_gpu_adam.py and test_gpu_adam_wide.py (plain module, not a
-conftest): the numpy fp32 restatement of the update ``include/vqcpc_optim.h`` states, the cases, the float64 / fp32
+conftest): the numpy fp32 restatement of the update ``include/vqcpc.h`` states, the cases, the float64 / fp32
 ``torch.optim.Adam`` runs on the CPU that judge it, and the arena of canaries the GPU tests carve a call's buffers from.
 
 The restatement (``scalars``, ``update``): every operation one numpy float32 operation -- correctly rounded, never fused -- in the

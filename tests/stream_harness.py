@@ -253,11 +253,11 @@ def hold(entry, inputs, decoy, **kw):
     return run(entry, inputs, decoy, **kw).verify()
 
 
-# ------------------------------------------------------------------- what every file that keeps a header's table does with it
-def check_entries_listed(header, entries, doc):
-    """The entries of ``include/<header>`` that take a ``stream`` are exactly ``entries`` (name -> how), and each has its row in the
+# ------------------------------------------------------------------- what the file that keeps the header's table does with it
+def check_entries_listed(entries, doc):
+    """The entries of ``include/vqcpc.h`` that take a ``stream`` are exactly ``entries`` (name -> how), and each has its row in the
     table of ``doc``, the test file's docstring.  Returns the names found in the header."""
-    text = open(os.path.join(ROOT, "include", header)).read()
+    text = open(os.path.join(ROOT, "include", "vqcpc.h")).read()
     found = set(re.findall(r"\bint\s+(vqcpc_\w+)\s*\([^;{]*?void\s*\*\s*stream\b[^;{]*?\)\s*;", text))
     assert found == set(entries), (sorted(found - set(entries)), sorted(set(entries) - found))
     for name, how in entries.items():

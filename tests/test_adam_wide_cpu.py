@@ -1,4 +1,4 @@
-"""What holds of the ``WIDE`` cases of tests/adam_ref.py without a GPU: the numpy restatement of ``include/vqcpc_optim.h``'s order is
+"""What holds of the ``WIDE`` cases of tests/adam_ref.py without a GPU: the numpy restatement of ``include/vqcpc.h``'s order is
 within the project's judge of ``torch.optim.Adam`` in float64 on every one of them (the ladders per tensor), and the cases hold
 what they were written to hold -- a full table of mixed sizes, a second launch behind empty tensors with a tensor of several
 chunks in it, every loop count and tail length of a last chunk, gradients from the contract's floor to the largest whose square is

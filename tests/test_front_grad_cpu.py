@@ -1,21 +1,14 @@
 """CPU side of the front-end gradients: the pins hold the float64 reference, two fp32 numpy restatements (the kernels' documented
 orders, and other orders) pass the judge of tests/front_grad_ref.py -- the fifteen cases and the fourteen ``WIDE_CASES`` -- eight
-seeded faults do not, the second header is plain C99 and
-its symbols are exported and bound, and ``fit_encoder`` / ``cli fit-encoder`` check their arguments before any GPU is needed."""
-import ctypes
-import os
-import re
-import subprocess
-
+seeded faults do not, and ``fit_encoder`` / ``cli fit-encoder`` check their arguments before any GPU is needed."""
 import numpy as np
 import pytest
 import torch
 
 import front_grad_ref as R
 import grad_judge
-from vectorquantizedcpc_amd import _lib, cli, driver
+from vectorquantizedcpc_amd import cli, driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [n for n in R.SMALL_CASES if not n.endswith(("_m1", "_m2"))]
 
 
@@ -109,53 +102,6 @@ def test_vq_bwd_formula_is_the_autograd_of_the_reference_lines():
     ((z_st * gs).sum() + 3.0 * loss).backward()
     want = R.vq_bwd64(x.detach().numpy(), q.numpy(), gs.numpy(), 3.0)
     assert np.abs(x.grad.numpy() - want).max() <= 1e-14
-
-
-# ------------------------------------------------------------------ the header
-def declared():
-    text = open(os.path.join(ROOT, "include", "vqcpc_grad.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vqcpc_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound():
-    """``_lib.SYMBOLS`` is pinned to include/vqcpc.h by tests/test_abi_cpu.py; the second header's list is ``_lib.GRAD_SYMBOLS``."""
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    names = declared()
-    assert len(names) == 4
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/vqcpc_grad.h but not exported"
-        assert getattr(_lib.load(), n).argtypes is not None, n
-    assert sorted(_lib.GRAD_SYMBOLS) == names
-    assert not set(_lib.GRAD_SYMBOLS) & set(_lib.SYMBOLS)
-
-
-def test_header_is_plain_c(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('''#include "vqcpc_grad.h"
-#include <stddef.h>
-int use(vqcpc_encoder *enc, float *p, void *saved, void *s) {
-    vqcpc_encoder_front_weights w;
-    vqcpc_encoder_front_grads g;
-    uint64_t n = 0;
-    int rc = vqcpc_encoder_front_saved_bytes(enc, 1, 32, &n);
-    w.conv_weight = p; g.conv_weight = p; w.ln_weight[4] = p; g.ln_bias[0] = NULL;
-    rc |= vqcpc_encoder_front_fwd(enc, p, 1, 32, VQCPC_CONV_AUTO, &w, p, saved, s);
-    rc |= vqcpc_encoder_front_fwd(enc, p, 1, 32, VQCPC_CONV_AUTO, NULL, p, saved, s);
-    rc |= vqcpc_encoder_front_bwd(enc, p, 1, 32, VQCPC_CONV_AUTO, &w, saved, p, &g, s);
-    rc |= vqcpc_encoder_vq_bwd(enc, p, p, 16, p, NULL, p, s);
-    return rc;
-}
-''')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only",
-                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_front_tensors_struct_mirrors_the_header():
-    fields = [n for n, _ in _lib.EncoderFrontTensors._fields_]
-    assert fields == ["conv_weight", "ln_weight", "ln_bias", "fc_weight", "out_weight", "out_bias"]
-    assert ctypes.sizeof(_lib.EncoderFrontTensors) == 17 * ctypes.sizeof(ctypes.c_void_p)
 
 
 # ------------------------------------------------------------------ argument checks that need no GPU

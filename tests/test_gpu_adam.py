@@ -1,5 +1,5 @@
 """-m gpu: ``vqcpc_adam_step`` (``csrc/optim.hip``) through ``optim.Adam`` -- its bits against the numpy restatement of
-``include/vqcpc_optim.h``'s order after every update of every case of tests/adam_ref.py, the same outputs against
+``include/vqcpc.h``'s order after every update of every case of tests/adam_ref.py, the same outputs against
 ``torch.optim.Adam`` in float64 by the project's judge, what must stay untouched (a parameter without a gradient, a cold state under
 an all-zero gradient, canaries around every buffer, every buffer after a refused call), state dicts moving between the two
 optimizers, and one library call per ``step()`` per param group.

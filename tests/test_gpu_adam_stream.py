@@ -1,18 +1,11 @@
-"""-m gpu: the entry of ``include/vqcpc_optim.h`` on a caller's stream -- the stream contract of ``include/vqcpc.h`` (*all work is
-enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly as the entries of the first four headers
-are held.  This file keeps the table of the fifth header:
+"""-m gpu: ``vqcpc_adam_step`` on a caller's stream -- the stream contract of ``include/vqcpc.h`` (*all work is enqueued on `stream`;
+no call synchronises*), held with tests/stream_harness.py exactly as tests/test_gpu_stream_contract.py holds the other entries.
+That file keeps the one table of entries against the header; its row names the test here.
 
-  ==================================  ===  ====================================================================================
-  entry                               how  held by
-  ==================================  ===  ====================================================================================
-  vqcpc_adam_step                     N    test_adam_step_on_a_callers_stream
-  ==================================  ===  ====================================================================================
-
-N: does not synchronise (``busy`` is asserted).  The parameters, the gradients and both moments of every tensor are among the
+Does not synchronise (``busy`` is asserted).  The parameters, the gradients and both moments of every tensor are among the
 buffers written behind the delay: an update enqueued anywhere but on the caller's stream reads the decoy, and one still running
 when the call returns is overtaken by the harness's clones.  The list is longer than one launch's table, so the second launch is
-held too.  ``test_every_stream_entry_is_listed`` reads the header with ``stream_harness.check_entries_listed`` and fails when an
-entry with a ``stream`` argument is missing above.
+held too.
 """
 import numpy as np
 import pytest
@@ -24,7 +17,6 @@ from vectorquantizedcpc_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-ENTRIES = {"vqcpc_adam_step": "N"}
 SIZES = [R.CHUNK + 1, 5, 2 * R.CHUNK + 3] + [3 + i % 4 for i in range(R.TABLE)]       # TABLE + 3 tensors: two launches
 
 
@@ -33,10 +25,6 @@ def release_what_this_file_holds():
     """The device buffers of this file are released when it is done, and the stream harness's session-wide delay chain and report
     are left as they were found (``stream_harness.release_after`` says why)."""
     yield from H.release_after()
-
-
-def test_every_stream_entry_is_listed():
-    H.check_entries_listed("vqcpc_optim.h", ENTRIES, __doc__)
 
 
 def _buffers(tag, v_floor):

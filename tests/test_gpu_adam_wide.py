@@ -107,7 +107,7 @@ def test_update_number_past_32_bits_reaches_the_scalars():
 
 # ------------------------------------------------------------------ d. non-finite and overflowing gradients
 def test_nonfinite_and_overflowing_gradients_follow_ieee_and_touch_no_neighbour():
-    """include/vqcpc_optim.h: g * g that overflows freezes the element's p (v' = inf, m' / d = 0), an infinite or NaN g makes it NaN,
+    """include/vqcpc.h: g * g that overflows freezes the element's p (v' = inf, m' / d = 0), an infinite or NaN g makes it NaN,
     no other element of the call is affected.  One special in the first vector, in the last element of chunk 0, in the first of
     chunk 1, three in the scalar tail.  NaN payloads are not compared."""
     name, C = "nonfinite", R.CHUNK

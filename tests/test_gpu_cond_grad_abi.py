@@ -1,4 +1,4 @@
-"""-m gpu: every ``VQCPC_ERR_INVALID`` condition of ``include/vqcpc_vocoder_cond_grad.h`` through raw ctypes: the call returns -1
+"""-m gpu: every ``VQCPC_ERR_INVALID`` condition of ``include/vqcpc.h`` through raw ctypes: the call returns -1
 with a message that names the condition, and nothing is enqueued -- the outputs keep the pattern they were filled with."""
 import ctypes
 

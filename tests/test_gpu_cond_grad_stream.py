@@ -1,22 +1,12 @@
-"""-m gpu: the entries of ``include/vqcpc_vocoder_cond_grad.h`` on a caller's stream -- the stream contract of ``include/vqcpc.h``
-(*all work is enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly as the entries of the first three
-headers are held.  This file keeps the table of the fourth header:
+"""-m gpu: ``vqcpc_vocoder_cond_fwd`` / ``_bwd`` and ``vqcpc_vocoder_ar_fwd_cond`` / ``_bwd_cond`` on a caller's stream -- the stream
+contract of ``include/vqcpc.h`` (*all work is enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly
+as tests/test_gpu_stream_contract.py holds the other entries.  That file keeps the one table of entries against the header; its
+rows name the tests here.
 
-  ==================================  ===  ====================================================================================
-  entry                               how  held by
-  ==================================  ===  ====================================================================================
-  vqcpc_vocoder_cond_fwd              N    test_cond_fwd_then_bwd_weights_in_stream_order
-  vqcpc_vocoder_cond_bwd              N    test_cond_bwd_alone
-  vqcpc_vocoder_ar_fwd_cond           N    test_ar_fwd_cond_then_bwd_cond
-  vqcpc_vocoder_ar_bwd_cond           N    test_ar_bwd_cond_alone
-  ==================================  ===  ====================================================================================
-
-N: does not synchronise (``busy`` is asserted).  A backward behind a forward of the same handle may wait for the staging arena of
+All four: does not synchronise (``busy`` is asserted).  A backward behind a forward of the same handle may wait for the staging arena of
 the forward's uploads, so each pair is probed after its first call and the backward is held on its own as well.  The eighteen
 tensors of the conditioning path are among the buffers written behind the delay: the per-call re-layout (the stacked w_ih / b_ih /
 b_hh and the W_hh fragments) must be made from what the stream holds when the call's turn comes.
-``test_every_stream_entry_is_listed`` reads the header with ``stream_harness.check_entries_listed`` and fails when an entry with a
-``stream`` argument is missing above.
 """
 
 import pytest
@@ -30,7 +20,6 @@ from vectorquantizedcpc_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-ENTRIES = {"vqcpc_vocoder_cond_fwd": "N", "vqcpc_vocoder_cond_bwd": "N", "vqcpc_vocoder_ar_fwd_cond": "N", "vqcpc_vocoder_ar_bwd_cond": "N"}
 CASE = "ragged"
 
 
@@ -39,10 +28,6 @@ def release_what_this_file_holds():
     """The cases, the references and the device buffers of this file are released when it is done, and the stream harness's
     session-wide delay chain and report are left as they were found (``stream_harness.release_after`` says why)."""
     yield from H.release_after()
-
-
-def test_every_stream_entry_is_listed():
-    H.check_entries_listed("vqcpc_vocoder_cond_grad.h", ENTRIES, __doc__)
 
 
 def cond_setup():

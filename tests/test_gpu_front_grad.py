@@ -1,4 +1,4 @@
-"""-m gpu: the front end's gradients (``csrc/front_grad.hip``, ``include/vqcpc_grad.h``) -- the forward's bits against
+"""-m gpu: the front end's gradients (``csrc/front_grad.hip``, ``include/vqcpc.h``) -- the forward's bits against
 ``vqcpc_encoder_stage``, the 17 gradients against float64 on the cases of tests/front_grad_ref.py, their repeatability on a dirty
 work space, partial requests, ``vqcpc_encoder_vq_bwd``, the autograd surface of ``Encoder.front_end`` / ``quantize``, the whole
 training step with ``CPCLoss``, the ABI's errors and ``cli fit-encoder``.

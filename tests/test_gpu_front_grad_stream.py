@@ -1,17 +1,7 @@
-"""-m gpu: the entries of ``include/vqcpc_grad.h`` on a caller's stream -- the stream contract of ``include/vqcpc.h`` (*all work is
-enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly as tests/test_gpu_stream_contract.py holds
-the entries of the first header.  That file's table is pinned to ``vqcpc.h``; this one keeps the table of the second header:
-
-  ==================================  ===  ====================================================================================
-  entry                               how  held by
-  ==================================  ===  ====================================================================================
-  vqcpc_encoder_front_fwd             N    test_front_fwd_bwd_weights_in_stream_order
-  vqcpc_encoder_front_bwd             N    test_front_fwd_bwd_weights_in_stream_order
-  vqcpc_encoder_vq_bwd                N    test_vq_bwd
-  ==================================  ===  ====================================================================================
-
-N: does not synchronise (``busy`` is asserted).  ``test_every_stream_entry_is_listed`` reads the header with
-``stream_harness.check_entries_listed`` and fails when an entry with a ``stream`` argument is missing above.
+"""-m gpu: the front-end and VQ gradient entries (``vqcpc_encoder_front_fwd`` / ``_bwd``, ``vqcpc_encoder_vq_bwd``) on a caller's
+stream -- the stream contract of ``include/vqcpc.h`` (*all work is enqueued on `stream`; no call synchronises*), held with
+tests/stream_harness.py exactly as tests/test_gpu_stream_contract.py holds the other entries.  That file keeps the one table of
+entries against the header; its rows name the tests here.  All three: does not synchronise (``busy`` is asserted).
 """
 
 import pytest
@@ -30,13 +20,6 @@ def release_what_this_file_holds():
     """The cases, the float64 references and the device buffers of this file are released when it is done, and the stream harness's
     session-wide delay chain and report are left as they were found (``stream_harness.release_after`` says why)."""
     yield from H.release_after(R._cases, R._fwd, R._refs)
-
-
-ENTRIES = {"vqcpc_encoder_front_fwd": "N", "vqcpc_encoder_front_bwd": "N", "vqcpc_encoder_vq_bwd": "N"}
-
-
-def test_every_stream_entry_is_listed():
-    H.check_entries_listed("vqcpc_grad.h", ENTRIES, __doc__)
 
 
 def encoder():

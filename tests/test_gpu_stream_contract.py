@@ -12,7 +12,8 @@ inputs.  One library call is in flight at a time; two streams are used only one 
 them (the header's "an event between" rule).
 
 Entries against the header.  N = held to "does not synchronise" (``busy`` asserted) and to ordering; O = ordering only (the header
-says the entry synchronises ``stream``); the tests that hold it:
+says the entry synchronises ``stream``); the tests that hold it, in this file unless the row names another (the gradient and
+optimizer entries are held, with the same harness, next to the cases they are run on):
 
   ==================================  ===  ====================================================================================
   vqcpc_encoder_encode                N    test_encoder_encode (fused 0, 1, 2)
@@ -23,6 +24,9 @@ says the entry synchronises ``stream``); the tests that hold it:
   vqcpc_encoder_context               N    test_encoder_context (1 x 300 resident scan, 17 x 33 one launch per step)
   vqcpc_encoder_context_fwd           N    test_context_fwd_bwd_weights_in_stream_order
   vqcpc_encoder_context_bwd           N    test_context_fwd_bwd_weights_in_stream_order
+  vqcpc_encoder_front_fwd             N    test_gpu_front_grad_stream.py::test_front_fwd_bwd_weights_in_stream_order
+  vqcpc_encoder_front_bwd             N    test_gpu_front_grad_stream.py::test_front_fwd_bwd_weights_in_stream_order
+  vqcpc_encoder_vq_bwd                N    test_gpu_front_grad_stream.py::test_vq_bwd
   vqcpc_cpc_score                     N    test_cpc_score (given and seeded negatives)
   vqcpc_cpc_grad                      N    test_cpc_grad (given / seeded negatives; W and bias written on s)
   vqcpc_abx_score                     N    test_abx_pair_distances
@@ -36,6 +40,12 @@ says the entry synchronises ``stream``); the tests that hold it:
   vqcpc_vocoder_stream_redo           O*   test_streaming
   vqcpc_vocoder_logits                N    test_logits
   vqcpc_vocoder_nll                   N    test_nll
+  vqcpc_vocoder_ar_fwd                N    test_gpu_voc_grad_stream.py::test_ar_fwd_then_bwd_weights_in_stream_order
+  vqcpc_vocoder_ar_bwd                N    test_gpu_voc_grad_stream.py::test_ar_bwd_alone
+  vqcpc_vocoder_ar_fwd_cond           N    test_gpu_cond_grad_stream.py::test_ar_fwd_cond_then_bwd_cond
+  vqcpc_vocoder_ar_bwd_cond           N    test_gpu_cond_grad_stream.py::test_ar_bwd_cond_alone
+  vqcpc_vocoder_cond_fwd              N    test_gpu_cond_grad_stream.py::test_cond_fwd_then_bwd_weights_in_stream_order
+  vqcpc_vocoder_cond_bwd              N    test_gpu_cond_grad_stream.py::test_cond_bwd_alone
   vqcpc_vocoder_glue                  N    test_glue_and_condition
   vqcpc_vocoder_condition             N    test_glue_and_condition
   vqcpc_vocoder_kernel_times          O    test_kernel_times_between_two_calls (must return with the stream idle)
@@ -43,6 +53,7 @@ says the entry synchronises ``stream``); the tests that hold it:
   vqcpc_resampler_run                 N    test_resampler (on a handle whose clock table is long enough, the header's condition)
   vqcpc_loudness_integrated           O    test_loudness
   vqcpc_loudness_normalize            O    test_loudness
+  vqcpc_adam_step                     N    test_gpu_adam_stream.py::test_adam_step_on_a_callers_stream
   ==================================  ===  ====================================================================================
 
   O*: a call on a vocoder handle waits on the host for the event behind the PREVIOUS call's uploads (the header says so), and
@@ -127,6 +138,9 @@ ENTRIES = {
     "vqcpc_vocoder_logits": "N", "vqcpc_vocoder_nll": "N", "vqcpc_vocoder_glue": "N", "vqcpc_vocoder_condition": "N",
     "vqcpc_vocoder_kernel_times": "O", "vqcpc_melfront_run": "O", "vqcpc_resampler_run": "N", "vqcpc_loudness_integrated": "O",
     "vqcpc_loudness_normalize": "O",
+    "vqcpc_encoder_front_fwd": "N", "vqcpc_encoder_front_bwd": "N", "vqcpc_encoder_vq_bwd": "N",
+    "vqcpc_vocoder_ar_fwd": "N", "vqcpc_vocoder_ar_bwd": "N", "vqcpc_vocoder_ar_fwd_cond": "N", "vqcpc_vocoder_ar_bwd_cond": "N",
+    "vqcpc_vocoder_cond_fwd": "N", "vqcpc_vocoder_cond_bwd": "N", "vqcpc_adam_step": "N",
 }
 
 
@@ -140,7 +154,7 @@ def ptr(t):
 
 # ---------------------------------------------------------------------------------------------------- the harness itself
 def test_every_stream_entry_is_listed():
-    assert len(H.check_entries_listed("vqcpc.h", ENTRIES, __doc__)) >= 20
+    assert len(H.check_entries_listed(ENTRIES, __doc__)) >= 36
 
 
 def test_harness_rejects_faulty_entries():

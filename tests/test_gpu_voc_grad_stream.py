@@ -1,18 +1,9 @@
-"""-m gpu: the entries of ``include/vqcpc_vocoder_grad.h`` on a caller's stream -- the stream contract of ``include/vqcpc.h`` (*all
-work is enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly as tests/test_gpu_stream_contract.py
-and tests/test_gpu_front_grad_stream.py hold the entries of the first two headers.  This file keeps the table of the third header:
+"""-m gpu: ``vqcpc_vocoder_ar_fwd`` / ``_bwd`` on a caller's stream -- the stream contract of ``include/vqcpc.h`` (*all work is
+enqueued on `stream`; no call synchronises*), held with tests/stream_harness.py exactly as tests/test_gpu_stream_contract.py holds
+the other entries.  That file keeps the one table of entries against the header; its rows name the tests here.
 
-  ==================================  ===  ====================================================================================
-  entry                               how  held by
-  ==================================  ===  ====================================================================================
-  vqcpc_vocoder_ar_fwd                N    test_ar_fwd_then_bwd_weights_in_stream_order
-  vqcpc_vocoder_ar_bwd                N    test_ar_bwd_alone
-  ==================================  ===  ====================================================================================
-
-N: does not synchronise (``busy`` is asserted).  A backward behind a forward of the same handle may wait for the staging arena of
+Both: does not synchronise (``busy`` is asserted).  A backward behind a forward of the same handle may wait for the staging arena of
 the forward's uploads, so the pair is probed after its first call and the backward is held on its own as well.
-``test_every_stream_entry_is_listed`` reads the header with ``stream_harness.check_entries_listed`` and fails when an entry with a
-``stream`` argument is missing above.
 """
 import pytest
 import torch
@@ -24,7 +15,6 @@ from vectorquantizedcpc_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-ENTRIES = {"vqcpc_vocoder_ar_fwd": "N", "vqcpc_vocoder_ar_bwd": "N"}
 CASE = "ragged"
 
 
@@ -33,10 +23,6 @@ def release_what_this_file_holds():
     """The cases, the references and the device buffers of this file are released when it is done, and the stream harness's
     session-wide delay chain and report are left as they were found (``stream_harness.release_after`` says why)."""
     yield from H.release_after(R._cases, R._refs)
-
-
-def test_every_stream_entry_is_listed():
-    H.check_entries_listed("vqcpc_vocoder_grad.h", ENTRIES, __doc__)
 
 
 def setup():

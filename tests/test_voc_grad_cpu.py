@@ -1,12 +1,7 @@
 """The vocoder gradients without a GPU: the float64 reference of tests/voc_grad_ref.py reproduces its pins and equals torch's own
-modules, the third header is exported, bound and plain C, the cases meet the conditions the GPU tests rely on, and the recorded
+modules, the ctypes struct names the module's tensors, the cases meet the conditions the GPU tests rely on, and the recorded
 float64 fit is a trend, not noise.  Past the twelve cases: the wide cases reproduce their pins, row pins included, hold the
 arithmetic their table claims, their fp32 CPU run passes both judges, and two seeded faults fail them."""
-import ctypes
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -14,8 +9,6 @@ import grad_judge
 import voc_fit_ref
 import voc_grad_ref as R
 from vectorquantizedcpc_amd import _lib, cli, driver
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("name", R.ALL_CASES)
@@ -167,54 +160,9 @@ def test_recorded_fit_is_a_trend():
     assert dec > 0 and dec >= 3.0 * spread
 
 
-# ------------------------------------------------------------------ the header
-def declared():
-    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_grad.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vqcpc_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    names = declared()
-    assert len(names) == 3
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/vqcpc_vocoder_grad.h but not exported"
-        assert getattr(_lib.load(), n).argtypes is not None, n
-    assert sorted(_lib.VOC_GRAD_SYMBOLS) == names
-    assert not set(_lib.VOC_GRAD_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.GRAD_SYMBOLS))
-    assert _lib.load().vqcpc_abi_version() == 1
-
-
-def test_header_is_plain_c(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('''#include "vqcpc_vocoder_grad.h"
-#include <stddef.h>
-int use(vqcpc_vocoder *voc, int64_t *i, float *p, double *d, void *saved, void *s) {
-    vqcpc_vocoder_ar_weights w;
-    vqcpc_vocoder_ar_grads g;
-    uint64_t n = 0;
-    int rc = vqcpc_vocoder_ar_saved_bytes(voc, 2, 321, &n);
-    w.embedding = p; w.w_ih = p; w.w_hh = p; w.b_ih = p; w.b_hh = p; w.fc1_weight = p; w.fc1_bias = p; w.fc2_weight = p; w.fc2_bias = p;
-    g = (vqcpc_vocoder_ar_grads){NULL, p, NULL, NULL, NULL, NULL, NULL, NULL, p};
-    rc |= vqcpc_vocoder_ar_fwd(voc, i, i, i, 2, 1, 321, NULL, NULL, &w, d, i, i, p, saved, s);
-    rc |= vqcpc_vocoder_ar_fwd(voc, i, i, i, 2, 1, 321, NULL, NULL, NULL, d, i, i, NULL, saved, s);
-    rc |= vqcpc_vocoder_ar_bwd(voc, i, i, i, 2, 1, 321, NULL, NULL, &w, saved, p, &g, p, s);
-    rc |= vqcpc_vocoder_ar_bwd(voc, i, i, i, 2, 1, 321, NULL, NULL, NULL, saved, NULL, NULL, p, s);
-    return rc;
-}
-''')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only",
-                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
+# ------------------------------------------------------------------ the struct and the module
 def test_ar_tensors_struct_mirrors_the_header():
-    text = open(os.path.join(ROOT, "include", "vqcpc_vocoder_grad.h")).read()
-    for kind in ("const float", "float"):
-        body = re.search(r"typedef struct \{([^}]*)\} vqcpc_vocoder_ar_%s;" % ("weights" if kind == "const float" else "grads"), text).group(1)
-        assert re.findall(r"\b%s \*(\w+);" % kind, body) == [n for n, _ in _lib.VocoderArTensors._fields_]
-    assert ctypes.sizeof(_lib.VocoderArTensors) == 9 * ctypes.sizeof(ctypes.c_void_p)
+    """``_lib.VocoderArTensors`` against the header: tests/test_abi_cpu.py.  Here: against the module and the reference."""
     import vectorquantizedcpc_amd as V
     assert tuple(n for n, _ in _lib.VocoderArTensors._fields_) == V.Vocoder.AR_KEYS == R.KEYS
     voc = V.Vocoder(V.ConfVocoder())

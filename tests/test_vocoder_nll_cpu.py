@@ -1,35 +1,17 @@
-"""Vocoder scoring without a GPU: the ABI of vqcpc_vocoder_nll, the `score-vocoder` command line, the driver's cut rule and
+"""Vocoder scoring without a GPU (the ABI of vqcpc_vocoder_nll: tests/test_abi_cpu.py): the `score-vocoder` command line, the driver's cut rule and
 bucket bookkeeping (stub models), the float64 helper against torch's cross_entropy, the mu-law path, and the conditions on the
 inputs of the GPU cases (tests/nll_ref.py): at most 1 % ambiguous samples, some surely correct ones.
 
-The tests of the ABI, the command line, the driver and the mu-law path need the feature and fail without it.  The float64 helper
+The tests of the command line, the driver and the mu-law path need the feature and fail without it.  The float64 helper
 test, the ambiguity-cap cases and the wave determinism test check the TEST inputs and helpers themselves (tests/nll_ref.py and
 oracle/f64_ref.py only): they hold with or without the feature, and are here so that a bad input is caught without a GPU."""
-import re
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import nll_ref
-from vectorquantizedcpc_amd import _lib, cli, driver, preprocess, synth
-
-ROOT = Path(__file__).resolve().parents[1]
-
-
-def test_header_symbols_and_argtypes_agree():
-    header = (ROOT / "include" / "vqcpc.h").read_text()
-    m = re.search(r"int vqcpc_vocoder_nll\(([^;]*)\);", header)
-    assert m, "vqcpc_vocoder_nll is not declared in include/vqcpc.h"
-    n_params = len([p for p in m.group(1).split(",") if p.strip()])
-    assert n_params == 14
-    assert "vqcpc_vocoder_nll" in _lib.SYMBOLS
-    lib = _lib.load()
-    assert len(lib.vqcpc_vocoder_nll.argtypes) == n_params
-    src = (ROOT / "vectorquantizedcpc_amd" / "csrc" / "Makefile").read_text()
-    assert "nll.o" in src
+from vectorquantizedcpc_amd import cli, driver, preprocess, synth
 
 
 def test_cli_score_vocoder_parses_and_rejects_a_missing_checkpoint(capsys):

@@ -318,7 +318,7 @@ extern "C" int vqcpc_encoder_context_bwd(vqcpc_encoder *e, const float *z, int B
     return vq_ctx_bwd(e->ctx, w, z, B, Tz, c, (const float *)saved, grad_c, grad_z, grad_w_ih, grad_w_hh, grad_bias, (hipStream_t)stream);
 }
 
-// ---- include/vqcpc_grad.h: the front end of a training step, its backward and the VQ step's backward (front_grad.hip)
+// ---- include/vqcpc.h: the front end of a training step, its backward and the VQ step's backward (front_grad.hip)
 // The checks vqcpc_encoder_front_fwd / _bwd share; nothing is enqueued before they pass.
 static int front_grad_begin(vqcpc_encoder *e, const char *what, const float *mel, int B, int T, int conv_mode,
                             const vqcpc_encoder_front_weights *w, FrontW &fw) {

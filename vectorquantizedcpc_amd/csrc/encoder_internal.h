@@ -1,7 +1,6 @@
 // What the encoder's kernels (encoder.hip), its handle (encoder_host.hip) and the exact-chain GEMM (gemm_chain.hip) share.
 #pragma once
 #include "common.h"
-#include "../../include/vqcpc_grad.h"
 
 // ------------------------------------------------------------------------------------------
 // im2col of Conv1d(k = 4, stride 2, padding 1) over mel (B, C, T) (model.py:43, :65): GEMM row m = b * To + tt, column kidx.
@@ -78,7 +77,7 @@ struct EmaP {
 void launch_ema_update(const EmaP &p, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
-// front_grad.hip: the front end of a training step and its backward (include/vqcpc_grad.h)
+// front_grad.hip: the front end of a training step and its backward (include/vqcpc.h)
 // ------------------------------------------------------------------------------------------
 // The front end's weights as the kernels read them: the handle's copies (built once at create), or a caller's tensors.
 struct FrontW {
@@ -114,7 +113,7 @@ struct FrontGradWork {
     size_t bytes() const { return convw.cap + wT.cap + d0.cap + d1.cap + part.cap + colpart.cap; }
 };
 size_t vq_front_saved_bytes(int B, int To);
-// C = in_channels, conv_mode 1 or 2 (resolved).  z_pre (R, 64) and `saved` as vqcpc_grad.h says.
+// C = in_channels, conv_mode 1 or 2 (resolved).  z_pre (R, 64) and `saved` as vqcpc.h says.
 int vq_front_fwd(FrontGradWork &k, FrontW w, const LnConst &lnc, const float *mel, int B, int C, int T, int conv_mode, float *z_pre,
                  float *saved, hipStream_t s);
 int vq_front_bwd(FrontGradWork &k, const FrontW &w, const float *mel, int B, int C, int T, const float *saved, const float *grad_z_pre,

@@ -1,6 +1,6 @@
 // Gradients of the encoder's front end, Encoder.conv + Encoder.encoder (model.py:43-55, :65-67), and of the VQ step's
 // straight-through estimator (model.py:147-150): a forward that keeps what the backward reads again, and the backward -- what
-// loss.backward() does below z in train_cpc.py:116-124.  Entry points: include/vqcpc_grad.h (encoder_host.hip).
+// loss.backward() does below z in train_cpc.py:116-124.  Entry points: include/vqcpc.h (encoder_host.hip).
 // B utterances of T mel frames, To = T / 2 output frames, rows r = b To + tt, R = B To; C = in_channels; layers l = 0 .. 4:
 //   x_0 = conv(mel), a_l = ReLU(LN_l(x_l)), x_{l+1} = a_l W_l^T (l < 4), z_pre = a_4 W_out^T + b_out.
 // Every sum has ONE order, fixed by the code and independent of the grid's timing: no floating-point read-modify-write on global
@@ -35,7 +35,7 @@
 //     the tile's partial.  Rows >= R of the last tile are skipped: they contribute nothing.  front_ln_slab_kernel: per column
 //     and slab, the slab's 64 tiles t go to four accumulators (t mod 4), t ascending, combined (a0 + a1) + (a2 + a3);
 //     front_sum_parts_kernel adds the slab sums in slab order.
-//   vq_bwd_kernel: the element-wise statements vqcpc_grad.h gives.
+//   vq_bwd_kernel: the element-wise statements vqcpc.h gives.
 //
 // Dirt: every partial that a finish kernel reads was written by the same call (the grids cover exactly the tiles and slabs
 // below R); the (R, 512) buffers are written for every row below R before they are read.  Nothing is zero-filled.

@@ -1,9 +1,8 @@
 // optim.h -- what optim.hip (the kernel and the C entry) and optim_plan.hip (the host arithmetic of the entry) share.
 #pragma once
 #include "common.h"
-#include "../../include/vqcpc_optim.h"
 
-// The six fp32 scalars of one update, formed in double and rounded once each (include/vqcpc_optim.h states them).
+// The six fp32 scalars of one update, formed in double and rounded once each (include/vqcpc.h states them).
 struct AdamScalars { float w1, c2, w2, rb, e, ss; };
 
 // One launch's table, passed BY VALUE as a kernel argument: per tensor the four pointers, numel and a chunk prefix.  Tensor i

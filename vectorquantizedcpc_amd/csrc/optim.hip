@@ -1,4 +1,4 @@
-// optim.hip -- vqcpc_adam_step (include/vqcpc_optim.h): one Adam update of a list of tensors in one launch per
+// optim.hip -- vqcpc_adam_step (include/vqcpc.h): one Adam update of a list of tensors in one launch per
 // VQCPC_ADAM_TABLE tensors.  The table of a launch -- four pointers, numel and a chunk prefix per tensor -- is a kernel argument
 // passed by value: nothing is allocated and nothing is copied to the device.  The host arithmetic is optim_plan.hip's.
 //

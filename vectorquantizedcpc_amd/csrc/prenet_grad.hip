@@ -1,6 +1,6 @@
 // Gradients of the vocoder's conditioning path (network_vocoder.py:73-77 and rnnms.prenet): code_embedding, speaker_embedding, the
 // repeat of every code over two frames, and the two bidirectional GRU layers -- vqcpc_vocoder_cond_fwd / _bwd of
-// include/vqcpc_vocoder_cond_grad.h (K16).  B utterances, utterance b has len[b] = 2 n_codes[b] frames at rows row0[b] .. of every
+// include/vqcpc.h (K16).  B utterances, utterance b has len[b] = 2 n_codes[b] frames at rows row0[b] .. of every
 // buffer below (run_condition's layout), R rows in all.  dz, ds: the embedding widths, F = dz + ds, Hp = dim_voc_latent / 2.
 // Layer l reads X (R, I), I = F (l = 0, the glued series) or 2Hp (l = 1, layer 0's output), and writes Hout (R, 2Hp) = [forward |
 // reverse].  Gate order r, z, n; h = (1 - z) n + z h_prev.  The forward direction's step s is frame s, the reverse direction's is
@@ -52,7 +52,6 @@
 #include "vocoder_internal.h"
 #include "bptt_step.h"
 #include "grad_slab.h"
-#include "../../include/vqcpc_vocoder_cond_grad.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 // Gradients of the vocoder objective (vocoder.py:62-63: F.cross_entropy of the teacher-forced energies of audio[:, :-1] against
 // audio[:, 1:]) through the sample-rate network rnnms.ar.* -- embedding, GRU, fc1, fc2 -- and with respect to the conditioning
-// series: vqcpc_vocoder_ar_fwd / _bwd of include/vqcpc_vocoder_grad.h, and their *_cond forms of include/vqcpc_vocoder_cond_grad.h, which
+// series: vqcpc_vocoder_ar_fwd / _bwd of include/vqcpc.h, and their *_cond forms, which
 // take the conditioning series from the caller instead of running the prenet.  The prenet and the two tables in front of it are frozen
 // here; their backward is prenet_grad.hip, fed by grad_cond.
 // B utterances, Hr = size_h_rnn, Hf = n_cls = 256, de = size_i_embed_ar, C = dim_voc_latent, up = upsampling_t.  Utterance b scores
@@ -57,7 +57,6 @@
 #include "vocoder_internal.h"
 #include "bptt_step.h"
 #include "grad_slab.h"
-#include "../../include/vqcpc_vocoder_cond_grad.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 """The optimizer step in HIP, and the reference's learning-rate schedule.
 
-``Adam`` is ``torch.optim.Adam`` with ``step()`` replaced by ``vqcpc_adam_step`` (``include/vqcpc_optim.h``): one launch over all
+``Adam`` is ``torch.optim.Adam`` with ``step()`` replaced by ``vqcpc_adam_step`` (``include/vqcpc.h``): one launch over all
 tensors of a param group, in the one order of fp32 operations the header states.  Everything else -- ``state_dict()``,
 ``load_state_dict()``, ``param_groups``, ``state[p]`` (``step``, ``exp_avg``, ``exp_avg_sq``), ``zero_grad`` -- is torch's own, so a
 state dict moves between the two optimizers in both directions, the ``"optimizer"`` entry of a reference checkpoint
